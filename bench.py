@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — all-pairs genetic-distance throughput on MI355X (BASELINE.json metric).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3raw|C3|C2|C5|C4]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3raw|C3|C2|C5|C4] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the hot path over the whole synthetic alignment, starting from the row-major
@@ -9,13 +9,17 @@ N x L Paradis byte matrix resident in HBM: bit-plane pack -> (difference lists) 
 distances in canonical order in HBM.  N>1: every rank computes a contiguous range of the canonical order into its own
 HBM (--exchange gather: and sends it straight to rank 0 over RCCL).
 Prints ONE JSON line (rank 0).  `value` = pairs of the whole job / step time, on the library's default
-path choice (DST_PATH_AUTO); the line also carries, each timed over the same steps/warmup:
+path choice (DST_PATH_AUTO); `ms_per_step` = the wall time of one of the --steps timed steps.
+A plain run does only that: set up, warm up, time the steps, print.  With --full the line also carries, each timed
+over the same steps/warmup:
   legs.dense      the same measure with the dense bit-plane kernels forced (VALU-issue roofline),
   legs.tn93*      the C3 measure (the metric is "raw+tn93"), default path and dense,
   legs.clades / legs.nruns   (N = 1) the same shape with phylogenetic structure (a third of the records share 2 % of the
                   sites) and with 5 % of the records half N: the consensus path's time depends on the data,
-  verify          ALWAYS: the default leg's results against the dense leg's bit for bit, rows against the oracle,
+  verify          the default leg's results against the dense leg's bit for bit, rows against the oracle,
   cpu_baseline(s) the oracle on the host cores for raw / tn93 / n_high / n (sparse walk) and the C1 line.
+--dump-outputs DIR (one GPU): after the timed steps, what the last one computed as DIR/<name>.npy (float64); a
+triangle of more than 2^22 results is written as a fixed, seeded sample of 2^21 of them (see dump_outputs()).
 `python bench.py --gpus N` without a launcher starts its N ranks itself (torch.distributed.run as a child process,
 before this process touches a GPU).  N > 1: the preparation of the set is shared out over the ranks (dst_upload_shared:
 every rank packs and lists 1/N of the records, one RCCL all-gather of the lists), every rank computes a contiguous row
@@ -174,6 +178,32 @@ def measured_traffic(name: str, kernel: str):
     return best
 
 
+DUMP_WHOLE_MAX = 1 << 22     # results written whole up to this count (32 MB of f64) ...
+DUMP_SAMPLE = 1 << 21        # ... above it, this many draws (16 MB of values + 16 MB of their indices)
+DUMP_SEED = 0xD0E5
+
+
+def dump_outputs(out_dir: str, out: torch.Tensor) -> dict:
+    """What the caller receives from the timed path — `out`, the results in canonical pair order (C4: one block per
+    batch) — as DIR/distances.npy (float64; n / n_high counts are exact in it).  Above DUMP_WHOLE_MAX results: the
+    results at DUMP_SAMPLE canonical pair indices drawn with a fixed seed (sorted, duplicates dropped), the same for
+    every run of the same shape, with the indices themselves in DIR/pair_index.npy (float64, exact below 2^53): that
+    file says which pairs were sampled, it is not a computed output.  Returns what was written, for the result line."""
+    os.makedirs(out_dir, exist_ok=True)
+    total = out.numel()
+    if total <= DUMP_WHOLE_MAX:
+        files = {"distances.npy": f"all {total} results, float64"}
+        values = out.to(torch.float64).cpu().numpy()
+    else:
+        idx = np.unique(np.random.default_rng(DUMP_SEED).integers(0, total, DUMP_SAMPLE, dtype=np.int64))
+        files = {"distances.npy": f"{len(idx)} of the {total} results, at pair indices drawn with seed {DUMP_SEED:#x}, float64"}
+        values = out.reshape(-1).index_select(0, torch.from_numpy(idx).to(out.device)).to(torch.float64).cpu().numpy()
+        np.save(os.path.join(out_dir, "pair_index.npy"), idx.astype(np.float64))
+        files["pair_index.npy"] = "metadata, not a computed output: the canonical pair index of each sampled result (float64)"
+    np.save(os.path.join(out_dir, "distances.npy"), values)
+    return {"dir": out_dir, "files": files}
+
+
 # ------------------------------------------------------------------------------------------------
 def main():
     ap = argparse.ArgumentParser()
@@ -191,23 +221,31 @@ def main():
                          "it (one D2H stream per GPU) - no collective in the data path; 'gather': every slab is sent to "
                          "rank 0 over RCCL send/recv (the north-star's exchange step, xGMI-ingest-bound)")
     ap.add_argument("--chunks", type=int, default=8, help="N>1 gather: sub-slabs per rank (send k overlaps compute k+1)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the extra timed legs (dense path, tn93)")
+    ap.add_argument("--full", action="store_true",
+                    help="also the extra timed legs, the verification against the dense path / the oracle and the CPU "
+                         "baselines (a plain run times the main leg only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="one GPU: write what the last timed step computed to DIR/<name>.npy (float64)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true", help="--full: skip the extra timed legs (dense path, tn93)")
     ap.add_argument("--seed", type=lambda s: int(s, 0), default=synth.SEED)
     ap.add_argument("--rehearse-gloo", action="store_true",
                     help="debug: N ranks share GPU 0 and exchange over gloo via host staging (checks the "
                          "multi-rank indexing on a 1-GPU box; RCCL itself needs one GPU per rank)")
-    ap.add_argument("--verify", action="store_true", help="(kept for old command lines: verification is always on)")
+    ap.add_argument("--verify", action="store_true", help="(kept for old command lines, which ran everything: = --full)")
     ap.add_argument("--wire-f64", action="store_true", help="N>1: always send 8-byte results, never uint16 tallies")
     ap.add_argument("--batch", type=int, default=64, help="C4: streamed records per batch")
     ap.add_argument("--batches", type=int, default=8, help="C4: streamed batches per step")
     args = ap.parse_args()
+    args.full = args.full or args.verify
 
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
     if world != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}")
+    if args.dump_outputs and world > 1:
+        raise SystemExit("--dump-outputs: one GPU only (with N > 1 the results are spread over the ranks' HBM)")
     flags = da.load().dst_build_flags().decode()
     if flags:
         raise SystemExit(f"libdistance_hip.so is a measurement build ({flags}): bench.py times production builds only")
@@ -224,7 +262,8 @@ def main():
             dist.init_process_group("nccl", device_id=dev)
     if args.workload == "C4":
         from tools.bench_c4 import bench_c4
-        return bench_c4(args, rank, world, dev, dev_index)
+        return bench_c4(args, rank, world, dev, dev_index,
+                        dump=(lambda out: dump_outputs(args.dump_outputs, out)) if args.dump_outputs else None)
 
     n, L, measure, config_id = WORKLOADS[args.workload]
     n = args.n or n
@@ -242,7 +281,7 @@ def main():
     host_codes = synth.alignment(args.seed ^ config_id, n, L, threads=host_threads())   # every rank: the full set
     codes = torch.from_numpy(host_codes).to(dev)
     host_codes_full = host_codes            # rank 0's oracle rows read it (all ranks generate the same set)
-    if rank != 0 or args.no_cpu_baseline:
+    if rank != 0 or args.no_cpu_baseline or not args.full:
         host_codes = host_codes[:1]
     eng = da.Engine(dev_index)
     eng.set_variant(args.variant)
@@ -397,12 +436,15 @@ def main():
                              "views), and sampled rows against the oracle (restated reference algorithm with libm)"}
         sample_rows = sorted({r for r in (0, n // 2, n - 2) if 0 <= r < n - 1})
         main_leg = single_gpu_leg(measure, args.path, full_out)
-        if main_leg["path_used"] != "dense":
-            verify["default_vs_dense_bits_equal"] = bits_equal_dense(full_out, measure, codes)
-        verify["oracle_" + measure] = oracle_rows(full_out, measure, host_codes_full, sample_rows)
-        if not args.no_extra and main_leg["path_used"] != "dense":
+        # before the legs below reuse full_out
+        dumped = dump_outputs(args.dump_outputs, full_out[:total_pairs]) if args.dump_outputs else None
+        if args.full:
+            if main_leg["path_used"] != "dense":
+                verify["default_vs_dense_bits_equal"] = bits_equal_dense(full_out, measure, codes)
+            verify["oracle_" + measure] = oracle_rows(full_out, measure, host_codes_full, sample_rows)
+        if args.full and not args.no_extra and main_leg["path_used"] != "dense":
             legs["dense"] = single_gpu_leg(measure, "dense", full_out)
-        if not args.no_extra:
+        if args.full and not args.no_extra:
             if stock and args.workload == "C3raw":
                 legs["tn93"] = single_gpu_leg("tn93", args.path, full_out)
                 verify["oracle_tn93"] = oracle_rows(full_out, "tn93", host_codes_full, sample_rows[:2])
@@ -459,10 +501,13 @@ def main():
             "whole_step": main_leg["whole_step"],
             "kernels_ms": main_leg["kernels_ms"],
             "site_compares_per_s": main_leg["pairs_per_s"] * L,
-            "legs": legs,
-            "verify": verify,
         }
-        if not args.no_cpu_baseline:
+        if dumped:
+            result["dump_outputs"] = dumped
+        if args.full:
+            result["legs"] = legs
+            result["verify"] = verify
+        if args.full and not args.no_cpu_baseline:
             base, others = cpu_baselines(host_codes[:min(n, 8000)], measure)
             result["cpu_baseline"] = base
             result["cpu_baselines"] = others
@@ -520,7 +565,7 @@ def main():
             elapsed = float(t.item())
             used = eng.last_path()
             # every rank checks rows of ITS slab against a fresh single-engine dense run; the counts meet on rank 0
-            rows = sorted({r for r in (r0, (r0 + r1) // 2, r1 - 1) if r0 <= r < min(r1, n - 1)})
+            rows = sorted({r for r in (r0, (r0 + r1) // 2, r1 - 1) if r0 <= r < min(r1, n - 1)}) if args.full else []
             check = verify_rows(eng, codes, local_out, n, L, m, rows, dev_index, stream, first_row=r0) if rows else \
                 {"rows_checked": 0, "rows_bad": 0}
             v = torch.tensor([check["rows_checked"], check["rows_bad"]], dtype=torch.int64, device=cpu_or_dev)
@@ -543,10 +588,10 @@ def main():
         main_leg = multi_leg(measure, args.path)
         legs = {}
         oracle_check = None
-        if rank == 0 and r1 > r0:
+        if args.full and rank == 0 and r1 > r0:
             # rank 0's slab starts at row 0: its first rows against the oracle
             oracle_check = oracle_rows(local_out, measure, host_codes_full, [0, min(r1 - 1, n - 2)])
-        if not args.no_extra:
+        if args.full and not args.no_extra:
             if main_leg["path_used"] != "dense":
                 legs["dense"] = multi_leg(measure, "dense")
             if stock and args.workload == "C3raw":
@@ -582,9 +627,10 @@ def main():
                 "kernels_ms": main_leg["kernels_ms"],
                 "preparation": main_leg["preparation"],
                 "site_compares_per_s": main_leg["pairs_per_s"] * L,
-                "legs": legs,
-                "verify": dict(main_leg["verify"], oracle=oracle_check),
             }
+            if args.full:
+                result["legs"] = legs
+                result["verify"] = dict(main_leg["verify"], oracle=oracle_check)
             print(json.dumps(result))
         assert bad_rows == 0, "a rank's slab differs from a single-engine dense run"
         assert oracle_check is None or oracle_check["rows_bad"] == 0, "rank 0's rows differ from the oracle"
@@ -765,8 +811,9 @@ def main():
             "roofline": roofline(measure, used, k_ms, launch_pairs),
             "site_compares_per_s": total_pairs / (elapsed / args.steps) * L,
         }
-        probe_rows = sorted(set([0, 1, n // 3, n // 2, n - 2] + [b for b in bounds[1:-1]] + [b - 1 for b in bounds[1:-1]]))
-        result["verify"] = verify_rows(eng, codes, full_out, n, L, measure, probe_rows, dev_index, stream)
+        if args.full:
+            probe_rows = sorted(set([0, 1, n // 3, n // 2, n - 2] + [b for b in bounds[1:-1]] + [b - 1 for b in bounds[1:-1]]))
+            result["verify"] = verify_rows(eng, codes, full_out, n, L, measure, probe_rows, dev_index, stream)
         print(json.dumps(result))
     dist.barrier()
     dist.destroy_process_group()

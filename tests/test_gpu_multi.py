@@ -16,7 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def run_ranks(world, port, extra):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={world}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(world), "--steps", "2", "--warmup", "1",
-           "--rehearse-gloo", "--no-cpu-baseline"] + extra
+           "--rehearse-gloo", "--full", "--no-cpu-baseline"] + extra
     r = subprocess.run(cmd, capture_output=True, timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr.decode()[-3000:]
     line = [l for l in r.stdout.decode().splitlines() if l.startswith("{")][-1]

@@ -2,7 +2,7 @@
 streamed batches, -m n_high.  The 100,000-record stream (500 GB encoded) is never materialised: a step is a fixed
 number of batches synthesised in page-locked host memory by SURVEY 8(d)'s generator before the timed region.
 
-Two figures:
+Two figures, the second with --full only:
   value / device_resident   batches already in HBM: pack + compare per batch (inputs resident when timing starts)
   h2d_inclusive             the same batches from page-locked host memory through the overlapped pipeline
                             (dst_stream_*: H2D of batch k+1 and D2H of batch k-1 under the compare of batch k), for both
@@ -27,7 +27,7 @@ import distance_amd as da
 from tools import synth
 
 
-def bench_c4(args, rank, world, dev, dev_index):
+def bench_c4(args, rank, world, dev, dev_index, dump=None):
     n_loaded = args.n or 1000
     L = args.len or 5_000_000
     measure = args.measure or "n_high"
@@ -49,7 +49,8 @@ def bench_c4(args, rank, world, dev, dev_index):
     for k, g in enumerate(mine):
         synth.records(seed, root, n_loaded + g * B, B, threads=threads, out=host[k].numpy())
     resident = host.to(dev, non_blocking=False)
-    out = torch.empty((B, n_loaded), dtype=torch.int64 if measure in da.INT_MEASURES else torch.float64, device=dev)
+    # one result block per batch of a step, as a caller keeps them
+    out = torch.empty((len(mine), B, n_loaded), dtype=torch.int64 if measure in da.INT_MEASURES else torch.float64, device=dev)
     pairs_per_step = nb * world * B * n_loaded
 
     def fence():
@@ -61,7 +62,7 @@ def bench_c4(args, rank, world, dev, dev_index):
     def step_resident():
         for k in range(len(mine)):
             eng.upload_device(1, resident[k].data_ptr(), B, L, L, None, stream.cuda_stream)
-            eng.run_rect_device(measure, 1, 0, 0, B, out.data_ptr(), out.numel() * width, stream=stream.cuda_stream)
+            eng.run_rect_device(measure, 1, 0, 0, B, out[k].data_ptr(), out[k].numel() * width, stream=stream.cuda_stream)
 
     for _ in range(args.warmup):
         step_resident()
@@ -74,6 +75,7 @@ def bench_c4(args, rank, world, dev, dev_index):
     fence()
     el_res = time.perf_counter() - t0
     used = eng.last_path()
+    dumped = dump(out) if dump is not None else None
 
     # ---- H2D-inclusive: the overlapped pipeline from page-locked memory ----------------------------
     def step_stream(st, data, copy):
@@ -89,7 +91,7 @@ def bench_c4(args, rank, world, dev, dev_index):
 
     h2d = {}
     host_nib = None
-    for wire in ("codes", "nibbles"):
+    for wire in ("codes", "nibbles") if args.full else ():
         if wire == "nibbles":
             host_nib = [da.engine.Stream.to_nibbles(host[k].numpy()) for k in range(len(mine))]
         data = [host[k].numpy() for k in range(len(mine))] if wire == "codes" else host_nib
@@ -105,7 +107,6 @@ def bench_c4(args, rank, world, dev, dev_index):
                 fence()
                 el = time.perf_counter() - t0
             h2d[(wire, copy)] = el
-    el_h2d = h2d[("codes", False)]
 
     def maxed(x):
         if world == 1:
@@ -114,7 +115,7 @@ def bench_c4(args, rank, world, dev, dev_index):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         return float(t.item())
 
-    el_res, el_h2d = maxed(el_res), maxed(el_h2d)
+    el_res = maxed(el_res)
     h2d = {k: maxed(v) for k, v in h2d.items()}
     if rank == 0:
         ms = 1e3 * el_res / args.steps
@@ -142,7 +143,16 @@ def bench_c4(args, rank, world, dev, dev_index):
                        "generator": f"tools/synth (SURVEY 8(d)): xoshiro256**, seed {args.seed:#x} ^ 4"},
             "device_resident": {"pairs_per_s": pairs_per_step / (el_res / args.steps), "ms_per_step": ms,
                                 "note": "batches in HBM when timing starts: pack + split-L pair kernel per batch"},
-            "h2d_inclusive": {
+            "roofline": {"bound": "valu", "achieved": lane_ops / 1e12, "peak": 256 * 4 * 32 * 2.4e9 / 1e12,
+                         "unit": "Tlane-op/s", "frac": lane_ops / (256 * 4 * 32 * 2.4e9), "kernel": "pair_kernel (split-L)",
+                         "kernel_ms": kernel_ms, "traffic": None,
+                         "note": "dense n_high: 5 VALU ops per 32 sites per pair; one launch = one batch"},
+            "site_compares_per_s": pairs_per_step / (el_res / args.steps) * L,
+        }
+        if dumped:
+            result["dump_outputs"] = dumped
+        if args.full:
+            result["h2d_inclusive"] = {
                 **{f"{wire}{'_with_host_copy' if copy else ''}": {
                     "pairs_per_s": pairs_per_step / (h2d[(wire, copy)] / args.steps),
                     "ms_per_step": 1e3 * h2d[(wire, copy)] / args.steps,
@@ -151,13 +161,7 @@ def bench_c4(args, rank, world, dev, dev_index):
                 "note": "page-locked host batches through dst_stream_* (depth 3): H2D, pack, compare, D2H overlapped; never "
                         "reported as `value`.  codes: Paradis bytes; nibbles: DST_WIRE_NIBBLES (half the bytes).  "
                         "*_with_host_copy adds a one-thread memcpy of every batch into its ring slot, the stand-in for a parser "
-                        "that does not write into the slot directly"},
-            "roofline": {"bound": "valu", "achieved": lane_ops / 1e12, "peak": 256 * 4 * 32 * 2.4e9 / 1e12,
-                         "unit": "Tlane-op/s", "frac": lane_ops / (256 * 4 * 32 * 2.4e9), "kernel": "pair_kernel (split-L)",
-                         "kernel_ms": kernel_ms, "traffic": None,
-                         "note": "dense n_high: 5 VALU ops per 32 sites per pair; one launch = one batch"},
-            "site_compares_per_s": pairs_per_step / (el_res / args.steps) * L,
-        }
+                        "that does not write into the slot directly"}
         print(json.dumps(result))
     if world > 1:
         dist.barrier()

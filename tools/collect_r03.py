@@ -13,13 +13,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "profiles", "r03")
 HEADS = {
     "prof_r03": ("summary.txt",
-                 "# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --no-extra   (tools/profile_r03.sh)",
+                 "# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --no-extra   (tools/profile_r03.sh)",
                  "# (default workload 50,000 x 30,000 raw on the default path; the two pair_kernel<MRaw> launches are the verify pass: dense slabs, untimed)"),
     "prof_r03_tn93": ("summary_tn93.txt",
-                      "# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline --workload C3 --no-extra   (tools/profile_r03.sh)",
+                      "# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline --workload C3 --no-extra   (tools/profile_r03.sh)",
                       "# (50,000 x 30,000 tn93 on the default path; the two pair_kernel<MTN93> launches are the verify pass: dense slabs, untimed)"),
     "prof_r03_full": ("summary_all_legs.txt",
-                      "# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline   (tools/profile_r03.sh)",
+                      "# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline   (tools/profile_r03.sh)",
                       "# (every leg of the default run: raw auto, dense, tn93 auto, tn93 dense, clades (hybrid), nruns (run records); kernels of one "
                       "name are averaged over the legs that use them)"),
 }

@@ -30,7 +30,7 @@ def short(name):
 lines = []
 for path in glob.glob(os.path.join(src, "trace", "*", "*_kernel_stats.csv")):
     rows = list(csv.DictReader(open(path)))
-    lines.append("# rocprofv3 --kernel-trace --stats -- python3 bench.py --steps 5 --warmup 2 --no-cpu-baseline")
+    lines.append("# rocprofv3 --kernel-trace --stats -- python3 bench.py --full --steps 5 --warmup 2 --no-cpu-baseline")
     lines.append("# (default workload 50,000 x 30,000: main leg raw/auto, then legs dense raw, tn93 auto, tn93 dense, clades, nruns; the verify passes' dense slabs included)")
     lines.append(f"{'kernel':62s} {'calls':>6s} {'total_ms':>11s} {'avg_ms':>11s} {'min_ms':>11s} {'max_ms':>11s}")
     for r in rows:

@@ -11,7 +11,7 @@ cd /tmp && export TMPDIR=/tmp
 run_set() {   # name, bench arguments
   local OUT=$REPO/gpurun_out/$1; shift
   rm -rf "$OUT"; mkdir -p "$OUT"
-  local BENCH="python3 $REPO/bench.py --steps 5 --warmup 2 --no-cpu-baseline $*"
+  local BENCH="python3 $REPO/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline $*"
   rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- $BENCH > "$OUT/trace_bench.json" 2> "$OUT/trace.err"; echo "$OUT trace rc=$?"
   for C in FETCH_SIZE WRITE_SIZE; do
     rocprofv3 --kernel-trace --pmc $C --output-format csv -d "$OUT/pmc_$C" -- $BENCH > "$OUT/pmc_${C}_bench.json" 2> "$OUT/pmc_$C.err"; echo "pmc $C rc=$?"
@@ -21,5 +21,5 @@ run_set() {   # name, bench arguments
 run_set prof_r03 --no-extra
 run_set prof_r03_tn93 --workload C3 --no-extra
 OUT=$REPO/gpurun_out/prof_r03_full; rm -rf "$OUT"; mkdir -p "$OUT"
-rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $REPO/bench.py --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/trace_bench.json" 2> "$OUT/trace.err"; echo "full trace rc=$?"
+rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/trace" -- python3 $REPO/bench.py --full --steps 5 --warmup 2 --no-cpu-baseline > "$OUT/trace_bench.json" 2> "$OUT/trace.err"; echo "full trace rc=$?"
 du -sh $REPO/gpurun_out/prof_r03*
