@@ -7,7 +7,8 @@
 // (src/lib.rs:612-644).  The pair generators and worker pools (src/lib.rs:269-474, 502-596) are
 // replaced by libdistance_hip.so through its C ABI; -t sizes the host formatting pool and -b is
 // accepted — neither changes the output, as in the reference (src/lib.rs:919-1154).
-// Extra flags: --gpus N (default 1) / --devices LIST, --slab-pairs P (result slab size).
+// Extra flags: --gpus N (default 1) / --devices LIST, --slab-pairs P (result slab size), --nearest K (the K nearest records
+// of every record instead of every pair: dst_nearest).
 //
 // Exactness: the GPU returns integer site tallies; f64 finalisation is dst_finalize() on the host
 // (reference operation order, glibc log/sqrt), so the printed digits do not depend on the device.
@@ -100,6 +101,8 @@ void print_help()
         "  -l, --licenses               Print licence information and exit\n"
         "      --gpus <n>               MI355X GPUs to use (default 1)\n"
         "      --devices <list>         Explicit device ordinals, e.g. 0,1,2,3 (overrides --gpus)\n"
+        "      --nearest <k>            Print only the k (1-256) nearest records of every record: of the same file with one "
+        "input, of the second file with two. One GPU, no --stream\n"
         "  -h, --help                   Print help\n"
         "  -V, --version                Print version");
 }
@@ -114,6 +117,8 @@ struct Args {
     int gpus = 1;
     std::vector<int> devices;  // explicit device ordinals (--devices 0,1,..); empty: 0..gpus-1
     size_t slab_pairs = (size_t)1 << 22;  // result slab: 4 Mi pairs pipelines GPU, formatters and writer well
+    size_t nearest = 0;                   // --nearest k (0: every pair)
+    bool has_nearest = false;
     std::string selftest;
 };
 
@@ -196,6 +201,12 @@ Args parse_args(int argc, char **argv)
             }
         } else if (arg == "--slab-pairs" || arg.rfind("--slab-pairs=", 0) == 0) {
             a.slab_pairs = std::max<size_t>(1, parse_usize(value_of(k, arg, "--slab-pairs <p>"), "--slab-pairs <p>"));
+        } else if (arg == "--nearest" || arg.rfind("--nearest=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--nearest <k>");
+            a.nearest = parse_usize(v, "--nearest <k>");
+            if (a.nearest < 1 || a.nearest > 256)
+                die_usage("invalid value '" + v + "' for '--nearest <k>': " + v + " is not in 1..=256");
+            a.has_nearest = true;
         } else if (arg == "--host-selftest") {
             a.selftest = value_of(k, arg, "--host-selftest <what>");
         } else {
@@ -204,6 +215,11 @@ Args parse_args(int argc, char **argv)
     }
     if (a.pos_inputs.size() > 2)
         die_usage("unexpected argument '" + a.pos_inputs[2] + "' found");
+    if (a.has_nearest && a.has_stream)
+        die_usage("the argument '--nearest <k>' cannot be used with '--stream <stream>'");
+    if (a.has_nearest && (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1)))
+        die_usage(std::string("the argument '--nearest <k>' cannot be used with '") +
+                  (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
     if (dst_measure_from_name(a.measure.c_str()) < 0)
         die_usage("invalid value '" + a.measure + "' for '--measure <measure>'\n  [possible values: n, n_high, raw, "
                   "jc69, k80, tn93]");
@@ -993,6 +1009,45 @@ void run_slabs(std::vector<Ctx> &gpus, const Job &job, int row_slot, int col_slo
 }
 
 // ---------------------------------------------------------------- host self-tests (no GPU) -----
+// --nearest: per record of the first file (in input order) its k_used nearest records — of the same file (one input,
+// the square) or of the second — from dst_nearest, each line "own id, neighbour id, value" with the value's text exactly
+// as the full run prints that pair: the canonical pair's tallies through dst_finalize, then dst_format_distance.
+void write_nearest(const Ctx &gpu, const std::vector<Alignment> &loaded, const std::vector<std::vector<uint32_t>> &counts,
+                   int measure, uint32_t k, Writer &wr)
+{
+    const bool square = loaded.size() == 1;
+    const Alignment &rows = loaded[0], &cols = loaded.back();
+    const size_t W = (size_t)dst_tally_width(measure);
+    const size_t cap = rows.n * std::min<size_t>(k, square ? (rows.n ? rows.n - 1 : 0) : cols.n);
+    std::vector<uint32_t> index(std::max<size_t>(cap, 1)), tallies(std::max<size_t>(cap * W, 1));
+    uint32_t ku = 0;
+    gpu.check(dst_nearest(gpu.h, measure, square ? 1 : 0, 0, 1, k, index.data(), tallies.data(), nullptr, cap, &ku), "nearest");
+    const uint32_t *rc = measure == DST_TN93 ? counts[0].data() : nullptr;
+    const uint32_t *cc = measure == DST_TN93 ? counts.back().data() : nullptr;
+    std::string out;
+    char num[64];
+    for (size_t i = 0; i < rows.n; ++i)
+        for (size_t e = 0; e < ku; ++e) {
+            const size_t at = i * ku + e, j = index[at];
+            const size_t q = square ? std::min(i, j) : i, t = square ? std::max(i, j) : j;
+            double f = 0;
+            int64_t v = 0;
+            dst_finalize(measure, &tallies[at * W], rc ? rc + 4 * q : nullptr, cc ? cc + 4 * t : nullptr, &f, &v);
+            const int len = dst_format_distance(measure, f, v, num, sizeof num);
+            out += rows.ids[i];
+            out += '\t';
+            out += cols.ids[j];
+            out += '\t';
+            out.append(num, (size_t)std::min<int>(len, (int)sizeof num - 1));
+            out += '\n';
+            if (out.size() >= ((size_t)1 << 20)) {
+                wr.write(out.data(), out.size());
+                out.clear();
+            }
+        }
+    wr.write(out.data(), out.size());
+}
+
 int host_selftest(const Args &a)
 {
     if (a.selftest == "fasta") {  // parse stdin, print one line per record
@@ -1210,7 +1265,9 @@ int main(int argc, char **argv)
     Job job;
     job.measure = measure;
     job.fmt_threads = std::max<size_t>(1, threads / (size_t)G);
-    if (!stream_fh) {
+    if (a.has_nearest) {
+        write_nearest(gpus[0], loaded, counts, measure, (uint32_t)a.nearest, wr);
+    } else if (!stream_fh) {
         // ---- load(): src/lib.rs:367-474 -------------------------------------------------------
         job.square = loaded.size() == 1;
         job.rows = &loaded[0];

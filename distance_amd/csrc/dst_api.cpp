@@ -1216,7 +1216,7 @@ int dst_destroy(dst_ctx *ctx)
                 (void)hipFree(b);
     for (void *b : {(void *)ctx->d_lut, (void *)ctx->d_total, (void *)ctx->scan_tmp, ctx->host_out, ctx->hot_tally, ctx->text_res,
                     ctx->text_num, (void *)ctx->text_len, (void *)ctx->text_scan, (void *)ctx->text_buf, (void *)ctx->text_flag, ctx->text_ties,
-                    (void *)ctx->ids[0].off, (void *)ctx->ids[0].chars, (void *)ctx->ids[1].off, (void *)ctx->ids[1].chars})
+                    (void *)ctx->ids[0].off, (void *)ctx->ids[0].chars, (void *)ctx->ids[1].off, (void *)ctx->ids[1].chars, ctx->nn_slab, ctx->nn_lists})
         if (b)
             (void)hipFree(b);
     if (ctx->scratch)
@@ -1645,26 +1645,10 @@ int dst_run_slabs(dst_ctx *ctx, int measure, int square, int row_slot, int col_s
     const uint64_t n_rows = ctx->set[row_slot].n, n_cols = ctx->set[col_slot].n;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // two device + two pinned host buffers sized for the largest slab
-    struct Slab {
-        uint64_t rb, re, first, pairs;
-    };
-    std::vector<Slab> slabs;
-    uint64_t first = 0, biggest = 0;
-    for (uint64_t rb = 0; rb < n_rows;) {
-        uint64_t re = rb, pairs = 0;
-        while (re < n_rows) {
-            const uint64_t row_pairs = square ? (n_cols - re - 1) : n_cols;
-            if (re > rb && pairs + row_pairs > max_pairs)
-                break;
-            pairs += row_pairs;
-            ++re;
-        }
-        if (pairs)
-            slabs.push_back({rb, re, first, pairs});
-        first += pairs;
-        biggest = std::max(biggest, pairs);
-        rb = re;
-    }
+    const std::vector<RowSlab> slabs = cut_row_slabs(square != 0, n_rows, n_cols, max_pairs);
+    uint64_t biggest = 0;
+    for (const RowSlab &s : slabs)
+        biggest = std::max(biggest, s.pairs);
     if (slabs.empty())
         return DST_OK;
     const size_t bytes = dst_out_bytes(measure, out_kind, biggest);
@@ -1697,7 +1681,7 @@ int dst_run_slabs(dst_ctx *ctx, int measure, int square, int row_slot, int col_s
         SLAB_TRY(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
     }
     auto issue = [&](size_t k) -> int {  // compute slab k and start its copy back, all on ctx->stream
-        const Slab &s = slabs[k];
+        const RowSlab &s = slabs[k];
         const size_t nb = dst_out_bytes(measure, out_kind, s.pairs);
         int r = run_common(ctx, measure, square != 0, row_slot, col_slot, s.rb, s.re, out_kind, d_buf[k & 1], nb,
                            (void *)ctx->stream);
@@ -1721,6 +1705,100 @@ int dst_run_slabs(dst_ctx *ctx, int measure, int square, int row_slot, int col_s
 #undef SLAB_TRY
     cleanup();
     return rc;
+}
+
+int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, uint32_t k, uint32_t *index,
+                uint32_t *tallies, void *values, size_t cap_entries, uint32_t *k_used)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (k_used)
+        *k_used = 0;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (k < 1 || k > kNearestMaxK)
+        return fail(ctx, DST_ERR_ARG, "k must be between 1 and 256");
+    if (!index || !k_used)
+        return fail(ctx, DST_ERR_ARG, "null index or k_used pointer");
+    if (square) {
+        row_slot = 0;
+        col_slot = 0;
+    } else {
+        if (row_slot < 0 || row_slot > 1 || col_slot < 0 || col_slot > 1)
+            return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
+        if (row_slot == col_slot)
+            return fail(ctx, DST_ERR_ARG, "row_slot == col_slot: use the square form for one set");
+    }
+    DeviceSet &rows = ctx->set[row_slot], &cols = ctx->set[col_slot];
+    if (!rows.loaded || !cols.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    if (rows.len != cols.len) {
+        char msg[128];  // src/fastaio.rs:93-95
+        std::snprintf(msg, sizeof msg, "Different length sequences in alignment(s): %zu vs %zu", rows.len, cols.len);
+        return fail(ctx, DST_ERR_STATE, msg);
+    }
+    const uint64_t n_rows = rows.n, n_cols = cols.n;
+    if (n_rows >= 0xFFFFFFFFull || n_cols >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    const uint64_t candidates = square ? (n_rows > 0 ? n_rows - 1 : 0) : n_cols;
+    const uint32_t ku = (uint32_t)std::min<uint64_t>(k, candidates);
+    if (n_rows * ku > cap_entries)
+        return fail(ctx, DST_ERR_CAPACITY, "cap_entries is below n_rows x k_used");
+    if (ku == 0 || n_rows == 0) {
+        *k_used = ku;
+        return DST_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const int W = tally_width(measure);
+    int rc = DST_OK;
+    if (measure == DST_TN93) {
+        rc = need_counts(ctx, rows, stream);
+        if (!rc && &cols != &rows)
+            rc = need_counts(ctx, cols, stream);
+        if (rc)
+            return rc;
+    }
+    const std::vector<RowSlab> slabs = cut_row_slabs(square != 0, n_rows, n_cols, kNearestSlabPairs);
+    uint64_t biggest = 0;
+    for (const RowSlab &s : slabs)
+        biggest = std::max(biggest, s.pairs);
+    const size_t slab_bytes = dst_out_bytes(measure, DST_OUT_TALLY, biggest);
+    const uint64_t entries = n_rows * ku;
+    const size_t val_bytes = entries * 8, idx_bytes = (entries * 4 + 255) / 256 * 256, tal_bytes = entries * W * 4;
+    HIP_TRY(ctx, hipStreamSynchronize(stream));   // (the grow-only buffers of an earlier call: nothing reads them now)
+    rc = ensure_bytes(ctx, &ctx->nn_slab, &ctx->nn_slab_bytes, std::max<size_t>(slab_bytes, 256));
+    if (!rc)
+        rc = ensure_bytes(ctx, &ctx->nn_lists, &ctx->nn_lists_bytes, val_bytes + idx_bytes + tal_bytes);
+    if (rc)
+        return rc;
+    NearestLists nl{};
+    nl.val = static_cast<uint64_t *>(ctx->nn_lists);
+    nl.idx = reinterpret_cast<uint32_t *>(static_cast<char *>(ctx->nn_lists) + val_bytes);
+    nl.tal = reinterpret_cast<uint32_t *>(static_cast<char *>(ctx->nn_lists) + val_bytes + idx_bytes);
+    nl.k = ku;
+    HIP_TRY(ctx, launch_nearest_init(nl, n_rows, stream));
+    const uint32_t *slab = static_cast<const uint32_t *>(ctx->nn_slab);
+    for (const RowSlab &s : slabs) {
+        // the pairs of the slab, each once (square: the triangle), as exact tallies
+        rc = run_sets(ctx, measure, square != 0, rows, cols, s.rb, s.re, DST_OUT_TALLY, ctx->nn_slab, ctx->nn_slab_bytes,
+                      (void *)stream);
+        if (rc)
+            return rc;
+        // both passes on the context's stream, behind the slab's pair kernel: they touch the same lists
+        HIP_TRY(ctx, launch_nearest_rows(measure, square != 0, slab, s.first, n_cols, s.rb, s.re, rows.counts, cols.counts,
+                                         nl, stream));
+        if (square)
+            HIP_TRY(ctx, launch_nearest_cols(measure, slab, s.first, n_cols, s.rb, s.re, cols.counts, nl, stream));
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(index, nl.idx, entries * 4, hipMemcpyDeviceToHost, stream));
+    if (values)
+        HIP_TRY(ctx, hipMemcpyAsync(values, nl.val, val_bytes, hipMemcpyDeviceToHost, stream));
+    if (tallies)
+        HIP_TRY(ctx, hipMemcpyAsync(tallies, nl.tal, tal_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    *k_used = ku;
+    return DST_OK;
 }
 
 int dst_run_square_host(dst_ctx *ctx, int measure, uint64_t row_begin, uint64_t row_end, int out_kind,

@@ -92,6 +92,9 @@ struct dst_ctx {
         uint64_t last_biggest = 0;   // entries of the largest block of the previous shared upload (sizes the next one)
         uint64_t uploads = 0, fallbacks = 0;
     } shared[2];
+    // dst_nearest: the slab's DST_OUT_TALLY scratch and the running lists (grow-only)
+    void *nn_slab = nullptr, *nn_lists = nullptr;
+    size_t nn_slab_bytes = 0, nn_lists_bytes = 0;
     // HIP events around the pair kernel ([0]) and the pack kernel ([1]) of the most recent launches, recorded on the launch
     // stream: a ring, so that a caller timing many steps reads them ONCE at the end (dst_kernel_ms_mean) instead of
     // waiting for the device after every step

@@ -42,6 +42,27 @@ uint64_t pairs_in_rows(bool square, uint64_t n_cols, uint64_t row_begin, uint64_
     return square_row_start(n_cols, e) - square_row_start(n_cols, b);
 }
 
+std::vector<RowSlab> cut_row_slabs(bool square, uint64_t n_rows, uint64_t n_cols, uint64_t max_pairs)
+{
+    std::vector<RowSlab> slabs;
+    uint64_t first = 0;
+    for (uint64_t rb = 0; rb < n_rows;) {
+        uint64_t re = rb, pairs = 0;
+        while (re < n_rows) {
+            const uint64_t row_pairs = square ? (n_cols - re - 1) : n_cols;
+            if (re > rb && pairs + row_pairs > max_pairs)
+                break;
+            pairs += row_pairs;
+            ++re;
+        }
+        if (pairs)
+            slabs.push_back({rb, re, first, pairs});
+        first += pairs;
+        rb = re;
+    }
+    return slabs;
+}
+
 // Tiles of one launch.  A column tile ("panel") of BN records is shared by every row tile that
 // meets it; the panel is the big operand (BN >> BM), so all row tiles of one panel are queued
 // back to back on ONE of 8 queues, and the queues are interleaved so that block ids b, b+8, ...

@@ -353,6 +353,28 @@ hipError_t launch_finalize(int measure, const PairLaunch &pl, const void *d_tall
 TileShape tile_shape(int measure, int variant);
 int variant_count(int measure);
 
+// ---- k nearest records (dst_nearest.hip, driven by dst_nearest in dst_api.cpp) -------------------------------------
+// A call cuts the rows into slabs of at most kNearestSlabPairs pairs (cut_row_slabs, like dst_run_slabs), runs each slab
+// into a DST_OUT_TALLY scratch (square: the triangle, every pair once) and merges it into device-resident lists of
+// k entries per record, sorted by (key of the DST_OUT_DISTANCE payload, column record).
+constexpr uint64_t kNearestSlabPairs = (uint64_t)1 << 25;   // 33.5 M pairs: 0.5 GB of tn93 tallies
+constexpr uint32_t kNearestMaxK = 256;
+struct NearestLists {
+    uint64_t *val;   // [records][k] DST_OUT_DISTANCE payloads (int64 / f64 bits)
+    uint32_t *idx;   // [records][k] column records (2^32-1: an empty entry)
+    uint32_t *tal;   // [records][k][tally_width] DST_OUT_TALLY words of the pair
+    uint32_t k;
+};
+hipError_t launch_nearest_init(const NearestLists &nl, uint64_t records, hipStream_t stream);
+// row pass: rows [rb, re) of the slab offer their pairs to their own lists (q_counts / t_counts: tn93's base counts of the
+// row and the column set)
+hipError_t launch_nearest_rows(int measure, bool square, const uint32_t *slab, uint64_t out_base, uint64_t n_cols, uint64_t rb,
+                               uint64_t re, const uint32_t *q_counts, const uint32_t *t_counts, const NearestLists &nl,
+                               hipStream_t stream);
+// column pass (square): pairs (i, j), i in [rb, re), j > i, offer i to record j's list
+hipError_t launch_nearest_cols(int measure, const uint32_t *slab, uint64_t out_base, uint64_t n, uint64_t rb, uint64_t re,
+                               const uint32_t *counts, const NearestLists &nl, hipStream_t stream);
+
 // ---- host-only logic (dst_host.cpp) ----------------------------------------------------------
 int tally_width(int measure);
 bool measure_is_int(int measure);
@@ -362,5 +384,11 @@ std::vector<BlockDesc> build_blocks(bool square, uint64_t row_begin, uint64_t ro
                                     uint64_t n_cols, TileShape ts);
 uint64_t square_row_start(uint64_t n, uint64_t i);
 uint64_t pairs_in_rows(bool square, uint64_t n_cols, uint64_t row_begin, uint64_t row_end);
+// rows [0, n_rows) cut in order into slabs of at most max_pairs pairs (at least one row each); slabs without pairs are
+// left out.  first = canonical index of the slab's first pair (dst_run_slabs, dst_nearest)
+struct RowSlab {
+    uint64_t rb, re, first, pairs;
+};
+std::vector<RowSlab> cut_row_slabs(bool square, uint64_t n_rows, uint64_t n_cols, uint64_t max_pairs);
 
 }  // namespace dst

@@ -1,0 +1,390 @@
+// dst_nearest.hip — the k nearest records of every record (dst_nearest): selection kernels over one row slab of
+// DST_OUT_TALLY tallies, merged into running lists that live on the device for the whole call.
+//
+//   nearest_init_kernel  every list entry := the sentinel (a key above every real one, index 2^32-1)
+//   nearest_rows_kernel  row pass: row i of the slab offers its pairs to record i's list (one wave per row)
+//   nearest_cols_kernel  column pass, square only: pairs (i, j) with i in the slab and j > i offer i to record j's list;
+//                        a wave owns 64 consecutive j, reads 64 rows of them coalesced into LDS, then walks the columns
+//
+// A list is sorted ascending by (key, index), a strict total order, so the k smallest are unique and the passes may
+// meet the candidates in any order.  Inside a kernel a wave holds one list in registers, entry e = 64 s + lane in slot
+// s (k <= kNearestMaxK = 256: four slots); a candidate below the list's k-th entry is inserted by a shift across the
+// lanes.  The value of a pair is the DST_OUT_DISTANCE payload, from the tallies through finalize_pair<M, false> — the
+// arithmetic of the pair kernels' epilogue and of finalize_kernel — so it is bitwise what a distance run returns.
+#include "dst_device.hpp"
+
+namespace dst {
+namespace {
+
+constexpr int kSlots = (int)(kNearestMaxK / 64);
+constexpr uint64_t kSentinelVal = 0x7FFFFFFFFFFFFFFFull;   // key ~0 for both the int64 and the f64 payloads
+constexpr uint32_t kSentinelIdx = 0xFFFFFFFFu;
+
+// the sort key of a DST_OUT_DISTANCE payload: int64 -> offset binary; f64 -> the order-preserving bit flip, every NaN
+// ~0 (after +inf, equal to each other), -0.0 the key of +0.0
+template <bool INT>
+__device__ __forceinline__ uint64_t nn_key(uint64_t bits)
+{
+    if constexpr (INT) {
+        return bits ^ 0x8000000000000000ull;
+    } else {
+        const uint64_t mag = bits & 0x7FFFFFFFFFFFFFFFull;
+        if (mag > 0x7FF0000000000000ull)
+            return ~0ull;
+        if (mag == 0)
+            return 0x8000000000000000ull;
+        return (bits >> 63) ? ~bits : bits | 0x8000000000000000ull;
+    }
+}
+
+__device__ __forceinline__ bool nn_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib)
+{
+    return ka < kb || (ka == kb && ia < ib);
+}
+
+__device__ __forceinline__ uint64_t shfl64(uint64_t x, int src)
+{
+    const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)x, src, 64), hi = (uint32_t)__shfl((int)(uint32_t)(x >> 32), src, 64);
+    return (uint64_t)hi << 32 | lo;
+}
+__device__ __forceinline__ uint32_t shfl32(uint32_t x, int src) { return (uint32_t)__shfl((int)x, src, 64); }
+
+template <int M>
+__device__ __forceinline__ uint64_t pair_value(const uint32_t *o, uint4 qc, uint4 tc)
+{
+    if constexpr (M == DST_N_HIGH)
+        return (uint64_t)(int64_t)o[0];
+    else
+        return (uint64_t)__double_as_longlong(finalize_pair<M>(o, qc, tc));
+}
+
+// one record's list, spread over the wave
+template <int W>
+struct WaveList {
+    uint64_t key[kSlots], val[kSlots];
+    uint32_t idx[kSlots], tal[kSlots][W];
+    uint64_t thr_key;   // entry k-1
+    uint32_t thr_idx;
+
+    template <bool INT>
+    __device__ void load(const uint64_t *lval, const uint32_t *lidx, const uint32_t *ltal, uint64_t base, uint32_t k, int lane)
+    {
+#pragma unroll
+        for (int s = 0; s < kSlots; ++s) {
+            const uint32_t e = (uint32_t)(s * 64 + lane);
+            if (e < k) {
+                val[s] = lval[base + e];
+                idx[s] = lidx[base + e];
+#pragma unroll
+                for (int t = 0; t < W; ++t)
+                    tal[s][t] = ltal[(base + e) * W + t];
+                key[s] = idx[s] == kSentinelIdx ? ~0ull : nn_key<INT>(val[s]);
+            } else {
+                val[s] = kSentinelVal;
+                idx[s] = kSentinelIdx;
+                key[s] = ~0ull;
+#pragma unroll
+                for (int t = 0; t < W; ++t)
+                    tal[s][t] = 0;
+            }
+        }
+        threshold(k);
+    }
+
+    __device__ void store(uint64_t *lval, uint32_t *lidx, uint32_t *ltal, uint64_t base, uint32_t k, int lane) const
+    {
+#pragma unroll
+        for (int s = 0; s < kSlots; ++s) {
+            const uint32_t e = (uint32_t)(s * 64 + lane);
+            if (e < k) {
+                lval[base + e] = val[s];
+                lidx[base + e] = idx[s];
+#pragma unroll
+                for (int t = 0; t < W; ++t)
+                    ltal[(base + e) * W + t] = tal[s][t];
+            }
+        }
+    }
+
+    __device__ void threshold(uint32_t k)
+    {
+        const int s_t = (int)((k - 1) / 64), l_t = (int)((k - 1) % 64);
+        uint64_t kk = 0;
+        uint32_t ii = 0;
+#pragma unroll
+        for (int s = 0; s < kSlots; ++s)
+            if (s == s_t) {   // (wave-uniform)
+                kk = key[s];
+                ii = idx[s];
+            }
+        thr_key = shfl64(kk, l_t);
+        thr_idx = shfl32(ii, l_t);
+    }
+
+    // the candidate (wave-uniform) is below entry k-1: it goes where it belongs, the entries behind it move up one
+    __device__ void insert(uint64_t ck, uint64_t cv, uint32_t ci, const uint32_t *ct, uint32_t k, int lane)
+    {
+        uint32_t pos = 0;
+#pragma unroll
+        for (int s = 0; s < kSlots; ++s)
+            pos += (uint32_t)__popcll(__ballot(nn_less(key[s], idx[s], ck, ci)));
+        const int from = lane == 0 ? 63 : lane - 1;
+#pragma unroll
+        for (int s = kSlots - 1; s >= 0; --s) {
+            // entry e - 1: the lane below in this slot, or lane 63 of the slot before for lane 0
+            uint64_t pk = shfl64(key[s], from), pv = shfl64(val[s], from);
+            uint32_t pi = shfl32(idx[s], from), pt[W];
+#pragma unroll
+            for (int t = 0; t < W; ++t)
+                pt[t] = shfl32(tal[s][t], from);
+            if (s > 0) {
+                const uint64_t qk = shfl64(key[s - 1], 63), qv = shfl64(val[s - 1], 63);
+                const uint32_t qi = shfl32(idx[s - 1], 63);
+                uint32_t qt[W];
+#pragma unroll
+                for (int t = 0; t < W; ++t)
+                    qt[t] = shfl32(tal[s - 1][t], 63);
+                if (lane == 0) {
+                    pk = qk;
+                    pv = qv;
+                    pi = qi;
+#pragma unroll
+                    for (int t = 0; t < W; ++t)
+                        pt[t] = qt[t];
+                }
+            }
+            const uint32_t e = (uint32_t)(s * 64 + lane);
+            if (e > pos) {
+                key[s] = pk;
+                val[s] = pv;
+                idx[s] = pi;
+#pragma unroll
+                for (int t = 0; t < W; ++t)
+                    tal[s][t] = pt[t];
+            } else if (e == pos) {
+                key[s] = ck;
+                val[s] = cv;
+                idx[s] = ci;
+#pragma unroll
+                for (int t = 0; t < W; ++t)
+                    tal[s][t] = ct[t];
+            }
+        }
+        threshold(k);
+    }
+
+    // every lane of `mask` offers its candidate, lowest lane first (the order does not matter: a total order)
+    template <bool INT>
+    __device__ void offer(uint64_t mask, bool pass, uint64_t ck, uint64_t cv, uint32_t ci, const uint32_t *ct, uint32_t k, int lane)
+    {
+        while (mask) {
+            const int src = __ffsll((unsigned long long)mask) - 1;
+            const uint64_t bk = shfl64(ck, src), bv = shfl64(cv, src);
+            const uint32_t bi = shfl32(ci, src);
+            uint32_t bt[W];
+#pragma unroll
+            for (int t = 0; t < W; ++t)
+                bt[t] = shfl32(ct[t], src);
+            insert(bk, bv, bi, bt, k, lane);
+            mask &= ~(1ull << src);
+            mask &= __ballot(pass && nn_less(ck, ci, thr_key, thr_idx));
+        }
+    }
+};
+
+__global__ __launch_bounds__(256) void nearest_init_kernel(uint64_t *lval, uint32_t *lidx, uint64_t entries)
+{
+    for (uint64_t e = (uint64_t)blockIdx.x * blockDim.x + threadIdx.x; e < entries; e += (uint64_t)gridDim.x * blockDim.x) {
+        lval[e] = kSentinelVal;
+        lidx[e] = kSentinelIdx;
+    }
+}
+
+// Row pass.  Row i of the slab: square, pairs (i, j > i) from slab entry tri_row_start(n, i) - out_base; rectangle,
+// pairs (i, 0 .. n_cols-1) from (i - rb) n_cols.  One wave per row, 64 consecutive candidates per step.
+template <int M, int W>
+__global__ __launch_bounds__(256) void nearest_rows_kernel(const uint32_t *__restrict__ slab, uint64_t out_base, uint32_t n_cols,
+                                                           uint32_t rb, uint32_t re, int square,
+                                                           const uint32_t *__restrict__ q_counts,
+                                                           const uint32_t *__restrict__ t_counts, uint64_t *lval,
+                                                           uint32_t *lidx, uint32_t *ltal, uint32_t k)
+{
+    constexpr bool INT = M == DST_N_HIGH;
+    const int lane = (int)(threadIdx.x & 63);
+    const uint32_t i = rb + (uint32_t)((blockIdx.x * blockDim.x + threadIdx.x) >> 6);
+    if (i >= re)
+        return;   // (whole waves)
+    const uint32_t jstart = square ? i + 1 : 0;
+    const uint64_t base = square ? tri_row_start(n_cols, i) - out_base : (uint64_t)(i - rb) * n_cols;
+    uint4 qc = make_uint4(0, 0, 0, 0), tc = qc;
+    if constexpr (M == DST_TN93)
+        qc = reinterpret_cast<const uint4 *>(q_counts)[i];
+    WaveList<W> L;
+    L.template load<INT>(lval, lidx, ltal, (uint64_t)i * k, k, lane);
+    for (uint32_t j0 = jstart; j0 < n_cols; j0 += 64) {
+        const uint32_t j = j0 + (uint32_t)lane;
+        const bool valid = j < n_cols;
+        uint32_t o[W];
+        uint64_t v = 0, key = ~0ull;
+        if (valid) {
+            const uint64_t at = base + (j - jstart);
+#pragma unroll
+            for (int t = 0; t < W; ++t)
+                o[t] = slab[at * W + t];
+            if constexpr (M == DST_TN93)
+                tc = reinterpret_cast<const uint4 *>(t_counts)[j];
+            v = pair_value<M>(o, qc, tc);
+            key = nn_key<INT>(v);
+        } else {
+#pragma unroll
+            for (int t = 0; t < W; ++t)
+                o[t] = 0;
+        }
+        const bool pass = valid && nn_less(key, j, L.thr_key, L.thr_idx);
+        const uint64_t mask = __ballot(pass);
+        if (mask)
+            L.template offer<INT>(mask, pass, key, v, j, o, k, lane);
+    }
+    L.store(lval, lidx, ltal, (uint64_t)i * k, k, lane);
+}
+
+// Column pass (square).  Block b: the 64 records j0 .. j0+63, j0 = rb + 1 + 64 b, against the slab's rows i < j.
+// Each step reads 64 rows of those 64 columns (lane = column: consecutive addresses within a row) into LDS, then takes
+// the columns one by one with lane = row, like a step of the row pass; a column's list is loaded only when one of
+// the 64 candidates is below its k-th entry (every lane keeps its own column's threshold in registers).
+template <int M, int W>
+__global__ __launch_bounds__(64) void nearest_cols_kernel(const uint32_t *__restrict__ slab, uint64_t out_base, uint32_t n,
+                                                          uint32_t rb, uint32_t re, const uint32_t *__restrict__ counts,
+                                                          uint64_t *lval, uint32_t *lidx, uint32_t *ltal, uint32_t k)
+{
+    constexpr bool INT = M == DST_N_HIGH;
+    __shared__ uint64_t tile[64][65];
+    const int lane = (int)threadIdx.x;
+    const uint32_t j0 = rb + 1 + blockIdx.x * 64;
+    const uint32_t jl = j0 + (uint32_t)lane;   // this lane's column in the load phase
+    const uint32_t iend = min(re, j0 + 63);    // rows below some column of the block
+    uint64_t my_thr_key = ~0ull;
+    uint32_t my_thr_idx = kSentinelIdx;
+    if (jl < n) {
+        const uint64_t e = (uint64_t)jl * k + (k - 1);
+        my_thr_idx = lidx[e];
+        my_thr_key = my_thr_idx == kSentinelIdx ? ~0ull : nn_key<INT>(lval[e]);
+    }
+    uint4 qc = make_uint4(0, 0, 0, 0), tc = qc;
+    if constexpr (M == DST_TN93)
+        if (jl < n)
+            tc = reinterpret_cast<const uint4 *>(counts)[jl];
+    for (uint32_t i0 = rb; i0 < iend; i0 += 64) {
+        const uint32_t rows = min(64u, iend - i0);
+        for (uint32_t r = 0; r < rows; ++r) {
+            const uint32_t i = i0 + r;
+            uint64_t v = 0;
+            if (i < jl && jl < n) {
+                const uint64_t at = tri_row_start(n, i) - out_base + (jl - i - 1);
+                uint32_t o[W];
+#pragma unroll
+                for (int t = 0; t < W; ++t)
+                    o[t] = slab[at * W + t];
+                if constexpr (M == DST_TN93)
+                    qc = reinterpret_cast<const uint4 *>(counts)[i];
+                v = pair_value<M>(o, qc, tc);
+            }
+            tile[r][lane] = v;
+        }
+        __syncthreads();
+        const uint32_t i = i0 + (uint32_t)lane;   // this lane's row in the selection phase
+        for (int c = 0; c < 64; ++c) {
+            const uint32_t j = j0 + (uint32_t)c;
+            if (j >= n)
+                break;
+            const bool valid = (uint32_t)lane < rows && i < j;
+            const uint64_t v = tile[lane][c];
+            const uint64_t key = valid ? nn_key<INT>(v) : ~0ull;
+            const uint64_t tk = shfl64(my_thr_key, c);
+            const uint32_t ti = shfl32(my_thr_idx, c);
+            const bool pass = valid && nn_less(key, i, tk, ti);
+            const uint64_t mask = __ballot(pass);
+            if (!mask)
+                continue;
+            uint32_t o[W];
+            if (pass) {
+                const uint64_t at = tri_row_start(n, i) - out_base + (j - i - 1);
+#pragma unroll
+                for (int t = 0; t < W; ++t)
+                    o[t] = slab[at * W + t];
+            } else {
+#pragma unroll
+                for (int t = 0; t < W; ++t)
+                    o[t] = 0;
+            }
+            WaveList<W> L;
+            L.template load<INT>(lval, lidx, ltal, (uint64_t)j * k, k, lane);
+            L.template offer<INT>(mask, pass, key, v, i, o, k, lane);
+            L.store(lval, lidx, ltal, (uint64_t)j * k, k, lane);
+            if (lane == c) {
+                my_thr_key = L.thr_key;
+                my_thr_idx = L.thr_idx;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+}  // namespace
+
+hipError_t launch_nearest_init(const NearestLists &nl, uint64_t records, hipStream_t stream)
+{
+    const uint64_t entries = records * nl.k;
+    if (entries == 0)
+        return hipSuccess;
+    const unsigned blocks = (unsigned)std::min<uint64_t>((entries + 255) / 256, 4096);
+    hipLaunchKernelGGL(nearest_init_kernel, dim3(blocks), dim3(256), 0, stream, nl.val, nl.idx, entries);
+    return hipGetLastError();
+}
+
+hipError_t launch_nearest_rows(int measure, bool square, const uint32_t *slab, uint64_t out_base, uint64_t n_cols, uint64_t rb,
+                               uint64_t re, const uint32_t *q_counts, const uint32_t *t_counts, const NearestLists &nl,
+                               hipStream_t stream)
+{
+    if (re <= rb)
+        return hipSuccess;
+    const unsigned blocks = (unsigned)((re - rb + 3) / 4);   // four waves (rows) per workgroup
+#define DST_NN_ROWS(MEAS, W)                                                                                            \
+    hipLaunchKernelGGL((nearest_rows_kernel<MEAS, W>), dim3(blocks), dim3(256), 0, stream, slab, out_base, (uint32_t)n_cols, \
+                       (uint32_t)rb, (uint32_t)re, square ? 1 : 0, q_counts, t_counts, nl.val, nl.idx, nl.tal, nl.k)
+    switch (measure) {
+    case DST_N:
+    case DST_N_HIGH: DST_NN_ROWS(DST_N_HIGH, 1); break;
+    case DST_RAW: DST_NN_ROWS(DST_RAW, 2); break;
+    case DST_JC69: DST_NN_ROWS(DST_JC69, 2); break;
+    case DST_K80: DST_NN_ROWS(DST_K80, 3); break;
+    case DST_TN93: DST_NN_ROWS(DST_TN93, 4); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef DST_NN_ROWS
+    return hipGetLastError();
+}
+
+hipError_t launch_nearest_cols(int measure, const uint32_t *slab, uint64_t out_base, uint64_t n, uint64_t rb, uint64_t re,
+                               const uint32_t *counts, const NearestLists &nl, hipStream_t stream)
+{
+    if (re <= rb || rb + 1 >= n)
+        return hipSuccess;
+    const unsigned blocks = (unsigned)((n - rb - 1 + 63) / 64);
+#define DST_NN_COLS(MEAS, W)                                                                                            \
+    hipLaunchKernelGGL((nearest_cols_kernel<MEAS, W>), dim3(blocks), dim3(64), 0, stream, slab, out_base, (uint32_t)n,      \
+                       (uint32_t)rb, (uint32_t)re, counts, nl.val, nl.idx, nl.tal, nl.k)
+    switch (measure) {
+    case DST_N:
+    case DST_N_HIGH: DST_NN_COLS(DST_N_HIGH, 1); break;
+    case DST_RAW: DST_NN_COLS(DST_RAW, 2); break;
+    case DST_JC69: DST_NN_COLS(DST_JC69, 2); break;
+    case DST_K80: DST_NN_COLS(DST_K80, 3); break;
+    case DST_TN93: DST_NN_COLS(DST_TN93, 4); break;
+    default: return hipErrorInvalidValue;
+    }
+#undef DST_NN_COLS
+    return hipGetLastError();
+}
+
+}  // namespace dst

@@ -303,6 +303,25 @@ class Engine:
         cb = SLAB_SINK(_cb)
         self._check(self._lib.dst_run_slabs(self._h, m, int(square), row_slot, col_slot, kind, max_pairs, cb, None))
 
+    def nearest(self, measure, k: int, square: bool = True, row_slot: int = 0, col_slot: int = 1, tallies: bool = False):
+        """The k nearest records of every row record (dst_nearest): (index[n_rows, k_used], values[n_rows, k_used]), plus
+        tallies[n_rows, k_used, width] when asked.  Ascending by (key of the value, index); square: slot 0 against itself
+        without the diagonal, the canonical pair's value; else row_slot against every record of col_slot."""
+        m = _measure_id(measure)
+        n_rows, _ = self.set_info(0 if square else row_slot)
+        n_cols, _ = self.set_info(0 if square else col_slot)
+        ku = min(int(k), max(n_rows - 1, 0) if square else n_cols) if 1 <= int(k) <= 256 else 0
+        width = self._lib.dst_tally_width(m)
+        index = np.zeros((n_rows, ku), np.uint32)
+        values = np.zeros((n_rows, ku), np.int64 if m in (0, 1) else np.float64)
+        tal = np.zeros((n_rows, ku, width), np.uint32) if tallies else None
+        k_used = C.c_uint32()
+        self._check(self._lib.dst_nearest(self._h, m, int(square), row_slot, col_slot, int(k), index.ctypes.data,
+                                          None if tal is None else tal.ctypes.data, values.ctypes.data, n_rows * ku,
+                                          C.byref(k_used)))
+        assert k_used.value == ku
+        return (index, values, tal) if tallies else (index, values)
+
     # ---- runs into device memory (bench / multi-GPU) ------------------------------------------
     def run_square_device(self, measure, row_begin: int, row_end: int, d_out: int, capacity: int,
                           tallies: bool = False, stream: int | None = None, out_kind: int | None = None):

@@ -299,6 +299,31 @@ typedef int (*dst_slab_sink)(void *user, uint64_t first_pair, uint64_t n_pairs, 
                              uint64_t row_end, const void *data);
 int dst_run_slabs(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, int out_kind,
                   uint64_t max_pairs, dst_slab_sink sink, void *user);
+/* ---- k nearest records ------------------------------------------------------------------------ */
+/* For every record of the row set, the k records with the smallest distance, computed next to the values on the GPU
+ * (the full result of a large alignment is tens of GB of text; placement, outbreak context and duplicate searches want a
+ * few neighbours per record).
+ *  square != 0: one set (slot 0; row_slot / col_slot ignored), record i against every j != i; identical sequences stay
+ *               (distance 0 is a neighbour).  Candidates per row: n - 1.
+ *  square == 0: every record of row_slot against every record of col_slot, none excluded; row_slot == col_slot is
+ *               DST_ERR_ARG (use the square form).  Candidates per row: n of col_slot.
+ * Order: ascending (key, column record), key from the pair's DST_OUT_DISTANCE payload v:
+ *   n / n_high (int64):  key = (uint64)v ^ 2^63
+ *   f64:                 NaN -> key ~0 (after +inf; NaNs equal to each other), -0.0 -> the key of +0.0, any other value
+ *                        the order-preserving flip (v >= 0: bits | 2^63, v < 0: ~bits)
+ * a strict total order, so the k smallest and their order are unique whatever the slabs.  Square results are those of
+ * the canonical pair (min(i, j), max(i, j)): the value and tallies of the line a full run prints for it (tn93: base
+ * counts in that order).  *k_used = min(k, candidates per row); 1 <= k <= 256, else DST_ERR_ARG; a square set of fewer
+ * than 2 records gives DST_OK with *k_used = 0.  Outputs (host memory, row-major by row record, k_used entries each):
+ *   index    n_rows x k_used column-record indices (required)
+ *   tallies  n_rows x k_used x dst_tally_width(measure) DST_OUT_TALLY words, or NULL (dst_finalize -> the reference's bits)
+ *   values   n_rows x k_used DST_OUT_DISTANCE payloads (the key's source), or NULL
+ * cap_entries: room for n_rows x k_used entries in each non-NULL buffer, else DST_ERR_CAPACITY.  DST_ERR_STATE: a set is
+ * not uploaded or the widths differ.  Synchronous on the context's stream.  The pairs are computed once (square: the
+ * triangle), in row slabs of at most 2^25 pairs whose tallies are merged into device-resident lists n_rows x k.
+ * Single GPU, loaded sets only (not dst_stream). */
+int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, uint32_t k, uint32_t *index,
+                uint32_t *tallies, void *values, size_t cap_entries, uint32_t *k_used);
 /* Page-locked host memory for the *_host forms' output buffers (copy-back by DMA at link speed instead
  * of through a pageable bounce buffer).  Free with dst_host_free. */
 int dst_host_alloc(size_t bytes, void **ptr);
