@@ -8,14 +8,16 @@
 // replaced by libdistance_hip.so through its C ABI; -t sizes the host formatting pool and -b is
 // accepted — neither changes the output, as in the reference (src/lib.rs:919-1154).
 // Extra flags: --gpus N (default 1) / --devices LIST, --slab-pairs P (result slab size), --nearest K (the K nearest records
-// of every record instead of every pair: dst_nearest).
+// of every record instead of every pair: dst_nearest), --clusters T (single-linkage clusters at threshold T: dst_clusters).
 //
 // Exactness: the GPU returns integer site tallies; f64 finalisation is dst_finalize() on the host
 // (reference operation order, glibc log/sqrt), so the printed digits do not depend on the device.
 #include <algorithm>
 #include <atomic>
+#include <cctype>
 #include <cerrno>
 #include <chrono>
+#include <cmath>
 #include <condition_variable>
 #include <csignal>
 #include <cstdio>
@@ -103,6 +105,9 @@ void print_help()
         "      --devices <list>         Explicit device ordinals, e.g. 0,1,2,3 (overrides --gpus)\n"
         "      --nearest <k>            Print only the k (1-256) nearest records of every record: of the same file with one "
         "input, of the second file with two. One GPU, no --stream\n"
+        "      --clusters <T>           Print the single-linkage cluster of every record instead of distances: records "
+        "within distance T (a number >= 0) of each other share a cluster, numbered from 1 in order of first record. One "
+        "input, one GPU, no --stream or --nearest\n"
         "  -h, --help                   Print help\n"
         "  -V, --version                Print version");
 }
@@ -119,6 +124,8 @@ struct Args {
     size_t slab_pairs = (size_t)1 << 22;  // result slab: 4 Mi pairs pipelines GPU, formatters and writer well
     size_t nearest = 0;                   // --nearest k (0: every pair)
     bool has_nearest = false;
+    double clusters = 0;                  // --clusters T
+    bool has_clusters = false;
     std::string selftest;
 };
 
@@ -207,6 +214,18 @@ Args parse_args(int argc, char **argv)
             if (a.nearest < 1 || a.nearest > 256)
                 die_usage("invalid value '" + v + "' for '--nearest <k>': " + v + " is not in 1..=256");
             a.has_nearest = true;
+        } else if (arg == "--clusters" || arg.rfind("--clusters=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--clusters <T>");
+            // the whole word is the number: strtod, nothing left over, not NaN, not negative
+            char *end = nullptr;
+            errno = 0;
+            const double t = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
+            if (v.empty() || end != v.c_str() + v.size() || t != t || std::isspace((unsigned char)v[0]))
+                die_usage("invalid value '" + v + "' for '--clusters <T>': not a number");
+            if (t < 0)
+                die_usage("invalid value '" + v + "' for '--clusters <T>': the threshold must not be negative");
+            a.clusters = t;
+            a.has_clusters = true;
         } else if (arg == "--host-selftest") {
             a.selftest = value_of(k, arg, "--host-selftest <what>");
         } else {
@@ -219,6 +238,15 @@ Args parse_args(int argc, char **argv)
         die_usage("the argument '--nearest <k>' cannot be used with '--stream <stream>'");
     if (a.has_nearest && (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1)))
         die_usage(std::string("the argument '--nearest <k>' cannot be used with '") +
+                  (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
+    if (a.has_clusters && a.has_stream)
+        die_usage("the argument '--clusters <T>' cannot be used with '--stream <stream>'");
+    if (a.has_clusters && a.has_nearest)
+        die_usage("the argument '--clusters <T>' cannot be used with '--nearest <k>'");
+    if (a.has_clusters && a.flag_inputs.size() + a.pos_inputs.size() > 1)
+        die_usage("the argument '--clusters <T>' takes one input alignment, not two");
+    if (a.has_clusters && (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1)))
+        die_usage(std::string("the argument '--clusters <T>' cannot be used with '") +
                   (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
     if (dst_measure_from_name(a.measure.c_str()) < 0)
         die_usage("invalid value '" + a.measure + "' for '--measure <measure>'\n  [possible values: n, n_high, raw, "
@@ -1048,6 +1076,32 @@ void write_nearest(const Ctx &gpu, const std::vector<Alignment> &loaded, const s
     wr.write(out.data(), out.size());
 }
 
+// --clusters: one line per record in input order, "id, cluster", from dst_clusters' labels (the smallest record of the
+// cluster); clusters are numbered from 1 in order of their first record, which is the record its label names.
+void write_clusters(const Ctx &gpu, const Alignment &set, int measure, double threshold, Writer &wr)
+{
+    std::vector<uint32_t> label(std::max<size_t>(set.n, 1)), number(std::max<size_t>(set.n, 1), 0);
+    uint64_t n_clusters = 0, links = 0;
+    gpu.check(dst_clusters(gpu.h, measure, threshold, 0, label.data(), set.n, &n_clusters, &links), "clusters");
+    static const char header[] = "sequence\tcluster\n";
+    wr.write(header, sizeof header - 1);
+    std::string out;
+    uint32_t next = 0;
+    for (size_t i = 0; i < set.n; ++i) {
+        if (label[i] == i)
+            number[i] = ++next;
+        out += set.ids[i];
+        out += '\t';
+        out += std::to_string(number[label[i]]);
+        out += '\n';
+        if (out.size() >= ((size_t)1 << 20)) {
+            wr.write(out.data(), out.size());
+            out.clear();
+        }
+    }
+    wr.write(out.data(), out.size());
+}
+
 int host_selftest(const Args &a)
 {
     if (a.selftest == "fasta") {  // parse stdin, print one line per record
@@ -1260,12 +1314,15 @@ int main(int argc, char **argv)
 
     timer.mark("upload + pack + counts");
     static const char header[] = "sequence1\tsequence2\tdistance\n";  // src/lib.rs:613
-    wr.write(header, sizeof header - 1);
+    if (!a.has_clusters)
+        wr.write(header, sizeof header - 1);
 
     Job job;
     job.measure = measure;
     job.fmt_threads = std::max<size_t>(1, threads / (size_t)G);
-    if (a.has_nearest) {
+    if (a.has_clusters) {
+        write_clusters(gpus[0], loaded[0], measure, a.clusters, wr);
+    } else if (a.has_nearest) {
         write_nearest(gpus[0], loaded, counts, measure, (uint32_t)a.nearest, wr);
     } else if (!stream_fh) {
         // ---- load(): src/lib.rs:367-474 -------------------------------------------------------

@@ -1216,7 +1216,8 @@ int dst_destroy(dst_ctx *ctx)
                 (void)hipFree(b);
     for (void *b : {(void *)ctx->d_lut, (void *)ctx->d_total, (void *)ctx->scan_tmp, ctx->host_out, ctx->hot_tally, ctx->text_res,
                     ctx->text_num, (void *)ctx->text_len, (void *)ctx->text_scan, (void *)ctx->text_buf, (void *)ctx->text_flag, ctx->text_ties,
-                    (void *)ctx->ids[0].off, (void *)ctx->ids[0].chars, (void *)ctx->ids[1].off, (void *)ctx->ids[1].chars, ctx->nn_slab, ctx->nn_lists})
+                    (void *)ctx->ids[0].off, (void *)ctx->ids[0].chars, (void *)ctx->ids[1].off, (void *)ctx->ids[1].chars, ctx->nn_slab, ctx->nn_lists,
+                    ctx->cl_slab, ctx->cl_work})
         if (b)
             (void)hipFree(b);
     if (ctx->scratch)
@@ -1798,6 +1799,98 @@ int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slo
         HIP_TRY(ctx, hipMemcpyAsync(tallies, nl.tal, tal_bytes, hipMemcpyDeviceToHost, stream));
     HIP_TRY(ctx, hipStreamSynchronize(stream));
     *k_used = ku;
+    return DST_OK;
+}
+
+int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs, uint32_t *label, size_t cap,
+                 uint64_t *n_clusters, uint64_t *links)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (n_clusters)
+        *n_clusters = 0;
+    if (links)
+        *links = 0;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (std::isnan(threshold))
+        return fail(ctx, DST_ERR_ARG, "threshold is NaN");
+    if (!label)
+        return fail(ctx, DST_ERR_ARG, "null label pointer");
+    DeviceSet &set = ctx->set[0];
+    if (!set.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    const uint64_t n = set.n;
+    if (n >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    if (cap < n)
+        return fail(ctx, DST_ERR_CAPACITY, "cap is below the set's record count");
+    // the threshold as a payload: int64 payloads link when v <= floor(T) (clamped to the int64 range); below -2^63
+    // nothing links
+    uint64_t t_bits;
+    bool any = true;
+    if (measure_is_int(measure)) {
+        const double f = std::floor(threshold);
+        int64_t t;
+        if (f >= 9223372036854775808.0)
+            t = INT64_MAX;
+        else if (f < -9223372036854775808.0) {
+            t = INT64_MIN;
+            any = false;
+        } else
+            t = (int64_t)f;
+        t_bits = (uint64_t)t;
+    } else {
+        std::memcpy(&t_bits, &threshold, 8);
+    }
+    if (n < 2) {
+        if (n == 1)
+            label[0] = 0;
+        if (n_clusters)
+            *n_clusters = n;
+        return DST_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const std::vector<RowSlab> slabs = cut_row_slabs(true, n, n, max_pairs ? max_pairs : kClusterSlabPairs);
+    uint64_t biggest = 0;
+    for (const RowSlab &s : slabs)
+        biggest = std::max(biggest, s.pairs);
+    const size_t parent_bytes = (n * 4 + 255) / 256 * 256;
+    HIP_TRY(ctx, hipStreamSynchronize(stream));   // (the grow-only buffers of an earlier call: nothing reads them now)
+    int rc = DST_OK;
+    if (any)
+        rc = ensure_bytes(ctx, &ctx->cl_slab, &ctx->cl_slab_bytes, std::max<size_t>(dst_out_bytes(measure, DST_OUT_DISTANCE, biggest), 256));
+    if (!rc)
+        rc = ensure_bytes(ctx, &ctx->cl_work, &ctx->cl_work_bytes, parent_bytes + 8);
+    if (rc)
+        return rc;
+    uint32_t *parent = static_cast<uint32_t *>(ctx->cl_work);
+    unsigned long long *d_links = reinterpret_cast<unsigned long long *>(static_cast<char *>(ctx->cl_work) + parent_bytes);
+    HIP_TRY(ctx, launch_clusters_init(parent, n, d_links, stream));
+    for (size_t k = 0; any && k < slabs.size(); ++k) {
+        const RowSlab &s = slabs[k];
+        // the slab's pairs, each once (the triangle), as DST_OUT_DISTANCE payloads
+        rc = run_sets(ctx, measure, true, set, set, s.rb, s.re, DST_OUT_DISTANCE, ctx->cl_slab, ctx->cl_slab_bytes,
+                      (void *)stream);
+        if (rc)
+            return rc;
+        // on the context's stream, behind the slab's pair kernel (and the previous slab's unions)
+        HIP_TRY(ctx, launch_clusters_link(measure, static_cast<const uint64_t *>(ctx->cl_slab), s.first, n, s.rb, s.re, t_bits,
+                                          parent, d_links, stream));
+    }
+    HIP_TRY(ctx, launch_clusters_final(parent, n, stream));
+    uint64_t h_links = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(label, parent, n * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&h_links, d_links, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    uint64_t roots = 0;
+    for (uint64_t i = 0; i < n; ++i)
+        roots += label[i] == i;
+    if (n_clusters)
+        *n_clusters = roots;
+    if (links)
+        *links = h_links;
     return DST_OK;
 }
 

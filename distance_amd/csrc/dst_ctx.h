@@ -95,6 +95,9 @@ struct dst_ctx {
     // dst_nearest: the slab's DST_OUT_TALLY scratch and the running lists (grow-only)
     void *nn_slab = nullptr, *nn_lists = nullptr;
     size_t nn_slab_bytes = 0, nn_lists_bytes = 0;
+    // dst_clusters: the slab's DST_OUT_DISTANCE scratch and the parent array + link counter (grow-only)
+    void *cl_slab = nullptr, *cl_work = nullptr;
+    size_t cl_slab_bytes = 0, cl_work_bytes = 0;
     // HIP events around the pair kernel ([0]) and the pack kernel ([1]) of the most recent launches, recorded on the launch
     // stream: a ring, so that a caller timing many steps reads them ONCE at the end (dst_kernel_ms_mean) instead of
     // waiting for the device after every step

@@ -314,5 +314,22 @@ __device__ __attribute__((noinline)) double finalize_pair_call(uint32_t o0, uint
     return finalize_pair<MEASURE>(o, qc, tc);
 }
 
+// the sort key of a DST_OUT_DISTANCE payload (dst_nearest's order, dst_clusters' threshold test): int64 -> offset
+// binary; f64 -> the order-preserving bit flip, every NaN ~0 (after +inf, equal to each other), -0.0 the key of +0.0
+template <bool INT>
+__device__ __forceinline__ uint64_t nn_key(uint64_t bits)
+{
+    if constexpr (INT) {
+        return bits ^ 0x8000000000000000ull;
+    } else {
+        const uint64_t mag = bits & 0x7FFFFFFFFFFFFFFFull;
+        if (mag > 0x7FF0000000000000ull)
+            return ~0ull;
+        if (mag == 0)
+            return 0x8000000000000000ull;
+        return (bits >> 63) ? ~bits : bits | 0x8000000000000000ull;
+    }
+}
+
 }  // namespace
 }  // namespace dst

@@ -375,6 +375,20 @@ hipError_t launch_nearest_rows(int measure, bool square, const uint32_t *slab, u
 hipError_t launch_nearest_cols(int measure, const uint32_t *slab, uint64_t out_base, uint64_t n, uint64_t rb, uint64_t re,
                                const uint32_t *counts, const NearestLists &nl, hipStream_t stream);
 
+// ---- single-linkage clusters (dst_clusters.hip, driven by dst_clusters in dst_api.cpp) ------------------------------
+// A call cuts the rows of slot 0 into slabs of at most kClusterSlabPairs pairs (cut_row_slabs), runs each slab's triangle
+// into a DST_OUT_DISTANCE scratch and unites the endpoints of its links in a device-resident parent array (lock-free
+// union-find, parent[x] <= x).  2^25 pairs (256 MB of payloads): the link launch of a full slab has 2^25 / 2048 = 16384
+// workgroups of four waves, 64 per CU, so every CU stays busy to the end of the slab; and a slab is one pair-kernel
+// launch, whose fixed cost is paid once per slab (2^24 measured slower at 50,000 records: DESIGN.md 3h).
+constexpr uint64_t kClusterSlabPairs = (uint64_t)1 << 25;
+hipError_t launch_clusters_init(uint32_t *parent, uint64_t n, unsigned long long *links, hipStream_t stream);
+// rows [rb, re) of the square, their payloads from slab entry tri_row_start(n, i) - out_base; t_bits: the threshold as a
+// payload (int64 for n / n_high, else f64 bits)
+hipError_t launch_clusters_link(int measure, const uint64_t *slab, uint64_t out_base, uint64_t n, uint64_t rb, uint64_t re,
+                                uint64_t t_bits, uint32_t *parent, unsigned long long *links, hipStream_t stream);
+hipError_t launch_clusters_final(uint32_t *parent, uint64_t n, hipStream_t stream);
+
 // ---- host-only logic (dst_host.cpp) ----------------------------------------------------------
 int tally_width(int measure);
 bool measure_is_int(int measure);

@@ -20,23 +20,6 @@ constexpr int kSlots = (int)(kNearestMaxK / 64);
 constexpr uint64_t kSentinelVal = 0x7FFFFFFFFFFFFFFFull;   // key ~0 for both the int64 and the f64 payloads
 constexpr uint32_t kSentinelIdx = 0xFFFFFFFFu;
 
-// the sort key of a DST_OUT_DISTANCE payload: int64 -> offset binary; f64 -> the order-preserving bit flip, every NaN
-// ~0 (after +inf, equal to each other), -0.0 the key of +0.0
-template <bool INT>
-__device__ __forceinline__ uint64_t nn_key(uint64_t bits)
-{
-    if constexpr (INT) {
-        return bits ^ 0x8000000000000000ull;
-    } else {
-        const uint64_t mag = bits & 0x7FFFFFFFFFFFFFFFull;
-        if (mag > 0x7FF0000000000000ull)
-            return ~0ull;
-        if (mag == 0)
-            return 0x8000000000000000ull;
-        return (bits >> 63) ? ~bits : bits | 0x8000000000000000ull;
-    }
-}
-
 __device__ __forceinline__ bool nn_less(uint64_t ka, uint32_t ia, uint64_t kb, uint32_t ib)
 {
     return ka < kb || (ka == kb && ia < ib);

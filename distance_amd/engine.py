@@ -322,6 +322,19 @@ class Engine:
         assert k_used.value == ku
         return (index, values, tal) if tallies else (index, values)
 
+    def clusters(self, measure, threshold: float, max_pairs: int = 0):
+        """Single-linkage clusters of slot 0 (dst_clusters): (labels uint32[n], links).  Records i < j are linked when the
+        pair's DST_OUT_DISTANCE payload v <= threshold (int measures: v <= floor(threshold); NaN never links);
+        labels[i] = the smallest record of i's cluster, links = the number of linked pairs.  max_pairs: the most pairs
+        of one row slab (0: the default)."""
+        m = _measure_id(measure)
+        n, _ = self.set_info(0)
+        labels = np.zeros(max(n, 1), np.uint32)   # (never a NULL label, also for an empty set)
+        n_clusters, links = C.c_uint64(), C.c_uint64()
+        self._check(self._lib.dst_clusters(self._h, m, float(threshold), int(max_pairs), labels.ctypes.data, n,
+                                           C.byref(n_clusters), C.byref(links)))
+        return labels[:n], int(links.value)
+
     # ---- runs into device memory (bench / multi-GPU) ------------------------------------------
     def run_square_device(self, measure, row_begin: int, row_end: int, d_out: int, capacity: int,
                           tallies: bool = False, stream: int | None = None, out_kind: int | None = None):

@@ -324,6 +324,29 @@ int dst_run_slabs(dst_ctx *ctx, int measure, int square, int row_slot, int col_s
  * Single GPU, loaded sets only (not dst_stream). */
 int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, uint32_t k, uint32_t *index,
                 uint32_t *tallies, void *values, size_t cap_entries, uint32_t *k_used);
+/* ---- single-linkage clusters ------------------------------------------------------------------- */
+/* Which records are linked within `threshold` differences (transmission clusters, duplicate groups at 0), computed next
+ * to the values on the GPU: one label per record, never a pair list.  One set (slot 0, n records).  Records i < j are
+ * linked when the pair's DST_OUT_DISTANCE payload v (the value dst_run_square returns, bit-identical on every path)
+ * satisfies v <= threshold:
+ *   n / n_high (int64):  as real numbers, v <= floor(threshold) (clamped to the int64 range; below -2^63 nothing links)
+ *   f64:                 IEEE v <= threshold, decided on dst_nearest's sort key: NaN never links, -0.0 links wherever
+ *                        +0.0 does, +inf links every pair whose value is not NaN
+ * A cluster is a connected component of the links; label[i] = the smallest record index in i's cluster, so the result is
+ * unique whatever order the pairs are met in.  jc69 / k80 / tn93 payloads are the pair kernels' series form, within 1e-15
+ * of the reference's value but not bitwise equal to it: a pair whose value lies that close to the threshold can be decided
+ * differently from a CPU computation.  raw, n and n_high are exact.
+ *   threshold   any non-NaN double (NaN: DST_ERR_ARG)
+ *   max_pairs   0: the default slab bound (2^25 pairs); else the most pairs of one row slab (at least one row per slab),
+ *               as in dst_run_slabs.  The result does not depend on it.
+ *   label       n labels (host memory, required); cap: its room in entries, below n DST_ERR_CAPACITY
+ *   n_clusters  the number of clusters, or NULL
+ *   links       the number of linked pairs i < j, exact, or NULL
+ * n < 2: the trivial labels and 0 links; n >= 2^32-1: DST_ERR_ARG.  DST_ERR_STATE: slot 0 is not uploaded; DST_ERR_ARG:
+ * an unknown measure or a NULL label.  Synchronous on the context's stream.  The pairs are computed once (the triangle),
+ * in row slabs whose payloads a lock-free union-find on the device consumes.  Single GPU, loaded set only (not dst_stream). */
+int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs, uint32_t *label, size_t cap,
+                 uint64_t *n_clusters, uint64_t *links);
 /* Page-locked host memory for the *_host forms' output buffers (copy-back by DMA at link speed instead
  * of through a pageable bounce buffer).  Free with dst_host_free. */
 int dst_host_alloc(size_t bytes, void **ptr);
