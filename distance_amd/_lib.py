@@ -106,6 +106,8 @@ _SIGS = {
     "dst_text_square": (C.c_int, [_vp, C.c_int, C.c_uint64, C.c_uint64, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dst_text_rect": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int, _vp, C.c_size_t,
                                 C.POINTER(C.c_size_t)]),
+    "dst_text_matrix": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_int, _vp,
+                                  C.c_size_t, C.POINTER(C.c_size_t)]),
 }
 
 _lib = None

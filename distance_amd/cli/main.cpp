@@ -8,7 +8,8 @@
 // replaced by libdistance_hip.so through its C ABI; -t sizes the host formatting pool and -b is
 // accepted — neither changes the output, as in the reference (src/lib.rs:919-1154).
 // Extra flags: --gpus N (default 1) / --devices LIST, --slab-pairs P (result slab size), --nearest K (the K nearest records
-// of every record instead of every pair: dst_nearest), --clusters T (single-linkage clusters at threshold T: dst_clusters).
+// of every record instead of every pair: dst_nearest), --clusters T (single-linkage clusters at threshold T: dst_clusters),
+// --matrix tsv|phylip (a square or rectangular distance matrix instead of the long form: dst_text_matrix).
 //
 // Exactness: the GPU returns integer site tallies; f64 finalisation is dst_finalize() on the host
 // (reference operation order, glibc log/sqrt), so the printed digits do not depend on the device.
@@ -108,6 +109,9 @@ void print_help()
         "      --clusters <T>           Print the single-linkage cluster of every record instead of distances: records "
         "within distance T (a number >= 0) of each other share a cluster, numbered from 1 in order of first record. One "
         "input, one GPU, no --stream or --nearest\n"
+        "      --matrix <format>        Print a distance matrix instead of one line per pair: tsv (one or two inputs, rows "
+        "from the first, columns from the last) or phylip (relaxed PHYLIP, one input). Not in stream, nearest or "
+        "clusters mode\n"
         "  -h, --help                   Print help\n"
         "  -V, --version                Print version");
 }
@@ -126,6 +130,7 @@ struct Args {
     bool has_nearest = false;
     double clusters = 0;                  // --clusters T
     bool has_clusters = false;
+    int matrix = -1;                      // --matrix: DST_MATRIX_TSV / DST_MATRIX_PHYLIP (-1: the long form)
     std::string selftest;
 };
 
@@ -226,6 +231,14 @@ Args parse_args(int argc, char **argv)
                 die_usage("invalid value '" + v + "' for '--clusters <T>': the threshold must not be negative");
             a.clusters = t;
             a.has_clusters = true;
+        } else if (arg == "--matrix" || arg.rfind("--matrix=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--matrix <format>");
+            if (v == "tsv")
+                a.matrix = DST_MATRIX_TSV;
+            else if (v == "phylip")
+                a.matrix = DST_MATRIX_PHYLIP;
+            else
+                die_usage("invalid value '" + v + "' for '--matrix <format>'\n  [possible values: tsv, phylip]");
         } else if (arg == "--host-selftest") {
             a.selftest = value_of(k, arg, "--host-selftest <what>");
         } else {
@@ -248,6 +261,14 @@ Args parse_args(int argc, char **argv)
     if (a.has_clusters && (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1)))
         die_usage(std::string("the argument '--clusters <T>' cannot be used with '") +
                   (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
+    if (a.matrix >= 0 && a.has_stream)
+        die_usage("the argument '--matrix <format>' cannot be used with '--stream <stream>'");
+    if (a.matrix >= 0 && a.has_nearest)
+        die_usage("the argument '--matrix <format>' cannot be used with '--nearest <k>'");
+    if (a.matrix >= 0 && a.has_clusters)
+        die_usage("the argument '--matrix <format>' cannot be used with '--clusters <T>'");
+    if (a.matrix == DST_MATRIX_PHYLIP && a.flag_inputs.size() + a.pos_inputs.size() > 1)
+        die_usage("the argument '--matrix phylip' takes one input alignment (a square matrix), not two");
     if (dst_measure_from_name(a.measure.c_str()) < 0)
         die_usage("invalid value '" + a.measure + "' for '--measure <measure>'\n  [possible values: n, n_high, raw, "
                   "jc69, k80, tn93]");
@@ -743,6 +764,7 @@ struct Job {
     const uint32_t *row_counts = nullptr, *col_counts = nullptr;  // tn93 {A,T,G,C}
     size_t fmt_threads = 1;
     bool gpu_text = false;            // the GPU writes the TSV lines itself (dst_text_*); the host only writes them out
+    int matrix = -1;                  // >= 0: rows of a distance matrix in this layout (dst_matrix_style), every column
 };
 
 // tallies -> TSV text, in canonical order, split over the formatting pool (-t)
@@ -868,6 +890,56 @@ void format_slab(const Job &job, Slab &slab)
     }
 }
 
+// tallies of whole matrix rows (every column, the slab's rectangle) -> "<id>" then "<sep><value>" per column, then '\n':
+// each cell the text the long form prints for its canonical pair (square: (min, max), tn93 counts in that order)
+void format_matrix_slab(const Job &job, Slab &slab)
+{
+    const int w = dst_tally_width(job.measure);
+    const uint64_t ncols = job.cols->n;
+    const uint64_t rows = slab.re - slab.rb;
+    const size_t T = std::max<size_t>(1, std::min<size_t>(job.fmt_threads, rows));
+    const bool is_int = job.measure == DST_N || job.measure == DST_N_HIGH;
+    const char sep = job.matrix == DST_MATRIX_PHYLIP ? ' ' : '\t';
+    slab.text.clear();
+    slab.text.resize(T);
+    auto work = [&](size_t k) {
+        TextBuf &out = slab.text[k];
+        const uint64_t r0 = slab.rb + rows * k / T, r1 = slab.rb + rows * (k + 1) / T;
+        out.ensure((size_t)(r1 - r0) * (ncols * 16 + 64) + 64);
+        for (uint64_t i = r0; i < r1; ++i) {
+            const std::string &id = job.rows->ids[i];
+            out.ensure(id.size() + 1);
+            std::memcpy(out.p.get() + out.len, id.data(), id.size());
+            out.len += id.size();
+            for (uint64_t j = 0; j < ncols; ++j) {
+                const uint32_t *tl = &slab.tallies[((i - slab.rb) * ncols + j) * w];
+                const uint64_t q = job.square ? std::min(i, j) : i, t = job.square ? std::max(i, j) : j;
+                double f = 0;
+                int64_t iv = 0;
+                dst_finalize(job.measure, tl, job.row_counts ? job.row_counts + 4 * q : nullptr,
+                             job.col_counts ? job.col_counts + 4 * t : nullptr, &f, &iv);
+                out.ensure(1 + cli::kFixed12Max + 1);
+                char *o = out.p.get() + out.len;
+                *o++ = sep;
+                o += is_int ? cli::fmt_i64(iv, o) : cli::fmt_fixed12(f, o);
+                out.len = (size_t)(o - out.p.get());
+            }
+            out.ensure(1);
+            out.p.get()[out.len++] = '\n';
+        }
+    };
+    if (T == 1) {
+        work(0);
+    } else {
+        std::vector<std::thread> th;
+        for (size_t k = 1; k < T; ++k)
+            th.emplace_back(work, k);
+        work(0);
+        for (auto &t : th)
+            t.join();
+    }
+}
+
 // rows [0, n_rows) cut into slabs of <= max_pairs pairs (at least one row each)
 std::vector<std::pair<uint64_t, uint64_t>> make_slabs(bool square, uint64_t n_rows, uint64_t n_cols, uint64_t max_pairs)
 {
@@ -896,7 +968,10 @@ std::vector<std::pair<uint64_t, uint64_t>> make_slabs(bool square, uint64_t n_ro
 //   the calling thread: writes slabs strictly in canonical order (gather_write's idx re-ordering).
 void run_slabs(std::vector<Ctx> &gpus, const Job &job, int row_slot, int col_slot, uint64_t max_pairs, Writer &wr)
 {
-    const auto slabs = make_slabs(job.square, job.rows->n, job.cols->n, max_pairs);
+    // a matrix has every column in every row (the square's both triangles and diagonal): slabs of whole rows of cells
+    const bool matrix = job.matrix >= 0;
+    const bool tri = job.square && !matrix;   // the long form's triangle
+    const auto slabs = make_slabs(tri, job.rows->n, job.cols->n, max_pairs);
     const int w = dst_tally_width(job.measure);
     std::mutex mu;
     std::condition_variable cv;
@@ -918,12 +993,16 @@ void run_slabs(std::vector<Ctx> &gpus, const Job &job, int row_slot, int col_slo
     for (const auto &id : job.cols->ids)
         col_id_max = std::max(col_id_max, id.size());
     // every text buffer has the size of the largest slab (ids + number + separators per line)
-    uint64_t slab_pairs_max = 0;
-    for (const auto &sl : slabs)
-        slab_pairs_max = std::max<uint64_t>(slab_pairs_max, job.square ? dst_square_row_start(job.cols->n, sl.second) -
-                                                                              dst_square_row_start(job.cols->n, sl.first)
-                                                                        : (sl.second - sl.first) * job.cols->n);
-    const size_t text_bytes = (size_t)slab_pairs_max * (row_id_max + col_id_max + 34) + 64;
+    uint64_t slab_pairs_max = 0, slab_rows_max = 0;
+    for (const auto &sl : slabs) {
+        slab_pairs_max = std::max<uint64_t>(slab_pairs_max, tri ? dst_square_row_start(job.cols->n, sl.second) -
+                                                                       dst_square_row_start(job.cols->n, sl.first)
+                                                                 : (sl.second - sl.first) * job.cols->n);
+        slab_rows_max = std::max<uint64_t>(slab_rows_max, sl.second - sl.first);
+    }
+    // matrix: separator + number per cell, id + '\n' per row
+    const size_t text_bytes = matrix ? (size_t)slab_pairs_max * 33 + (size_t)slab_rows_max * (row_id_max + 1) + 64
+                                     : (size_t)slab_pairs_max * (row_id_max + col_id_max + 34) + 64;
     if (job.gpu_text && !slabs.empty())
         pool.prewarm(std::min(window, slabs.size()), text_bytes);
 
@@ -939,8 +1018,8 @@ void run_slabs(std::vector<Ctx> &gpus, const Job &job, int row_slot, int col_slo
             auto s = std::make_unique<Slab>();
             s->rb = slabs[k].first;
             s->re = slabs[k].second;
-            const uint64_t pairs = job.square ? dst_square_row_start(job.cols->n, s->re) - dst_square_row_start(job.cols->n, s->rb)
-                                              : (s->re - s->rb) * job.cols->n;
+            const uint64_t pairs = tri ? dst_square_row_start(job.cols->n, s->re) - dst_square_row_start(job.cols->n, s->rb)
+                                       : (s->re - s->rb) * job.cols->n;
             if (job.gpu_text) {
                 // ids + number + separators per line; a slab the device formatter declines (a value without a short
                 // text, a slab beyond its limits) is formatted on the host like before
@@ -949,9 +1028,11 @@ void run_slabs(std::vector<Ctx> &gpus, const Job &job, int row_slot, int col_slo
                 char *buf = reinterpret_cast<char *>(pool.acquire(text_bytes, &cap));
                 if (!buf)
                     gpus[g].check(DST_ERR_NOMEM, "pinned host buffer");
-                const int trc = job.square ? dst_text_square(gpus[g].h, job.measure, s->rb, s->re, buf, cap, &len)
-                                           : dst_text_rect(gpus[g].h, job.measure, row_slot, col_slot, s->rb, s->re, 0, buf,
-                                                           cap, &len);
+                const int trc = matrix ? dst_text_matrix(gpus[g].h, job.measure, job.square ? 1 : 0, row_slot, col_slot, s->rb,
+                                                         s->re, job.matrix, buf, cap, &len)
+                                : job.square ? dst_text_square(gpus[g].h, job.measure, s->rb, s->re, buf, cap, &len)
+                                             : dst_text_rect(gpus[g].h, job.measure, row_slot, col_slot, s->rb, s->re, 0, buf,
+                                                             cap, &len);
                 if (trc == DST_OK) {
                     s->gtext = buf;
                     s->gtext_len = len;
@@ -971,10 +1052,11 @@ void run_slabs(std::vector<Ctx> &gpus, const Job &job, int row_slot, int col_slo
             s->tallies = pool.acquire(std::max<size_t>(n_tallies, 1) * 4, &s->tallies_cap);
             if (!s->tallies)
                 gpus[g].check(DST_ERR_NOMEM, "pinned host buffer");
-            const int rc = job.square ? dst_run_square_host(gpus[g].h, job.measure, s->rb, s->re, DST_OUT_TALLY,
-                                                            s->tallies, n_tallies * 4)
-                                      : dst_run_rect_host(gpus[g].h, job.measure, row_slot, col_slot, s->rb, s->re,
-                                                          DST_OUT_TALLY, s->tallies, n_tallies * 4);
+            // (a square matrix: the set against itself as a rectangle, every column of the rows)
+            const int rc = tri ? dst_run_square_host(gpus[g].h, job.measure, s->rb, s->re, DST_OUT_TALLY, s->tallies,
+                                                     n_tallies * 4)
+                               : dst_run_rect_host(gpus[g].h, job.measure, job.square ? 0 : row_slot, job.square ? 0 : col_slot,
+                                                   s->rb, s->re, DST_OUT_TALLY, s->tallies, n_tallies * 4);
             gpus[g].check(rc, "run");
             {
                 std::lock_guard<std::mutex> lk(mu);
@@ -997,7 +1079,10 @@ void run_slabs(std::vector<Ctx> &gpus, const Job &job, int row_slot, int col_slo
                 item = std::move(computed.front());
                 computed.pop_front();
             }
-            format_slab(fjob, *item.second);
+            if (matrix)
+                format_matrix_slab(fjob, *item.second);
+            else
+                format_slab(fjob, *item.second);
             pool.release(item.second->tallies, item.second->tallies_cap);
             item.second->tallies = nullptr;
             {
@@ -1314,8 +1399,21 @@ int main(int argc, char **argv)
 
     timer.mark("upload + pack + counts");
     static const char header[] = "sequence1\tsequence2\tdistance\n";  // src/lib.rs:613
-    if (!a.has_clusters)
+    if (a.matrix == DST_MATRIX_TSV) {
+        // an empty corner cell, then the column ids (the last input's records)
+        std::string h;
+        for (const auto &id : loaded.back().ids) {
+            h += '\t';
+            h += id;
+        }
+        h += '\n';
+        wr.write(h.data(), h.size());
+    } else if (a.matrix == DST_MATRIX_PHYLIP) {
+        const std::string h = std::to_string(loaded[0].n) + "\n";
+        wr.write(h.data(), h.size());
+    } else if (!a.has_clusters) {
         wr.write(header, sizeof header - 1);
+    }
 
     Job job;
     job.measure = measure;
@@ -1327,6 +1425,7 @@ int main(int argc, char **argv)
     } else if (!stream_fh) {
         // ---- load(): src/lib.rs:367-474 -------------------------------------------------------
         job.square = loaded.size() == 1;
+        job.matrix = a.matrix;
         job.rows = &loaded[0];
         job.cols = &loaded.back();
         job.row_counts = measure == DST_TN93 ? counts[0].data() : nullptr;

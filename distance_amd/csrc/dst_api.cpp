@@ -614,6 +614,10 @@ int ensure_index(dst_ctx *ctx, DeviceSet &s, DeviceSet &refset, bool want_sites,
     const bool from_pack = &s == &refset && s.rec.pre_valid && s.rec.pre_epoch == s.epoch;
     if (!from_pack) {
         s.runs.active = false;   // lists from the planes keep every entry (index_kernel knows no run chunks)
+        // the pack's list counts (pre_cold / pre_hot) are the STRIPPED ones: a later square run on this set must not
+        // take them for lists that now hold the run chunks' entries too (a row set of a rectangle ends here)
+        if (s.runs.n_run != 0)
+            s.rec.pre_valid = false;
         rc = ensure_planes(ctx, s, stream);
         if (rc)
             return rc;

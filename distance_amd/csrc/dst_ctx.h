@@ -75,7 +75,7 @@ struct dst_ctx {
     uint32_t *text_len = nullptr;  // line lengths -> offsets
     uint32_t *text_scan = nullptr;
     char *text_buf = nullptr;
-    uint32_t *text_flag = nullptr;   // [0] a value without a short text, [1] near ties noted
+    uint32_t *text_flag = nullptr;   // [0] a value without a short text, [1] near ties noted, [2] placed (dst_text_matrix)
     void *text_ties = nullptr;       // the slab's near ties (dst_text.hip: NearTie), device and page-locked host copies
     void *text_ties_host = nullptr;
     size_t text_res_bytes = 0, text_num_bytes = 0, text_len_bytes = 0, text_scan_bytes = 0, text_buf_bytes = 0;

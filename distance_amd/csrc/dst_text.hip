@@ -25,6 +25,9 @@
 // operation order) and overwrites their digits in the text it has just received.  Every other line is provably the
 // same text for any value within the guard.  raw needs none of this (fin_raw is the IEEE division bit for bit), nor
 // do the integers.
+//
+// dst_text_matrix lays the same cells out as a distance matrix (rows of "<id>" then "<sep><value>" per column): see
+// matrix_kernel below.
 #include "dst_ctx.h"
 #include "dst_device.hpp"
 
@@ -161,6 +164,9 @@ __device__ __forceinline__ bool slab_pair(const SlabShape &sh, uint32_t &row, ui
     }
     return true;
 }
+
+// ctx->text_flag: [0] a value without a short text, [1] near ties noted, [2] near ties placed (dst_text_matrix)
+constexpr int kTextFlagWords = 4;
 
 // one near tie: what the host needs to re-finalise the pair and to find its digits in the text
 struct NearTie {
@@ -310,8 +316,8 @@ int patch_near_ties(dst_ctx *ctx, int measure, int row_slot, int col_slot, int s
             char text[40];
             const int new_len = dst_format_distance(measure, f, 0, text, sizeof text);
             char *at = out + e.at;
-            uint32_t old_len = 0;
-            while (at[old_len] != '\n')
+            uint32_t old_len = 0;   // a number ends the line (long form) or its matrix cell ('\t' / ' ' / '\n')
+            while (at[old_len] != '\n' && at[old_len] != '\t' && at[old_len] != ' ')
                 ++old_len;
             if ((uint32_t)new_len == old_len) {
                 if (std::memcmp(at, text, old_len) != 0) {
@@ -405,7 +411,7 @@ int text_common(dst_ctx *ctx, int measure, bool square, int row_slot, int col_sl
     if (!rc && ties_cap)
         rc = ensure_bytes(ctx, &ctx->text_ties, &ctx->text_ties_bytes, (size_t)ties_cap * sizeof(NearTie));
     if (!rc && !ctx->text_flag)
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->text_flag, 2 * sizeof(uint32_t)));
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->text_flag, kTextFlagWords * sizeof(uint32_t)));
     if (!rc && !ctx->d_total)
         HIP_TRY(ctx, hipMalloc((void **)&ctx->d_total, 2 * sizeof(unsigned long long)));
     if (rc)
@@ -504,6 +510,315 @@ int text_common(dst_ctx *ctx, int measure, bool square, int row_slot, int col_sl
     return DST_OK;
 }
 
+// ---- dst_text_matrix: whole rows of a distance matrix, "<id>" then "<sep><value>" per column, then '\n'
+//
+//   matrix_kernel<.., false>   workgroup (c, r): the text length of cells 256 c .. 256 c + 255 of slab row r (plus the
+//                              row's id in chunk 0 and its '\n' in the last chunk) -> one word per chunk; counts the
+//                              values without a short text and the near ties
+//   (scan)                     exclusive scan of the chunk lengths -> every chunk's offset in the text
+//   matrix_kernel<.., true>    the same workgroup formats its cells again, each thread into its own 32-byte LDS slot,
+//                              block-scans the lengths, packs the chunk's bytes in LDS at the text's alignment modulo 16
+//                              and stores them with 16-byte stores (bytes at the two ends); notes each near tie's offset
+// No per-cell record goes to HBM: the slab's results are read twice and the text is written once.
+constexpr uint32_t kMatChunk = 256;   // cells per workgroup: one per thread
+
+struct MatShape {
+    uint64_t n_cols, row_begin;
+    uint32_t n_chunks;   // per row (>= 1: a row of no cells still has its id and '\n')
+    int square;          // rows and columns are one set: tn93 counts and near ties in canonical order (min, max)
+    int sep;             // '\t' or ' '
+};
+
+// exclusive scan over the 256 threads of the workgroup (4 waves of 64); *total: the sum
+__device__ __forceinline__ uint32_t block_scan256(uint32_t v, uint32_t *wsum, uint32_t *total)
+{
+    const uint32_t lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    uint32_t x = v;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const uint32_t y = __shfl_up(x, d, 64);
+        if (lane >= (uint32_t)d)
+            x += y;
+    }
+    if (lane == 63)
+        wsum[w] = x;
+    __syncthreads();
+    uint32_t before = 0, all = 0;
+#pragma unroll
+    for (uint32_t k = 0; k < 4; ++k) {
+        const uint32_t s = wsum[k];
+        before += k < w ? s : 0u;
+        all += s;
+    }
+    *total = all;
+    return before + x - v;
+}
+
+template <int SRC, class T, bool WRITE>
+__global__ __launch_bounds__(256) void matrix_kernel(const void *__restrict__ results, MatShape sh,
+                                                     const uint32_t *__restrict__ row_id_off, const char *__restrict__ row_ids,
+                                                     const uint32_t *__restrict__ row_counts,
+                                                     const uint32_t *__restrict__ col_counts,
+                                                     uint32_t *__restrict__ chunk_len,   // !WRITE: lengths; WRITE: offsets
+                                                     uint32_t *__restrict__ flags, NearTie *__restrict__ ties,
+                                                     uint32_t ties_cap, char *__restrict__ text)
+{
+    __shared__ __attribute__((aligned(16))) char slot[kMatChunk * 32];           // thread t's number at 32 t
+    __shared__ __attribute__((aligned(16))) char body[16 + kMatChunk * 32 + 16];  // the chunk's bytes, text alignment
+    __shared__ uint32_t wsum[4];
+    const uint32_t t = threadIdx.x;
+    const uint32_t row = (uint32_t)sh.row_begin + blockIdx.y;
+    const uint64_t col = (uint64_t)blockIdx.x * kMatChunk + t;
+    const uint64_t chunk = (uint64_t)blockIdx.y * sh.n_chunks + blockIdx.x;
+    const bool last = blockIdx.x + 1 == sh.n_chunks;
+    // canonical order of the pair: the square's (j, i) is its (i, j)
+    const uint32_t lo = sh.square && col < row ? (uint32_t)col : row;
+    const uint32_t hi = sh.square && col < row ? row : (uint32_t)col;
+    char *num = slot + 32 * t;
+    int len = 0;
+    bool ok = true, near = false;
+    uint32_t o[4] = {0, 0, 0, 0};
+    if (col < sh.n_cols) {
+        const uint64_t p = (uint64_t)blockIdx.y * sh.n_cols + col;   // the slab's rectangle of results
+        if constexpr (SRC == -1) {
+            const long long v = static_cast<const long long *>(results)[p];
+            if (v < 0) {
+                num[0] = '-';
+                len = 1 + put_u64((uint64_t)(-(v + 1)) + 1, num + 1);
+            } else {
+                len = put_u64((uint64_t)v, num);
+            }
+        } else if constexpr (SRC == -2) {
+            ok = put_fixed12(static_cast<const double *>(results)[p], num, len, near);
+            near = false;   // raw: the device's quotient IS the host's
+        } else {
+            constexpr int NT = SRC == DST_K80 ? 3 : SRC == DST_TN93 ? 4 : 2;
+            const T *tl = static_cast<const T *>(results) + p * NT;
+#pragma unroll
+            for (int k = 0; k < NT; ++k)
+                o[k] = tl[k];
+            uint4 qc = make_uint4(0, 0, 0, 0), tc = qc;
+            if constexpr (SRC == DST_TN93) {
+                qc = reinterpret_cast<const uint4 *>(row_counts)[lo];
+                tc = reinterpret_cast<const uint4 *>(col_counts)[hi];
+            }
+            ok = put_fixed12(finalize_pair<SRC, true>(o, qc, tc), num, len, near);
+        }
+        if (!ok)
+            len = 0;
+    }
+    const uint32_t l = col < sh.n_cols ? 1u + (uint32_t)len : 0u;   // separator + number
+    const uint32_t id_len = blockIdx.x == 0 ? row_id_off[row + 1] - row_id_off[row] : 0u;
+    if constexpr (!WRITE) {
+        if (!ok)
+            atomicOr(&flags[0], 1u);
+        if (near && ok)
+            atomicAdd(&flags[1], 1u);
+        uint32_t total = 0;
+        (void)block_scan256(l, wsum, &total);
+        if (t == 0)
+            chunk_len[chunk] = total + id_len + (last ? 1u : 0u);
+    } else {
+        uint32_t total = 0;
+        const uint32_t at = block_scan256(l, wsum, &total);
+        const uint64_t start = chunk_len[chunk];
+        for (uint32_t k = t; k < id_len; k += kMatChunk)
+            text[start + k] = row_ids[row_id_off[row] + k];
+        const uint64_t b0 = start + id_len;          // the chunk's first cell in the text
+        const uint32_t a = (uint32_t)(b0 & 15);      // ... and in `body`: the same address modulo 16
+        if (l) {
+            char *d = body + a + at;
+            d[0] = (char)sh.sep;
+            for (int k = 0; k < len; ++k)
+                d[1 + k] = num[k];
+        }
+        if (last && t == 0)
+            body[a + total] = '\n';
+        const uint32_t nb = total + (last ? 1u : 0u);
+        __syncthreads();
+        const uint32_t head = min(nb, (16u - a) & 15u);
+        if (t < head)
+            text[b0 + t] = body[a + t];
+        const uint32_t n16 = (nb - head) / 16;
+        for (uint32_t v = t; v < n16; v += kMatChunk)
+            *reinterpret_cast<uint4 *>(text + b0 + head + 16ull * v) = *reinterpret_cast<const uint4 *>(body + a + head + 16 * v);
+        const uint32_t tail = head + 16 * n16;
+        if (tail + t < nb)
+            text[b0 + tail + t] = body[a + tail + t];
+        if (near && ok) {
+            const uint32_t k = atomicAdd(&flags[2], 1u);
+            if (k < ties_cap) {
+                NearTie e;
+                e.row = lo;
+                e.col = hi;
+                e.at = (uint32_t)(b0 + at + 1);   // the number, after its separator
+                e.pre_len = 0;
+                e.t[0] = o[0], e.t[1] = o[1], e.t[2] = o[2], e.t[3] = o[3];
+                reinterpret_cast<uint4 *>(ties)[2 * k] = reinterpret_cast<const uint4 *>(&e)[0];
+                reinterpret_cast<uint4 *>(ties)[2 * k + 1] = reinterpret_cast<const uint4 *>(&e)[1];
+            }
+        }
+    }
+}
+
+int text_matrix(dst_ctx *ctx, int measure, bool square, int row_slot, int col_slot, uint64_t rb, uint64_t re, int style,
+                char *out, size_t cap, size_t *len)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (!len || (!out && cap))
+        return fail(ctx, DST_ERR_ARG, "null pointer");
+    *len = 0;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (style != DST_MATRIX_TSV && style != DST_MATRIX_PHYLIP)
+        return fail(ctx, DST_ERR_ARG, "unknown matrix style");
+    if (square) {
+        row_slot = col_slot = 0;
+    } else {
+        if (row_slot < 0 || row_slot > 1 || col_slot < 0 || col_slot > 1)
+            return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
+        if (row_slot == col_slot)
+            return fail(ctx, DST_ERR_ARG, "row_slot == col_slot: use the square form for one set");
+    }
+    DeviceSet &rows = ctx->set[row_slot], &cols = ctx->set[col_slot];
+    if (!rows.loaded || !cols.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    dst_ctx::Ids &rid = ctx->ids[row_slot];
+    if (!rid.off || rid.n != rows.n)
+        return fail(ctx, DST_ERR_STATE, "record ids of the set not given (dst_set_ids)");
+    if (rb > re || re > rows.n)
+        return fail(ctx, DST_ERR_ARG, "row range out of bounds");
+    if (re == rb)
+        return DST_OK;
+    const uint64_t cells = (re - rb) * cols.n;
+    if (cells >= (1ull << 31) || re - rb > 65535)
+        return fail(ctx, DST_ERR_ARG, "text slab too large (at most 2^31 cells and 65,535 rows per call)");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const uint32_t n_chunks = (uint32_t)std::max<uint64_t>(1, (cols.n + kMatChunk - 1) / kMatChunk);
+    const uint64_t n_words = (re - rb) * n_chunks;
+    const bool from_tallies = measure == DST_JC69 || measure == DST_K80 || measure == DST_TN93;
+    const bool tally16 = from_tallies && rows.len <= 65535;
+    const int res_kind = !from_tallies ? DST_OUT_DISTANCE : tally16 ? DST_OUT_TALLY16 : DST_OUT_TALLY;
+    const size_t res_bytes = dst_out_bytes(measure, res_kind, cells);
+    const uint32_t ties_cap = from_tallies ? (uint32_t)std::max<uint64_t>(4096, cells / 16) : 0;
+    int rc = ensure_bytes(ctx, &ctx->text_res, &ctx->text_res_bytes, std::max<size_t>(res_bytes, 16));
+    if (!rc)
+        rc = ensure_bytes(ctx, (void **)&ctx->text_len, &ctx->text_len_bytes, (n_words + 1) * sizeof(uint32_t));
+    if (!rc)
+        rc = ensure_bytes(ctx, (void **)&ctx->text_scan, &ctx->text_scan_bytes, scan_tmp_words(n_words + 1) * sizeof(uint32_t));
+    if (!rc && ties_cap)
+        rc = ensure_bytes(ctx, &ctx->text_ties, &ctx->text_ties_bytes, (size_t)ties_cap * sizeof(NearTie));
+    if (!rc && !ctx->text_flag)
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->text_flag, kTextFlagWords * sizeof(uint32_t)));
+    if (!rc && !ctx->d_total)
+        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_total, 2 * sizeof(unsigned long long)));
+    if (rc)
+        return rc;
+    if (measure == DST_TN93) {
+        // the base counts: on the device for matrix_kernel, on the host for the near ties
+        for (int slot : {row_slot, col_slot}) {
+            DeviceSet &s = ctx->set[slot];
+            rc = need_counts(ctx, s, stream);
+            if (rc)
+                return rc;
+            if (ctx->text_counts_epoch[slot] != s.epoch || ctx->text_counts[slot].size() != s.n * 4) {
+                ctx->text_counts[slot].resize(s.n * 4);
+                HIP_TRY(ctx, hipMemcpyAsync(ctx->text_counts[slot].data(), s.counts, s.n * 16, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(ctx, hipStreamSynchronize(stream));
+                ctx->text_counts_epoch[slot] = s.epoch;
+            }
+        }
+    }
+    // the square as a rectangle of the set against itself: both triangles and the diagonal in one run
+    rc = run_sets(ctx, measure, false, rows, cols, rb, re, res_kind, ctx->text_res, res_bytes, stream);
+    if (rc)
+        return rc;
+    const MatShape sh{cols.n, rb, n_chunks, square ? 1 : 0, style == DST_MATRIX_PHYLIP ? ' ' : '\t'};
+    const dim3 grid(n_chunks, (unsigned)(re - rb));
+    NearTie *d_ties = static_cast<NearTie *>(ctx->text_ties);
+    HIP_TRY(ctx, hipMemsetAsync(ctx->text_flag, 0, kTextFlagWords * sizeof(uint32_t), stream));
+    HIP_TRY(ctx, hipMemsetAsync(ctx->text_len + n_words, 0, sizeof(uint32_t), stream));
+    auto launch = [&](bool write) {
+#define DST_MATRIX(SRC, T)                                                                                                  \
+    do {                                                                                                                    \
+        if (write)                                                                                                          \
+            hipLaunchKernelGGL((matrix_kernel<SRC, T, true>), grid, dim3(kMatChunk), 0, stream, ctx->text_res, sh, rid.off, \
+                               rid.chars, rows.counts, cols.counts, ctx->text_len, ctx->text_flag, d_ties, ties_cap,        \
+                               ctx->text_buf);                                                                              \
+        else                                                                                                                \
+            hipLaunchKernelGGL((matrix_kernel<SRC, T, false>), grid, dim3(kMatChunk), 0, stream, ctx->text_res, sh,         \
+                               rid.off, rid.chars, rows.counts, cols.counts, ctx->text_len, ctx->text_flag, d_ties,         \
+                               ties_cap, ctx->text_buf);                                                                    \
+    } while (0)
+        if (measure_is_int(measure))
+            DST_MATRIX(-1, uint32_t);
+        else if (measure == DST_RAW)
+            DST_MATRIX(-2, uint32_t);
+        else if (measure == DST_JC69 && tally16)
+            DST_MATRIX(DST_JC69, uint16_t);
+        else if (measure == DST_JC69)
+            DST_MATRIX(DST_JC69, uint32_t);
+        else if (measure == DST_K80 && tally16)
+            DST_MATRIX(DST_K80, uint16_t);
+        else if (measure == DST_K80)
+            DST_MATRIX(DST_K80, uint32_t);
+        else if (tally16)
+            DST_MATRIX(DST_TN93, uint16_t);
+        else
+            DST_MATRIX(DST_TN93, uint32_t);
+#undef DST_MATRIX
+        return hipGetLastError();
+    };
+    HIP_TRY(ctx, launch(false));
+    // the offsets are 32-bit: a slab's text must stay below 4 GB (checked against the un-scanned total first)
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_total, 0, 2 * sizeof(unsigned long long), stream));
+    HIP_TRY(ctx, launch_sum2_u32(ctx->text_len, ctx->text_len, n_words, ctx->d_total, stream));
+    unsigned long long total = 0;
+    uint32_t flags[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(&total, ctx->d_total, sizeof total, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(flags, ctx->text_flag, sizeof flags, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (flags[0])
+        return fail(ctx, DST_ERR_STATE, "a value of this slab has no short {:.12} text (|v| >= 1.8e7): format it on the host");
+    const uint32_t n_ties = flags[1];
+    if (n_ties > ties_cap)
+        return fail(ctx, DST_ERR_STATE, "too many values of this slab lie near a rounding boundary of the 12th decimal: format it on the host");
+    if (total >= (1ull << 32))
+        return fail(ctx, DST_ERR_ARG, "text slab too large (4 GB of text per call)");
+    if (total > cap)
+        return fail(ctx, DST_ERR_CAPACITY, "text buffer too small for the requested rows");
+    rc = ensure_bytes(ctx, (void **)&ctx->text_buf, &ctx->text_buf_bytes, (size_t)total + 16);
+    if (rc)
+        return rc;
+    if (n_ties && ctx->text_ties_host_bytes < (size_t)n_ties * sizeof(NearTie)) {
+        if (ctx->text_ties_host)
+            HIP_TRY(ctx, hipHostFree(ctx->text_ties_host));
+        ctx->text_ties_host = nullptr;
+        ctx->text_ties_host_bytes = 0;
+        const size_t want = std::max<size_t>((size_t)n_ties * 2, 8192) * sizeof(NearTie);
+        HIP_TRY(ctx, hipHostMalloc(&ctx->text_ties_host, want, hipHostMallocDefault));
+        ctx->text_ties_host_bytes = want;
+    }
+    HIP_TRY(ctx, launch_exclusive_scan(ctx->text_len, n_words + 1, ctx->text_scan, stream));
+    HIP_TRY(ctx, launch(true));
+    uint32_t placed = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&placed, ctx->text_flag + 2, sizeof placed, hipMemcpyDeviceToHost, stream));
+    if (n_ties)
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->text_ties_host, d_ties, (size_t)n_ties * sizeof(NearTie), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(out, ctx->text_buf, (size_t)total, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (placed != n_ties)
+        return fail(ctx, DST_ERR_STATE, "near ties of the two text passes differ");
+    *len = (size_t)total;
+    ctx->text_near_ties += n_ties;
+    if (n_ties)
+        return patch_near_ties(ctx, measure, row_slot, col_slot, 0, static_cast<const NearTie *>(ctx->text_ties_host), n_ties,
+                               out, cap, len);
+    return DST_OK;
+}
+
 }  // namespace
 }  // namespace dst
 
@@ -559,6 +874,12 @@ int dst_text_rect(dst_ctx *ctx, int measure, int row_slot, int col_slot, uint64_
                   char *out, size_t capacity, size_t *len)
 {
     return text_common(ctx, measure, false, row_slot, col_slot, row_begin, row_end, swap_ids, out, capacity, len);
+}
+
+int dst_text_matrix(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, uint64_t row_begin, uint64_t row_end,
+                    int style, char *out, size_t capacity, size_t *len)
+{
+    return text_matrix(ctx, measure, square != 0, row_slot, col_slot, row_begin, row_end, style, out, capacity, len);
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@ FLOAT_MEASURES = ("raw", "jc69", "k80", "tn93")
 OUT_DISTANCE, OUT_TALLY, OUT_TALLY16 = 0, 1, 2
 FIN_CLOSE = 0x100
 PATHS = {"auto": 0, "dense": 1, "consensus": 2, "hybrid": 3}
+MATRIX_STYLES = {"tsv": 0, "phylip": 1}
 
 
 def _measure_id(measure) -> int:
@@ -383,6 +384,20 @@ class Engine:
         n = C.c_size_t(0)
         self._check(self._lib.dst_text_rect(self._h, _measure_id(measure), row_slot, col_slot, row_begin, row_end,
                                             int(swap_ids), C.addressof(buf), capacity, C.byref(n)))
+        return buf.raw[:n.value]
+
+    def text_matrix(self, measure, row_begin: int = 0, row_end: int | None = None, square: bool = True, row_slot: int = 0,
+                    col_slot: int = 1, style: str | int = "tsv", capacity: int = 1 << 26) -> bytes:
+        """Rows [row_begin, row_end) of a distance matrix, formatted on the GPU (dst_text_matrix): per row the id, then
+        a separator ('\\t' for "tsv", ' ' for "phylip") and the value for every column, then '\\n'; no header line.
+        square: slot 0 against itself, diagonal included; else row_slot x col_slot.  row_end None: every row."""
+        if row_end is None:
+            row_end = self.set_info(0 if square else row_slot)[0]
+        st = MATRIX_STYLES[style] if isinstance(style, str) else int(style)
+        buf = C.create_string_buffer(max(int(capacity), 1))
+        n = C.c_size_t(0)
+        self._check(self._lib.dst_text_matrix(self._h, _measure_id(measure), int(bool(square)), row_slot, col_slot,
+                                              row_begin, row_end, st, C.addressof(buf), capacity, C.byref(n)))
         return buf.raw[:n.value]
 
     def text_stats(self) -> tuple[int, int]:

@@ -413,6 +413,24 @@ int dst_text_square(dst_ctx *ctx, int measure, uint64_t row_begin, uint64_t row_
 int dst_text_rect(dst_ctx *ctx, int measure, int row_slot, int col_slot, uint64_t row_begin, uint64_t row_end,
                   int swap_ids, char *out, size_t capacity, size_t *len);
 
+typedef enum { DST_MATRIX_TSV = 0, DST_MATRIX_PHYLIP = 1 } dst_matrix_style;
+/* Rows [row_begin, row_end) of a distance matrix as text, formatted on the GPU: per row "<id>" then "<sep><value>" per
+ * column, then '\n' (sep '\t' for TSV, ' ' for PHYLIP); header lines are the caller's.  square != 0: slot 0 against
+ * itself, every column incl. the diagonal; square == 0: row_slot x col_slot, row_slot != col_slot.  Ids as for
+ * dst_text_* (dst_set_ids).
+ *
+ * Cell (i, j) is exactly the text dst_text_* prints for that pair (dst_format_distance of dst_finalize): square, both
+ * (i, j) and (j, i) are the canonical pair (min(i, j), max(i, j)) — tn93 takes the base counts in that order — so the
+ * matrix is symmetric byte for byte; the diagonal (i, i) is the measure of record i against itself (0 / 0.000000000000
+ * for a record with a resolved site, NaN for raw of a record without one: not a constant).  square == 0: cell (i, j) is
+ * row record i against column record j, as dst_text_rect prints it.  Near ties are handed to the host as for dst_text_*.
+ * Limits as for dst_text_*: at most 2^31 cells, 65,535 rows and 4 GB of text per call.  DST_ERR_CAPACITY: `capacity` is
+ * too small; DST_ERR_STATE: a set or its ids are missing, a value has no short text (|v| >= 1.8e7) or more than 1/16 of
+ * the cells are near ties (format those rows on the host); DST_ERR_ARG: a bad slot, range, style or measure, or
+ * square == 0 with equal slots. */
+int dst_text_matrix(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, uint64_t row_begin,
+                    uint64_t row_end, int style, char *out, size_t capacity, size_t *len);
+
 #ifdef __cplusplus
 }
 #endif
