@@ -9,7 +9,8 @@
 // accepted — neither changes the output, as in the reference (src/lib.rs:919-1154).
 // Extra flags: --gpus N (default 1) / --devices LIST, --slab-pairs P (result slab size), --nearest K (the K nearest records
 // of every record instead of every pair: dst_nearest), --clusters T (single-linkage clusters at threshold T: dst_clusters),
-// --matrix tsv|phylip (a square or rectangular distance matrix instead of the long form: dst_text_matrix).
+// --matrix tsv|phylip (a square or rectangular distance matrix instead of the long form: dst_text_matrix), --tree nj (the
+// neighbour-joining tree as one Newick line: dst_nj, dst_newick).
 //
 // Exactness: the GPU returns integer site tallies; f64 finalisation is dst_finalize() on the host
 // (reference operation order, glibc log/sqrt), so the printed digits do not depend on the device.
@@ -112,6 +113,8 @@ void print_help()
         "      --matrix <format>        Print a distance matrix instead of one line per pair: tsv (one or two inputs, rows "
         "from the first, columns from the last) or phylip (relaxed PHYLIP, one input). Not in stream, nearest or "
         "clusters mode\n"
+        "      --tree <method>          Print the tree of the records as one Newick line instead of distances: method nj "
+        "(neighbour joining). One input, one GPU, no --stream and no other output mode\n"
         "  -h, --help                   Print help\n"
         "  -V, --version                Print version");
 }
@@ -131,6 +134,8 @@ struct Args {
     double clusters = 0;                  // --clusters T
     bool has_clusters = false;
     int matrix = -1;                      // --matrix: DST_MATRIX_TSV / DST_MATRIX_PHYLIP (-1: the long form)
+    bool has_tree = false;                // --tree nj
+    bool has_slab_pairs = false;
     std::string selftest;
 };
 
@@ -213,6 +218,7 @@ Args parse_args(int argc, char **argv)
             }
         } else if (arg == "--slab-pairs" || arg.rfind("--slab-pairs=", 0) == 0) {
             a.slab_pairs = std::max<size_t>(1, parse_usize(value_of(k, arg, "--slab-pairs <p>"), "--slab-pairs <p>"));
+            a.has_slab_pairs = true;
         } else if (arg == "--nearest" || arg.rfind("--nearest=", 0) == 0) {
             const std::string v = value_of(k, arg, "--nearest <k>");
             a.nearest = parse_usize(v, "--nearest <k>");
@@ -239,6 +245,11 @@ Args parse_args(int argc, char **argv)
                 a.matrix = DST_MATRIX_PHYLIP;
             else
                 die_usage("invalid value '" + v + "' for '--matrix <format>'\n  [possible values: tsv, phylip]");
+        } else if (arg == "--tree" || arg.rfind("--tree=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--tree <method>");
+            if (v != "nj")
+                die_usage("invalid value '" + v + "' for '--tree <method>'\n  [possible values: nj]");
+            a.has_tree = true;
         } else if (arg == "--host-selftest") {
             a.selftest = value_of(k, arg, "--host-selftest <what>");
         } else {
@@ -269,6 +280,19 @@ Args parse_args(int argc, char **argv)
         die_usage("the argument '--matrix <format>' cannot be used with '--clusters <T>'");
     if (a.matrix == DST_MATRIX_PHYLIP && a.flag_inputs.size() + a.pos_inputs.size() > 1)
         die_usage("the argument '--matrix phylip' takes one input alignment (a square matrix), not two");
+    if (a.has_tree && a.has_stream)
+        die_usage("the argument '--tree <method>' cannot be used with '--stream <stream>'");
+    if (a.has_tree && a.has_nearest)
+        die_usage("the argument '--tree <method>' cannot be used with '--nearest <k>'");
+    if (a.has_tree && a.has_clusters)
+        die_usage("the argument '--tree <method>' cannot be used with '--clusters <T>'");
+    if (a.has_tree && a.matrix >= 0)
+        die_usage("the argument '--tree <method>' cannot be used with '--matrix <format>'");
+    if (a.has_tree && a.flag_inputs.size() + a.pos_inputs.size() > 1)
+        die_usage("the argument '--tree <method>' takes one input alignment, not two");
+    if (a.has_tree && (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1)))
+        die_usage(std::string("the argument '--tree <method>' cannot be used with '") +
+                  (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
     if (dst_measure_from_name(a.measure.c_str()) < 0)
         die_usage("invalid value '" + a.measure + "' for '--measure <measure>'\n  [possible values: n, n_high, raw, "
                   "jc69, k80, tn93]");
@@ -1187,6 +1211,45 @@ void write_clusters(const Ctx &gpu, const Alignment &set, int measure, double th
     wr.write(out.data(), out.size());
 }
 
+// --tree nj: the neighbour-joining tree of one set as one Newick line (dst_nj on the GPU, dst_newick on the host)
+void write_tree(const Ctx &gpu, const Alignment &set, int measure, uint64_t max_pairs, Writer &wr)
+{
+    if (set.n < 3) {
+        std::fprintf(stderr, "error: a neighbour-joining tree needs at least 3 records, the input has %zu\n", (size_t)set.n);
+        leave(1);
+    }
+    std::vector<uint32_t> parent(2 * set.n - 2);
+    std::vector<double> length(2 * set.n - 2);
+    const int rc = dst_nj(gpu.h, measure, max_pairs, parent.data(), length.data(), parent.size());
+    if (rc == DST_ERR_STATE) {
+        // "... the distance of records I and J is not finite": name the pair by its ids
+        const std::string msg = dst_last_error(gpu.h);
+        unsigned long long i = 0, j = 0;
+        const size_t at = msg.find("records ");
+        if (at != std::string::npos && std::sscanf(msg.c_str() + at, "records %llu and %llu", &i, &j) == 2 && i < set.n &&
+            j < set.n) {
+            std::fprintf(stderr, "error: the distance of '%s' and '%s' is not finite: no neighbour-joining tree\n",
+                         set.ids[i].c_str(), set.ids[j].c_str());
+            leave(1);
+        }
+    }
+    gpu.check(rc, "neighbour joining");
+    std::string chars;
+    std::vector<uint64_t> offsets(set.n + 1, 0);
+    for (size_t r = 0; r < set.n; ++r) {
+        chars += set.ids[r];
+        offsets[r + 1] = chars.size();
+    }
+    size_t len = 0;
+    dst_newick(set.n, parent.data(), length.data(), chars.data(), offsets.data(), nullptr, 0, &len);
+    std::string out(len, '\0');
+    if (dst_newick(set.n, parent.data(), length.data(), chars.data(), offsets.data(), out.data(), out.size(), &len) != DST_OK) {
+        std::fprintf(stderr, "error: the Newick text of the tree could not be written\n");
+        leave(1);
+    }
+    wr.write(out.data(), len);
+}
+
 int host_selftest(const Args &a)
 {
     if (a.selftest == "fasta") {  // parse stdin, print one line per record
@@ -1411,14 +1474,16 @@ int main(int argc, char **argv)
     } else if (a.matrix == DST_MATRIX_PHYLIP) {
         const std::string h = std::to_string(loaded[0].n) + "\n";
         wr.write(h.data(), h.size());
-    } else if (!a.has_clusters) {
+    } else if (!a.has_clusters && !a.has_tree) {
         wr.write(header, sizeof header - 1);
     }
 
     Job job;
     job.measure = measure;
     job.fmt_threads = std::max<size_t>(1, threads / (size_t)G);
-    if (a.has_clusters) {
+    if (a.has_tree) {
+        write_tree(gpus[0], loaded[0], measure, a.has_slab_pairs ? a.slab_pairs : 0, wr);
+    } else if (a.has_clusters) {
         write_clusters(gpus[0], loaded[0], measure, a.clusters, wr);
     } else if (a.has_nearest) {
         write_nearest(gpus[0], loaded, counts, measure, (uint32_t)a.nearest, wr);

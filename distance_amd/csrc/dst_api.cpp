@@ -1898,6 +1898,163 @@ int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs
     return DST_OK;
 }
 
+namespace {
+
+// The device memory of one NJ call: the two matrix buffers and one block for the rest.  Per call, not grow-only: the
+// square of 50,000 records is 20 GB.  Freed behind the context's stream.
+struct NjAlloc {
+    dst_ctx *ctx;
+    void *D0 = nullptr, *D1 = nullptr, *work = nullptr;
+    NjBuffers b{};
+    unsigned long long *bad = nullptr;
+    explicit NjAlloc(dst_ctx *c) : ctx(c) {}
+    ~NjAlloc()
+    {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void *p : {D0, D1, work})
+            if (p)
+                (void)hipFree(p);
+    }
+    int alloc(void **p, size_t bytes)
+    {
+        if (hipMalloc(p, bytes) != hipSuccess) {
+            *p = nullptr;
+            (void)hipGetLastError();   // (clear the out-of-memory status: later launches check hipGetLastError)
+            return fail(ctx, DST_ERR_NOMEM, "neighbour joining: cannot allocate " + std::to_string(bytes) +
+                                                " bytes of device memory");
+        }
+        return DST_OK;
+    }
+    int setup(uint64_t n)
+    {
+        const uint64_t n1 = std::max<uint64_t>(3 * n / 4, 1);
+        int rc = alloc(&D0, n * n * 8);
+        if (!rc)
+            rc = alloc(&D1, n1 * n1 * 8);
+        auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+        const size_t nodes = 2 * n - 2;
+        const size_t o_r1 = up(n * 8), o_ids0 = o_r1 + up(n * 8), o_ids1 = o_ids0 + up(n * 4), o_act = o_ids1 + up(n * 4),
+                     o_pos = o_act + up(n), o_pk = o_pos + up(n * 4), o_pij = o_pk + up(kNjScanBlocks * 8),
+                     o_par = o_pij + up(kNjScanBlocks * 8), o_len = o_par + up(nodes * 4), o_bad = o_len + up(nodes * 8),
+                     total = o_bad + 256;
+        if (!rc)
+            rc = alloc(&work, total);
+        if (rc)
+            return rc;
+        char *w = static_cast<char *>(work);
+        b.D[0] = static_cast<double *>(D0);
+        b.D[1] = static_cast<double *>(D1);
+        b.r[0] = reinterpret_cast<double *>(w);
+        b.r[1] = reinterpret_cast<double *>(w + o_r1);
+        b.ids[0] = reinterpret_cast<uint32_t *>(w + o_ids0);
+        b.ids[1] = reinterpret_cast<uint32_t *>(w + o_ids1);
+        b.active = reinterpret_cast<uint8_t *>(w + o_act);
+        b.pos = reinterpret_cast<uint32_t *>(w + o_pos);
+        b.part_key = reinterpret_cast<uint64_t *>(w + o_pk);
+        b.part_ij = reinterpret_cast<uint64_t *>(w + o_pij);
+        b.parent = reinterpret_cast<uint32_t *>(w + o_par);
+        b.length = reinterpret_cast<double *>(w + o_len);
+        bad = reinterpret_cast<unsigned long long *>(w + o_bad);
+        return DST_OK;
+    }
+};
+
+int nj_check_out(dst_ctx *ctx, uint64_t n, uint32_t *parent, double *length, size_t cap)
+{
+    if (!parent || !length)
+        return fail(ctx, DST_ERR_ARG, "null parent or length pointer");
+    if (n < 3)
+        return fail(ctx, DST_ERR_ARG, "neighbour joining needs at least 3 records");
+    if (n >= ((uint64_t)1 << 31))
+        return fail(ctx, DST_ERR_ARG, "neighbour joining of 2^31 records or more");
+    if (cap < 2 * n - 2)
+        return fail(ctx, DST_ERR_CAPACITY, "cap is below 2n - 2 entries");
+    return DST_OK;
+}
+
+// the rounds behind the fill on the context's stream, then one copy of the tree to the host
+int nj_finish(dst_ctx *ctx, NjAlloc &al, uint64_t n, uint32_t *parent, double *length)
+{
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(ctx, launch_nj_rounds(al.b, n, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(parent, al.b.parent, (2 * n - 2) * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(length, al.b.length, (2 * n - 2) * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    return DST_OK;
+}
+
+}  // namespace
+
+int dst_nj(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *parent, double *length, size_t cap)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    DeviceSet &set = ctx->set[0];
+    if (!set.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    const uint64_t n = set.n;
+    if (int rc = nj_check_out(ctx, n, parent, length, cap))
+        return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const std::vector<RowSlab> slabs = cut_row_slabs(true, n, n, max_pairs ? max_pairs : kClusterSlabPairs);
+    uint64_t biggest = 0;
+    for (const RowSlab &s : slabs)
+        biggest = std::max(biggest, s.pairs);
+    HIP_TRY(ctx, hipStreamSynchronize(stream));   // (the grow-only slab scratch of an earlier call: nothing reads it now)
+    int rc = ensure_bytes(ctx, &ctx->cl_slab, &ctx->cl_slab_bytes,
+                          std::max<size_t>(dst_out_bytes(measure, DST_OUT_DISTANCE, biggest), 256));
+    if (rc)
+        return rc;
+    NjAlloc al(ctx);
+    if ((rc = al.setup(n)))
+        return rc;
+    HIP_TRY(ctx, launch_nj_init(al.b.D[0], n, al.b.ids[0], al.b.active, al.bad, stream));
+    for (const RowSlab &s : slabs) {
+        // the slab's pairs, each once (the triangle), as DST_OUT_DISTANCE payloads
+        rc = run_sets(ctx, measure, true, set, set, s.rb, s.re, DST_OUT_DISTANCE, ctx->cl_slab, ctx->cl_slab_bytes,
+                      (void *)stream);
+        if (rc)
+            return rc;
+        HIP_TRY(ctx, launch_nj_scatter(measure, static_cast<const uint64_t *>(ctx->cl_slab), s.first, n, s.rb, s.re,
+                                       al.b.D[0], al.bad, stream));
+    }
+    // one look at the fill before the rounds: a non-finite distance ends the call
+    unsigned long long bad = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, al.bad, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (bad != ~0ull)
+        return fail(ctx, DST_ERR_STATE, "neighbour joining: the distance of records " + std::to_string(bad / n) + " and " +
+                                            std::to_string(bad % n) + " is not finite");
+    return nj_finish(ctx, al, n, parent, length);
+}
+
+int dst_nj_matrix(dst_ctx *ctx, const double *d, uint64_t n, uint32_t *parent, double *length, size_t cap)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (!d)
+        return fail(ctx, DST_ERR_ARG, "null matrix pointer");
+    if (int rc = nj_check_out(ctx, n, parent, length, cap))
+        return rc;
+    for (uint64_t i = 0; i < n; ++i)
+        for (uint64_t j = i + 1; j < n; ++j)
+            if (!std::isfinite(d[i * n + j]))
+                return fail(ctx, DST_ERR_ARG, "neighbour joining: the distance of records " + std::to_string(i) + " and " +
+                                                  std::to_string(j) + " is not finite");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    NjAlloc al(ctx);
+    if (int rc = al.setup(n))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(al.b.D[0], d, n * n * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, launch_nj_init(al.b.D[0], n, al.b.ids[0], al.b.active, al.bad, stream));
+    HIP_TRY(ctx, launch_nj_mirror(al.b.D[0], n, stream));
+    return nj_finish(ctx, al, n, parent, length);
+}
+
 int dst_run_square_host(dst_ctx *ctx, int measure, uint64_t row_begin, uint64_t row_end, int out_kind,
                         void *h_out, size_t cap)
 {

@@ -3,6 +3,7 @@
 // order (src/measures.rs) and the TSV number format (src/lib.rs:626-633).
 // Built with -ffp-contract=off: rustc never contracts a*b+c, and ln/sqrt are glibc's in both.
 #include <algorithm>
+#include <cctype>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -520,6 +521,117 @@ int dst_format_distance(int measure, double as_float, int64_t as_int, char *buf,
     if (std::isinf(as_float))
         return std::snprintf(buf, cap, as_float < 0 ? "-inf" : "inf");
     return std::snprintf(buf, cap, "%.12f", as_float);
+}
+
+// Newick text of a dst_nj tree: children in ascending node id, leaves by their ids (quoted where Newick needs it),
+// lengths as dst_format_distance prints an f64 distance.  Iterative: a caterpillar tree is n levels deep.
+int dst_newick(uint64_t n, const uint32_t *parent, const double *length, const char *chars, const uint64_t *offsets,
+               char *out, size_t cap, size_t *len)
+{
+    if (len)
+        *len = 0;
+    if (!parent || !length || !offsets || !len || n < 3 || n >= ((uint64_t)1 << 31) || (!out && cap))
+        return DST_ERR_ARG;
+    if (offsets[n] > 0 && !chars)
+        return DST_ERR_ARG;
+    for (uint64_t r = 0; r < n; ++r)
+        if (offsets[r] > offsets[r + 1])
+            return DST_ERR_ARG;
+    const uint64_t N = 2 * n - 2;
+    // children lists (ascending: nodes are visited in id order), one root, the right number of children everywhere
+    std::vector<uint64_t> first(N + 1, 0), child(N);
+    uint64_t root = N;
+    for (uint64_t x = 0; x < N; ++x) {
+        if (parent[x] == 0xFFFFFFFFu) {
+            if (root != N)
+                return DST_ERR_ARG;
+            root = x;
+        } else if (parent[x] >= N || parent[x] == x) {
+            return DST_ERR_ARG;
+        } else {
+            ++first[parent[x] + 1];
+        }
+    }
+    if (root == N || root < n)
+        return DST_ERR_ARG;
+    for (uint64_t x = 0; x < N; ++x) {
+        const uint64_t kids = first[x + 1];
+        if (kids != (x < n ? 0u : x == root ? 3u : 2u))
+            return DST_ERR_ARG;
+    }
+    for (uint64_t x = 0; x < N; ++x)
+        first[x + 1] += first[x];
+    {
+        std::vector<uint64_t> fill(first.begin(), first.end() - 1);
+        for (uint64_t x = 0; x < N; ++x)
+            if (x != root)
+                child[fill[parent[x]]++] = x;
+    }
+    auto quoted = [](const char *s, size_t l) {
+        if (l == 0)
+            return true;
+        for (size_t k = 0; k < l; ++k)
+            if (std::isspace((unsigned char)s[k]) || std::strchr("()[]':;,", s[k]))
+                return true;
+        return false;
+    };
+    // depth-first: a node's opening text, then its children, then its closing text
+    std::string text;
+    uint64_t visited = 0;
+    std::vector<std::pair<uint64_t, uint64_t>> stack;   // (node, next child)
+    stack.push_back({root, 0});
+    char num[64];
+    while (!stack.empty()) {
+        auto &[x, k] = stack.back();
+        const uint64_t x_ = x;
+        if (k == 0) {
+            ++visited;
+            if (visited > N)
+                return DST_ERR_ARG;
+            if (x_ < n) {
+                const char *s = chars ? chars + offsets[x_] : "";
+                const size_t l = offsets[x_ + 1] - offsets[x_];
+                if (quoted(s, l)) {
+                    text += '\'';
+                    for (size_t q = 0; q < l; ++q) {
+                        if (s[q] == '\'')
+                            text += '\'';
+                        text += s[q];
+                    }
+                    text += '\'';
+                } else {
+                    text.append(s, l);
+                }
+            } else {
+                text += '(';
+            }
+        }
+        const uint64_t kids = first[x_ + 1] - first[x_];
+        if (k < kids) {
+            if (k > 0)
+                text += ',';
+            const uint64_t c = child[first[x_] + k];
+            ++k;
+            stack.push_back({c, 0});
+            continue;
+        }
+        if (x_ >= n)
+            text += ')';
+        if (x_ != root) {
+            text += ':';
+            const int l = dst_format_distance(DST_RAW, length[x_], 0, num, sizeof num);
+            text.append(num, (size_t)std::min<int>(std::max(l, 0), (int)sizeof num - 1));
+        }
+        stack.pop_back();
+    }
+    if (visited != N)
+        return DST_ERR_ARG;   // a cycle: some nodes hang below nodes the root never reaches
+    text += ";\n";
+    *len = text.size();
+    if (cap < text.size())
+        return DST_ERR_CAPACITY;
+    std::memcpy(out, text.data(), text.size());
+    return DST_OK;
 }
 
 }  // extern "C"

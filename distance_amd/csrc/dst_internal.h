@@ -389,6 +389,33 @@ hipError_t launch_clusters_link(int measure, const uint64_t *slab, uint64_t out_
                                 uint64_t t_bits, uint32_t *parent, unsigned long long *links, hipStream_t stream);
 hipError_t launch_clusters_final(uint32_t *parent, uint64_t n, hipStream_t stream);
 
+// ---- neighbour-joining trees (dst_nj.hip, driven by dst_nj / dst_nj_matrix in dst_api.cpp) --------------------------
+// The n x n f64 square on the device, filled from row slabs of DST_OUT_DISTANCE payloads (as dst_clusters) or from the
+// caller's matrix, then n - 3 rounds of a scan launch (kNjScanBlocks workgroups at most, one partial each) and a merge
+// launch, and a compaction into the other matrix buffer whenever m <= floor(3P/4).  D[0]: n x n; D[1]: at least
+// floor(3n/4)^2 entries (the first compaction's target; later ones fit either buffer).
+constexpr uint64_t kNjScanBlocks = 2048;
+struct NjBuffers {
+    double *D[2];
+    double *r[2];          // row sums by slot, read by one round's merge and written for the next
+    uint32_t *ids[2];      // node id by slot (the second: the compaction's target)
+    uint8_t *active;       // slot in the list
+    uint32_t *pos;         // the compaction's gather map
+    uint64_t *part_key, *part_ij;   // kNjScanBlocks scan partials
+    uint32_t *parent;      // 2n - 2 entries
+    double *length;
+};
+// diagonal := +0.0, ids := identity, every slot active, *bad := ~0
+hipError_t launch_nj_init(double *D, uint64_t n, uint32_t *ids, uint8_t *active, unsigned long long *bad, hipStream_t stream);
+// rows [rb, re) of the square from slab entry tri_row_start(n, i) - out_base into D (both halves); *bad := min(*bad,
+// i * n + j) for every non-finite payload
+hipError_t launch_nj_scatter(int measure, const uint64_t *slab, uint64_t out_base, uint64_t n, uint64_t rb, uint64_t re,
+                             double *D, unsigned long long *bad, hipStream_t stream);
+// D's strict upper triangle into the lower one
+hipError_t launch_nj_mirror(double *D, uint64_t n, hipStream_t stream);
+// every round, the root included, into b.parent / b.length; n >= 3, D[0] symmetric with a +0.0 diagonal
+hipError_t launch_nj_rounds(const NjBuffers &b, uint64_t n, hipStream_t stream);
+
 // ---- host-only logic (dst_host.cpp) ----------------------------------------------------------
 int tally_width(int measure);
 bool measure_is_int(int measure);

@@ -111,6 +111,30 @@ def format_distance(measure, value) -> str:
     return buf.value.decode()
 
 
+def newick(parent, length, ids) -> bytes:
+    """Newick text of a tree from Engine.nj / nj_matrix (dst_newick): ids name the leaves 0..n-1 (str or bytes)."""
+    parent = np.ascontiguousarray(parent, np.uint32)
+    length = np.ascontiguousarray(length, np.float64)
+    names = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+    n = len(names)
+    chars = b"".join(names)
+    offsets = np.zeros(n + 1, np.uint64)
+    offsets[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64) if n else []
+    if len(parent) != max(2 * n - 2, 0) or len(length) != len(parent):
+        raise ValueError("parent and length need 2n - 2 entries for n ids")
+    lib = load()
+    need = C.c_size_t(0)
+    rc = lib.dst_newick(n, parent.ctypes.data, length.ctypes.data, chars, offsets.ctypes.data, None, 0, C.byref(need))
+    if rc not in (0, 6):
+        raise DistanceError(rc, "dst_newick: malformed tree or arguments")
+    buf = C.create_string_buffer(max(need.value, 1))
+    rc = lib.dst_newick(n, parent.ctypes.data, length.ctypes.data, chars, offsets.ctypes.data, buf, need.value,
+                        C.byref(need))
+    if rc:
+        raise DistanceError(rc, "dst_newick")
+    return buf.raw[:need.value]
+
+
 class Engine:
     """One GPU's context.  `device` is the HIP device ordinal."""
 
@@ -335,6 +359,30 @@ class Engine:
         self._check(self._lib.dst_clusters(self._h, m, float(threshold), int(max_pairs), labels.ctypes.data, n,
                                            C.byref(n_clusters), C.byref(links)))
         return labels[:n], int(links.value)
+
+    def nj(self, measure, max_pairs: int = 0):
+        """Neighbour-joining tree of slot 0 (dst_nj): (parent uint32[2n-2], length float64[2n-2]).  Leaves are 0..n-1,
+        the node made in round s is n + s, the root 2n - 3 (parent 0xFFFFFFFF, length 0).  max_pairs: the most pairs of
+        one row slab of the fill (0: the default); the tree does not depend on it."""
+        m = _measure_id(measure)
+        n, _ = self.set_info(0)
+        cap = max(2 * n - 2, 1)
+        parent, length = np.zeros(cap, np.uint32), np.zeros(cap, np.float64)
+        self._check(self._lib.dst_nj(self._h, m, int(max_pairs), parent.ctypes.data, length.ctypes.data, 2 * n - 2))
+        return parent, length
+
+    def nj_matrix(self, d):
+        """Neighbour-joining tree of an n x n distance matrix (dst_nj_matrix; only the strict upper triangle is read):
+        (parent, length) as nj()."""
+        d = np.ascontiguousarray(d, np.float64)
+        if d.ndim != 2 or d.shape[0] != d.shape[1]:
+            raise ValueError("nj_matrix needs a square matrix")
+        n = d.shape[0]
+        cap = max(2 * n - 2, 1)
+        parent, length = np.zeros(cap, np.uint32), np.zeros(cap, np.float64)
+        self._check(self._lib.dst_nj_matrix(self._h, d.ctypes.data, n, parent.ctypes.data, length.ctypes.data,
+                                            max(2 * n - 2, 0)))
+        return parent, length
 
     # ---- runs into device memory (bench / multi-GPU) ------------------------------------------
     def run_square_device(self, measure, row_begin: int, row_end: int, d_out: int, capacity: int,

@@ -347,6 +347,56 @@ int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slo
  * in row slabs whose payloads a lock-free union-find on the device consumes.  Single GPU, loaded set only (not dst_stream). */
 int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs, uint32_t *label, size_t cap,
                  uint64_t *n_clusters, uint64_t *links);
+/* ---- neighbour-joining trees ------------------------------------------------------------------- */
+/* The neighbour-joining (NJ) tree of n >= 3 records, built on the GPU from the square it holds, with the arithmetic fixed
+ * below so that a restatement in any language reproduces it bit for bit.  Every expression is evaluated in the order
+ * written (the library is compiled -ffp-contract=off: no fused multiply-add).
+ *
+ * Input.  dst_nj: slot 0 (n records); D(i, j) is the pair's DST_OUT_DISTANCE payload for `measure` (f64 as is, int64 of
+ * n / n_high converted to double), bit-identical on every path, so the tree depends neither on the path nor on
+ * max_pairs (the most pairs of one row slab of the fill; 0: the default, as in dst_clusters).  dst_nj_matrix: a host
+ * n x n row-major matrix of which only the strict upper triangle is read.  D(i, i) = +0.0.
+ *
+ * Active list.  The active nodes form a list, initially records 0 .. n-1 in order; m is its length and "position" a place
+ * in it.  r_x = sum of d(x, k) over active k != x, summed left to right in position order from +0.0; computed so at the
+ * start and at every compaction.  (Adding the +0.0 diagonal gives the same bits: a sum that starts at +0.0 is never
+ * -0.0.  Payloads can be -0.0.)
+ *
+ * One round, while m > 3:
+ *   0. compaction: let P be the stored dimension (initially n); when m <= floor(3P/4), the matrix is compacted to the
+ *      active nodes in their order, P := m, and every r is recomputed as above.  The schedule depends on (n, m) only.
+ *   1. the pair: for positions a < b, Q(a, b) = ((double)(m-2) * d_ab - r_a) - r_b; the smallest Q, compared through
+ *      nn_key (the sort key of dst_nearest: -0 equals +0, NaN sorts last), ties to the smallest (a, b) in lexicographic
+ *      position order
+ *   2. branch lengths: delta_a = d_ab * 0.5 + (r_a - r_b) / (double)(2*(m-2)); delta_b = d_ab - delta_a
+ *   3. a new internal node u takes position a; b leaves the list
+ *   4. for every other active k: d_uk = ((d_ak + d_bk) - d_ab) * 0.5; d_uu = +0.0
+ *   5. for every other active k: r_k = ((r_k - d_ak) - d_bk) + d_uk; r_u = ((r_a + r_b) - (double)m * d_ab) * 0.5 (the
+ *      closed form of the sum of d_uk)
+ * The last round (m = 3, positions x < y < z) joins the three at the root: delta_x = ((d_xy + d_xz) - d_yz) * 0.5,
+ * delta_y = ((d_xy + d_yz) - d_xz) * 0.5, delta_z = ((d_xz + d_yz) - d_xy) * 0.5.  Negative branch lengths are kept as
+ * computed (NJ gives them on non-additive data).  With integer measures, or any matrix of small integers, every step
+ * above is exact in f64 (sums of integers, halves of them, and a quotient that an additive matrix makes exact).
+ *
+ * Output.  Leaves are nodes 0 .. n-1, the internal node made in round s is n + s, the root is 2n - 3 (so the ids give the
+ * order of the joins).  parent[x] and length[x] (the edge from x to its parent) for 2n - 2 nodes; the root has parent
+ * UINT32_MAX and length 0.  cap: the room of both arrays in entries, below 2n - 2 DST_ERR_CAPACITY.
+ *
+ * Errors: n < 3 or n >= 2^31, a NULL pointer or an unknown measure: DST_ERR_ARG; a non-finite D: DST_ERR_STATE from
+ * dst_nj (the context's message names the first pair in canonical order), DST_ERR_ARG from dst_nj_matrix; slot 0 not
+ * uploaded: DST_ERR_STATE; device memory for the square (8 n^2 bytes, plus 8 floor(3n/4)^2 for the compaction): DST_ERR_NOMEM
+ * with the byte count in the message.  Synchronous on the context's stream; single GPU, loaded set only (not dst_stream). */
+int dst_nj(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *parent, double *length, size_t cap);
+int dst_nj_matrix(dst_ctx *ctx, const double *d, uint64_t n, uint32_t *parent, double *length, size_t cap);
+/* Newick text of a dst_nj tree (host only, no GPU): "(c1,c2,c3);\n" at the root, children in ascending node id, each
+ * node written as name:length (internal nodes as (children):length), lengths exactly as dst_format_distance prints an
+ * f64 distance ({:.12}).  Leaf r is named chars[offsets[r] .. offsets[r+1]) (offsets: n + 1 entries, as dst_set_ids); a
+ * name that is empty or holds whitespace or any of ()[]':;, is single-quoted with every ' doubled.  *len receives the
+ * text's length (no NUL is written); cap below it: DST_ERR_CAPACITY, nothing written (out may be NULL with cap 0).
+ * DST_ERR_ARG: n < 3, a NULL pointer, decreasing offsets, or a malformed parent array (an index out of range, not exactly
+ * one root, a cycle, a leaf with children, an internal node without 2 children or a root without 3). */
+int dst_newick(uint64_t n, const uint32_t *parent, const double *length, const char *chars, const uint64_t *offsets,
+               char *out, size_t cap, size_t *len);
 /* Page-locked host memory for the *_host forms' output buffers (copy-back by DMA at link speed instead
  * of through a pageable bounce buffer).  Free with dst_host_free. */
 int dst_host_alloc(size_t bytes, void **ptr);
