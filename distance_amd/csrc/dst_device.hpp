@@ -191,9 +191,12 @@ __device__ __forceinline__ double fin_tn93(uint32_t count_L, uint32_t count_d, u
 // and the host's libm for the near ties (dst_text.hip), DST_OUT_TALLY + dst_finalize give the reference's bits.  So for
 // the low-diversity alignments the consensus path exists for — every logarithm's argument within 2^-5 of 1 — the
 // distance is evaluated as sums of -ln(1 - e) = e + e^2/2 + ... + e^9/9 (remainder below 3e-15 of the value) with
-// reciprocals from the f32 unit and one Newton step (2^-44) and no quotient corrections: ~105 instructions for tn93,
-// ~20 for jc69, ~32 for k80, absolute error below 1e-13.  Anything else — an argument further from 1, zero
-// denominators, tallies of 2^24 and more, NaN — takes the functions above.
+// reciprocals from the f32 unit and one Newton step (2^-46; jc69 / k80 denominators of 2^24 and more also carry the
+// rounding of their f32 conversion into the seed) and no quotient corrections: ~105 instructions for tn93, ~20 for jc69,
+// ~32 for k80.  Against the exact value (tests/test_gpu_finalise_accuracy.py) the error is at most 2^-44 of the value for
+// jc69 / k80 and 2^-42 of the sum of tn93's three terms (measured on an MI355X: 1.4e-14, 1.1e-14, 3.4e-14).  Anything
+// else — a log argument further from 1, zero denominators or frequency sums, tn93 counts of 2^24 and more, NaN — takes
+// the functions above, whose error is the reference formula's own (1 - e rounds away 2^-53 / e of a small e).
 __device__ __forceinline__ double rcp_fast(double b)   // b > 0, inside the f32 range
 {
     const double y0 = (double)__builtin_amdgcn_rcpf((float)b);
@@ -244,7 +247,9 @@ __device__ __forceinline__ double fin_k80_fast(uint32_t count_L, uint32_t ts, ui
     const double inv_L = rcp_fast((double)count_L);
     const double P = (double)ts * inv_L, Q = (double)tv * inv_L;
     const double ea = 2.0 * P + Q, eb = 2.0 * Q;   // -0.5 ln((1 - ea) sqrt(1 - eb)) = 0.5 S(ea) + 0.25 S(eb)
-    if (count_L == 0 || !(ea < kSeriesMax))         // (eb <= ea)
+    // both terms need the series bound: eb = 2Q exceeds ea = 2P + Q whenever tv > 2 ts (ts = 0, tv just below L/32:
+    // eb near 2^-4, where nine terms leave ~7e-13 of the value)
+    if (count_L == 0 || !(ea < kSeriesMax && eb < kSeriesMax))
         return fin_k80_close(count_L, ts, tv, tab);
     return 0.5 * neg_ln1m(ea) + 0.25 * neg_ln1m(eb);
 }

@@ -333,8 +333,8 @@ int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slo
  *   f64:                 IEEE v <= threshold, decided on dst_nearest's sort key: NaN never links, -0.0 links wherever
  *                        +0.0 does, +inf links every pair whose value is not NaN
  * A cluster is a connected component of the links; label[i] = the smallest record index in i's cluster, so the result is
- * unique whatever order the pairs are met in.  jc69 / k80 / tn93 payloads are the pair kernels' series form, within 1e-15
- * of the reference's value but not bitwise equal to it: a pair whose value lies that close to the threshold can be decided
+ * unique whatever order the pairs are met in.  jc69 / k80 / tn93 payloads are the pair kernels' series form, within 2^-44
+ * (jc69, k80) or 2^-42 (tn93) of the exact value relatively (measured <= 3.4e-14), not bitwise the reference's: a pair whose value lies that close to the threshold can be decided
  * differently from a CPU computation.  raw, n and n_high are exact.
  *   threshold   any non-NaN double (NaN: DST_ERR_ARG)
  *   max_pairs   0: the default slab bound (2^25 pairs); else the most pairs of one row slab (at least one row per slab),

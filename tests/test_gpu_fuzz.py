@@ -44,7 +44,8 @@ def _close(got, want):
         return math.isnan(got)
     if math.isinf(want):
         return got == want
-    return abs(got - want) <= 1e-12 and abs(got - want) <= 1e-12 * max(abs(want), 1e-300) + 1e-300 or abs(got - want) <= 1e-12
+    err = abs(got - want)
+    return err <= 1e-12 and (abs(want) < 1e-3 or err <= 1e-12 * abs(want))
 
 
 @pytest.mark.parametrize("fused", [False, True])

@@ -41,7 +41,8 @@ def assert_close(got, want):
     ok = ~(nan_w | inf)
     err = np.abs(got[ok] - want[ok])
     assert np.all(err <= TOL), f"abs err {err.max()}"
-    assert np.all(err <= TOL * np.maximum(np.abs(want[ok]), 1e-300) + 1e-300) or np.all(err <= TOL)
+    big = np.abs(want[ok]) >= 1e-3          # relative too: 1e-12 absolute alone is 1e-9 of a distance of 1e-3
+    assert np.all(err[big] <= TOL * np.abs(want[ok][big])), f"rel err {(err[big] / np.abs(want[ok][big])).max()}"
 
 
 def oracle_tallies_square(measure, codes):
