@@ -94,6 +94,11 @@ _SIGS = {
     "dst_nj": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, C.c_size_t]),
     "dst_nj_matrix": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_size_t]),
     "dst_newick": (C.c_int, [C.c_uint64, _vp, _vp, C.c_char_p, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
+    "dst_newick_support": (C.c_int, [C.c_uint64, _vp, _vp, C.c_char_p, _vp, _vp, _vp, C.c_size_t,
+                                     C.POINTER(C.c_size_t)]),
+    "dst_bootstrap_columns": (None, [C.c_uint64, C.c_uint32, C.c_uint64, _vp]),
+    "dst_nj_bootstrap": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint64,
+                                   C.c_uint64, _vp, _vp, _vp, C.c_size_t]),
     "dst_host_alloc": (C.c_int, [C.c_size_t, C.POINTER(_vp)]),
     "dst_host_free": (C.c_int, [_vp]),
     "dst_out_bytes": (C.c_size_t, [C.c_int, C.c_int, C.c_uint64]),

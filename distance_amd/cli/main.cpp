@@ -10,7 +10,8 @@
 // Extra flags: --gpus N (default 1) / --devices LIST, --slab-pairs P (result slab size), --nearest K (the K nearest records
 // of every record instead of every pair: dst_nearest), --clusters T (single-linkage clusters at threshold T: dst_clusters),
 // --matrix tsv|phylip (a square or rectangular distance matrix instead of the long form: dst_text_matrix), --tree nj (the
-// neighbour-joining tree as one Newick line: dst_nj, dst_newick).
+// neighbour-joining tree as one Newick line: dst_nj, dst_newick), --bootstrap B / --seed S (the tree's splits labelled
+// with their support in B column resamplings: dst_nj_bootstrap, dst_newick_support).
 //
 // Exactness: the GPU returns integer site tallies; f64 finalisation is dst_finalize() on the host
 // (reference operation order, glibc log/sqrt), so the printed digits do not depend on the device.
@@ -115,6 +116,9 @@ void print_help()
         "clusters mode\n"
         "      --tree <method>          Print the tree of the records as one Newick line instead of distances: method nj "
         "(neighbour joining). One input, one GPU, no --stream and no other output mode\n"
+        "      --bootstrap <B>          Label each internal edge of the neighbour-joining tree with the number of B "
+        "(1-10000) bootstrap replicates (alignments of columns drawn with replacement) whose tree holds its split\n"
+        "      --seed <S>               Seed of the bootstrap's column draws, 0 to 2^64-1 [default: 1]\n"
         "  -h, --help                   Print help\n"
         "  -V, --version                Print version");
 }
@@ -135,6 +139,10 @@ struct Args {
     bool has_clusters = false;
     int matrix = -1;                      // --matrix: DST_MATRIX_TSV / DST_MATRIX_PHYLIP (-1: the long form)
     bool has_tree = false;                // --tree nj
+    uint32_t bootstrap = 0;               // --bootstrap B (0: none)
+    bool has_bootstrap = false;
+    uint64_t seed = 1;                    // --seed S
+    bool has_seed = false;
     bool has_slab_pairs = false;
     std::string selftest;
 };
@@ -250,6 +258,16 @@ Args parse_args(int argc, char **argv)
             if (v != "nj")
                 die_usage("invalid value '" + v + "' for '--tree <method>'\n  [possible values: nj]");
             a.has_tree = true;
+        } else if (arg == "--bootstrap" || arg.rfind("--bootstrap=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--bootstrap <B>");
+            const size_t b = parse_usize(v, "--bootstrap <B>");
+            if (b < 1 || b > 10000)
+                die_usage("invalid value '" + v + "' for '--bootstrap <B>': " + v + " is not in 1..=10000");
+            a.bootstrap = (uint32_t)b;
+            a.has_bootstrap = true;
+        } else if (arg == "--seed" || arg.rfind("--seed=", 0) == 0) {
+            a.seed = parse_usize(value_of(k, arg, "--seed <S>"), "--seed <S>");
+            a.has_seed = true;
         } else if (arg == "--host-selftest") {
             a.selftest = value_of(k, arg, "--host-selftest <what>");
         } else {
@@ -293,6 +311,10 @@ Args parse_args(int argc, char **argv)
     if (a.has_tree && (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1)))
         die_usage(std::string("the argument '--tree <method>' cannot be used with '") +
                   (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
+    if (a.has_bootstrap && !a.has_tree)
+        die_usage("the argument '--bootstrap <B>' requires '--tree nj'");
+    if (a.has_seed && !a.has_bootstrap)
+        die_usage("the argument '--seed <S>' requires '--bootstrap <B>'");
     if (dst_measure_from_name(a.measure.c_str()) < 0)
         die_usage("invalid value '" + a.measure + "' for '--measure <measure>'\n  [possible values: n, n_high, raw, "
                   "jc69, k80, tn93]");
@@ -1211,8 +1233,26 @@ void write_clusters(const Ctx &gpu, const Alignment &set, int measure, double th
     wr.write(out.data(), out.size());
 }
 
-// --tree nj: the neighbour-joining tree of one set as one Newick line (dst_nj on the GPU, dst_newick on the host)
-void write_tree(const Ctx &gpu, const Alignment &set, int measure, uint64_t max_pairs, Writer &wr)
+// a DST_ERR_STATE message "... the distance of records I and J is not finite" of the NJ calls, with the pair named by
+// its ids; false when the message names no pair of the set
+bool non_finite_pair(const Ctx &gpu, const Alignment &set, const char *prefix, const char *suffix)
+{
+    const std::string msg = dst_last_error(gpu.h);
+    unsigned long long i = 0, j = 0;
+    const size_t at = msg.find("records ");
+    if (at == std::string::npos || std::sscanf(msg.c_str() + at, "records %llu and %llu", &i, &j) != 2 || i >= set.n ||
+        j >= set.n)
+        return false;
+    std::fprintf(stderr, "error: %sthe distance of '%s' and '%s' is not finite%s\n", prefix, set.ids[i].c_str(),
+                 set.ids[j].c_str(), suffix);
+    return true;
+}
+
+// --tree nj: the neighbour-joining tree of one set as one Newick line (dst_nj on the GPU, dst_newick on the host);
+// with --bootstrap B its internal nodes carry their support in B replicates (dst_nj_bootstrap, dst_newick_support),
+// and nothing is written unless every replicate succeeded
+void write_tree(const Ctx &gpu, const Alignment &set, int measure, uint64_t max_pairs, uint32_t bootstrap, uint64_t seed,
+                Writer &wr)
 {
     if (set.n < 3) {
         std::fprintf(stderr, "error: a neighbour-joining tree needs at least 3 records, the input has %zu\n", (size_t)set.n);
@@ -1220,30 +1260,42 @@ void write_tree(const Ctx &gpu, const Alignment &set, int measure, uint64_t max_
     }
     std::vector<uint32_t> parent(2 * set.n - 2);
     std::vector<double> length(2 * set.n - 2);
-    const int rc = dst_nj(gpu.h, measure, max_pairs, parent.data(), length.data(), parent.size());
-    if (rc == DST_ERR_STATE) {
-        // "... the distance of records I and J is not finite": name the pair by its ids
-        const std::string msg = dst_last_error(gpu.h);
-        unsigned long long i = 0, j = 0;
-        const size_t at = msg.find("records ");
-        if (at != std::string::npos && std::sscanf(msg.c_str() + at, "records %llu and %llu", &i, &j) == 2 && i < set.n &&
-            j < set.n) {
-            std::fprintf(stderr, "error: the distance of '%s' and '%s' is not finite: no neighbour-joining tree\n",
-                         set.ids[i].c_str(), set.ids[j].c_str());
+    int rc = dst_nj(gpu.h, measure, max_pairs, parent.data(), length.data(), parent.size());
+    if (rc == DST_ERR_STATE && non_finite_pair(gpu, set, "", ": no neighbour-joining tree"))
+        leave(1);
+    gpu.check(rc, "neighbour joining");
+    std::vector<uint32_t> support;
+    if (bootstrap) {
+        support.resize(parent.size());
+        rc = dst_nj_bootstrap(gpu.h, measure, set.codes.data(), set.n, set.width, set.width, bootstrap, seed, max_pairs,
+                              parent.data(), support.data(), nullptr, support.size());
+        if (rc == DST_ERR_STATE) {
+            // "bootstrap replicate R: the distance of records I and J is not finite"
+            unsigned long long r = 0;
+            const std::string msg = dst_last_error(gpu.h);
+            if (std::sscanf(msg.c_str(), "bootstrap replicate %llu", &r) == 1) {
+                const std::string prefix = "bootstrap replicate " + std::to_string(r) + ": ";
+                if (non_finite_pair(gpu, set, prefix.c_str(), ""))
+                    leave(1);
+            }
+        }
+        if (rc != DST_OK) {
+            std::fprintf(stderr, "error: bootstrap: %s\n", dst_last_error(gpu.h));
             leave(1);
         }
     }
-    gpu.check(rc, "neighbour joining");
     std::string chars;
     std::vector<uint64_t> offsets(set.n + 1, 0);
     for (size_t r = 0; r < set.n; ++r) {
         chars += set.ids[r];
         offsets[r + 1] = chars.size();
     }
+    const uint32_t *sup = bootstrap ? support.data() : nullptr;
     size_t len = 0;
-    dst_newick(set.n, parent.data(), length.data(), chars.data(), offsets.data(), nullptr, 0, &len);
+    dst_newick_support(set.n, parent.data(), length.data(), chars.data(), offsets.data(), sup, nullptr, 0, &len);
     std::string out(len, '\0');
-    if (dst_newick(set.n, parent.data(), length.data(), chars.data(), offsets.data(), out.data(), out.size(), &len) != DST_OK) {
+    if (dst_newick_support(set.n, parent.data(), length.data(), chars.data(), offsets.data(), sup, out.data(), out.size(),
+                           &len) != DST_OK) {
         std::fprintf(stderr, "error: the Newick text of the tree could not be written\n");
         leave(1);
     }
@@ -1482,7 +1534,7 @@ int main(int argc, char **argv)
     job.measure = measure;
     job.fmt_threads = std::max<size_t>(1, threads / (size_t)G);
     if (a.has_tree) {
-        write_tree(gpus[0], loaded[0], measure, a.has_slab_pairs ? a.slab_pairs : 0, wr);
+        write_tree(gpus[0], loaded[0], measure, a.has_slab_pairs ? a.slab_pairs : 0, a.bootstrap, a.seed, wr);
     } else if (a.has_clusters) {
         write_clusters(gpus[0], loaded[0], measure, a.clusters, wr);
     } else if (a.has_nearest) {

@@ -249,10 +249,20 @@ int invalid_code_error(dst_ctx *ctx, unsigned long long first_bad, size_t len)
 
 bool consensus_shape_ok(const DeviceSet &rows, const DeviceSet &cols);
 
+int pack_set(dst_ctx *ctx, DeviceSet &s, const uint8_t *d_codes, size_t n, size_t len, size_t row_stride,
+             const uint32_t *d_counts, hipStream_t stream);
+
 int pack_from_device(dst_ctx *ctx, int slot, const uint8_t *d_codes, size_t n, size_t len,
                      size_t row_stride, const uint32_t *d_counts, hipStream_t stream)
 {
-    DeviceSet &s = ctx->set[slot];
+    return pack_set(ctx, ctx->set[slot], d_codes, n, len, row_stride, d_counts, stream);
+}
+
+// the upload of device bytes into any set of the context (a slot, or dst_nj_bootstrap's replicate): the pack, the
+// report and its one synchronisation
+int pack_set(dst_ctx *ctx, DeviceSet &s, const uint8_t *d_codes, size_t n, size_t len, size_t row_stride,
+             const uint32_t *d_counts, hipStream_t stream)
+{
     // the consensus path's preparation rides on the pack when a run of this set is likely to take it: not forced
     // dense, a shape the lists can index, and more work than the dense kernels finish before lists are built
     const bool want_lists = ctx->path != DST_PATH_DENSE && n >= 2 && len > 0 && n < kEntryMask && len < kSiteMask &&
@@ -1209,6 +1219,7 @@ int dst_destroy(dst_ctx *ctx)
     (void)hipDeviceSynchronize();
     free_set(ctx->set[0]);
     free_set(ctx->set[1]);
+    free_set(ctx->boot);
     if (ctx->stage)
         (void)hipFree(ctx->stage);
     for (auto &s : ctx->schedules)
@@ -1972,6 +1983,44 @@ int nj_check_out(dst_ctx *ctx, uint64_t n, uint32_t *parent, double *length, siz
     return DST_OK;
 }
 
+// the row slabs of the fill of an n-record square and the context's slab scratch for them (grow-only; the wait lets an
+// earlier call's slab go before it is replaced)
+int nj_slabs(dst_ctx *ctx, int measure, uint64_t n, uint64_t max_pairs, std::vector<RowSlab> &slabs)
+{
+    slabs = cut_row_slabs(true, n, n, max_pairs ? max_pairs : kClusterSlabPairs);
+    uint64_t biggest = 0;
+    for (const RowSlab &s : slabs)
+        biggest = std::max(biggest, s.pairs);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return ensure_bytes(ctx, &ctx->cl_slab, &ctx->cl_slab_bytes,
+                        std::max<size_t>(dst_out_bytes(measure, DST_OUT_DISTANCE, biggest), 256));
+}
+
+// the square of `set` into al's first matrix buffer and the non-finite flag, queued on the context's stream without a
+// wait: the initial state, then per slab its pairs (each once, the triangle) as DST_OUT_DISTANCE payloads, scattered
+int nj_fill(dst_ctx *ctx, int measure, DeviceSet &set, const std::vector<RowSlab> &slabs, NjAlloc &al)
+{
+    hipStream_t stream = ctx->stream;
+    const uint64_t n = set.n;
+    HIP_TRY(ctx, launch_nj_init(al.b.D[0], n, al.b.ids[0], al.b.active, al.bad, stream));
+    for (const RowSlab &s : slabs) {
+        const int rc = run_sets(ctx, measure, true, set, set, s.rb, s.re, DST_OUT_DISTANCE, ctx->cl_slab,
+                                ctx->cl_slab_bytes, (void *)stream);
+        if (rc)
+            return rc;
+        HIP_TRY(ctx, launch_nj_scatter(measure, static_cast<const uint64_t *>(ctx->cl_slab), s.first, n, s.rb, s.re,
+                                       al.b.D[0], al.bad, stream));
+    }
+    return DST_OK;
+}
+
+// the message of a non-finite fill: the first pair in canonical order, from the flag's linear index i * n + j
+int nj_bad_pair(dst_ctx *ctx, const std::string &what, unsigned long long bad, uint64_t n)
+{
+    return fail(ctx, DST_ERR_STATE, what + "the distance of records " + std::to_string(bad / n) + " and " +
+                                        std::to_string(bad % n) + " is not finite");
+}
+
 // the rounds behind the fill on the context's stream, then one copy of the tree to the host
 int nj_finish(dst_ctx *ctx, NjAlloc &al, uint64_t n, uint32_t *parent, double *length)
 {
@@ -1982,6 +2031,37 @@ int nj_finish(dst_ctx *ctx, NjAlloc &al, uint64_t n, uint32_t *parent, double *l
     HIP_TRY(ctx, hipStreamSynchronize(stream));
     return DST_OK;
 }
+
+// dst_nj_bootstrap's device memory beside NjAlloc: the original codes, the replicate's codes (both n x pitch) and the
+// column map.  Freed behind the context's stream, with the replicate's packed set.
+struct BootAlloc {
+    dst_ctx *ctx;
+    uint8_t *src = nullptr, *rep = nullptr;
+    uint32_t *map = nullptr;
+    explicit BootAlloc(dst_ctx *c) : ctx(c) {}
+    ~BootAlloc()
+    {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void *p : {(void *)src, (void *)rep, (void *)map})
+            if (p)
+                (void)hipFree(p);
+        free_set(ctx->boot);
+    }
+    int setup(uint64_t n, uint64_t pitch, uint64_t len)
+    {
+        const size_t bytes[3] = {std::max<size_t>(n * pitch, 128), std::max<size_t>(n * pitch, 128),
+                                 std::max<size_t>(len * 4, 4)};
+        void **ptrs[3] = {(void **)&src, (void **)&rep, (void **)&map};
+        for (int k = 0; k < 3; ++k)
+            if (hipMalloc(ptrs[k], bytes[k]) != hipSuccess) {
+                *ptrs[k] = nullptr;
+                (void)hipGetLastError();
+                return fail(ctx, DST_ERR_NOMEM, "bootstrap: cannot allocate " + std::to_string(bytes[k]) +
+                                                    " bytes of device memory");
+            }
+        return DST_OK;
+    }
+};
 
 }  // namespace
 
@@ -1999,36 +2079,87 @@ int dst_nj(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *parent, doub
         return rc;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
-    const std::vector<RowSlab> slabs = cut_row_slabs(true, n, n, max_pairs ? max_pairs : kClusterSlabPairs);
-    uint64_t biggest = 0;
-    for (const RowSlab &s : slabs)
-        biggest = std::max(biggest, s.pairs);
-    HIP_TRY(ctx, hipStreamSynchronize(stream));   // (the grow-only slab scratch of an earlier call: nothing reads it now)
-    int rc = ensure_bytes(ctx, &ctx->cl_slab, &ctx->cl_slab_bytes,
-                          std::max<size_t>(dst_out_bytes(measure, DST_OUT_DISTANCE, biggest), 256));
+    std::vector<RowSlab> slabs;
+    int rc = nj_slabs(ctx, measure, n, max_pairs, slabs);
     if (rc)
         return rc;
     NjAlloc al(ctx);
     if ((rc = al.setup(n)))
         return rc;
-    HIP_TRY(ctx, launch_nj_init(al.b.D[0], n, al.b.ids[0], al.b.active, al.bad, stream));
-    for (const RowSlab &s : slabs) {
-        // the slab's pairs, each once (the triangle), as DST_OUT_DISTANCE payloads
-        rc = run_sets(ctx, measure, true, set, set, s.rb, s.re, DST_OUT_DISTANCE, ctx->cl_slab, ctx->cl_slab_bytes,
-                      (void *)stream);
-        if (rc)
-            return rc;
-        HIP_TRY(ctx, launch_nj_scatter(measure, static_cast<const uint64_t *>(ctx->cl_slab), s.first, n, s.rb, s.re,
-                                       al.b.D[0], al.bad, stream));
-    }
+    if ((rc = nj_fill(ctx, measure, set, slabs, al)))
+        return rc;
     // one look at the fill before the rounds: a non-finite distance ends the call
     unsigned long long bad = 0;
     HIP_TRY(ctx, hipMemcpyAsync(&bad, al.bad, 8, hipMemcpyDeviceToHost, stream));
     HIP_TRY(ctx, hipStreamSynchronize(stream));
     if (bad != ~0ull)
-        return fail(ctx, DST_ERR_STATE, "neighbour joining: the distance of records " + std::to_string(bad / n) + " and " +
-                                            std::to_string(bad % n) + " is not finite");
+        return nj_bad_pair(ctx, "neighbour joining: ", bad, n);
     return nj_finish(ctx, al, n, parent, length);
+}
+
+int dst_nj_bootstrap(dst_ctx *ctx, int measure, const uint8_t *codes, size_t n, size_t len, size_t row_stride,
+                     uint32_t replicates, uint64_t seed, uint64_t max_pairs, const uint32_t *parent, uint32_t *support,
+                     uint32_t *rep_parent, size_t cap)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (!parent || !support)
+        return fail(ctx, DST_ERR_ARG, "null parent or support pointer");
+    if ((len && !codes) || row_stride < len)
+        return fail(ctx, DST_ERR_ARG, "null codes or row_stride < len");
+    if (n < 3)
+        return fail(ctx, DST_ERR_ARG, "neighbour joining needs at least 3 records");
+    if (n >= ((uint64_t)1 << 31) || len >= 0xFFFFFF00ull)
+        return fail(ctx, DST_ERR_ARG, "bootstrap: n must be below 2^31 and len must fit 32 bits");
+    if (replicates < 1 || replicates > 10000)
+        return fail(ctx, DST_ERR_ARG, "bootstrap: replicates must be in 1..=10000");
+    const uint64_t N = 2 * n - 2;
+    if (cap < N)
+        return fail(ctx, DST_ERR_CAPACITY, "cap is below 2n - 2 entries");
+    SplitCounter splits;
+    if (!splits.init(n, parent))
+        return fail(ctx, DST_ERR_ARG, "bootstrap: the main tree is not a dst_nj tree on n leaves");
+    std::vector<uint32_t> count(N, 0), rp(N);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    std::vector<RowSlab> slabs;
+    int rc = nj_slabs(ctx, measure, n, max_pairs, slabs);
+    if (rc)
+        return rc;
+    const uint64_t pitch = std::max<uint64_t>((len + 127) / 128 * 128, 128);
+    NjAlloc al(ctx);   // (destroyed after `boot`: the replicate set is freed first, then the square)
+    BootAlloc boot(ctx);
+    if ((rc = boot.setup(n, pitch, len)) || (rc = al.setup(n)))
+        return rc;
+    if (len)
+        HIP_TRY(ctx, hipMemcpy2DAsync(boot.src, pitch, codes, row_stride, len, n, hipMemcpyHostToDevice, stream));
+    // the original once through the pack: every byte is checked, as dst_upload checks it (a replicate draws a subset)
+    if ((rc = pack_set(ctx, ctx->boot, boot.src, n, len, pitch, nullptr, stream)))
+        return rc;
+    for (uint32_t r = 0; r < replicates; ++r) {
+        HIP_TRY(ctx, launch_boot_resample(boot.src, pitch, boot.rep, n, len, seed, r, boot.map, stream));
+        // tn93: no counts passed, so the pair kernels count the replicate's bases by code (need_counts)
+        if ((rc = pack_set(ctx, ctx->boot, boot.rep, n, len, pitch, nullptr, stream)))
+            return rc;
+        if ((rc = nj_fill(ctx, measure, ctx->boot, slabs, al)))
+            return rc;
+        // the rounds run whatever the flag says (their indices stay in range on non-finite values); one wait per tree
+        unsigned long long bad = 0;
+        uint32_t *dst = rep_parent ? rep_parent + (uint64_t)r * N : rp.data();
+        HIP_TRY(ctx, launch_nj_rounds(al.b, n, stream));
+        HIP_TRY(ctx, hipMemcpyAsync(dst, al.b.parent, N * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipMemcpyAsync(&bad, al.bad, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+        if (bad != ~0ull)
+            return nj_bad_pair(ctx, "bootstrap replicate " + std::to_string(r) + ": ", bad, n);
+        if (!splits.count(dst, count.data()))
+            return fail(ctx, DST_ERR_STATE, "bootstrap replicate " + std::to_string(r) + ": malformed replicate tree");
+    }
+    for (uint64_t x = 0; x < N; ++x)
+        support[x] = x < n || parent[x] == 0xFFFFFFFFu ? 0xFFFFFFFFu : count[x];
+    return DST_OK;
 }
 
 int dst_nj_matrix(dst_ctx *ctx, const double *d, uint64_t n, uint32_t *parent, double *length, size_t cap)

@@ -12,6 +12,7 @@ struct dst_ctx {
     int device = 0;
     hipStream_t stream = nullptr;
     DeviceSet set[2];
+    DeviceSet boot;   // dst_nj_bootstrap's replicate: packed like a slot, never one (freed when the call ends)
     // staging for host uploads / unaligned device inputs
     uint8_t *stage = nullptr;
     size_t stage_bytes = 0;

@@ -9,6 +9,9 @@
 #include <cstdlib>
 #include <cstring>
 #include <numeric>
+#include <string>
+#include <unordered_map>
+#include <vector>
 
 #include "dst_internal.h"
 
@@ -316,6 +319,156 @@ std::vector<ConsensusTile> build_consensus_tiles(bool square, uint64_t row_begin
     return out;
 }
 
+bool tree_children(uint64_t n, const uint32_t *parent, std::vector<uint64_t> &first, std::vector<uint64_t> &child,
+                   uint64_t &root)
+{
+    const uint64_t N = 2 * n - 2;
+    first.assign(N + 1, 0);
+    child.assign(N, 0);
+    root = N;
+    for (uint64_t x = 0; x < N; ++x) {
+        if (parent[x] == 0xFFFFFFFFu) {
+            if (root != N)
+                return false;
+            root = x;
+        } else if (parent[x] >= N || parent[x] == x) {
+            return false;
+        } else {
+            ++first[parent[x] + 1];
+        }
+    }
+    if (root == N || root < n)
+        return false;
+    for (uint64_t x = 0; x < N; ++x) {
+        const uint64_t kids = first[x + 1];
+        if (kids != (x < n ? 0u : x == root ? 3u : 2u))
+            return false;
+    }
+    for (uint64_t x = 0; x < N; ++x)
+        first[x + 1] += first[x];
+    {
+        std::vector<uint64_t> fill(first.begin(), first.end() - 1);
+        for (uint64_t x = 0; x < N; ++x)
+            if (x != root)
+                child[fill[parent[x]]++] = x;
+    }
+    // every node below the root: no cycle hangs off the side
+    uint64_t reached = 0;
+    std::vector<uint64_t> stack{root};
+    while (!stack.empty() && reached <= N) {
+        const uint64_t x = stack.back();
+        stack.pop_back();
+        ++reached;
+        for (uint64_t k = first[x]; k < first[x + 1]; ++k)
+            stack.push_back(child[k]);
+    }
+    return reached == N;
+}
+
+// The tree re-rooted at leaf 0: `order` lists the nodes depth first from leaf 0 (a subtree's nodes are contiguous in
+// it), up[v] is v's neighbour towards leaf 0.  The tree passed tree_children.
+void SplitCounter::walk(const uint32_t *parent, std::vector<uint32_t> &order, std::vector<uint32_t> &up)
+{
+    const uint64_t N = 2 * n_ - 2;
+    // undirected adjacency: every edge x - parent[x] in the lists of both ends
+    adj_first_.assign(N + 1, 0);
+    for (uint64_t x = 0; x < N; ++x)
+        if (parent[x] != 0xFFFFFFFFu) {
+            ++adj_first_[x + 1];
+            ++adj_first_[parent[x] + 1];
+        }
+    for (uint64_t x = 0; x < N; ++x)
+        adj_first_[x + 1] += adj_first_[x];
+    adj_.assign(adj_first_[N], 0);
+    std::vector<uint32_t> fill(adj_first_.begin(), adj_first_.end() - 1);
+    for (uint64_t x = 0; x < N; ++x)
+        if (parent[x] != 0xFFFFFFFFu) {
+            adj_[fill[x]++] = parent[x];
+            adj_[fill[parent[x]]++] = (uint32_t)x;
+        }
+    order.clear();
+    up.assign(N, 0xFFFFFFFFu);
+    std::vector<uint32_t> stack{0};
+    while (!stack.empty()) {
+        const uint32_t v = stack.back();
+        stack.pop_back();
+        order.push_back(v);
+        for (uint32_t k = adj_first_[v]; k < adj_first_[v + 1]; ++k) {
+            const uint32_t w = adj_[k];
+            if (w != up[v] && w != 0) {
+                up[w] = v;
+                stack.push_back(w);
+            }
+        }
+    }
+}
+
+// Day (1985): number the leaves other than leaf 0 in a depth-first order from leaf 0, so that the side of every split
+// without leaf 0 is an interval [lo, hi] of those numbers; key each main split by its interval.
+bool SplitCounter::init(uint64_t n, const uint32_t *parent)
+{
+    n_ = n;
+    std::vector<uint64_t> first, child;
+    uint64_t root;
+    if (n < 3 || !tree_children(n, parent, first, child, root))
+        return false;
+    walk(parent, order_, up_);
+    rank_.assign(n, 0);
+    uint32_t next = 0;
+    for (uint32_t v : order_)
+        if (v < n && v != 0)
+            rank_[v] = next++;
+    const uint64_t N = 2 * n - 2;
+    lo_.assign(N, 0xFFFFFFFFu);
+    hi_.assign(N, 0);
+    split_.clear();
+    split_.reserve(2 * n);
+    for (size_t k = order_.size(); k-- > 1;) {   // children before parents; order_[0] is leaf 0
+        const uint32_t v = order_[k];
+        if (v < n) {
+            lo_[v] = hi_[v] = rank_[v];
+        } else {
+            // the edge v - up[v] is the edge above x in the dst_nj rooting
+            const uint32_t x = parent[v] == up_[v] ? v : up_[v];
+            if (x >= n && x != root)
+                split_.emplace(((uint64_t)lo_[v] << 32) | hi_[v], x);
+        }
+        const uint32_t u = up_[v];
+        lo_[u] = std::min(lo_[u], lo_[v]);
+        hi_[u] = std::max(hi_[u], hi_[v]);
+    }
+    return true;
+}
+
+bool SplitCounter::count(const uint32_t *rep_parent, uint32_t *support)
+{
+    std::vector<uint64_t> first, child;
+    uint64_t root;
+    if (!tree_children(n_, rep_parent, first, child, root))
+        return false;
+    walk(rep_parent, order_, up_);
+    const uint64_t N = 2 * n_ - 2;
+    lo_.assign(N, 0xFFFFFFFFu);
+    hi_.assign(N, 0);
+    cnt_.assign(N, 0);
+    for (size_t k = order_.size(); k-- > 1;) {
+        const uint32_t v = order_[k];
+        if (v < n_) {
+            lo_[v] = hi_[v] = rank_[v];
+            cnt_[v] = 1;
+        } else if ((uint64_t)hi_[v] - lo_[v] + 1 == cnt_[v]) {
+            const auto it = split_.find(((uint64_t)lo_[v] << 32) | hi_[v]);
+            if (it != split_.end())
+                ++support[it->second];
+        }
+        const uint32_t u = up_[v];
+        lo_[u] = std::min(lo_[u], lo_[v]);
+        hi_[u] = std::max(hi_[u], hi_[v]);
+        cnt_[u] += cnt_[v];
+    }
+    return true;
+}
+
 }  // namespace dst
 
 // ================================================================================================
@@ -524,9 +677,10 @@ int dst_format_distance(int measure, double as_float, int64_t as_int, char *buf,
 }
 
 // Newick text of a dst_nj tree: children in ascending node id, leaves by their ids (quoted where Newick needs it),
-// lengths as dst_format_distance prints an f64 distance.  Iterative: a caterpillar tree is n levels deep.
-int dst_newick(uint64_t n, const uint32_t *parent, const double *length, const char *chars, const uint64_t *offsets,
-               char *out, size_t cap, size_t *len)
+// lengths as dst_format_distance prints an f64 distance, and support[x] after an internal non-root node's ')' when
+// support is given.  Iterative: a caterpillar tree is n levels deep.
+static int newick_text(uint64_t n, const uint32_t *parent, const double *length, const char *chars, const uint64_t *offsets,
+                const uint32_t *support, char *out, size_t cap, size_t *len)
 {
     if (len)
         *len = 0;
@@ -538,35 +692,10 @@ int dst_newick(uint64_t n, const uint32_t *parent, const double *length, const c
         if (offsets[r] > offsets[r + 1])
             return DST_ERR_ARG;
     const uint64_t N = 2 * n - 2;
-    // children lists (ascending: nodes are visited in id order), one root, the right number of children everywhere
-    std::vector<uint64_t> first(N + 1, 0), child(N);
-    uint64_t root = N;
-    for (uint64_t x = 0; x < N; ++x) {
-        if (parent[x] == 0xFFFFFFFFu) {
-            if (root != N)
-                return DST_ERR_ARG;
-            root = x;
-        } else if (parent[x] >= N || parent[x] == x) {
-            return DST_ERR_ARG;
-        } else {
-            ++first[parent[x] + 1];
-        }
-    }
-    if (root == N || root < n)
+    std::vector<uint64_t> first, child;
+    uint64_t root;
+    if (!tree_children(n, parent, first, child, root))
         return DST_ERR_ARG;
-    for (uint64_t x = 0; x < N; ++x) {
-        const uint64_t kids = first[x + 1];
-        if (kids != (x < n ? 0u : x == root ? 3u : 2u))
-            return DST_ERR_ARG;
-    }
-    for (uint64_t x = 0; x < N; ++x)
-        first[x + 1] += first[x];
-    {
-        std::vector<uint64_t> fill(first.begin(), first.end() - 1);
-        for (uint64_t x = 0; x < N; ++x)
-            if (x != root)
-                child[fill[parent[x]]++] = x;
-    }
     auto quoted = [](const char *s, size_t l) {
         if (l == 0)
             return true;
@@ -617,6 +746,8 @@ int dst_newick(uint64_t n, const uint32_t *parent, const double *length, const c
         }
         if (x_ >= n)
             text += ')';
+        if (support && x_ >= n && x_ != root)
+            text += std::to_string(support[x_]);
         if (x_ != root) {
             text += ':';
             const int l = dst_format_distance(DST_RAW, length[x_], 0, num, sizeof num);
@@ -632,6 +763,18 @@ int dst_newick(uint64_t n, const uint32_t *parent, const double *length, const c
         return DST_ERR_CAPACITY;
     std::memcpy(out, text.data(), text.size());
     return DST_OK;
+}
+
+int dst_newick(uint64_t n, const uint32_t *parent, const double *length, const char *chars, const uint64_t *offsets,
+               char *out, size_t cap, size_t *len)
+{
+    return newick_text(n, parent, length, chars, offsets, nullptr, out, cap, len);
+}
+
+int dst_newick_support(uint64_t n, const uint32_t *parent, const double *length, const char *chars,
+                       const uint64_t *offsets, const uint32_t *support, char *out, size_t cap, size_t *len)
+{
+    return newick_text(n, parent, length, chars, offsets, support, out, cap, len);
 }
 
 }  // extern "C"

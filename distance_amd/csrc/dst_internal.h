@@ -5,6 +5,7 @@
 #include <cstddef>
 #include <cstdint>
 #include <string>
+#include <unordered_map>
 #include <vector>
 
 #include <hip/hip_runtime.h>
@@ -416,6 +417,12 @@ hipError_t launch_nj_mirror(double *D, uint64_t n, hipStream_t stream);
 // every round, the root included, into b.parent / b.length; n >= 3, D[0] symmetric with a +0.0 diagonal
 hipError_t launch_nj_rounds(const NjBuffers &b, uint64_t n, hipStream_t stream);
 
+// ---- bootstrap replicates (dst_bootstrap.hip, driven by dst_nj_bootstrap in dst_api.cpp) -----------------------------
+// replicate r of the n x len codes at src (rows pitch bytes apart, pitch a multiple of 128 and >= len) into out (the same
+// pitch): out[i][c] := src[i][boot_column(seed, r * len + c, len)]; map: len entries of scratch
+hipError_t launch_boot_resample(const uint8_t *src, uint64_t pitch, uint8_t *out, uint64_t n, uint64_t len, uint64_t seed,
+                                uint32_t replicate, uint32_t *map, hipStream_t stream);
+
 // ---- host-only logic (dst_host.cpp) ----------------------------------------------------------
 int tally_width(int measure);
 bool measure_is_int(int measure);
@@ -431,5 +438,22 @@ struct RowSlab {
     uint64_t rb, re, first, pairs;
 };
 std::vector<RowSlab> cut_row_slabs(bool square, uint64_t n_rows, uint64_t n_cols, uint64_t max_pairs);
+// dst_newick's shape checks of a dst_nj tree (2n - 2 nodes): ids in range, exactly one root, three children at the root,
+// two at every other internal node, none at a leaf, every node below the root.  The children of x in ascending id are
+// child[first[x] .. first[x + 1]).
+bool tree_children(uint64_t n, const uint32_t *parent, std::vector<uint64_t> &first, std::vector<uint64_t> &child,
+                   uint64_t &root);
+// Bootstrap support (dst_nj_bootstrap): the main tree's splits, each internal non-root node x's, keyed exactly by an
+// interval of leaf numbers; count() adds 1 to support[x] for every main split a replicate tree holds.  O(n) per tree.
+class SplitCounter {
+public:
+    bool init(uint64_t n, const uint32_t *parent);        // false: not a valid tree (tree_children)
+    bool count(const uint32_t *rep_parent, uint32_t *support);
+private:
+    void walk(const uint32_t *parent, std::vector<uint32_t> &order, std::vector<uint32_t> &up);
+    uint64_t n_ = 0;
+    std::vector<uint32_t> rank_, order_, up_, lo_, hi_, cnt_, adj_, adj_first_;
+    std::unordered_map<uint64_t, uint32_t> split_;   // (lo << 32 | hi) -> main node
+};
 
 }  // namespace dst

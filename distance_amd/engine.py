@@ -111,8 +111,10 @@ def format_distance(measure, value) -> str:
     return buf.value.decode()
 
 
-def newick(parent, length, ids) -> bytes:
-    """Newick text of a tree from Engine.nj / nj_matrix (dst_newick): ids name the leaves 0..n-1 (str or bytes)."""
+def newick(parent, length, ids, support=None) -> bytes:
+    """Newick text of a tree from Engine.nj / nj_matrix (dst_newick): ids name the leaves 0..n-1 (str or bytes).
+    support: uint32[2n-2] from Engine.nj_bootstrap, written after every internal non-root node's ')' (dst_newick_support);
+    None gives dst_newick's text."""
     parent = np.ascontiguousarray(parent, np.uint32)
     length = np.ascontiguousarray(length, np.float64)
     names = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
@@ -123,16 +125,34 @@ def newick(parent, length, ids) -> bytes:
     if len(parent) != max(2 * n - 2, 0) or len(length) != len(parent):
         raise ValueError("parent and length need 2n - 2 entries for n ids")
     lib = load()
+    if support is None:
+        name = "dst_newick"
+        call = lambda out, cap, need: lib.dst_newick(n, parent.ctypes.data, length.ctypes.data, chars,  # noqa: E731
+                                                     offsets.ctypes.data, out, cap, need)
+    else:
+        support = np.ascontiguousarray(support, np.uint32)
+        if len(support) != len(parent):
+            raise ValueError("support needs 2n - 2 entries for n ids")
+        name = "dst_newick_support"
+        call = lambda out, cap, need: lib.dst_newick_support(n, parent.ctypes.data, length.ctypes.data,  # noqa: E731
+                                                             chars, offsets.ctypes.data, support.ctypes.data, out,
+                                                             cap, need)
     need = C.c_size_t(0)
-    rc = lib.dst_newick(n, parent.ctypes.data, length.ctypes.data, chars, offsets.ctypes.data, None, 0, C.byref(need))
+    rc = call(None, 0, C.byref(need))
     if rc not in (0, 6):
-        raise DistanceError(rc, "dst_newick: malformed tree or arguments")
+        raise DistanceError(rc, f"{name}: malformed tree or arguments")
     buf = C.create_string_buffer(max(need.value, 1))
-    rc = lib.dst_newick(n, parent.ctypes.data, length.ctypes.data, chars, offsets.ctypes.data, buf, need.value,
-                        C.byref(need))
+    rc = call(buf, need.value, C.byref(need))
     if rc:
-        raise DistanceError(rc, "dst_newick")
+        raise DistanceError(rc, name)
     return buf.raw[:need.value]
+
+
+def bootstrap_columns(seed: int, replicate: int, length: int) -> np.ndarray:
+    """The source column of every column of bootstrap replicate `replicate` (dst_bootstrap_columns): uint32[length]."""
+    cols = np.zeros(max(int(length), 1), np.uint32)
+    load().dst_bootstrap_columns(int(seed), int(replicate), int(length), cols.ctypes.data)
+    return cols[:int(length)]
 
 
 class Engine:
@@ -370,6 +390,30 @@ class Engine:
         parent, length = np.zeros(cap, np.uint32), np.zeros(cap, np.float64)
         self._check(self._lib.dst_nj(self._h, m, int(max_pairs), parent.ctypes.data, length.ctypes.data, 2 * n - 2))
         return parent, length
+
+    def nj_bootstrap(self, measure, codes, parent, replicates: int, seed: int = 1, max_pairs: int = 0,
+                     trees: bool = False):
+        """Bootstrap support of the main tree `parent` (dst_nj_bootstrap) from `replicates` column resamplings of
+        `codes` (n x L uint8, host memory; slots 0 and 1 are not touched): support uint32[2n-2], the number of
+        replicate trees that hold the split of each internal non-root node (0xFFFFFFFF at leaves and the root).
+        trees=True: (support, replicate parents uint32[replicates, 2n-2])."""
+        m = _measure_id(measure)
+        codes = np.asarray(codes)
+        if codes.dtype != np.uint8 or codes.ndim != 2:
+            raise ValueError("codes must be a 2-D uint8 array")
+        codes = np.ascontiguousarray(codes)
+        n, L = codes.shape
+        parent = np.ascontiguousarray(parent, np.uint32)
+        N = max(2 * n - 2, 1)
+        if len(parent) != 2 * n - 2:
+            raise ValueError("parent needs 2n - 2 entries for n records")
+        support = np.zeros(N, np.uint32)
+        reps = np.zeros((max(int(replicates), 1), N), np.uint32) if trees else None
+        self._check(self._lib.dst_nj_bootstrap(self._h, m, codes.ctypes.data, n, L, max(L, 1), int(replicates),
+                                               int(seed) & 0xFFFFFFFFFFFFFFFF, int(max_pairs), parent.ctypes.data,
+                                               support.ctypes.data, None if reps is None else reps.ctypes.data,
+                                               2 * n - 2))
+        return (support, reps) if trees else support
 
     def nj_matrix(self, d):
         """Neighbour-joining tree of an n x n distance matrix (dst_nj_matrix; only the strict upper triangle is read):

@@ -397,6 +397,39 @@ int dst_nj_matrix(dst_ctx *ctx, const double *d, uint64_t n, uint32_t *parent, d
  * one root, a cycle, a leaf with children, an internal node without 2 children or a root without 3). */
 int dst_newick(uint64_t n, const uint32_t *parent, const double *length, const char *chars, const uint64_t *offsets,
                char *out, size_t cap, size_t *len);
+
+/* ---- bootstrap support of neighbour-joining trees ------------------------------------------------------------------ */
+/* Replicate columns.  Replicate r (0-based) of an alignment of len sites has len columns; its column c is source column
+ * col(seed, r, c), from SplitMix64 output number k = r * len + c of a generator seeded with `seed` (all mod 2^64):
+ *   z = seed + (k + 1) * 0x9E3779B97F4A7C15
+ *   z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9
+ *   z = (z ^ (z >> 27)) * 0x94D049BB133111EB
+ *   z =  z ^ (z >> 31)
+ *   col = the high 64 bits of the 128-bit product z * len
+ * dst_bootstrap_columns (host only, no GPU) writes the len columns of one replicate; the device computes the same
+ * function (one definition serves both). */
+void dst_bootstrap_columns(uint64_t seed, uint32_t replicate, uint64_t len, uint32_t *cols);
+/* Bootstrap support of a main tree.  codes: n x len host Paradis bytes, rows row_stride bytes apart (as for dst_upload),
+ * copied to the device once per call.  Replicate tree: exactly the tree dst_nj would return with the replicate alignment
+ * uploaded to slot 0 (tn93 base counts counted by code from the replicate), so it depends on neither the path nor
+ * max_pairs.  parent: the main tree in dst_nj form on n leaves, validated as dst_newick validates it.  Each internal
+ * non-root node x (n <= x < 2n - 3) defines one split, the leaves below x or their complement, whichever side does not
+ * hold leaf 0; support[x] = the number of replicates whose tree holds that split as an unrooted bipartition (compared
+ * exactly; zero-length edges count).  Leaves and the root get UINT32_MAX.  cap: the room of support in entries (below
+ * 2n - 2: DST_ERR_CAPACITY).  rep_parent: NULL, or replicates x (2n - 2) entries that receive every replicate's parent
+ * array in order.  replicates in 1..=10000.
+ * Per replicate, on the context's stream: resample (on the device, from the call's copy of the codes), pack, fill the
+ * square, the NJ rounds; the split count runs on the host.  Slots 0 and 1 are neither read nor changed.
+ * Errors: DST_ERR_ARG for a bad argument or tree; DST_ERR_STATE when a replicate has a non-finite distance (raw NaN for a
+ * record without a resolved site in the replicate, jc69 inf): the message names the replicate and the first pair in
+ * canonical order; DST_ERR_INVALID_CODE as dst_upload; DST_ERR_NOMEM as dst_nj.  Synchronous on the context's stream. */
+int dst_nj_bootstrap(dst_ctx *ctx, int measure, const uint8_t *codes, size_t n, size_t len, size_t row_stride,
+                     uint32_t replicates, uint64_t seed, uint64_t max_pairs, const uint32_t *parent, uint32_t *support,
+                     uint32_t *rep_parent, size_t cap);
+/* dst_newick with support labels: an internal non-root node x is written (children)S:length, S = support[x] in decimal;
+ * leaves and the root as dst_newick writes them.  support == NULL: byte for byte dst_newick. */
+int dst_newick_support(uint64_t n, const uint32_t *parent, const double *length, const char *chars,
+                       const uint64_t *offsets, const uint32_t *support, char *out, size_t cap, size_t *len);
 /* Page-locked host memory for the *_host forms' output buffers (copy-back by DMA at link speed instead
  * of through a pageable bounce buffer).  Free with dst_host_free. */
 int dst_host_alloc(size_t bytes, void **ptr);
