@@ -21,6 +21,15 @@ ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size
 SLAB_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64, C.c_uint64, C.c_void_p)
 
 
+class LaunchInfo(C.Structure):
+    """dst_launch_info"""
+    _fields_ = [("path", C.c_int), ("measure", C.c_int), ("family", C.c_int), ("out_kind", C.c_int), ("wide", C.c_int),
+                ("square", C.c_int), ("event_waves", C.c_int), ("heavy_events", C.c_int), ("rows_per_tile", C.c_uint32),
+                ("tile_cols", C.c_uint32), ("tiles", C.c_uint64), ("hot", C.c_int), ("run_records", C.c_int),
+                ("variant", C.c_int), ("ksplit", C.c_uint32), ("pairs", C.c_uint64), ("events_per_pair", C.c_double),
+                ("list_length", C.c_double), ("run_adds", C.c_double)]
+
+
 class DistanceError(RuntimeError):
     def __init__(self, status: int, message: str):
         super().__init__(f"[dst status {status}] {message}")
@@ -50,6 +59,9 @@ _SIGS = {
     "dst_set_ksplit": (C.c_int, [_vp, C.c_int]),
     "dst_set_path": (C.c_int, [_vp, C.c_int]),
     "dst_last_path": (C.c_int, [_vp]),
+    "dst_last_launch": (C.c_int, [_vp, _vp]),
+    "dst_plan_consensus_launch": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, C.c_uint64,
+                                            C.c_double, C.c_double, C.c_double, C.c_int, _vp]),
     "dst_run_records": (C.c_int, [_vp, C.c_int, _u64p, _u64p]),
     "dst_planes_stored": (C.c_int, [_vp, C.c_int, C.POINTER(C.c_int)]),
     "dst_consensus": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t]),

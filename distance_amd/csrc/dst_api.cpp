@@ -809,6 +809,52 @@ int cheapest_path(const DeviceSet &rows, const DeviceSet &cols, int measure, uin
     return path;
 }
 
+// Which variant of the consensus pair kernel a launch gets: the tile height, the split of the workgroup's waves between
+// the event and the output role, and with it the instantiation (EW).  Pure host code, no context: run_sets launches what
+// this says and reports it (dst_last_launch), dst_plan_consensus_launch answers the same for any shape.
+//  events_per_pair / list_length: the sample's view of the launch's event load (the figures the path choice reads)
+//  run_adds: what the run records' correction tables add per pair; hot: the launch adds the hot columns' tallies (hybrid)
+void plan_consensus_launch(int measure, int out_kind, bool wide, bool square, uint64_t n_rows, uint64_t n_cols, uint64_t total_pairs,
+                           double events_per_pair, double list_length, double run_adds, bool hot, dst_launch_info *info)
+{
+    // rows per tile: 32, fewer for launches that would not fill the GPU a few times over (256 CUs x 3 workgroups:
+    // a 10,000-record job is 800 tiles of 32 rows — one round and a nearly empty second one)
+    uint32_t rows_per_tile = kConsensusRowsPerTile;
+    const uint64_t n_panels = (n_cols + kPanelCols - 1) / kPanelCols;
+    auto tiles_at = [&](uint32_t r) { return n_panels * ((n_rows + r - 1) / r) / (square ? 2 : 1); };
+    while (rows_per_tile > 8 && tiles_at(rows_per_tile) < 8 * 768)
+        rows_per_tile /= 2;
+    // The 4 + 4 wave split beyond event-heavy launches (raw at 50,000 x 30,000 unless noted): any run records at all
+    // (1 % of the records: 2.36 against 2.65 ms, 5 %: 3.14 against 3.38 — their adds come at the point of use, not
+    // through the events' pipeline); hybrid launches (the event waves also bring in the hot columns' tallies, a
+    // word per pair); launches of a few rounds of workgroups (10,000 records: raw 0.121 -> 0.117 ms, n_high 0.111 ->
+    // 0.108, k80 0.199 -> 0.193; even at 20,000, 0.4 % slower at 30,000: with little to overlap it with, a tile's
+    // first events are what a workgroup waits for).  Not tn93, whose eight waves all take both roles
+    // (event_waves()), and not jc69 (0.128 -> 0.154 ms at 10,000 records: its f64 output wants the six waves).
+    const bool split_helps = measure != DST_TN93 && measure != DST_JC69 &&
+                             (run_adds > 0.0 || hot || total_pairs < 120000000ull);
+    const int heavy_events = events_per_pair + run_adds > 1.0 ? 2
+                             : events_per_pair + run_adds > 0.3 || list_length > 100.0 || split_helps ? 1 : 0;
+    info->measure = measure;
+    info->family = family_of(measure);
+    info->out_kind = out_kind;
+    info->wide = wide ? 1 : 0;
+    info->square = square ? 1 : 0;
+    info->heavy_events = heavy_events;
+    info->event_waves = consensus_event_waves(measure, out_kind, wide, heavy_events);
+    info->rows_per_tile = rows_per_tile;
+    info->tile_cols = kPanelCols;
+    info->tiles = tiles_at(rows_per_tile);
+    info->hot = hot ? 1 : 0;
+    info->run_records = run_adds > 0.0 ? 1 : 0;
+    info->variant = 0;
+    info->ksplit = 0;
+    info->pairs = total_pairs;
+    info->events_per_pair = events_per_pair;
+    info->list_length = list_length;
+    info->run_adds = run_adds;
+}
+
 int run_common(dst_ctx *ctx, int measure, bool square, int row_slot, int col_slot, uint64_t rb,
                uint64_t re, int out_kind, void *d_out, size_t cap, void *stream_v)
 {
@@ -916,15 +962,18 @@ int run_sets(dst_ctx *ctx, int measure, bool square, DeviceSet &rows, DeviceSet 
             rc = ensure_aconst(ctx, rows, cols, fam, wide, stream);
         const void *d_tiles = nullptr;
         uint32_t ntiles = 0;
-        // rows per tile: 32, fewer for launches that would not fill the GPU a few times over (256 CUs x 3 workgroups:
-        // a 10,000-record job is 800 tiles of 32 rows — one round and a nearly empty second one)
-        uint32_t rows_per_tile = kConsensusRowsPerTile;
-        {
-            const uint64_t n_panels = (cols.n + kPanelCols - 1) / kPanelCols;
-            auto tiles_at = [&](uint32_t r) { return n_panels * ((re - rb + r - 1) / r) / (square ? 2 : 1); };
-            while (rows_per_tile > 8 && tiles_at(rows_per_tile) < 8 * 768)
-                rows_per_tile /= 2;
+        dst_launch_info li{};
+        {   // the sample's view of this launch's event load (the same figures the path choice reads)
+            const uint64_t *st = cols.ref.h_stats;
+            const double S = (double)std::max<uint64_t>(st[3], 1);
+            const double f = run_scale(cols);
+            const double events = f * f * (double)(hybrid ? st[7] : st[2]) / (S * S), list = f * (double)(hybrid ? st[6] : st[1]) / S;
+            // (a run record's row or column adds one word per pair from the correction tables: like an event, a cheaper one)
+            const double run_adds = cols.runs.active && square ? 2.0 * cols.runs.n_run / std::max<double>((double)cols.n, 1.0) : 0.0;
+            plan_consensus_launch(measure, out_kind, wide, square, re - rb, cols.n, total_pairs, events, list, run_adds, hybrid, &li);
+            li.path = path;
         }
+        const uint32_t rows_per_tile = li.rows_per_tile;
         if (!rc)
             rc = prepare_schedule(ctx, square, rb, re, cols.n, (int)rows_per_tile, -1, stream, &d_tiles, &ntiles);
         if (rc)
@@ -992,24 +1041,9 @@ int run_sets(dst_ctx *ctx, int measure, bool square, DeviceSet &rows, DeviceSet 
         cl.wide = wide;
         cl.d_lut = ctx->d_lut;
         cl.d_hot = d_hot;
-        {   // the sample's view of this launch's event load (the same figures the path choice reads)
-            const uint64_t *st = cols.ref.h_stats;
-            const double S = (double)std::max<uint64_t>(st[3], 1);
-            const double f = run_scale(cols);
-            const double events = f * f * (double)(hybrid ? st[7] : st[2]) / (S * S), list = f * (double)(hybrid ? st[6] : st[1]) / S;
-            // (a run record's row or column adds one word per pair from the correction tables: like an event, a cheaper one)
-            const double run_adds = cols.runs.active && square ? 2.0 * cols.runs.n_run / std::max<double>((double)cols.n, 1.0) : 0.0;
-            // The 4 + 4 wave split beyond event-heavy launches (raw at 50,000 x 30,000 unless noted): any run records at all
-            // (1 % of the records: 2.36 against 2.65 ms, 5 %: 3.14 against 3.38 — their adds come at the point of use, not
-            // through the events' pipeline); hybrid launches (the event waves also bring in the hot columns' tallies, a
-            // word per pair); launches of a few rounds of workgroups (10,000 records: raw 0.121 -> 0.117 ms, n_high 0.111 ->
-            // 0.108, k80 0.199 -> 0.193; even at 20,000, 0.4 % slower at 30,000: with little to overlap it with, a tile's
-            // first events are what a workgroup waits for).  Not tn93, whose eight waves all take both roles
-            // (event_waves()), and not jc69 (0.128 -> 0.154 ms at 10,000 records: its f64 output wants the six waves).
-            const bool split_helps = measure != DST_TN93 && measure != DST_JC69 &&
-                                     (run_adds > 0.0 || d_hot || total_pairs < 120000000ull);
-            cl.heavy_events = events + run_adds > 1.0 ? 2 : events + run_adds > 0.3 || list > 100.0 || split_helps ? 1 : 0;
-        }
+        cl.heavy_events = li.heavy_events;   // (li.hot == (d_hot != NULL) for every launch with tiles)
+        li.tiles = ntiles;
+        ctx->last_launch = li;
         ctx->last_path = path;
         if (ntiles) {
             if (int rc_t = timer_begin(ctx, 0, stream))
@@ -1064,6 +1098,21 @@ int run_sets(dst_ctx *ctx, int measure, bool square, DeviceSet &rows, DeviceSet 
     if (out_kind == DST_OUT_TALLY16)
         ksplit = 1;  // no 16-bit atomics: such launches sweep L in one piece
     pl.ksplit = ksplit;
+    {
+        dst_launch_info li{};
+        li.path = DST_PATH_DENSE;
+        li.measure = measure;
+        li.family = family_of(measure);
+        li.out_kind = out_kind;
+        li.square = square ? 1 : 0;
+        li.rows_per_tile = (uint32_t)ts.bm;
+        li.tile_cols = (uint32_t)ts.bn;
+        li.tiles = nblocks;
+        li.variant = ctx->variant >= 0 && ctx->variant < variant_count(measure) ? ctx->variant : 0;
+        li.ksplit = ksplit;
+        li.pairs = total_pairs;
+        ctx->last_launch = li;
+    }
     const bool f64_out = out_kind == DST_OUT_DISTANCE && !measure_is_int(measure);
     if (nblocks && ksplit > 1) {
         if (f64_out) {
@@ -1300,6 +1349,33 @@ int dst_set_path(dst_ctx *ctx, int path)
 }
 
 int dst_last_path(const dst_ctx *ctx) { return ctx ? ctx->last_path : -1; }
+
+int dst_last_launch(const dst_ctx *ctx, dst_launch_info *info)
+{
+    if (!ctx || !info)
+        return DST_ERR_ARG;
+    *info = ctx->last_launch;
+    return DST_OK;
+}
+
+int dst_plan_consensus_launch(int measure, int out_kind, int wide, int square, uint64_t n_rows_in_launch, uint64_t n_cols,
+                              uint64_t total_pairs, double events_per_pair, double list_length, double run_adds, int hot,
+                              dst_launch_info *info)
+{
+    if (measure < DST_N || measure > DST_TN93 || !info)
+        return DST_ERR_ARG;
+    if (out_kind != DST_OUT_DISTANCE && out_kind != DST_OUT_TALLY && out_kind != DST_OUT_TALLY16)
+        return DST_ERR_ARG;
+    if (out_kind == DST_OUT_TALLY16 && wide)
+        return DST_ERR_ARG;   // 16-bit tallies end below 65,536 sites, where the wide packing begins
+    if (!(events_per_pair >= 0.0) || !(list_length >= 0.0) || !(run_adds >= 0.0))
+        return DST_ERR_ARG;
+    *info = dst_launch_info{};
+    plan_consensus_launch(measure, out_kind, wide != 0, square != 0, n_rows_in_launch, n_cols, total_pairs, events_per_pair,
+                          list_length, run_adds, hot != 0, info);
+    info->path = hot ? DST_PATH_HYBRID : DST_PATH_CONSENSUS;
+    return DST_OK;
+}
 
 int dst_run_records(const dst_ctx *ctx, int slot, uint64_t *run_records, uint64_t *entries_removed)
 {

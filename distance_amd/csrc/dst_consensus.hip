@@ -2626,35 +2626,80 @@ hipError_t launch_cpair_ew(const ConsensusLaunch &cl, const FWords &fw, hipStrea
     return hipGetLastError();
 }
 
+// EW of the instantiation a launch of <FAM, WIDE, OUT> gets for ConsensusLaunch::heavy_events: the one choice, read by
+// the launcher and by the plan (consensus_event_waves)
+template <int FAM, bool WIDE, int OUT>
+constexpr int cpair_event_waves(int heavy_events)
+{
+    return heavy_events >= 2 ? kEventWavesAll : heavy_events ? kEventWavesHeavy : event_waves<FAM, WIDE, OUT>();
+}
+
 template <int FAM, bool WIDE, int OUT>
 hipError_t launch_cpair(const ConsensusLaunch &cl, const FWords &fw, hipStream_t stream)
 {
-    if (cl.heavy_events >= 2)
+    const int ew = cpair_event_waves<FAM, WIDE, OUT>(cl.heavy_events);
+    if (ew == kEventWavesAll)
         return launch_cpair_ew<FAM, WIDE, OUT, kEventWavesAll>(cl, fw, stream);
-    if (cl.heavy_events)
+    if (ew == kEventWavesHeavy)
         return launch_cpair_ew<FAM, WIDE, OUT, kEventWavesHeavy>(cl, fw, stream);
     return launch_cpair_ew<FAM, WIDE, OUT, event_waves<FAM, WIDE, OUT>()>(cl, fw, stream);
 }
 
-template <int FAM, bool WIDE>
-hipError_t launch_cpair_outputs(int measure, const ConsensusLaunch &cl, const FWords &fw, hipStream_t stream)
+// what the dispatch below does with the <FAM, WIDE, OUT> it arrives at: launch it, or say which EW it would get
+struct CpairLaunchOp {
+    const ConsensusLaunch &cl;
+    const FWords &fw;
+    hipStream_t stream;
+    template <int FAM, bool WIDE, int OUT>
+    hipError_t run() const { return launch_cpair<FAM, WIDE, OUT>(cl, fw, stream); }
+};
+struct CpairPlanOp {
+    int heavy_events;
+    int *ew;
+    template <int FAM, bool WIDE, int OUT>
+    hipError_t run() const
+    {
+        *ew = cpair_event_waves<FAM, WIDE, OUT>(heavy_events);
+        return hipSuccess;
+    }
+};
+
+template <int FAM, bool WIDE, typename Op>
+hipError_t cpair_outputs(int measure, int out_kind, const Op &op)
 {
-    if (cl.out_kind == DST_OUT_TALLY)
-        return launch_cpair<FAM, WIDE, OUT_TALLY>(cl, fw, stream);
-    if (cl.out_kind == DST_OUT_TALLY16) {
+    if (out_kind == DST_OUT_TALLY)
+        return op.template run<FAM, WIDE, OUT_TALLY>();
+    if (out_kind == DST_OUT_TALLY16) {
         if constexpr (!WIDE)
-            return launch_cpair<FAM, WIDE, OUT_TALLY16>(cl, fw, stream);
+            return op.template run<FAM, WIDE, OUT_TALLY16>();
         return hipErrorInvalidValue;
     }
     if constexpr (FAM == FAM_NHIGH)
-        return launch_cpair<FAM, WIDE, OUT_INT>(cl, fw, stream);
+        return op.template run<FAM, WIDE, OUT_INT>();
     else if constexpr (FAM == FAM_RAW)
-        return measure == DST_RAW ? launch_cpair<FAM, WIDE, DST_RAW>(cl, fw, stream)
-                                  : launch_cpair<FAM, WIDE, DST_JC69>(cl, fw, stream);
+        return measure == DST_RAW ? op.template run<FAM, WIDE, DST_RAW>() : op.template run<FAM, WIDE, DST_JC69>();
     else if constexpr (FAM == FAM_K80)
-        return launch_cpair<FAM, WIDE, DST_K80>(cl, fw, stream);
+        return op.template run<FAM, WIDE, DST_K80>();
     else
-        return launch_cpair<FAM, WIDE, DST_TN93>(cl, fw, stream);
+        return op.template run<FAM, WIDE, DST_TN93>();
+}
+
+template <typename Op>
+hipError_t cpair_dispatch(int measure, int out_kind, bool wide, const Op &op)
+{
+#define DST_FAM(F)                                                             \
+    case F:                                                                    \
+        return wide ? cpair_outputs<F, true>(measure, out_kind, op)            \
+                    : cpair_outputs<F, false>(measure, out_kind, op);
+    switch (family_of(measure)) {
+        DST_FAM(FAM_NHIGH)
+        DST_FAM(FAM_RAW)
+        DST_FAM(FAM_K80)
+        DST_FAM(FAM_TN93)
+    default: break;
+    }
+#undef DST_FAM
+    return hipErrorInvalidValue;
 }
 
 }  // namespace
@@ -2665,20 +2710,13 @@ hipError_t launch_consensus_pairs(int measure, const ConsensusLaunch &cl, const 
     FWords fw;
     for (int w = 0; w < kMaxWords; ++w)
         fw.w[w] = f_words[w];
-    const int fam = family_of(measure);
-#define DST_FAM(F)                                                                     \
-    case F:                                                                            \
-        return cl.wide ? launch_cpair_outputs<F, true>(measure, cl, fw, stream)        \
-                       : launch_cpair_outputs<F, false>(measure, cl, fw, stream);
-    switch (fam) {
-        DST_FAM(FAM_NHIGH)
-        DST_FAM(FAM_RAW)
-        DST_FAM(FAM_K80)
-        DST_FAM(FAM_TN93)
-    default: break;
-    }
-#undef DST_FAM
-    return hipErrorInvalidValue;
+    return cpair_dispatch(measure, cl.out_kind, cl.wide, CpairLaunchOp{cl, fw, stream});
+}
+
+int consensus_event_waves(int measure, int out_kind, bool wide, int heavy_events)
+{
+    int ew = 0;
+    return cpair_dispatch(measure, out_kind, wide, CpairPlanOp{heavy_events, &ew}) == hipSuccess ? ew : 0;
 }
 
 hipError_t launch_shared_block(uint32_t *block, const SharedLayout &lay, const DeviceSet &set, size_t rec_begin, size_t count,

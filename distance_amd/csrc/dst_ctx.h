@@ -38,6 +38,7 @@ struct dst_ctx {
     int path = DST_PATH_AUTO;         // dst_set_path
     double prep_min_work = 2.0e10;    // dst_set_prep_threshold: site comparisons below which DST_PATH_AUTO stays dense unasked
     int last_path = DST_PATH_DENSE;   // what the most recent run used
+    dst_launch_info last_launch = {-1};   // ... and which kernel variant its pair launch was (dst_last_launch; path -1: none yet)
     // consensus path: tables, counters and scratch shared by the two sets
     ConsensusLut *d_lut = nullptr;
     unsigned long long *d_total = nullptr;

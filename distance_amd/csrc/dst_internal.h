@@ -309,6 +309,9 @@ hipError_t launch_sum2_u32(const uint32_t *a0, const uint32_t *a1, size_t n, uns
 // f_words: F_k (known reference sites x the per-site unit), packed like the accumulators
 hipError_t launch_consensus_pairs(int measure, const ConsensusLaunch &cl, const uint32_t f_words[kMaxWords],
                                   hipStream_t stream);
+// EW of the consensus_pair_kernel<FAM, WIDE, OUT, EW> that launch_consensus_pairs picks for (measure, out_kind, wide,
+// heavy_events), by the launcher's own dispatch; 0 for a combination it refuses.  Pure host code.
+int consensus_event_waves(int measure, int out_kind, bool wide, int heavy_events);
 // exact per-site counts of known G, C, T over the records of `set`, added into hist[len][3]
 hipError_t launch_site_hist(const DeviceSet &set, uint32_t *hist, hipStream_t stream);
 

@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import ALLGATHER_FN, SLAB_SINK, DistanceError, load
+from ._lib import ALLGATHER_FN, SLAB_SINK, DistanceError, LaunchInfo, load
 
 MEASURES = {"n": 0, "n_high": 1, "raw": 2, "jc69": 3, "k80": 4, "tn93": 5}
 INT_MEASURES = ("n", "n_high")
@@ -85,6 +85,37 @@ def plan_tiles(square: bool, row_begin: int, row_end: int, n_cols: int, measure,
         raise DistanceError(rc, "dst_plan_tiles")
     ij = ij[:count.value]
     return ij, bm.value, bn.value
+
+
+_PATH_NAMES = {1: "dense", 2: "consensus", 3: "hybrid"}
+_MEASURE_NAMES = {v: k for k, v in MEASURES.items()}
+
+
+def _launch_dict(li: LaunchInfo) -> dict:
+    d = {name: getattr(li, name) for name, _ in LaunchInfo._fields_}
+    d["path"] = _PATH_NAMES.get(li.path)
+    d["measure"] = _MEASURE_NAMES.get(li.measure)
+    for key in ("wide", "square", "hot", "run_records"):
+        d[key] = bool(d[key])
+    return d
+
+
+def plan_consensus_launch(measure, out_kind: int = OUT_DISTANCE, wide: bool = False, square: bool = True, n_rows: int = 0,
+                          n_cols: int = 0, total_pairs: int | None = None, events_per_pair: float = 0.0,
+                          list_length: float = 0.0, run_adds: float = 0.0, hot: bool = False) -> dict:
+    """Which consensus pair kernel variant and tile height a launch of n_rows rows against n_cols column records would get
+    (dst_plan_consensus_launch; no GPU needed): a dict like Engine.last_launch()."""
+    if total_pairs is None:
+        total_pairs = n_rows * n_cols
+        if square:   # rows [0, n_rows) of the n_cols x n_cols triangle
+            total_pairs = n_rows * n_cols - n_rows * (n_rows + 1) // 2
+    li = LaunchInfo()
+    rc = load().dst_plan_consensus_launch(_measure_id(measure), int(out_kind), int(wide), int(square), int(n_rows), int(n_cols),
+                                          int(total_pairs), float(events_per_pair), float(list_length), float(run_adds),
+                                          int(hot), C.byref(li))
+    if rc:
+        raise DistanceError(rc, "dst_plan_consensus_launch")
+    return _launch_dict(li)
 
 
 def finalize(measure, tallies, q_counts=None, t_counts=None):
@@ -204,6 +235,15 @@ class Engine:
 
     def last_path(self) -> str:
         return {1: "dense", 2: "consensus", 3: "hybrid"}.get(self._lib.dst_last_path(self._h), "?")
+
+    def last_launch(self) -> dict:
+        """Which kernel variant the most recent pair launch was (dst_last_launch): path, measure, family, out_kind, wide,
+        square, event_waves (EW of the consensus pair kernel as instantiated; 0: dense), heavy_events, rows_per_tile, tiles,
+        hot, run_records, variant and ksplit (dense), pairs, and the sampled figures the choice was made from.
+        path is None before the first launch."""
+        li = LaunchInfo()
+        self._check(self._lib.dst_last_launch(self._h, C.byref(li)))
+        return _launch_dict(li)
 
     def run_records(self, slot: int = 0) -> tuple[int, int]:
         """(records the consensus path treats as run records — long runs of N left out of their lists —, entries removed)"""

@@ -136,6 +136,39 @@ int dst_run_records(const dst_ctx *ctx, int slot, uint64_t *run_records, uint64_
 int dst_planes_stored(const dst_ctx *ctx, int slot, int *stored);
 /* DST_PATH_DENSE, DST_PATH_CONSENSUS or DST_PATH_HYBRID: what the most recent run on this context used */
 int dst_last_path(const dst_ctx *ctx);
+/* Which kernel variant the most recent pair launch of this context was.  The consensus pair kernel is a family of
+ * instantiations <tally family, wide, output, event waves> and three tile heights, chosen per launch from its size and the
+ * sampled statistics of the column set; the dense kernels have tile variants and a split-L factor.  Diagnostic: tests
+ * assert with it that a shape reached the variant it was written for; the results do not depend on it. */
+typedef struct {
+    int path;               /* dst_path of the launch; -1: no pair launch on this context yet */
+    int measure;            /* dst_measure */
+    int family;             /* the tallies accumulated: 0 {d} (n, n_high), 1 {n, d} (raw, jc69), 2 k80's, 3 tn93's */
+    int out_kind;           /* dst_output */
+    int wide;               /* consensus / hybrid: 1 = one 32-bit word per tally (65,536 sites or more) */
+    int square;             /* 1: square job (dst_run_square), 0: rectangle */
+    int event_waves;        /* consensus / hybrid: event waves of a workgroup's 8 as instantiated (8: no roles); 0: dense */
+    int heavy_events;       /* consensus / hybrid: 0 the output's default split, 1 four event waves, 2 no roles */
+    uint32_t rows_per_tile; /* consensus / hybrid: 8, 16 or 32; dense: rows of the tile variant */
+    uint32_t tile_cols;     /* consensus / hybrid: records of a column panel; dense: columns of the tile variant */
+    uint64_t tiles;         /* workgroups of the pair launch (dst_plan_consensus_launch: the estimate the tile height is chosen by) */
+    int hot;                /* 1: hot-column tallies from the dense kernels were added (hybrid) */
+    int run_records;        /* 1: run-record corrections were applied (dst_run_records) */
+    int variant;            /* dense: the tile variant used, as its number among the measure's (0 is the default's own) */
+    uint32_t ksplit;        /* dense: the split-L factor used, also when dst_set_ksplit(0) leaves it to the library; else 0 */
+    uint64_t pairs;         /* pairs of the launch */
+    double events_per_pair; /* consensus / hybrid: the sample's estimates the choice was made from: events per pair, */
+    double list_length;     /*   mean list entries per record, */
+    double run_adds;        /*   and the run records' adds per pair */
+} dst_launch_info;
+int dst_last_launch(const dst_ctx *ctx, dst_launch_info *info);
+/* The choice itself, for any shape (pure host code, no GPU needed): what a consensus-path launch of n_rows_in_launch rows
+ * against n_cols column records (total_pairs pairs) with these statistics gets.  hot != 0: a hybrid launch; run_adds > 0:
+ * a square launch over a set with run records (2 x run records / records).  dst_run_square / dst_run_rect decide by this
+ * function.  DST_ERR_ARG: an unknown measure or output, DST_OUT_TALLY16 with wide, a negative or NaN figure. */
+int dst_plan_consensus_launch(int measure, int out_kind, int wide, int square, uint64_t n_rows_in_launch, uint64_t n_cols,
+                              uint64_t total_pairs, double events_per_pair, double list_length, double run_adds, int hot,
+                              dst_launch_info *info);
 
 /* ---- input: replaces Setup.loaded_fastas[slot] (src/lib.rs:133-144) --------------------- */
 /* codes: row-major n x len Paradis bytes, rows row_stride bytes apart (>= len).

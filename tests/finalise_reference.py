@@ -53,7 +53,14 @@ def _to_ld(v):
 def _ratio(num, den):
     """num / den for arrays of non-negative Python integers, with the f64 semantics of a zero denominator"""
     out = np.empty(len(num), LD)
-    for k, (a, b) in enumerate(zip(num, den)):
+    # non-negative integers below 2^64 convert exactly (what _to_ld gives them): whole arrays at once; the others one by one
+    small = np.asarray((num >= 0) & (num < (1 << 64)) & (den >= 0) & (den < (1 << 64)), bool)
+    if small.any():
+        a, b = num[small].astype(np.uint64), den[small].astype(np.uint64)
+        with np.errstate(all="ignore"):
+            out[small] = np.where(b == 0, np.where(a == 0, LD(np.nan), LD(np.inf)), a.astype(LD) / b.astype(LD))
+    for k in np.nonzero(~small)[0]:
+        a, b = num[k], den[k]
         out[k] = (np.nan if a == 0 else np.inf) if b == 0 else _to_ld(a) / _to_ld(b)
     return out
 

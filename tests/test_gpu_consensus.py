@@ -147,6 +147,8 @@ def test_wide_tallies_for_long_alignments(eng):
                 want = [int(x) for x in oracle.tallies(om, a[i], b[j])]
                 assert list(rect[i, j]) == want and list(stream[j, i]) == want, (m, i, j)
         assert eng.last_path() == "consensus"
+        li = eng.last_launch()                        # the stream-order rectangle: one 32-bit word per tally
+        assert li["wide"] and not li["square"] and li["out_kind"] == da.OUT_TALLY and li["event_waves"] > 0, (m, li)
     assert int(eng.run_square("tn93", 3, 4, tallies=True)[0][0]) > 65535
     eng.set_path("auto")
 
@@ -432,9 +434,13 @@ def test_event_heavy_launches_on_every_path(eng, L):
         eng.set_path(path)
         for (m, r), w in want.items():
             assert np.array_equal(eng.run_square(m, r, r + 2 if r + 2 < n else r + 1), w, equal_nan=True), (path, m, r)
+            li = eng.last_launch()                       # the no-roles variant is what ran, with the accumulators of this L
+            assert li["path"] == path and li["event_waves"] == 8 and li["heavy_events"] == 2, (path, m, r, li)
+            assert li["wide"] == (L >= 65536) and li["hot"] == (path == "hybrid"), (path, m, r, li)
         for m, w in want_t.items():
             got = eng.run_square(m, 3, 6, tallies=True)
             assert np.array_equal(got, w), (path, m)
+            assert eng.last_launch()["event_waves"] == 8 and eng.last_launch()["out_kind"] == da.OUT_TALLY, (path, m)
             for j in (4, n // 2, n - 1):                 # and this path's own tallies against the oracle
                 assert list(got[j - 4]) == [int(x) for x in oracle.tallies(m, codes[3], codes[j])], (path, m, j)
         for m in ("jc69", "tn93"):                       # device distances of the variant: BASELINE's 1e-12

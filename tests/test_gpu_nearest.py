@@ -273,3 +273,139 @@ def test_full_size_sampled_rows():
         exp = smallest(keys(want), 10, exclude=int(i))
         assert np.array_equal(idx[i], exp), i
         assert np.array_equal(vals[i].view(np.uint64), want[exp].view(np.uint64)), i
+
+
+# ---- lists wider than one wave: 64 s + lane in slot s, carried across slots through lane 63 -> lane 0 -----------------
+WIDE_K = (63, 64, 65, 127, 128, 129, 192, 193, 255, 256)
+
+
+def tied_alignment(n, L, seed):
+    """low diversity on a short alignment: a handful of distinct n_high values, so nearly every list boundary is a tie"""
+    rng = np.random.default_rng(seed)
+    root = rng.choice(np.array([136, 72, 40, 24], np.uint8), size=L)
+    codes = np.tile(root, (n, 1))
+    m = rng.random((n, L)) < 0.02
+    codes[m] = rng.choice(np.array([136, 72, 40, 24, 240, 192], np.uint8), size=int(m.sum()))
+    return codes
+
+
+def sample_rows(n, n_cols, square, seed):
+    """first and last rows, the rows either side of every slab cut, and a random few"""
+    cuts, pairs = [], 0
+    for i in range(n):
+        w = n_cols - i - 1 if square else n_cols
+        if pairs + w > SLAB_PAIRS:
+            cuts += [i - 1, i]
+            pairs = 0
+        pairs += w
+    rng = np.random.default_rng(seed)
+    return sorted({0, 1, n - 2, n - 1, *cuts} | {int(x) for x in rng.integers(0, n, 40)}), len(cuts) // 2 + 1
+
+
+@pytest.mark.parametrize("k", WIDE_K)
+def test_wide_lists_with_heavy_ties_over_several_slabs(wide_engine, k):
+    """square: the row pass and the column pass each merge into a record's list once per slab"""
+    eng, codes = wide_engine
+    n = len(codes)
+    rows, slabs = sample_rows(n, n, True, k)
+    assert slabs >= 3
+    idx, vals = eng.nearest("n_high", k)
+    assert idx.shape == (n, k)
+    want = oracle.all_pairs_rect("n_high", codes[rows], codes, threads=16).astype(np.int64)
+    kk = keys(want)
+    for r, i in enumerate(rows):
+        exp = smallest(kk[r], k, exclude=i)
+        assert np.array_equal(idx[i], exp), (k, i)
+        assert np.array_equal(vals[i], want[r][exp]), (k, i)
+    # heavy ties, by the oracle's values: in most rows the last entry kept and the first one left out are equal
+    tied = [np.sort(np.delete(want[r], i))[k - 1:k + 1] for r, i in enumerate(rows)]
+    assert sum(int(a == b) for a, b in tied) > len(rows) // 2
+
+
+@pytest.fixture(scope="module")
+def wide_engine():
+    codes = tied_alignment(12_500, 64, seed=81)
+    with da.Engine(0) as eng:
+        eng.upload(0, codes)
+        yield eng, codes
+
+
+@pytest.fixture(scope="module")
+def wide_rect_engine():
+    a, b = tied_alignment(4200, 64, seed=82), tied_alignment(25_000, 64, seed=83)
+    with da.Engine(0) as eng:
+        eng.upload(0, a)
+        eng.upload(1, b)
+        yield eng, a, b
+
+
+@pytest.mark.parametrize("k", WIDE_K)
+def test_wide_lists_rectangle_over_several_slabs(wide_rect_engine, k):
+    eng, a, b = wide_rect_engine
+    rows, slabs = sample_rows(len(a), len(b), False, k)
+    assert slabs >= 3
+    idx, vals = eng.nearest("n_high", k, square=False, row_slot=0, col_slot=1)
+    assert idx.shape == (len(a), k)
+    want = oracle.all_pairs_rect("n_high", a[rows], b, threads=16).astype(np.int64)
+    kk = keys(want)
+    for r, i in enumerate(rows):
+        exp = smallest(kk[r], k)
+        assert np.array_equal(idx[i], exp), (k, i)
+        assert np.array_equal(vals[i], want[r][exp]), (k, i)
+
+
+def special_values_set():
+    """40 x 400: ten copies of a root (zeros; jc69 / k80 give -0.0), ten records that differ from it at exactly 300 sites
+    (raw 0.75: jc69 +inf), five records without a resolved site (raw NaN against everyone), fifteen ordinary ones"""
+    rng = np.random.default_rng(91)
+    L = 400
+    root = rng.choice(np.array([136, 72, 40, 24], np.uint8), size=L)
+    alt = np.array([{136: 72, 72: 136, 40: 24, 24: 40}[int(c)] for c in root], np.uint8)
+    codes = np.tile(root, (40, 1))
+    codes[10:20, :300] = alt[:300]
+    codes[20:25] = 240
+    m = rng.random((15, L)) < 0.05
+    codes[25:][m] = rng.choice(np.array([136, 72, 40, 24], np.uint8), size=int(m.sum()))
+    return codes
+
+
+@pytest.mark.parametrize("path", ["dense", "consensus"])
+def test_nan_inf_and_signed_zeros_inside_a_list(path):
+    """k larger than the number of finite candidates: the infinities come after every finite value, the NaN block after
+    them, each ordered by index; zeros of either sign tie and are ordered by index; every value comes back with the
+    bits run_square gives that pair (a -0.0 stays -0.0); k_used is min(k, n - 1)"""
+    codes = special_values_set()
+    n = len(codes)
+    with da.Engine(0) as eng:
+        eng.set_prep_threshold(0)
+        eng.set_path(path)
+        eng.upload(0, codes)
+        for m in ALL:
+            if m in ("n", "n_high", "raw"):
+                cond = as_payload(m, oracle.all_pairs_square(m, codes))
+                assert np.array_equal(eng.run_square(m).view(np.uint64), cond.view(np.uint64)), m
+            else:
+                cond = eng.run_square(m)
+            for k in (39, 64, 256):
+                idx, vals = eng.nearest(m, k)
+                assert idx.shape == (n, 39), (m, k)                        # k_used = n - 1
+                assert np.array_equal(idx, expected_square(cond, n, 39)), (m, k)
+                rows = np.repeat(np.arange(n), 39).reshape(n, 39)
+                assert np.array_equal(vals.view(np.uint64), cond[canon(n, rows, idx)].view(np.uint64)), (m, k)
+            if m in da.INT_MEASURES:
+                continue
+            # row 0 (a copy of the root), its blocks as the ORACLE's values say: zeros first, the infinities after every
+            # finite value, the NaN block last, each in index order
+            o = square_matrix(oracle.all_pairs_square(m, codes), n)[0]
+            others = np.arange(1, n)
+            zeros, infs, nans = (others[f(o[1:])] for f in (lambda x: x == 0, np.isposinf, np.isnan))
+            v = vals[0]
+            assert len(zeros) == 9 and len(nans) >= 5 and (m != "jc69" or len(infs) == 10), (m, zeros, infs, nans)
+            assert (v[:9] == 0).all() and list(idx[0][:9]) == list(zeros), (m, v)
+            assert np.isnan(v[39 - len(nans):]).all() and list(idx[0][39 - len(nans):]) == list(nans), (m, v)
+            at = 39 - len(nans) - len(infs)
+            assert np.isposinf(v[at:at + len(infs)]).all() and list(idx[0][at:at + len(infs)]) == list(infs), (m, v)
+            assert np.isfinite(v[:at]).all()
+            if m in ("jc69", "k80"):
+                assert np.signbit(v[:9]).all() and np.signbit(o[zeros]).all()     # -k ln(1) = -0.0, and it stays -0.0
+            assert np.isnan(vals[22]).all() and list(idx[22]) == [j for j in range(n) if j != 22], m

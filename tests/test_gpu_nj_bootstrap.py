@@ -77,6 +77,61 @@ def test_exact_support_low_divergence(eng, measure):
     check_support(eng, measure, codes, 16, seed=5)
 
 
+# Rows of up to 49,152 bytes are staged in LDS (boot_resample_kernel<true>), longer ones are gathered from global memory
+# (<false>); a thread writes four columns as one 32-bit store, the last one N-padded when L is not a multiple of 4.
+@pytest.mark.parametrize("L,measure,path", [(49152, "n_high", "auto"), (49153, "raw", "auto"), (49167, "n", "auto"),
+                                            (65537, "n_high", "auto"), (65537, "raw", "consensus")])
+def test_exact_support_beyond_the_staged_row(eng, L, measure, path):
+    """the last staged size, the first rows gathered from global memory, L = 1 and 3 (mod 4) there, and 65,537 sites on
+    the consensus path (one 32-bit word per tally)"""
+    codes = alignment(24, L, seed=L, divergence=0.02)
+    try:
+        if path != "auto":
+            eng.set_prep_threshold(0)
+            eng.set_path(path)
+        check_support(eng, measure, codes, 4, seed=L + 3)
+        if path != "auto":
+            # the bootstrap's own pair launches go through the context's launcher: the report right after a call is its
+            # last replicate's fill, on the forced path with one 32-bit word per tally
+            eng.upload(0, codes)
+            main = eng.nj(measure)[0]
+            eng.run_square(measure, 0, 1)                 # (a 23-pair launch, so that the report below is not this one)
+            eng.nj_bootstrap(measure, codes, main, 2, seed=L + 3)
+            li = eng.last_launch()
+            assert li["path"] == path and li["wide"] == (L >= 65536) and li["pairs"] == 24 * 23 // 2, li
+    finally:
+        eng.set_path("auto")
+        eng.set_prep_threshold(2e10)
+
+
+@pytest.mark.parametrize("n,L", [(9, 301), (9, 303), (7, 15), (6, 17), (5, 1)])
+def test_exact_support_of_odd_and_tiny_widths(eng, n, L):
+    """L = 1 and 3 (mod 4): the tail of a row's last 32-bit store; a single site (n_high is finite whatever is drawn)"""
+    codes = alignment(n, L, seed=n * 100 + L, divergence=0.2)
+    check_support(eng, "n_high", codes, 8, seed=L)
+
+
+def test_row_stride_larger_than_the_width(eng):
+    """rows stride bytes apart with stride > len, the padding filled with a byte that is no Paradis code: a read past len
+    would be DST_ERR_INVALID_CODE or another tree"""
+    n, L, reps, seed = 12, 303, 6, 21
+    codes = alignment(n, L, seed=5, divergence=0.1)
+    eng.upload(0, codes)
+    main = eng.nj("n_high")[0]
+    want_support, want_trees = check_support(eng, "n_high", codes, reps, seed=seed)
+    stride = L + 37
+    padded = np.full((n, stride), 7, np.uint8)
+    padded[:, :L] = codes
+    view = padded[:, :L]
+    assert view.strides == (stride, 1) and 7 not in CODES
+    support = np.zeros(2 * n - 2, np.uint32)
+    trees = np.zeros((reps, 2 * n - 2), np.uint32)
+    rc = da.load().dst_nj_bootstrap(eng._h, da.MEASURES["n_high"], view.ctypes.data, n, L, stride, reps, seed, 0,
+                                    main.ctypes.data, support.ctypes.data, trees.ctypes.data, 2 * n - 2)
+    assert rc == 0, eng._lib.dst_last_error(eng._h)
+    assert np.array_equal(trees, want_trees) and np.array_equal(support, want_support)
+
+
 # ---- 2. invariance -------------------------------------------------------------------------------------------------
 def test_invariance(eng):
     codes = alignment(120, 800, seed=3)

@@ -204,7 +204,16 @@ def test_split_over_L_agrees_with_single_sweep(eng):
         for k in (1, 0, 2, 7, 40):
             eng.set_ksplit(k)
             d, t = eng.run_square(m), eng.run_square(m, tallies=True)
+            li_square = eng.last_launch()
             r = eng.run_rect(m, row_begin=2, row_end=8)
+            for li in (li_square, eng.last_launch()):
+                # the factor the report gives: forced (capped at this alignment's 40 chunks: ceil(5000 / 128)), or the library's own for
+                # launches of fewer than 1,024 tiles: enough parts for 2,048 workgroups, eight chunks each at least
+                # (uniform codes: the hybrid engine finds mostly hot columns and runs dense too)
+                assert li["path"] == "dense" or eng.path_name != "dense", (m, k, li)
+                if li["path"] == "dense":
+                    assert 0 < li["tiles"] < 1024
+                    assert li["ksplit"] == (min(k, 40) if k else min(-(-2048 // li["tiles"]), 40 // 8, 64)), (m, k, li)
             if ref_d is None:
                 ref_d, ref_t, ref_r = d, t, r
             assert np.array_equal(d, ref_d, equal_nan=True), (m, k)
@@ -526,7 +535,12 @@ def test_very_long_alignment_rect_and_stream(eng):
     for i in range(6):
         for j in range(5):
             assert list(tl[i, j]) == list(oracle.tallies("tn93", a[i], b[j]))
+    li = eng.last_launch()               # one tile x 15,626 chunks: the library splits the sweep over L 64 ways by itself
+    assert li["ksplit"] == 64 if li["path"] == "dense" else li["wide"] and li["event_waves"] > 0, li
     assert_close(eng.run_square("raw"), oracle.all_pairs_square("raw", a))
+    li = eng.last_launch()
+    assert li["ksplit"] == 64 if li["path"] == "dense" else li["wide"] and li["event_waves"] > 0, li
+    assert eng.path_name != "dense" or li["path"] == "dense"
 
 
 def test_many_records_short_alignment(eng):
