@@ -64,6 +64,9 @@ def _load(native: bool = False) -> C.CDLL:
     lib.orc_tn93.restype = C.c_double
     lib.orc_tallies.argtypes = [C.c_int, _u8p, _u8p, C.c_size_t, _u64p]
     lib.orc_tallies.restype = C.c_int
+    lib.orc_tallies_rect.argtypes = [C.c_int, _u8p, C.c_size_t, C.c_size_t, _u8p, C.c_size_t, C.c_size_t, C.c_size_t,
+                                     C.c_int, _u64p]
+    lib.orc_tallies_rect.restype = C.c_int
     lib.orc_finalize.argtypes = [C.c_int, _u64p, _u64p, _u64p]
     lib.orc_finalize.restype = C.c_double
     lib.orc_pairs_square.argtypes = [C.c_size_t, _u64p]
@@ -200,6 +203,25 @@ def tallies(measure: str, q, t) -> np.ndarray:
     out = np.zeros(4, np.uint64)
     k = lib().orc_tallies(MEASURES[measure], _p8(q), _p8(t), t.size, _p64(out))
     return out[:k].copy()
+
+
+def _rows(a) -> np.ndarray:
+    """a 2-D uint8 matrix as it is when its rows run forwards in memory with unit site stride (any row stride); else a copy"""
+    a = np.asarray(a, dtype=np.uint8)
+    if a.ndim != 2 or (a.shape[1] and a.strides[1] != 1) or a.strides[0] < a.shape[1]:
+        a = np.ascontiguousarray(a)
+    return a
+
+
+def tallies_rect(measure: str, a, b, threads: int = 1) -> np.ndarray:
+    """tallies() of every record of `a` against every record of `b`: uint64 (len(a), len(b), width)."""
+    a, b = _rows(a), _rows(b)
+    out = np.zeros((a.shape[0], b.shape[0], 4), np.uint64)
+    rc = lib().orc_tallies_rect(MEASURES[measure], _p8(a), a.shape[0], a.strides[0], _p8(b), b.shape[0], b.strides[0],
+                                a.shape[1], threads, _p64(out))
+    if rc:
+        raise RuntimeError(f"orc_tallies_rect rc={rc}")
+    return out[:, :, :N_TALLIES[measure]].copy()
 
 
 def finalize(measure: str, tl, q_counts=None, t_counts=None) -> float:

@@ -402,6 +402,50 @@ size_t orc_pairs_rectangle(size_t n1, size_t n2, uint64_t *ij)
     return k;
 }
 
+/* orc_tallies of every record of `a` against every record of `b`: out[(i * nb + j) * 4 + k], unused tallies zero.
+ * Pairs are dealt out to `threads` workers (the per-pair call from Python costs more than the loop it makes). */
+typedef struct {
+    int measure, k, threads;
+    const uint8_t *a, *b;
+    size_t na, nb, stride_a, stride_b, len;
+    uint64_t *out;
+} tally_job_t;
+
+static void *tally_worker(void *arg)
+{
+    const tally_job_t *jb = arg;
+    for (size_t p = (size_t)jb->k; p < jb->na * jb->nb; p += (size_t)jb->threads) {
+        uint64_t t4[4] = {0, 0, 0, 0};
+        orc_tallies(jb->measure, jb->a + (p / jb->nb) * jb->stride_a, jb->b + (p % jb->nb) * jb->stride_b, jb->len, t4);
+        memcpy(jb->out + 4 * p, t4, sizeof t4);
+    }
+    return NULL;
+}
+
+int orc_tallies_rect(int measure, const uint8_t *a, size_t na, size_t stride_a, const uint8_t *b, size_t nb,
+                     size_t stride_b, size_t len, int threads, uint64_t *out)
+{
+    if (measure < ORC_N || measure > ORC_TN93)
+        return -1;
+    if (threads < 1)
+        threads = 1;
+    if (threads > 64)
+        threads = 64;
+    tally_job_t jobs[64];
+    pthread_t tid[64];
+    int started[64];
+    for (int k = 0; k < threads; ++k) {
+        jobs[k] = (tally_job_t){measure, k, threads, a, b, na, nb, stride_a, stride_b, len, out};
+        started[k] = pthread_create(&tid[k], NULL, tally_worker, &jobs[k]) == 0;
+        if (!started[k])
+            tally_worker(&jobs[k]); /* no thread to be had: this share of the pairs here and now */
+    }
+    for (int k = 0; k < threads; ++k)
+        if (started[k])
+            pthread_join(tid[k], NULL);
+    return 0;
+}
+
 /* ---------------------------------------------------------------- lib.rs:626-633 ------ */
 int orc_format_int(int64_t v, char *buf, size_t cap) { return snprintf(buf, cap, "%lld", (long long)v); }
 

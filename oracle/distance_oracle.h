@@ -72,6 +72,9 @@ double orc_tn93(const uint8_t *q, const uint8_t *t, size_t len, const uint64_t q
  * raw/jc69: out = {n, d}; k80: {count_L, ts, tv}; tn93: {count_L, count_d, count_P1, count_P2};
  * n/n_high: {d}.  Returns the number of tallies written. */
 int orc_tallies(int measure, const uint8_t *q, const uint8_t *t, size_t len, uint64_t out[4]);
+/* ... of every record of `a` against every record of `b`: out[(i * nb + j) * 4 + k], unused tallies zero */
+int orc_tallies_rect(int measure, const uint8_t *a, size_t na, size_t stride_a, const uint8_t *b, size_t nb,
+                     size_t stride_b, size_t len, int threads, uint64_t *out);
 
 /* Finalisation alone, in the reference's f64 operation order, from integer tallies. */
 double orc_finalize(int measure, const uint64_t tallies[4], const uint64_t q_counts[4],
