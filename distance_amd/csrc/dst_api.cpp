@@ -883,7 +883,7 @@ int run_sets(dst_ctx *ctx, int measure, bool square, DeviceSet &rows, DeviceSet 
     }
     if (rb > re || re > rows.n)
         return fail(ctx, DST_ERR_ARG, "row range out of bounds");
-    if (out_kind == DST_OUT_TALLY16 && rows.len > 65535)
+    if (out_kind == DST_OUT_TALLY16 && rows.len > kNarrowMaxLen)
         return fail(ctx, DST_ERR_ARG, "DST_OUT_TALLY16 needs alignments shorter than 65,536 sites");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = stream_v ? (hipStream_t)stream_v : ctx->stream;
@@ -955,7 +955,7 @@ int run_sets(dst_ctx *ctx, int measure, bool square, DeviceSet &rows, DeviceSet 
     }
     if (path != DST_PATH_DENSE) {
         const int fam = family_of(measure);
-        const bool wide = rows.len >= 65536;
+        const bool wide = rows.len > kNarrowMaxLen;
         const bool hybrid = path == DST_PATH_HYBRID;
         rc = ensure_aconst(ctx, cols, cols, fam, wide, stream);
         if (!rc && &rows != &cols)

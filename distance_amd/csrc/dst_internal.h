@@ -36,6 +36,10 @@ enum Plane : int {
 constexpr uint32_t kChunkSites = 128;  // sites per uint4
 constexpr uint32_t kPadRecords = 512;  // npad granularity (>= every tile's BN)
 constexpr uint32_t kBlockThreads = 256;
+// The widest alignment of the narrow tally form: every tally of a pair is at most len, so up to here two of them share a
+// 32-bit word in the consensus pair kernel (Pack, pack_words), the hot columns' tallies travel as uint16, DST_OUT_TALLY16
+// exists and the text kernels read 16-bit tallies.  One site more and everything is one tally per 32-bit word ("wide").
+constexpr uint64_t kNarrowMaxLen = 65535;
 
 // ---- consensus-delta path (dst_consensus.hip) -------------------------------------------------
 // Every tally of every measure is a sum over sites of a per-site function f_k(q[s], t[s]) of the two

@@ -397,7 +397,7 @@ int text_common(dst_ctx *ctx, int measure, bool square, int row_slot, int col_sl
     hipStream_t stream = ctx->stream;
     // jc69 / k80 / tn93: from the tallies, with the near ties of the 12th decimal left to the host (see the top of the file)
     const bool from_tallies = measure == DST_JC69 || measure == DST_K80 || measure == DST_TN93;
-    const bool tally16 = from_tallies && rows.len <= 65535;
+    const bool tally16 = from_tallies && rows.len <= kNarrowMaxLen;
     const int res_kind = !from_tallies ? DST_OUT_DISTANCE : tally16 ? DST_OUT_TALLY16 : DST_OUT_TALLY;
     const size_t res_bytes = dst_out_bytes(measure, res_kind, pairs);
     const uint32_t ties_cap = from_tallies ? (uint32_t)std::max<uint64_t>(4096, pairs / 16) : 0;
@@ -699,7 +699,7 @@ int text_matrix(dst_ctx *ctx, int measure, bool square, int row_slot, int col_sl
     const uint32_t n_chunks = (uint32_t)std::max<uint64_t>(1, (cols.n + kMatChunk - 1) / kMatChunk);
     const uint64_t n_words = (re - rb) * n_chunks;
     const bool from_tallies = measure == DST_JC69 || measure == DST_K80 || measure == DST_TN93;
-    const bool tally16 = from_tallies && rows.len <= 65535;
+    const bool tally16 = from_tallies && rows.len <= kNarrowMaxLen;
     const int res_kind = !from_tallies ? DST_OUT_DISTANCE : tally16 ? DST_OUT_TALLY16 : DST_OUT_TALLY;
     const size_t res_bytes = dst_out_bytes(measure, res_kind, cells);
     const uint32_t ties_cap = from_tallies ? (uint32_t)std::max<uint64_t>(4096, cells / 16) : 0;
