@@ -103,6 +103,7 @@ _SIGS = {
     "dst_gather_slabs": (C.c_int, [_vp, _vp, _vp, _u64p, _u64p, C.c_int, _vp]),
     "dst_nearest": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, _vp, _vp, _vp, C.c_size_t, _u32p]),
     "dst_clusters": (C.c_int, [_vp, C.c_int, C.c_double, C.c_uint64, _vp, C.c_size_t, _u64p, _u64p]),
+    "dst_mst": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, C.c_size_t, _u64p, _u32p]),
     "dst_nj": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, C.c_size_t]),
     "dst_nj_matrix": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_size_t]),
     "dst_newick": (C.c_int, [C.c_uint64, _vp, _vp, C.c_char_p, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),

@@ -11,7 +11,8 @@
 // of every record instead of every pair: dst_nearest), --clusters T (single-linkage clusters at threshold T: dst_clusters),
 // --matrix tsv|phylip (a square or rectangular distance matrix instead of the long form: dst_text_matrix), --tree nj (the
 // neighbour-joining tree as one Newick line: dst_nj, dst_newick), --bootstrap B / --seed S (the tree's splits labelled
-// with their support in B column resamplings: dst_nj_bootstrap, dst_newick_support).
+// with their support in B column resamplings: dst_nj_bootstrap, dst_newick_support), --mst (the edges of the minimum
+// spanning tree in ascending order, one "id1, id2, value" line each: dst_mst).
 //
 // Exactness: the GPU returns integer site tallies; f64 finalisation is dst_finalize() on the host
 // (reference operation order, glibc log/sqrt), so the printed digits do not depend on the device.
@@ -119,6 +120,9 @@ void print_help()
         "      --bootstrap <B>          Label each internal edge of the neighbour-joining tree with the number of B "
         "(1-10000) bootstrap replicates (alignments of columns drawn with replacement) whose tree holds its split\n"
         "      --seed <S>               Seed of the bootstrap's column draws, 0 to 2^64-1 [default: 1]\n"
+        "      --mst                    Print only the edges of the minimum spanning tree of the records (pairs without a "
+        "distance, NaN, are no edges: a forest then), in ascending order of (distance, first record, second record), each "
+        "as the line the full run prints for that pair. One input, one GPU, no --stream and no other output mode\n"
         "  -h, --help                   Print help\n"
         "  -V, --version                Print version");
 }
@@ -144,6 +148,7 @@ struct Args {
     uint64_t seed = 1;                    // --seed S
     bool has_seed = false;
     bool has_slab_pairs = false;
+    bool has_mst = false;                 // --mst
     std::string selftest;
 };
 
@@ -268,6 +273,8 @@ Args parse_args(int argc, char **argv)
         } else if (arg == "--seed" || arg.rfind("--seed=", 0) == 0) {
             a.seed = parse_usize(value_of(k, arg, "--seed <S>"), "--seed <S>");
             a.has_seed = true;
+        } else if (arg == "--mst") {
+            a.has_mst = true;
         } else if (arg == "--host-selftest") {
             a.selftest = value_of(k, arg, "--host-selftest <what>");
         } else {
@@ -311,6 +318,18 @@ Args parse_args(int argc, char **argv)
     if (a.has_tree && (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1)))
         die_usage(std::string("the argument '--tree <method>' cannot be used with '") +
                   (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
+    if (a.has_mst) {
+        const char *other = a.has_stream ? "--stream <stream>" : a.has_nearest ? "--nearest <k>" : a.has_clusters ? "--clusters <T>"
+                            : a.matrix >= 0 ? "--matrix <format>" : a.has_tree ? "--tree <method>"
+                            : a.has_bootstrap ? "--bootstrap <B>" : nullptr;
+        if (other)
+            die_usage(std::string("the argument '--mst' cannot be used with '") + other + "'");
+        if (a.flag_inputs.size() + a.pos_inputs.size() > 1)
+            die_usage("the argument '--mst' takes one input alignment, not two");
+        if (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1))
+            die_usage(std::string("the argument '--mst' cannot be used with '") +
+                      (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
+    }
     if (a.has_bootstrap && !a.has_tree)
         die_usage("the argument '--bootstrap <B>' requires '--tree nj'");
     if (a.has_seed && !a.has_bootstrap)
@@ -1233,6 +1252,39 @@ void write_clusters(const Ctx &gpu, const Alignment &set, int measure, double th
     wr.write(out.data(), out.size());
 }
 
+// --mst: the edges of dst_mst in its order, each line "id_i, id_j, value" with the value's text exactly as the full run
+// prints that pair: the edge's tallies through dst_finalize, then dst_format_distance (as write_nearest).
+void write_mst(const Ctx &gpu, const Alignment &set, const std::vector<uint32_t> &counts, int measure, uint64_t max_pairs,
+               Writer &wr)
+{
+    const size_t W = (size_t)dst_tally_width(measure);
+    const size_t cap = std::max<size_t>(set.n, 1);
+    std::vector<uint32_t> ei(cap), ej(cap), tallies(cap * W);
+    uint64_t n_edges = 0;
+    gpu.check(dst_mst(gpu.h, measure, max_pairs, ei.data(), ej.data(), nullptr, tallies.data(), cap, &n_edges, nullptr), "mst");
+    const uint32_t *cc = measure == DST_TN93 ? counts.data() : nullptr;
+    std::string out;
+    char num[64];
+    for (size_t e = 0; e < n_edges; ++e) {
+        const size_t i = ei[e], j = ej[e];
+        double f = 0;
+        int64_t v = 0;
+        dst_finalize(measure, &tallies[e * W], cc ? cc + 4 * i : nullptr, cc ? cc + 4 * j : nullptr, &f, &v);
+        const int len = dst_format_distance(measure, f, v, num, sizeof num);
+        out += set.ids[i];
+        out += '\t';
+        out += set.ids[j];
+        out += '\t';
+        out.append(num, (size_t)std::min<int>(len, (int)sizeof num - 1));
+        out += '\n';
+        if (out.size() >= ((size_t)1 << 20)) {
+            wr.write(out.data(), out.size());
+            out.clear();
+        }
+    }
+    wr.write(out.data(), out.size());
+}
+
 // a DST_ERR_STATE message "... the distance of records I and J is not finite" of the NJ calls, with the pair named by
 // its ids; false when the message names no pair of the set
 bool non_finite_pair(const Ctx &gpu, const Alignment &set, const char *prefix, const char *suffix)
@@ -1537,6 +1589,8 @@ int main(int argc, char **argv)
         write_tree(gpus[0], loaded[0], measure, a.has_slab_pairs ? a.slab_pairs : 0, a.bootstrap, a.seed, wr);
     } else if (a.has_clusters) {
         write_clusters(gpus[0], loaded[0], measure, a.clusters, wr);
+    } else if (a.has_mst) {
+        write_mst(gpus[0], loaded[0], counts[0], measure, a.has_slab_pairs ? a.slab_pairs : 0, wr);
     } else if (a.has_nearest) {
         write_nearest(gpus[0], loaded, counts, measure, (uint32_t)a.nearest, wr);
     } else if (!stream_fh) {

@@ -1281,7 +1281,7 @@ int dst_destroy(dst_ctx *ctx)
     for (void *b : {(void *)ctx->d_lut, (void *)ctx->d_total, (void *)ctx->scan_tmp, ctx->host_out, ctx->hot_tally, ctx->text_res,
                     ctx->text_num, (void *)ctx->text_len, (void *)ctx->text_scan, (void *)ctx->text_buf, (void *)ctx->text_flag, ctx->text_ties,
                     (void *)ctx->ids[0].off, (void *)ctx->ids[0].chars, (void *)ctx->ids[1].off, (void *)ctx->ids[1].chars, ctx->nn_slab, ctx->nn_lists,
-                    ctx->cl_slab, ctx->cl_work})
+                    ctx->cl_slab, ctx->cl_work, ctx->mst_work})
         if (b)
             (void)hipFree(b);
     if (ctx->scratch)
@@ -1982,6 +1982,135 @@ int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs
         *n_clusters = roots;
     if (links)
         *links = h_links;
+    return DST_OK;
+}
+
+int dst_mst(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *edge_i, uint32_t *edge_j, void *values,
+            uint32_t *tallies, size_t cap, uint64_t *n_edges, uint32_t *rounds)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (n_edges)
+        *n_edges = 0;
+    if (rounds)
+        *rounds = 0;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (!edge_i || !edge_j)
+        return fail(ctx, DST_ERR_ARG, "null edge_i or edge_j pointer");
+    DeviceSet &set = ctx->set[0];
+    if (!set.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    const uint64_t n = set.n;
+    if (n >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    if (n < 2)
+        return DST_OK;
+    if (cap < n - 1)
+        return fail(ctx, DST_ERR_CAPACITY, "cap is below n - 1 entries");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const bool finish = values || tallies;
+    const int W = tally_width(measure);
+    int rc = DST_OK;
+    if (finish && measure == DST_TN93) {
+        rc = need_counts(ctx, set, stream);
+        if (rc)
+            return rc;
+    }
+    const std::vector<RowSlab> slabs = cut_row_slabs(true, n, n, max_pairs ? max_pairs : kClusterSlabPairs);
+    uint64_t biggest = 0;
+    for (const RowSlab &s : slabs)
+        biggest = std::max(biggest, s.pairs);
+    const size_t slab_bytes = std::max(dst_out_bytes(measure, DST_OUT_DISTANCE, biggest),
+                                       finish ? dst_out_bytes(measure, DST_OUT_TALLY, biggest) : (size_t)0);
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t o_hook = up(n * 4), o_key = o_hook + up(n * 4), o_pair = o_key + up(n * 8), o_edges = o_pair + up(n * 8),
+                 o_ekeys = o_edges + up(n * 8), o_val = o_ekeys + up(n * 8), o_tal = o_val + up(n * 8),
+                 o_count = o_tal + up(n * (size_t)W * 4), total = o_count + 256;
+    HIP_TRY(ctx, hipStreamSynchronize(stream));   // (the grow-only buffers of an earlier call: nothing reads them now)
+    rc = ensure_bytes(ctx, &ctx->cl_slab, &ctx->cl_slab_bytes, std::max<size_t>(slab_bytes, 256));
+    if (!rc)
+        rc = ensure_bytes(ctx, &ctx->mst_work, &ctx->mst_work_bytes, total);
+    if (rc)
+        return rc;
+    char *w = static_cast<char *>(ctx->mst_work);
+    MstBuffers b{};
+    b.comp = reinterpret_cast<uint32_t *>(w);
+    b.hook = reinterpret_cast<uint32_t *>(w + o_hook);
+    b.best_key = reinterpret_cast<uint64_t *>(w + o_key);
+    b.best_pair = reinterpret_cast<uint64_t *>(w + o_pair);
+    b.edges = reinterpret_cast<uint64_t *>(w + o_edges);
+    b.edge_keys = reinterpret_cast<uint64_t *>(w + o_ekeys);
+    b.val = reinterpret_cast<uint64_t *>(w + o_val);
+    b.tal = reinterpret_cast<uint32_t *>(w + o_tal);
+    b.counters = reinterpret_cast<uint64_t *>(w + o_count);
+    // Boruvka rounds: a round that emits nothing ends the call (the forest of a graph that is not connected); n - 1
+    // edges end it without that last sweep.  Every round at least halves the components that still have an edge out.
+    uint64_t h_count[2] = {0, 0};
+    uint32_t n_rounds = 0;
+    for (bool first = true;; first = false) {
+        if (n_rounds > 64)
+            return fail(ctx, DST_ERR_STATE, "minimum spanning tree: more rounds than any set can need");
+        HIP_TRY(ctx, launch_mst_reset(b, n, first, stream));
+        for (const RowSlab &s : slabs) {
+            // the slab's pairs, each once (the triangle), as DST_OUT_DISTANCE payloads; the two scan launches behind it
+            rc = run_sets(ctx, measure, true, set, set, s.rb, s.re, DST_OUT_DISTANCE, ctx->cl_slab, ctx->cl_slab_bytes,
+                          (void *)stream);
+            if (rc)
+                return rc;
+            HIP_TRY(ctx, launch_mst_scan(measure, static_cast<const uint64_t *>(ctx->cl_slab), s.first, n, s.rb, s.re, b, stream));
+        }
+        HIP_TRY(ctx, launch_mst_hook(b, n, stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_count, b.counters, 16, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+        if (h_count[1] == 0)
+            break;
+        ++n_rounds;
+        if (h_count[0] >= n - 1)
+            break;
+    }
+    const uint64_t ne = h_count[0];
+    if (ne > n - 1)
+        return fail(ctx, DST_ERR_STATE, "minimum spanning tree: more than n - 1 edges");
+    if (finish && ne)
+        for (const RowSlab &s : slabs) {
+            rc = run_sets(ctx, measure, true, set, set, s.rb, s.re, DST_OUT_TALLY, ctx->cl_slab, ctx->cl_slab_bytes, (void *)stream);
+            if (rc)
+                return rc;
+            HIP_TRY(ctx, launch_mst_gather(measure, static_cast<const uint32_t *>(ctx->cl_slab), s.first, n, s.rb, s.re, set.counts, b,
+                                           ne, stream));
+        }
+    // the edges back once, sorted here by (key, i, j)
+    std::vector<uint64_t> h_edges(ne), h_keys(ne), h_val(finish ? ne : 0);
+    std::vector<uint32_t> h_tal(tallies ? ne * W : 0), order(ne);
+    if (ne) {
+        HIP_TRY(ctx, hipMemcpyAsync(h_edges.data(), b.edges, ne * 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_keys.data(), b.edge_keys, ne * 8, hipMemcpyDeviceToHost, stream));
+        if (finish)
+            HIP_TRY(ctx, hipMemcpyAsync(h_val.data(), b.val, ne * 8, hipMemcpyDeviceToHost, stream));
+        if (tallies)
+            HIP_TRY(ctx, hipMemcpyAsync(h_tal.data(), b.tal, ne * W * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+    }
+    for (uint64_t e = 0; e < ne; ++e)
+        order[e] = (uint32_t)e;
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        return h_keys[x] != h_keys[y] ? h_keys[x] < h_keys[y] : h_edges[x] < h_edges[y];
+    });
+    for (uint64_t e = 0; e < ne; ++e) {
+        const uint32_t src = order[e];
+        edge_i[e] = (uint32_t)(h_edges[src] >> 32);
+        edge_j[e] = (uint32_t)h_edges[src];
+        if (values)
+            static_cast<uint64_t *>(values)[e] = h_val[src];
+        if (tallies)
+            std::memcpy(tallies + e * W, h_tal.data() + (size_t)src * W, (size_t)W * 4);
+    }
+    if (n_edges)
+        *n_edges = ne;
+    if (rounds)
+        *rounds = n_rounds;
     return DST_OK;
 }
 

@@ -397,6 +397,31 @@ hipError_t launch_clusters_link(int measure, const uint64_t *slab, uint64_t out_
                                 uint64_t t_bits, uint32_t *parent, unsigned long long *links, hipStream_t stream);
 hipError_t launch_clusters_final(uint32_t *parent, uint64_t n, hipStream_t stream);
 
+// ---- minimum spanning forest (dst_mst.hip, driven by dst_mst in dst_api.cpp) ------------------------------------------
+// Boruvka rounds: every round runs each row slab of the triangle into the DST_OUT_DISTANCE scratch (as dst_clusters) and
+// scans it twice (the minimal key of every component's outgoing edges, then the smallest pair of that key), hooks every
+// component along its best edge and flattens the component labels.  O(n) device state beside the slab.
+struct MstBuffers {
+    uint32_t *comp;        // [n] component of a record: a root r has comp[r] == r (between rounds)
+    uint32_t *hook;        // [n] this round's hooks, by component root
+    uint64_t *best_key;    // [n] by component root: the smallest nn_key of its outgoing edges (~0: none)
+    uint64_t *best_pair;   // [n] ... and the smallest i << 32 | j of that key
+    uint64_t *edges;       // [n] the forest's edges i << 32 | j in order of emission
+    uint64_t *edge_keys;   // [n] their keys
+    uint64_t *val;         // [n] their DST_OUT_DISTANCE payloads (the finish)
+    uint32_t *tal;         // [n][tally_width] their DST_OUT_TALLY words
+    uint64_t *counters;    // [0] edges so far, [1] edges of the current round
+};
+hipError_t launch_mst_reset(const MstBuffers &b, uint64_t n, bool first, hipStream_t stream);
+// rows [rb, re) of the square, payloads from slab entry tri_row_start(n, i) - out_base: the key launch, then the pair launch
+hipError_t launch_mst_scan(int measure, const uint64_t *slab, uint64_t out_base, uint64_t n, uint64_t rb, uint64_t re,
+                           const MstBuffers &b, hipStream_t stream);
+hipError_t launch_mst_hook(const MstBuffers &b, uint64_t n, hipStream_t stream);   // hook + emit, then flatten
+// the same rows as DST_OUT_TALLY words: the tallies and the value of every forest edge whose row lies in them (counts:
+// tn93's base counts of the set)
+hipError_t launch_mst_gather(int measure, const uint32_t *slab, uint64_t out_base, uint64_t n, uint64_t rb, uint64_t re,
+                             const uint32_t *counts, const MstBuffers &b, uint64_t n_edges, hipStream_t stream);
+
 // ---- neighbour-joining trees (dst_nj.hip, driven by dst_nj / dst_nj_matrix in dst_api.cpp) --------------------------
 // The n x n f64 square on the device, filled from row slabs of DST_OUT_DISTANCE payloads (as dst_clusters) or from the
 // caller's matrix, then n - 3 rounds of a scan launch (kNjScanBlocks workgroups at most, one partial each) and a merge

@@ -420,6 +420,27 @@ class Engine:
                                            C.byref(n_clusters), C.byref(links)))
         return labels[:n], int(links.value)
 
+    def mst(self, measure, max_pairs: int = 0, tallies: bool = False):
+        """Minimum spanning forest of slot 0 (dst_mst): (edges uint32[n_edges, 2], values[n_edges], rounds), plus
+        tallies[n_edges, width] when asked.  An edge for every pair whose DST_OUT_DISTANCE payload is not NaN, ordered by
+        (key of the value, i, j); the result is the unique minimum spanning forest under that order, its edges ascending,
+        values bitwise run_square's.  rounds: the Boruvka rounds that added edges.  max_pairs: the most pairs of one row
+        slab (0: the default); the result does not depend on it."""
+        m = _measure_id(measure)
+        n, _ = self.set_info(0)
+        cap = max(n - 1, 1)
+        width = self._lib.dst_tally_width(m)
+        ei, ej = np.zeros(cap, np.uint32), np.zeros(cap, np.uint32)
+        values = np.zeros(cap, np.int64 if m in (0, 1) else np.float64)
+        tal = np.zeros((cap, width), np.uint32) if tallies else None
+        n_edges, rounds = C.c_uint64(), C.c_uint32()
+        self._check(self._lib.dst_mst(self._h, m, int(max_pairs), ei.ctypes.data, ej.ctypes.data, values.ctypes.data,
+                                      None if tal is None else tal.ctypes.data, cap, C.byref(n_edges), C.byref(rounds)))
+        ne = int(n_edges.value)
+        edges = np.stack([ei[:ne], ej[:ne]], axis=1)
+        out = (edges, values[:ne].copy(), int(rounds.value))
+        return out + (tal[:ne].copy(),) if tallies else out
+
     def nj(self, measure, max_pairs: int = 0):
         """Neighbour-joining tree of slot 0 (dst_nj): (parent uint32[2n-2], length float64[2n-2]).  Leaves are 0..n-1,
         the node made in round s is n + s, the root 2n - 3 (parent 0xFFFFFFFF, length 0).  max_pairs: the most pairs of

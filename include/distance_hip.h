@@ -380,6 +380,36 @@ int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slo
  * in row slabs whose payloads a lock-free union-find on the device consumes.  Single GPU, loaded set only (not dst_stream). */
 int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs, uint32_t *label, size_t cap,
                  uint64_t *n_clusters, uint64_t *links);
+/* ---- minimum spanning tree --------------------------------------------------------------------- */
+/* The single-linkage picture for every threshold at once: the minimum spanning tree (forest) of one set (slot 0, n
+ * records), as GrapeTree- and PHYLOViZ-style viewers draw it, computed next to the values on the GPU by Boruvka rounds
+ * that recompute the triangle in row slabs: O(n) device memory beside one slab, so it also serves sets whose square
+ * cannot be held.  The definition is fixed to the bit:
+ *   graph   an edge {i, j}, i < j, for every pair whose DST_OUT_DISTANCE payload v (the value dst_run_square returns,
+ *           bit-identical on every path) is not NaN.  +inf is an edge; -0.0 is +0.0; NaN is never an edge (as in
+ *           dst_clusters, where NaN never links).
+ *   order   edges are ordered by (key(v), i, j) lexicographically, key = dst_nearest's sort key: n / n_high (int64)
+ *           (uint64)v ^ 2^63; f64 -0.0 -> the key of +0.0, any other non-NaN value the order-preserving flip (v >= 0:
+ *           bits | 2^63, v < 0: ~bits).  A strict total order, so the minimum spanning forest under it is unique: the
+ *           forest Kruskal's algorithm builds when it takes the edges in that order.
+ *   result  that forest's edges in ascending order: *n_edges = n - c of them, c the number of connected components of
+ *           the non-NaN graph (a connected graph: n - 1).  It depends neither on the path nor on max_pairs.
+ * Consequence: for every T, the connected components of the result's edges with v <= T (by dst_clusters' rule) are
+ * exactly dst_clusters(T)'s clusters: the edges in order are the single-linkage dendrogram.
+ *   max_pairs   0: the default slab bound (2^25 pairs); else the most pairs of one row slab, as in dst_clusters
+ *   edge_i, edge_j   the edges, edge_i[e] < edge_j[e] (host memory, required)
+ *   values      NULL, or the edges' DST_OUT_DISTANCE payloads: bitwise what dst_run_square returns for the pair
+ *   tallies     NULL, or dst_tally_width(measure) DST_OUT_TALLY words per edge (dst_finalize -> the reference's bits;
+ *               tn93: base counts in (i, j) order)
+ *   cap         the room of every non-NULL output in entries; below n - 1 (n >= 2): DST_ERR_CAPACITY, whatever the
+ *               forest turns out to hold
+ *   rounds      the Boruvka rounds that added edges (at most ceil(log2 n)), or NULL; n_edges may be NULL too
+ * n < 2: DST_OK, 0 edges, 0 rounds.  DST_ERR_ARG: an unknown measure, a NULL edge_i or edge_j, n >= 2^32-1;
+ * DST_ERR_STATE: slot 0 is not uploaded.  Synchronous on the context's stream.  Every round computes the triangle once
+ * more (row slabs, as dst_clusters); one more sweep as tallies serves values / tallies and is skipped when both are NULL.
+ * Slots, the path choice and later dst_run_square results are untouched.  Single GPU, loaded set only (not dst_stream). */
+int dst_mst(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *edge_i, uint32_t *edge_j, void *values,
+            uint32_t *tallies, size_t cap, uint64_t *n_edges, uint32_t *rounds);
 /* ---- neighbour-joining trees ------------------------------------------------------------------- */
 /* The neighbour-joining (NJ) tree of n >= 3 records, built on the GPU from the square it holds, with the arithmetic fixed
  * below so that a restatement in any language reproduces it bit for bit.  Every expression is evaluated in the order
