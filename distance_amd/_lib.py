@@ -109,6 +109,9 @@ _SIGS = {
     "dst_newick": (C.c_int, [C.c_uint64, _vp, _vp, C.c_char_p, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dst_newick_support": (C.c_int, [C.c_uint64, _vp, _vp, C.c_char_p, _vp, _vp, _vp, C.c_size_t,
                                      C.POINTER(C.c_size_t)]),
+    "dst_dendrogram": (C.c_int, [_vp, C.c_int, C.c_int, C.c_uint64, _vp, _vp, _vp, C.c_size_t, _u64p]),
+    "dst_dendrogram_matrix": (C.c_int, [_vp, _vp, C.c_uint64, C.c_int, _vp, _vp, _vp, C.c_size_t, _u64p]),
+    "dst_newick_rooted": (C.c_int, [C.c_uint64, _vp, _vp, C.c_char_p, _vp, _vp, C.c_size_t, C.POINTER(C.c_size_t)]),
     "dst_bootstrap_columns": (None, [C.c_uint64, C.c_uint32, C.c_uint64, _vp]),
     "dst_nj_bootstrap": (C.c_int, [_vp, C.c_int, _vp, C.c_size_t, C.c_size_t, C.c_size_t, C.c_uint32, C.c_uint64,
                                    C.c_uint64, _vp, _vp, _vp, C.c_size_t]),

@@ -12,7 +12,8 @@
 // --matrix tsv|phylip (a square or rectangular distance matrix instead of the long form: dst_text_matrix), --tree nj (the
 // neighbour-joining tree as one Newick line: dst_nj, dst_newick), --bootstrap B / --seed S (the tree's splits labelled
 // with their support in B column resamplings: dst_nj_bootstrap, dst_newick_support), --mst (the edges of the minimum
-// spanning tree in ascending order, one "id1, id2, value" line each: dst_mst).
+// spanning tree in ascending order, one "id1, id2, value" line each: dst_mst), --dendrogram average|weighted|complete (the
+// UPGMA / WPGMA / complete-linkage dendrogram as one Newick line with a binary root: dst_dendrogram, dst_newick_rooted).
 //
 // Exactness: the GPU returns integer site tallies; f64 finalisation is dst_finalize() on the host
 // (reference operation order, glibc log/sqrt), so the printed digits do not depend on the device.
@@ -123,6 +124,9 @@ void print_help()
         "      --mst                    Print only the edges of the minimum spanning tree of the records (pairs without a "
         "distance, NaN, are no edges: a forest then), in ascending order of (distance, first record, second record), each "
         "as the line the full run prints for that pair. One input, one GPU, no --stream and no other output mode\n"
+        "      --dendrogram <linkage>   Print the rooted hierarchical-clustering tree of the records as one Newick line instead "
+        "of distances: linkage average (UPGMA), weighted (WPGMA) or complete. One input, one GPU, no --stream and no other "
+        "output mode\n"
         "  -h, --help                   Print help\n"
         "  -V, --version                Print version");
 }
@@ -149,6 +153,7 @@ struct Args {
     bool has_seed = false;
     bool has_slab_pairs = false;
     bool has_mst = false;                 // --mst
+    int dendrogram = -1;                  // --dendrogram: DST_LINK_* (-1: none)
     std::string selftest;
 };
 
@@ -261,7 +266,8 @@ Args parse_args(int argc, char **argv)
         } else if (arg == "--tree" || arg.rfind("--tree=", 0) == 0) {
             const std::string v = value_of(k, arg, "--tree <method>");
             if (v != "nj")
-                die_usage("invalid value '" + v + "' for '--tree <method>'\n  [possible values: nj]");
+                die_usage("invalid value '" + v + "' for '--tree <method>'\n  [possible values: nj]\n  (UPGMA and the other "
+                          "rooted linkage trees: see '--dendrogram average')");
             a.has_tree = true;
         } else if (arg == "--bootstrap" || arg.rfind("--bootstrap=", 0) == 0) {
             const std::string v = value_of(k, arg, "--bootstrap <B>");
@@ -275,6 +281,17 @@ Args parse_args(int argc, char **argv)
             a.has_seed = true;
         } else if (arg == "--mst") {
             a.has_mst = true;
+        } else if (arg == "--dendrogram" || arg.rfind("--dendrogram=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--dendrogram <linkage>");
+            if (v == "average")
+                a.dendrogram = DST_LINK_AVERAGE;
+            else if (v == "weighted")
+                a.dendrogram = DST_LINK_WEIGHTED;
+            else if (v == "complete")
+                a.dendrogram = DST_LINK_COMPLETE;
+            else
+                die_usage("invalid value '" + v + "' for '--dendrogram <linkage>'\n  [possible values: average, weighted, "
+                          "complete]");
         } else if (arg == "--host-selftest") {
             a.selftest = value_of(k, arg, "--host-selftest <what>");
         } else {
@@ -283,6 +300,18 @@ Args parse_args(int argc, char **argv)
     }
     if (a.pos_inputs.size() > 2)
         die_usage("unexpected argument '" + a.pos_inputs[2] + "' found");
+    if (a.dendrogram >= 0) {
+        // (--bootstrap and --seed: the checks below, which ask for '--tree nj')
+        const char *other = a.has_stream ? "--stream <stream>" : a.has_nearest ? "--nearest <k>" : a.has_clusters ? "--clusters <T>"
+                            : a.matrix >= 0 ? "--matrix <format>" : a.has_tree ? "--tree <method>" : a.has_mst ? "--mst" : nullptr;
+        if (other)
+            die_usage(std::string("the argument '--dendrogram <linkage>' cannot be used with '") + other + "'");
+        if (a.flag_inputs.size() + a.pos_inputs.size() > 1)
+            die_usage("the argument '--dendrogram <linkage>' takes one input alignment, not two");
+        if (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1))
+            die_usage(std::string("the argument '--dendrogram <linkage>' cannot be used with '") +
+                      (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
+    }
     if (a.has_nearest && a.has_stream)
         die_usage("the argument '--nearest <k>' cannot be used with '--stream <stream>'");
     if (a.has_nearest && (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1)))
@@ -1354,6 +1383,38 @@ void write_tree(const Ctx &gpu, const Alignment &set, int measure, uint64_t max_
     wr.write(out.data(), len);
 }
 
+// --dendrogram: the UPGMA / WPGMA / complete-linkage tree of one set as one Newick line with a binary root
+// (dst_dendrogram on the GPU, dst_newick_rooted on the host)
+void write_dendrogram(const Ctx &gpu, const Alignment &set, int measure, int linkage, uint64_t max_pairs, Writer &wr)
+{
+    if (set.n < 2) {
+        std::fprintf(stderr, "error: a dendrogram needs at least 2 records, the input has %zu\n", (size_t)set.n);
+        leave(1);
+    }
+    std::vector<uint32_t> parent(2 * set.n - 1);
+    std::vector<double> length(2 * set.n - 1);
+    const int rc = dst_dendrogram(gpu.h, measure, linkage, max_pairs, parent.data(), length.data(), nullptr, parent.size(),
+                                  nullptr);
+    if (rc == DST_ERR_STATE && non_finite_pair(gpu, set, "", ": no dendrogram"))
+        leave(1);
+    gpu.check(rc, "dendrogram");
+    std::string chars;
+    std::vector<uint64_t> offsets(set.n + 1, 0);
+    for (size_t r = 0; r < set.n; ++r) {
+        chars += set.ids[r];
+        offsets[r + 1] = chars.size();
+    }
+    size_t len = 0;
+    dst_newick_rooted(set.n, parent.data(), length.data(), chars.data(), offsets.data(), nullptr, 0, &len);
+    std::string out(len, '\0');
+    if (dst_newick_rooted(set.n, parent.data(), length.data(), chars.data(), offsets.data(), out.data(), out.size(), &len) !=
+        DST_OK) {
+        std::fprintf(stderr, "error: the Newick text of the tree could not be written\n");
+        leave(1);
+    }
+    wr.write(out.data(), len);
+}
+
 int host_selftest(const Args &a)
 {
     if (a.selftest == "fasta") {  // parse stdin, print one line per record
@@ -1578,7 +1639,7 @@ int main(int argc, char **argv)
     } else if (a.matrix == DST_MATRIX_PHYLIP) {
         const std::string h = std::to_string(loaded[0].n) + "\n";
         wr.write(h.data(), h.size());
-    } else if (!a.has_clusters && !a.has_tree) {
+    } else if (!a.has_clusters && !a.has_tree && a.dendrogram < 0) {
         wr.write(header, sizeof header - 1);
     }
 
@@ -1587,6 +1648,8 @@ int main(int argc, char **argv)
     job.fmt_threads = std::max<size_t>(1, threads / (size_t)G);
     if (a.has_tree) {
         write_tree(gpus[0], loaded[0], measure, a.has_slab_pairs ? a.slab_pairs : 0, a.bootstrap, a.seed, wr);
+    } else if (a.dendrogram >= 0) {
+        write_dendrogram(gpus[0], loaded[0], measure, a.dendrogram, a.has_slab_pairs ? a.slab_pairs : 0, wr);
     } else if (a.has_clusters) {
         write_clusters(gpus[0], loaded[0], measure, a.clusters, wr);
     } else if (a.has_mst) {

@@ -1281,7 +1281,7 @@ int dst_destroy(dst_ctx *ctx)
     for (void *b : {(void *)ctx->d_lut, (void *)ctx->d_total, (void *)ctx->scan_tmp, ctx->host_out, ctx->hot_tally, ctx->text_res,
                     ctx->text_num, (void *)ctx->text_len, (void *)ctx->text_scan, (void *)ctx->text_buf, (void *)ctx->text_flag, ctx->text_ties,
                     (void *)ctx->ids[0].off, (void *)ctx->ids[0].chars, (void *)ctx->ids[1].off, (void *)ctx->ids[1].chars, ctx->nn_slab, ctx->nn_lists,
-                    ctx->cl_slab, ctx->cl_work, ctx->mst_work})
+                    ctx->cl_slab, ctx->cl_work, ctx->mst_work, ctx->dg_work})
         if (b)
             (void)hipFree(b);
     if (ctx->scratch)
@@ -2117,13 +2117,15 @@ int dst_mst(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *edge_i, uin
 namespace {
 
 // The device memory of one NJ call: the two matrix buffers and one block for the rest.  Per call, not grow-only: the
-// square of 50,000 records is 20 GB.  Freed behind the context's stream.
+// square of 50,000 records is 20 GB.  Freed behind the context's stream.  dst_dendrogram fills the same square through
+// nj_fill and needs no compaction: setup(n, false) leaves the second matrix buffer out.
 struct NjAlloc {
     dst_ctx *ctx;
+    const char *what;
     void *D0 = nullptr, *D1 = nullptr, *work = nullptr;
     NjBuffers b{};
     unsigned long long *bad = nullptr;
-    explicit NjAlloc(dst_ctx *c) : ctx(c) {}
+    explicit NjAlloc(dst_ctx *c, const char *w = "neighbour joining") : ctx(c), what(w) {}
     ~NjAlloc()
     {
         (void)hipStreamSynchronize(ctx->stream);
@@ -2136,16 +2138,16 @@ struct NjAlloc {
         if (hipMalloc(p, bytes) != hipSuccess) {
             *p = nullptr;
             (void)hipGetLastError();   // (clear the out-of-memory status: later launches check hipGetLastError)
-            return fail(ctx, DST_ERR_NOMEM, "neighbour joining: cannot allocate " + std::to_string(bytes) +
+            return fail(ctx, DST_ERR_NOMEM, std::string(what) + ": cannot allocate " + std::to_string(bytes) +
                                                 " bytes of device memory");
         }
         return DST_OK;
     }
-    int setup(uint64_t n)
+    int setup(uint64_t n, bool compaction = true)
     {
         const uint64_t n1 = std::max<uint64_t>(3 * n / 4, 1);
         int rc = alloc(&D0, n * n * 8);
-        if (!rc)
+        if (!rc && compaction)
             rc = alloc(&D1, n1 * n1 * 8);
         auto up = [](size_t x) { return (x + 255) / 256 * 256; };
         const size_t nodes = 2 * n - 2;
@@ -2389,6 +2391,141 @@ int dst_nj_matrix(dst_ctx *ctx, const double *d, uint64_t n, uint32_t *parent, d
     HIP_TRY(ctx, launch_nj_init(al.b.D[0], n, al.b.ids[0], al.b.active, al.bad, stream));
     HIP_TRY(ctx, launch_nj_mirror(al.b.D[0], n, stream));
     return nj_finish(ctx, al, n, parent, length);
+}
+
+namespace {
+
+int dg_check(dst_ctx *ctx, uint64_t n, int linkage, uint32_t *parent, double *length, size_t cap)
+{
+    if (linkage < DST_LINK_AVERAGE || linkage > DST_LINK_COMPLETE)
+        return fail(ctx, DST_ERR_ARG, "unknown linkage");
+    if (!parent || !length)
+        return fail(ctx, DST_ERR_ARG, "null parent or length pointer");
+    if (n < 2)
+        return fail(ctx, DST_ERR_ARG, "a dendrogram needs at least 2 records");
+    if (n >= ((uint64_t)1 << 31))
+        return fail(ctx, DST_ERR_ARG, "a dendrogram of 2^31 records or more");
+    if (n > ((uint64_t)1 << 30))   // (8 n^2 must fit 64 bits before it is asked for; 2^30 records are 2^63 bytes)
+        return fail(ctx, DST_ERR_NOMEM, "dendrogram: a square of " + std::to_string(n) + " records does not fit device memory");
+    if (cap < 2 * n - 1)
+        return fail(ctx, DST_ERR_CAPACITY, "cap is below 2n - 1 entries");
+    return DST_OK;
+}
+
+// the O(n) state of a dendrogram call in the context's grow-only scratch, beside the square (and its flags) of `al`
+int dg_buffers(dst_ctx *ctx, NjAlloc &al, uint64_t n, DgBuffers &b)
+{
+    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
+    const size_t nodes = 2 * n - 1, nblk = (n + kDgBlockRows - 1) / kDgBlockRows;
+    const size_t o_key = up(n * 4), o_col = o_key + up(n * 8), o_blk = o_col + up(n * 4), o_list = o_blk + up(nblk * 8),
+                 o_cnt = o_list + up(n * 4), o_par = o_cnt + 256, o_len = o_par + up(nodes * 4), o_hgt = o_len + up(nodes * 8),
+                 total = o_hgt + up(nodes * 8);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (an earlier call's state goes before it is replaced)
+    if (int rc = ensure_bytes(ctx, &ctx->dg_work, &ctx->dg_work_bytes, total))
+        return rc;
+    char *w = static_cast<char *>(ctx->dg_work);
+    b.D = al.b.D[0];
+    b.active = al.b.active;
+    b.node = al.b.ids[0];
+    b.size = reinterpret_cast<uint32_t *>(w);
+    b.row_key = reinterpret_cast<uint64_t *>(w + o_key);
+    b.row_col = reinterpret_cast<uint32_t *>(w + o_col);
+    b.blk_key = reinterpret_cast<uint64_t *>(w + o_blk);
+    b.list = reinterpret_cast<uint32_t *>(w + o_list);
+    b.counters = reinterpret_cast<uint32_t *>(w + o_cnt);
+    b.scans = reinterpret_cast<unsigned long long *>(w + o_cnt + 16);
+    b.pair = reinterpret_cast<DgPair *>(w + o_cnt + 32);
+    b.parent = reinterpret_cast<uint32_t *>(w + o_par);
+    b.length = reinterpret_cast<double *>(w + o_len);
+    b.height = reinterpret_cast<double *>(w + o_hgt);
+    return DST_OK;
+}
+
+// the rounds behind the fill on the context's stream, then one copy of the tree to the host
+int dg_finish(dst_ctx *ctx, const DgBuffers &b, uint64_t n, int linkage, uint32_t *parent, double *length, double *height,
+              uint64_t *row_scans)
+{
+    hipStream_t stream = ctx->stream;
+    unsigned long long scans = 0;
+    HIP_TRY(ctx, launch_dg_init(b, n, stream));
+    HIP_TRY(ctx, launch_dg_rounds(b, n, linkage, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(parent, b.parent, (2 * n - 1) * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(length, b.length, (2 * n - 1) * 8, hipMemcpyDeviceToHost, stream));
+    if (height)
+        HIP_TRY(ctx, hipMemcpyAsync(height, b.height, (2 * n - 1) * 8, hipMemcpyDeviceToHost, stream));
+    uint32_t failed = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&scans, b.scans, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&failed, b.counters + 2, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (row_scans)
+        *row_scans = scans;
+    if (failed)   // (the row-minimum cache lost the pair: never a tree that is silently wrong)
+        return fail(ctx, DST_ERR_STATE, "dendrogram: internal error, round " + std::to_string(failed - 1) +
+                                            " found no active pair");
+    return DST_OK;
+}
+
+}  // namespace
+
+int dst_dendrogram(dst_ctx *ctx, int measure, int linkage, uint64_t max_pairs, uint32_t *parent, double *length,
+                   double *height, size_t cap, uint64_t *row_scans)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    DeviceSet &set = ctx->set[0];
+    if (!set.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    const uint64_t n = set.n;
+    if (int rc = dg_check(ctx, n, linkage, parent, length, cap))
+        return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    std::vector<RowSlab> slabs;
+    int rc = nj_slabs(ctx, measure, n, max_pairs, slabs);
+    if (rc)
+        return rc;
+    NjAlloc al(ctx, "dendrogram");
+    DgBuffers b{};
+    if ((rc = al.setup(n, false)) || (rc = dg_buffers(ctx, al, n, b)))
+        return rc;
+    if ((rc = nj_fill(ctx, measure, set, slabs, al)))
+        return rc;
+    // one look at the fill before the rounds: a non-finite distance ends the call
+    unsigned long long bad = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, al.bad, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (bad != ~0ull)
+        return nj_bad_pair(ctx, "dendrogram: ", bad, n);
+    return dg_finish(ctx, b, n, linkage, parent, length, height, row_scans);
+}
+
+int dst_dendrogram_matrix(dst_ctx *ctx, const double *d, uint64_t n, int linkage, uint32_t *parent, double *length,
+                          double *height, size_t cap, uint64_t *row_scans)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (!d)
+        return fail(ctx, DST_ERR_ARG, "null matrix pointer");
+    if (int rc = dg_check(ctx, n, linkage, parent, length, cap))
+        return rc;
+    for (uint64_t i = 0; i < n; ++i)
+        for (uint64_t j = i + 1; j < n; ++j)
+            if (!std::isfinite(d[i * n + j]))
+                return fail(ctx, DST_ERR_ARG, "dendrogram: the distance of records " + std::to_string(i) + " and " +
+                                                  std::to_string(j) + " is not finite");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    NjAlloc al(ctx, "dendrogram");
+    DgBuffers b{};
+    int rc;
+    if ((rc = al.setup(n, false)) || (rc = dg_buffers(ctx, al, n, b)))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(b.D, d, n * n * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, launch_nj_init(b.D, n, b.node, b.active, al.bad, stream));
+    HIP_TRY(ctx, launch_nj_mirror(b.D, n, stream));
+    return dg_finish(ctx, b, n, linkage, parent, length, height, row_scans);
 }
 
 int dst_run_square_host(dst_ctx *ctx, int measure, uint64_t row_begin, uint64_t row_end, int out_kind,

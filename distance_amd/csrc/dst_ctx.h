@@ -103,6 +103,9 @@ struct dst_ctx {
     // dst_mst: the component, best-edge and edge-list arrays (grow-only; the slab scratch is cl_slab)
     void *mst_work = nullptr;
     size_t mst_work_bytes = 0;
+    // dst_dendrogram: the O(n) state beside the per-call square (grow-only; the slab scratch is cl_slab)
+    void *dg_work = nullptr;
+    size_t dg_work_bytes = 0;
     // HIP events around the pair kernel ([0]) and the pack kernel ([1]) of the most recent launches, recorded on the launch
     // stream: a ring, so that a caller timing many steps reads them ONCE at the end (dst_kernel_ms_mean) instead of
     // waiting for the device after every step

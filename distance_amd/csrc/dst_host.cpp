@@ -320,9 +320,9 @@ std::vector<ConsensusTile> build_consensus_tiles(bool square, uint64_t row_begin
 }
 
 bool tree_children(uint64_t n, const uint32_t *parent, std::vector<uint64_t> &first, std::vector<uint64_t> &child,
-                   uint64_t &root)
+                   uint64_t &root, bool rooted)
 {
-    const uint64_t N = 2 * n - 2;
+    const uint64_t N = rooted ? 2 * n - 1 : 2 * n - 2;
     first.assign(N + 1, 0);
     child.assign(N, 0);
     root = N;
@@ -341,7 +341,7 @@ bool tree_children(uint64_t n, const uint32_t *parent, std::vector<uint64_t> &fi
         return false;
     for (uint64_t x = 0; x < N; ++x) {
         const uint64_t kids = first[x + 1];
-        if (kids != (x < n ? 0u : x == root ? 3u : 2u))
+        if (kids != (x < n ? 0u : x == root && !rooted ? 3u : 2u))
             return false;
     }
     for (uint64_t x = 0; x < N; ++x)
@@ -676,25 +676,26 @@ int dst_format_distance(int measure, double as_float, int64_t as_int, char *buf,
     return std::snprintf(buf, cap, "%.12f", as_float);
 }
 
-// Newick text of a dst_nj tree: children in ascending node id, leaves by their ids (quoted where Newick needs it),
+// Newick text of a dst_nj tree (rooted: of a dst_dendrogram tree, 2n - 1 nodes and a binary root): children in
+// ascending node id, leaves by their ids (quoted where Newick needs it),
 // lengths as dst_format_distance prints an f64 distance, and support[x] after an internal non-root node's ')' when
 // support is given.  Iterative: a caterpillar tree is n levels deep.
 static int newick_text(uint64_t n, const uint32_t *parent, const double *length, const char *chars, const uint64_t *offsets,
-                const uint32_t *support, char *out, size_t cap, size_t *len)
+                const uint32_t *support, char *out, size_t cap, size_t *len, bool rooted = false)
 {
     if (len)
         *len = 0;
-    if (!parent || !length || !offsets || !len || n < 3 || n >= ((uint64_t)1 << 31) || (!out && cap))
+    if (!parent || !length || !offsets || !len || n < (rooted ? 2u : 3u) || n >= ((uint64_t)1 << 31) || (!out && cap))
         return DST_ERR_ARG;
     if (offsets[n] > 0 && !chars)
         return DST_ERR_ARG;
     for (uint64_t r = 0; r < n; ++r)
         if (offsets[r] > offsets[r + 1])
             return DST_ERR_ARG;
-    const uint64_t N = 2 * n - 2;
+    const uint64_t N = rooted ? 2 * n - 1 : 2 * n - 2;
     std::vector<uint64_t> first, child;
     uint64_t root;
-    if (!tree_children(n, parent, first, child, root))
+    if (!tree_children(n, parent, first, child, root, rooted))
         return DST_ERR_ARG;
     auto quoted = [](const char *s, size_t l) {
         if (l == 0)
@@ -775,6 +776,12 @@ int dst_newick_support(uint64_t n, const uint32_t *parent, const double *length,
                        const uint64_t *offsets, const uint32_t *support, char *out, size_t cap, size_t *len)
 {
     return newick_text(n, parent, length, chars, offsets, support, out, cap, len);
+}
+
+int dst_newick_rooted(uint64_t n, const uint32_t *parent, const double *length, const char *chars,
+                      const uint64_t *offsets, char *out, size_t cap, size_t *len)
+{
+    return newick_text(n, parent, length, chars, offsets, nullptr, out, cap, len, true);
 }
 
 }  // extern "C"

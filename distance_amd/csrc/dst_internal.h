@@ -449,6 +449,37 @@ hipError_t launch_nj_mirror(double *D, uint64_t n, hipStream_t stream);
 // every round, the root included, into b.parent / b.length; n >= 3, D[0] symmetric with a +0.0 diagonal
 hipError_t launch_nj_rounds(const NjBuffers &b, uint64_t n, hipStream_t stream);
 
+// ---- dendrograms (dst_dendrogram.hip, driven by dst_dendrogram / dst_dendrogram_matrix in dst_api.cpp) --------------
+// The n x n f64 square (filled as for NJ) and a row-minimum cache: for every active slot x the smallest (nn_key, column)
+// over the active k > x, and per block of kDgBlockRows rows the smallest cached key.  A round is three launches known
+// from n alone: the select (one workgroup: the pair from the block minima, the new node), the merge (thread k: the
+// linkage update of (a, k) and (k, a), row k's cache entry lowered or invalidated) and the rescan (a fixed grid that
+// takes the invalidated rows from a device list).  All of it is O(n) beside D.
+constexpr uint32_t kDgBlockRows = 256;
+struct DgPair {
+    uint32_t a, b, sa, sb;
+};
+struct DgBuffers {
+    double *D;             // n x n
+    uint8_t *active;       // slot holds a cluster
+    uint32_t *node;        // node id by slot
+    uint32_t *size;        // cluster size by slot
+    uint64_t *row_key;     // cached minimum of row x over active k > x (~0: none, or the row waits for its rescan)
+    uint32_t *row_col;     // ... and its column
+    uint64_t *blk_key;     // ceil(n / kDgBlockRows) block minima of row_key
+    uint32_t *list;        // the rows to rescan (n entries)
+    uint32_t *counters;    // [0] entries of list, [1] entries taken, [2] 0, or 1 + the first round that found no pair
+    unsigned long long *scans;   // whole-row scans so far
+    DgPair *pair;          // the round's pair, from the select to the merge
+    uint32_t *parent;      // 2n - 1 entries
+    double *length, *height;
+};
+// node := identity, size := 1, heights := +0.0, every row listed for its first scan, the block minima := ~0
+hipError_t launch_dg_init(const DgBuffers &b, uint64_t n, hipStream_t stream);
+// the first scan of every row, then every round, the root included, into b.parent / b.length / b.height; n >= 2, D
+// symmetric and finite
+hipError_t launch_dg_rounds(const DgBuffers &b, uint64_t n, int linkage, hipStream_t stream);
+
 // ---- bootstrap replicates (dst_bootstrap.hip, driven by dst_nj_bootstrap in dst_api.cpp) -----------------------------
 // replicate r of the n x len codes at src (rows pitch bytes apart, pitch a multiple of 128 and >= len) into out (the same
 // pitch): out[i][c] := src[i][boot_column(seed, r * len + c, len)]; map: len entries of scratch
@@ -472,9 +503,9 @@ struct RowSlab {
 std::vector<RowSlab> cut_row_slabs(bool square, uint64_t n_rows, uint64_t n_cols, uint64_t max_pairs);
 // dst_newick's shape checks of a dst_nj tree (2n - 2 nodes): ids in range, exactly one root, three children at the root,
 // two at every other internal node, none at a leaf, every node below the root.  The children of x in ascending id are
-// child[first[x] .. first[x + 1]).
+// child[first[x] .. first[x + 1]).  rooted: a dst_dendrogram tree instead (2n - 1 nodes, two children at the root too).
 bool tree_children(uint64_t n, const uint32_t *parent, std::vector<uint64_t> &first, std::vector<uint64_t> &child,
-                   uint64_t &root);
+                   uint64_t &root, bool rooted = false);
 // Bootstrap support (dst_nj_bootstrap): the main tree's splits, each internal non-root node x's, keyed exactly by an
 // interval of leaf numbers; count() adds 1 to support[x] for every main split a replicate tree holds.  O(n) per tree.
 class SplitCounter {

@@ -179,6 +179,43 @@ def newick(parent, length, ids, support=None) -> bytes:
     return buf.raw[:need.value]
 
 
+LINKAGES = ("average", "weighted", "complete")
+
+
+def _linkage_id(linkage) -> int:
+    if isinstance(linkage, str):
+        if linkage not in LINKAGES:
+            raise ValueError(f"unknown linkage {linkage!r}: one of {', '.join(LINKAGES)}")
+        return LINKAGES.index(linkage)
+    return int(linkage)
+
+
+def newick_rooted(parent, length, ids) -> bytes:
+    """Newick text of a tree from Engine.dendrogram / dendrogram_matrix (dst_newick_rooted): 2n - 1 nodes, a binary
+    root; ids name the leaves 0..n-1 (str or bytes)."""
+    parent = np.ascontiguousarray(parent, np.uint32)
+    length = np.ascontiguousarray(length, np.float64)
+    names = [i.encode() if isinstance(i, str) else bytes(i) for i in ids]
+    n = len(names)
+    chars = b"".join(names)
+    offsets = np.zeros(n + 1, np.uint64)
+    offsets[1:] = np.cumsum([len(x) for x in names], dtype=np.uint64) if n else []
+    if len(parent) != max(2 * n - 1, 0) or len(length) != len(parent):
+        raise ValueError("parent and length need 2n - 1 entries for n ids")
+    lib = load()
+    need = C.c_size_t(0)
+    rc = lib.dst_newick_rooted(n, parent.ctypes.data, length.ctypes.data, chars, offsets.ctypes.data, None, 0,
+                               C.byref(need))
+    if rc not in (0, 6):
+        raise DistanceError(rc, "dst_newick_rooted: malformed tree or arguments")
+    buf = C.create_string_buffer(max(need.value, 1))
+    rc = lib.dst_newick_rooted(n, parent.ctypes.data, length.ctypes.data, chars, offsets.ctypes.data, buf, need.value,
+                               C.byref(need))
+    if rc:
+        raise DistanceError(rc, "dst_newick_rooted")
+    return buf.raw[:need.value]
+
+
 def bootstrap_columns(seed: int, replicate: int, length: int) -> np.ndarray:
     """The source column of every column of bootstrap replicate `replicate` (dst_bootstrap_columns): uint32[length]."""
     cols = np.zeros(max(int(length), 1), np.uint32)
@@ -488,6 +525,36 @@ class Engine:
         self._check(self._lib.dst_nj_matrix(self._h, d.ctypes.data, n, parent.ctypes.data, length.ctypes.data,
                                             max(2 * n - 2, 0)))
         return parent, length
+
+    def dendrogram(self, measure, linkage="average", max_pairs: int = 0, stats: bool = False):
+        """Dendrogram of slot 0 (dst_dendrogram) under linkage "average" (UPGMA), "weighted" (WPGMA) or "complete":
+        (parent uint32[2n-1], length float64[2n-1], height float64[2n-1]).  Leaves are 0..n-1, the node made in round t
+        is n + t, the root 2n - 2 (parent 0xFFFFFFFF, length 0).  max_pairs: the most pairs of one row slab of the fill
+        (0: the default); the tree does not depend on it.  stats=True: also row_scans, the whole-row scans made."""
+        m, link = _measure_id(measure), _linkage_id(linkage)
+        n, _ = self.set_info(0)
+        cap = max(2 * n - 1, 1)
+        parent, length, height = np.zeros(cap, np.uint32), np.zeros(cap, np.float64), np.zeros(cap, np.float64)
+        scans = C.c_uint64()
+        self._check(self._lib.dst_dendrogram(self._h, m, link, int(max_pairs), parent.ctypes.data, length.ctypes.data,
+                                             height.ctypes.data, max(2 * n - 1, 0), C.byref(scans)))
+        return (parent, length, height, int(scans.value)) if stats else (parent, length, height)
+
+    def dendrogram_matrix(self, d, linkage="average", stats: bool = False):
+        """Dendrogram of an n x n distance matrix (dst_dendrogram_matrix; only the strict upper triangle is read):
+        (parent, length, height) as dendrogram(), with row_scans when stats=True."""
+        d = np.ascontiguousarray(d, np.float64)
+        if d.ndim != 2 or d.shape[0] != d.shape[1]:
+            raise ValueError("dendrogram_matrix needs a square matrix")
+        link = _linkage_id(linkage)
+        n = d.shape[0]
+        cap = max(2 * n - 1, 1)
+        parent, length, height = np.zeros(cap, np.uint32), np.zeros(cap, np.float64), np.zeros(cap, np.float64)
+        scans = C.c_uint64()
+        self._check(self._lib.dst_dendrogram_matrix(self._h, d.ctypes.data, n, link, parent.ctypes.data,
+                                                    length.ctypes.data, height.ctypes.data, max(2 * n - 1, 0),
+                                                    C.byref(scans)))
+        return (parent, length, height, int(scans.value)) if stats else (parent, length, height)
 
     # ---- runs into device memory (bench / multi-GPU) ------------------------------------------
     def run_square_device(self, measure, row_begin: int, row_end: int, d_out: int, capacity: int,

@@ -461,6 +461,55 @@ int dst_nj_matrix(dst_ctx *ctx, const double *d, uint64_t n, uint32_t *parent, d
 int dst_newick(uint64_t n, const uint32_t *parent, const double *length, const char *chars, const uint64_t *offsets,
                char *out, size_t cap, size_t *len);
 
+/* ---- hierarchical-clustering dendrograms ------------------------------------------------------------ */
+/* The rooted dendrogram of n >= 2 records under a Lance-Williams linkage (UPGMA, WPGMA, complete linkage), built on the
+ * GPU from the square it holds, with the arithmetic fixed below so that a restatement in any language reproduces it bit
+ * for bit.  Every expression is evaluated in the order written (the library is compiled -ffp-contract=off).
+ *
+ * Input.  dst_dendrogram: slot 0 (n records); D(i, j) is the pair's DST_OUT_DISTANCE payload for `measure` (f64 as is,
+ * int64 of n / n_high converted to double), bit-identical on every path, so the tree depends neither on the path nor on
+ * max_pairs (the most pairs of one row slab of the fill; 0: the default, as in dst_nj).  dst_dendrogram_matrix: a host
+ * n x n row-major matrix of which only the strict upper triangle is read.
+ *
+ * State.  Every active cluster has a slot (the smallest record index it contains), a node id, a size s (an integer)
+ * and a height h.  Initially record i is the cluster of slot i, node i, s = 1, h = +0.0.
+ *
+ * Round t = 0 .. n-2:
+ *   1. the pair: over active slots a < b, the smallest (nn_key(d_ab), a, b) lexicographically; nn_key is the sort key
+ *      of dst_nearest (-0.0 equals +0.0).  A strict total order: the tree is unique.
+ *   2. the node: u = n + t, h_u = d_ab * 0.5; length[node(a)] = h_u - h_a, length[node(b)] = h_u - h_b; the parent of
+ *      both is u
+ *   3. u takes slot a, slot b leaves; s_u = s_a + s_b
+ *   4. for every other active slot k, d_uk (stored for both (a, k) and (k, a)):
+ *        DST_LINK_AVERAGE  (UPGMA)  ((double)s_a * d_ak + (double)s_b * d_bk) / (double)(s_a + s_b)
+ *        DST_LINK_WEIGHTED (WPGMA)  (d_ak + d_bk) * 0.5
+ *        DST_LINK_COMPLETE          d_ak < d_bk ? d_bk : d_ak
+ *
+ * Output.  Leaves are nodes 0 .. n-1, the node made in round t is n + t, the root is 2n - 2.  parent[x], length[x] (the
+ * edge from x to its parent) and height[x] (h_x; leaves +0.0) for 2n - 1 nodes; the root has parent UINT32_MAX and
+ * length 0.  height may be NULL.  cap: the room of every non-NULL array in entries, below 2n - 1 DST_ERR_CAPACITY.
+ * Lengths are kept as computed: under average and weighted linkage a rounding can make one a few ulps negative.  Complete
+ * linkage is pure selection: every value in it is an input value or half of one, and heights never decrease.
+ * row_scans: NULL, or the number of whole-row scans of the square the call made (the n that build the row-minimum
+ * cache included); a diagnostic, not part of the bit-fixed result.
+ *
+ * Errors: n < 2 or n >= 2^31, an unknown linkage or measure, a NULL ctx, parent or length: DST_ERR_ARG; a non-finite D:
+ * DST_ERR_STATE from dst_dendrogram (the message names the first pair in canonical order, as dst_nj's), DST_ERR_ARG from
+ * dst_dendrogram_matrix; slot 0 not uploaded: DST_ERR_STATE; device memory for the square (8 n^2 bytes; there is no
+ * compaction buffer): DST_ERR_NOMEM with the byte count in the message.  Synchronous on the context's stream; single
+ * GPU, loaded set only (not dst_stream).  Slots, the path choice and later results are untouched. */
+typedef enum { DST_LINK_AVERAGE = 0, DST_LINK_WEIGHTED = 1, DST_LINK_COMPLETE = 2 } dst_linkage;
+int dst_dendrogram(dst_ctx *ctx, int measure, int linkage, uint64_t max_pairs, uint32_t *parent, double *length,
+                   double *height, size_t cap, uint64_t *row_scans);
+int dst_dendrogram_matrix(dst_ctx *ctx, const double *d, uint64_t n, int linkage, uint32_t *parent, double *length,
+                          double *height, size_t cap, uint64_t *row_scans);
+/* Newick text of a dst_dendrogram tree (host only, no GPU): "(c1:l1,c2:l2);\n" with a binary root, n >= 2 leaves and
+ * 2n - 1 nodes; everything else as dst_newick (children in ascending node id, {:.12} lengths, the same quoting, *len and
+ * cap).  DST_ERR_ARG: n < 2, a NULL pointer, decreasing offsets, or a malformed parent array (an index out of range, not
+ * exactly one root, a cycle, a leaf with children, an internal node, the root included, without exactly 2 children). */
+int dst_newick_rooted(uint64_t n, const uint32_t *parent, const double *length, const char *chars,
+                      const uint64_t *offsets, char *out, size_t cap, size_t *len);
+
 /* ---- bootstrap support of neighbour-joining trees ------------------------------------------------------------------ */
 /* Replicate columns.  Replicate r (0-based) of an alignment of len sites has len columns; its column c is source column
  * col(seed, r, c), from SplitMix64 output number k = r * len + c of a generator seeded with `seed` (all mod 2^64):
