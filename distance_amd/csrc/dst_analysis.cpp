@@ -1,0 +1,788 @@
+// dst_analysis.cpp — the analyses of the C ABI that consume a set's pairs slab by slab on the device and return an O(n)
+// or O(n k) result: dst_nearest, dst_clusters, dst_mst, dst_nj (+ _matrix, _bootstrap), dst_dendrogram (+ _matrix).
+// Each one is the same program: plan the row slabs, grow the context's slab scratch, walk the slabs (the
+// pair kernel of a slab into the scratch, the analysis' kernels directly behind it), carve its O(n) state out of one
+// allocation, copy the result back.  Everything runs on the context's stream and waits before it returns.
+#include <algorithm>
+#include <cmath>
+#include <cstdio>
+#include <cstring>
+#include <string>
+#include <vector>
+
+#include "dst_ctx.h"
+
+using namespace dst;
+
+namespace dst {
+
+SlabPlan plan_slabs(bool square, uint64_t n_rows, uint64_t n_cols, uint64_t max_pairs, uint64_t default_pairs)
+{
+    SlabPlan plan;
+    plan.slabs = cut_row_slabs(square, n_rows, n_cols, max_pairs ? max_pairs : default_pairs);
+    for (const RowSlab &s : plan.slabs)
+        plan.biggest = std::max(plan.biggest, s.pairs);
+    return plan;
+}
+
+}  // namespace dst
+
+namespace {
+
+// An analysis takes the context's stream over here: whatever an earlier call queued has finished after the wait, so
+// nothing reads the grow-only buffers any more and they may be replaced.  Then the slab scratch grows to `bytes` (the
+// largest slab in the call's output kind); wanted = false: a call that will run no slab leaves it alone.
+int slab_scratch(dst_ctx *ctx, size_t bytes, bool wanted = true)
+{
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (!wanted)
+        return DST_OK;
+    return ensure_bytes(ctx, &ctx->pair_slab, &ctx->pair_slab_bytes, std::max<size_t>(bytes, 256));
+}
+
+// Every slab in order: its pairs, each once (square: the triangle), as `out_kind` into the slab scratch, then
+// consume(slab), whose launches go on the context's stream directly behind the slab's pair kernel.  Nothing waits.
+template <typename Consume>
+int walk_slabs(dst_ctx *ctx, int measure, bool square, DeviceSet &rows, DeviceSet &cols, const std::vector<RowSlab> &slabs,
+               int out_kind, Consume &&consume)
+{
+    for (const RowSlab &s : slabs) {
+        int rc = run_sets(ctx, measure, square, rows, cols, s.rb, s.re, out_kind, ctx->pair_slab, ctx->pair_slab_bytes,
+                          (void *)ctx->stream);
+        if (!rc)
+            rc = consume(s);
+        if (rc)
+            return rc;
+    }
+    return DST_OK;
+}
+
+// Pieces of one allocation, each 256-byte aligned.  A layout is written once as a function over a Carve: run on a null
+// base it only adds up `used` (every pointer null), run on the allocation it sets the pointers.
+struct Carve {
+    char *base;
+    size_t used = 0;
+    explicit Carve(void *b) : base(static_cast<char *>(b)) {}
+    template <typename T>
+    T *take(size_t count)
+    {
+        T *p = base ? reinterpret_cast<T *>(base + used) : nullptr;
+        used += (count * sizeof(T) + 255) / 256 * 256;
+        return p;
+    }
+};
+
+int not_finite(dst_ctx *ctx, int status, const std::string &prefix, uint64_t i, uint64_t j)
+{
+    return fail(ctx, status, prefix + "the distance of records " + std::to_string(i) + " and " + std::to_string(j) +
+                                 " is not finite");
+}
+
+// a caller's n x n matrix: the first non-finite entry of the upper triangle ends the call
+int matrix_finite(dst_ctx *ctx, const std::string &prefix, const double *d, uint64_t n)
+{
+    for (uint64_t i = 0; i < n; ++i)
+        for (uint64_t j = i + 1; j < n; ++j)
+            if (!std::isfinite(d[i * n + j]))
+                return not_finite(ctx, DST_ERR_ARG, prefix, i, j);
+    return DST_OK;
+}
+
+size_t nearest_layout(void *base, uint64_t entries, int W, NearestLists &nl)
+{
+    Carve c(base);
+    nl.val = c.take<uint64_t>(entries);
+    nl.idx = c.take<uint32_t>(entries);
+    nl.tal = c.take<uint32_t>(entries * (size_t)W);
+    return c.used;
+}
+
+size_t mst_layout(void *base, uint64_t n, int W, MstBuffers &b)
+{
+    Carve c(base);
+    b.comp = c.take<uint32_t>(n);
+    b.hook = c.take<uint32_t>(n);
+    b.best_key = c.take<uint64_t>(n);
+    b.best_pair = c.take<uint64_t>(n);
+    b.edges = c.take<uint64_t>(n);
+    b.edge_keys = c.take<uint64_t>(n);
+    b.val = c.take<uint64_t>(n);
+    b.tal = c.take<uint32_t>(n * (size_t)W);
+    b.counters = c.take<uint64_t>(2);
+    return c.used;
+}
+
+// The device memory of one n x n f64 square (dst_nj, dst_dendrogram and their forms): the two matrix buffers and one
+// block for the rest.  Per call, not grow-only: the square of 50,000 records is 20 GB.  Freed behind the context's
+// stream.  A dendrogram needs no compaction: setup(n, false) leaves the second matrix buffer out.
+struct SquareAlloc {
+    dst_ctx *ctx;
+    const char *what;
+    void *D0 = nullptr, *D1 = nullptr, *work = nullptr;
+    NjBuffers b{};
+    unsigned long long *bad = nullptr;
+    explicit SquareAlloc(dst_ctx *c, const char *w = "neighbour joining") : ctx(c), what(w) {}
+    ~SquareAlloc()
+    {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void *p : {D0, D1, work})
+            if (p)
+                (void)hipFree(p);
+    }
+    int alloc(void **p, size_t bytes)
+    {
+        if (hipMalloc(p, bytes) != hipSuccess) {
+            *p = nullptr;
+            (void)hipGetLastError();   // (clear the out-of-memory status: later launches check hipGetLastError)
+            return fail(ctx, DST_ERR_NOMEM, std::string(what) + ": cannot allocate " + std::to_string(bytes) +
+                                                " bytes of device memory");
+        }
+        return DST_OK;
+    }
+    size_t layout(void *base, uint64_t n)
+    {
+        const size_t nodes = 2 * n - 2;
+        Carve c(base);
+        b.r[0] = c.take<double>(n);
+        b.r[1] = c.take<double>(n);
+        b.ids[0] = c.take<uint32_t>(n);
+        b.ids[1] = c.take<uint32_t>(n);
+        b.active = c.take<uint8_t>(n);
+        b.pos = c.take<uint32_t>(n);
+        b.part_key = c.take<uint64_t>(kNjScanBlocks);
+        b.part_ij = c.take<uint64_t>(kNjScanBlocks);
+        b.parent = c.take<uint32_t>(nodes);
+        b.length = c.take<double>(nodes);
+        bad = c.take<unsigned long long>(1);
+        return c.used;
+    }
+    int setup(uint64_t n, bool compaction = true)
+    {
+        const uint64_t n1 = std::max<uint64_t>(3 * n / 4, 1);
+        int rc = alloc(&D0, n * n * 8);
+        if (!rc && compaction)
+            rc = alloc(&D1, n1 * n1 * 8);
+        if (!rc)
+            rc = alloc(&work, layout(nullptr, n));
+        if (rc)
+            return rc;
+        layout(work, n);
+        b.D[0] = static_cast<double *>(D0);
+        b.D[1] = static_cast<double *>(D1);
+        return DST_OK;
+    }
+};
+
+// the row slabs of the fill of an n-record square and the slab scratch for them
+int square_slabs(dst_ctx *ctx, int measure, uint64_t n, uint64_t max_pairs, SlabPlan &plan)
+{
+    plan = plan_slabs(true, n, n, max_pairs, kClusterSlabPairs);
+    return slab_scratch(ctx, dst_out_bytes(measure, DST_OUT_DISTANCE, plan.biggest));
+}
+
+// the square of `set` into al's first matrix buffer and the non-finite flag, queued on the context's stream without a
+// wait: the initial state, then per slab its DST_OUT_DISTANCE payloads, scattered
+int square_fill(dst_ctx *ctx, int measure, DeviceSet &set, const SlabPlan &plan, SquareAlloc &al)
+{
+    hipStream_t stream = ctx->stream;
+    const uint64_t n = set.n;
+    HIP_TRY(ctx, launch_nj_init(al.b.D[0], n, al.b.ids[0], al.b.active, al.bad, stream));
+    return walk_slabs(ctx, measure, true, set, set, plan.slabs, DST_OUT_DISTANCE, [&](const RowSlab &s) -> int {
+        HIP_TRY(ctx, launch_nj_scatter(measure, static_cast<const uint64_t *>(ctx->pair_slab), s.first, n, s.rb, s.re,
+                                       al.b.D[0], al.bad, stream));
+        return DST_OK;
+    });
+}
+
+// the message of a non-finite fill: the first pair in canonical order, from the flag's linear index i * n + j
+int square_bad_pair(dst_ctx *ctx, const std::string &prefix, unsigned long long bad, uint64_t n)
+{
+    return not_finite(ctx, DST_ERR_STATE, prefix, bad / n, bad % n);
+}
+
+// one look at the fill before the rounds: a non-finite distance ends the call
+int square_check(dst_ctx *ctx, const SquareAlloc &al, uint64_t n)
+{
+    unsigned long long bad = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&bad, al.bad, 8, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return bad == ~0ull ? DST_OK : square_bad_pair(ctx, std::string(al.what) + ": ", bad, n);
+}
+
+int nj_check_out(dst_ctx *ctx, uint64_t n, uint32_t *parent, double *length, size_t cap)
+{
+    if (!parent || !length)
+        return fail(ctx, DST_ERR_ARG, "null parent or length pointer");
+    if (n < 3)
+        return fail(ctx, DST_ERR_ARG, "neighbour joining needs at least 3 records");
+    if (n >= ((uint64_t)1 << 31))
+        return fail(ctx, DST_ERR_ARG, "neighbour joining of 2^31 records or more");
+    if (cap < 2 * n - 2)
+        return fail(ctx, DST_ERR_CAPACITY, "cap is below 2n - 2 entries");
+    return DST_OK;
+}
+
+// the rounds behind the fill on the context's stream, then one copy of the tree to the host
+int nj_finish(dst_ctx *ctx, SquareAlloc &al, uint64_t n, uint32_t *parent, double *length)
+{
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(ctx, launch_nj_rounds(al.b, n, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(parent, al.b.parent, (2 * n - 2) * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(length, al.b.length, (2 * n - 2) * 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    return DST_OK;
+}
+
+// dst_nj_bootstrap's device memory beside SquareAlloc: the original codes, the replicate's codes (both n x pitch) and
+// the column map.  Freed behind the context's stream, with the replicate's packed set.
+struct BootAlloc {
+    dst_ctx *ctx;
+    uint8_t *src = nullptr, *rep = nullptr;
+    uint32_t *map = nullptr;
+    explicit BootAlloc(dst_ctx *c) : ctx(c) {}
+    ~BootAlloc()
+    {
+        (void)hipStreamSynchronize(ctx->stream);
+        for (void *p : {(void *)src, (void *)rep, (void *)map})
+            if (p)
+                (void)hipFree(p);
+        free_set(ctx->boot);
+    }
+    int setup(uint64_t n, uint64_t pitch, uint64_t len)
+    {
+        const size_t bytes[3] = {std::max<size_t>(n * pitch, 128), std::max<size_t>(n * pitch, 128),
+                                 std::max<size_t>(len * 4, 4)};
+        void **ptrs[3] = {(void **)&src, (void **)&rep, (void **)&map};
+        for (int k = 0; k < 3; ++k)
+            if (hipMalloc(ptrs[k], bytes[k]) != hipSuccess) {
+                *ptrs[k] = nullptr;
+                (void)hipGetLastError();
+                return fail(ctx, DST_ERR_NOMEM, "bootstrap: cannot allocate " + std::to_string(bytes[k]) +
+                                                    " bytes of device memory");
+            }
+        return DST_OK;
+    }
+};
+
+int dg_check(dst_ctx *ctx, uint64_t n, int linkage, uint32_t *parent, double *length, size_t cap)
+{
+    if (linkage < DST_LINK_AVERAGE || linkage > DST_LINK_COMPLETE)
+        return fail(ctx, DST_ERR_ARG, "unknown linkage");
+    if (!parent || !length)
+        return fail(ctx, DST_ERR_ARG, "null parent or length pointer");
+    if (n < 2)
+        return fail(ctx, DST_ERR_ARG, "a dendrogram needs at least 2 records");
+    if (n >= ((uint64_t)1 << 31))
+        return fail(ctx, DST_ERR_ARG, "a dendrogram of 2^31 records or more");
+    if (n > ((uint64_t)1 << 30))   // (8 n^2 must fit 64 bits before it is asked for; 2^30 records are 2^63 bytes)
+        return fail(ctx, DST_ERR_NOMEM, "dendrogram: a square of " + std::to_string(n) + " records does not fit device memory");
+    if (cap < 2 * n - 1)
+        return fail(ctx, DST_ERR_CAPACITY, "cap is below 2n - 1 entries");
+    return DST_OK;
+}
+
+size_t dg_layout(void *base, uint64_t n, DgBuffers &b)
+{
+    const size_t nodes = 2 * n - 1, nblk = (n + kDgBlockRows - 1) / kDgBlockRows;
+    Carve c(base);
+    b.size = c.take<uint32_t>(n);
+    b.row_key = c.take<uint64_t>(n);
+    b.row_col = c.take<uint32_t>(n);
+    b.blk_key = c.take<uint64_t>(nblk);
+    b.list = c.take<uint32_t>(n);
+    b.counters = c.take<uint32_t>(12);   // one piece for the three: the scan count at +16, the round's pair at +32
+    b.parent = c.take<uint32_t>(nodes);
+    b.length = c.take<double>(nodes);
+    b.height = c.take<double>(nodes);
+    return c.used;
+}
+
+// the O(n) state of a dendrogram call in the context's grow-only scratch, beside the square (and its flags) of `al`
+int dg_buffers(dst_ctx *ctx, SquareAlloc &al, uint64_t n, DgBuffers &b)
+{
+    const size_t total = dg_layout(nullptr, n, b);
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (an earlier call's state goes before it is replaced)
+    if (int rc = ensure_bytes(ctx, &ctx->dg_work, &ctx->dg_work_bytes, total))
+        return rc;
+    dg_layout(ctx->dg_work, n, b);
+    b.scans = reinterpret_cast<unsigned long long *>(b.counters + 4);
+    b.pair = reinterpret_cast<DgPair *>(b.counters + 8);
+    b.D = al.b.D[0];
+    b.active = al.b.active;
+    b.node = al.b.ids[0];
+    return DST_OK;
+}
+
+// the rounds behind the fill on the context's stream, then one copy of the tree to the host
+int dg_finish(dst_ctx *ctx, const DgBuffers &b, uint64_t n, int linkage, uint32_t *parent, double *length, double *height,
+              uint64_t *row_scans)
+{
+    hipStream_t stream = ctx->stream;
+    unsigned long long scans = 0;
+    HIP_TRY(ctx, launch_dg_init(b, n, stream));
+    HIP_TRY(ctx, launch_dg_rounds(b, n, linkage, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(parent, b.parent, (2 * n - 1) * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(length, b.length, (2 * n - 1) * 8, hipMemcpyDeviceToHost, stream));
+    if (height)
+        HIP_TRY(ctx, hipMemcpyAsync(height, b.height, (2 * n - 1) * 8, hipMemcpyDeviceToHost, stream));
+    uint32_t failed = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(&scans, b.scans, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&failed, b.counters + 2, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (row_scans)
+        *row_scans = scans;
+    if (failed)   // (the row-minimum cache lost the pair: never a tree that is silently wrong)
+        return fail(ctx, DST_ERR_STATE, "dendrogram: internal error, round " + std::to_string(failed - 1) +
+                                            " found no active pair");
+    return DST_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, uint32_t k, uint32_t *index,
+                uint32_t *tallies, void *values, size_t cap_entries, uint32_t *k_used)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (k_used)
+        *k_used = 0;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (k < 1 || k > kNearestMaxK)
+        return fail(ctx, DST_ERR_ARG, "k must be between 1 and 256");
+    if (!index || !k_used)
+        return fail(ctx, DST_ERR_ARG, "null index or k_used pointer");
+    if (square) {
+        row_slot = 0;
+        col_slot = 0;
+    } else {
+        if (row_slot < 0 || row_slot > 1 || col_slot < 0 || col_slot > 1)
+            return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
+        if (row_slot == col_slot)
+            return fail(ctx, DST_ERR_ARG, "row_slot == col_slot: use the square form for one set");
+    }
+    DeviceSet &rows = ctx->set[row_slot], &cols = ctx->set[col_slot];
+    if (!rows.loaded || !cols.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    if (rows.len != cols.len) {
+        char msg[128];  // src/fastaio.rs:93-95
+        std::snprintf(msg, sizeof msg, "Different length sequences in alignment(s): %zu vs %zu", rows.len, cols.len);
+        return fail(ctx, DST_ERR_STATE, msg);
+    }
+    const uint64_t n_rows = rows.n, n_cols = cols.n;
+    if (n_rows >= 0xFFFFFFFFull || n_cols >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    const uint64_t candidates = square ? (n_rows > 0 ? n_rows - 1 : 0) : n_cols;
+    const uint32_t ku = (uint32_t)std::min<uint64_t>(k, candidates);
+    if (n_rows * ku > cap_entries)
+        return fail(ctx, DST_ERR_CAPACITY, "cap_entries is below n_rows x k_used");
+    if (ku == 0 || n_rows == 0) {
+        *k_used = ku;
+        return DST_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    int rc = DST_OK;
+    if (measure == DST_TN93) {
+        rc = need_counts(ctx, rows, stream);
+        if (!rc && &cols != &rows)
+            rc = need_counts(ctx, cols, stream);
+        if (rc)
+            return rc;
+    }
+    const SlabPlan plan = plan_slabs(square != 0, n_rows, n_cols, 0, kNearestSlabPairs);
+    const uint64_t entries = n_rows * ku;
+    const int W = tally_width(measure);
+    NearestLists nl{};
+    rc = slab_scratch(ctx, dst_out_bytes(measure, DST_OUT_TALLY, plan.biggest));
+    if (!rc)
+        rc = ensure_bytes(ctx, &ctx->nn_lists, &ctx->nn_lists_bytes, nearest_layout(nullptr, entries, W, nl));
+    if (rc)
+        return rc;
+    nearest_layout(ctx->nn_lists, entries, W, nl);
+    nl.k = ku;
+    HIP_TRY(ctx, launch_nearest_init(nl, n_rows, stream));
+    const uint32_t *slab = static_cast<const uint32_t *>(ctx->pair_slab);
+    // the slab's exact tallies, then both passes behind its pair kernel: they touch the same lists
+    rc = walk_slabs(ctx, measure, square != 0, rows, cols, plan.slabs, DST_OUT_TALLY, [&](const RowSlab &s) -> int {
+        HIP_TRY(ctx, launch_nearest_rows(measure, square != 0, slab, s.first, n_cols, s.rb, s.re, rows.counts, cols.counts,
+                                         nl, stream));
+        if (square)
+            HIP_TRY(ctx, launch_nearest_cols(measure, slab, s.first, n_cols, s.rb, s.re, cols.counts, nl, stream));
+        return DST_OK;
+    });
+    if (rc)
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(index, nl.idx, entries * 4, hipMemcpyDeviceToHost, stream));
+    if (values)
+        HIP_TRY(ctx, hipMemcpyAsync(values, nl.val, entries * 8, hipMemcpyDeviceToHost, stream));
+    if (tallies)
+        HIP_TRY(ctx, hipMemcpyAsync(tallies, nl.tal, entries * W * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    *k_used = ku;
+    return DST_OK;
+}
+
+int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs, uint32_t *label, size_t cap,
+                 uint64_t *n_clusters, uint64_t *links)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (n_clusters)
+        *n_clusters = 0;
+    if (links)
+        *links = 0;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (std::isnan(threshold))
+        return fail(ctx, DST_ERR_ARG, "threshold is NaN");
+    if (!label)
+        return fail(ctx, DST_ERR_ARG, "null label pointer");
+    DeviceSet &set = ctx->set[0];
+    if (!set.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    const uint64_t n = set.n;
+    if (n >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    if (cap < n)
+        return fail(ctx, DST_ERR_CAPACITY, "cap is below the set's record count");
+    // the threshold as a payload: int64 payloads link when v <= floor(T) (clamped to the int64 range); below -2^63
+    // nothing links
+    uint64_t t_bits;
+    bool any = true;
+    if (measure_is_int(measure)) {
+        const double f = std::floor(threshold);
+        int64_t t;
+        if (f >= 9223372036854775808.0)
+            t = INT64_MAX;
+        else if (f < -9223372036854775808.0) {
+            t = INT64_MIN;
+            any = false;
+        } else
+            t = (int64_t)f;
+        t_bits = (uint64_t)t;
+    } else {
+        std::memcpy(&t_bits, &threshold, 8);
+    }
+    if (n < 2) {
+        if (n == 1)
+            label[0] = 0;
+        if (n_clusters)
+            *n_clusters = n;
+        return DST_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    SlabPlan plan = plan_slabs(true, n, n, max_pairs, kClusterSlabPairs);
+    if (!any)
+        plan.slabs.clear();   // (nothing can link: no slab is run, and no scratch is kept for one)
+    uint32_t *parent = nullptr;
+    unsigned long long *d_links = nullptr;
+    auto layout = [&](void *base) {   // the parent array and the link counter
+        Carve c(base);
+        parent = c.take<uint32_t>(n);
+        d_links = c.take<unsigned long long>(1);
+        return c.used;
+    };
+    int rc = slab_scratch(ctx, dst_out_bytes(measure, DST_OUT_DISTANCE, plan.biggest), any);
+    if (!rc)
+        rc = ensure_bytes(ctx, &ctx->cl_work, &ctx->cl_work_bytes, layout(nullptr));
+    if (rc)
+        return rc;
+    layout(ctx->cl_work);
+    HIP_TRY(ctx, launch_clusters_init(parent, n, d_links, stream));
+    // the slab's DST_OUT_DISTANCE payloads, then its unions behind the pair kernel (and the previous slab's unions)
+    rc = walk_slabs(ctx, measure, true, set, set, plan.slabs, DST_OUT_DISTANCE, [&](const RowSlab &s) -> int {
+        HIP_TRY(ctx, launch_clusters_link(measure, static_cast<const uint64_t *>(ctx->pair_slab), s.first, n, s.rb, s.re, t_bits,
+                                          parent, d_links, stream));
+        return DST_OK;
+    });
+    if (rc)
+        return rc;
+    HIP_TRY(ctx, launch_clusters_final(parent, n, stream));
+    uint64_t h_links = 0;
+    HIP_TRY(ctx, hipMemcpyAsync(label, parent, n * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(&h_links, d_links, 8, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    uint64_t roots = 0;
+    for (uint64_t i = 0; i < n; ++i)
+        roots += label[i] == i;
+    if (n_clusters)
+        *n_clusters = roots;
+    if (links)
+        *links = h_links;
+    return DST_OK;
+}
+
+int dst_mst(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *edge_i, uint32_t *edge_j, void *values,
+            uint32_t *tallies, size_t cap, uint64_t *n_edges, uint32_t *rounds)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (n_edges)
+        *n_edges = 0;
+    if (rounds)
+        *rounds = 0;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (!edge_i || !edge_j)
+        return fail(ctx, DST_ERR_ARG, "null edge_i or edge_j pointer");
+    DeviceSet &set = ctx->set[0];
+    if (!set.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    const uint64_t n = set.n;
+    if (n >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    if (n < 2)
+        return DST_OK;
+    if (cap < n - 1)
+        return fail(ctx, DST_ERR_CAPACITY, "cap is below n - 1 entries");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const bool finish = values || tallies;
+    const int W = tally_width(measure);
+    int rc = DST_OK;
+    if (finish && measure == DST_TN93) {
+        rc = need_counts(ctx, set, stream);
+        if (rc)
+            return rc;
+    }
+    const SlabPlan plan = plan_slabs(true, n, n, max_pairs, kClusterSlabPairs);
+    MstBuffers b{};
+    // the scratch holds a slab of payloads in the rounds and, for the finish, the same slab as tallies
+    rc = slab_scratch(ctx, std::max(dst_out_bytes(measure, DST_OUT_DISTANCE, plan.biggest),
+                                    finish ? dst_out_bytes(measure, DST_OUT_TALLY, plan.biggest) : (size_t)0));
+    if (!rc)
+        rc = ensure_bytes(ctx, &ctx->mst_work, &ctx->mst_work_bytes, mst_layout(nullptr, n, W, b));
+    if (rc)
+        return rc;
+    mst_layout(ctx->mst_work, n, W, b);
+    // Boruvka rounds: a round that emits nothing ends the call (the forest of a graph that is not connected); n - 1
+    // edges end it without that last sweep.  Every round at least halves the components that still have an edge out.
+    uint64_t h_count[2] = {0, 0};
+    uint32_t n_rounds = 0;
+    for (bool first = true;; first = false) {
+        if (n_rounds > 64)
+            return fail(ctx, DST_ERR_STATE, "minimum spanning tree: more rounds than any set can need");
+        HIP_TRY(ctx, launch_mst_reset(b, n, first, stream));
+        // the slab's DST_OUT_DISTANCE payloads, the two scan launches behind it
+        rc = walk_slabs(ctx, measure, true, set, set, plan.slabs, DST_OUT_DISTANCE, [&](const RowSlab &s) -> int {
+            HIP_TRY(ctx, launch_mst_scan(measure, static_cast<const uint64_t *>(ctx->pair_slab), s.first, n, s.rb, s.re, b, stream));
+            return DST_OK;
+        });
+        if (rc)
+            return rc;
+        HIP_TRY(ctx, launch_mst_hook(b, n, stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_count, b.counters, 16, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+        if (h_count[1] == 0)
+            break;
+        ++n_rounds;
+        if (h_count[0] >= n - 1)
+            break;
+    }
+    const uint64_t ne = h_count[0];
+    if (ne > n - 1)
+        return fail(ctx, DST_ERR_STATE, "minimum spanning tree: more than n - 1 edges");
+    if (finish && ne) {
+        rc = walk_slabs(ctx, measure, true, set, set, plan.slabs, DST_OUT_TALLY, [&](const RowSlab &s) -> int {
+            HIP_TRY(ctx, launch_mst_gather(measure, static_cast<const uint32_t *>(ctx->pair_slab), s.first, n, s.rb, s.re,
+                                           set.counts, b, ne, stream));
+            return DST_OK;
+        });
+        if (rc)
+            return rc;
+    }
+    // the edges back once, sorted here by (key, i, j)
+    std::vector<uint64_t> h_edges(ne), h_keys(ne), h_val(finish ? ne : 0);
+    std::vector<uint32_t> h_tal(tallies ? ne * W : 0), order(ne);
+    if (ne) {
+        HIP_TRY(ctx, hipMemcpyAsync(h_edges.data(), b.edges, ne * 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_keys.data(), b.edge_keys, ne * 8, hipMemcpyDeviceToHost, stream));
+        if (finish)
+            HIP_TRY(ctx, hipMemcpyAsync(h_val.data(), b.val, ne * 8, hipMemcpyDeviceToHost, stream));
+        if (tallies)
+            HIP_TRY(ctx, hipMemcpyAsync(h_tal.data(), b.tal, ne * W * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+    }
+    for (uint64_t e = 0; e < ne; ++e)
+        order[e] = (uint32_t)e;
+    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
+        return h_keys[x] != h_keys[y] ? h_keys[x] < h_keys[y] : h_edges[x] < h_edges[y];
+    });
+    for (uint64_t e = 0; e < ne; ++e) {
+        const uint32_t src = order[e];
+        edge_i[e] = (uint32_t)(h_edges[src] >> 32);
+        edge_j[e] = (uint32_t)h_edges[src];
+        if (values)
+            static_cast<uint64_t *>(values)[e] = h_val[src];
+        if (tallies)
+            std::memcpy(tallies + e * W, h_tal.data() + (size_t)src * W, (size_t)W * 4);
+    }
+    if (n_edges)
+        *n_edges = ne;
+    if (rounds)
+        *rounds = n_rounds;
+    return DST_OK;
+}
+
+int dst_nj(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *parent, double *length, size_t cap)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    DeviceSet &set = ctx->set[0];
+    if (!set.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    const uint64_t n = set.n;
+    if (int rc = nj_check_out(ctx, n, parent, length, cap))
+        return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    SlabPlan plan;
+    int rc = square_slabs(ctx, measure, n, max_pairs, plan);
+    if (rc)
+        return rc;
+    SquareAlloc al(ctx);
+    if ((rc = al.setup(n)) || (rc = square_fill(ctx, measure, set, plan, al)) || (rc = square_check(ctx, al, n)))
+        return rc;
+    return nj_finish(ctx, al, n, parent, length);
+}
+
+int dst_nj_bootstrap(dst_ctx *ctx, int measure, const uint8_t *codes, size_t n, size_t len, size_t row_stride,
+                     uint32_t replicates, uint64_t seed, uint64_t max_pairs, const uint32_t *parent, uint32_t *support,
+                     uint32_t *rep_parent, size_t cap)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (!parent || !support)
+        return fail(ctx, DST_ERR_ARG, "null parent or support pointer");
+    if ((len && !codes) || row_stride < len)
+        return fail(ctx, DST_ERR_ARG, "null codes or row_stride < len");
+    if (n < 3)
+        return fail(ctx, DST_ERR_ARG, "neighbour joining needs at least 3 records");
+    if (n >= ((uint64_t)1 << 31) || len >= 0xFFFFFF00ull)
+        return fail(ctx, DST_ERR_ARG, "bootstrap: n must be below 2^31 and len must fit 32 bits");
+    if (replicates < 1 || replicates > 10000)
+        return fail(ctx, DST_ERR_ARG, "bootstrap: replicates must be in 1..=10000");
+    const uint64_t N = 2 * n - 2;
+    if (cap < N)
+        return fail(ctx, DST_ERR_CAPACITY, "cap is below 2n - 2 entries");
+    SplitCounter splits;
+    if (!splits.init(n, parent))
+        return fail(ctx, DST_ERR_ARG, "bootstrap: the main tree is not a dst_nj tree on n leaves");
+    std::vector<uint32_t> count(N, 0), rp(N);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    SlabPlan plan;
+    int rc = square_slabs(ctx, measure, n, max_pairs, plan);
+    if (rc)
+        return rc;
+    const uint64_t pitch = std::max<uint64_t>((len + 127) / 128 * 128, 128);
+    SquareAlloc al(ctx);   // (destroyed after `boot`: the replicate set is freed first, then the square)
+    BootAlloc boot(ctx);
+    if ((rc = boot.setup(n, pitch, len)) || (rc = al.setup(n)))
+        return rc;
+    if (len)
+        HIP_TRY(ctx, hipMemcpy2DAsync(boot.src, pitch, codes, row_stride, len, n, hipMemcpyHostToDevice, stream));
+    // the original once through the pack: every byte is checked, as dst_upload checks it (a replicate draws a subset)
+    if ((rc = pack_set(ctx, ctx->boot, boot.src, n, len, pitch, nullptr, stream)))
+        return rc;
+    for (uint32_t r = 0; r < replicates; ++r) {
+        HIP_TRY(ctx, launch_boot_resample(boot.src, pitch, boot.rep, n, len, seed, r, boot.map, stream));
+        // tn93: no counts passed, so the pair kernels count the replicate's bases by code (need_counts)
+        if ((rc = pack_set(ctx, ctx->boot, boot.rep, n, len, pitch, nullptr, stream)))
+            return rc;
+        if ((rc = square_fill(ctx, measure, ctx->boot, plan, al)))
+            return rc;
+        // the rounds run whatever the flag says (their indices stay in range on non-finite values), so the flag comes
+        // back with the tree instead of through square_check: one wait per tree
+        unsigned long long bad = 0;
+        uint32_t *dst = rep_parent ? rep_parent + (uint64_t)r * N : rp.data();
+        HIP_TRY(ctx, launch_nj_rounds(al.b, n, stream));
+        HIP_TRY(ctx, hipMemcpyAsync(dst, al.b.parent, N * 4, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipMemcpyAsync(&bad, al.bad, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+        if (bad != ~0ull)
+            return square_bad_pair(ctx, "bootstrap replicate " + std::to_string(r) + ": ", bad, n);
+        if (!splits.count(dst, count.data()))
+            return fail(ctx, DST_ERR_STATE, "bootstrap replicate " + std::to_string(r) + ": malformed replicate tree");
+    }
+    for (uint64_t x = 0; x < N; ++x)
+        support[x] = x < n || parent[x] == 0xFFFFFFFFu ? 0xFFFFFFFFu : count[x];
+    return DST_OK;
+}
+
+int dst_nj_matrix(dst_ctx *ctx, const double *d, uint64_t n, uint32_t *parent, double *length, size_t cap)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (!d)
+        return fail(ctx, DST_ERR_ARG, "null matrix pointer");
+    int rc;
+    if ((rc = nj_check_out(ctx, n, parent, length, cap)) || (rc = matrix_finite(ctx, "neighbour joining: ", d, n)))
+        return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    SquareAlloc al(ctx);
+    if ((rc = al.setup(n)))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(al.b.D[0], d, n * n * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, launch_nj_init(al.b.D[0], n, al.b.ids[0], al.b.active, al.bad, stream));
+    HIP_TRY(ctx, launch_nj_mirror(al.b.D[0], n, stream));
+    return nj_finish(ctx, al, n, parent, length);
+}
+
+int dst_dendrogram(dst_ctx *ctx, int measure, int linkage, uint64_t max_pairs, uint32_t *parent, double *length,
+                   double *height, size_t cap, uint64_t *row_scans)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    DeviceSet &set = ctx->set[0];
+    if (!set.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    const uint64_t n = set.n;
+    if (int rc = dg_check(ctx, n, linkage, parent, length, cap))
+        return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    SlabPlan plan;
+    int rc = square_slabs(ctx, measure, n, max_pairs, plan);
+    if (rc)
+        return rc;
+    SquareAlloc al(ctx, "dendrogram");
+    DgBuffers b{};
+    if ((rc = al.setup(n, false)) || (rc = dg_buffers(ctx, al, n, b)) || (rc = square_fill(ctx, measure, set, plan, al)) ||
+        (rc = square_check(ctx, al, n)))
+        return rc;
+    return dg_finish(ctx, b, n, linkage, parent, length, height, row_scans);
+}
+
+int dst_dendrogram_matrix(dst_ctx *ctx, const double *d, uint64_t n, int linkage, uint32_t *parent, double *length,
+                          double *height, size_t cap, uint64_t *row_scans)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (!d)
+        return fail(ctx, DST_ERR_ARG, "null matrix pointer");
+    int rc;
+    if ((rc = dg_check(ctx, n, linkage, parent, length, cap)) || (rc = matrix_finite(ctx, "dendrogram: ", d, n)))
+        return rc;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    SquareAlloc al(ctx, "dendrogram");
+    DgBuffers b{};
+    if ((rc = al.setup(n, false)) || (rc = dg_buffers(ctx, al, n, b)))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(b.D, d, n * n * 8, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, launch_nj_init(b.D, n, b.node, b.active, al.bad, stream));
+    HIP_TRY(ctx, launch_nj_mirror(b.D, n, stream));
+    return dg_finish(ctx, b, n, linkage, parent, length, height, row_scans);
+}
+
+}  // extern "C"

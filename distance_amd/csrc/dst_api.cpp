@@ -249,17 +249,12 @@ int invalid_code_error(dst_ctx *ctx, unsigned long long first_bad, size_t len)
 
 bool consensus_shape_ok(const DeviceSet &rows, const DeviceSet &cols);
 
-int pack_set(dst_ctx *ctx, DeviceSet &s, const uint8_t *d_codes, size_t n, size_t len, size_t row_stride,
-             const uint32_t *d_counts, hipStream_t stream);
-
 int pack_from_device(dst_ctx *ctx, int slot, const uint8_t *d_codes, size_t n, size_t len,
                      size_t row_stride, const uint32_t *d_counts, hipStream_t stream)
 {
     return pack_set(ctx, ctx->set[slot], d_codes, n, len, row_stride, d_counts, stream);
 }
 
-// the upload of device bytes into any set of the context (a slot, or dst_nj_bootstrap's replicate): the pack, the
-// report and its one synchronisation
 int pack_set(dst_ctx *ctx, DeviceSet &s, const uint8_t *d_codes, size_t n, size_t len, size_t row_stride,
              const uint32_t *d_counts, hipStream_t stream)
 {
@@ -1280,8 +1275,8 @@ int dst_destroy(dst_ctx *ctx)
                 (void)hipFree(b);
     for (void *b : {(void *)ctx->d_lut, (void *)ctx->d_total, (void *)ctx->scan_tmp, ctx->host_out, ctx->hot_tally, ctx->text_res,
                     ctx->text_num, (void *)ctx->text_len, (void *)ctx->text_scan, (void *)ctx->text_buf, (void *)ctx->text_flag, ctx->text_ties,
-                    (void *)ctx->ids[0].off, (void *)ctx->ids[0].chars, (void *)ctx->ids[1].off, (void *)ctx->ids[1].chars, ctx->nn_slab, ctx->nn_lists,
-                    ctx->cl_slab, ctx->cl_work, ctx->mst_work, ctx->dg_work})
+                    (void *)ctx->ids[0].off, (void *)ctx->ids[0].chars, (void *)ctx->ids[1].off, (void *)ctx->ids[1].chars, ctx->pair_slab, ctx->nn_lists,
+                    ctx->cl_work, ctx->mst_work, ctx->dg_work})
         if (b)
             (void)hipFree(b);
     if (ctx->scratch)
@@ -1737,13 +1732,11 @@ int dst_run_slabs(dst_ctx *ctx, int measure, int square, int row_slot, int col_s
     const uint64_t n_rows = ctx->set[row_slot].n, n_cols = ctx->set[col_slot].n;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // two device + two pinned host buffers sized for the largest slab
-    const std::vector<RowSlab> slabs = cut_row_slabs(square != 0, n_rows, n_cols, max_pairs);
-    uint64_t biggest = 0;
-    for (const RowSlab &s : slabs)
-        biggest = std::max(biggest, s.pairs);
+    const SlabPlan plan = plan_slabs(square != 0, n_rows, n_cols, max_pairs, max_pairs);
+    const std::vector<RowSlab> &slabs = plan.slabs;
     if (slabs.empty())
         return DST_OK;
-    const size_t bytes = dst_out_bytes(measure, out_kind, biggest);
+    const size_t bytes = dst_out_bytes(measure, out_kind, plan.biggest);
     void *d_buf[2] = {nullptr, nullptr}, *h_buf[2] = {nullptr, nullptr};
     hipEvent_t done[2] = {nullptr, nullptr};
     int rc = DST_OK;
@@ -1797,735 +1790,6 @@ int dst_run_slabs(dst_ctx *ctx, int measure, int square, int row_slot, int col_s
 #undef SLAB_TRY
     cleanup();
     return rc;
-}
-
-int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, uint32_t k, uint32_t *index,
-                uint32_t *tallies, void *values, size_t cap_entries, uint32_t *k_used)
-{
-    if (!ctx)
-        return DST_ERR_ARG;
-    if (k_used)
-        *k_used = 0;
-    if (measure < DST_N || measure > DST_TN93)
-        return fail(ctx, DST_ERR_ARG, "unknown measure");
-    if (k < 1 || k > kNearestMaxK)
-        return fail(ctx, DST_ERR_ARG, "k must be between 1 and 256");
-    if (!index || !k_used)
-        return fail(ctx, DST_ERR_ARG, "null index or k_used pointer");
-    if (square) {
-        row_slot = 0;
-        col_slot = 0;
-    } else {
-        if (row_slot < 0 || row_slot > 1 || col_slot < 0 || col_slot > 1)
-            return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
-        if (row_slot == col_slot)
-            return fail(ctx, DST_ERR_ARG, "row_slot == col_slot: use the square form for one set");
-    }
-    DeviceSet &rows = ctx->set[row_slot], &cols = ctx->set[col_slot];
-    if (!rows.loaded || !cols.loaded)
-        return fail(ctx, DST_ERR_STATE, "set not uploaded");
-    if (rows.len != cols.len) {
-        char msg[128];  // src/fastaio.rs:93-95
-        std::snprintf(msg, sizeof msg, "Different length sequences in alignment(s): %zu vs %zu", rows.len, cols.len);
-        return fail(ctx, DST_ERR_STATE, msg);
-    }
-    const uint64_t n_rows = rows.n, n_cols = cols.n;
-    if (n_rows >= 0xFFFFFFFFull || n_cols >= 0xFFFFFFFFull)
-        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
-    const uint64_t candidates = square ? (n_rows > 0 ? n_rows - 1 : 0) : n_cols;
-    const uint32_t ku = (uint32_t)std::min<uint64_t>(k, candidates);
-    if (n_rows * ku > cap_entries)
-        return fail(ctx, DST_ERR_CAPACITY, "cap_entries is below n_rows x k_used");
-    if (ku == 0 || n_rows == 0) {
-        *k_used = ku;
-        return DST_OK;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t stream = ctx->stream;
-    const int W = tally_width(measure);
-    int rc = DST_OK;
-    if (measure == DST_TN93) {
-        rc = need_counts(ctx, rows, stream);
-        if (!rc && &cols != &rows)
-            rc = need_counts(ctx, cols, stream);
-        if (rc)
-            return rc;
-    }
-    const std::vector<RowSlab> slabs = cut_row_slabs(square != 0, n_rows, n_cols, kNearestSlabPairs);
-    uint64_t biggest = 0;
-    for (const RowSlab &s : slabs)
-        biggest = std::max(biggest, s.pairs);
-    const size_t slab_bytes = dst_out_bytes(measure, DST_OUT_TALLY, biggest);
-    const uint64_t entries = n_rows * ku;
-    const size_t val_bytes = entries * 8, idx_bytes = (entries * 4 + 255) / 256 * 256, tal_bytes = entries * W * 4;
-    HIP_TRY(ctx, hipStreamSynchronize(stream));   // (the grow-only buffers of an earlier call: nothing reads them now)
-    rc = ensure_bytes(ctx, &ctx->nn_slab, &ctx->nn_slab_bytes, std::max<size_t>(slab_bytes, 256));
-    if (!rc)
-        rc = ensure_bytes(ctx, &ctx->nn_lists, &ctx->nn_lists_bytes, val_bytes + idx_bytes + tal_bytes);
-    if (rc)
-        return rc;
-    NearestLists nl{};
-    nl.val = static_cast<uint64_t *>(ctx->nn_lists);
-    nl.idx = reinterpret_cast<uint32_t *>(static_cast<char *>(ctx->nn_lists) + val_bytes);
-    nl.tal = reinterpret_cast<uint32_t *>(static_cast<char *>(ctx->nn_lists) + val_bytes + idx_bytes);
-    nl.k = ku;
-    HIP_TRY(ctx, launch_nearest_init(nl, n_rows, stream));
-    const uint32_t *slab = static_cast<const uint32_t *>(ctx->nn_slab);
-    for (const RowSlab &s : slabs) {
-        // the pairs of the slab, each once (square: the triangle), as exact tallies
-        rc = run_sets(ctx, measure, square != 0, rows, cols, s.rb, s.re, DST_OUT_TALLY, ctx->nn_slab, ctx->nn_slab_bytes,
-                      (void *)stream);
-        if (rc)
-            return rc;
-        // both passes on the context's stream, behind the slab's pair kernel: they touch the same lists
-        HIP_TRY(ctx, launch_nearest_rows(measure, square != 0, slab, s.first, n_cols, s.rb, s.re, rows.counts, cols.counts,
-                                         nl, stream));
-        if (square)
-            HIP_TRY(ctx, launch_nearest_cols(measure, slab, s.first, n_cols, s.rb, s.re, cols.counts, nl, stream));
-    }
-    HIP_TRY(ctx, hipMemcpyAsync(index, nl.idx, entries * 4, hipMemcpyDeviceToHost, stream));
-    if (values)
-        HIP_TRY(ctx, hipMemcpyAsync(values, nl.val, val_bytes, hipMemcpyDeviceToHost, stream));
-    if (tallies)
-        HIP_TRY(ctx, hipMemcpyAsync(tallies, nl.tal, tal_bytes, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    *k_used = ku;
-    return DST_OK;
-}
-
-int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs, uint32_t *label, size_t cap,
-                 uint64_t *n_clusters, uint64_t *links)
-{
-    if (!ctx)
-        return DST_ERR_ARG;
-    if (n_clusters)
-        *n_clusters = 0;
-    if (links)
-        *links = 0;
-    if (measure < DST_N || measure > DST_TN93)
-        return fail(ctx, DST_ERR_ARG, "unknown measure");
-    if (std::isnan(threshold))
-        return fail(ctx, DST_ERR_ARG, "threshold is NaN");
-    if (!label)
-        return fail(ctx, DST_ERR_ARG, "null label pointer");
-    DeviceSet &set = ctx->set[0];
-    if (!set.loaded)
-        return fail(ctx, DST_ERR_STATE, "set not uploaded");
-    const uint64_t n = set.n;
-    if (n >= 0xFFFFFFFFull)
-        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
-    if (cap < n)
-        return fail(ctx, DST_ERR_CAPACITY, "cap is below the set's record count");
-    // the threshold as a payload: int64 payloads link when v <= floor(T) (clamped to the int64 range); below -2^63
-    // nothing links
-    uint64_t t_bits;
-    bool any = true;
-    if (measure_is_int(measure)) {
-        const double f = std::floor(threshold);
-        int64_t t;
-        if (f >= 9223372036854775808.0)
-            t = INT64_MAX;
-        else if (f < -9223372036854775808.0) {
-            t = INT64_MIN;
-            any = false;
-        } else
-            t = (int64_t)f;
-        t_bits = (uint64_t)t;
-    } else {
-        std::memcpy(&t_bits, &threshold, 8);
-    }
-    if (n < 2) {
-        if (n == 1)
-            label[0] = 0;
-        if (n_clusters)
-            *n_clusters = n;
-        return DST_OK;
-    }
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t stream = ctx->stream;
-    const std::vector<RowSlab> slabs = cut_row_slabs(true, n, n, max_pairs ? max_pairs : kClusterSlabPairs);
-    uint64_t biggest = 0;
-    for (const RowSlab &s : slabs)
-        biggest = std::max(biggest, s.pairs);
-    const size_t parent_bytes = (n * 4 + 255) / 256 * 256;
-    HIP_TRY(ctx, hipStreamSynchronize(stream));   // (the grow-only buffers of an earlier call: nothing reads them now)
-    int rc = DST_OK;
-    if (any)
-        rc = ensure_bytes(ctx, &ctx->cl_slab, &ctx->cl_slab_bytes, std::max<size_t>(dst_out_bytes(measure, DST_OUT_DISTANCE, biggest), 256));
-    if (!rc)
-        rc = ensure_bytes(ctx, &ctx->cl_work, &ctx->cl_work_bytes, parent_bytes + 8);
-    if (rc)
-        return rc;
-    uint32_t *parent = static_cast<uint32_t *>(ctx->cl_work);
-    unsigned long long *d_links = reinterpret_cast<unsigned long long *>(static_cast<char *>(ctx->cl_work) + parent_bytes);
-    HIP_TRY(ctx, launch_clusters_init(parent, n, d_links, stream));
-    for (size_t k = 0; any && k < slabs.size(); ++k) {
-        const RowSlab &s = slabs[k];
-        // the slab's pairs, each once (the triangle), as DST_OUT_DISTANCE payloads
-        rc = run_sets(ctx, measure, true, set, set, s.rb, s.re, DST_OUT_DISTANCE, ctx->cl_slab, ctx->cl_slab_bytes,
-                      (void *)stream);
-        if (rc)
-            return rc;
-        // on the context's stream, behind the slab's pair kernel (and the previous slab's unions)
-        HIP_TRY(ctx, launch_clusters_link(measure, static_cast<const uint64_t *>(ctx->cl_slab), s.first, n, s.rb, s.re, t_bits,
-                                          parent, d_links, stream));
-    }
-    HIP_TRY(ctx, launch_clusters_final(parent, n, stream));
-    uint64_t h_links = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(label, parent, n * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&h_links, d_links, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    uint64_t roots = 0;
-    for (uint64_t i = 0; i < n; ++i)
-        roots += label[i] == i;
-    if (n_clusters)
-        *n_clusters = roots;
-    if (links)
-        *links = h_links;
-    return DST_OK;
-}
-
-int dst_mst(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *edge_i, uint32_t *edge_j, void *values,
-            uint32_t *tallies, size_t cap, uint64_t *n_edges, uint32_t *rounds)
-{
-    if (!ctx)
-        return DST_ERR_ARG;
-    if (n_edges)
-        *n_edges = 0;
-    if (rounds)
-        *rounds = 0;
-    if (measure < DST_N || measure > DST_TN93)
-        return fail(ctx, DST_ERR_ARG, "unknown measure");
-    if (!edge_i || !edge_j)
-        return fail(ctx, DST_ERR_ARG, "null edge_i or edge_j pointer");
-    DeviceSet &set = ctx->set[0];
-    if (!set.loaded)
-        return fail(ctx, DST_ERR_STATE, "set not uploaded");
-    const uint64_t n = set.n;
-    if (n >= 0xFFFFFFFFull)
-        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
-    if (n < 2)
-        return DST_OK;
-    if (cap < n - 1)
-        return fail(ctx, DST_ERR_CAPACITY, "cap is below n - 1 entries");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t stream = ctx->stream;
-    const bool finish = values || tallies;
-    const int W = tally_width(measure);
-    int rc = DST_OK;
-    if (finish && measure == DST_TN93) {
-        rc = need_counts(ctx, set, stream);
-        if (rc)
-            return rc;
-    }
-    const std::vector<RowSlab> slabs = cut_row_slabs(true, n, n, max_pairs ? max_pairs : kClusterSlabPairs);
-    uint64_t biggest = 0;
-    for (const RowSlab &s : slabs)
-        biggest = std::max(biggest, s.pairs);
-    const size_t slab_bytes = std::max(dst_out_bytes(measure, DST_OUT_DISTANCE, biggest),
-                                       finish ? dst_out_bytes(measure, DST_OUT_TALLY, biggest) : (size_t)0);
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t o_hook = up(n * 4), o_key = o_hook + up(n * 4), o_pair = o_key + up(n * 8), o_edges = o_pair + up(n * 8),
-                 o_ekeys = o_edges + up(n * 8), o_val = o_ekeys + up(n * 8), o_tal = o_val + up(n * 8),
-                 o_count = o_tal + up(n * (size_t)W * 4), total = o_count + 256;
-    HIP_TRY(ctx, hipStreamSynchronize(stream));   // (the grow-only buffers of an earlier call: nothing reads them now)
-    rc = ensure_bytes(ctx, &ctx->cl_slab, &ctx->cl_slab_bytes, std::max<size_t>(slab_bytes, 256));
-    if (!rc)
-        rc = ensure_bytes(ctx, &ctx->mst_work, &ctx->mst_work_bytes, total);
-    if (rc)
-        return rc;
-    char *w = static_cast<char *>(ctx->mst_work);
-    MstBuffers b{};
-    b.comp = reinterpret_cast<uint32_t *>(w);
-    b.hook = reinterpret_cast<uint32_t *>(w + o_hook);
-    b.best_key = reinterpret_cast<uint64_t *>(w + o_key);
-    b.best_pair = reinterpret_cast<uint64_t *>(w + o_pair);
-    b.edges = reinterpret_cast<uint64_t *>(w + o_edges);
-    b.edge_keys = reinterpret_cast<uint64_t *>(w + o_ekeys);
-    b.val = reinterpret_cast<uint64_t *>(w + o_val);
-    b.tal = reinterpret_cast<uint32_t *>(w + o_tal);
-    b.counters = reinterpret_cast<uint64_t *>(w + o_count);
-    // Boruvka rounds: a round that emits nothing ends the call (the forest of a graph that is not connected); n - 1
-    // edges end it without that last sweep.  Every round at least halves the components that still have an edge out.
-    uint64_t h_count[2] = {0, 0};
-    uint32_t n_rounds = 0;
-    for (bool first = true;; first = false) {
-        if (n_rounds > 64)
-            return fail(ctx, DST_ERR_STATE, "minimum spanning tree: more rounds than any set can need");
-        HIP_TRY(ctx, launch_mst_reset(b, n, first, stream));
-        for (const RowSlab &s : slabs) {
-            // the slab's pairs, each once (the triangle), as DST_OUT_DISTANCE payloads; the two scan launches behind it
-            rc = run_sets(ctx, measure, true, set, set, s.rb, s.re, DST_OUT_DISTANCE, ctx->cl_slab, ctx->cl_slab_bytes,
-                          (void *)stream);
-            if (rc)
-                return rc;
-            HIP_TRY(ctx, launch_mst_scan(measure, static_cast<const uint64_t *>(ctx->cl_slab), s.first, n, s.rb, s.re, b, stream));
-        }
-        HIP_TRY(ctx, launch_mst_hook(b, n, stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_count, b.counters, 16, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(ctx, hipStreamSynchronize(stream));
-        if (h_count[1] == 0)
-            break;
-        ++n_rounds;
-        if (h_count[0] >= n - 1)
-            break;
-    }
-    const uint64_t ne = h_count[0];
-    if (ne > n - 1)
-        return fail(ctx, DST_ERR_STATE, "minimum spanning tree: more than n - 1 edges");
-    if (finish && ne)
-        for (const RowSlab &s : slabs) {
-            rc = run_sets(ctx, measure, true, set, set, s.rb, s.re, DST_OUT_TALLY, ctx->cl_slab, ctx->cl_slab_bytes, (void *)stream);
-            if (rc)
-                return rc;
-            HIP_TRY(ctx, launch_mst_gather(measure, static_cast<const uint32_t *>(ctx->cl_slab), s.first, n, s.rb, s.re, set.counts, b,
-                                           ne, stream));
-        }
-    // the edges back once, sorted here by (key, i, j)
-    std::vector<uint64_t> h_edges(ne), h_keys(ne), h_val(finish ? ne : 0);
-    std::vector<uint32_t> h_tal(tallies ? ne * W : 0), order(ne);
-    if (ne) {
-        HIP_TRY(ctx, hipMemcpyAsync(h_edges.data(), b.edges, ne * 8, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(ctx, hipMemcpyAsync(h_keys.data(), b.edge_keys, ne * 8, hipMemcpyDeviceToHost, stream));
-        if (finish)
-            HIP_TRY(ctx, hipMemcpyAsync(h_val.data(), b.val, ne * 8, hipMemcpyDeviceToHost, stream));
-        if (tallies)
-            HIP_TRY(ctx, hipMemcpyAsync(h_tal.data(), b.tal, ne * W * 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(ctx, hipStreamSynchronize(stream));
-    }
-    for (uint64_t e = 0; e < ne; ++e)
-        order[e] = (uint32_t)e;
-    std::sort(order.begin(), order.end(), [&](uint32_t x, uint32_t y) {
-        return h_keys[x] != h_keys[y] ? h_keys[x] < h_keys[y] : h_edges[x] < h_edges[y];
-    });
-    for (uint64_t e = 0; e < ne; ++e) {
-        const uint32_t src = order[e];
-        edge_i[e] = (uint32_t)(h_edges[src] >> 32);
-        edge_j[e] = (uint32_t)h_edges[src];
-        if (values)
-            static_cast<uint64_t *>(values)[e] = h_val[src];
-        if (tallies)
-            std::memcpy(tallies + e * W, h_tal.data() + (size_t)src * W, (size_t)W * 4);
-    }
-    if (n_edges)
-        *n_edges = ne;
-    if (rounds)
-        *rounds = n_rounds;
-    return DST_OK;
-}
-
-namespace {
-
-// The device memory of one NJ call: the two matrix buffers and one block for the rest.  Per call, not grow-only: the
-// square of 50,000 records is 20 GB.  Freed behind the context's stream.  dst_dendrogram fills the same square through
-// nj_fill and needs no compaction: setup(n, false) leaves the second matrix buffer out.
-struct NjAlloc {
-    dst_ctx *ctx;
-    const char *what;
-    void *D0 = nullptr, *D1 = nullptr, *work = nullptr;
-    NjBuffers b{};
-    unsigned long long *bad = nullptr;
-    explicit NjAlloc(dst_ctx *c, const char *w = "neighbour joining") : ctx(c), what(w) {}
-    ~NjAlloc()
-    {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (void *p : {D0, D1, work})
-            if (p)
-                (void)hipFree(p);
-    }
-    int alloc(void **p, size_t bytes)
-    {
-        if (hipMalloc(p, bytes) != hipSuccess) {
-            *p = nullptr;
-            (void)hipGetLastError();   // (clear the out-of-memory status: later launches check hipGetLastError)
-            return fail(ctx, DST_ERR_NOMEM, std::string(what) + ": cannot allocate " + std::to_string(bytes) +
-                                                " bytes of device memory");
-        }
-        return DST_OK;
-    }
-    int setup(uint64_t n, bool compaction = true)
-    {
-        const uint64_t n1 = std::max<uint64_t>(3 * n / 4, 1);
-        int rc = alloc(&D0, n * n * 8);
-        if (!rc && compaction)
-            rc = alloc(&D1, n1 * n1 * 8);
-        auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-        const size_t nodes = 2 * n - 2;
-        const size_t o_r1 = up(n * 8), o_ids0 = o_r1 + up(n * 8), o_ids1 = o_ids0 + up(n * 4), o_act = o_ids1 + up(n * 4),
-                     o_pos = o_act + up(n), o_pk = o_pos + up(n * 4), o_pij = o_pk + up(kNjScanBlocks * 8),
-                     o_par = o_pij + up(kNjScanBlocks * 8), o_len = o_par + up(nodes * 4), o_bad = o_len + up(nodes * 8),
-                     total = o_bad + 256;
-        if (!rc)
-            rc = alloc(&work, total);
-        if (rc)
-            return rc;
-        char *w = static_cast<char *>(work);
-        b.D[0] = static_cast<double *>(D0);
-        b.D[1] = static_cast<double *>(D1);
-        b.r[0] = reinterpret_cast<double *>(w);
-        b.r[1] = reinterpret_cast<double *>(w + o_r1);
-        b.ids[0] = reinterpret_cast<uint32_t *>(w + o_ids0);
-        b.ids[1] = reinterpret_cast<uint32_t *>(w + o_ids1);
-        b.active = reinterpret_cast<uint8_t *>(w + o_act);
-        b.pos = reinterpret_cast<uint32_t *>(w + o_pos);
-        b.part_key = reinterpret_cast<uint64_t *>(w + o_pk);
-        b.part_ij = reinterpret_cast<uint64_t *>(w + o_pij);
-        b.parent = reinterpret_cast<uint32_t *>(w + o_par);
-        b.length = reinterpret_cast<double *>(w + o_len);
-        bad = reinterpret_cast<unsigned long long *>(w + o_bad);
-        return DST_OK;
-    }
-};
-
-int nj_check_out(dst_ctx *ctx, uint64_t n, uint32_t *parent, double *length, size_t cap)
-{
-    if (!parent || !length)
-        return fail(ctx, DST_ERR_ARG, "null parent or length pointer");
-    if (n < 3)
-        return fail(ctx, DST_ERR_ARG, "neighbour joining needs at least 3 records");
-    if (n >= ((uint64_t)1 << 31))
-        return fail(ctx, DST_ERR_ARG, "neighbour joining of 2^31 records or more");
-    if (cap < 2 * n - 2)
-        return fail(ctx, DST_ERR_CAPACITY, "cap is below 2n - 2 entries");
-    return DST_OK;
-}
-
-// the row slabs of the fill of an n-record square and the context's slab scratch for them (grow-only; the wait lets an
-// earlier call's slab go before it is replaced)
-int nj_slabs(dst_ctx *ctx, int measure, uint64_t n, uint64_t max_pairs, std::vector<RowSlab> &slabs)
-{
-    slabs = cut_row_slabs(true, n, n, max_pairs ? max_pairs : kClusterSlabPairs);
-    uint64_t biggest = 0;
-    for (const RowSlab &s : slabs)
-        biggest = std::max(biggest, s.pairs);
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return ensure_bytes(ctx, &ctx->cl_slab, &ctx->cl_slab_bytes,
-                        std::max<size_t>(dst_out_bytes(measure, DST_OUT_DISTANCE, biggest), 256));
-}
-
-// the square of `set` into al's first matrix buffer and the non-finite flag, queued on the context's stream without a
-// wait: the initial state, then per slab its pairs (each once, the triangle) as DST_OUT_DISTANCE payloads, scattered
-int nj_fill(dst_ctx *ctx, int measure, DeviceSet &set, const std::vector<RowSlab> &slabs, NjAlloc &al)
-{
-    hipStream_t stream = ctx->stream;
-    const uint64_t n = set.n;
-    HIP_TRY(ctx, launch_nj_init(al.b.D[0], n, al.b.ids[0], al.b.active, al.bad, stream));
-    for (const RowSlab &s : slabs) {
-        const int rc = run_sets(ctx, measure, true, set, set, s.rb, s.re, DST_OUT_DISTANCE, ctx->cl_slab,
-                                ctx->cl_slab_bytes, (void *)stream);
-        if (rc)
-            return rc;
-        HIP_TRY(ctx, launch_nj_scatter(measure, static_cast<const uint64_t *>(ctx->cl_slab), s.first, n, s.rb, s.re,
-                                       al.b.D[0], al.bad, stream));
-    }
-    return DST_OK;
-}
-
-// the message of a non-finite fill: the first pair in canonical order, from the flag's linear index i * n + j
-int nj_bad_pair(dst_ctx *ctx, const std::string &what, unsigned long long bad, uint64_t n)
-{
-    return fail(ctx, DST_ERR_STATE, what + "the distance of records " + std::to_string(bad / n) + " and " +
-                                        std::to_string(bad % n) + " is not finite");
-}
-
-// the rounds behind the fill on the context's stream, then one copy of the tree to the host
-int nj_finish(dst_ctx *ctx, NjAlloc &al, uint64_t n, uint32_t *parent, double *length)
-{
-    hipStream_t stream = ctx->stream;
-    HIP_TRY(ctx, launch_nj_rounds(al.b, n, stream));
-    HIP_TRY(ctx, hipMemcpyAsync(parent, al.b.parent, (2 * n - 2) * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipMemcpyAsync(length, al.b.length, (2 * n - 2) * 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    return DST_OK;
-}
-
-// dst_nj_bootstrap's device memory beside NjAlloc: the original codes, the replicate's codes (both n x pitch) and the
-// column map.  Freed behind the context's stream, with the replicate's packed set.
-struct BootAlloc {
-    dst_ctx *ctx;
-    uint8_t *src = nullptr, *rep = nullptr;
-    uint32_t *map = nullptr;
-    explicit BootAlloc(dst_ctx *c) : ctx(c) {}
-    ~BootAlloc()
-    {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (void *p : {(void *)src, (void *)rep, (void *)map})
-            if (p)
-                (void)hipFree(p);
-        free_set(ctx->boot);
-    }
-    int setup(uint64_t n, uint64_t pitch, uint64_t len)
-    {
-        const size_t bytes[3] = {std::max<size_t>(n * pitch, 128), std::max<size_t>(n * pitch, 128),
-                                 std::max<size_t>(len * 4, 4)};
-        void **ptrs[3] = {(void **)&src, (void **)&rep, (void **)&map};
-        for (int k = 0; k < 3; ++k)
-            if (hipMalloc(ptrs[k], bytes[k]) != hipSuccess) {
-                *ptrs[k] = nullptr;
-                (void)hipGetLastError();
-                return fail(ctx, DST_ERR_NOMEM, "bootstrap: cannot allocate " + std::to_string(bytes[k]) +
-                                                    " bytes of device memory");
-            }
-        return DST_OK;
-    }
-};
-
-}  // namespace
-
-int dst_nj(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *parent, double *length, size_t cap)
-{
-    if (!ctx)
-        return DST_ERR_ARG;
-    if (measure < DST_N || measure > DST_TN93)
-        return fail(ctx, DST_ERR_ARG, "unknown measure");
-    DeviceSet &set = ctx->set[0];
-    if (!set.loaded)
-        return fail(ctx, DST_ERR_STATE, "set not uploaded");
-    const uint64_t n = set.n;
-    if (int rc = nj_check_out(ctx, n, parent, length, cap))
-        return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t stream = ctx->stream;
-    std::vector<RowSlab> slabs;
-    int rc = nj_slabs(ctx, measure, n, max_pairs, slabs);
-    if (rc)
-        return rc;
-    NjAlloc al(ctx);
-    if ((rc = al.setup(n)))
-        return rc;
-    if ((rc = nj_fill(ctx, measure, set, slabs, al)))
-        return rc;
-    // one look at the fill before the rounds: a non-finite distance ends the call
-    unsigned long long bad = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&bad, al.bad, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    if (bad != ~0ull)
-        return nj_bad_pair(ctx, "neighbour joining: ", bad, n);
-    return nj_finish(ctx, al, n, parent, length);
-}
-
-int dst_nj_bootstrap(dst_ctx *ctx, int measure, const uint8_t *codes, size_t n, size_t len, size_t row_stride,
-                     uint32_t replicates, uint64_t seed, uint64_t max_pairs, const uint32_t *parent, uint32_t *support,
-                     uint32_t *rep_parent, size_t cap)
-{
-    if (!ctx)
-        return DST_ERR_ARG;
-    if (measure < DST_N || measure > DST_TN93)
-        return fail(ctx, DST_ERR_ARG, "unknown measure");
-    if (!parent || !support)
-        return fail(ctx, DST_ERR_ARG, "null parent or support pointer");
-    if ((len && !codes) || row_stride < len)
-        return fail(ctx, DST_ERR_ARG, "null codes or row_stride < len");
-    if (n < 3)
-        return fail(ctx, DST_ERR_ARG, "neighbour joining needs at least 3 records");
-    if (n >= ((uint64_t)1 << 31) || len >= 0xFFFFFF00ull)
-        return fail(ctx, DST_ERR_ARG, "bootstrap: n must be below 2^31 and len must fit 32 bits");
-    if (replicates < 1 || replicates > 10000)
-        return fail(ctx, DST_ERR_ARG, "bootstrap: replicates must be in 1..=10000");
-    const uint64_t N = 2 * n - 2;
-    if (cap < N)
-        return fail(ctx, DST_ERR_CAPACITY, "cap is below 2n - 2 entries");
-    SplitCounter splits;
-    if (!splits.init(n, parent))
-        return fail(ctx, DST_ERR_ARG, "bootstrap: the main tree is not a dst_nj tree on n leaves");
-    std::vector<uint32_t> count(N, 0), rp(N);
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t stream = ctx->stream;
-    std::vector<RowSlab> slabs;
-    int rc = nj_slabs(ctx, measure, n, max_pairs, slabs);
-    if (rc)
-        return rc;
-    const uint64_t pitch = std::max<uint64_t>((len + 127) / 128 * 128, 128);
-    NjAlloc al(ctx);   // (destroyed after `boot`: the replicate set is freed first, then the square)
-    BootAlloc boot(ctx);
-    if ((rc = boot.setup(n, pitch, len)) || (rc = al.setup(n)))
-        return rc;
-    if (len)
-        HIP_TRY(ctx, hipMemcpy2DAsync(boot.src, pitch, codes, row_stride, len, n, hipMemcpyHostToDevice, stream));
-    // the original once through the pack: every byte is checked, as dst_upload checks it (a replicate draws a subset)
-    if ((rc = pack_set(ctx, ctx->boot, boot.src, n, len, pitch, nullptr, stream)))
-        return rc;
-    for (uint32_t r = 0; r < replicates; ++r) {
-        HIP_TRY(ctx, launch_boot_resample(boot.src, pitch, boot.rep, n, len, seed, r, boot.map, stream));
-        // tn93: no counts passed, so the pair kernels count the replicate's bases by code (need_counts)
-        if ((rc = pack_set(ctx, ctx->boot, boot.rep, n, len, pitch, nullptr, stream)))
-            return rc;
-        if ((rc = nj_fill(ctx, measure, ctx->boot, slabs, al)))
-            return rc;
-        // the rounds run whatever the flag says (their indices stay in range on non-finite values); one wait per tree
-        unsigned long long bad = 0;
-        uint32_t *dst = rep_parent ? rep_parent + (uint64_t)r * N : rp.data();
-        HIP_TRY(ctx, launch_nj_rounds(al.b, n, stream));
-        HIP_TRY(ctx, hipMemcpyAsync(dst, al.b.parent, N * 4, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(ctx, hipMemcpyAsync(&bad, al.bad, 8, hipMemcpyDeviceToHost, stream));
-        HIP_TRY(ctx, hipStreamSynchronize(stream));
-        if (bad != ~0ull)
-            return nj_bad_pair(ctx, "bootstrap replicate " + std::to_string(r) + ": ", bad, n);
-        if (!splits.count(dst, count.data()))
-            return fail(ctx, DST_ERR_STATE, "bootstrap replicate " + std::to_string(r) + ": malformed replicate tree");
-    }
-    for (uint64_t x = 0; x < N; ++x)
-        support[x] = x < n || parent[x] == 0xFFFFFFFFu ? 0xFFFFFFFFu : count[x];
-    return DST_OK;
-}
-
-int dst_nj_matrix(dst_ctx *ctx, const double *d, uint64_t n, uint32_t *parent, double *length, size_t cap)
-{
-    if (!ctx)
-        return DST_ERR_ARG;
-    if (!d)
-        return fail(ctx, DST_ERR_ARG, "null matrix pointer");
-    if (int rc = nj_check_out(ctx, n, parent, length, cap))
-        return rc;
-    for (uint64_t i = 0; i < n; ++i)
-        for (uint64_t j = i + 1; j < n; ++j)
-            if (!std::isfinite(d[i * n + j]))
-                return fail(ctx, DST_ERR_ARG, "neighbour joining: the distance of records " + std::to_string(i) + " and " +
-                                                  std::to_string(j) + " is not finite");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t stream = ctx->stream;
-    NjAlloc al(ctx);
-    if (int rc = al.setup(n))
-        return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(al.b.D[0], d, n * n * 8, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ctx, launch_nj_init(al.b.D[0], n, al.b.ids[0], al.b.active, al.bad, stream));
-    HIP_TRY(ctx, launch_nj_mirror(al.b.D[0], n, stream));
-    return nj_finish(ctx, al, n, parent, length);
-}
-
-namespace {
-
-int dg_check(dst_ctx *ctx, uint64_t n, int linkage, uint32_t *parent, double *length, size_t cap)
-{
-    if (linkage < DST_LINK_AVERAGE || linkage > DST_LINK_COMPLETE)
-        return fail(ctx, DST_ERR_ARG, "unknown linkage");
-    if (!parent || !length)
-        return fail(ctx, DST_ERR_ARG, "null parent or length pointer");
-    if (n < 2)
-        return fail(ctx, DST_ERR_ARG, "a dendrogram needs at least 2 records");
-    if (n >= ((uint64_t)1 << 31))
-        return fail(ctx, DST_ERR_ARG, "a dendrogram of 2^31 records or more");
-    if (n > ((uint64_t)1 << 30))   // (8 n^2 must fit 64 bits before it is asked for; 2^30 records are 2^63 bytes)
-        return fail(ctx, DST_ERR_NOMEM, "dendrogram: a square of " + std::to_string(n) + " records does not fit device memory");
-    if (cap < 2 * n - 1)
-        return fail(ctx, DST_ERR_CAPACITY, "cap is below 2n - 1 entries");
-    return DST_OK;
-}
-
-// the O(n) state of a dendrogram call in the context's grow-only scratch, beside the square (and its flags) of `al`
-int dg_buffers(dst_ctx *ctx, NjAlloc &al, uint64_t n, DgBuffers &b)
-{
-    auto up = [](size_t x) { return (x + 255) / 256 * 256; };
-    const size_t nodes = 2 * n - 1, nblk = (n + kDgBlockRows - 1) / kDgBlockRows;
-    const size_t o_key = up(n * 4), o_col = o_key + up(n * 8), o_blk = o_col + up(n * 4), o_list = o_blk + up(nblk * 8),
-                 o_cnt = o_list + up(n * 4), o_par = o_cnt + 256, o_len = o_par + up(nodes * 4), o_hgt = o_len + up(nodes * 8),
-                 total = o_hgt + up(nodes * 8);
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (an earlier call's state goes before it is replaced)
-    if (int rc = ensure_bytes(ctx, &ctx->dg_work, &ctx->dg_work_bytes, total))
-        return rc;
-    char *w = static_cast<char *>(ctx->dg_work);
-    b.D = al.b.D[0];
-    b.active = al.b.active;
-    b.node = al.b.ids[0];
-    b.size = reinterpret_cast<uint32_t *>(w);
-    b.row_key = reinterpret_cast<uint64_t *>(w + o_key);
-    b.row_col = reinterpret_cast<uint32_t *>(w + o_col);
-    b.blk_key = reinterpret_cast<uint64_t *>(w + o_blk);
-    b.list = reinterpret_cast<uint32_t *>(w + o_list);
-    b.counters = reinterpret_cast<uint32_t *>(w + o_cnt);
-    b.scans = reinterpret_cast<unsigned long long *>(w + o_cnt + 16);
-    b.pair = reinterpret_cast<DgPair *>(w + o_cnt + 32);
-    b.parent = reinterpret_cast<uint32_t *>(w + o_par);
-    b.length = reinterpret_cast<double *>(w + o_len);
-    b.height = reinterpret_cast<double *>(w + o_hgt);
-    return DST_OK;
-}
-
-// the rounds behind the fill on the context's stream, then one copy of the tree to the host
-int dg_finish(dst_ctx *ctx, const DgBuffers &b, uint64_t n, int linkage, uint32_t *parent, double *length, double *height,
-              uint64_t *row_scans)
-{
-    hipStream_t stream = ctx->stream;
-    unsigned long long scans = 0;
-    HIP_TRY(ctx, launch_dg_init(b, n, stream));
-    HIP_TRY(ctx, launch_dg_rounds(b, n, linkage, stream));
-    HIP_TRY(ctx, hipMemcpyAsync(parent, b.parent, (2 * n - 1) * 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipMemcpyAsync(length, b.length, (2 * n - 1) * 8, hipMemcpyDeviceToHost, stream));
-    if (height)
-        HIP_TRY(ctx, hipMemcpyAsync(height, b.height, (2 * n - 1) * 8, hipMemcpyDeviceToHost, stream));
-    uint32_t failed = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&scans, b.scans, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipMemcpyAsync(&failed, b.counters + 2, 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    if (row_scans)
-        *row_scans = scans;
-    if (failed)   // (the row-minimum cache lost the pair: never a tree that is silently wrong)
-        return fail(ctx, DST_ERR_STATE, "dendrogram: internal error, round " + std::to_string(failed - 1) +
-                                            " found no active pair");
-    return DST_OK;
-}
-
-}  // namespace
-
-int dst_dendrogram(dst_ctx *ctx, int measure, int linkage, uint64_t max_pairs, uint32_t *parent, double *length,
-                   double *height, size_t cap, uint64_t *row_scans)
-{
-    if (!ctx)
-        return DST_ERR_ARG;
-    if (measure < DST_N || measure > DST_TN93)
-        return fail(ctx, DST_ERR_ARG, "unknown measure");
-    DeviceSet &set = ctx->set[0];
-    if (!set.loaded)
-        return fail(ctx, DST_ERR_STATE, "set not uploaded");
-    const uint64_t n = set.n;
-    if (int rc = dg_check(ctx, n, linkage, parent, length, cap))
-        return rc;
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t stream = ctx->stream;
-    std::vector<RowSlab> slabs;
-    int rc = nj_slabs(ctx, measure, n, max_pairs, slabs);
-    if (rc)
-        return rc;
-    NjAlloc al(ctx, "dendrogram");
-    DgBuffers b{};
-    if ((rc = al.setup(n, false)) || (rc = dg_buffers(ctx, al, n, b)))
-        return rc;
-    if ((rc = nj_fill(ctx, measure, set, slabs, al)))
-        return rc;
-    // one look at the fill before the rounds: a non-finite distance ends the call
-    unsigned long long bad = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&bad, al.bad, 8, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    if (bad != ~0ull)
-        return nj_bad_pair(ctx, "dendrogram: ", bad, n);
-    return dg_finish(ctx, b, n, linkage, parent, length, height, row_scans);
-}
-
-int dst_dendrogram_matrix(dst_ctx *ctx, const double *d, uint64_t n, int linkage, uint32_t *parent, double *length,
-                          double *height, size_t cap, uint64_t *row_scans)
-{
-    if (!ctx)
-        return DST_ERR_ARG;
-    if (!d)
-        return fail(ctx, DST_ERR_ARG, "null matrix pointer");
-    if (int rc = dg_check(ctx, n, linkage, parent, length, cap))
-        return rc;
-    for (uint64_t i = 0; i < n; ++i)
-        for (uint64_t j = i + 1; j < n; ++j)
-            if (!std::isfinite(d[i * n + j]))
-                return fail(ctx, DST_ERR_ARG, "dendrogram: the distance of records " + std::to_string(i) + " and " +
-                                                  std::to_string(j) + " is not finite");
-    HIP_TRY(ctx, hipSetDevice(ctx->device));
-    hipStream_t stream = ctx->stream;
-    NjAlloc al(ctx, "dendrogram");
-    DgBuffers b{};
-    int rc;
-    if ((rc = al.setup(n, false)) || (rc = dg_buffers(ctx, al, n, b)))
-        return rc;
-    HIP_TRY(ctx, hipMemcpyAsync(b.D, d, n * n * 8, hipMemcpyHostToDevice, stream));
-    HIP_TRY(ctx, launch_nj_init(b.D, n, b.node, b.active, al.bad, stream));
-    HIP_TRY(ctx, launch_nj_mirror(b.D, n, stream));
-    return dg_finish(ctx, b, n, linkage, parent, length, height, row_scans);
 }
 
 int dst_run_square_host(dst_ctx *ctx, int measure, uint64_t row_begin, uint64_t row_end, int out_kind,

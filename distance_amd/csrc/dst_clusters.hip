@@ -193,8 +193,7 @@ hipError_t launch_clusters_link(int measure, const uint64_t *slab, uint64_t out_
         return hipSuccess;
     const bool int_payload = measure == DST_N || measure == DST_N_HIGH;
     const unsigned chunks = (unsigned)((n - rb - 1 + kClusterBlockPairs - 1) / kClusterBlockPairs);   // of row rb, the longest
-    for (uint64_t row0 = rb; row0 < re; row0 += 65535) {   // (grid y is at most 65535 rows)
-        const unsigned rows = (unsigned)std::min<uint64_t>(re - row0, 65535);
+    return for_row_grids(rb, re, [&](uint64_t row0, unsigned rows) {
         const dim3 grid(chunks, rows);
         if (int_payload)
             hipLaunchKernelGGL(clusters_link_kernel<true>, grid, dim3(256), 0, stream, slab, out_base, (uint32_t)n,
@@ -202,11 +201,8 @@ hipError_t launch_clusters_link(int measure, const uint64_t *slab, uint64_t out_
         else
             hipLaunchKernelGGL(clusters_link_kernel<false>, grid, dim3(256), 0, stream, slab, out_base, (uint32_t)n,
                                (uint32_t)row0, (uint32_t)re, t_bits, parent, links);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_clusters_final(uint32_t *parent, uint64_t n, hipStream_t stream)

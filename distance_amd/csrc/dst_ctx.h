@@ -1,5 +1,6 @@
 // dst_ctx.h — the context behind the C ABI and the helpers its translation units share
-// (dst_api.cpp: uploads and runs, dst_stream.cpp: the stream-mode pipeline, dst_gather.cpp: multi-GPU gather).
+// (dst_api.cpp: uploads and runs, dst_analysis.cpp: the slab-driven analyses, dst_stream.cpp: the stream-mode pipeline,
+// dst_gather.cpp: multi-GPU gather).
 #pragma once
 #include <string>
 #include <vector>
@@ -94,16 +95,20 @@ struct dst_ctx {
         uint64_t last_biggest = 0;   // entries of the largest block of the previous shared upload (sizes the next one)
         uint64_t uploads = 0, fallbacks = 0;
     } shared[2];
-    // dst_nearest: the slab's DST_OUT_TALLY scratch and the running lists (grow-only)
-    void *nn_slab = nullptr, *nn_lists = nullptr;
-    size_t nn_slab_bytes = 0, nn_lists_bytes = 0;
-    // dst_clusters: the slab's DST_OUT_DISTANCE scratch and the parent array + link counter (grow-only)
-    void *cl_slab = nullptr, *cl_work = nullptr;
-    size_t cl_slab_bytes = 0, cl_work_bytes = 0;
-    // dst_mst: the component, best-edge and edge-list arrays (grow-only; the slab scratch is cl_slab)
+    // the analyses (dst_analysis.cpp): the one slab scratch their pair kernels write, DST_OUT_TALLY or DST_OUT_DISTANCE as
+    // the call needs (grow-only; a call owns it until it returns, and every call waits for the stream before it does)
+    void *pair_slab = nullptr;
+    size_t pair_slab_bytes = 0;
+    // dst_nearest: the running lists (grow-only)
+    void *nn_lists = nullptr;
+    size_t nn_lists_bytes = 0;
+    // dst_clusters: the parent array + link counter (grow-only)
+    void *cl_work = nullptr;
+    size_t cl_work_bytes = 0;
+    // dst_mst: the component, best-edge and edge-list arrays (grow-only)
     void *mst_work = nullptr;
     size_t mst_work_bytes = 0;
-    // dst_dendrogram: the O(n) state beside the per-call square (grow-only; the slab scratch is cl_slab)
+    // dst_dendrogram: the O(n) state beside the per-call square (grow-only)
     void *dg_work = nullptr;
     size_t dg_work_bytes = 0;
     // HIP events around the pair kernel ([0]) and the pack kernel ([1]) of the most recent launches, recorded on the launch
@@ -148,10 +153,21 @@ void free_set(DeviceSet &s);
 int pack_queue(dst_ctx *ctx, DeviceSet &s, const uint8_t *d_codes, size_t n, size_t len, size_t row_stride,
                const uint32_t *d_counts, unsigned long long *d_first_bad, hipStream_t stream, bool want_lists, bool nibbles = false);
 int invalid_code_error(dst_ctx *ctx, unsigned long long first_bad, size_t len);
+// the upload of device bytes into any set of the context (a slot, or dst_nj_bootstrap's replicate): the pack, the
+// report and its one synchronisation
+int pack_set(dst_ctx *ctx, DeviceSet &s, const uint8_t *d_codes, size_t n, size_t len, size_t row_stride,
+             const uint32_t *d_counts, hipStream_t stream);
 // the per-record {A,T,G,C} counts of `s` on the device (counted by code unless the upload brought them)
 int need_counts(dst_ctx *ctx, DeviceSet &s, hipStream_t stream);
 // rows [rb, re) of `rows` against every (square: later) record of `cols` — any two packed sets of this context
 int run_sets(dst_ctx *ctx, int measure, bool square, DeviceSet &rows, DeviceSet &cols, uint64_t rb, uint64_t re,
              int out_kind, void *d_out, size_t cap, void *stream_v);
+// the row slabs of a call, cut at max_pairs (0: default_pairs) pairs, and the pair count of the largest one
+// (dst_analysis.cpp; dst_run_slabs plans with it too)
+struct SlabPlan {
+    std::vector<RowSlab> slabs;
+    uint64_t biggest = 0;
+};
+SlabPlan plan_slabs(bool square, uint64_t n_rows, uint64_t n_cols, uint64_t max_pairs, uint64_t default_pairs);
 
 }  // namespace dst

@@ -319,6 +319,17 @@ __device__ __attribute__((noinline)) double finalize_pair_call(uint32_t o0, uint
     return finalize_pair<MEASURE>(o, qc, tc);
 }
 
+// the DST_OUT_DISTANCE payload of a pair from its DST_OUT_TALLY words (dst_nearest's lists, dst_mst's finish): bitwise
+// what a distance run returns
+template <int M>
+__device__ __forceinline__ uint64_t pair_value(const uint32_t *o, uint4 qc, uint4 tc)
+{
+    if constexpr (M == DST_N_HIGH)
+        return (uint64_t)(int64_t)o[0];
+    else
+        return (uint64_t)__double_as_longlong(finalize_pair<M>(o, qc, tc));
+}
+
 // the sort key of a DST_OUT_DISTANCE payload (dst_nearest's order, dst_clusters' threshold test): int64 -> offset
 // binary; f64 -> the order-preserving bit flip, every NaN ~0 (after +inf, equal to each other), -0.0 the key of +0.0
 template <bool INT>

@@ -1,7 +1,8 @@
-// dst_internal.h — shared between the HIP kernels (dst_kernels.hip), the C-ABI (dst_api.cpp)
+// dst_internal.h — shared between the HIP kernels (dst_kernels.hip), the C-ABI (dst_api.cpp, dst_analysis.cpp)
 // and the host-only logic (dst_host.cpp).  Not installed; the public surface is
 // include/distance_hip.h.
 #pragma once
+#include <algorithm>
 #include <cstddef>
 #include <cstdint>
 #include <string>
@@ -361,7 +362,23 @@ hipError_t launch_finalize(int measure, const PairLaunch &pl, const void *d_tall
 TileShape tile_shape(int measure, int variant);
 int variant_count(int measure);
 
-// ---- k nearest records (dst_nearest.hip, driven by dst_nearest in dst_api.cpp) -------------------------------------
+// ---- the analyses (dst_analysis.cpp drives the launchers below, slab by slab) ------------------------------------------
+// A grid's y dimension holds at most 65,535 rows: the rows [rb, re) of a launch that gives every row a grid row, in such
+// grids.  launch(row0, rows) queues one of them and returns its status; the first failure ends the walk.
+constexpr uint64_t kGridRowsMax = 65535;
+inline unsigned grid_rows(uint64_t rows) { return (unsigned)std::min<uint64_t>(rows, kGridRowsMax); }
+template <typename Launch>
+inline hipError_t for_row_grids(uint64_t rb, uint64_t re, Launch &&launch)
+{
+    for (uint64_t row0 = rb; row0 < re; row0 += kGridRowsMax) {
+        const hipError_t e = launch(row0, grid_rows(re - row0));
+        if (e != hipSuccess)
+            return e;
+    }
+    return hipSuccess;
+}
+
+// ---- k nearest records (dst_nearest.hip, driven by dst_nearest in dst_analysis.cpp) ---------------------------------
 // A call cuts the rows into slabs of at most kNearestSlabPairs pairs (cut_row_slabs, like dst_run_slabs), runs each slab
 // into a DST_OUT_TALLY scratch (square: the triangle, every pair once) and merges it into device-resident lists of
 // k entries per record, sorted by (key of the DST_OUT_DISTANCE payload, column record).
@@ -383,7 +400,7 @@ hipError_t launch_nearest_rows(int measure, bool square, const uint32_t *slab, u
 hipError_t launch_nearest_cols(int measure, const uint32_t *slab, uint64_t out_base, uint64_t n, uint64_t rb, uint64_t re,
                                const uint32_t *counts, const NearestLists &nl, hipStream_t stream);
 
-// ---- single-linkage clusters (dst_clusters.hip, driven by dst_clusters in dst_api.cpp) ------------------------------
+// ---- single-linkage clusters (dst_clusters.hip, driven by dst_clusters in dst_analysis.cpp) -------------------------
 // A call cuts the rows of slot 0 into slabs of at most kClusterSlabPairs pairs (cut_row_slabs), runs each slab's triangle
 // into a DST_OUT_DISTANCE scratch and unites the endpoints of its links in a device-resident parent array (lock-free
 // union-find, parent[x] <= x).  2^25 pairs (256 MB of payloads): the link launch of a full slab has 2^25 / 2048 = 16384
@@ -397,7 +414,7 @@ hipError_t launch_clusters_link(int measure, const uint64_t *slab, uint64_t out_
                                 uint64_t t_bits, uint32_t *parent, unsigned long long *links, hipStream_t stream);
 hipError_t launch_clusters_final(uint32_t *parent, uint64_t n, hipStream_t stream);
 
-// ---- minimum spanning forest (dst_mst.hip, driven by dst_mst in dst_api.cpp) ------------------------------------------
+// ---- minimum spanning forest (dst_mst.hip, driven by dst_mst in dst_analysis.cpp) -------------------------------------
 // Boruvka rounds: every round runs each row slab of the triangle into the DST_OUT_DISTANCE scratch (as dst_clusters) and
 // scans it twice (the minimal key of every component's outgoing edges, then the smallest pair of that key), hooks every
 // component along its best edge and flattens the component labels.  O(n) device state beside the slab.
@@ -422,7 +439,7 @@ hipError_t launch_mst_hook(const MstBuffers &b, uint64_t n, hipStream_t stream);
 hipError_t launch_mst_gather(int measure, const uint32_t *slab, uint64_t out_base, uint64_t n, uint64_t rb, uint64_t re,
                              const uint32_t *counts, const MstBuffers &b, uint64_t n_edges, hipStream_t stream);
 
-// ---- neighbour-joining trees (dst_nj.hip, driven by dst_nj / dst_nj_matrix in dst_api.cpp) --------------------------
+// ---- neighbour-joining trees (dst_nj.hip, driven by dst_nj / dst_nj_matrix in dst_analysis.cpp) ---------------------
 // The n x n f64 square on the device, filled from row slabs of DST_OUT_DISTANCE payloads (as dst_clusters) or from the
 // caller's matrix, then n - 3 rounds of a scan launch (kNjScanBlocks workgroups at most, one partial each) and a merge
 // launch, and a compaction into the other matrix buffer whenever m <= floor(3P/4).  D[0]: n x n; D[1]: at least
@@ -449,7 +466,7 @@ hipError_t launch_nj_mirror(double *D, uint64_t n, hipStream_t stream);
 // every round, the root included, into b.parent / b.length; n >= 3, D[0] symmetric with a +0.0 diagonal
 hipError_t launch_nj_rounds(const NjBuffers &b, uint64_t n, hipStream_t stream);
 
-// ---- dendrograms (dst_dendrogram.hip, driven by dst_dendrogram / dst_dendrogram_matrix in dst_api.cpp) --------------
+// ---- dendrograms (dst_dendrogram.hip, driven by dst_dendrogram / dst_dendrogram_matrix in dst_analysis.cpp) ---------
 // The n x n f64 square (filled as for NJ) and a row-minimum cache: for every active slot x the smallest (nn_key, column)
 // over the active k > x, and per block of kDgBlockRows rows the smallest cached key.  A round is three launches known
 // from n alone: the select (one workgroup: the pair from the block minima, the new node), the merge (thread k: the
@@ -480,7 +497,7 @@ hipError_t launch_dg_init(const DgBuffers &b, uint64_t n, hipStream_t stream);
 // symmetric and finite
 hipError_t launch_dg_rounds(const DgBuffers &b, uint64_t n, int linkage, hipStream_t stream);
 
-// ---- bootstrap replicates (dst_bootstrap.hip, driven by dst_nj_bootstrap in dst_api.cpp) -----------------------------
+// ---- bootstrap replicates (dst_bootstrap.hip, driven by dst_nj_bootstrap in dst_analysis.cpp) ------------------------
 // replicate r of the n x len codes at src (rows pitch bytes apart, pitch a multiple of 128 and >= len) into out (the same
 // pitch): out[i][c] := src[i][boot_column(seed, r * len + c, len)]; map: len entries of scratch
 hipError_t launch_boot_resample(const uint8_t *src, uint64_t pitch, uint8_t *out, uint64_t n, uint64_t len, uint64_t seed,

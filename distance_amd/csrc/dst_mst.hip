@@ -202,15 +202,6 @@ __global__ __launch_bounds__(256) void mst_flatten_kernel(uint32_t *comp, uint32
     comp[x] = r;
 }
 
-template <int M>
-__device__ __forceinline__ uint64_t mst_pair_value(const uint32_t *o, uint4 qc, uint4 tc)
-{
-    if constexpr (M == DST_N_HIGH)
-        return (uint64_t)(int64_t)o[0];
-    else
-        return (uint64_t)__double_as_longlong(finalize_pair<M>(o, qc, tc));
-}
-
 // rows [rb, re) of the square as DST_OUT_TALLY words from slab entry tri_row_start(n, i) - out_base
 template <int M, int W>
 __global__ __launch_bounds__(256) void mst_gather_kernel(const uint32_t *__restrict__ slab, uint64_t out_base, uint32_t n,
@@ -237,7 +228,7 @@ __global__ __launch_bounds__(256) void mst_gather_kernel(const uint32_t *__restr
         qc = reinterpret_cast<const uint4 *>(counts)[i];
         tc = reinterpret_cast<const uint4 *>(counts)[j];
     }
-    val[e] = mst_pair_value<M>(o, qc, tc);
+    val[e] = pair_value<M>(o, qc, tc);
 }
 
 }  // namespace
@@ -260,9 +251,8 @@ hipError_t launch_mst_scan(int measure, const uint64_t *slab, uint64_t out_base,
 #define DST_MST_SCAN(INT, PAIRS)                                                                                           \
     hipLaunchKernelGGL((mst_scan_kernel<INT, PAIRS>), grid, dim3(256), 0, stream, slab, out_base, (uint32_t)n, (uint32_t)row0, \
                        (uint32_t)re, b.comp, b.best_key, b.best_pair)
-    for (int pass = 0; pass < 2; ++pass)   // launch A over the whole slab, then launch B
-        for (uint64_t row0 = rb; row0 < re; row0 += 65535) {   // (grid y is at most 65535 rows)
-            const unsigned rows = (unsigned)std::min<uint64_t>(re - row0, 65535);
+    for (int pass = 0; pass < 2; ++pass) {   // launch A over the whole slab, then launch B
+        const hipError_t e = for_row_grids(rb, re, [&](uint64_t row0, unsigned rows) {
             const dim3 grid(chunks, rows);
             if (int_payload) {
                 if (pass == 0)
@@ -275,10 +265,11 @@ hipError_t launch_mst_scan(int measure, const uint64_t *slab, uint64_t out_base,
                 else
                     DST_MST_SCAN(false, true);
             }
-            const hipError_t e = hipGetLastError();
-            if (e != hipSuccess)
-                return e;
-        }
+            return hipGetLastError();
+        });
+        if (e != hipSuccess)
+            return e;
+    }
 #undef DST_MST_SCAN
     return hipSuccess;
 }

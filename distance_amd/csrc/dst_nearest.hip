@@ -32,15 +32,6 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t x, int src)
 }
 __device__ __forceinline__ uint32_t shfl32(uint32_t x, int src) { return (uint32_t)__shfl((int)x, src, 64); }
 
-template <int M>
-__device__ __forceinline__ uint64_t pair_value(const uint32_t *o, uint4 qc, uint4 tc)
-{
-    if constexpr (M == DST_N_HIGH)
-        return (uint64_t)(int64_t)o[0];
-    else
-        return (uint64_t)__double_as_longlong(finalize_pair<M>(o, qc, tc));
-}
-
 // one record's list, spread over the wave
 template <int W>
 struct WaveList {

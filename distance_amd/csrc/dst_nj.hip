@@ -288,11 +288,6 @@ __global__ void nj_final_kernel(const double *__restrict__ D, uint64_t P, const 
     length[root] = 0.0;
 }
 
-unsigned grid_rows(uint64_t rows)
-{
-    return (unsigned)std::min<uint64_t>(rows, 65535);
-}
-
 }  // namespace
 
 hipError_t launch_nj_init(double *D, uint64_t n, uint32_t *ids, uint8_t *active, unsigned long long *bad, hipStream_t stream)
@@ -309,29 +304,26 @@ hipError_t launch_nj_scatter(int measure, const uint64_t *slab, uint64_t out_bas
         return hipSuccess;
     const bool int_payload = measure == DST_N || measure == DST_N_HIGH;
     const unsigned chunks = (unsigned)((n - rb - 1 + kNjThreads - 1) / kNjThreads);   // of row rb, the longest
-    for (uint64_t row0 = rb; row0 < re; row0 += 65535) {
-        const dim3 grid(chunks, grid_rows(re - row0));
+    return for_row_grids(rb, re, [&](uint64_t row0, unsigned rows) {
+        const dim3 grid(chunks, rows);
         if (int_payload)
             hipLaunchKernelGGL(nj_scatter_kernel<true>, grid, dim3(kNjThreads), 0, stream, slab, out_base, n, row0, re, D, bad);
         else
             hipLaunchKernelGGL(nj_scatter_kernel<false>, grid, dim3(kNjThreads), 0, stream, slab, out_base, n, row0, re, D, bad);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_nj_mirror(double *D, uint64_t n, hipStream_t stream)
 {
+    if (n < 2)
+        return hipSuccess;
     const unsigned chunks = (unsigned)((n + kNjThreads - 1) / kNjThreads);
-    for (uint64_t row0 = 0; row0 + 1 < n; row0 += 65535) {
+    // rows 0 .. n - 2 hold the triangle; the grids stay cut from n rows, so the last one carries row n - 1 as well
+    return for_row_grids(0, n - 1, [&](uint64_t row0, unsigned) {
         hipLaunchKernelGGL(nj_mirror_kernel, dim3(chunks, grid_rows(n - row0)), dim3(kNjThreads), 0, stream, D, n, row0);
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess)
-            return e;
-    }
-    return hipSuccess;
+        return hipGetLastError();
+    });
 }
 
 // Every round of the join on the stream, without a synchronisation: the compaction schedule depends on (n, m) only.
