@@ -32,6 +32,8 @@ int fail(dst_ctx *ctx, int status, const std::string &msg)
 
 int fail_hip(dst_ctx *ctx, hipError_t e, const char *what)
 {
+    (void)hipGetLastError();   // a call that returned its error (not a launch) leaves it with the thread: the next launch's check
+                               // would report it again, on whatever context
     return fail(ctx, e == hipErrorOutOfMemory ? DST_ERR_NOMEM : DST_ERR_HIP,
                 std::string(what) + ": " + hipGetErrorString(e));
 }
@@ -725,8 +727,12 @@ int ensure_aconst(dst_ctx *ctx, DeviceSet &s, DeviceSet &refset, int family, boo
             return rc;
     }
     HIP_TRY(ctx, launch_aconst(s, family, wide, ctx->d_lut, stream));
-    if (s.runs.active)
-        HIP_TRY(ctx, launch_run_tables(s, family, wide, s.rec.without_hot, ctx->d_lut, stream));
+    if (s.runs.active) {
+        const char *failed = nullptr;
+        const hipError_t e = launch_run_tables(s, family, wide, ctx->d_lut, stream, &failed);
+        if (e != hipSuccess)
+            return fail_hip(ctx, e, (std::string("the run records' correction tables, ") + failed).c_str());
+    }
     rc = publish_prep(ctx, stream);
     if (rc)
         return rc;

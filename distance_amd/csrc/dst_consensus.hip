@@ -1240,53 +1240,63 @@ constexpr int kSumPieces = 5;   // 7 + 7 + 7 + 7 + 4 bits of a 32-bit sum
 // fold (run_index != NULL): a run record's sums also lose known[c] x unit on its own run chunks — then the product with
 // another run record's mask carries the F term of the two (+F after the sign flip).  The table the run ROWS read is built
 // from the folded sums, the table the run COLUMNS read from the plain ones: a pair of two run records meets the F term once.
+// The chunks are walked in slices of `row` (SumSlices: LDS does not grow with the alignment).  A record's entries ascend by
+// site and so does a lane's strided share of them: every lane keeps its place in the list from slice to slice, and the
+// list is read once.
 template <int W>
 __global__ __launch_bounds__(256) void chunk_sums_kernel(const uint32_t *__restrict__ off, const uint32_t *__restrict__ ent,
                                                          const uint32_t *__restrict__ aent, size_t aent_stride, uint32_t n,
-                                                         uint32_t kpad, uint8_t *__restrict__ s7,
+                                                         uint32_t kpad, uint32_t row, uint8_t *__restrict__ s7,
                                                          const uint32_t *__restrict__ run_index, const uint32_t *__restrict__ mask,
                                                          const uint32_t *__restrict__ known, const ConsensusLut *__restrict__ lut,
                                                          int family, int wide)
 {
-    extern __shared__ uint32_t srow[];   // [4 waves][W][kpad]
+    extern __shared__ uint32_t srow[];   // [4 waves][W][row]
     const uint32_t lane = threadIdx.x & 63u, wv = threadIdx.x >> 6, r = blockIdx.x * 4u + wv;
     const size_t n_tiles = (n + 31u) / 32u;
-    uint32_t *mine = srow + (size_t)wv * W * kpad;
-    for (uint32_t c = lane; c < W * kpad; c += 64)
-        mine[c] = 0;
-    if (r >= n)
+    uint32_t *mine = srow + (size_t)wv * W * row;
+    if (r >= n)   // (a whole wave: nothing in here waits for another)
         return;
     const uint32_t end = off[r + 1];
-    for (uint32_t i = off[r] + lane; i < end; i += 64) {
-        const uint32_t c = (ent[i] & kSiteMask) >> 7;
+    uint32_t i = off[r] + lane;
+    const uint32_t *m = run_index && run_index[r] != 0xFFFFFFFFu ? mask + (size_t)run_index[r] * (kpad / 32u) : nullptr;
+    for (uint32_t c0 = 0; c0 < kpad; c0 += row) {
+        const uint32_t width = min(row, kpad - c0);   // (whole mask words: kpad and row are multiples of 32)
+        for (uint32_t c = lane; c < W * row; c += 64)
+            mine[c] = 0;
+        for (; i < end; i += 64) {
+            const uint32_t c = ((ent[i] & kSiteMask) >> 7) - c0;   // (never below c0: the entries before it are done)
+            if (c >= width)
+                break;
 #pragma unroll
-        for (int w = 0; w < W; ++w)
-            atomicAdd(&mine[w * kpad + c], aent[(size_t)w * aent_stride + i]);
-    }
-    if (run_index && run_index[r] != 0xFFFFFFFFu) {
-        const uint32_t *m = mask + (size_t)run_index[r] * (kpad / 32u);
-        for (uint32_t c = lane; c < kpad; c += 64)
-            if ((m[c >> 5] >> (c & 31u)) & 1u) {
+            for (int w = 0; w < W; ++w)
+                atomicAdd(&mine[w * row + c], aent[(size_t)w * aent_stride + i]);
+        }
+        if (m) {
+            for (uint32_t c = lane; c < width; c += 64)
+                if ((m[(c0 + c) >> 5] >> (c & 31u)) & 1u) {
 #pragma unroll
-                for (int w = 0; w < W; ++w)
-                    mine[w * kpad + c] -= known[c] * lut->unit[family][wide][w];
-            }
-    }
-    // (one wave writes and reads its own LDS rows: in order)
-    for (uint32_t c4 = lane * 4; c4 < kpad; c4 += 256) {
+                    for (int w = 0; w < W; ++w)
+                        mine[w * row + c] -= known[c0 + c] * lut->unit[family][wide][w];
+                }
+        }
+        // (one wave writes and reads its own LDS rows: in order)
+        for (uint32_t l4 = lane * 4; l4 < width; l4 += 256) {
+            const uint32_t c4 = c0 + l4;
 #pragma unroll
-        for (int w = 0; w < W; ++w) {
-            const uint32_t v[4] = {mine[w * kpad + c4], mine[w * kpad + c4 + 1], mine[w * kpad + c4 + 2], mine[w * kpad + c4 + 3]};
+            for (int w = 0; w < W; ++w) {
+                const uint32_t v[4] = {mine[w * row + l4], mine[w * row + l4 + 1], mine[w * row + l4 + 2], mine[w * row + l4 + 3]};
 #pragma unroll
-            for (int p = 0; p < kSumPieces; ++p) {
-                const uint32_t sh = 7u * p;
-                const uint32_t packed = ((v[0] >> sh) & 127u) | ((v[1] >> sh) & 127u) << 8 | ((v[2] >> sh) & 127u) << 16 |
-                                        ((v[3] >> sh) & 127u) << 24;
-                // laid out as corr_mfma_kernel's lanes read it: per (tile of 32 records, step of 32 chunks) one contiguous KB,
-                // lane (half, record in tile) at 16 bytes x (32 half + record): a wave's operand load is eight whole lines
-                const size_t tile = r >> 5, ks = c4 >> 5, hf = (c4 >> 4) & 1u;
-                *reinterpret_cast<uint32_t *>(s7 + ((((size_t)w * kSumPieces + p) * n_tiles + tile) * (kpad / 32u) + ks) * 1024u +
-                                              (hf * 32u + (r & 31u)) * 16u + (c4 & 15u)) = packed;
+                for (int p = 0; p < kSumPieces; ++p) {
+                    const uint32_t sh = 7u * p;
+                    const uint32_t packed = ((v[0] >> sh) & 127u) | ((v[1] >> sh) & 127u) << 8 | ((v[2] >> sh) & 127u) << 16 |
+                                            ((v[3] >> sh) & 127u) << 24;
+                    // laid out as corr_mfma_kernel's lanes read it: per (tile of 32 records, step of 32 chunks) one contiguous KB,
+                    // lane (half, record in tile) at 16 bytes x (32 half + record): a wave's operand load is eight whole lines
+                    const size_t tile = r >> 5, ks = c4 >> 5, hf = (c4 >> 4) & 1u;
+                    *reinterpret_cast<uint32_t *>(s7 + ((((size_t)w * kSumPieces + p) * n_tiles + tile) * (kpad / 32u) + ks) * 1024u +
+                                                  (hf * 32u + (r & 31u)) * 16u + (c4 & 15u)) = packed;
+                }
             }
         }
     }
@@ -2547,31 +2557,44 @@ hipError_t launch_aconst(const DeviceSet &set, int family, bool wide, const Cons
 // the run records' tables of one (family, packing) from the set's current lists: the panels' first run records, the
 // per-chunk sums in 7-bit pieces, then X's terms by the matrix cores (corr_mfma_kernel) and the run x run F terms;
 // aconst_kernel must have run for the same (family, packing) first (it leaves the entries' a-words in runs.aent)
-hipError_t launch_run_tables(const DeviceSet &set, int family, bool wide, bool without_hot, const ConsensusLut *d_lut, hipStream_t stream)
+hipError_t launch_run_tables(const DeviceSet &set, int family, bool wide, const ConsensusLut *d_lut, hipStream_t stream,
+                             const char **failed)
 {
+    *failed = "launch_run_tables";
     const RunIndex &ru = set.runs;
     const uint32_t n = (uint32_t)set.n, n_panels = (uint32_t)((set.n + kPanelCols - 1) / kPanelCols);
-    const uint32_t mw = (uint32_t)ru.mask_words, kpad = 32u * mw;
     const int words = family_words(family, wide);
+    const SumSlices sl = sum_slices(set.nchunks, words);   // (kpad = 32 mask_words: ensure_index sizes the masks from nchunks too)
+    const uint32_t mw = sl.kpad / 32u, kpad = sl.kpad;
+    const size_t lds = sl.lds_bytes;
+    if (mw != ru.mask_words)   // (s7 and the masks were sized by mask_words)
+        return hipErrorInvalidValue;
+    hipError_t e;
     hipLaunchKernelGGL(run_panels_kernel, dim3((n_panels + 256) / 256), dim3(256), 0, stream, ru.ids, ru.n_run, n_panels, ru.panel_first);
+    if ((e = hipGetLastError()) != hipSuccess) {
+        *failed = "run_panels_kernel";
+        return e;
+    }
     const size_t stride = ru.aent_cap / (kMaxWords * sizeof(uint32_t));
     const dim3 grid((n + 127) / 128, (ru.n_run + 127) / 128);   // corr_mfma_kernel: 128 records x 128 run records per block
+#define DST_LAUNCHED(NAME)                        \
+    if ((e = hipGetLastError()) != hipSuccess) {  \
+        *failed = NAME;                           \
+        return e;                                 \
+    }
 #define DST_CORR(WW)                                                                                                                  \
     do {                                                                                                                              \
-        const size_t lds = (size_t)4 * WW * kpad * sizeof(uint32_t);                                                                  \
-        if (lds > 64 * 1024) {                                                                                                        \
-            const hipError_t ea = hipFuncSetAttribute(reinterpret_cast<const void *>(chunk_sums_kernel<WW>),                          \
-                                                      hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);                          \
-            if (ea != hipSuccess)                                                                                                     \
-                return ea;                                                                                                            \
-        }                                                                                                                             \
         /* the run COLUMNS' table from the plain sums, the run ROWS' table from the sums with the F terms folded in */              \
         hipLaunchKernelGGL((chunk_sums_kernel<WW>), dim3((n + 3) / 4), dim3(256), lds, stream, set.rec.off, set.rec.ent, ru.aent,     \
-                           stride, n, kpad, ru.s7, nullptr, nullptr, nullptr, d_lut, family, wide ? 1 : 0);                           \
+                           stride, n, kpad, sl.row, ru.s7, nullptr, nullptr, nullptr, d_lut, family, wide ? 1 : 0);                   \
+        DST_LAUNCHED("chunk_sums_kernel<" #WW ">");                                                                                   \
         hipLaunchKernelGGL((corr_mfma_kernel<WW, true>), grid, dim3(256), 0, stream, ru.mask + (size_t)ru.n_run * mw, mw, ru.s7, n, ru.n_run, ru.corr_t);     \
+        DST_LAUNCHED("corr_mfma_kernel<" #WW ", true>");                                                                              \
         hipLaunchKernelGGL((chunk_sums_kernel<WW>), dim3((n + 3) / 4), dim3(256), lds, stream, set.rec.off, set.rec.ent, ru.aent,     \
-                           stride, n, kpad, ru.s7, ru.index, ru.mask, ru.known, d_lut, family, wide ? 1 : 0);                         \
+                           stride, n, kpad, sl.row, ru.s7, ru.index, ru.mask, ru.known, d_lut, family, wide ? 1 : 0);                 \
+        DST_LAUNCHED("chunk_sums_kernel<" #WW ">");                                                                                   \
         hipLaunchKernelGGL((corr_mfma_kernel<WW, false>), grid, dim3(256), 0, stream, ru.mask + (size_t)ru.n_run * mw, mw, ru.s7, n, ru.n_run, ru.corr);      \
+        DST_LAUNCHED("corr_mfma_kernel<" #WW ", false>");                                                                             \
     } while (0)
     switch (words) {
     case 1: DST_CORR(1); break;
@@ -2580,8 +2603,8 @@ hipError_t launch_run_tables(const DeviceSet &set, int family, bool wide, bool w
     default: DST_CORR(4); break;
     }
 #undef DST_CORR
-    (void)without_hot;
-    return hipGetLastError();
+#undef DST_LAUNCHED
+    return hipSuccess;
 }
 
 hipError_t launch_run_masks(const DeviceSet &set, hipStream_t stream)

@@ -140,6 +140,27 @@ struct RunIndex {
     uint64_t corr_epoch = 0;
 };
 
+// chunk_sums_kernel keeps one row of per-chunk sums per wave and accumulator word in LDS and walks the chunks in slices of
+// kSumSliceChunks, so what a workgroup needs does not grow with the alignment: 4 waves x 4 words x 1,024 chunks x 4 bytes
+// = 64 KiB at most, what a kernel gets without asking for more.  (One row over all chunks, the first form, passed
+// 64 KiB at 131,073 sites of tn93 and the CU's whole 160 KiB at 327,681.)
+constexpr uint32_t kSumSliceChunks = 1024;   // a multiple of 32: a slice is whole mask words and whole k-steps of s7
+struct SumSlices {
+    uint32_t kpad;        // chunks padded to whole mask words: 32 x mask_words
+    uint32_t row;         // chunks of one LDS row: min(kpad, kSumSliceChunks)
+    uint32_t n_slices;    // slice k covers chunks [k * row, min((k + 1) * row, kpad))
+    size_t lds_bytes;     // dynamic LDS of a workgroup: [4 waves][words][row] uint32_t
+};
+inline SumSlices sum_slices(size_t nchunks, int words)
+{
+    SumSlices s;
+    s.kpad = 32u * (uint32_t)((nchunks + 31) / 32);
+    s.row = std::min(s.kpad, kSumSliceChunks);
+    s.n_slices = s.row ? (s.kpad + s.row - 1) / s.row : 0u;
+    s.lds_bytes = (size_t)4 * (size_t)words * s.row * sizeof(uint32_t);
+    return s;
+}
+
 struct SiteIndex {                // the same entries of a column set by (site, panel of kPanelCols records)
     // [n_sites * n_panels] 32 bytes per bucket = 16 halfwords: [0] entries in the bucket, then up to kInlineEvents
     // entries as record-in-panel | nibble << 11.  The pair kernel reads THIS: one request per (row entry, panel)
@@ -300,7 +321,9 @@ hipError_t launch_aconst(const DeviceSet &set, int family, bool wide, const Cons
 // tables of one (family, packing) — after launch_aconst for the same, which leaves the entries' a-words in runs.aent
 hipError_t launch_run_known(const DeviceSet &set, const uint4 *ref_planes, const uint4 *hot_planes, hipStream_t stream);
 hipError_t launch_run_masks(const DeviceSet &set, hipStream_t stream);   // runs.mask from the slots' run-chunk flags
-hipError_t launch_run_tables(const DeviceSet &set, int family, bool wide, bool without_hot, const ConsensusLut *d_lut, hipStream_t stream);
+// (*failed: the kernel whose launch was refused, for the error's message)
+hipError_t launch_run_tables(const DeviceSet &set, int family, bool wide, const ConsensusLut *d_lut, hipStream_t stream,
+                             const char **failed);
 constexpr int kReportWords = 13;   // [0] first invalid byte, [1..8] the sample's statistics, [9..10] list totals, [11] run records, [12] entries their lists lost
 // cnt_cold / cnt_hot (may be NULL): the pack's list lengths, summed into words 9 and 10.  runs: the pack's run-chunk
 // counters — records with kRunMin run chunks and more become run records (numbered in runs->index / ids, word 11 = how

@@ -86,6 +86,32 @@ int main()
     CHECK(cli::fmt_i64(-9223372036854775807LL - 1, buf) == 20 && std::memcmp(buf, "-9223372036854775808", 20) == 0);
     CHECK(dst_format_distance(DST_RAW, 1.0, 0, nullptr, 0) == -1);
     CHECK(dst_measure_from_name(nullptr) == -1 && dst_measure_from_name("tn93") == DST_TN93);
+    // chunk_sums_kernel's slices (sum_slices): for every accumulator width and every alignment the lists can index
+    // (kSiteMask / 128 = 262,144 chunks; every multiple of the slice and its neighbours are among them) the workgroup's LDS
+    // stays within 64 KiB, kpad is whole mask words, and the slices cover [0, kpad) exactly once in whole mask words
+    CHECK(kSumSliceChunks % 32u == 0 && (size_t)4 * 4 * kSumSliceChunks * sizeof(uint32_t) <= 65536);
+    CHECK(sum_slices(kSumSliceChunks, 4).n_slices == 1 && sum_slices(kSumSliceChunks + 1, 4).n_slices == 2);
+    CHECK(sum_slices(2561, 4).lds_bytes == 65536 && sum_slices(1, 1).lds_bytes == 512);
+    for (int words = 1; words <= 4; ++words)
+        for (size_t nchunks = 1; nchunks <= (kSiteMask + 1u) / kChunkSites; ++nchunks) {
+            const SumSlices sl = sum_slices(nchunks, words);
+            bool ok = sl.lds_bytes <= 65536 && sl.lds_bytes == (size_t)16 * words * sl.row;
+            ok = ok && sl.kpad % 32u == 0 && sl.kpad >= nchunks && sl.kpad < nchunks + 32;
+            ok = ok && sl.row % 32u == 0 && sl.row >= 32 && sl.row <= kSumSliceChunks;
+            uint64_t next = 0;   // the kernel's walk: c0 += row, width = min(row, kpad - c0)
+            uint32_t slices = 0;
+            for (uint32_t c0 = 0; c0 < sl.kpad; c0 += sl.row, ++slices) {
+                const uint32_t width = std::min(sl.row, sl.kpad - c0);
+                ok = ok && c0 == next && width % 32u == 0 && width >= 32;
+                next += width;
+            }
+            ok = ok && next == sl.kpad && slices == sl.n_slices;
+            if (!ok) {
+                std::fprintf(stderr, "sum_slices(%zu, %d)\n", nchunks, words);
+                CHECK(ok);
+                break;
+            }
+        }
     if (failures == 0)
         std::puts("host_check: all checks passed");
     return failures ? 1 : 0;
