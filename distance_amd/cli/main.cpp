@@ -13,7 +13,9 @@
 // neighbour-joining tree as one Newick line: dst_nj, dst_newick), --bootstrap B / --seed S (the tree's splits labelled
 // with their support in B column resamplings: dst_nj_bootstrap, dst_newick_support), --mst (the edges of the minimum
 // spanning tree in ascending order, one "id1, id2, value" line each: dst_mst), --dendrogram average|weighted|complete (the
-// UPGMA / WPGMA / complete-linkage dendrogram as one Newick line with a binary root: dst_dendrogram, dst_newick_rooted).
+// UPGMA / WPGMA / complete-linkage dendrogram as one Newick line with a binary root: dst_dendrogram, dst_newick_rooted),
+// --max-distance T (the long output filtered on the GPU: only the lines of the pairs within T, in the full run's order:
+// dst_links).
 //
 // Exactness: the GPU returns integer site tallies; f64 finalisation is dst_finalize() on the host
 // (reference operation order, glibc log/sqrt), so the printed digits do not depend on the device.
@@ -113,6 +115,9 @@ void print_help()
         "      --clusters <T>           Print the single-linkage cluster of every record instead of distances: records "
         "within distance T (a number >= 0) of each other share a cluster, numbered from 1 in order of first record. One "
         "input, one GPU, no --stream or --nearest\n"
+        "      --max-distance <T>       Print only the pairs within distance T (a number >= 0, or inf): the lines of the full "
+        "run whose distance is at most T, in the same order and with the same text. One or two inputs, one GPU, no --stream "
+        "and no other output mode\n"
         "      --matrix <format>        Print a distance matrix instead of one line per pair: tsv (one or two inputs, rows "
         "from the first, columns from the last) or phylip (relaxed PHYLIP, one input). Not in stream, nearest or "
         "clusters mode\n"
@@ -145,6 +150,8 @@ struct Args {
     bool has_nearest = false;
     double clusters = 0;                  // --clusters T
     bool has_clusters = false;
+    double max_distance = 0;              // --max-distance T
+    bool has_max_distance = false;
     int matrix = -1;                      // --matrix: DST_MATRIX_TSV / DST_MATRIX_PHYLIP (-1: the long form)
     bool has_tree = false;                // --tree nj
     uint32_t bootstrap = 0;               // --bootstrap B (0: none)
@@ -255,6 +262,20 @@ Args parse_args(int argc, char **argv)
                 die_usage("invalid value '" + v + "' for '--clusters <T>': the threshold must not be negative");
             a.clusters = t;
             a.has_clusters = true;
+        } else if (arg == "--max-distance" || arg.rfind("--max-distance=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--max-distance <T>");
+            if (a.has_max_distance)
+                die_usage("the argument '--max-distance <T>' cannot be used multiple times");
+            // the whole word is the number (or inf), as for --clusters <T>
+            char *end = nullptr;
+            errno = 0;
+            const double t = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
+            if (v.empty() || end != v.c_str() + v.size() || t != t || std::isspace((unsigned char)v[0]))
+                die_usage("invalid value '" + v + "' for '--max-distance <T>': not a number");
+            if (t < 0)
+                die_usage("invalid value '" + v + "' for '--max-distance <T>': the threshold must not be negative");
+            a.max_distance = t;
+            a.has_max_distance = true;
         } else if (arg == "--matrix" || arg.rfind("--matrix=", 0) == 0) {
             const std::string v = value_of(k, arg, "--matrix <format>");
             if (v == "tsv")
@@ -300,10 +321,22 @@ Args parse_args(int argc, char **argv)
     }
     if (a.pos_inputs.size() > 2)
         die_usage("unexpected argument '" + a.pos_inputs[2] + "' found");
+    if (a.has_max_distance) {
+        const char *other = a.has_stream ? "--stream <stream>" : a.has_nearest ? "--nearest <k>" : a.has_clusters ? "--clusters <T>"
+                            : a.matrix >= 0 ? "--matrix <format>" : a.has_tree ? "--tree <method>"
+                            : a.has_bootstrap ? "--bootstrap <B>" : a.has_mst ? "--mst"
+                            : a.dendrogram >= 0 ? "--dendrogram <linkage>" : nullptr;
+        if (other)
+            die_usage(std::string("the argument '--max-distance <T>' cannot be used with '") + other + "'");
+        if (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1))
+            die_usage(std::string("the argument '--max-distance <T>' cannot be used with '") +
+                      (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
+    }
     if (a.dendrogram >= 0) {
         // (--bootstrap and --seed: the checks below, which ask for '--tree nj')
         const char *other = a.has_stream ? "--stream <stream>" : a.has_nearest ? "--nearest <k>" : a.has_clusters ? "--clusters <T>"
-                            : a.matrix >= 0 ? "--matrix <format>" : a.has_tree ? "--tree <method>" : a.has_mst ? "--mst" : nullptr;
+                            : a.matrix >= 0 ? "--matrix <format>" : a.has_tree ? "--tree <method>" : a.has_mst ? "--mst"
+                            : a.has_max_distance ? "--max-distance <T>" : nullptr;
         if (other)
             die_usage(std::string("the argument '--dendrogram <linkage>' cannot be used with '") + other + "'");
         if (a.flag_inputs.size() + a.pos_inputs.size() > 1)
@@ -350,7 +383,7 @@ Args parse_args(int argc, char **argv)
     if (a.has_mst) {
         const char *other = a.has_stream ? "--stream <stream>" : a.has_nearest ? "--nearest <k>" : a.has_clusters ? "--clusters <T>"
                             : a.matrix >= 0 ? "--matrix <format>" : a.has_tree ? "--tree <method>"
-                            : a.has_bootstrap ? "--bootstrap <B>" : nullptr;
+                            : a.has_bootstrap ? "--bootstrap <B>" : a.has_max_distance ? "--max-distance <T>" : nullptr;
         if (other)
             die_usage(std::string("the argument '--mst' cannot be used with '") + other + "'");
         if (a.flag_inputs.size() + a.pos_inputs.size() > 1)
@@ -1314,6 +1347,55 @@ void write_mst(const Ctx &gpu, const Alignment &set, const std::vector<uint32_t>
     wr.write(out.data(), out.size());
 }
 
+// --max-distance: the lines of the full run whose pair is a link of dst_links at T, in its (the full run's) order.  The
+// sink formats one chunk of links at a time: "id_row, id_col, value" with the value's text exactly as the full run prints
+// that pair, from the link's tallies through dst_finalize, then dst_format_distance (as write_mst).
+struct LinksText {
+    const Alignment *rows, *cols;
+    const uint32_t *row_counts, *col_counts;   // tn93
+    int measure;
+    size_t W;
+    Writer *wr;
+    std::string out;
+};
+
+int links_text_sink(void *user, uint64_t, uint64_t n_links, const uint32_t *row, const uint32_t *col, const void *,
+                    const uint32_t *tallies)
+{
+    LinksText &lt = *static_cast<LinksText *>(user);
+    char num[64];
+    for (uint64_t e = 0; e < n_links; ++e) {
+        const size_t i = row[e], j = col[e];
+        double f = 0;
+        int64_t v = 0;
+        dst_finalize(lt.measure, tallies + e * lt.W, lt.row_counts ? lt.row_counts + 4 * i : nullptr,
+                     lt.col_counts ? lt.col_counts + 4 * j : nullptr, &f, &v);
+        const int len = dst_format_distance(lt.measure, f, v, num, sizeof num);
+        lt.out += lt.rows->ids[i];
+        lt.out += '\t';
+        lt.out += lt.cols->ids[j];
+        lt.out += '\t';
+        lt.out.append(num, (size_t)std::min<int>(len, (int)sizeof num - 1));
+        lt.out += '\n';
+        if (lt.out.size() >= ((size_t)1 << 20)) {
+            lt.wr->write(lt.out.data(), lt.out.size());
+            lt.out.clear();
+        }
+    }
+    return 0;
+}
+
+void write_links(const Ctx &gpu, const std::vector<Alignment> &loaded, const std::vector<std::vector<uint32_t>> &counts,
+                 int measure, double threshold, uint64_t max_pairs, Writer &wr)
+{
+    LinksText lt{&loaded[0], &loaded.back(), measure == DST_TN93 ? counts[0].data() : nullptr,
+                 measure == DST_TN93 ? counts.back().data() : nullptr, measure, (size_t)dst_tally_width(measure), &wr, {}};
+    gpu.check(dst_links(gpu.h, measure, loaded.size() == 1 ? 1 : 0, 0, 1, threshold, max_pairs, DST_LINKS_TALLIES,
+                        links_text_sink, &lt, nullptr),
+              "links");
+    wr.write(lt.out.data(), lt.out.size());
+}
+
 // a DST_ERR_STATE message "... the distance of records I and J is not finite" of the NJ calls, with the pair named by
 // its ids; false when the message names no pair of the set
 bool non_finite_pair(const Ctx &gpu, const Alignment &set, const char *prefix, const char *suffix)
@@ -1654,6 +1736,8 @@ int main(int argc, char **argv)
         write_clusters(gpus[0], loaded[0], measure, a.clusters, wr);
     } else if (a.has_mst) {
         write_mst(gpus[0], loaded[0], counts[0], measure, a.has_slab_pairs ? a.slab_pairs : 0, wr);
+    } else if (a.has_max_distance) {
+        write_links(gpus[0], loaded, counts, measure, a.max_distance, a.has_slab_pairs ? a.slab_pairs : 0, wr);
     } else if (a.has_nearest) {
         write_nearest(gpus[0], loaded, counts, measure, (uint32_t)a.nearest, wr);
     } else if (!stream_fh) {

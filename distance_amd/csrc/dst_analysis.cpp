@@ -1,5 +1,6 @@
 // dst_analysis.cpp — the analyses of the C ABI that consume a set's pairs slab by slab on the device and return an O(n)
-// or O(n k) result: dst_nearest, dst_clusters, dst_mst, dst_nj (+ _matrix, _bootstrap), dst_dendrogram (+ _matrix).
+// or O(n k) result: dst_nearest, dst_clusters, dst_mst, dst_nj (+ _matrix, _bootstrap), dst_dendrogram (+ _matrix); and
+// dst_links, which hands the pairs that pass a threshold to a sink.
 // Each one is the same program: plan the row slabs, grow the context's slab scratch, walk the slabs (the
 // pair kernel of a slab into the scratch, the analysis' kernels directly behind it), carve its O(n) state out of one
 // allocation, copy the result back.  Everything runs on the context's stream and waits before it returns.
@@ -85,6 +86,59 @@ int matrix_finite(dst_ctx *ctx, const std::string &prefix, const double *d, uint
         for (uint64_t j = i + 1; j < n; ++j)
             if (!std::isfinite(d[i * n + j]))
                 return not_finite(ctx, DST_ERR_ARG, prefix, i, j);
+    return DST_OK;
+}
+
+// The threshold of dst_clusters / dst_links as a payload: int64 payloads link when v <= floor(T) (clamped to the int64
+// range), f64 payloads on their bits through nn_key.  false: floor(T) is below -2^63, nothing links.
+bool threshold_payload(int measure, double threshold, uint64_t &t_bits)
+{
+    if (!measure_is_int(measure)) {
+        std::memcpy(&t_bits, &threshold, 8);
+        return true;
+    }
+    const double f = std::floor(threshold);
+    bool any = true;
+    int64_t t;
+    if (f >= 9223372036854775808.0)
+        t = INT64_MAX;
+    else if (f < -9223372036854775808.0) {
+        t = INT64_MIN;
+        any = false;
+    } else
+        t = (int64_t)f;
+    t_bits = (uint64_t)t;
+    return any;
+}
+
+size_t links_layout(void *base, uint64_t blocks, uint64_t chunk, bool values, int W, LinksBuffers &b)
+{
+    Carve c(base);
+    b.counts = c.take<uint32_t>(blocks);
+    b.offsets = c.take<uint64_t>(blocks + 1);
+    b.grand = c.take<uint64_t>(1);
+    b.row = c.take<uint32_t>(chunk);
+    b.col = c.take<uint32_t>(chunk);
+    b.val = c.take<uint64_t>(values ? chunk : 0);
+    b.tal = c.take<uint32_t>(chunk * (size_t)W);
+    return c.used;
+}
+
+// the page-locked host copy of one chunk of links (grow-only)
+int links_host(dst_ctx *ctx, size_t bytes)
+{
+    if (ctx->links_host_bytes >= bytes)
+        return DST_OK;
+    if (ctx->links_host)
+        HIP_TRY(ctx, hipHostFree(ctx->links_host));
+    ctx->links_host = nullptr;
+    ctx->links_host_bytes = 0;
+    if (hipHostMalloc(&ctx->links_host, bytes, hipHostMallocDefault) != hipSuccess) {
+        ctx->links_host = nullptr;
+        (void)hipGetLastError();
+        return fail(ctx, DST_ERR_NOMEM, "links: cannot allocate " + std::to_string(bytes) + " bytes of page-locked memory");
+    }
+    ctx->links_host_bytes = bytes;
     return DST_OK;
 }
 
@@ -448,24 +502,8 @@ int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs
         return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
     if (cap < n)
         return fail(ctx, DST_ERR_CAPACITY, "cap is below the set's record count");
-    // the threshold as a payload: int64 payloads link when v <= floor(T) (clamped to the int64 range); below -2^63
-    // nothing links
     uint64_t t_bits;
-    bool any = true;
-    if (measure_is_int(measure)) {
-        const double f = std::floor(threshold);
-        int64_t t;
-        if (f >= 9223372036854775808.0)
-            t = INT64_MAX;
-        else if (f < -9223372036854775808.0) {
-            t = INT64_MIN;
-            any = false;
-        } else
-            t = (int64_t)f;
-        t_bits = (uint64_t)t;
-    } else {
-        std::memcpy(&t_bits, &threshold, 8);
-    }
+    const bool any = threshold_payload(measure, threshold, t_bits);
     if (n < 2) {
         if (n == 1)
             label[0] = 0;
@@ -513,6 +551,123 @@ int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs
         *n_clusters = roots;
     if (links)
         *links = h_links;
+    return DST_OK;
+}
+
+int dst_links(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, double threshold, uint64_t max_pairs,
+              int what, dst_links_sink sink, void *user, uint64_t *n_links)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (n_links)
+        *n_links = 0;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (std::isnan(threshold))
+        return fail(ctx, DST_ERR_ARG, "threshold is NaN");
+    if (what & ~(DST_LINKS_VALUES | DST_LINKS_TALLIES))
+        return fail(ctx, DST_ERR_ARG, "unknown bits in what");
+    if (square) {
+        row_slot = 0;
+        col_slot = 0;
+    } else {
+        if (row_slot < 0 || row_slot > 1 || col_slot < 0 || col_slot > 1)
+            return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
+        if (row_slot == col_slot)
+            return fail(ctx, DST_ERR_ARG, "row_slot == col_slot: use the square form for one set");
+    }
+    DeviceSet &rows = ctx->set[row_slot], &cols = ctx->set[col_slot];
+    if (!rows.loaded || !cols.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    if (rows.len != cols.len) {
+        char msg[128];  // src/fastaio.rs:93-95
+        std::snprintf(msg, sizeof msg, "Different length sequences in alignment(s): %zu vs %zu", rows.len, cols.len);
+        return fail(ctx, DST_ERR_STATE, msg);
+    }
+    const uint64_t n_rows = rows.n, n_cols = cols.n;
+    if (n_rows >= 0xFFFFFFFFull || n_cols >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    uint64_t t_bits;
+    const bool any = threshold_payload(measure, threshold, t_bits);
+    if (!any || (square ? n_rows < 2 : (n_rows == 0 || n_cols == 0)))
+        return DST_OK;   // (nothing can link: no slab is run)
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const bool values = sink && (what & DST_LINKS_VALUES), tallies = sink && (what & DST_LINKS_TALLIES);
+    const int W = tally_width(measure);
+    int rc = DST_OK;
+    if (tallies && measure == DST_TN93) {
+        rc = need_counts(ctx, rows, stream);
+        if (!rc && &cols != &rows)
+            rc = need_counts(ctx, cols, stream);
+        if (rc)
+            return rc;
+    }
+    const int kind = tallies ? DST_OUT_TALLY : DST_OUT_DISTANCE;
+    const SlabPlan plan = plan_slabs(square != 0, n_rows, n_cols, max_pairs, kClusterSlabPairs);
+    uint64_t blocks = 0;
+    for (const RowSlab &s : plan.slabs)
+        blocks = std::max(blocks, links_blocks(square != 0, n_cols, s.rb, s.re));
+    // one window of outputs: never more links than the largest slab has pairs
+    const uint64_t chunk = sink ? std::min<uint64_t>(DST_LINKS_CHUNK, plan.biggest) : 0;
+    LinksBuffers b{};
+    rc = slab_scratch(ctx, dst_out_bytes(measure, kind, plan.biggest));
+    if (!rc)
+        rc = ensure_bytes(ctx, &ctx->links_work, &ctx->links_work_bytes,
+                          links_layout(nullptr, blocks, chunk, values, tallies ? W : 0, b));
+    // the host copy: row, col, values, tallies, each piece where the window's entries of it start
+    const size_t h_col = chunk * 4, h_val = h_col + chunk * 4, h_tal = h_val + (values ? chunk * 8 : 0);
+    if (!rc && sink)
+        rc = links_host(ctx, h_tal + (tallies ? chunk * 4 * (size_t)W : 0));
+    if (rc)
+        return rc;
+    links_layout(ctx->links_work, blocks, chunk, values, tallies ? W : 0, b);
+    char *host = static_cast<char *>(ctx->links_host);
+    HIP_TRY(ctx, hipMemsetAsync(b.grand, 0, 8, stream));
+    uint64_t total = 0;
+    // the slab, its block counts and their scan behind the pair kernel; with a sink the slab's total comes back (one wait),
+    // then every window of at most `chunk` ranks is written, copied (one wait) and handed over
+    rc = walk_slabs(ctx, measure, square != 0, rows, cols, plan.slabs, kind, [&](const RowSlab &s) -> int {
+        HIP_TRY(ctx, launch_links_count(measure, tallies, square != 0, ctx->pair_slab, s.first, n_cols, s.rb, s.re, t_bits,
+                                        rows.counts, cols.counts, b, stream));
+        if (!sink)
+            return DST_OK;
+        uint64_t in_slab = 0;
+        HIP_TRY(ctx, hipMemcpyAsync(&in_slab, b.offsets + links_blocks(square != 0, n_cols, s.rb, s.re), 8,
+                                    hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+        if (in_slab > s.pairs)
+            return fail(ctx, DST_ERR_STATE, "links: more links than pairs in a slab");
+        for (uint64_t lo = 0; lo < in_slab; lo += chunk) {
+            const uint64_t hi = std::min(in_slab, lo + chunk), m = hi - lo;
+            HIP_TRY(ctx, launch_links_write(measure, tallies, square != 0, ctx->pair_slab, s.first, n_cols, s.rb, s.re, t_bits,
+                                            rows.counts, cols.counts, b, lo, hi, values, tallies, stream));
+            HIP_TRY(ctx, hipMemcpyAsync(host, b.row, m * 4, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(ctx, hipMemcpyAsync(host + h_col, b.col, m * 4, hipMemcpyDeviceToHost, stream));
+            if (values)
+                HIP_TRY(ctx, hipMemcpyAsync(host + h_val, b.val, m * 8, hipMemcpyDeviceToHost, stream));
+            if (tallies)
+                HIP_TRY(ctx, hipMemcpyAsync(host + h_tal, b.tal, m * 4 * (size_t)W, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(ctx, hipStreamSynchronize(stream));
+            if (sink(user, total, m, reinterpret_cast<const uint32_t *>(host), reinterpret_cast<const uint32_t *>(host + h_col),
+                     values ? host + h_val : nullptr, tallies ? reinterpret_cast<const uint32_t *>(host + h_tal) : nullptr))
+                return fail(ctx, DST_ERR_STATE, "stopped by sink");
+            total += m;
+            if (n_links)
+                *n_links = total;
+        }
+        return DST_OK;
+    });
+    if (rc) {
+        (void)hipStreamSynchronize(stream);   // (a stop between two slabs leaves nothing queued on the buffers)
+        return rc;
+    }
+    if (!sink) {
+        HIP_TRY(ctx, hipMemcpyAsync(&total, b.grand, 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+    }
+    if (n_links)
+        *n_links = total;
     return DST_OK;
 }
 

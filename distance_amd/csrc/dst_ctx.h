@@ -111,6 +111,10 @@ struct dst_ctx {
     // dst_dendrogram: the O(n) state beside the per-call square (grow-only)
     void *dg_work = nullptr;
     size_t dg_work_bytes = 0;
+    // dst_links: the block counts / offsets and one chunk of outputs on the device, the same chunk in page-locked host
+    // memory (both grow-only)
+    void *links_work = nullptr, *links_host = nullptr;
+    size_t links_work_bytes = 0, links_host_bytes = 0;
     // HIP events around the pair kernel ([0]) and the pack kernel ([1]) of the most recent launches, recorded on the launch
     // stream: a ring, so that a caller timing many steps reads them ONCE at the end (dst_kernel_ms_mean) instead of
     // waiting for the device after every step

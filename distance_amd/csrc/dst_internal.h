@@ -437,6 +437,32 @@ hipError_t launch_clusters_link(int measure, const uint64_t *slab, uint64_t out_
                                 uint64_t t_bits, uint32_t *parent, unsigned long long *links, hipStream_t stream);
 hipError_t launch_clusters_final(uint32_t *parent, uint64_t n, hipStream_t stream);
 
+// ---- pairs within a threshold (dst_links.hip, driven by dst_links in dst_analysis.cpp) --------------------------------
+// Per row slab (cut as for dst_clusters; DST_OUT_DISTANCE payloads, or DST_OUT_TALLY words when the links' tallies are
+// wanted: `tally`) a count launch with dst_clusters' geometry, one count per workgroup, the workgroups numbered in canonical
+// order; a one-workgroup scan of the counts into 64-bit offsets; and per window of at most DST_LINKS_CHUNK ranks a write
+// launch that places every link of the window at its rank.  No sort: rank order is canonical pair order.
+struct LinksBuffers {
+    uint32_t *counts;     // [blocks] links per workgroup of the slab
+    uint64_t *offsets;    // [blocks + 1] their exclusive scan; the last entry: the slab's links
+    uint64_t *grand;      // the call's links so far (every scan adds its slab's)
+    uint32_t *row, *col;  // one window of links: DST_LINKS_CHUNK entries at most
+    uint64_t *val;        // their DST_OUT_DISTANCE payloads
+    uint32_t *tal;        // their DST_OUT_TALLY words
+};
+// workgroups (= counts) of the launches over rows [rb, re): rows x the 2048-entry runs of the longest row, row rb
+uint64_t links_blocks(bool square, uint64_t n_cols, uint64_t rb, uint64_t re);
+// rows [rb, re) of the slab: square, pairs (i, j > i) of n_cols records from slab entry tri_row_start(n_cols, i) - out_base;
+// else pairs (i, 0 .. n_cols-1) from (i - rb) n_cols.  t_bits: the threshold as a payload.  q_counts / t_counts: tn93's base
+// counts of the row and the column set (tally slabs only).  The count launch and the scan behind it:
+hipError_t launch_links_count(int measure, bool tally, bool square, const void *slab, uint64_t out_base, uint64_t n_cols,
+                              uint64_t rb, uint64_t re, uint64_t t_bits, const uint32_t *q_counts, const uint32_t *t_counts,
+                              const LinksBuffers &b, hipStream_t stream);
+// the links of ranks [lo, hi) of the slab into b.row / b.col (and b.val, b.tal when asked), entry rank - lo
+hipError_t launch_links_write(int measure, bool tally, bool square, const void *slab, uint64_t out_base, uint64_t n_cols,
+                              uint64_t rb, uint64_t re, uint64_t t_bits, const uint32_t *q_counts, const uint32_t *t_counts,
+                              const LinksBuffers &b, uint64_t lo, uint64_t hi, bool values, bool tallies, hipStream_t stream);
+
 // ---- minimum spanning forest (dst_mst.hip, driven by dst_mst in dst_analysis.cpp) -------------------------------------
 // Boruvka rounds: every round runs each row slab of the triangle into the DST_OUT_DISTANCE scratch (as dst_clusters) and
 // scans it twice (the minimal key of every component's outgoing edges, then the smallest pair of that key), hooks every

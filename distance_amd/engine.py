@@ -11,7 +11,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import ALLGATHER_FN, SLAB_SINK, DistanceError, LaunchInfo, load
+from ._lib import (ALLGATHER_FN, LINKS_CHUNK, LINKS_SINK, LINKS_TALLIES, LINKS_VALUES, SLAB_SINK, DistanceError, LaunchInfo,
+                   load)
 
 MEASURES = {"n": 0, "n_high": 1, "raw": 2, "jc69": 3, "k80": 4, "tn93": 5}
 INT_MEASURES = ("n", "n_high")
@@ -234,6 +235,7 @@ class Engine:
             raise DistanceError(rc, self._lib.dst_last_error(None).decode())
         self._h = h
         self.device = device
+        self.last_links_calls, self.last_links_first = [], []   # Engine.links: n_links / first_link of every sink call
 
     # ---- lifetime --------------------------------------------------------------------------
     def close(self):
@@ -456,6 +458,54 @@ class Engine:
         self._check(self._lib.dst_clusters(self._h, m, float(threshold), int(max_pairs), labels.ctypes.data, n,
                                            C.byref(n_clusters), C.byref(links)))
         return labels[:n], int(links.value)
+
+    def links(self, measure, threshold: float, square: bool = True, row_slot: int = 0, col_slot: int = 1, max_pairs: int = 0,
+              values: bool = True, tallies: bool = False, count_only: bool = False):
+        """The pairs within `threshold` (dst_links), in canonical pair order: (row uint32[n_links], col uint32[n_links]), then
+        values[n_links] (int64 / float64, bitwise run_square's / run_rect's) and tallies[n_links, width] (uint32) when asked.
+        A pair is a link by dst_clusters' rule (int measures: v <= floor(threshold); f64: IEEE v <= threshold, NaN never).
+        square: slot 0, pairs row < col; else every record of row_slot against every record of col_slot.  count_only: the
+        int n_links, nothing copied.  The arrays are copied out of the library's buffers during the sink's calls;
+        last_links_calls keeps the n_links of every call, last_links_first its first_link.  max_pairs: the most pairs of one row slab (0: the default); the
+        result does not depend on it."""
+        m = _measure_id(measure)
+        width = self._lib.dst_tally_width(m)
+        total = C.c_uint64()
+        self.last_links_calls, self.last_links_first = [], []
+        if count_only:
+            self._check(self._lib.dst_links(self._h, m, int(square), row_slot, col_slot, float(threshold), int(max_pairs), 0,
+                                            None, None, C.byref(total)))
+            return int(total.value)
+        vtype = np.int64 if m in (0, 1) else np.float64
+        parts = ([], [], [], [])
+
+        def _cb(_user, first, count, row, col, val, tal):
+            count = int(count)
+            self.last_links_calls.append(count)
+            self.last_links_first.append(int(first))
+            parts[0].append(np.ctypeslib.as_array(C.cast(row, C.POINTER(C.c_uint32)), shape=(count,)).copy())
+            parts[1].append(np.ctypeslib.as_array(C.cast(col, C.POINTER(C.c_uint32)), shape=(count,)).copy())
+            if values:
+                parts[2].append(np.ctypeslib.as_array(C.cast(val, C.POINTER(C.c_int64)), shape=(count,)).view(vtype).copy())
+            if tallies:
+                parts[3].append(np.ctypeslib.as_array(C.cast(tal, C.POINTER(C.c_uint32)), shape=(count, width)).copy())
+            return 0
+
+        cb = LINKS_SINK(_cb)
+        what = (LINKS_VALUES if values else 0) | (LINKS_TALLIES if tallies else 0)
+        self._check(self._lib.dst_links(self._h, m, int(square), row_slot, col_slot, float(threshold), int(max_pairs), what,
+                                        cb, None, C.byref(total)))
+        assert int(total.value) == sum(self.last_links_calls)
+
+        def cat(p, dtype, shape):
+            return np.concatenate(p) if p else np.zeros(shape, dtype)
+
+        out = (cat(parts[0], np.uint32, 0), cat(parts[1], np.uint32, 0))
+        if values:
+            out += (cat(parts[2], vtype, 0),)
+        if tallies:
+            out += (cat(parts[3], np.uint32, (0, width)),)
+        return out
 
     def mst(self, measure, max_pairs: int = 0, tallies: bool = False):
         """Minimum spanning forest of slot 0 (dst_mst): (edges uint32[n_edges, 2], values[n_edges], rounds), plus

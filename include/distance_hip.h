@@ -380,6 +380,51 @@ int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slo
  * in row slabs whose payloads a lock-free union-find on the device consumes.  Single GPU, loaded set only (not dst_stream). */
 int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs, uint32_t *label, size_t cap,
                  uint64_t *n_clusters, uint64_t *links);
+/* ---- pairs within a threshold ------------------------------------------------------------------ */
+/* Which pairs are within `threshold` (the edge list of a transmission network, the sparse output of a thresholded run),
+ * selected next to the values on the GPU and handed to a sink in chunks: the full result is never written.  The
+ * definition is fixed to the bit:
+ *   link    a pair whose DST_OUT_DISTANCE payload v (the value dst_run_square / dst_run_rect returns, bit-identical on
+ *           every path) satisfies dst_clusters' rule against T = threshold:
+ *             n / n_high (int64):  as real numbers, v <= floor(T) (clamped to the int64 range; below -2^63 nothing links)
+ *             f64:                 IEEE v <= T, decided on dst_nearest's sort key: NaN is never a link, -0.0 links
+ *                                  wherever +0.0 does, T = +inf links every pair whose value is not NaN
+ *           jc69 / k80 / tn93 payloads are the pair kernels' series form, within 2^-44 (jc69, k80) or 2^-42 (tn93) of the
+ *           exact value relatively, not bitwise the reference's: a pair whose value lies that close to T can be decided
+ *           differently from a CPU computation (as in dst_clusters).  raw, n and n_high are exact.
+ *   pairs   square != 0: slot 0 against itself (row_slot / col_slot ignored), the pairs i < j.
+ *           square == 0: every record of row_slot against every record of col_slot; row_slot == col_slot is DST_ERR_ARG
+ *           (use the square form), as in dst_nearest.
+ *   result  the links in canonical pair order (square: i < j row-major; rectangle: i outer, j inner): the entries of the
+ *           full result that pass the rule, nothing reordered.  It depends neither on the path nor on max_pairs.
+ * Consequences: *n_links of a square call equals dst_clusters' `links` for the same T, and the connected components of the
+ * links are dst_clusters' clusters.
+ *
+ * The sink is called on the calling thread, strictly in canonical order, each time with 1 <= n_links <= DST_LINKS_CHUNK
+ * links: a row slab with more links is delivered in several calls, a slab with none in no call.  first_link is the running
+ * index of the call's first link; row[e], col[e] are record indices (square: row[e] < col[e]); values (DST_LINKS_VALUES)
+ * are the links' DST_OUT_DISTANCE payloads, bitwise what dst_run_square / dst_run_rect gives for the pair; tallies
+ * (DST_LINKS_TALLIES) are dst_tally_width(measure) DST_OUT_TALLY words per link, the exact integers (tn93: base counts in
+ * (row, col) order), so that dst_finalize gives the reference's bits.  values / tallies are NULL unless asked for in
+ * `what`.  The buffers are library-owned page-locked memory, valid only during the call.  A non-zero return stops the run:
+ * DST_ERR_STATE, message "stopped by sink", as dst_run_slabs.  sink == NULL counts only: nothing is compacted or copied,
+ * and the known bits of `what` mean nothing.
+ *   threshold   any non-NaN double (NaN: DST_ERR_ARG)
+ *   max_pairs   0: the default slab bound (2^25 pairs); else the most pairs of one row slab, as in dst_clusters
+ *   n_links     the total, or NULL; 0 on any error before the first slab, after a stop the links delivered so far
+ * A square set of fewer than 2 records, or an empty row or column set: DST_OK, 0 links, no sink call.  A threshold below
+ * which nothing can link (n / n_high with floor(T) < -2^63) runs no slab, as dst_clusters.  DST_ERR_ARG: a NULL ctx, an
+ * unknown measure, a NaN threshold, a bad slot, equal slots with square == 0, unknown bits in `what`, a set of 2^32-1
+ * records or more.  DST_ERR_STATE: a set is not uploaded, or the widths differ (dst_nearest's message).  Synchronous on the
+ * context's stream; per row slab a count, a scan and one windowed write per DST_LINKS_CHUNK links, no sort.  Slots, the
+ * path choice and later results are untouched.  Single GPU, loaded sets only (not dst_stream). */
+#define DST_LINKS_VALUES 1  /* hand the sink the links' DST_OUT_DISTANCE payloads */
+#define DST_LINKS_TALLIES 2 /* and/or dst_tally_width(measure) DST_OUT_TALLY words per link */
+#define DST_LINKS_CHUNK (1u << 22) /* the most links of one sink call */
+typedef int (*dst_links_sink)(void *user, uint64_t first_link, uint64_t n_links, const uint32_t *row, const uint32_t *col,
+                              const void *values, const uint32_t *tallies);
+int dst_links(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, double threshold, uint64_t max_pairs,
+              int what, dst_links_sink sink, void *user, uint64_t *n_links);
 /* ---- minimum spanning tree --------------------------------------------------------------------- */
 /* The single-linkage picture for every threshold at once: the minimum spanning tree (forest) of one set (slot 0, n
  * records), as GrapeTree- and PHYLOViZ-style viewers draw it, computed next to the values on the GPU by Boruvka rounds
