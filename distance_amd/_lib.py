@@ -23,6 +23,8 @@ SLAB_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
 LINKS_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 LINKS_VALUES, LINKS_TALLIES = 1, 2
 LINKS_CHUNK = 1 << 22   # DST_LINKS_CHUNK: the most links of one sink call
+SUMMARY_SCALE_BITS = 37   # DST_SUMMARY_SCALE_BITS: f64 distances are summed as rint(v * 2^37)
+SUMMARY_MAX_BINS = 4096   # DST_SUMMARY_MAX_BINS
 
 
 class LaunchInfo(C.Structure):
@@ -32,6 +34,12 @@ class LaunchInfo(C.Structure):
                 ("tile_cols", C.c_uint32), ("tiles", C.c_uint64), ("hot", C.c_int), ("run_records", C.c_int),
                 ("variant", C.c_int), ("ksplit", C.c_uint32), ("pairs", C.c_uint64), ("events_per_pair", C.c_double),
                 ("list_length", C.c_double), ("run_adds", C.c_double)]
+
+
+class SummaryTotals(C.Structure):
+    """dst_summary_totals"""
+    _fields_ = [("pairs", C.c_uint64), ("nan_pairs", C.c_uint64), ("summable_pairs", C.c_uint64), ("links", C.c_uint64),
+                ("sum", C.c_double)]
 
 
 class DistanceError(RuntimeError):
@@ -108,6 +116,8 @@ _SIGS = {
     "dst_nearest": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, _vp, _vp, _vp, C.c_size_t, _u32p]),
     "dst_clusters": (C.c_int, [_vp, C.c_int, C.c_double, C.c_uint64, _vp, C.c_size_t, _u64p, _u64p]),
     "dst_links": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_int, _vp, _vp, _u64p]),
+    "dst_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint32, C.c_double, _vp, _vp,
+                              _vp, _vp, C.c_size_t, _vp]),
     "dst_mst": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, C.c_size_t, _u64p, _u32p]),
     "dst_nj": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, C.c_size_t]),
     "dst_nj_matrix": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_size_t]),

@@ -15,7 +15,9 @@
 // spanning tree in ascending order, one "id1, id2, value" line each: dst_mst), --dendrogram average|weighted|complete (the
 // UPGMA / WPGMA / complete-linkage dendrogram as one Newick line with a binary root: dst_dendrogram, dst_newick_rooted),
 // --max-distance T (the long output filtered on the GPU: only the lines of the pairs within T, in the full run's order:
-// dst_links).
+// dst_links), --summary T (one line per record: how many records lie within T of it, how many it was compared with and its
+// mean distance to them: dst_summary), --histogram W / --bins B (the histogram of the pairwise distances in B bins of width
+// W, one "lower edge, pairs" line per bin and a last line for the pairs without a distance: dst_summary).
 //
 // Exactness: the GPU returns integer site tallies; f64 finalisation is dst_finalize() on the host
 // (reference operation order, glibc log/sqrt), so the printed digits do not depend on the device.
@@ -118,6 +120,13 @@ void print_help()
         "      --max-distance <T>       Print only the pairs within distance T (a number >= 0, or inf): the lines of the full "
         "run whose distance is at most T, in the same order and with the same text. One or two inputs, one GPU, no --stream "
         "and no other output mode\n"
+        "      --summary <T>            Print one line per record instead of one per pair: how many records lie within distance "
+        "T (a number >= 0, or inf) of it, how many it was compared with (pairs with a distance) and its mean distance to "
+        "those. With two inputs: the records of the first against the second. One GPU, no --stream and no other output mode\n"
+        "      --histogram <W>          Print the histogram of the pairwise distances instead of the pairs: one line per bin "
+        "of width W (a number > 0; an integer with -m n / n_high), its lower edge and its pairs, the last bin open-ended, then "
+        "the pairs without a distance (NaN). One GPU, no --stream and no other output mode\n"
+        "      --bins <B>               Bins of the histogram, 1 to 4096 [default: 256]. Requires --histogram\n"
         "      --matrix <format>        Print a distance matrix instead of one line per pair: tsv (one or two inputs, rows "
         "from the first, columns from the last) or phylip (relaxed PHYLIP, one input). Not in stream, nearest or "
         "clusters mode\n"
@@ -152,6 +161,12 @@ struct Args {
     bool has_clusters = false;
     double max_distance = 0;              // --max-distance T
     bool has_max_distance = false;
+    double summary = 0;                   // --summary T
+    bool has_summary = false;
+    double histogram = 0;                 // --histogram W
+    bool has_histogram = false;
+    size_t bins = 256;                    // --bins B
+    bool has_bins = false;
     int matrix = -1;                      // --matrix: DST_MATRIX_TSV / DST_MATRIX_PHYLIP (-1: the long form)
     bool has_tree = false;                // --tree nj
     uint32_t bootstrap = 0;               // --bootstrap B (0: none)
@@ -276,6 +291,40 @@ Args parse_args(int argc, char **argv)
                 die_usage("invalid value '" + v + "' for '--max-distance <T>': the threshold must not be negative");
             a.max_distance = t;
             a.has_max_distance = true;
+        } else if (arg == "--summary" || arg.rfind("--summary=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--summary <T>");
+            if (a.has_summary)
+                die_usage("the argument '--summary <T>' cannot be used multiple times");
+            // the whole word is the number (or inf), as for --clusters <T>
+            char *end = nullptr;
+            errno = 0;
+            const double t = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
+            if (v.empty() || end != v.c_str() + v.size() || t != t || std::isspace((unsigned char)v[0]))
+                die_usage("invalid value '" + v + "' for '--summary <T>': not a number");
+            if (t < 0)
+                die_usage("invalid value '" + v + "' for '--summary <T>': the threshold must not be negative");
+            a.summary = t;
+            a.has_summary = true;
+        } else if (arg == "--histogram" || arg.rfind("--histogram=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--histogram <W>");
+            if (a.has_histogram)
+                die_usage("the argument '--histogram <W>' cannot be used multiple times");
+            char *end = nullptr;
+            errno = 0;
+            const double w = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
+            if (v.empty() || end != v.c_str() + v.size() || w != w || std::isspace((unsigned char)v[0]))
+                die_usage("invalid value '" + v + "' for '--histogram <W>': not a number");
+            // dst_summary's bounds: the width as a fixed-point value is at least one unit (2^-37) and below 2^62
+            if (!(w > 0) || !(w < 0x1p25) || std::rint(std::ldexp(w, DST_SUMMARY_SCALE_BITS)) < 1)
+                die_usage("invalid value '" + v + "' for '--histogram <W>': the bin width must be above 0 and below 2^25");
+            a.histogram = w;
+            a.has_histogram = true;
+        } else if (arg == "--bins" || arg.rfind("--bins=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--bins <B>");
+            a.bins = parse_usize(v, "--bins <B>");
+            if (a.bins < 1 || a.bins > DST_SUMMARY_MAX_BINS)
+                die_usage("invalid value '" + v + "' for '--bins <B>': " + v + " is not in 1..=4096");
+            a.has_bins = true;
         } else if (arg == "--matrix" || arg.rfind("--matrix=", 0) == 0) {
             const std::string v = value_of(k, arg, "--matrix <format>");
             if (v == "tsv")
@@ -321,6 +370,23 @@ Args parse_args(int argc, char **argv)
     }
     if (a.pos_inputs.size() > 2)
         die_usage("unexpected argument '" + a.pos_inputs[2] + "' found");
+    for (int mode = 0; mode < 2; ++mode) {   // --summary, then --histogram: each against everything else
+        if (!(mode == 0 ? a.has_summary : a.has_histogram))
+            continue;
+        const std::string self = mode == 0 ? "--summary <T>" : "--histogram <W>";
+        const char *other = a.has_stream ? "--stream <stream>" : a.has_nearest ? "--nearest <k>" : a.has_clusters ? "--clusters <T>"
+                            : a.matrix >= 0 ? "--matrix <format>" : a.has_tree ? "--tree <method>"
+                            : a.has_bootstrap ? "--bootstrap <B>" : a.has_mst ? "--mst"
+                            : a.dendrogram >= 0 ? "--dendrogram <linkage>" : a.has_max_distance ? "--max-distance <T>"
+                            : mode == 0 && a.has_histogram ? "--histogram <W>" : nullptr;
+        if (other)
+            die_usage("the argument '" + self + "' cannot be used with '" + other + "'");
+        if (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1))
+            die_usage("the argument '" + self + "' cannot be used with '" +
+                      (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
+    }
+    if (a.has_bins && !a.has_histogram)
+        die_usage("the argument '--bins <B>' requires '--histogram <W>'");
     if (a.has_max_distance) {
         const char *other = a.has_stream ? "--stream <stream>" : a.has_nearest ? "--nearest <k>" : a.has_clusters ? "--clusters <T>"
                             : a.matrix >= 0 ? "--matrix <format>" : a.has_tree ? "--tree <method>"
@@ -399,6 +465,8 @@ Args parse_args(int argc, char **argv)
     if (dst_measure_from_name(a.measure.c_str()) < 0)
         die_usage("invalid value '" + a.measure + "' for '--measure <measure>'\n  [possible values: n, n_high, raw, "
                   "jc69, k80, tn93]");
+    if (a.has_histogram && dst_measure_from_name(a.measure.c_str()) <= DST_N_HIGH && a.histogram != std::floor(a.histogram))
+        die_usage("invalid value for '--histogram <W>': the bin width must be an integer with '--measure " + a.measure + "'");
     return a;
 }
 
@@ -1396,6 +1464,66 @@ void write_links(const Ctx &gpu, const std::vector<Alignment> &loaded, const std
     wr.write(lt.out.data(), lt.out.size());
 }
 
+// --summary: one line per record of the first input in input order, "id, within, compared, mean" from dst_summary: the
+// records within T, the partners with a summable distance, and sum / compared printed as an f64 distance (NaN: none)
+void write_summary(const Ctx &gpu, const std::vector<Alignment> &loaded, int measure, double threshold, uint64_t max_pairs,
+                   Writer &wr)
+{
+    const Alignment &set = loaded[0];
+    const size_t cap = std::max<size_t>(set.n, 1);
+    std::vector<uint32_t> within(cap), summable(cap);
+    std::vector<double> sum(cap);
+    gpu.check(dst_summary(gpu.h, measure, loaded.size() == 1 ? 1 : 0, 0, 1, threshold, max_pairs, 0, 0.0, nullptr, within.data(),
+                          summable.data(), sum.data(), set.n, nullptr),
+              "summary");
+    static const char header[] = "sequence\twithin\tcompared\tmean\n";
+    wr.write(header, sizeof header - 1);
+    std::string out;
+    char num[64];
+    for (size_t i = 0; i < set.n; ++i) {
+        const double mean = summable[i] ? sum[i] / (double)summable[i] : std::nan("");
+        const int len = dst_format_distance(DST_RAW, mean, 0, num, sizeof num);
+        out += set.ids[i];
+        out += '\t';
+        out += std::to_string(within[i]);
+        out += '\t';
+        out += std::to_string(summable[i]);
+        out += '\t';
+        out.append(num, (size_t)std::min<int>(len, (int)sizeof num - 1));
+        out += '\n';
+        if (out.size() >= ((size_t)1 << 20)) {
+            wr.write(out.data(), out.size());
+            out.clear();
+        }
+    }
+    wr.write(out.data(), out.size());
+}
+
+// --histogram: one line per bin, "lower edge, pairs" (the edge b W as the measure's distances are printed; the last bin is
+// open-ended), then "NaN, pairs without a distance"
+void write_histogram(const Ctx &gpu, const std::vector<Alignment> &loaded, int measure, double width, uint32_t bins,
+                     uint64_t max_pairs, Writer &wr)
+{
+    std::vector<uint64_t> hist(bins);
+    dst_summary_totals totals;
+    gpu.check(dst_summary(gpu.h, measure, loaded.size() == 1 ? 1 : 0, 0, 1, 0.0, max_pairs, bins, width, hist.data(), nullptr,
+                          nullptr, nullptr, 0, &totals),
+              "histogram");
+    static const char header[] = "distance\tpairs\n";
+    wr.write(header, sizeof header - 1);
+    std::string out;
+    char num[64];
+    for (uint32_t b = 0; b < bins; ++b) {
+        const int len = dst_format_distance(measure, (double)b * width, (int64_t)b * (int64_t)width, num, sizeof num);
+        out.append(num, (size_t)std::min<int>(len, (int)sizeof num - 1));
+        out += '\t';
+        out += std::to_string(hist[b]);
+        out += '\n';
+    }
+    out += "NaN\t" + std::to_string(totals.nan_pairs) + "\n";
+    wr.write(out.data(), out.size());
+}
+
 // a DST_ERR_STATE message "... the distance of records I and J is not finite" of the NJ calls, with the pair named by
 // its ids; false when the message names no pair of the set
 bool non_finite_pair(const Ctx &gpu, const Alignment &set, const char *prefix, const char *suffix)
@@ -1721,7 +1849,7 @@ int main(int argc, char **argv)
     } else if (a.matrix == DST_MATRIX_PHYLIP) {
         const std::string h = std::to_string(loaded[0].n) + "\n";
         wr.write(h.data(), h.size());
-    } else if (!a.has_clusters && !a.has_tree && a.dendrogram < 0) {
+    } else if (!a.has_clusters && !a.has_tree && a.dendrogram < 0 && !a.has_summary && !a.has_histogram) {
         wr.write(header, sizeof header - 1);
     }
 
@@ -1738,6 +1866,10 @@ int main(int argc, char **argv)
         write_mst(gpus[0], loaded[0], counts[0], measure, a.has_slab_pairs ? a.slab_pairs : 0, wr);
     } else if (a.has_max_distance) {
         write_links(gpus[0], loaded, counts, measure, a.max_distance, a.has_slab_pairs ? a.slab_pairs : 0, wr);
+    } else if (a.has_summary) {
+        write_summary(gpus[0], loaded, measure, a.summary, a.has_slab_pairs ? a.slab_pairs : 0, wr);
+    } else if (a.has_histogram) {
+        write_histogram(gpus[0], loaded, measure, a.histogram, (uint32_t)a.bins, a.has_slab_pairs ? a.slab_pairs : 0, wr);
     } else if (a.has_nearest) {
         write_nearest(gpus[0], loaded, counts, measure, (uint32_t)a.nearest, wr);
     } else if (!stream_fh) {

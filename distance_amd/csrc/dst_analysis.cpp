@@ -1,6 +1,6 @@
 // dst_analysis.cpp — the analyses of the C ABI that consume a set's pairs slab by slab on the device and return an O(n)
-// or O(n k) result: dst_nearest, dst_clusters, dst_mst, dst_nj (+ _matrix, _bootstrap), dst_dendrogram (+ _matrix); and
-// dst_links, which hands the pairs that pass a threshold to a sink.
+// or O(n k) result: dst_nearest, dst_clusters, dst_mst, dst_nj (+ _matrix, _bootstrap), dst_dendrogram (+ _matrix),
+// dst_summary; and dst_links, which hands the pairs that pass a threshold to a sink.
 // Each one is the same program: plan the row slabs, grow the context's slab scratch, walk the slabs (the
 // pair kernel of a slab into the scratch, the analysis' kernels directly behind it), carve its O(n) state out of one
 // allocation, copy the result back.  Everything runs on the context's stream and waits before it returns.
@@ -140,6 +140,26 @@ int links_host(dst_ctx *ctx, size_t bytes)
     }
     ctx->links_host_bytes = bytes;
     return DST_OK;
+}
+
+size_t summary_layout(void *base, uint64_t records, uint32_t bins, SummaryBuffers &b)
+{
+    Carve c(base);
+    b.within = c.take<uint32_t>(records);
+    b.summable = c.take<uint32_t>(records);
+    b.hi = c.take<int64_t>(records);
+    b.lo = c.take<uint64_t>(records);
+    b.hist = c.take<uint64_t>(bins);
+    b.tot = c.take<uint64_t>(kSummaryTotals);
+    return c.used;
+}
+
+// dst_summary's conversion: the exact sum hi 2^32 + lo to double once (round to nearest even), f64 measures scaled by
+// 2^-DST_SUMMARY_SCALE_BITS (exact)
+double summary_value(__int128 s, bool int_payload)
+{
+    const double d = (double)s;
+    return int_payload ? d : std::ldexp(d, -DST_SUMMARY_SCALE_BITS);
 }
 
 size_t nearest_layout(void *base, uint64_t entries, int W, NearestLists &nl)
@@ -668,6 +688,152 @@ int dst_links(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
     }
     if (n_links)
         *n_links = total;
+    return DST_OK;
+}
+
+int dst_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, double threshold, uint64_t max_pairs,
+                uint32_t bins, double width, uint64_t *hist, uint32_t *within, uint32_t *summable, double *sum, size_t cap,
+                dst_summary_totals *totals)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (totals)
+        *totals = dst_summary_totals{0, 0, 0, 0, 0.0};
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (std::isnan(threshold))
+        return fail(ctx, DST_ERR_ARG, "threshold is NaN");
+    const bool int_payload = measure_is_int(measure);
+    uint64_t width_q = 0;
+    if (bins) {
+        if (bins > DST_SUMMARY_MAX_BINS)
+            return fail(ctx, DST_ERR_ARG, "bins must be between 0 and 4096");
+        if (!hist)
+            return fail(ctx, DST_ERR_ARG, "null hist pointer");
+        if (!(width > 0 && width < 0x1p25))   // (NaN fails both)
+            return fail(ctx, DST_ERR_ARG, "width must be finite, above 0 and below 2^25");
+        if (int_payload && width != std::floor(width))
+            return fail(ctx, DST_ERR_ARG, "width must be an integer for n and n_high");
+        width_q = int_payload ? (uint64_t)width : (uint64_t)std::llrint(std::ldexp(width, DST_SUMMARY_SCALE_BITS));
+        if (width_q < 1)
+            return fail(ctx, DST_ERR_ARG, "width is below one unit of the fixed-point scale");
+    }
+    if (square) {
+        row_slot = 0;
+        col_slot = 0;
+    } else {
+        if (row_slot < 0 || row_slot > 1 || col_slot < 0 || col_slot > 1)
+            return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
+        if (row_slot == col_slot)
+            return fail(ctx, DST_ERR_ARG, "row_slot == col_slot: use the square form for one set");
+    }
+    DeviceSet &rows = ctx->set[row_slot], &cols = ctx->set[col_slot];
+    if (!rows.loaded || !cols.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    if (rows.len != cols.len) {
+        char msg[128];  // src/fastaio.rs:93-95
+        std::snprintf(msg, sizeof msg, "Different length sequences in alignment(s): %zu vs %zu", rows.len, cols.len);
+        return fail(ctx, DST_ERR_STATE, msg);
+    }
+    const uint64_t n_rows = rows.n, n_cols = cols.n;
+    if (n_rows >= 0xFFFFFFFFull || n_cols >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    const bool per_record = within || summable || sum;
+    if (per_record && cap < n_rows)
+        return fail(ctx, DST_ERR_CAPACITY, "cap is below the row set's record count");
+    for (uint64_t x = 0; x < n_rows; ++x) {   // (also what an empty call returns)
+        if (within)
+            within[x] = 0;
+        if (summable)
+            summable[x] = 0;
+        if (sum)
+            sum[x] = 0.0;
+    }
+    for (uint32_t k = 0; k < bins; ++k)
+        hist[k] = 0;
+    if (square ? n_rows < 2 : (n_rows == 0 || n_cols == 0))
+        return DST_OK;   // (no pair: no slab is run)
+    const uint64_t pairs = square ? n_rows * (n_rows - 1) / 2 : n_rows * n_cols;
+    // the flat pass counts the totals as it goes, so it also serves a call that wants the totals and no per-record array
+    const bool flat = bins > 0 || (totals && !per_record);
+    if (!per_record && !flat)
+        return DST_OK;   // (nothing is asked for)
+    uint64_t t_bits;
+    const bool any = threshold_payload(measure, threshold, t_bits);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const SlabPlan plan = plan_slabs(square != 0, n_rows, n_cols, max_pairs, kClusterSlabPairs);
+    SummaryBuffers b{};
+    const size_t state_bytes = summary_layout(nullptr, n_rows, bins, b);
+    int rc = slab_scratch(ctx, dst_out_bytes(measure, DST_OUT_DISTANCE, plan.biggest));
+    if (!rc)
+        rc = ensure_bytes(ctx, &ctx->summary_work, &ctx->summary_work_bytes, state_bytes);
+    if (rc)
+        return rc;
+    summary_layout(ctx->summary_work, n_rows, bins, b);
+    static const bool no_aggregation = std::getenv("DST_SUMMARY_NO_AGGREGATION") != nullptr;   // measurement knob
+    HIP_TRY(ctx, hipMemsetAsync(ctx->summary_work, 0, state_bytes, stream));
+    const uint64_t *slab = static_cast<const uint64_t *>(ctx->pair_slab);
+    // the slab's DST_OUT_DISTANCE payloads, then the wanted passes behind its pair kernel
+    rc = walk_slabs(ctx, measure, square != 0, rows, cols, plan.slabs, DST_OUT_DISTANCE, [&](const RowSlab &s) -> int {
+        if (per_record) {
+            HIP_TRY(ctx, launch_summary_rows(measure, square != 0, slab, s.first, n_cols, s.rb, s.re, t_bits, any, b, stream));
+            if (square)
+                HIP_TRY(ctx, launch_summary_cols(measure, slab, s.first, n_cols, s.rb, s.re, t_bits, any, b, stream));
+        }
+        if (flat)
+            HIP_TRY(ctx, launch_summary_hist(measure, slab, s.pairs, bins, width_q, t_bits, any, !no_aggregation, b, stream));
+        return DST_OK;
+    });
+    if (rc)
+        return rc;
+    // the state back in one copy, then the 128-bit sums here
+    std::vector<char> host(state_bytes);
+    HIP_TRY(ctx, hipMemcpyAsync(host.data(), ctx->summary_work, state_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    SummaryBuffers h{};
+    summary_layout(host.data(), n_rows, bins, h);
+    for (uint32_t k = 0; k < bins; ++k)
+        hist[k] = h.hist[k];
+    dst_summary_totals t{pairs, 0, 0, 0, 0.0};
+    __int128 all = 0;
+    if (flat) {
+        t.nan_pairs = h.tot[0];
+        t.summable_pairs = h.tot[1];
+        t.links = h.tot[2];
+        all = (__int128)(((unsigned __int128)h.tot[3] << 64) | h.tot[4]);   // (the flat pass' 128-bit total: high word, low word)
+    }
+    if (per_record) {
+        // the totals from the records' entries too: every pair once in a rectangle, twice in the square
+        uint64_t w2 = 0, s2 = 0;
+        __int128 all2 = 0;
+        for (uint64_t x = 0; x < n_rows; ++x) {
+            const __int128 S = (__int128)h.hi[x] * ((__int128)1 << 32) + (__int128)h.lo[x];
+            if (within)
+                within[x] = h.within[x];
+            if (summable)
+                summable[x] = h.summable[x];
+            if (sum)
+                sum[x] = summary_value(S, int_payload);
+            w2 += h.within[x];
+            s2 += h.summable[x];
+            all2 += S;
+        }
+        const unsigned each = square ? 2 : 1;
+        if (w2 % each || s2 % each || all2 % each)
+            return fail(ctx, DST_ERR_STATE, "summary: internal error, the two sides of the square disagree");
+        if (flat && (t.links != w2 / each || t.summable_pairs != s2 / each || all != all2 / each || t.nan_pairs != h.tot[5]))
+            return fail(ctx, DST_ERR_STATE, "summary: internal error, the passes disagree");
+        if (!flat) {
+            t.links = w2 / each;
+            t.summable_pairs = s2 / each;
+            all = all2 / each;
+            t.nan_pairs = h.tot[5];
+        }
+    }
+    t.sum = summary_value(all, int_payload);
+    if (totals)
+        *totals = t;
     return DST_OK;
 }
 

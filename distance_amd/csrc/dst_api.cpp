@@ -1282,7 +1282,7 @@ int dst_destroy(dst_ctx *ctx)
     for (void *b : {(void *)ctx->d_lut, (void *)ctx->d_total, (void *)ctx->scan_tmp, ctx->host_out, ctx->hot_tally, ctx->text_res,
                     ctx->text_num, (void *)ctx->text_len, (void *)ctx->text_scan, (void *)ctx->text_buf, (void *)ctx->text_flag, ctx->text_ties,
                     (void *)ctx->ids[0].off, (void *)ctx->ids[0].chars, (void *)ctx->ids[1].off, (void *)ctx->ids[1].chars, ctx->pair_slab, ctx->nn_lists,
-                    ctx->cl_work, ctx->mst_work, ctx->dg_work, ctx->links_work})
+                    ctx->cl_work, ctx->mst_work, ctx->dg_work, ctx->links_work, ctx->summary_work})
         if (b)
             (void)hipFree(b);
     if (ctx->links_host)

@@ -115,6 +115,9 @@ struct dst_ctx {
     // memory (both grow-only)
     void *links_work = nullptr, *links_host = nullptr;
     size_t links_work_bytes = 0, links_host_bytes = 0;
+    // dst_summary: the per-record counters and accumulators, the histogram and the totals (grow-only)
+    void *summary_work = nullptr;
+    size_t summary_work_bytes = 0;
     // HIP events around the pair kernel ([0]) and the pack kernel ([1]) of the most recent launches, recorded on the launch
     // stream: a ring, so that a caller timing many steps reads them ONCE at the end (dst_kernel_ms_mean) instead of
     // waiting for the device after every step

@@ -463,6 +463,34 @@ hipError_t launch_links_write(int measure, bool tally, bool square, const void *
                               uint64_t rb, uint64_t re, uint64_t t_bits, const uint32_t *q_counts, const uint32_t *t_counts,
                               const LinksBuffers &b, uint64_t lo, uint64_t hi, bool values, bool tallies, hipStream_t stream);
 
+// ---- per-record and histogram summaries (dst_summary.hip, driven by dst_summary in dst_analysis.cpp) -------------------
+// Per row slab of DST_OUT_DISTANCE payloads (cut as for dst_clusters) up to three launches, each wanted or not: the row pass
+// (dst_clusters' geometry, one set of atomics per workgroup to its row's record), the column pass (square only: thread =
+// column record, the slab's rows in segments) and the flat histogram pass, which also counts the call's totals.  All state is
+// integer: per record two 32-bit counters and the exact sum of the fixed-point values as hi = sum of (q >> 32), lo = sum of
+// (q & 0xFFFFFFFF), so the result does not depend on the order anything arrives in.
+constexpr int kSummaryTotals = 6;   // tot[]: NaN pairs, summable pairs, links, the high and the low word of the 128-bit sum
+                                    // over pairs (the histogram pass); [5] NaN pairs again, by the row pass
+struct SummaryBuffers {
+    uint32_t *within;     // [records] links of the record
+    uint32_t *summable;   // [records] its summable partners
+    int64_t *hi;          // [records] sum of (q >> 32) over them
+    uint64_t *lo;         // [records] sum of (q & 0xFFFFFFFF)
+    uint64_t *hist;       // [bins]
+    uint64_t *tot;        // [kSummaryTotals]
+};
+// rows [rb, re) of the slab, indexed as launch_links_count's; t_bits: the threshold as a payload, any: false when nothing
+// can link (threshold_payload)
+hipError_t launch_summary_rows(int measure, bool square, const uint64_t *slab, uint64_t out_base, uint64_t n_cols, uint64_t rb,
+                               uint64_t re, uint64_t t_bits, bool any, const SummaryBuffers &b, hipStream_t stream);
+// the same rows of the square, pairs (i, j > i), added to record j
+hipError_t launch_summary_cols(int measure, const uint64_t *slab, uint64_t out_base, uint64_t n, uint64_t rb, uint64_t re,
+                               uint64_t t_bits, bool any, const SummaryBuffers &b, hipStream_t stream);
+// entries [0, pairs) of the slab into b.hist (bins == 0: none) and b.tot; width_q: the bin width as a fixed-point value;
+// aggregate: lanes of a wave that share a bin add once (false: the measurement's other side)
+hipError_t launch_summary_hist(int measure, const uint64_t *slab, uint64_t pairs, uint32_t bins, uint64_t width_q,
+                               uint64_t t_bits, bool any, bool aggregate, const SummaryBuffers &b, hipStream_t stream);
+
 // ---- minimum spanning forest (dst_mst.hip, driven by dst_mst in dst_analysis.cpp) -------------------------------------
 // Boruvka rounds: every round runs each row slab of the triangle into the DST_OUT_DISTANCE scratch (as dst_clusters) and
 // scans it twice (the minimal key of every component's outgoing edges, then the smallest pair of that key), hooks every

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (ALLGATHER_FN, LINKS_CHUNK, LINKS_SINK, LINKS_TALLIES, LINKS_VALUES, SLAB_SINK, DistanceError, LaunchInfo,
-                   load)
+                   SummaryTotals, load)
 
 MEASURES = {"n": 0, "n_high": 1, "raw": 2, "jc69": 3, "k80": 4, "tn93": 5}
 INT_MEASURES = ("n", "n_high")
@@ -505,6 +505,38 @@ class Engine:
             out += (cat(parts[2], vtype, 0),)
         if tallies:
             out += (cat(parts[3], np.uint32, (0, width)),)
+        return out
+
+    def summary(self, measure, threshold: float = 0.0, square: bool = True, row_slot: int = 0, col_slot: int = 1,
+                max_pairs: int = 0, bins: int = 0, width: float = 1.0, per_record: bool = True) -> dict:
+        """Per-record and histogram summaries of the pairwise distances (dst_summary), a dict: `within` (uint32[n_rows], the
+        partners within `threshold` by dst_clusters' rule), `summable` (uint32[n_rows], the partners whose value is not
+        NaN and below 2^25) and `sum` (float64[n_rows], the exact fixed-point sum of their values, rounded once) unless
+        per_record is False; `hist` (uint64[bins], bin b = values in [b width, (b + 1) width), the last bin open-ended,
+        NaN in none) when bins > 0; and the totals `pairs`, `nan_pairs`, `summable_pairs`, `links`, `total_sum`, every pair once.
+        square: slot 0, every pair counts for both of its records; else the records of row_slot against those of col_slot.
+        max_pairs: the most pairs of one row slab (0: the default); the result does not depend on it."""
+        m = _measure_id(measure)
+        n_rows, _ = self.set_info(0 if square else row_slot)
+        bins = int(bins)
+        cap = max(n_rows, 1)
+        within = np.zeros(cap, np.uint32) if per_record else None
+        summable = np.zeros(cap, np.uint32) if per_record else None
+        sums = np.zeros(cap, np.float64) if per_record else None
+        hist = np.zeros(max(bins, 1), np.uint64) if bins else None
+        tot = SummaryTotals()
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data
+
+        self._check(self._lib.dst_summary(self._h, m, int(square), row_slot, col_slot, float(threshold), int(max_pairs), bins,
+                                          float(width), ptr(hist), ptr(within), ptr(summable), ptr(sums), n_rows, C.byref(tot)))
+        out = {"pairs": int(tot.pairs), "nan_pairs": int(tot.nan_pairs), "summable_pairs": int(tot.summable_pairs),
+               "links": int(tot.links), "total_sum": float(tot.sum)}
+        if per_record:
+            out.update(within=within[:n_rows], summable=summable[:n_rows], sum=sums[:n_rows])
+        if bins:
+            out["hist"] = hist[:bins]
         return out
 
     def mst(self, measure, max_pairs: int = 0, tallies: bool = False):

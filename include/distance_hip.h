@@ -425,6 +425,61 @@ typedef int (*dst_links_sink)(void *user, uint64_t first_link, uint64_t n_links,
                               const void *values, const uint32_t *tallies);
 int dst_links(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, double threshold, uint64_t max_pairs,
               int what, dst_links_sink sink, void *user, uint64_t *n_links);
+/* ---- per-record and histogram summaries ---------------------------------------------------------- */
+/* What the distances of a set look like, computed next to the values on the GPU: the histogram of the pairwise distances
+ * (from which a threshold is chosen) and, per record, how many records lie within `threshold` of it (its degree in the
+ * dst_links network) and the sum of its distances to the rest (mean distance: outliers, the medoid; averaged over the
+ * records with raw, the nucleotide diversity).  O(n + bins) of state, the full result is never written.  The definition
+ * is fixed to the bit, and every accumulation is an integer one, so the result depends neither on the path, nor on
+ * max_pairs, nor on the order the pairs are met in.
+ *   pairs   as in dst_links.  square != 0: slot 0 against itself (row_slot / col_slot ignored), the pairs i < j; a pair
+ *           counts for both of its records in the per-record results and once in the histogram and the totals.
+ *           square == 0: every record of row_slot against every record of col_slot, per-record results for the row
+ *           records only; row_slot == col_slot is DST_ERR_ARG (use the square form), as in dst_nearest.
+ * Per pair, from its DST_OUT_DISTANCE payload v (the value dst_run_square / dst_run_rect returns, bit-identical on every
+ * path):
+ *   link      dst_clusters' rule against T = threshold: n / n_high v <= floor(T) (clamped to the int64 range; below -2^63
+ *             nothing links); f64 IEEE v <= T on dst_nearest's sort key: NaN never links, -0.0 links wherever +0.0 does
+ *   q         the fixed-point value, a signed 64-bit integer.  n / n_high: q = v, always "summable".  f64 measures:
+ *             q = rint(v * 2^DST_SUMMARY_SCALE_BITS), round to nearest even (the product is exact), defined only when v
+ *             is summable: not NaN and |v| < 2^25 (no distance reaches 2^25)
+ *   bin       (bins > 0) with width_q = rint(width * 2^DST_SUMMARY_SCALE_BITS) for f64 measures, (int64)width for
+ *             n / n_high: NaN lies in no bin (it is counted in nan_pairs); v >= 2^25, +inf included, in bin bins - 1;
+ *             v <= -2^25 in bin 0; any other value in bin clamp(floor(q / width_q), 0, bins - 1), the integer floor quotient
+ * Per record x over its partners (each array may be NULL: not wanted):
+ *   within[x]    the partners whose pair is a link
+ *   summable[x]  the partners whose pair is summable
+ *   sum[x]       S = the sum of q over the summable partners, an exact integer, converted to double once (round to nearest
+ *                even) and, for f64 measures, scaled by 2^-DST_SUMMARY_SCALE_BITS (exact).  It misses the real sum of the
+ *                payloads by at most summable[x] * 2^-(DST_SUMMARY_SCALE_BITS + 1), plus the one rounding.
+ * totals (may be NULL): pairs; nan_pairs (payload NaN); summable_pairs; links; sum, the same conversion of the exact sum
+ * over the pairs, each once.  hist[b] (bins entries): the pairs in bin b; their sum is pairs - nan_pairs.
+ * Consequences: `links` of a square call equals dst_clusters' `links` and dst_links' count for the same T; within[x] is the
+ * number of dst_links entries that name x.
+ *   threshold   any non-NaN double (NaN: DST_ERR_ARG)
+ *   max_pairs   0: the default slab bound (2^25 pairs); else the most pairs of one row slab, as in dst_clusters
+ *   bins        0: no histogram (hist, width ignored); else 1 .. DST_SUMMARY_MAX_BINS with a non-NULL hist and a width
+ *               that is finite, > 0 and < 2^25 with width_q >= 1; for n / n_high an integer value >= 1.  Else DST_ERR_ARG.
+ *   cap         the room of each non-NULL per-record array in entries; below the row set's record count DST_ERR_CAPACITY
+ * A square set of fewer than 2 records, or an empty row or column set: DST_OK, zero totals, a zero histogram, zero
+ * per-record entries, no slab run.  DST_ERR_ARG: a NULL ctx, an unknown measure, a NaN threshold, a bad slot, equal slots
+ * with square == 0, a set of 2^32-1 records or more; DST_ERR_STATE: a set is not uploaded, or the widths differ
+ * (dst_nearest's message) - dst_links' checks and messages.  Synchronous on the context's stream: per row slab a row pass
+ * and (square) a column pass when a per-record array is wanted, a histogram pass when bins > 0 or only the totals are
+ * wanted; one copy back.  Slots, the path choice and later results are untouched.  Single GPU, loaded sets only (not
+ * dst_stream). */
+#define DST_SUMMARY_SCALE_BITS 37
+#define DST_SUMMARY_MAX_BINS 4096
+typedef struct dst_summary_totals {
+    uint64_t pairs;
+    uint64_t nan_pairs;
+    uint64_t summable_pairs;
+    uint64_t links;
+    double sum;
+} dst_summary_totals;
+int dst_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, double threshold, uint64_t max_pairs,
+                uint32_t bins, double width, uint64_t *hist, uint32_t *within, uint32_t *summable, double *sum, size_t cap,
+                dst_summary_totals *totals);
 /* ---- minimum spanning tree --------------------------------------------------------------------- */
 /* The single-linkage picture for every threshold at once: the minimum spanning tree (forest) of one set (slot 0, n
  * records), as GrapeTree- and PHYLOViZ-style viewers draw it, computed next to the values on the GPU by Boruvka rounds
