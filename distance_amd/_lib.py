@@ -103,6 +103,10 @@ _SIGS = {
     "dst_stream_collect": (C.c_int, [_vp, C.POINTER(C.c_size_t), C.POINTER(_vp)]),
     "dst_stream_in_flight": (C.c_int, [_vp]),
     "dst_stream_close": (C.c_int, [_vp]),
+    "dst_stream_open_closest": (C.c_int, [_vp, C.c_int, C.c_uint32, C.c_int, C.c_size_t, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "dst_stream_closest_next_index": (C.c_int, [_vp, C.c_uint64]),
+    "dst_stream_closest_result": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _u32p]),
+    "dst_stream_closest_batch": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _u32p]),
     "dst_comm_unique_id": (C.c_int, [_vp, C.c_size_t]),
     "dst_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "dst_comm_create_custom": (C.c_int, [_vp, C.c_int, C.c_int, ALLGATHER_FN, _vp, C.POINTER(_vp)]),

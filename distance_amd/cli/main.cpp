@@ -7,7 +7,8 @@
 // (src/lib.rs:612-644).  The pair generators and worker pools (src/lib.rs:269-474, 502-596) are
 // replaced by libdistance_hip.so through its C ABI; -t sizes the host formatting pool and -b is
 // accepted — neither changes the output, as in the reference (src/lib.rs:919-1154).
-// Extra flags: --gpus N (default 1) / --devices LIST, --slab-pairs P (result slab size), --nearest K (the K nearest records
+// Extra flags: --gpus N (default 1) / --devices LIST, --slab-pairs P (result slab size), --closest K [--closest-for SIDE]
+// (stream mode: the K closest records only, dst_stream_open_closest), --nearest K (the K nearest records
 // of every record instead of every pair: dst_nearest), --clusters T (single-linkage clusters at threshold T: dst_clusters),
 // --matrix tsv|phylip (a square or rectangular distance matrix instead of the long form: dst_text_matrix), --tree nj (the
 // neighbour-joining tree as one Newick line: dst_nj, dst_newick), --bootstrap B / --seed S (the tree's splits labelled
@@ -114,6 +115,11 @@ void print_help()
         "      --devices <list>         Explicit device ordinals, e.g. 0,1,2,3 (overrides --gpus)\n"
         "      --nearest <k>            Print only the k (1-256) nearest records of every record: of the same file with one "
         "input, of the second file with two. One GPU, no --stream\n"
+        "      --closest <k>            Stream mode only: print only the k (1-256) closest records instead of every pair, "
+        "each as the line the full run prints for that pair. Requires --stream, one loaded file, one GPU, no other output mode\n"
+        "      --closest-for <side>     Whose closest records --closest prints: loaded (for every loaded record its k closest "
+        "streamed records, written when the stream ends) or streamed (for every streamed record its k closest loaded "
+        "records, in stream order) [default: loaded]\n"
         "      --clusters <T>           Print the single-linkage cluster of every record instead of distances: records "
         "within distance T (a number >= 0) of each other share a cluster, numbered from 1 in order of first record. One "
         "input, one GPU, no --stream or --nearest\n"
@@ -157,6 +163,9 @@ struct Args {
     size_t slab_pairs = (size_t)1 << 22;  // result slab: 4 Mi pairs pipelines GPU, formatters and writer well
     size_t nearest = 0;                   // --nearest k (0: every pair)
     bool has_nearest = false;
+    size_t closest = 0;                   // --closest k (stream mode)
+    bool has_closest = false, has_closest_for = false;
+    int closest_side = DST_CLOSEST_FOR_LOADED;   // --closest-for loaded|streamed
     double clusters = 0;                  // --clusters T
     bool has_clusters = false;
     double max_distance = 0;              // --max-distance T
@@ -265,6 +274,21 @@ Args parse_args(int argc, char **argv)
             if (a.nearest < 1 || a.nearest > 256)
                 die_usage("invalid value '" + v + "' for '--nearest <k>': " + v + " is not in 1..=256");
             a.has_nearest = true;
+        } else if (arg == "--closest" || arg.rfind("--closest=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--closest <k>");
+            a.closest = parse_usize(v, "--closest <k>");
+            if (a.closest < 1 || a.closest > 256)
+                die_usage("invalid value '" + v + "' for '--closest <k>': " + v + " is not in 1..=256");
+            a.has_closest = true;
+        } else if (arg == "--closest-for" || arg.rfind("--closest-for=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--closest-for <side>");
+            if (v == "loaded")
+                a.closest_side = DST_CLOSEST_FOR_LOADED;
+            else if (v == "streamed")
+                a.closest_side = DST_CLOSEST_FOR_STREAMED;
+            else
+                die_usage("invalid value '" + v + "' for '--closest-for <side>'\n  [possible values: loaded, streamed]");
+            a.has_closest_for = true;
         } else if (arg == "--clusters" || arg.rfind("--clusters=", 0) == 0) {
             const std::string v = value_of(k, arg, "--clusters <T>");
             // the whole word is the number: strtod, nothing left over, not NaN, not negative
@@ -370,6 +394,24 @@ Args parse_args(int argc, char **argv)
     }
     if (a.pos_inputs.size() > 2)
         die_usage("unexpected argument '" + a.pos_inputs[2] + "' found");
+    if (a.has_closest_for && !a.has_closest)
+        die_usage("the argument '--closest-for <side>' requires '--closest <k>'");
+    if (a.has_closest) {   // against every other output mode, before their own checks (which name --stream)
+        const char *other = a.has_nearest ? "--nearest <k>" : a.has_clusters ? "--clusters <T>"
+                            : a.matrix >= 0 ? "--matrix <format>" : a.has_tree ? "--tree <method>"
+                            : a.has_bootstrap ? "--bootstrap <B>" : a.has_mst ? "--mst"
+                            : a.dendrogram >= 0 ? "--dendrogram <linkage>" : a.has_max_distance ? "--max-distance <T>"
+                            : a.has_histogram ? "--histogram <W>" : a.has_summary ? "--summary <T>" : nullptr;
+        if (other)
+            die_usage(std::string("the argument '--closest <k>' cannot be used with '") + other + "'");
+        if (!a.has_stream)
+            die_usage("the argument '--closest <k>' requires '--stream <stream>'");
+        if (a.flag_inputs.size() + a.pos_inputs.size() > 1)
+            die_usage("the argument '--closest <k>' takes one loaded alignment, not two");
+        if (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1))
+            die_usage(std::string("the argument '--closest <k>' cannot be used with '") +
+                      (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
+    }
     for (int mode = 0; mode < 2; ++mode) {   // --summary, then --histogram: each against everything else
         if (!(mode == 0 ? a.has_summary : a.has_histogram))
             continue;
@@ -1955,9 +1997,39 @@ int main(int argc, char **argv)
         // DISTANCE_WIRE=codes keeps the Paradis bytes (tests run both)
         const char *wire_env = std::getenv("DISTANCE_WIRE");
         const bool nibbles = !(wire_env && std::strcmp(wire_env, "codes") == 0);
+        // --closest: the lists stay on the GPU (dst_stream_open_closest); one GPU, so submission order is stream order
+        const bool closest = a.has_closest, closest_loaded = closest && a.closest_side == DST_CLOSEST_FOR_LOADED;
+        const size_t TW = (size_t)dst_tally_width(measure);
+        // closest for the loaded records: the streamed ids (one arena + offsets) and, for tn93, base counts until the end
+        std::vector<char> kept_ids;
+        std::vector<uint64_t> kept_off(1, 0);
+        std::vector<uint32_t> kept_counts;
+        // "loaded id <tab> streamed id <tab> value": the pair's tallies through dst_finalize with the streamed counts as q
+        auto closest_line = [&](TextBuf &out, const std::string &lid, const char *sid, size_t sid_len, const uint32_t *tal,
+                                const uint32_t *qc, const uint32_t *tc) {
+            double f = 0;
+            int64_t v = 0;
+            dst_finalize(measure, tal, qc, tc, &f, &v);
+            char num[64];
+            const int len = std::min<int>(dst_format_distance(measure, f, v, num, sizeof num), (int)sizeof num - 1);
+            out.ensure(lid.size() + sid_len + (size_t)len + 3);
+            char *w = out.p.get() + out.len;
+            std::memcpy(w, lid.data(), lid.size());
+            w += lid.size();
+            *w++ = '\t';
+            std::memcpy(w, sid, sid_len);
+            w += sid_len;
+            *w++ = '\t';
+            std::memcpy(w, num, (size_t)len);
+            w += len;
+            *w++ = '\n';
+            out.len = (size_t)(w - out.p.get());
+        };
         for (int g = 0; g < G; ++g)
-            gpus[g].check(dst_stream_open_wire(gpus[g].h, measure, DST_OUT_TALLY, batch_records, kDepth,
-                                               nibbles ? DST_WIRE_NIBBLES : DST_WIRE_CODES, &streams[g]), "stream open");
+            gpus[g].check(closest ? dst_stream_open_closest(gpus[g].h, measure, (uint32_t)a.closest, a.closest_side, batch_records,
+                                                            kDepth, nibbles ? DST_WIRE_NIBBLES : DST_WIRE_CODES, &streams[g])
+                                  : dst_stream_open_wire(gpus[g].h, measure, DST_OUT_TALLY, batch_records, kDepth,
+                                                         nibbles ? DST_WIRE_NIBBLES : DST_WIRE_CODES, &streams[g]), "stream open");
         auto gpu_stream_worker = [&](int g) {
             std::deque<Item> inflight;
             auto collect_one = [&]() {
@@ -1966,6 +2038,29 @@ int main(int argc, char **argv)
                 gpus[g].check(dst_stream_collect(streams[g], &n_rec, &res), "stream collect");
                 Item it = std::move(inflight.front());
                 inflight.pop_front();
+                if (closest) {
+                    std::vector<TextBuf> text;
+                    if (!closest_loaded) {   // the batch's records in stream order, each with its k_used closest loaded records
+                        const uint32_t *index = nullptr, *tal = nullptr;
+                        uint32_t ku = 0;
+                        gpus[g].check(dst_stream_closest_batch(streams[g], &index, &tal, nullptr, &ku), "stream closest batch");
+                        text.emplace_back();
+                        const Alignment &al = *it.batch;
+                        for (size_t r = 0; r < n_rec; ++r)
+                            for (size_t e = 0; e < ku; ++e) {
+                                const size_t at = r * ku + e, j = index[at];
+                                closest_line(text.back(), ref.ids[j], al.ids[r].data(), al.ids[r].size(), tal + at * TW,
+                                             measure == DST_TN93 ? al.counts.data() + 4 * r : nullptr,
+                                             measure == DST_TN93 ? counts[0].data() + 4 * j : nullptr);
+                            }
+                    }
+                    {
+                        std::lock_guard<std::mutex> lk(wmu);
+                        done_text[it.idx] = std::move(text);
+                    }
+                    wcv.notify_all();
+                    return;
+                }
                 Job sj = job;
                 sj.square = false;
                 sj.swap_ids = true;          // id1 = loaded record, id2 = streamed record (src/lib.rs:327-330)
@@ -2022,6 +2117,15 @@ int main(int argc, char **argv)
                 if (measure == DST_TN93)
                     std::memcpy(cbuf, al.counts.data(), al.n * 4 * sizeof(uint32_t));
                 gpus[g].check(dst_stream_submit(streams[g], al.n, measure == DST_TN93 ? 1 : 0), "stream submit");
+                if (closest_loaded) {   // ordinal = position in submission order: keep what the final lines need
+                    for (size_t r = 0; r < al.n; ++r) {
+                        kept_ids.insert(kept_ids.end(), al.ids[r].begin(), al.ids[r].end());
+                        kept_off.push_back(kept_ids.size());
+                    }
+                    if (measure == DST_TN93)
+                        kept_counts.insert(kept_counts.end(), al.counts.begin(), al.counts.end());
+                    it.batch.reset();
+                }
                 inflight.push_back(std::move(it));
             }
             while (!inflight.empty())
@@ -2107,6 +2211,26 @@ int main(int argc, char **argv)
         dispatcher.join();
         for (auto &t : workers)
             t.join();
+        if (closest_loaded) {   // every loaded record in input order with its k_used closest streamed records
+            const size_t cap = ref.n * std::min<size_t>(a.closest, kept_off.size() - 1);
+            std::vector<uint32_t> index(std::max<size_t>(cap, 1)), tal(std::max<size_t>(cap * TW, 1));
+            uint32_t ku = 0;
+            gpus[0].check(dst_stream_closest_result(streams[0], index.data(), tal.data(), nullptr, cap, &ku), "stream closest result");
+            TextBuf out;
+            for (size_t i = 0; i < ref.n; ++i) {
+                for (size_t e = 0; e < ku; ++e) {
+                    const size_t at = i * ku + e, o = index[at];
+                    closest_line(out, ref.ids[i], kept_ids.data() + kept_off[o], (size_t)(kept_off[o + 1] - kept_off[o]),
+                                 tal.data() + at * TW, measure == DST_TN93 ? kept_counts.data() + 4 * o : nullptr,
+                                 measure == DST_TN93 ? counts[0].data() + 4 * i : nullptr);
+                }
+                if (out.len >= ((size_t)1 << 20)) {
+                    wr.write(out.p.get(), out.len);
+                    out.len = 0;
+                }
+            }
+            wr.write(out.p.get(), out.len);
+        }
         for (int g = 0; g < G; ++g)
             dst_stream_close(streams[g]);
         reader_thread.join();

@@ -422,6 +422,11 @@ hipError_t launch_nearest_rows(int measure, bool square, const uint32_t *slab, u
 // column pass (square): pairs (i, j), i in [rb, re), j > i, offer i to record j's list
 hipError_t launch_nearest_cols(int measure, const uint32_t *slab, uint64_t out_base, uint64_t n, uint64_t rb, uint64_t re,
                                const uint32_t *counts, const NearestLists &nl, hipStream_t stream);
+// column pass over a rectangle (closest streams): the slab is one batch's tallies [n_batch][n_loaded]; row r offers the
+// streamed ordinal first_ordinal + r (<= 2^32-2) to every loaded record's list.  q_counts: the batch's, t_counts: the
+// loaded set's (tn93).  Launches that share lists must follow one another on one stream.
+hipError_t launch_nearest_stream_cols(int measure, const uint32_t *slab, uint64_t n_batch, uint64_t n_loaded, uint32_t first_ordinal,
+                                      const uint32_t *q_counts, const uint32_t *t_counts, const NearestLists &nl, hipStream_t stream);
 
 // ---- single-linkage clusters (dst_clusters.hip, driven by dst_clusters in dst_analysis.cpp) -------------------------
 // A call cuts the rows of slot 0 into slabs of at most kClusterSlabPairs pairs (cut_row_slabs), runs each slab's triangle

@@ -408,6 +408,13 @@ class Engine:
         nibbles: the 4-bit wire format (DST_WIRE_NIBBLES): push() packs the codes' high nibbles, two sites per byte."""
         return Stream(self, measure, max_records, depth, tallies, nibbles)
 
+    def closest_stream(self, measure, k: int, max_records: int, side: str = "loaded", depth: int = 3,
+                       nibbles: bool = False) -> "ClosestStream":
+        """A stream that keeps the k nearest records instead of the result matrix (dst_stream_open_closest).
+        side="loaded": every loaded record's k nearest streamed records over the whole stream (result());
+        side="streamed": every streamed record's k nearest loaded records, per batch (pop())."""
+        return ClosestStream(self, measure, k, max_records, side, depth, nibbles)
+
     def run_slabs(self, measure, sink, max_pairs: int, square: bool = True, row_slot: int = 0, col_slot: int = 1,
                   tallies: bool = False):
         """In-order slab sink (dst_run_slabs): sink(first_pair, rb, re, array) per slab; a truthy return stops."""
@@ -791,9 +798,13 @@ class Stream:
         self._kind = OUT_TALLY if tallies else OUT_DISTANCE
         self._n_loaded, self._len = eng.set_info(0)
         self.max_records, self.depth = max_records, depth
+        self._h = self._open()
+
+    def _open(self):
         h = C.c_void_p()
-        eng._check(self._lib.dst_stream_open_wire(eng._h, self._m, self._kind, max_records, depth, int(nibbles), C.byref(h)))
-        self._h = h
+        self._eng._check(self._lib.dst_stream_open_wire(self._eng._h, self._m, self._kind, self.max_records, self.depth,
+                                                        int(self.nibbles), C.byref(h)))
+        return h
 
     def buffer(self):
         """(codes view (max_records, width) into the page-locked input buffer, counts view (max_records, 4))"""
@@ -846,3 +857,70 @@ class Stream:
 
     def __exit__(self, *exc):
         self.close()
+
+
+CLOSEST_SIDES = {"loaded": 0, "streamed": 1}   # dst_closest_side
+
+
+class ClosestStream(Stream):
+    """dst_stream_open_closest: a Stream whose batches leave the k nearest records behind instead of the result matrix.
+    side="loaded": pop() returns the batch's record count and result() the lists of the loaded records so far,
+    index = streamed ordinals; side="streamed": pop() returns (index, values, tallies) of the batch's records, index =
+    loaded records.  Ascending by (key of the value, index); values int64 for n / n_high, float64 otherwise."""
+
+    def __init__(self, eng: Engine, measure, k: int, max_records: int, side="loaded", depth: int = 3, nibbles: bool = False):
+        self.k = int(k)
+        self.side = side
+        self._side = CLOSEST_SIDES.get(side, side)
+        if not isinstance(self._side, int):
+            raise DistanceError(1, f"unknown side {side!r}: loaded or streamed")
+        super().__init__(eng, measure, max_records, depth, True, nibbles)
+        self._w = self._lib.dst_tally_width(self._m)
+        self._vtype = np.int64 if self._m in (0, 1) else np.float64
+
+    def _open(self):
+        h = C.c_void_p()
+        self._eng._check(self._lib.dst_stream_open_closest(self._eng._h, self._m, self.k, self._side, self.max_records,
+                                                           self.depth, int(self.nibbles), C.byref(h)))
+        return h
+
+    def pop(self, copy: bool = True):
+        n, p = C.c_size_t(), C.c_void_p()
+        self._eng._check(self._lib.dst_stream_collect(self._h, C.byref(n), C.byref(p)))
+        if self._side != 1:
+            return n.value
+        return self.closest_batch(n.value)
+
+    def closest_batch(self, n_records: int):
+        """(index, values, tallies) of the batch pop() collected last: copies (dst_stream_closest_batch)"""
+        ip, tp, vp, ku = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_uint32()
+        self._eng._check(self._lib.dst_stream_closest_batch(self._h, C.byref(ip), C.byref(tp), C.byref(vp), C.byref(ku)))
+        k = ku.value
+        if n_records * k == 0:
+            return (np.zeros((n_records, k), np.uint32), np.zeros((n_records, k), self._vtype),
+                    np.zeros((n_records, k, self._w), np.uint32))
+        index = np.ctypeslib.as_array(C.cast(ip, C.POINTER(C.c_uint32)), shape=(n_records, k)).copy()
+        vt = C.c_int64 if self._vtype is np.int64 else C.c_double
+        values = np.ctypeslib.as_array(C.cast(vp, C.POINTER(vt)), shape=(n_records, k)).copy()
+        tal = np.ctypeslib.as_array(C.cast(tp, C.POINTER(C.c_uint32)), shape=(n_records, k, self._w)).copy()
+        return index, values, tal
+
+    def next_index(self, n: int):
+        """The ordinal of the next pushed record (dst_stream_closest_next_index)"""
+        self._eng._check(self._lib.dst_stream_closest_next_index(self._h, int(n)))
+
+    def result(self, tallies: bool = False, cap_entries: int | None = None):
+        """side="loaded": (index[n_loaded, k_used], values[n_loaded, k_used][, tallies[n_loaded, k_used, width]]), a snapshot
+        (dst_stream_closest_result); every pushed batch must have been popped."""
+        cap = self._n_loaded * self.k if cap_entries is None else int(cap_entries)
+        index = np.zeros(max(cap, 1), np.uint32)
+        values = np.zeros(max(cap, 1), self._vtype)
+        tal = np.zeros(max(cap, 1) * self._w, np.uint32) if tallies else None
+        ku = C.c_uint32()
+        self._eng._check(self._lib.dst_stream_closest_result(self._h, index.ctypes.data, None if tal is None else tal.ctypes.data,
+                                                             values.ctypes.data, cap, C.byref(ku)))
+        k, n = ku.value, self._n_loaded
+        index, values = index[:n * k].reshape(n, k).copy(), values[:n * k].reshape(n, k).copy()
+        if tallies:
+            return index, values, tal[:n * k * self._w].reshape(n, k, self._w).copy()
+        return index, values

@@ -264,6 +264,47 @@ int dst_stream_submit(dst_stream *stream, size_t n_records, int use_base_counts)
 int dst_stream_collect(dst_stream *stream, size_t *n_records, const void **results);
 int dst_stream_in_flight(const dst_stream *stream);   /* submitted, not yet collected */
 int dst_stream_close(dst_stream *stream);
+/* ---- closest records in stream mode ------------------------------------------------------------ */
+/* A stream that keeps, instead of the result matrix, the k nearest records per record (1 <= k <= 256): what
+ * `gofasta closest` answers for a database that does not fit in memory.  A closest stream IS a dst_stream:
+ * dst_stream_acquire / _submit / _collect / _in_flight / _close work on it as on any other, with both wire formats, the
+ * caller's base counts and the ring of `depth` slots.  The differences: the result matrix is never copied to the host
+ * (dst_stream_collect returns *results = NULL, but still waits for the batch and still reports DST_ERR_INVALID_CODE);
+ * after a batch with an invalid code the lists are not trustworthy, and every later dst_stream_submit,
+ * dst_stream_closest_result and dst_stream_closest_batch on that stream is DST_ERR_STATE.
+ * The value of the pair (streamed s, loaded i) is the payload the same stream would deliver for it as DST_OUT_DISTANCE,
+ * bit for bit (tn93: the streamed record's base counts as q, the loaded record's as t; the same use_base_counts); its
+ * tallies are the plain stream's DST_OUT_TALLY words; its key is dst_nearest's sort key (below: int64 v ^ 2^63; f64 NaN
+ * after +inf, -0.0 as +0.0).
+ *  DST_CLOSEST_FOR_LOADED    every loaded record i keeps, over the whole life of the stream, its k smallest entries in the
+ *                            order (key, streamed ordinal); a record's ordinal is the number of records submitted before it
+ *                            (plus what dst_stream_closest_next_index skipped).  The order is strict, so the answer does not
+ *                            depend on how the stream is cut into batches.  Ordinals are uint32 and 2^32-1 is the lists'
+ *                            sentinel: a submit whose last ordinal would pass 2^32-2 is DST_ERR_CAPACITY and changes nothing.
+ *  DST_CLOSEST_FOR_STREAMED  every streamed record gets its k nearest loaded records, in the order (key, loaded index):
+ *                            dst_nearest's rectangle form with the batch as rows.  The lists are per batch.
+ * Open: an unknown measure, side or wire, k outside 1..256, max_records == 0, depth outside 2..16: DST_ERR_ARG; slot 0 not
+ * loaded: DST_ERR_STATE.  The calls below on a plain stream, or on a closest stream of the other side, are DST_ERR_ARG.
+ * Single GPU.  All selection launches of a FOR_LOADED stream write the same lists, so they follow one another on the
+ * stream's compute stream, each directly behind its batch's pair kernel. */
+typedef enum { DST_CLOSEST_FOR_LOADED = 0, DST_CLOSEST_FOR_STREAMED = 1 } dst_closest_side;
+int dst_stream_open_closest(dst_ctx *ctx, int measure, uint32_t k, int side, size_t max_records, int depth, int wire,
+                            dst_stream **stream);
+/* FOR_LOADED only.  Sets the ordinal of the next submitted record (numbering the shards of one database).  Allowed only with
+ * nothing in flight (else DST_ERR_STATE) and with the current ordinal <= next <= 2^32-1 (else DST_ERR_ARG). */
+int dst_stream_closest_next_index(dst_stream *stream, uint64_t next);
+/* FOR_LOADED only.  A snapshot of the lists: n_loaded x k_used entries, row-major by loaded record, dense, ascending;
+ * k_used = min(k, records submitted so far) - the records, not the ordinal, when ordinals were skipped.  index: the
+ * streamed ordinals (required); values: DST_OUT_DISTANCE payloads, tallies: dst_tally_width(measure) words per entry, either
+ * may be NULL (host memory, as dst_nearest's).  Needs dst_stream_in_flight() == 0, else DST_ERR_STATE; cap_entries below
+ * n_loaded x k_used: DST_ERR_CAPACITY.  Streaming may go on afterwards, and the call may be repeated. */
+int dst_stream_closest_result(dst_stream *stream, uint32_t *index, uint32_t *tallies, void *values, size_t cap_entries,
+                              uint32_t *k_used);
+/* FOR_STREAMED only.  After dst_stream_collect: the collected batch's lists, n_records x k_used entries, dense,
+ * k_used = min(k, n_loaded), in page-locked, library-owned memory that is valid until the next dst_stream_submit.  index is
+ * required; tallies and values may be NULL.  DST_ERR_STATE when no batch has been collected. */
+int dst_stream_closest_batch(dst_stream *stream, const uint32_t **index, const uint32_t **tallies, const void **values,
+                             uint32_t *k_used);
 
 /* ---- multi-GPU: the gather of the result slabs (one process per GPU, RCCL over xGMI) --------- */
 /* The pair space shards by contiguous canonical ranges (dst_partition_square / dst_partition_rect): every rank
@@ -354,7 +395,7 @@ int dst_run_slabs(dst_ctx *ctx, int measure, int square, int row_slot, int col_s
  * cap_entries: room for n_rows x k_used entries in each non-NULL buffer, else DST_ERR_CAPACITY.  DST_ERR_STATE: a set is
  * not uploaded or the widths differ.  Synchronous on the context's stream.  The pairs are computed once (square: the
  * triangle), in row slabs of at most 2^25 pairs whose tallies are merged into device-resident lists n_rows x k.
- * Single GPU, loaded sets only (not dst_stream). */
+ * Single GPU, loaded sets only (stream mode: dst_stream_open_closest). */
 int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, uint32_t k, uint32_t *index,
                 uint32_t *tallies, void *values, size_t cap_entries, uint32_t *k_used);
 /* ---- single-linkage clusters ------------------------------------------------------------------- */
