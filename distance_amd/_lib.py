@@ -23,6 +23,8 @@ SLAB_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
 LINKS_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 LINKS_VALUES, LINKS_TALLIES = 1, 2
 LINKS_CHUNK = 1 << 22   # DST_LINKS_CHUNK: the most links of one sink call
+PAIR_SITES_BATCH = 1 << 20    # DST_PAIR_SITES_BATCH: the most pairs of one device batch of dst_pair_sites
+PAIR_SITES_WINDOW = 1 << 24   # DST_PAIR_SITES_WINDOW: the most entries of one device output window
 SUMMARY_SCALE_BITS = 37   # DST_SUMMARY_SCALE_BITS: f64 distances are summed as rint(v * 2^37)
 SUMMARY_MAX_BINS = 4096   # DST_SUMMARY_MAX_BINS
 
@@ -120,6 +122,7 @@ _SIGS = {
     "dst_nearest": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, _vp, _vp, _vp, C.c_size_t, _u32p]),
     "dst_clusters": (C.c_int, [_vp, C.c_int, C.c_double, C.c_uint64, _vp, C.c_size_t, _u64p, _u64p]),
     "dst_links": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_int, _vp, _vp, _u64p]),
+    "dst_pair_sites": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_size_t, _u64p]),
     "dst_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint32, C.c_double, _vp, _vp,
                               _vp, _vp, C.c_size_t, _vp]),
     "dst_mst": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, C.c_size_t, _u64p, _u32p]),

@@ -18,7 +18,8 @@
 // --max-distance T (the long output filtered on the GPU: only the lines of the pairs within T, in the full run's order:
 // dst_links), --summary T (one line per record: how many records lie within T of it, how many it was compared with and its
 // mean distance to them: dst_summary), --histogram W / --bins B (the histogram of the pairwise distances in B bins of width
-// W, one "lower edge, pairs" line per bin and a last line for the pairs without a distance: dst_summary).
+// W, one "lower edge, pairs" line per bin and a last line for the pairs without a distance: dst_summary), --sites (with
+// --max-distance or --mst: a fourth field per line, the sites that separate the two records: dst_pair_sites).
 //
 // Exactness: the GPU returns integer site tallies; f64 finalisation is dst_finalize() on the host
 // (reference operation order, glibc log/sqrt), so the printed digits do not depend on the device.
@@ -144,6 +145,10 @@ void print_help()
         "      --mst                    Print only the edges of the minimum spanning tree of the records (pairs without a "
         "distance, NaN, are no edges: a forest then), in ascending order of (distance, first record, second record), each "
         "as the line the full run prints for that pair. One input, one GPU, no --stream and no other output mode\n"
+        "      --sites                  With one of the two pair-list outputs (the pairs within a distance, the minimum spanning "
+        "tree): a fourth field per line, the sites that separate the two "
+        "records as a comma-separated list of X<pos>Y (pos 1-based, X the first record's IUPAC letter, Y the second's; '.' "
+        "when there are none): the sites the measure counts as differences\n"
         "      --dendrogram <linkage>   Print the rooted hierarchical-clustering tree of the records as one Newick line instead "
         "of distances: linkage average (UPGMA), weighted (WPGMA) or complete. One input, one GPU, no --stream and no other "
         "output mode\n"
@@ -184,6 +189,7 @@ struct Args {
     bool has_seed = false;
     bool has_slab_pairs = false;
     bool has_mst = false;                 // --mst
+    bool has_sites = false;               // --sites (a modifier of --max-distance and --mst)
     int dendrogram = -1;                  // --dendrogram: DST_LINK_* (-1: none)
     std::string selftest;
 };
@@ -375,6 +381,8 @@ Args parse_args(int argc, char **argv)
             a.has_seed = true;
         } else if (arg == "--mst") {
             a.has_mst = true;
+        } else if (arg == "--sites") {
+            a.has_sites = true;
         } else if (arg == "--dendrogram" || arg.rfind("--dendrogram=", 0) == 0) {
             const std::string v = value_of(k, arg, "--dendrogram <linkage>");
             if (v == "average")
@@ -396,6 +404,17 @@ Args parse_args(int argc, char **argv)
         die_usage("unexpected argument '" + a.pos_inputs[2] + "' found");
     if (a.has_closest_for && !a.has_closest)
         die_usage("the argument '--closest-for <side>' requires '--closest <k>'");
+    if (a.has_sites) {   // a modifier of the two pair-list outputs: no other output mode, and one of the two
+        const char *other = a.has_stream ? "--stream <stream>" : a.has_nearest ? "--nearest <k>" : a.has_closest ? "--closest <k>"
+                            : a.has_clusters ? "--clusters <T>" : a.matrix >= 0 ? "--matrix <format>"
+                            : a.has_tree ? "--tree <method>" : a.has_bootstrap ? "--bootstrap <B>"
+                            : a.dendrogram >= 0 ? "--dendrogram <linkage>" : a.has_summary ? "--summary <T>"
+                            : a.has_histogram ? "--histogram <W>" : nullptr;
+        if (other)
+            die_usage(std::string("the argument '--sites' cannot be used with '") + other + "'");
+        if (!a.has_max_distance && !a.has_mst)
+            die_usage("the argument '--sites' requires '--max-distance <T>' or '--mst'");
+    }
     if (a.has_closest) {   // against every other output mode, before their own checks (which name --stream)
         const char *other = a.has_nearest ? "--nearest <k>" : a.has_clusters ? "--clusters <T>"
                             : a.matrix >= 0 ? "--matrix <format>" : a.has_tree ? "--tree <method>"
@@ -1426,8 +1445,85 @@ void write_clusters(const Ctx &gpu, const Alignment &set, int measure, double th
 
 // --mst: the edges of dst_mst in its order, each line "id_i, id_j, value" with the value's text exactly as the full run
 // prints that pair: the edge's tallies through dst_finalize, then dst_format_distance (as write_nearest).
+// --sites: the fourth field of a --max-distance / --mst line.  The pairs of dst_pair_sites' entries, each "X<pos>Y": pos
+// 1-based, X / Y the IUPAC letter of the first / second record's nibble; "." for a pair without listed sites.
+// diff_tally: how many entries a pair has, from its DST_OUT_TALLY words (dst_pair_sites' first consequence), which sizes
+// the buffers without a counting call.
+uint64_t diff_tally(int measure, const uint32_t *t)
+{
+    return measure == DST_K80 ? (uint64_t)t[1] + t[2] : measure == DST_TN93 ? t[1] : t[0];
+}
+
+void append_sites(std::string &out, const uint32_t *sites, const uint8_t *bases, uint64_t begin, uint64_t end)
+{
+    static const char letter[] = "?TCYGKSBAWMHRDVN";   // by nibble: A 8, G 4, C 2, T 1
+    if (begin == end)
+        out += '.';
+    for (uint64_t k = begin; k < end; ++k) {
+        if (k != begin)
+            out += ',';
+        out += letter[bases[k] >> 4];
+        out += std::to_string((uint64_t)sites[k] + 1);
+        out += letter[bases[k] & 15];
+    }
+}
+
+// "id_i, id_j, value": the three fields of every pair line, the value from the pair's tallies (as write_nearest)
+void append_pair(std::string &out, const std::string &id_i, const std::string &id_j, int measure, const uint32_t *tallies,
+                 const uint32_t *qc, const uint32_t *tc)
+{
+    char num[64];
+    double f = 0;
+    int64_t v = 0;
+    dst_finalize(measure, tallies, qc, tc, &f, &v);
+    const int len = dst_format_distance(measure, f, v, num, sizeof num);
+    out += id_i;
+    out += '\t';
+    out += id_j;
+    out += '\t';
+    out.append(num, (size_t)std::min<int>(len, (int)sizeof num - 1));
+}
+
+// The lines of pairs (row[e], col[e]), e < n, with their sites: dst_pair_sites in batches of DST_PAIR_SITES_BATCH pairs,
+// each batch's buffers sized from the pairs' tallies.
+void write_pairs_with_sites(const Ctx &gpu, const Alignment &rows, const Alignment &cols, bool square, const uint32_t *row_counts,
+                            const uint32_t *col_counts, int measure, const uint32_t *row, const uint32_t *col,
+                            const uint32_t *tallies, uint64_t n, Writer &wr)
+{
+    const size_t W = (size_t)dst_tally_width(measure);
+    std::vector<uint64_t> offsets;
+    std::vector<uint32_t> sites;
+    std::vector<uint8_t> bases;
+    std::string out;
+    for (uint64_t e0 = 0; e0 < n; e0 += DST_PAIR_SITES_BATCH) {
+        const uint64_t m = std::min<uint64_t>(DST_PAIR_SITES_BATCH, n - e0);
+        uint64_t cap = 0, total = 0;
+        for (uint64_t e = e0; e < e0 + m; ++e)
+            cap += diff_tally(measure, tallies + e * W);
+        offsets.assign(m + 1, 0);
+        sites.resize(std::max<uint64_t>(cap, 1));
+        bases.resize(std::max<uint64_t>(cap, 1));
+        gpu.check(dst_pair_sites(gpu.h, measure, square ? 1 : 0, 0, 1, row + e0, col + e0, m, offsets.data(), sites.data(),
+                                 bases.data(), cap, &total),
+                  "pair sites");
+        for (uint64_t k = 0; k < m; ++k) {
+            const size_t i = row[e0 + k], j = col[e0 + k];
+            append_pair(out, rows.ids[i], cols.ids[j], measure, tallies + (e0 + k) * W, row_counts ? row_counts + 4 * i : nullptr,
+                        col_counts ? col_counts + 4 * j : nullptr);
+            out += '\t';
+            append_sites(out, sites.data(), bases.data(), offsets[k], offsets[k + 1]);
+            out += '\n';
+            if (out.size() >= ((size_t)1 << 20)) {
+                wr.write(out.data(), out.size());
+                out.clear();
+            }
+        }
+    }
+    wr.write(out.data(), out.size());
+}
+
 void write_mst(const Ctx &gpu, const Alignment &set, const std::vector<uint32_t> &counts, int measure, uint64_t max_pairs,
-               Writer &wr)
+               bool with_sites, Writer &wr)
 {
     const size_t W = (size_t)dst_tally_width(measure);
     const size_t cap = std::max<size_t>(set.n, 1);
@@ -1435,6 +1531,10 @@ void write_mst(const Ctx &gpu, const Alignment &set, const std::vector<uint32_t>
     uint64_t n_edges = 0;
     gpu.check(dst_mst(gpu.h, measure, max_pairs, ei.data(), ej.data(), nullptr, tallies.data(), cap, &n_edges, nullptr), "mst");
     const uint32_t *cc = measure == DST_TN93 ? counts.data() : nullptr;
+    if (with_sites) {
+        write_pairs_with_sites(gpu, set, set, true, cc, cc, measure, ei.data(), ej.data(), tallies.data(), n_edges, wr);
+        return;
+    }
     std::string out;
     char num[64];
     for (size_t e = 0; e < n_edges; ++e) {
@@ -1504,6 +1604,36 @@ void write_links(const Ctx &gpu, const std::vector<Alignment> &loaded, const std
                         links_text_sink, &lt, nullptr),
               "links");
     wr.write(lt.out.data(), lt.out.size());
+}
+
+// --max-distance --sites: the context is not re-entrant, so the sink only keeps the links (row, col, tallies: 12 + 4 W
+// bytes each) in host memory; the lines are written, with their sites, after dst_links has returned.
+struct LinksKept {
+    size_t W;
+    std::vector<uint32_t> row, col, tallies;
+};
+
+int links_keep_sink(void *user, uint64_t, uint64_t n_links, const uint32_t *row, const uint32_t *col, const void *,
+                    const uint32_t *tallies)
+{
+    LinksKept &lk = *static_cast<LinksKept *>(user);
+    lk.row.insert(lk.row.end(), row, row + n_links);
+    lk.col.insert(lk.col.end(), col, col + n_links);
+    lk.tallies.insert(lk.tallies.end(), tallies, tallies + n_links * lk.W);
+    return 0;
+}
+
+void write_links_sites(const Ctx &gpu, const std::vector<Alignment> &loaded, const std::vector<std::vector<uint32_t>> &counts,
+                       int measure, double threshold, uint64_t max_pairs, Writer &wr)
+{
+    LinksKept lk{(size_t)dst_tally_width(measure), {}, {}, {}};
+    const bool square = loaded.size() == 1;
+    gpu.check(dst_links(gpu.h, measure, square ? 1 : 0, 0, 1, threshold, max_pairs, DST_LINKS_TALLIES, links_keep_sink, &lk,
+                        nullptr),
+              "links");
+    write_pairs_with_sites(gpu, loaded[0], loaded.back(), square, measure == DST_TN93 ? counts[0].data() : nullptr,
+                           measure == DST_TN93 ? counts.back().data() : nullptr, measure, lk.row.data(), lk.col.data(),
+                           lk.tallies.data(), lk.row.size(), wr);
 }
 
 // --summary: one line per record of the first input in input order, "id, within, compared, mean" from dst_summary: the
@@ -1891,6 +2021,9 @@ int main(int argc, char **argv)
     } else if (a.matrix == DST_MATRIX_PHYLIP) {
         const std::string h = std::to_string(loaded[0].n) + "\n";
         wr.write(h.data(), h.size());
+    } else if (a.has_sites) {
+        static const char sites_header[] = "sequence1\tsequence2\tdistance\tsites\n";
+        wr.write(sites_header, sizeof sites_header - 1);
     } else if (!a.has_clusters && !a.has_tree && a.dendrogram < 0 && !a.has_summary && !a.has_histogram) {
         wr.write(header, sizeof header - 1);
     }
@@ -1905,9 +2038,12 @@ int main(int argc, char **argv)
     } else if (a.has_clusters) {
         write_clusters(gpus[0], loaded[0], measure, a.clusters, wr);
     } else if (a.has_mst) {
-        write_mst(gpus[0], loaded[0], counts[0], measure, a.has_slab_pairs ? a.slab_pairs : 0, wr);
+        write_mst(gpus[0], loaded[0], counts[0], measure, a.has_slab_pairs ? a.slab_pairs : 0, a.has_sites, wr);
     } else if (a.has_max_distance) {
-        write_links(gpus[0], loaded, counts, measure, a.max_distance, a.has_slab_pairs ? a.slab_pairs : 0, wr);
+        if (a.has_sites)
+            write_links_sites(gpus[0], loaded, counts, measure, a.max_distance, a.has_slab_pairs ? a.slab_pairs : 0, wr);
+        else
+            write_links(gpus[0], loaded, counts, measure, a.max_distance, a.has_slab_pairs ? a.slab_pairs : 0, wr);
     } else if (a.has_summary) {
         write_summary(gpus[0], loaded, measure, a.summary, a.has_slab_pairs ? a.slab_pairs : 0, wr);
     } else if (a.has_histogram) {

@@ -1282,11 +1282,14 @@ int dst_destroy(dst_ctx *ctx)
     for (void *b : {(void *)ctx->d_lut, (void *)ctx->d_total, (void *)ctx->scan_tmp, ctx->host_out, ctx->hot_tally, ctx->text_res,
                     ctx->text_num, (void *)ctx->text_len, (void *)ctx->text_scan, (void *)ctx->text_buf, (void *)ctx->text_flag, ctx->text_ties,
                     (void *)ctx->ids[0].off, (void *)ctx->ids[0].chars, (void *)ctx->ids[1].off, (void *)ctx->ids[1].chars, ctx->pair_slab, ctx->nn_lists,
-                    ctx->cl_work, ctx->mst_work, ctx->dg_work, ctx->links_work, ctx->summary_work})
+                    ctx->cl_work, ctx->mst_work, ctx->dg_work, ctx->links_work, ctx->summary_work, ctx->ps_batch, ctx->ps_window})
         if (b)
             (void)hipFree(b);
     if (ctx->links_host)
         (void)hipHostFree(ctx->links_host);
+    for (void *b : {ctx->ps_batch_host, ctx->ps_window_host})
+        if (b)
+            (void)hipHostFree(b);
     if (ctx->scratch)
         (void)hipFree(ctx->scratch);
     if (ctx->text_ties_host)
@@ -1642,6 +1645,144 @@ int dst_differences(dst_ctx *ctx, int slot, const uint8_t *other, size_t len, ui
     for (uint64_t k = 0; k < total; ++k)
         sites[k] &= kSiteMask;  // drop the reference class and the nibble the pair kernel's lists carry
     return done(DST_OK);
+}
+
+// page-locked host memory of dst_pair_sites (grow-only)
+static int pair_sites_host(dst_ctx *ctx, void **ptr, size_t *have, size_t want)
+{
+    if (*have >= want)
+        return DST_OK;
+    if (*ptr)
+        HIP_TRY(ctx, hipHostFree(*ptr));
+    *ptr = nullptr;
+    *have = 0;
+    if (hipHostMalloc(ptr, want, hipHostMallocDefault) != hipSuccess) {
+        *ptr = nullptr;
+        (void)hipGetLastError();
+        return fail(ctx, DST_ERR_NOMEM, "pair sites: cannot allocate " + std::to_string(want) + " bytes of page-locked memory");
+    }
+    *have = want;
+    return DST_OK;
+}
+
+int dst_pair_sites(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, const uint32_t *row, const uint32_t *col,
+                   uint64_t n_pairs, uint64_t *offsets, uint32_t *sites, uint8_t *bases, size_t cap_entries, uint64_t *total_out)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (total_out)
+        *total_out = 0;
+    if (!row || !col || !offsets)
+        return fail(ctx, DST_ERR_ARG, "null pointer");
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if ((sites == nullptr) != (bases == nullptr))
+        return fail(ctx, DST_ERR_ARG, "sites and bases must both be given or both be NULL");
+    if (square) {
+        row_slot = 0;
+        col_slot = 0;
+    } else {
+        if (row_slot < 0 || row_slot > 1 || col_slot < 0 || col_slot > 1)
+            return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
+        if (row_slot == col_slot)
+            return fail(ctx, DST_ERR_ARG, "row_slot == col_slot: use the square form for one set");
+    }
+    DeviceSet &rows = ctx->set[row_slot], &cols = ctx->set[col_slot];
+    if (!rows.loaded || !cols.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    if (rows.len != cols.len) {
+        char msg[128];  // src/fastaio.rs:93-95
+        std::snprintf(msg, sizeof msg, "Different length sequences in alignment(s): %zu vs %zu", rows.len, cols.len);
+        return fail(ctx, DST_ERR_STATE, msg);
+    }
+    if (rows.partial || cols.partial)
+        return fail(ctx, DST_ERR_STATE, "a set uploaded with dst_upload_shared runs on the consensus path only (this rank holds "
+                                        "the planes of its own records)");
+    if (rows.len >= ((uint64_t)1 << 32))
+        return fail(ctx, DST_ERR_ARG, "alignments of 2^32 sites or more are beyond dst_pair_sites");
+    for (uint64_t e = 0; e < n_pairs; ++e)
+        if (row[e] >= rows.n || col[e] >= cols.n) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "pair %llu (%u, %u) is out of range: %zu row records, %zu column records",
+                          (unsigned long long)e, row[e], col[e], rows.n, cols.n);
+            return fail(ctx, DST_ERR_ARG, msg);
+        }
+    offsets[0] = 0;
+    if (n_pairs == 0)
+        return DST_OK;
+    if (rows.len == 0) {
+        std::fill(offsets, offsets + n_pairs + 1, (uint64_t)0);
+        return DST_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(ctx, hipStreamSynchronize(stream));   // (nothing queued earlier reads the grow-only buffers any more)
+    int rc = ensure_planes(ctx, rows, stream);
+    if (!rc && &cols != &rows)
+        rc = ensure_planes(ctx, cols, stream);
+    // one batch on the device and in page-locked memory: row, col, counts, offsets
+    const uint64_t mb = std::min<uint64_t>(n_pairs, DST_PAIR_SITES_BATCH);
+    const size_t at_col = mb * 4, at_cnt = at_col + mb * 4, at_off = (at_cnt + mb * 4 + 255) / 256 * 256,
+                 batch_bytes = at_off + (mb + 1) * 8;
+    if (!rc)
+        rc = ensure_bytes(ctx, &ctx->ps_batch, &ctx->ps_batch_bytes, batch_bytes);
+    if (!rc)
+        rc = pair_sites_host(ctx, &ctx->ps_batch_host, &ctx->ps_batch_host_bytes, batch_bytes);
+    if (rc)
+        return rc;
+    char *d_batch = static_cast<char *>(ctx->ps_batch), *h_batch = static_cast<char *>(ctx->ps_batch_host);
+    PairSitesBuffers b{};
+    b.row = reinterpret_cast<uint32_t *>(d_batch);
+    b.col = reinterpret_cast<uint32_t *>(d_batch + at_col);
+    b.counts = reinterpret_cast<uint32_t *>(d_batch + at_cnt);
+    b.offsets = reinterpret_cast<uint64_t *>(d_batch + at_off);
+    const uint64_t *h_off = reinterpret_cast<const uint64_t *>(h_batch + at_off);
+    const bool write = sites != nullptr;
+    bool fits = true;   // every entry so far has had room: the batches after the first that has not are only counted
+    uint64_t total = 0;
+    for (uint64_t e0 = 0; e0 < n_pairs; e0 += mb) {
+        const uint64_t m = std::min(mb, n_pairs - e0);
+        std::memcpy(h_batch, row + e0, m * 4);
+        std::memcpy(h_batch + at_col, col + e0, m * 4);
+        HIP_TRY(ctx, hipMemcpyAsync(d_batch, h_batch, at_col + m * 4, hipMemcpyHostToDevice, stream));
+        HIP_TRY(ctx, launch_pair_sites_count(measure, rows, cols, (uint32_t)m, b, stream));
+        HIP_TRY(ctx, hipMemcpyAsync(h_batch + at_off, b.offsets, (m + 1) * 8, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+        const uint64_t in_batch = h_off[m];
+        if (in_batch > m * rows.len)
+            return fail(ctx, DST_ERR_STATE, "pair sites: more entries than sites in a batch");
+        for (uint64_t k = 0; k < m; ++k)
+            offsets[e0 + k + 1] = total + h_off[k + 1];
+        fits = fits && total + in_batch <= cap_entries;
+        if (write && fits && in_batch) {
+            // one window of entries on the device and in page-locked memory: sites, then bases
+            const uint64_t win = std::min<uint64_t>(in_batch, DST_PAIR_SITES_WINDOW);
+            rc = ensure_bytes(ctx, &ctx->ps_window, &ctx->ps_window_bytes, win * 5);
+            if (!rc)
+                rc = pair_sites_host(ctx, &ctx->ps_window_host, &ctx->ps_window_host_bytes, win * 5);
+            if (rc)
+                return rc;
+            const uint64_t wcap = std::min<uint64_t>(std::min(ctx->ps_window_bytes, ctx->ps_window_host_bytes) / 5, DST_PAIR_SITES_WINDOW);
+            b.sites = static_cast<uint32_t *>(ctx->ps_window);
+            b.bases = static_cast<uint8_t *>(ctx->ps_window) + wcap * 4;
+            char *h_win = static_cast<char *>(ctx->ps_window_host);
+            for (uint64_t lo = 0; lo < in_batch; lo += wcap) {
+                const uint64_t hi = std::min(in_batch, lo + wcap), w = hi - lo;
+                HIP_TRY(ctx, launch_pair_sites_write(measure, rows, cols, (uint32_t)m, b, lo, hi, stream));
+                HIP_TRY(ctx, hipMemcpyAsync(h_win, b.sites, w * 4, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(ctx, hipMemcpyAsync(h_win + wcap * 4, b.bases, w, hipMemcpyDeviceToHost, stream));
+                HIP_TRY(ctx, hipStreamSynchronize(stream));
+                std::memcpy(sites + total + lo, h_win, w * 4);
+                std::memcpy(bases + total + lo, h_win + wcap * 4, w);
+            }
+        }
+        total += in_batch;
+    }
+    if (total_out)
+        *total_out = total;
+    if (write && !fits)
+        return fail(ctx, DST_ERR_CAPACITY, "sites / bases buffers too small");
+    return DST_OK;
 }
 
 int dst_run_square(dst_ctx *ctx, int measure, uint64_t row_begin, uint64_t row_end, int out_kind,

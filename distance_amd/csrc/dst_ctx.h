@@ -115,6 +115,10 @@ struct dst_ctx {
     // memory (both grow-only)
     void *links_work = nullptr, *links_host = nullptr;
     size_t links_work_bytes = 0, links_host_bytes = 0;
+    // dst_pair_sites: one batch of pairs with its counts and offsets, one window of entries, and both again in page-locked
+    // host memory (all grow-only)
+    void *ps_batch = nullptr, *ps_window = nullptr, *ps_batch_host = nullptr, *ps_window_host = nullptr;
+    size_t ps_batch_bytes = 0, ps_window_bytes = 0, ps_batch_host_bytes = 0, ps_window_host_bytes = 0;
     // dst_summary: the per-record counters and accumulators, the histogram and the totals (grow-only)
     void *summary_work = nullptr;
     size_t summary_work_bytes = 0;
@@ -153,6 +157,8 @@ int fail_hip(dst_ctx *ctx, hipError_t e, const char *what);
     } while (0)
 
 int ensure_bytes(dst_ctx *ctx, void **ptr, size_t *have, size_t want);
+// the base planes a deferred upload left out, written before anything but the consensus path reads planes (dst_api.cpp)
+int ensure_planes(dst_ctx *ctx, DeviceSet &s, hipStream_t stream);
 void free_set(DeviceSet &s);
 // queue the pack of an n x len byte matrix (device memory) into `s`; *d_first_bad receives the index of the first
 // byte that is not a Paradis code (or stays ~0).  Nothing here waits for the device.

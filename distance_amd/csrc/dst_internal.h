@@ -468,6 +468,24 @@ hipError_t launch_links_write(int measure, bool tally, bool square, const void *
                               uint64_t rb, uint64_t re, uint64_t t_bits, const uint32_t *q_counts, const uint32_t *t_counts,
                               const LinksBuffers &b, uint64_t lo, uint64_t hi, bool values, bool tallies, hipStream_t stream);
 
+// ---- difference sites of a pair list (dst_pair_sites.hip, driven by dst_pair_sites in dst_api.cpp) ---------------------
+// Per batch of at most DST_PAIR_SITES_BATCH pairs: a count launch (one wave per pair, the lanes along its chunks) and a
+// one-workgroup scan into 64-bit offsets; then per window of at most DST_PAIR_SITES_WINDOW ranks a write launch that places
+// every listed site of the window, and the two records' nibbles, at its rank.  Reads the sets' four base planes only.
+struct PairSitesBuffers {
+    uint32_t *row, *col;  // [pairs] the batch's record indices
+    uint32_t *counts;     // [pairs] listed sites per pair
+    uint64_t *offsets;    // [pairs + 1] their exclusive scan; the last entry: the batch's entries
+    uint32_t *sites;      // one window of entries: DST_PAIR_SITES_WINDOW at most
+    uint8_t *bases;       // row nibble << 4 | column nibble
+};
+// b.row / b.col hold `pairs` valid record indices of rows / cols (two packed sets of one width, planes stored)
+hipError_t launch_pair_sites_count(int measure, const DeviceSet &rows, const DeviceSet &cols, uint32_t pairs, const PairSitesBuffers &b,
+                                   hipStream_t stream);
+// the entries of ranks [lo, hi) of the batch into b.sites / b.bases, entry rank - lo
+hipError_t launch_pair_sites_write(int measure, const DeviceSet &rows, const DeviceSet &cols, uint32_t pairs, const PairSitesBuffers &b,
+                                   uint64_t lo, uint64_t hi, hipStream_t stream);
+
 // ---- per-record and histogram summaries (dst_summary.hip, driven by dst_summary in dst_analysis.cpp) -------------------
 // Per row slab of DST_OUT_DISTANCE payloads (cut as for dst_clusters) up to three launches, each wanted or not: the row pass
 // (dst_clusters' geometry, one set of atomics per workgroup to its row's record), the column pass (square only: thread =

@@ -514,6 +514,33 @@ class Engine:
             out += (cat(parts[3], np.uint32, (0, width)),)
         return out
 
+    def pair_sites(self, measure, row, col, square: bool = True, row_slot: int = 0, col_slot: int = 1, count_only: bool = False):
+        """The difference sites of the listed pairs (dst_pair_sites), CSR: (offsets uint64[n_pairs + 1], sites uint32[total],
+        bases uint8[total]), or offsets alone with count_only.  Pair e is record row[e] against record col[e] (square: both
+        of slot 0, any order, repeats and row == col allowed; else of row_slot and col_slot); its entries
+        [offsets[e], offsets[e + 1]) are the ascending 0-based sites that add 1 to the measure's difference tally, with
+        bases = the row record's nibble << 4 | the column record's (A 8, G 4, C 2, T 1)."""
+        m = _measure_id(measure)
+        row = np.ascontiguousarray(row, np.uint32).ravel()
+        col = np.ascontiguousarray(col, np.uint32).ravel()
+        if row.size != col.size:
+            raise ValueError("row and col must have the same length")
+        n_pairs = int(row.size)
+        rbuf = row if n_pairs else np.zeros(1, np.uint32)   # (never a NULL index array, also for an empty list)
+        cbuf = col if n_pairs else np.zeros(1, np.uint32)
+        offsets = np.zeros(n_pairs + 1, np.uint64)
+        total = C.c_uint64()
+        self._check(self._lib.dst_pair_sites(self._h, m, int(square), row_slot, col_slot, rbuf.ctypes.data, cbuf.ctypes.data,
+                                             n_pairs, offsets.ctypes.data, None, None, 0, C.byref(total)))
+        if count_only:
+            return offsets
+        cap = max(int(total.value), 1)
+        sites, bases = np.zeros(cap, np.uint32), np.zeros(cap, np.uint8)
+        self._check(self._lib.dst_pair_sites(self._h, m, int(square), row_slot, col_slot, rbuf.ctypes.data, cbuf.ctypes.data,
+                                             n_pairs, offsets.ctypes.data, sites.ctypes.data, bases.ctypes.data, cap,
+                                             C.byref(total)))
+        return offsets, sites[:int(total.value)], bases[:int(total.value)]
+
     def summary(self, measure, threshold: float = 0.0, square: bool = True, row_slot: int = 0, col_slot: int = 1,
                 max_pairs: int = 0, bins: int = 0, width: float = 1.0, per_record: bool = True) -> dict:
         """Per-record and histogram summaries of the pairwise distances (dst_summary), a dict: `within` (uint32[n_rows], the

@@ -466,6 +466,41 @@ typedef int (*dst_links_sink)(void *user, uint64_t first_link, uint64_t n_links,
                               const void *values, const uint32_t *tallies);
 int dst_links(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, double threshold, uint64_t max_pairs,
               int what, dst_links_sink sink, void *user, uint64_t *n_links);
+/* ---- difference sites of a list of pairs ---------------------------------------------------------- */
+/* WHICH sites separate two records (the label of a 2-SNP link, of an MST edge: "C241T, A23403G"), for a list of pairs the
+ * caller names (dst_links' row / col, dst_mst's edges), gathered from the bit-planes the GPU already holds.  The
+ * definition is fixed to the bit.  a and b are the high nibbles of the Paradis codes of the row record and the column
+ * record at a site: A = 8, G = 4, C = 2, T = 1, nibble 15 is N / - / ?; a nibble determines everything any measure reads.
+ * A site is a difference site of `measure` when it adds 1 to the measure's difference tally, as dst_site_tallies
+ * defines it:
+ *   n, n_high, raw, jc69   (a & b) == 0
+ *   k80                    (a & b) == 0, and each of a, b is purine-class {8, 4, 12} or pyrimidine-class {2, 1, 3} (the site
+ *                          counts as ts or tv)
+ *   tn93                   (a & b) == 0, and both a and b are one of {8, 4, 2, 1} (the site counts in count_d)
+ * Consequences: the number of listed sites of a pair equals the pair's difference tally in DST_OUT_TALLY (word 0 of n /
+ * n_high / raw / jc69, ts + tv of k80, count_d of tn93); sites at or beyond len (the pack's N padding) are never listed.
+ *   pairs    square != 0: both indices address slot 0 (row_slot / col_slot ignored); any row[e], col[e] below n, in any
+ *            order, repeated pairs allowed, and row[e] == col[e], which lists nothing.
+ *            square == 0: row[e] indexes row_slot, col[e] indexes col_slot; equal slots are DST_ERR_ARG, as in dst_nearest.
+ *   result   CSR in host memory: offsets has n_pairs + 1 entries (required); sites holds the ascending 0-based site
+ *            indices of pair e at [offsets[e], offsets[e + 1]); bases[k] = a << 4 | b of that site.
+ *            sites == NULL and bases == NULL: offsets and *total only, no write pass runs.  cap_entries below the total:
+ *            DST_ERR_CAPACITY with offsets and *total valid, as dst_differences.  total may be NULL.
+ * n_pairs == 0: DST_OK, offsets[0] = 0.  DST_ERR_ARG: a NULL ctx, row, col or offsets; an unknown measure; a bad slot;
+ * exactly one of sites / bases NULL; an index out of range (the message names the first such pair); len >= 2^32.
+ * DST_ERR_STATE: a set is not uploaded, the widths differ (dst_nearest's message), or a set came from dst_upload_shared
+ * (it holds no planes: the dense kernels' refusal).  Synchronous on the context's stream.  Slots, the path choice and
+ * later results are untouched; a set with deferred planes gets them first, as for any plane reader.  Device memory
+ * besides the sets is bounded whatever n_pairs and the total: the pairs go to the device in batches of at most
+ * DST_PAIR_SITES_BATCH (per batch a count launch, one wave per pair, and a scan), the entries come back in windows of at
+ * most DST_PAIR_SITES_WINDOW (one write launch each) through page-locked staging; a pair's entries may straddle
+ * windows.  Work ~ pairs x len whatever the data: 128 bytes of planes per pair and 128-site chunk, read once to count
+ * and once more per window that the pair's entries meet.  Single GPU, loaded sets only (not dst_stream). */
+#define DST_PAIR_SITES_BATCH  (1u << 20)  /* most pairs of one device batch */
+#define DST_PAIR_SITES_WINDOW (1u << 24)  /* most entries of one device output window */
+int dst_pair_sites(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
+                   const uint32_t *row, const uint32_t *col, uint64_t n_pairs,
+                   uint64_t *offsets, uint32_t *sites, uint8_t *bases, size_t cap_entries, uint64_t *total);
 /* ---- per-record and histogram summaries ---------------------------------------------------------- */
 /* What the distances of a set look like, computed next to the values on the GPU: the histogram of the pairwise distances
  * (from which a threshold is chosen) and, per record, how many records lie within `threshold` of it (its degree in the
