@@ -38,7 +38,7 @@ int slab_scratch(dst_ctx *ctx, size_t bytes, bool wanted = true)
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     if (!wanted)
         return DST_OK;
-    return ensure_bytes(ctx, &ctx->pair_slab, &ctx->pair_slab_bytes, std::max<size_t>(bytes, 256));
+    return ctx->pair_slab.grow(ctx, std::max<size_t>(bytes, 256));
 }
 
 // Every slab in order: its pairs, each once (square: the triangle), as `out_kind` into the slab scratch, then
@@ -48,7 +48,7 @@ int walk_slabs(dst_ctx *ctx, int measure, bool square, DeviceSet &rows, DeviceSe
                int out_kind, Consume &&consume)
 {
     for (const RowSlab &s : slabs) {
-        int rc = run_sets(ctx, measure, square, rows, cols, s.rb, s.re, out_kind, ctx->pair_slab, ctx->pair_slab_bytes,
+        int rc = run_sets(ctx, measure, square, rows, cols, s.rb, s.re, out_kind, ctx->pair_slab, ctx->pair_slab.bytes,
                           (void *)ctx->stream);
         if (!rc)
             rc = consume(s);
@@ -122,24 +122,6 @@ size_t links_layout(void *base, uint64_t blocks, uint64_t chunk, bool values, in
     b.val = c.take<uint64_t>(values ? chunk : 0);
     b.tal = c.take<uint32_t>(chunk * (size_t)W);
     return c.used;
-}
-
-// the page-locked host copy of one chunk of links (grow-only)
-int links_host(dst_ctx *ctx, size_t bytes)
-{
-    if (ctx->links_host_bytes >= bytes)
-        return DST_OK;
-    if (ctx->links_host)
-        HIP_TRY(ctx, hipHostFree(ctx->links_host));
-    ctx->links_host = nullptr;
-    ctx->links_host_bytes = 0;
-    if (hipHostMalloc(&ctx->links_host, bytes, hipHostMallocDefault) != hipSuccess) {
-        ctx->links_host = nullptr;
-        (void)hipGetLastError();
-        return fail(ctx, DST_ERR_NOMEM, "links: cannot allocate " + std::to_string(bytes) + " bytes of page-locked memory");
-    }
-    ctx->links_host_bytes = bytes;
-    return DST_OK;
 }
 
 size_t summary_layout(void *base, uint64_t records, uint32_t bins, SummaryBuffers &b)
@@ -262,7 +244,7 @@ int square_fill(dst_ctx *ctx, int measure, DeviceSet &set, const SlabPlan &plan,
     const uint64_t n = set.n;
     HIP_TRY(ctx, launch_nj_init(al.b.D[0], n, al.b.ids[0], al.b.active, al.bad, stream));
     return walk_slabs(ctx, measure, true, set, set, plan.slabs, DST_OUT_DISTANCE, [&](const RowSlab &s) -> int {
-        HIP_TRY(ctx, launch_nj_scatter(measure, static_cast<const uint64_t *>(ctx->pair_slab), s.first, n, s.rb, s.re,
+        HIP_TRY(ctx, launch_nj_scatter(measure, static_cast<const uint64_t *>(ctx->pair_slab.ptr), s.first, n, s.rb, s.re,
                                        al.b.D[0], al.bad, stream));
         return DST_OK;
     });
@@ -376,7 +358,7 @@ int dg_buffers(dst_ctx *ctx, SquareAlloc &al, uint64_t n, DgBuffers &b)
 {
     const size_t total = dg_layout(nullptr, n, b);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (an earlier call's state goes before it is replaced)
-    if (int rc = ensure_bytes(ctx, &ctx->dg_work, &ctx->dg_work_bytes, total))
+    if (int rc = ctx->dg_work.grow(ctx, total))
         return rc;
     dg_layout(ctx->dg_work, n, b);
     b.scans = reinterpret_cast<unsigned long long *>(b.counters + 4);
@@ -428,26 +410,11 @@ int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slo
         return fail(ctx, DST_ERR_ARG, "k must be between 1 and 256");
     if (!index || !k_used)
         return fail(ctx, DST_ERR_ARG, "null index or k_used pointer");
-    if (square) {
-        row_slot = 0;
-        col_slot = 0;
-    } else {
-        if (row_slot < 0 || row_slot > 1 || col_slot < 0 || col_slot > 1)
-            return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
-        if (row_slot == col_slot)
-            return fail(ctx, DST_ERR_ARG, "row_slot == col_slot: use the square form for one set");
-    }
-    DeviceSet &rows = ctx->set[row_slot], &cols = ctx->set[col_slot];
-    if (!rows.loaded || !cols.loaded)
-        return fail(ctx, DST_ERR_STATE, "set not uploaded");
-    if (rows.len != cols.len) {
-        char msg[128];  // src/fastaio.rs:93-95
-        std::snprintf(msg, sizeof msg, "Different length sequences in alignment(s): %zu vs %zu", rows.len, cols.len);
-        return fail(ctx, DST_ERR_STATE, msg);
-    }
+    TwoSets ts;
+    if (int rc = two_sets(ctx, square != 0, row_slot, col_slot, ts, true, true))
+        return rc;
+    DeviceSet &rows = *ts.rows, &cols = *ts.cols;
     const uint64_t n_rows = rows.n, n_cols = cols.n;
-    if (n_rows >= 0xFFFFFFFFull || n_cols >= 0xFFFFFFFFull)
-        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
     const uint64_t candidates = square ? (n_rows > 0 ? n_rows - 1 : 0) : n_cols;
     const uint32_t ku = (uint32_t)std::min<uint64_t>(k, candidates);
     if (n_rows * ku > cap_entries)
@@ -472,13 +439,13 @@ int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slo
     NearestLists nl{};
     rc = slab_scratch(ctx, dst_out_bytes(measure, DST_OUT_TALLY, plan.biggest));
     if (!rc)
-        rc = ensure_bytes(ctx, &ctx->nn_lists, &ctx->nn_lists_bytes, nearest_layout(nullptr, entries, W, nl));
+        rc = ctx->nn_lists.grow(ctx, nearest_layout(nullptr, entries, W, nl));
     if (rc)
         return rc;
     nearest_layout(ctx->nn_lists, entries, W, nl);
     nl.k = ku;
     HIP_TRY(ctx, launch_nearest_init(nl, n_rows, stream));
-    const uint32_t *slab = static_cast<const uint32_t *>(ctx->pair_slab);
+    const uint32_t *slab = static_cast<const uint32_t *>(ctx->pair_slab.ptr);
     // the slab's exact tallies, then both passes behind its pair kernel: they touch the same lists
     rc = walk_slabs(ctx, measure, square != 0, rows, cols, plan.slabs, DST_OUT_TALLY, [&](const RowSlab &s) -> int {
         HIP_TRY(ctx, launch_nearest_rows(measure, square != 0, slab, s.first, n_cols, s.rb, s.re, rows.counts, cols.counts,
@@ -546,14 +513,14 @@ int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs
     };
     int rc = slab_scratch(ctx, dst_out_bytes(measure, DST_OUT_DISTANCE, plan.biggest), any);
     if (!rc)
-        rc = ensure_bytes(ctx, &ctx->cl_work, &ctx->cl_work_bytes, layout(nullptr));
+        rc = ctx->cl_work.grow(ctx, layout(nullptr));
     if (rc)
         return rc;
     layout(ctx->cl_work);
     HIP_TRY(ctx, launch_clusters_init(parent, n, d_links, stream));
     // the slab's DST_OUT_DISTANCE payloads, then its unions behind the pair kernel (and the previous slab's unions)
     rc = walk_slabs(ctx, measure, true, set, set, plan.slabs, DST_OUT_DISTANCE, [&](const RowSlab &s) -> int {
-        HIP_TRY(ctx, launch_clusters_link(measure, static_cast<const uint64_t *>(ctx->pair_slab), s.first, n, s.rb, s.re, t_bits,
+        HIP_TRY(ctx, launch_clusters_link(measure, static_cast<const uint64_t *>(ctx->pair_slab.ptr), s.first, n, s.rb, s.re, t_bits,
                                           parent, d_links, stream));
         return DST_OK;
     });
@@ -587,26 +554,11 @@ int dst_links(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
         return fail(ctx, DST_ERR_ARG, "threshold is NaN");
     if (what & ~(DST_LINKS_VALUES | DST_LINKS_TALLIES))
         return fail(ctx, DST_ERR_ARG, "unknown bits in what");
-    if (square) {
-        row_slot = 0;
-        col_slot = 0;
-    } else {
-        if (row_slot < 0 || row_slot > 1 || col_slot < 0 || col_slot > 1)
-            return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
-        if (row_slot == col_slot)
-            return fail(ctx, DST_ERR_ARG, "row_slot == col_slot: use the square form for one set");
-    }
-    DeviceSet &rows = ctx->set[row_slot], &cols = ctx->set[col_slot];
-    if (!rows.loaded || !cols.loaded)
-        return fail(ctx, DST_ERR_STATE, "set not uploaded");
-    if (rows.len != cols.len) {
-        char msg[128];  // src/fastaio.rs:93-95
-        std::snprintf(msg, sizeof msg, "Different length sequences in alignment(s): %zu vs %zu", rows.len, cols.len);
-        return fail(ctx, DST_ERR_STATE, msg);
-    }
+    TwoSets ts;
+    if (int rc = two_sets(ctx, square != 0, row_slot, col_slot, ts, true, true))
+        return rc;
+    DeviceSet &rows = *ts.rows, &cols = *ts.cols;
     const uint64_t n_rows = rows.n, n_cols = cols.n;
-    if (n_rows >= 0xFFFFFFFFull || n_cols >= 0xFFFFFFFFull)
-        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
     uint64_t t_bits;
     const bool any = threshold_payload(measure, threshold, t_bits);
     if (!any || (square ? n_rows < 2 : (n_rows == 0 || n_cols == 0)))
@@ -633,16 +585,15 @@ int dst_links(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
     LinksBuffers b{};
     rc = slab_scratch(ctx, dst_out_bytes(measure, kind, plan.biggest));
     if (!rc)
-        rc = ensure_bytes(ctx, &ctx->links_work, &ctx->links_work_bytes,
-                          links_layout(nullptr, blocks, chunk, values, tallies ? W : 0, b));
+        rc = ctx->links_work.grow(ctx, links_layout(nullptr, blocks, chunk, values, tallies ? W : 0, b));
     // the host copy: row, col, values, tallies, each piece where the window's entries of it start
     const size_t h_col = chunk * 4, h_val = h_col + chunk * 4, h_tal = h_val + (values ? chunk * 8 : 0);
     if (!rc && sink)
-        rc = links_host(ctx, h_tal + (tallies ? chunk * 4 * (size_t)W : 0));
+        rc = ctx->links_host.grow(ctx, h_tal + (tallies ? chunk * 4 * (size_t)W : 0), "links");
     if (rc)
         return rc;
     links_layout(ctx->links_work, blocks, chunk, values, tallies ? W : 0, b);
-    char *host = static_cast<char *>(ctx->links_host);
+    char *host = ctx->links_host;
     HIP_TRY(ctx, hipMemsetAsync(b.grand, 0, 8, stream));
     uint64_t total = 0;
     // the slab, its block counts and their scan behind the pair kernel; with a sink the slab's total comes back (one wait),
@@ -718,26 +669,11 @@ int dst_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slo
         if (width_q < 1)
             return fail(ctx, DST_ERR_ARG, "width is below one unit of the fixed-point scale");
     }
-    if (square) {
-        row_slot = 0;
-        col_slot = 0;
-    } else {
-        if (row_slot < 0 || row_slot > 1 || col_slot < 0 || col_slot > 1)
-            return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
-        if (row_slot == col_slot)
-            return fail(ctx, DST_ERR_ARG, "row_slot == col_slot: use the square form for one set");
-    }
-    DeviceSet &rows = ctx->set[row_slot], &cols = ctx->set[col_slot];
-    if (!rows.loaded || !cols.loaded)
-        return fail(ctx, DST_ERR_STATE, "set not uploaded");
-    if (rows.len != cols.len) {
-        char msg[128];  // src/fastaio.rs:93-95
-        std::snprintf(msg, sizeof msg, "Different length sequences in alignment(s): %zu vs %zu", rows.len, cols.len);
-        return fail(ctx, DST_ERR_STATE, msg);
-    }
+    TwoSets ts;
+    if (int rc = two_sets(ctx, square != 0, row_slot, col_slot, ts, true, true))
+        return rc;
+    DeviceSet &rows = *ts.rows, &cols = *ts.cols;
     const uint64_t n_rows = rows.n, n_cols = cols.n;
-    if (n_rows >= 0xFFFFFFFFull || n_cols >= 0xFFFFFFFFull)
-        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
     const bool per_record = within || summable || sum;
     if (per_record && cap < n_rows)
         return fail(ctx, DST_ERR_CAPACITY, "cap is below the row set's record count");
@@ -767,13 +703,13 @@ int dst_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slo
     const size_t state_bytes = summary_layout(nullptr, n_rows, bins, b);
     int rc = slab_scratch(ctx, dst_out_bytes(measure, DST_OUT_DISTANCE, plan.biggest));
     if (!rc)
-        rc = ensure_bytes(ctx, &ctx->summary_work, &ctx->summary_work_bytes, state_bytes);
+        rc = ctx->summary_work.grow(ctx, state_bytes);
     if (rc)
         return rc;
     summary_layout(ctx->summary_work, n_rows, bins, b);
     static const bool no_aggregation = std::getenv("DST_SUMMARY_NO_AGGREGATION") != nullptr;   // measurement knob
     HIP_TRY(ctx, hipMemsetAsync(ctx->summary_work, 0, state_bytes, stream));
-    const uint64_t *slab = static_cast<const uint64_t *>(ctx->pair_slab);
+    const uint64_t *slab = static_cast<const uint64_t *>(ctx->pair_slab.ptr);
     // the slab's DST_OUT_DISTANCE payloads, then the wanted passes behind its pair kernel
     rc = walk_slabs(ctx, measure, square != 0, rows, cols, plan.slabs, DST_OUT_DISTANCE, [&](const RowSlab &s) -> int {
         if (per_record) {
@@ -876,7 +812,7 @@ int dst_mst(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *edge_i, uin
     rc = slab_scratch(ctx, std::max(dst_out_bytes(measure, DST_OUT_DISTANCE, plan.biggest),
                                     finish ? dst_out_bytes(measure, DST_OUT_TALLY, plan.biggest) : (size_t)0));
     if (!rc)
-        rc = ensure_bytes(ctx, &ctx->mst_work, &ctx->mst_work_bytes, mst_layout(nullptr, n, W, b));
+        rc = ctx->mst_work.grow(ctx, mst_layout(nullptr, n, W, b));
     if (rc)
         return rc;
     mst_layout(ctx->mst_work, n, W, b);
@@ -890,7 +826,7 @@ int dst_mst(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *edge_i, uin
         HIP_TRY(ctx, launch_mst_reset(b, n, first, stream));
         // the slab's DST_OUT_DISTANCE payloads, the two scan launches behind it
         rc = walk_slabs(ctx, measure, true, set, set, plan.slabs, DST_OUT_DISTANCE, [&](const RowSlab &s) -> int {
-            HIP_TRY(ctx, launch_mst_scan(measure, static_cast<const uint64_t *>(ctx->pair_slab), s.first, n, s.rb, s.re, b, stream));
+            HIP_TRY(ctx, launch_mst_scan(measure, static_cast<const uint64_t *>(ctx->pair_slab.ptr), s.first, n, s.rb, s.re, b, stream));
             return DST_OK;
         });
         if (rc)
@@ -909,7 +845,7 @@ int dst_mst(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *edge_i, uin
         return fail(ctx, DST_ERR_STATE, "minimum spanning tree: more than n - 1 edges");
     if (finish && ne) {
         rc = walk_slabs(ctx, measure, true, set, set, plan.slabs, DST_OUT_TALLY, [&](const RowSlab &s) -> int {
-            HIP_TRY(ctx, launch_mst_gather(measure, static_cast<const uint32_t *>(ctx->pair_slab), s.first, n, s.rb, s.re,
+            HIP_TRY(ctx, launch_mst_gather(measure, static_cast<const uint32_t *>(ctx->pair_slab.ptr), s.first, n, s.rb, s.re,
                                            set.counts, b, ne, stream));
             return DST_OK;
         });

@@ -22,6 +22,7 @@ std::mutex g_create_mu;
 
 int publish_prep(dst_ctx *ctx, hipStream_t stream);
 int wait_for_other_runs(dst_ctx *ctx, hipStream_t stream);
+dst_ctx::Mark &mark_of(dst_ctx *ctx, hipStream_t stream);
 
 int fail(dst_ctx *ctx, int status, const std::string &msg)
 {
@@ -65,6 +66,61 @@ int ensure_bytes(dst_ctx *ctx, void **ptr, size_t *have, size_t want)
     }
     HIP_TRY(ctx, hipMalloc(ptr, want));
     *have = want;
+    return DST_OK;
+}
+
+// the one place a context-level buffer is allocated and the one place it is freed (Grown, dst_ctx.h); the device path
+// fails as ensure_bytes does, a page-locked buffer with the caller's `what`
+int GrownBase::grow(dst_ctx *ctx, size_t want, const char *what)
+{
+    if (bytes >= want)
+        return DST_OK;
+    if (const hipError_t e = release())
+        return fail_hip(ctx, e, pinned ? "hipHostFree(ptr)" : "hipFree(*ptr)");
+    const hipError_t e = pinned ? hipHostMalloc(&ptr, want, hipHostMallocDefault) : hipMalloc(&ptr, want);
+    if (e != hipSuccess) {
+        ptr = nullptr;
+        if (!what)
+            return fail_hip(ctx, e, pinned ? "hipHostMalloc(ptr, want)" : "hipMalloc(ptr, want)");
+        (void)hipGetLastError();
+        return fail(ctx, DST_ERR_NOMEM, std::string(what) + ": cannot allocate " + std::to_string(want) + " bytes of page-locked memory");
+    }
+    bytes = want;
+    return DST_OK;
+}
+
+hipError_t GrownBase::release()
+{
+    const hipError_t e = !ptr ? hipSuccess : pinned ? hipHostFree(ptr) : hipFree(ptr);
+    if (e == hipSuccess) {
+        ptr = nullptr;
+        bytes = 0;
+    }
+    return e;
+}
+
+int two_sets(dst_ctx *ctx, bool square, int row_slot, int col_slot, TwoSets &out, bool same_len, bool count_32)
+{
+    if (square) {
+        row_slot = 0;
+        col_slot = 0;
+    } else {
+        if (row_slot < 0 || row_slot > 1 || col_slot < 0 || col_slot > 1)
+            return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
+        if (row_slot == col_slot)
+            return fail(ctx, DST_ERR_ARG, "row_slot == col_slot: use the square form for one set");
+    }
+    DeviceSet &rows = ctx->set[row_slot], &cols = ctx->set[col_slot];
+    if (!rows.loaded || !cols.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    if (same_len && rows.len != cols.len) {
+        char msg[128];  // src/fastaio.rs:93-95
+        std::snprintf(msg, sizeof msg, "Different length sequences in alignment(s): %zu vs %zu", rows.len, cols.len);
+        return fail(ctx, DST_ERR_STATE, msg);
+    }
+    if (count_32 && (rows.n >= 0xFFFFFFFFull || cols.n >= 0xFFFFFFFFull))
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    out = TwoSets{row_slot, col_slot, &rows, &cols};
     return DST_OK;
 }
 
@@ -364,11 +420,12 @@ int prepare_schedule(dst_ctx *ctx, bool square, uint64_t rb, uint64_t re, uint64
                      hipStream_t stream, const void **d_blocks, uint32_t *nblocks)
 {
     constexpr size_t kMaxSchedules = 16;
+    const uint64_t user = mark_of(ctx, stream).id;   // (recorded behind the launch: note_run)
     for (auto &s : ctx->schedules) {
         if (s.square == square && s.rb == rb && s.re == re && s.ncols == ncols && s.bm == bm && s.bn == bn) {
             s.last_use = ++ctx->schedule_clock;
-            if (std::find(s.users.begin(), s.users.end(), stream) == s.users.end())
-                s.users.push_back(stream);
+            if (std::find(s.users.begin(), s.users.end(), user) == s.users.end())
+                s.users.push_back(user);
             *d_blocks = s.d_blocks;
             *nblocks = s.nblocks;
             return DST_OK;
@@ -400,41 +457,39 @@ int prepare_schedule(dst_ctx *ctx, bool square, uint64_t rb, uint64_t re, uint64
     s.last_use = ++ctx->schedule_clock;
     if (ctx->schedules.size() >= kMaxSchedules) {
         // evict the least recently used; a kernel queued on any of the streams that launched with it may still read it
-        // (sub-slab launches alternate between streams, the caller may bring its own): those streams are waited for — not
-        // the device: a loop over row slabs (the CLI's text calls) evicts on every call.  A stream that is gone: the device.
+        // (sub-slab launches alternate between streams, the caller may bring its own): those streams' marks are waited
+        // for — not the device: a loop over row slabs (the CLI's text calls) evicts on every call.  Streams are in order,
+        // so a mark recorded behind a later launch covers this one; a mark that is gone was complete (mark_of).
         size_t victim = 0;
         for (size_t k = 1; k < ctx->schedules.size(); ++k)
             if (ctx->schedules[k].last_use < ctx->schedules[victim].last_use)
                 victim = k;
-        for (hipStream_t u : ctx->schedules[victim].users)
-            if (hipStreamSynchronize(u) != hipSuccess) {
-                (void)hipGetLastError();
-                HIP_TRY(ctx, hipDeviceSynchronize());
-                break;
-            }
-        // its buffer is recycled when it is big enough (row slabs of one run have similar tile counts)
-        void *spare = ctx->schedules[victim].d_blocks;
-        const size_t spare_bytes = ctx->schedules[victim].bytes;
-        ctx->schedules.erase(ctx->schedules.begin() + (long)victim);
-        if (spare && spare_bytes >= bytes && count) {
-            s.d_blocks = spare;
-            s.bytes = spare_bytes;
-        } else if (spare) {
-            HIP_TRY(ctx, hipFree(spare));
+        // The context's own stream records no mark behind a dense launch (note_run): it is waited for itself.
+        for (const auto &m : ctx->marks) {
+            const auto &users = ctx->schedules[victim].users;
+            if (std::find(users.begin(), users.end(), m.id) == users.end())
+                continue;
+            if (m.key == ctx->stream)
+                HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+            else if (m.event.e)
+                HIP_TRY(ctx, hipEventSynchronize(m.event));
         }
+        // its buffer is recycled when it is big enough (row slabs of one run have similar tile counts)
+        if (count)
+            s.d_blocks = std::move(ctx->schedules[victim].d_blocks);
+        ctx->schedules.erase(ctx->schedules.begin() + (long)victim);
     }
     if (count) {
-        if (!s.d_blocks) {
-            s.bytes = bytes + bytes / 4;
-            HIP_TRY(ctx, hipMalloc(&s.d_blocks, s.bytes));
-        }
+        if (s.d_blocks.bytes < bytes)
+            if (int rc = s.d_blocks.grow(ctx, bytes + bytes / 4))
+                return rc;
         // pageable source: the copy is complete on return, later kernels on any stream see it
         HIP_TRY(ctx, hipMemcpy(s.d_blocks, src, bytes, hipMemcpyHostToDevice));
     }
-    s.users.assign(1, stream);
-    ctx->schedules.push_back(s);
+    s.users.assign(1, user);
     *d_blocks = s.d_blocks;
     *nblocks = s.nblocks;
+    ctx->schedules.push_back(std::move(s));
     return DST_OK;
 }
 
@@ -465,11 +520,10 @@ int ensure_lut(dst_ctx *ctx)
         return DST_OK;
     auto lut = std::make_unique<ConsensusLut>();
     build_consensus_lut(*lut);
-    HIP_TRY(ctx, hipMalloc((void **)&ctx->d_lut, sizeof(ConsensusLut)));
+    if (int rc = ctx->d_lut.grow(ctx, sizeof(ConsensusLut)))
+        return rc;
     HIP_TRY(ctx, hipMemcpy(ctx->d_lut, lut.get(), sizeof(ConsensusLut), hipMemcpyHostToDevice));
-    if (!ctx->d_total)   // (the text path may have made it already)
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_total, 2 * sizeof(unsigned long long)));  // [0] list entries, [1] overflow entries
-    return DST_OK;
+    return ctx->d_total.grow(ctx, 2 * sizeof(unsigned long long));   // (the text path may have made it already)
 }
 
 // ---- ordering between streams without host synchronisation -----------------------------------------
@@ -479,43 +533,62 @@ int ensure_lut(dst_ctx *ctx)
 // hipStreamSynchronize here: six host round trips per step, 0.4 ms of a 0.9 ms step at 10,000 x 30,000.)
 int publish_prep(dst_ctx *ctx, hipStream_t stream)
 {
-    HIP_TRY(ctx, hipEventRecord(ctx->prep_event, stream));
+    HIP_TRY(ctx, ctx->prep_event.record(stream));
     ctx->prep_stream = stream;
-    ctx->prep_pending = true;
     static const bool host_sync = std::getenv("DST_HOST_SYNC") != nullptr;  // measurement knob: the r02a behaviour
     if (host_sync)
-        HIP_TRY(ctx, hipStreamSynchronize(stream));
+        HIP_TRY(ctx, hipEventSynchronize(ctx->prep_event));
     return DST_OK;
 }
 
 int order_after_prep(dst_ctx *ctx, hipStream_t stream)
 {
-    if (ctx->prep_pending && ctx->prep_stream != stream)
+    if (ctx->prep_event.e && ctx->prep_stream != stream)
         HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->prep_event, 0));
     return DST_OK;
 }
 
 int wait_for_other_runs(dst_ctx *ctx, hipStream_t stream)
 {
-    for (auto &r : ctx->recent)
-        if (r.used && r.stream != stream)
-            HIP_TRY(ctx, hipStreamWaitEvent(stream, r.event, 0));
+    for (auto &m : ctx->marks)
+        if (m.event.e && m.key != stream)
+            HIP_TRY(ctx, hipStreamWaitEvent(stream, m.event, 0));
     return DST_OK;
 }
 
+// The mark of `stream` (dst_ctx::Mark).  A stream not seen before gets a new one; when that makes more than a few, the
+// marks whose event has completed go first, and with them their entries in the schedules' user lists: everything
+// queued before a completed mark has finished, so nobody has to wait for it again.
+dst_ctx::Mark &mark_of(dst_ctx *ctx, hipStream_t stream)
+{
+    constexpr size_t kMarksKept = 4;
+    for (auto &m : ctx->marks)
+        if (m.key == stream)
+            return m;
+    for (size_t k = ctx->marks.size() >= kMarksKept ? ctx->marks.size() : 0; k-- > 0;) {
+        const dst_ctx::Mark &m = ctx->marks[k];
+        if (m.key == ctx->stream)   // (stays: its dense launches are waited for on the stream, not by an event)
+            continue;
+        if (m.event.e && hipEventQuery(m.event) != hipSuccess) {
+            (void)hipGetLastError();   // (hipErrorNotReady is an answer, not a failure for the next launch's check to find)
+            continue;
+        }
+        for (auto &s : ctx->schedules)
+            s.users.erase(std::remove(s.users.begin(), s.users.end(), m.id), s.users.end());
+        ctx->marks.erase(ctx->marks.begin() + (long)k);
+    }
+    ctx->marks.emplace_back();
+    ctx->marks.back().id = ++ctx->mark_ids;
+    ctx->marks.back().key = stream;
+    return ctx->marks.back();
+}
+
+// behind a run's pair launch: what a later eviction of its tile schedule, or a rebuild of what it reads on another
+// stream, waits for.  (A call that fails between its launch and this, at timer_end, leaves the launch without a mark, as
+// it left it without a recent-run event before: such a failure is the runtime's, and the context is not used on.)
 int note_run(dst_ctx *ctx, hipStream_t stream)
 {
-    dst_ctx::Recent *slot = nullptr;
-    for (auto &r : ctx->recent)
-        if (r.used && r.stream == stream)
-            slot = &r;
-    if (!slot) {
-        slot = &ctx->recent[ctx->recent_next % 4];
-        ctx->recent_next += 1;
-    }
-    HIP_TRY(ctx, hipEventRecord(slot->event, stream));
-    slot->stream = stream;
-    slot->used = true;
+    HIP_TRY(ctx, mark_of(ctx, stream).event.record(stream));
     return DST_OK;
 }
 
@@ -608,7 +681,7 @@ int ensure_index(dst_ctx *ctx, DeviceSet &s, DeviceSet &refset, bool want_sites,
     if (!rc && want_sites)
         rc = ensure_bytes(ctx, (void **)&s.site.inl, &s.site.inl_cap, std::max<size_t>(n_buckets, 1) * 2 * sizeof(uint4));
     if (!rc)
-        rc = ensure_bytes(ctx, (void **)&ctx->scan_tmp, &ctx->scan_tmp_bytes, scan_tmp_words(s.n + 1) * sizeof(uint32_t));
+        rc = ctx->scan_tmp.grow(ctx, scan_tmp_words(s.n + 1) * sizeof(uint32_t));
     if (rc)
         return rc;
     s.rec.valid = false;
@@ -659,7 +732,7 @@ int ensure_index(dst_ctx *ctx, DeviceSet &s, DeviceSet &refset, bool want_sites,
         return rc;
     // (the scan also clears the counters behind it: [0..1] the list total of the count pass, [2..3] the overflow entries)
     HIP_TRY(ctx, launch_exclusive_scan(s.rec.off, s.n + 1, ctx->scan_tmp, stream, scan_src0, scan_src1,
-                                       reinterpret_cast<uint32_t *>(ctx->d_total), 4));
+                                       static_cast<uint32_t *>(ctx->d_total.ptr), 4));
     if (from_pack)   // the entries are in the pack's slots already
         HIP_TRY(ctx, launch_slot_fill(s, refset.ref.planes, refset.ref.hot_planes, without_hot, s.rec.off, s.rec.ent,
                                       want_sites ? s.rec.range_start : nullptr, stream));
@@ -987,9 +1060,9 @@ int run_sets(dst_ctx *ctx, int measure, bool square, DeviceSet &rows, DeviceSet 
                 rc = ensure_hot(ctx, rows, cols, stream);
             const int hot_kind = wide ? DST_OUT_TALLY : DST_OUT_TALLY16;
             const size_t hot_bytes = dst_out_bytes(measure, hot_kind, total_pairs);
-            if (!rc && ctx->hot_tally_bytes < hot_bytes) {
+            if (!rc && ctx->hot_tally.bytes < hot_bytes) {
                 HIP_TRY(ctx, hipDeviceSynchronize());
-                rc = ensure_bytes(ctx, &ctx->hot_tally, &ctx->hot_tally_bytes, hot_bytes);
+                rc = ctx->hot_tally.grow(ctx, hot_bytes);
             }
             if (rc)
                 return rc;
@@ -1008,16 +1081,16 @@ int run_sets(dst_ctx *ctx, int measure, bool square, DeviceSet &rows, DeviceSet 
             hp.row_end = re;
             hp.out_base = square ? square_row_start(cols.n, rb) : 0;
             hp.out_kind = hot_kind;
-            hp.d_out = ctx->hot_tally;
+            hp.d_out = ctx->hot_tally.ptr;
             hp.d_blocks = d_hblocks;
             hp.nblocks = hblocks;
             hp.ksplit = 1;
             // one scratch buffer per context: a hybrid run on another stream must be done reading it first
-            if (ctx->hot_used)
+            if (ctx->hot_free.e)
                 HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->hot_free, 0));
             if (hblocks)
                 HIP_TRY(ctx, launch_pairs(measure, ctx->variant, hp, stream));
-            d_hot = ctx->hot_tally;
+            d_hot = ctx->hot_tally.ptr;
         }
         // F_k: every (cold) site where the reference is a known base adds f_k(base, base)
         int unit[4];
@@ -1052,10 +1125,8 @@ int run_sets(dst_ctx *ctx, int measure, bool square, DeviceSet &rows, DeviceSet 
             HIP_TRY(ctx, launch_consensus_pairs(measure, cl, f_words, stream));
             if (int rc_t = timer_end(ctx, 0, stream))
                 return rc_t;
-            if (d_hot) {
-                HIP_TRY(ctx, hipEventRecord(ctx->hot_free, stream));
-                ctx->hot_used = true;
-            }
+            if (d_hot)
+                HIP_TRY(ctx, ctx->hot_free.record(stream));
             rc = note_run(ctx, stream);  // a rebuild of the lists on another stream waits for this run
             if (rc)
                 return rc;
@@ -1118,18 +1189,18 @@ int run_sets(dst_ctx *ctx, int measure, bool square, DeviceSet &rows, DeviceSet 
     if (nblocks && ksplit > 1) {
         if (f64_out) {
             const size_t want = (size_t)total_pairs * tally_width(measure) * sizeof(uint32_t);
-            if (ctx->scratch_bytes < want) {
+            if (ctx->scratch.bytes < want) {
                 HIP_TRY(ctx, hipDeviceSynchronize());  // an earlier run (any stream) may still read the old one
-                rc = ensure_bytes(ctx, (void **)&ctx->scratch, &ctx->scratch_bytes, want);
+                rc = ctx->scratch.grow(ctx, want);
                 if (rc)
                     return rc;
             }
             // one meeting buffer per context: a run on another stream must be done with it first
-            if (ctx->scratch_used)
+            if (ctx->scratch_free.e)
                 HIP_TRY(ctx, hipStreamWaitEvent(stream, ctx->scratch_free, 0));
             HIP_TRY(ctx, hipMemsetAsync(ctx->scratch, 0, want, stream));
             pl.out_kind = DST_OUT_TALLY;
-            pl.d_out = ctx->scratch;
+            pl.d_out = ctx->scratch.ptr;
         } else {
             HIP_TRY(ctx, hipMemsetAsync(d_out, 0, need, stream));
         }
@@ -1142,9 +1213,12 @@ int run_sets(dst_ctx *ctx, int measure, bool square, DeviceSet &rows, DeviceSet 
             return rc_t;
         if (ksplit > 1 && f64_out) {
             HIP_TRY(ctx, launch_finalize(measure, pl, ctx->scratch, false, d_out, stream));
-            HIP_TRY(ctx, hipEventRecord(ctx->scratch_free, stream));
-            ctx->scratch_used = true;
+            HIP_TRY(ctx, ctx->scratch_free.record(stream));
         }
+        // what the eviction of this launch's tile schedule waits for; the context's own stream needs none (the eviction
+        // waits for that stream itself), so the analyses' slabs and the synchronous forms record nothing more than before
+        if (stream != ctx->stream && (rc = note_run(ctx, stream)))
+            return rc;
     }
     if (!stream_v)
         HIP_TRY(ctx, hipStreamSynchronize(stream));
@@ -1169,7 +1243,7 @@ int run_host(dst_ctx *ctx, int measure, bool square, int row_slot, int col_slot,
         return fail(ctx, DST_ERR_ARG, "null output pointer");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // one grow-only device buffer per context for the host-buffer forms (no allocation per call)
-    int rc = ensure_bytes(ctx, &ctx->host_out, &ctx->host_out_bytes, bytes);
+    int rc = ctx->host_out.grow(ctx, bytes);
     if (rc)
         return rc;
     rc = run_common(ctx, measure, square, row_slot, col_slot, rb, re, out_kind, ctx->host_out, bytes, (void *)ctx->stream);
@@ -1184,6 +1258,23 @@ int run_host(dst_ctx *ctx, int measure, bool square, int row_slot, int col_slot,
 }
 
 }  // namespace dst
+
+// what is no Grown or Event member: the sets, the timing events, the stream
+dst_ctx::~dst_ctx()
+{
+    free_set(set[0]);
+    free_set(set[1]);
+    free_set(boot);
+    for (auto &t : timer)
+        for (int k = 0; k < kTimerRing; ++k) {
+            if (t.begin[k])
+                (void)hipEventDestroy(t.begin[k]);
+            if (t.end[k])
+                (void)hipEventDestroy(t.end[k]);
+        }
+    if (stream)
+        (void)hipStreamDestroy(stream);
+}
 
 extern "C" {
 
@@ -1242,21 +1333,17 @@ int dst_create(int device, dst_ctx **out)
         for (int k = 0; k < dst_ctx::kTimerRing; ++k)
             if ((e = hipEventCreate(&t.begin[k])) != hipSuccess || (e = hipEventCreate(&t.end[k])) != hipSuccess)
                 return bail(c, e, "hipEventCreate");
-    if ((e = hipMalloc((void **)&c->d_first_bad, sizeof(unsigned long long))) != hipSuccess)
-        return bail(c, e, "hipMalloc");
-    if ((e = hipHostMalloc((void **)&c->h_report, 16 * sizeof(unsigned long long), hipHostMallocDefault)) != hipSuccess)
-        return bail(c, e, "hipHostMalloc");
+    int rc = c->d_first_bad.grow(c, sizeof(unsigned long long));
+    if (!rc)
+        rc = c->h_report.grow(c, 16 * sizeof(unsigned long long));
+    if (rc) {
+        std::lock_guard<std::mutex> lk(g_create_mu);
+        g_create_err = c->err;
+        delete c;
+        return rc;
+    }
     if ((e = hipHostGetDevicePointer((void **)&c->d_report, c->h_report, 0)) != hipSuccess)
         return bail(c, e, "hipHostGetDevicePointer");
-    if ((e = hipEventCreateWithFlags(&c->scratch_free, hipEventDisableTiming)) != hipSuccess)
-        return bail(c, e, "hipEventCreate");
-    if ((e = hipEventCreateWithFlags(&c->hot_free, hipEventDisableTiming)) != hipSuccess)
-        return bail(c, e, "hipEventCreate");
-    if ((e = hipEventCreateWithFlags(&c->prep_event, hipEventDisableTiming)) != hipSuccess)
-        return bail(c, e, "hipEventCreate");
-    for (auto &r : c->recent)
-        if ((e = hipEventCreateWithFlags(&r.event, hipEventDisableTiming)) != hipSuccess)
-            return bail(c, e, "hipEventCreate");
     *out = c;
     return DST_OK;
 }
@@ -1267,56 +1354,7 @@ int dst_destroy(dst_ctx *ctx)
         return DST_OK;
     (void)hipSetDevice(ctx->device);
     (void)hipDeviceSynchronize();
-    free_set(ctx->set[0]);
-    free_set(ctx->set[1]);
-    free_set(ctx->boot);
-    if (ctx->stage)
-        (void)hipFree(ctx->stage);
-    for (auto &s : ctx->schedules)
-        if (s.d_blocks)
-            (void)hipFree(s.d_blocks);
-    for (auto &sh : ctx->shared)
-        for (void *b : {sh.send, sh.recv, (void *)sh.off_local})
-            if (b)
-                (void)hipFree(b);
-    for (void *b : {(void *)ctx->d_lut, (void *)ctx->d_total, (void *)ctx->scan_tmp, ctx->host_out, ctx->hot_tally, ctx->text_res,
-                    ctx->text_num, (void *)ctx->text_len, (void *)ctx->text_scan, (void *)ctx->text_buf, (void *)ctx->text_flag, ctx->text_ties,
-                    (void *)ctx->ids[0].off, (void *)ctx->ids[0].chars, (void *)ctx->ids[1].off, (void *)ctx->ids[1].chars, ctx->pair_slab, ctx->nn_lists,
-                    ctx->cl_work, ctx->mst_work, ctx->dg_work, ctx->links_work, ctx->summary_work, ctx->ps_batch, ctx->ps_window})
-        if (b)
-            (void)hipFree(b);
-    if (ctx->links_host)
-        (void)hipHostFree(ctx->links_host);
-    for (void *b : {ctx->ps_batch_host, ctx->ps_window_host})
-        if (b)
-            (void)hipHostFree(b);
-    if (ctx->scratch)
-        (void)hipFree(ctx->scratch);
-    if (ctx->text_ties_host)
-        (void)hipHostFree(ctx->text_ties_host);
-    if (ctx->scratch_free)
-        (void)hipEventDestroy(ctx->scratch_free);
-    if (ctx->hot_free)
-        (void)hipEventDestroy(ctx->hot_free);
-    if (ctx->prep_event)
-        (void)hipEventDestroy(ctx->prep_event);
-    for (auto &r : ctx->recent)
-        if (r.event)
-            (void)hipEventDestroy(r.event);
-    if (ctx->d_first_bad)
-        (void)hipFree(ctx->d_first_bad);
-    if (ctx->h_report)
-        (void)hipHostFree(ctx->h_report);
-    for (auto &t : ctx->timer)
-        for (int k = 0; k < dst_ctx::kTimerRing; ++k) {
-            if (t.begin[k])
-                (void)hipEventDestroy(t.begin[k]);
-            if (t.end[k])
-                (void)hipEventDestroy(t.end[k]);
-        }
-    if (ctx->stream)
-        (void)hipStreamDestroy(ctx->stream);
-    delete ctx;
+    delete ctx;   // (every buffer and event goes with its member)
     return DST_OK;
 }
 
@@ -1429,7 +1467,7 @@ int dst_upload(dst_ctx *ctx, int slot, const uint8_t *codes, size_t n, size_t le
     const size_t pitch = ((len + 127) / 128) * 128;
     const size_t want = std::max<size_t>(pitch * n, 128) + (base_counts ? n * 16 : 0);
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    int rc = ensure_bytes(ctx, (void **)&ctx->stage, &ctx->stage_bytes, want);
+    int rc = ctx->stage.grow(ctx, want);
     if (rc)
         return rc;
     if (len)
@@ -1443,11 +1481,8 @@ int dst_upload(dst_ctx *ctx, int slot, const uint8_t *codes, size_t n, size_t le
     rc = pack_from_device(ctx, slot, ctx->stage, n, len, pitch, d_counts, ctx->stream);
     // the bytes are not needed once they are packed: a large staging buffer (a whole loaded set) is given back, a
     // small one (streamed batches) is kept for the next upload
-    if (ctx->stage_bytes > ((size_t)256 << 20)) {
-        (void)hipFree(ctx->stage);
-        ctx->stage = nullptr;
-        ctx->stage_bytes = 0;
-    }
+    if (ctx->stage.bytes > ((size_t)256 << 20))
+        (void)ctx->stage.release();
     return rc;
 }
 
@@ -1647,24 +1682,6 @@ int dst_differences(dst_ctx *ctx, int slot, const uint8_t *other, size_t len, ui
     return done(DST_OK);
 }
 
-// page-locked host memory of dst_pair_sites (grow-only)
-static int pair_sites_host(dst_ctx *ctx, void **ptr, size_t *have, size_t want)
-{
-    if (*have >= want)
-        return DST_OK;
-    if (*ptr)
-        HIP_TRY(ctx, hipHostFree(*ptr));
-    *ptr = nullptr;
-    *have = 0;
-    if (hipHostMalloc(ptr, want, hipHostMallocDefault) != hipSuccess) {
-        *ptr = nullptr;
-        (void)hipGetLastError();
-        return fail(ctx, DST_ERR_NOMEM, "pair sites: cannot allocate " + std::to_string(want) + " bytes of page-locked memory");
-    }
-    *have = want;
-    return DST_OK;
-}
-
 int dst_pair_sites(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, const uint32_t *row, const uint32_t *col,
                    uint64_t n_pairs, uint64_t *offsets, uint32_t *sites, uint8_t *bases, size_t cap_entries, uint64_t *total_out)
 {
@@ -1678,23 +1695,10 @@ int dst_pair_sites(dst_ctx *ctx, int measure, int square, int row_slot, int col_
         return fail(ctx, DST_ERR_ARG, "unknown measure");
     if ((sites == nullptr) != (bases == nullptr))
         return fail(ctx, DST_ERR_ARG, "sites and bases must both be given or both be NULL");
-    if (square) {
-        row_slot = 0;
-        col_slot = 0;
-    } else {
-        if (row_slot < 0 || row_slot > 1 || col_slot < 0 || col_slot > 1)
-            return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
-        if (row_slot == col_slot)
-            return fail(ctx, DST_ERR_ARG, "row_slot == col_slot: use the square form for one set");
-    }
-    DeviceSet &rows = ctx->set[row_slot], &cols = ctx->set[col_slot];
-    if (!rows.loaded || !cols.loaded)
-        return fail(ctx, DST_ERR_STATE, "set not uploaded");
-    if (rows.len != cols.len) {
-        char msg[128];  // src/fastaio.rs:93-95
-        std::snprintf(msg, sizeof msg, "Different length sequences in alignment(s): %zu vs %zu", rows.len, cols.len);
-        return fail(ctx, DST_ERR_STATE, msg);
-    }
+    TwoSets ts;
+    if (int rc = two_sets(ctx, square != 0, row_slot, col_slot, ts))
+        return rc;
+    DeviceSet &rows = *ts.rows, &cols = *ts.cols;
     if (rows.partial || cols.partial)
         return fail(ctx, DST_ERR_STATE, "a set uploaded with dst_upload_shared runs on the consensus path only (this rank holds "
                                         "the planes of its own records)");
@@ -1725,12 +1729,12 @@ int dst_pair_sites(dst_ctx *ctx, int measure, int square, int row_slot, int col_
     const size_t at_col = mb * 4, at_cnt = at_col + mb * 4, at_off = (at_cnt + mb * 4 + 255) / 256 * 256,
                  batch_bytes = at_off + (mb + 1) * 8;
     if (!rc)
-        rc = ensure_bytes(ctx, &ctx->ps_batch, &ctx->ps_batch_bytes, batch_bytes);
+        rc = ctx->ps_batch.grow(ctx, batch_bytes);
     if (!rc)
-        rc = pair_sites_host(ctx, &ctx->ps_batch_host, &ctx->ps_batch_host_bytes, batch_bytes);
+        rc = ctx->ps_batch_host.grow(ctx, batch_bytes, "pair sites");
     if (rc)
         return rc;
-    char *d_batch = static_cast<char *>(ctx->ps_batch), *h_batch = static_cast<char *>(ctx->ps_batch_host);
+    char *d_batch = ctx->ps_batch, *h_batch = ctx->ps_batch_host;
     PairSitesBuffers b{};
     b.row = reinterpret_cast<uint32_t *>(d_batch);
     b.col = reinterpret_cast<uint32_t *>(d_batch + at_col);
@@ -1757,15 +1761,15 @@ int dst_pair_sites(dst_ctx *ctx, int measure, int square, int row_slot, int col_
         if (write && fits && in_batch) {
             // one window of entries on the device and in page-locked memory: sites, then bases
             const uint64_t win = std::min<uint64_t>(in_batch, DST_PAIR_SITES_WINDOW);
-            rc = ensure_bytes(ctx, &ctx->ps_window, &ctx->ps_window_bytes, win * 5);
+            rc = ctx->ps_window.grow(ctx, win * 5);
             if (!rc)
-                rc = pair_sites_host(ctx, &ctx->ps_window_host, &ctx->ps_window_host_bytes, win * 5);
+                rc = ctx->ps_window_host.grow(ctx, win * 5, "pair sites");
             if (rc)
                 return rc;
-            const uint64_t wcap = std::min<uint64_t>(std::min(ctx->ps_window_bytes, ctx->ps_window_host_bytes) / 5, DST_PAIR_SITES_WINDOW);
-            b.sites = static_cast<uint32_t *>(ctx->ps_window);
-            b.bases = static_cast<uint8_t *>(ctx->ps_window) + wcap * 4;
-            char *h_win = static_cast<char *>(ctx->ps_window_host);
+            const uint64_t wcap = std::min<uint64_t>(std::min(ctx->ps_window.bytes, ctx->ps_window_host.bytes) / 5, DST_PAIR_SITES_WINDOW);
+            b.sites = static_cast<uint32_t *>(ctx->ps_window.ptr);
+            b.bases = static_cast<uint8_t *>(ctx->ps_window.ptr) + wcap * 4;
+            char *h_win = ctx->ps_window_host;
             for (uint64_t lo = 0; lo < in_batch; lo += wcap) {
                 const uint64_t hi = std::min(in_batch, lo + wcap), w = hi - lo;
                 HIP_TRY(ctx, launch_pair_sites_write(measure, rows, cols, (uint32_t)m, b, lo, hi, stream));

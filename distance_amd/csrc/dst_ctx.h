@@ -9,18 +9,90 @@
 
 using namespace dst;
 
+struct dst_ctx;
+
+namespace dst {
+
+// A buffer the context owns: device memory, or page-locked host memory.  Grow-only between uses: grow() keeps what is
+// big enough, else frees and allocates exactly `want` bytes (a caller that wants slack asks for it).  A failure leaves it
+// empty (capacity 0), with the runtime's sticky error cleared; `what` names the caller in the page-locked refusal
+// ("links: cannot allocate N bytes of page-locked memory").  Released when its owner goes (dst_destroy has waited for
+// the device by then), so a new buffer of the context is one member and its grow() calls, nothing else.
+struct GrownBase {
+    void *ptr = nullptr;
+    size_t bytes = 0;   // capacity
+    const bool pinned;
+    explicit GrownBase(bool pinned_) : pinned(pinned_) {}
+    GrownBase(GrownBase &&o) noexcept : ptr(o.ptr), bytes(o.bytes), pinned(o.pinned) { o.ptr = nullptr, o.bytes = 0; }
+    GrownBase &operator=(GrownBase &&o) noexcept
+    {
+        std::swap(ptr, o.ptr);   // (both of one kind: what was here goes with `o`)
+        std::swap(bytes, o.bytes);
+        return *this;
+    }
+    ~GrownBase() { (void)release(); }
+    int grow(dst_ctx *ctx, size_t want, const char *what = nullptr);
+    hipError_t release();
+};
+template <typename T = void, bool kPinned = false>
+struct Grown : GrownBase {
+    Grown() : GrownBase(kPinned) {}
+    operator T *() const { return static_cast<T *>(ptr); }
+};
+
+// An ordering event (no timing) of the context: made by its first record, destroyed with its owner.
+struct Event {
+    hipEvent_t e = nullptr;   // NULL: never recorded, nothing to wait for
+    Event() = default;
+    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
+    Event &operator=(Event &&o) noexcept
+    {
+        std::swap(e, o.e);
+        return *this;
+    }
+    ~Event()
+    {
+        if (e)
+            (void)hipEventDestroy(e);
+    }
+    hipError_t record(hipStream_t stream)
+    {
+        if (!e)
+            if (const hipError_t err = hipEventCreateWithFlags(&e, hipEventDisableTiming))
+                return err;
+        return hipEventRecord(e, stream);
+    }
+    operator hipEvent_t() const { return e; }
+};
+
+}  // namespace dst
+
 struct dst_ctx {
+    ~dst_ctx();   // (dst_api.cpp; after dst_destroy's wait for the device)
     int device = 0;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;   // the context's own: the one stream handle it ever synchronises
     DeviceSet set[2];
     DeviceSet boot;   // dst_nj_bootstrap's replicate: packed like a slot, never one (freed when the call ends)
     // staging for host uploads / unaligned device inputs
-    uint8_t *stage = nullptr;
-    size_t stage_bytes = 0;
-    unsigned long long *d_first_bad = nullptr;
+    Grown<uint8_t> stage;
+    Grown<unsigned long long> d_first_bad;
     // what an upload reports to the host (first invalid byte, the sample's statistics, the list totals): written by the
     // device into this page-locked block, so the upload's one synchronisation needs no device-to-host copy
-    unsigned long long *h_report = nullptr, *d_report = nullptr;
+    Grown<unsigned long long, true> h_report;
+    unsigned long long *d_report = nullptr;   // (the device's address of h_report)
+    // Streams other than its own the context only ever sees as an argument of the call that brought them (a caller's,
+    // a dst_stream's).  What outlives that call is a MARK: an event of the context's, recorded behind the stream's
+    // latest pair launch (note_run), and the handle's value as a key that is compared and never handed back to the
+    // runtime.  So a stream may be destroyed as soon as the work queued on it has completed.  A new stream that gets a
+    // destroyed stream's handle value re-records that stream's mark: a later point of a stream whose earlier work was
+    // complete, which is what a waiter wants.
+    struct Mark {
+        uint64_t id = 0;
+        hipStream_t key = nullptr;
+        Event event;
+    };
+    std::vector<Mark> marks;   // one per distinct stream seen; trimmed of completed ones when a new stream comes (mark_of)
+    uint64_t mark_ids = 0;
     // tile schedules already on the device, keyed by the launch geometry (multi-GPU runs cycle
     // through a few sub-slab ranges every step: no host sync or H2D on a hit)
     struct Schedule {
@@ -28,10 +100,9 @@ struct dst_ctx {
         uint64_t rb = 0, re = 0, ncols = 0;
         int bm = 0, bn = 0;  // dense tile shape; consensus-path tile lists: bm = rows per tile, bn = -1
         uint32_t nblocks = 0;
-        void *d_blocks = nullptr;
-        size_t bytes = 0;  // capacity of d_blocks
+        Grown<> d_blocks;
         uint64_t last_use = 0;
-        std::vector<hipStream_t> users;   // the streams whose launches read it (waited for before its buffer is recycled)
+        std::vector<uint64_t> users;   // the marks (by id) of the streams whose launches read it: waited for before its buffer is recycled
     };
     std::vector<Schedule> schedules;
     uint64_t schedule_clock = 0;
@@ -41,87 +112,58 @@ struct dst_ctx {
     int last_path = DST_PATH_DENSE;   // what the most recent run used
     dst_launch_info last_launch = {-1};   // ... and which kernel variant its pair launch was (dst_last_launch; path -1: none yet)
     // consensus path: tables, counters and scratch shared by the two sets
-    ConsensusLut *d_lut = nullptr;
-    unsigned long long *d_total = nullptr;
-    uint32_t *scan_tmp = nullptr;
-    size_t scan_tmp_bytes = 0;
-    void *hot_tally = nullptr;  // hybrid path: the dense kernels' tallies of the hot columns (grow-only)
-    size_t hot_tally_bytes = 0;
-    hipEvent_t hot_free = nullptr;  // recorded after the last reader of `hot_tally`
-    bool hot_used = false;
+    Grown<ConsensusLut> d_lut;
+    Grown<unsigned long long> d_total;   // [0] list entries, [1] overflow entries (the text path sums its lengths here too)
+    Grown<uint32_t> scan_tmp;
+    Grown<> hot_tally;   // hybrid path: the dense kernels' tallies of the hot columns
+    Event hot_free;      // recorded after the last reader of `hot_tally`
     // cross-stream ordering of derived data (dst_api.cpp: publish_prep / order_after_prep / wait_for_other_runs)
-    hipEvent_t prep_event = nullptr;
-    hipStream_t prep_stream = nullptr;
-    bool prep_pending = false;
-    struct Recent {
-        hipStream_t stream = nullptr;
-        hipEvent_t event = nullptr;
-        bool used = false;
-    } recent[4];
-    unsigned recent_next = 0;
-    void *host_out = nullptr;  // device staging of the *_host run forms (grow-only)
-    size_t host_out_bytes = 0;
+    Event prep_event;
+    hipStream_t prep_stream = nullptr;   // where prep_event was last recorded: a key, like Mark::key
+    Grown<> host_out;   // device staging of the *_host run forms
     int ksplit = 0;  // 0 = automatic split-L factor, >= 1 forced
-    uint32_t *scratch = nullptr;  // partial-tally meeting buffer of split-L f64 runs
-    size_t scratch_bytes = 0;
-    hipEvent_t scratch_free = nullptr;  // recorded after the last reader of `scratch`
-    bool scratch_used = false;
-    // TSV text on the device (dst_text.hip): the sets' record ids and grow-only scratch
+    Grown<uint32_t> scratch;   // partial-tally meeting buffer of split-L f64 runs
+    Event scratch_free;        // recorded after the last reader of `scratch`
+    // TSV text on the device (dst_text.hip): the sets' record ids and scratch
     struct Ids {
-        uint32_t *off = nullptr;  // [n + 1] into chars
-        char *chars = nullptr;
-        size_t off_bytes = 0, chars_bytes = 0;
+        Grown<uint32_t> off;   // [n + 1] into chars
+        Grown<char> chars;
         uint64_t n = 0;
     } ids[2];
-    void *text_res = nullptr;      // the slab's results (8 B per pair) or tallies (<= 16 B per pair)
-    void *text_num = nullptr;      // 32-byte number records
-    uint32_t *text_len = nullptr;  // line lengths -> offsets
-    uint32_t *text_scan = nullptr;
-    char *text_buf = nullptr;
-    uint32_t *text_flag = nullptr;   // [0] a value without a short text, [1] near ties noted, [2] placed (dst_text_matrix)
-    void *text_ties = nullptr;       // the slab's near ties (dst_text.hip: NearTie), device and page-locked host copies
-    void *text_ties_host = nullptr;
-    size_t text_res_bytes = 0, text_num_bytes = 0, text_len_bytes = 0, text_scan_bytes = 0, text_buf_bytes = 0;
-    size_t text_ties_bytes = 0, text_ties_host_bytes = 0;
+    Grown<> text_res;             // the slab's results (8 B per pair) or tallies (<= 16 B per pair)
+    Grown<> text_num;             // 32-byte number records
+    Grown<uint32_t> text_len;     // line lengths -> offsets
+    Grown<uint32_t> text_scan;
+    Grown<char> text_buf;
+    Grown<uint32_t> text_flag;    // [0] a value without a short text, [1] near ties noted, [2] placed (dst_text_matrix)
+    Grown<> text_ties;            // the slab's near ties (dst_text.hip: NearTie), device and page-locked host copies
+    Grown<void, true> text_ties_host;
     // the sets' {A,T,G,C} counts on the host (tn93 near ties are re-finalised there), valid while the epoch matches
     std::vector<uint32_t> text_counts[2];
     uint64_t text_counts_epoch[2] = {~0ull, ~0ull};
     uint64_t text_near_ties = 0, text_patched = 0;   // running totals (dst_text_stats)
     // dst_upload_shared (dst_shared.cpp): this rank's exchange block, everybody's blocks, and what the last exchange told
     struct Shared {
-        void *send = nullptr, *recv = nullptr;
-        uint32_t *off_local = nullptr;
-        size_t send_bytes = 0, recv_bytes = 0, off_local_bytes = 0;
+        Grown<> send, recv;
+        Grown<uint32_t> off_local;
         uint64_t last_biggest = 0;   // entries of the largest block of the previous shared upload (sizes the next one)
         uint64_t uploads = 0, fallbacks = 0;
     } shared[2];
     // the analyses (dst_analysis.cpp): the one slab scratch their pair kernels write, DST_OUT_TALLY or DST_OUT_DISTANCE as
-    // the call needs (grow-only; a call owns it until it returns, and every call waits for the stream before it does)
-    void *pair_slab = nullptr;
-    size_t pair_slab_bytes = 0;
-    // dst_nearest: the running lists (grow-only)
-    void *nn_lists = nullptr;
-    size_t nn_lists_bytes = 0;
-    // dst_clusters: the parent array + link counter (grow-only)
-    void *cl_work = nullptr;
-    size_t cl_work_bytes = 0;
-    // dst_mst: the component, best-edge and edge-list arrays (grow-only)
-    void *mst_work = nullptr;
-    size_t mst_work_bytes = 0;
-    // dst_dendrogram: the O(n) state beside the per-call square (grow-only)
-    void *dg_work = nullptr;
-    size_t dg_work_bytes = 0;
-    // dst_links: the block counts / offsets and one chunk of outputs on the device, the same chunk in page-locked host
-    // memory (both grow-only)
-    void *links_work = nullptr, *links_host = nullptr;
-    size_t links_work_bytes = 0, links_host_bytes = 0;
+    // the call needs (a call owns it until it returns, and every call waits for the stream before it does)
+    Grown<> pair_slab;
+    Grown<> nn_lists;       // dst_nearest: the running lists
+    Grown<> cl_work;        // dst_clusters: the parent array + link counter
+    Grown<> mst_work;       // dst_mst: the component, best-edge and edge-list arrays
+    Grown<> dg_work;        // dst_dendrogram: the O(n) state beside the per-call square
+    // dst_links: the block counts / offsets and one chunk of outputs on the device, the same chunk in page-locked host memory
+    Grown<> links_work;
+    Grown<char, true> links_host;
     // dst_pair_sites: one batch of pairs with its counts and offsets, one window of entries, and both again in page-locked
-    // host memory (all grow-only)
-    void *ps_batch = nullptr, *ps_window = nullptr, *ps_batch_host = nullptr, *ps_window_host = nullptr;
-    size_t ps_batch_bytes = 0, ps_window_bytes = 0, ps_batch_host_bytes = 0, ps_window_host_bytes = 0;
-    // dst_summary: the per-record counters and accumulators, the histogram and the totals (grow-only)
-    void *summary_work = nullptr;
-    size_t summary_work_bytes = 0;
+    // host memory
+    Grown<char> ps_batch, ps_window;
+    Grown<char, true> ps_batch_host, ps_window_host;
+    Grown<> summary_work;   // dst_summary: the per-record counters and accumulators, the histogram and the totals
     // HIP events around the pair kernel ([0]) and the pack kernel ([1]) of the most recent launches, recorded on the launch
     // stream: a ring, so that a caller timing many steps reads them ONCE at the end (dst_kernel_ms_mean) instead of
     // waiting for the device after every step
@@ -156,7 +198,14 @@ int fail_hip(dst_ctx *ctx, hipError_t e, const char *what);
             return dst::fail_hip((ctx), e_, #call); \
     } while (0)
 
-int ensure_bytes(dst_ctx *ctx, void **ptr, size_t *have, size_t want);
+int ensure_bytes(dst_ctx *ctx, void **ptr, size_t *have, size_t want);   // (a DeviceSet's own buffers and their *_cap)
+// The two sets of a call that takes (square, row_slot, col_slot): square means slot 0 against itself; else two different
+// slots in range.  Both must be loaded; same_len: and of one width; count_32: and of fewer than 2^32-1 records each.
+struct TwoSets {
+    int row_slot = 0, col_slot = 0;
+    DeviceSet *rows = nullptr, *cols = nullptr;
+};
+int two_sets(dst_ctx *ctx, bool square, int row_slot, int col_slot, TwoSets &out, bool same_len = true, bool count_32 = false);
 // the base planes a deferred upload left out, written before anything but the consensus path reads planes (dst_api.cpp)
 int ensure_planes(dst_ctx *ctx, DeviceSet &s, hipStream_t stream);
 void free_set(DeviceSet &s);

@@ -100,11 +100,11 @@ extern "C" int dst_upload_shared(dst_comm *comm, int slot, const void *d_codes_v
     const size_t n_ranges = (s.nchunks * kChunkSites + kBucketSites - 1) / kBucketSites;
     rc = ensure_bytes(ctx, (void **)&s.rec.pre_slots, &s.rec.pre_slots_cap, s.nchunks * s.npad * sizeof(uint4));
     if (!rc)
-        rc = ensure_bytes(ctx, (void **)&sh.send, &sh.send_bytes, block_bytes);
+        rc = sh.send.grow(ctx, block_bytes);
     if (!rc)
-        rc = ensure_bytes(ctx, (void **)&sh.recv, &sh.recv_bytes, block_bytes * (size_t)world);
+        rc = sh.recv.grow(ctx, block_bytes * (size_t)world);
     if (!rc)
-        rc = ensure_bytes(ctx, (void **)&sh.off_local, &sh.off_local_bytes, (lay.rmax + 2) * sizeof(uint32_t));
+        rc = sh.off_local.grow(ctx, (lay.rmax + 2) * sizeof(uint32_t));
     if (!rc)
         rc = ensure_bytes(ctx, (void **)&s.rec.off, &s.rec.off_cap, (n + 1) * sizeof(uint32_t));
     if (!rc)
@@ -114,7 +114,7 @@ extern "C" int dst_upload_shared(dst_comm *comm, int slot, const void *d_codes_v
     if (!rc)
         rc = ensure_bytes(ctx, (void **)&s.rec.range_start, &s.rec.range_cap, n_ranges * s.npad * sizeof(uint32_t));
     if (!rc)
-        rc = ensure_bytes(ctx, (void **)&ctx->scan_tmp, &ctx->scan_tmp_bytes, scan_tmp_words(n + 1) * sizeof(uint32_t));
+        rc = ctx->scan_tmp.grow(ctx, scan_tmp_words(n + 1) * sizeof(uint32_t));
     if (rc)
         return rc;
     // ---- this rank's share: reference from the bytes, pack + count, scan, lists straight into the block
@@ -138,7 +138,7 @@ extern "C" int dst_upload_shared(dst_comm *comm, int slot, const void *d_codes_v
     rc = timer_end(ctx, 1, stream);
     if (rc)
         return rc;
-    uint32_t *block = static_cast<uint32_t *>(sh.send);
+    uint32_t *block = static_cast<uint32_t *>(sh.send.ptr);
     HIP_TRY(ctx, launch_exclusive_scan(sh.off_local, count + 1, ctx->scan_tmp, stream, s.rec.pre_cold + rec_begin, s.rec.pre_hot + rec_begin));
     HIP_TRY(ctx, launch_shared_block(block, lay, s, rec_begin, count, sh.off_local, ctx->d_first_bad, stream));
     HIP_TRY(ctx, launch_slot_fill(s, s.ref.planes, s.ref.hot_planes, false, sh.off_local, block + lay.ent_at, nullptr, stream,
@@ -149,7 +149,7 @@ extern "C" int dst_upload_shared(dst_comm *comm, int slot, const void *d_codes_v
     rc = comm_allgather(comm, sh.send, sh.recv, block_bytes, stream);
     if (rc)
         return rc;
-    HIP_TRY(ctx, launch_shared_splice(static_cast<const uint32_t *>(sh.recv), lay, s, s.rec.pre_cold, ctx->scan_tmp, with_counts != 0,
+    HIP_TRY(ctx, launch_shared_splice(static_cast<const uint32_t *>(sh.recv.ptr), lay, s, s.rec.pre_cold, ctx->scan_tmp, with_counts != 0,
                                       ctx->d_report, stream));
     HIP_TRY(ctx, hipStreamSynchronize(stream));
     const unsigned long long first_bad = ctx->h_report[0], total = ctx->h_report[9], over = ctx->h_report[10];

@@ -83,21 +83,8 @@ void destroy(dst_stream *s)
     for (hipStream_t st : {s->s_in, s->s_compute, s->s_out})
         if (st)
             (void)hipStreamSynchronize(st);
-    // the context must not keep handles of the streams destroyed below: a later eviction of a tile schedule waits for its
-    // users (prepare_schedule), a rebuild for the recent runs' streams — the runtime aborts on a destroyed handle.  They
-    // are idle now, so there is nothing left to wait for.
-    dst_ctx *ctx = s->ctx;
-    for (hipStream_t st : {s->s_in, s->s_compute, s->s_out}) {
-        if (!st)
-            continue;
-        for (auto &sch : ctx->schedules)
-            sch.users.erase(std::remove(sch.users.begin(), sch.users.end(), st), sch.users.end());
-        for (auto &r : ctx->recent)
-            if (r.used && r.stream == st)
-                r.used = false;
-        if (ctx->prep_pending && ctx->prep_stream == st)
-            ctx->prep_pending = false;
-    }
+    // (the context keeps marks of these streams, events of its own, and no handle it would hand to the runtime again:
+    // dst_ctx::Mark.  They are idle now, so those events have completed.)
     for (auto &sl : s->slots) {
         if (sl.h_in) (void)hipHostFree(sl.h_in);
         if (sl.h_out) (void)hipHostFree(sl.h_out);

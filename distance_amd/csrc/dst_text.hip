@@ -368,6 +368,94 @@ int patch_near_ties(dst_ctx *ctx, int measure, int row_slot, int col_slot, int s
     return DST_OK;
 }
 
+// ---- the host steps dst_text_square / _rect and dst_text_matrix share ------------------------------------------------
+// jc69 / k80 / tn93: from the tallies, with the near ties of the 12th decimal left to the host (see the top of the file)
+void text_source(int measure, const DeviceSet &rows, uint64_t values, bool &tally16, int &res_kind, size_t &res_bytes,
+                 uint32_t &ties_cap)
+{
+    const bool from_tallies = measure == DST_JC69 || measure == DST_K80 || measure == DST_TN93;
+    tally16 = from_tallies && rows.len <= kNarrowMaxLen;
+    res_kind = !from_tallies ? DST_OUT_DISTANCE : tally16 ? DST_OUT_TALLY16 : DST_OUT_TALLY;
+    res_bytes = dst_out_bytes(measure, res_kind, values);
+    ties_cap = from_tallies ? (uint32_t)std::max<uint64_t>(4096, values / 16) : 0;
+}
+
+// the scratch of a slab: its results, the number records (num_bytes, 0: none), `words` lengths + 1 and their scan, the near ties
+int text_scratch(dst_ctx *ctx, size_t res_bytes, size_t num_bytes, uint64_t words, uint32_t ties_cap)
+{
+    int rc = ctx->text_res.grow(ctx, res_bytes);
+    if (!rc)
+        rc = ctx->text_num.grow(ctx, num_bytes);
+    if (!rc)
+        rc = ctx->text_len.grow(ctx, (words + 1) * sizeof(uint32_t));
+    if (!rc)
+        rc = ctx->text_scan.grow(ctx, scan_tmp_words(words + 1) * sizeof(uint32_t));
+    if (!rc)
+        rc = ctx->text_ties.grow(ctx, (size_t)ties_cap * sizeof(NearTie));
+    if (!rc)
+        rc = ctx->text_flag.grow(ctx, kTextFlagWords * sizeof(uint32_t));
+    if (!rc)
+        rc = ctx->d_total.grow(ctx, 2 * sizeof(unsigned long long));
+    return rc;
+}
+
+// tn93's base counts: on the device for the text kernels, on the host for the near ties
+int text_counts(dst_ctx *ctx, int row_slot, int col_slot, hipStream_t stream)
+{
+    for (int slot : {row_slot, col_slot}) {
+        DeviceSet &s = ctx->set[slot];
+        if (int rc = need_counts(ctx, s, stream))
+            return rc;
+        if (ctx->text_counts_epoch[slot] != s.epoch || ctx->text_counts[slot].size() != s.n * 4) {
+            ctx->text_counts[slot].resize(s.n * 4);
+            HIP_TRY(ctx, hipMemcpyAsync(ctx->text_counts[slot].data(), s.counts, s.n * 16, hipMemcpyDeviceToHost, stream));
+            HIP_TRY(ctx, hipStreamSynchronize(stream));
+            ctx->text_counts_epoch[slot] = s.epoch;
+        }
+    }
+    return DST_OK;
+}
+
+// behind the length pass: the text's size and the near ties' number come back (one wait), the slab is refused or gets its
+// text buffer and the page-locked near-tie buffer
+int text_measured(dst_ctx *ctx, uint64_t words, uint32_t ties_cap, size_t cap, hipStream_t stream, unsigned long long &total,
+                  uint32_t &n_ties)
+{
+    // the offsets are 32-bit: a slab's text must stay below 4 GB (checked against the un-scanned total first)
+    HIP_TRY(ctx, hipMemsetAsync(ctx->d_total, 0, 2 * sizeof(unsigned long long), stream));
+    HIP_TRY(ctx, launch_sum2_u32(ctx->text_len, ctx->text_len, words, ctx->d_total, stream));
+    uint32_t flags[2] = {0, 0};
+    HIP_TRY(ctx, hipMemcpyAsync(&total, ctx->d_total, sizeof total, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(flags, ctx->text_flag, sizeof flags, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (flags[0])
+        return fail(ctx, DST_ERR_STATE, "a value of this slab has no short {:.12} text (|v| >= 1.8e7): format it on the host");
+    n_ties = flags[1];
+    if (n_ties > ties_cap)   // (distances far above 1: the guard is relative)
+        return fail(ctx, DST_ERR_STATE, "too many values of this slab lie near a rounding boundary of the 12th decimal: format it on the host");
+    if (total >= (1ull << 32))
+        return fail(ctx, DST_ERR_ARG, "text slab too large (4 GB of text per call)");
+    if (total > cap)
+        return fail(ctx, DST_ERR_CAPACITY, "text buffer too small for the requested rows");
+    if (int rc = ctx->text_buf.grow(ctx, (size_t)total + 16))
+        return rc;
+    if (ctx->text_ties_host.bytes < (size_t)n_ties * sizeof(NearTie))
+        return ctx->text_ties_host.grow(ctx, std::max<size_t>((size_t)n_ties * 2, 8192) * sizeof(NearTie));
+    return DST_OK;
+}
+
+// the text has arrived in `out`: its length, and the near ties' second look
+int text_arrived(dst_ctx *ctx, int measure, int row_slot, int col_slot, int swap_ids, uint32_t n_ties, unsigned long long total,
+                 char *out, size_t cap, size_t *len)
+{
+    *len = (size_t)total;
+    ctx->text_near_ties += n_ties;
+    if (n_ties)
+        return patch_near_ties(ctx, measure, row_slot, col_slot, swap_ids, static_cast<const NearTie *>(ctx->text_ties_host.ptr),
+                               n_ties, out, cap, len);
+    return DST_OK;
+}
+
 int text_common(dst_ctx *ctx, int measure, bool square, int row_slot, int col_slot, uint64_t rb, uint64_t re, int swap_ids,
                 char *out, size_t cap, size_t *len)
 {
@@ -395,42 +483,16 @@ int text_common(dst_ctx *ctx, int measure, bool square, int row_slot, int col_sl
         return fail(ctx, DST_ERR_ARG, "text slab too large (at most 2^31 pairs and 65,535 rows per call)");
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     hipStream_t stream = ctx->stream;
-    // jc69 / k80 / tn93: from the tallies, with the near ties of the 12th decimal left to the host (see the top of the file)
-    const bool from_tallies = measure == DST_JC69 || measure == DST_K80 || measure == DST_TN93;
-    const bool tally16 = from_tallies && rows.len <= kNarrowMaxLen;
-    const int res_kind = !from_tallies ? DST_OUT_DISTANCE : tally16 ? DST_OUT_TALLY16 : DST_OUT_TALLY;
-    const size_t res_bytes = dst_out_bytes(measure, res_kind, pairs);
-    const uint32_t ties_cap = from_tallies ? (uint32_t)std::max<uint64_t>(4096, pairs / 16) : 0;
-    int rc = ensure_bytes(ctx, &ctx->text_res, &ctx->text_res_bytes, res_bytes);
-    if (!rc)
-        rc = ensure_bytes(ctx, (void **)&ctx->text_num, &ctx->text_num_bytes, pairs * 32);
-    if (!rc)
-        rc = ensure_bytes(ctx, (void **)&ctx->text_len, &ctx->text_len_bytes, (pairs + 1) * sizeof(uint32_t));
-    if (!rc)
-        rc = ensure_bytes(ctx, (void **)&ctx->text_scan, &ctx->text_scan_bytes, scan_tmp_words(pairs + 1) * sizeof(uint32_t));
-    if (!rc && ties_cap)
-        rc = ensure_bytes(ctx, &ctx->text_ties, &ctx->text_ties_bytes, (size_t)ties_cap * sizeof(NearTie));
-    if (!rc && !ctx->text_flag)
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->text_flag, kTextFlagWords * sizeof(uint32_t)));
-    if (!rc && !ctx->d_total)
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_total, 2 * sizeof(unsigned long long)));
+    bool tally16;
+    int res_kind;
+    size_t res_bytes;
+    uint32_t ties_cap;
+    text_source(measure, rows, pairs, tally16, res_kind, res_bytes, ties_cap);
+    int rc = text_scratch(ctx, res_bytes, pairs * 32, pairs, ties_cap);
+    if (!rc && measure == DST_TN93)
+        rc = text_counts(ctx, row_slot, col_slot, stream);
     if (rc)
         return rc;
-    if (measure == DST_TN93) {
-        // the base counts: on the device for number_kernel, on the host for the near ties
-        for (int slot : {row_slot, col_slot}) {
-            DeviceSet &s = ctx->set[slot];
-            rc = need_counts(ctx, s, stream);
-            if (rc)
-                return rc;
-            if (ctx->text_counts_epoch[slot] != s.epoch || ctx->text_counts[slot].size() != s.n * 4) {
-                ctx->text_counts[slot].resize(s.n * 4);
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->text_counts[slot].data(), s.counts, s.n * 16, hipMemcpyDeviceToHost, stream));
-                HIP_TRY(ctx, hipStreamSynchronize(stream));
-                ctx->text_counts_epoch[slot] = s.epoch;
-            }
-        }
-    }
     rc = run_sets(ctx, measure, square, rows, cols, rb, re, res_kind, ctx->text_res, res_bytes, stream);
     if (rc)
         return rc;
@@ -439,8 +501,8 @@ int text_common(dst_ctx *ctx, int measure, bool square, int row_slot, int col_sl
     const dim3 grid((unsigned)((widest + 255) / 256), (unsigned)(re - rb));
     HIP_TRY(ctx, hipMemsetAsync(ctx->text_flag, 0, 2 * sizeof(uint32_t), stream));
     HIP_TRY(ctx, hipMemsetAsync(ctx->text_len + pairs, 0, sizeof(uint32_t), stream));
-    NumText *nums = reinterpret_cast<NumText *>(ctx->text_num);
-    NearTie *d_ties = static_cast<NearTie *>(ctx->text_ties);
+    NumText *nums = static_cast<NumText *>(ctx->text_num.ptr);
+    NearTie *d_ties = static_cast<NearTie *>(ctx->text_ties.ptr);
 #define DST_NUMBER(SRC, T)                                                                                                  \
     hipLaunchKernelGGL((number_kernel<SRC, T>), grid, dim3(256), 0, stream, ctx->text_res, sh, rid.off, cid.off, rows.counts, \
                        cols.counts, nums, ctx->text_len, ctx->text_flag, d_ties, ties_cap)
@@ -462,38 +524,14 @@ int text_common(dst_ctx *ctx, int measure, bool square, int row_slot, int col_sl
         DST_NUMBER(DST_TN93, uint32_t);
 #undef DST_NUMBER
     HIP_TRY(ctx, hipGetLastError());
-    // the offsets are 32-bit: a slab's text must stay below 4 GB (checked against the un-scanned total first)
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_total, 0, 2 * sizeof(unsigned long long), stream));
-    HIP_TRY(ctx, launch_sum2_u32(ctx->text_len, ctx->text_len, pairs, ctx->d_total, stream));
     unsigned long long total = 0;
-    uint32_t flags[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(&total, ctx->d_total, sizeof total, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipMemcpyAsync(flags, ctx->text_flag, sizeof flags, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    if (flags[0])
-        return fail(ctx, DST_ERR_STATE, "a value of this slab has no short {:.12} text (|v| >= 1.8e7): format it on the host");
-    const uint32_t n_ties = flags[1];
-    if (n_ties > ties_cap)   // (distances far above 1: the guard is relative)
-        return fail(ctx, DST_ERR_STATE, "too many values of this slab lie near a rounding boundary of the 12th decimal: format it on the host");
-    if (total >= (1ull << 32))
-        return fail(ctx, DST_ERR_ARG, "text slab too large (4 GB of text per call)");
-    if (total > cap)
-        return fail(ctx, DST_ERR_CAPACITY, "text buffer too small for the requested rows");
-    rc = ensure_bytes(ctx, (void **)&ctx->text_buf, &ctx->text_buf_bytes, (size_t)total + 16);
+    uint32_t n_ties = 0;
+    rc = text_measured(ctx, pairs, ties_cap, cap, stream, total, n_ties);
     if (rc)
         return rc;
-    if (n_ties && ctx->text_ties_host_bytes < (size_t)n_ties * sizeof(NearTie)) {
-        if (ctx->text_ties_host)
-            HIP_TRY(ctx, hipHostFree(ctx->text_ties_host));
-        ctx->text_ties_host = nullptr;
-        ctx->text_ties_host_bytes = 0;
-        const size_t want = std::max<size_t>((size_t)n_ties * 2, 8192) * sizeof(NearTie);
-        HIP_TRY(ctx, hipHostMalloc(&ctx->text_ties_host, want, hipHostMallocDefault));
-        ctx->text_ties_host_bytes = want;
-    }
     HIP_TRY(ctx, launch_exclusive_scan(ctx->text_len, pairs + 1, ctx->text_scan, stream));
     hipLaunchKernelGGL(line_kernel, grid, dim3(256), 0, stream, sh, rid.off, rid.chars, cid.off, cid.chars, swap_ids,
-                       reinterpret_cast<const NumText *>(ctx->text_num), ctx->text_len, ctx->text_buf);
+                       nums, ctx->text_len, ctx->text_buf);
     HIP_TRY(ctx, hipGetLastError());
     if (n_ties) {
         hipLaunchKernelGGL(place_kernel, dim3((n_ties + 255) / 256), dim3(256), 0, stream, d_ties, n_ties, ctx->text_len);
@@ -502,12 +540,7 @@ int text_common(dst_ctx *ctx, int measure, bool square, int row_slot, int col_sl
     }
     HIP_TRY(ctx, hipMemcpyAsync(out, ctx->text_buf, (size_t)total, hipMemcpyDeviceToHost, stream));
     HIP_TRY(ctx, hipStreamSynchronize(stream));
-    *len = (size_t)total;
-    ctx->text_near_ties += n_ties;
-    if (n_ties)
-        return patch_near_ties(ctx, measure, row_slot, col_slot, swap_ids, static_cast<const NearTie *>(ctx->text_ties_host), n_ties,
-                               out, cap, len);
-    return DST_OK;
+    return text_arrived(ctx, measure, row_slot, col_slot, swap_ids, n_ties, total, out, cap, len);
 }
 
 // ---- dst_text_matrix: whole rows of a distance matrix, "<id>" then "<sep><value>" per column, then '\n'
@@ -673,17 +706,11 @@ int text_matrix(dst_ctx *ctx, int measure, bool square, int row_slot, int col_sl
         return fail(ctx, DST_ERR_ARG, "unknown measure");
     if (style != DST_MATRIX_TSV && style != DST_MATRIX_PHYLIP)
         return fail(ctx, DST_ERR_ARG, "unknown matrix style");
-    if (square) {
-        row_slot = col_slot = 0;
-    } else {
-        if (row_slot < 0 || row_slot > 1 || col_slot < 0 || col_slot > 1)
-            return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
-        if (row_slot == col_slot)
-            return fail(ctx, DST_ERR_ARG, "row_slot == col_slot: use the square form for one set");
-    }
-    DeviceSet &rows = ctx->set[row_slot], &cols = ctx->set[col_slot];
-    if (!rows.loaded || !cols.loaded)
-        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    TwoSets ts;
+    if (int rc0 = two_sets(ctx, square, row_slot, col_slot, ts, false))   // (the widths: run_sets, after the ids)
+        return rc0;
+    row_slot = ts.row_slot, col_slot = ts.col_slot;
+    DeviceSet &rows = *ts.rows, &cols = *ts.cols;
     dst_ctx::Ids &rid = ctx->ids[row_slot];
     if (!rid.off || rid.n != rows.n)
         return fail(ctx, DST_ERR_STATE, "record ids of the set not given (dst_set_ids)");
@@ -698,46 +725,23 @@ int text_matrix(dst_ctx *ctx, int measure, bool square, int row_slot, int col_sl
     hipStream_t stream = ctx->stream;
     const uint32_t n_chunks = (uint32_t)std::max<uint64_t>(1, (cols.n + kMatChunk - 1) / kMatChunk);
     const uint64_t n_words = (re - rb) * n_chunks;
-    const bool from_tallies = measure == DST_JC69 || measure == DST_K80 || measure == DST_TN93;
-    const bool tally16 = from_tallies && rows.len <= kNarrowMaxLen;
-    const int res_kind = !from_tallies ? DST_OUT_DISTANCE : tally16 ? DST_OUT_TALLY16 : DST_OUT_TALLY;
-    const size_t res_bytes = dst_out_bytes(measure, res_kind, cells);
-    const uint32_t ties_cap = from_tallies ? (uint32_t)std::max<uint64_t>(4096, cells / 16) : 0;
-    int rc = ensure_bytes(ctx, &ctx->text_res, &ctx->text_res_bytes, std::max<size_t>(res_bytes, 16));
-    if (!rc)
-        rc = ensure_bytes(ctx, (void **)&ctx->text_len, &ctx->text_len_bytes, (n_words + 1) * sizeof(uint32_t));
-    if (!rc)
-        rc = ensure_bytes(ctx, (void **)&ctx->text_scan, &ctx->text_scan_bytes, scan_tmp_words(n_words + 1) * sizeof(uint32_t));
-    if (!rc && ties_cap)
-        rc = ensure_bytes(ctx, &ctx->text_ties, &ctx->text_ties_bytes, (size_t)ties_cap * sizeof(NearTie));
-    if (!rc && !ctx->text_flag)
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->text_flag, kTextFlagWords * sizeof(uint32_t)));
-    if (!rc && !ctx->d_total)
-        HIP_TRY(ctx, hipMalloc((void **)&ctx->d_total, 2 * sizeof(unsigned long long)));
+    bool tally16;
+    int res_kind;
+    size_t res_bytes;
+    uint32_t ties_cap;
+    text_source(measure, rows, cells, tally16, res_kind, res_bytes, ties_cap);
+    int rc = text_scratch(ctx, std::max<size_t>(res_bytes, 16), 0, n_words, ties_cap);
+    if (!rc && measure == DST_TN93)
+        rc = text_counts(ctx, row_slot, col_slot, stream);
     if (rc)
         return rc;
-    if (measure == DST_TN93) {
-        // the base counts: on the device for matrix_kernel, on the host for the near ties
-        for (int slot : {row_slot, col_slot}) {
-            DeviceSet &s = ctx->set[slot];
-            rc = need_counts(ctx, s, stream);
-            if (rc)
-                return rc;
-            if (ctx->text_counts_epoch[slot] != s.epoch || ctx->text_counts[slot].size() != s.n * 4) {
-                ctx->text_counts[slot].resize(s.n * 4);
-                HIP_TRY(ctx, hipMemcpyAsync(ctx->text_counts[slot].data(), s.counts, s.n * 16, hipMemcpyDeviceToHost, stream));
-                HIP_TRY(ctx, hipStreamSynchronize(stream));
-                ctx->text_counts_epoch[slot] = s.epoch;
-            }
-        }
-    }
     // the square as a rectangle of the set against itself: both triangles and the diagonal in one run
     rc = run_sets(ctx, measure, false, rows, cols, rb, re, res_kind, ctx->text_res, res_bytes, stream);
     if (rc)
         return rc;
     const MatShape sh{cols.n, rb, n_chunks, square ? 1 : 0, style == DST_MATRIX_PHYLIP ? ' ' : '\t'};
     const dim3 grid(n_chunks, (unsigned)(re - rb));
-    NearTie *d_ties = static_cast<NearTie *>(ctx->text_ties);
+    NearTie *d_ties = static_cast<NearTie *>(ctx->text_ties.ptr);
     HIP_TRY(ctx, hipMemsetAsync(ctx->text_flag, 0, kTextFlagWords * sizeof(uint32_t), stream));
     HIP_TRY(ctx, hipMemsetAsync(ctx->text_len + n_words, 0, sizeof(uint32_t), stream));
     auto launch = [&](bool write) {
@@ -772,35 +776,11 @@ int text_matrix(dst_ctx *ctx, int measure, bool square, int row_slot, int col_sl
         return hipGetLastError();
     };
     HIP_TRY(ctx, launch(false));
-    // the offsets are 32-bit: a slab's text must stay below 4 GB (checked against the un-scanned total first)
-    HIP_TRY(ctx, hipMemsetAsync(ctx->d_total, 0, 2 * sizeof(unsigned long long), stream));
-    HIP_TRY(ctx, launch_sum2_u32(ctx->text_len, ctx->text_len, n_words, ctx->d_total, stream));
     unsigned long long total = 0;
-    uint32_t flags[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(&total, ctx->d_total, sizeof total, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipMemcpyAsync(flags, ctx->text_flag, sizeof flags, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(ctx, hipStreamSynchronize(stream));
-    if (flags[0])
-        return fail(ctx, DST_ERR_STATE, "a value of this slab has no short {:.12} text (|v| >= 1.8e7): format it on the host");
-    const uint32_t n_ties = flags[1];
-    if (n_ties > ties_cap)
-        return fail(ctx, DST_ERR_STATE, "too many values of this slab lie near a rounding boundary of the 12th decimal: format it on the host");
-    if (total >= (1ull << 32))
-        return fail(ctx, DST_ERR_ARG, "text slab too large (4 GB of text per call)");
-    if (total > cap)
-        return fail(ctx, DST_ERR_CAPACITY, "text buffer too small for the requested rows");
-    rc = ensure_bytes(ctx, (void **)&ctx->text_buf, &ctx->text_buf_bytes, (size_t)total + 16);
+    uint32_t n_ties = 0;
+    rc = text_measured(ctx, n_words, ties_cap, cap, stream, total, n_ties);
     if (rc)
         return rc;
-    if (n_ties && ctx->text_ties_host_bytes < (size_t)n_ties * sizeof(NearTie)) {
-        if (ctx->text_ties_host)
-            HIP_TRY(ctx, hipHostFree(ctx->text_ties_host));
-        ctx->text_ties_host = nullptr;
-        ctx->text_ties_host_bytes = 0;
-        const size_t want = std::max<size_t>((size_t)n_ties * 2, 8192) * sizeof(NearTie);
-        HIP_TRY(ctx, hipHostMalloc(&ctx->text_ties_host, want, hipHostMallocDefault));
-        ctx->text_ties_host_bytes = want;
-    }
     HIP_TRY(ctx, launch_exclusive_scan(ctx->text_len, n_words + 1, ctx->text_scan, stream));
     HIP_TRY(ctx, launch(true));
     uint32_t placed = 0;
@@ -811,12 +791,7 @@ int text_matrix(dst_ctx *ctx, int measure, bool square, int row_slot, int col_sl
     HIP_TRY(ctx, hipStreamSynchronize(stream));
     if (placed != n_ties)
         return fail(ctx, DST_ERR_STATE, "near ties of the two text passes differ");
-    *len = (size_t)total;
-    ctx->text_near_ties += n_ties;
-    if (n_ties)
-        return patch_near_ties(ctx, measure, row_slot, col_slot, 0, static_cast<const NearTie *>(ctx->text_ties_host), n_ties,
-                               out, cap, len);
-    return DST_OK;
+    return text_arrived(ctx, measure, row_slot, col_slot, 0, n_ties, total, out, cap, len);
 }
 
 }  // namespace
@@ -842,9 +817,9 @@ int dst_set_ids(dst_ctx *ctx, int slot, const char *chars, const uint64_t *offse
             return fail(ctx, DST_ERR_ARG, "id offsets must not decrease");
         off32[k] = (uint32_t)offsets[k];
     }
-    int rc = ensure_bytes(ctx, (void **)&ids.off, &ids.off_bytes, (n + 1) * sizeof(uint32_t));
+    int rc = ids.off.grow(ctx, (n + 1) * sizeof(uint32_t));
     if (!rc)
-        rc = ensure_bytes(ctx, (void **)&ids.chars, &ids.chars_bytes, std::max<size_t>(offsets[n], 1));
+        rc = ids.chars.grow(ctx, std::max<size_t>(offsets[n], 1));
     if (rc)
         return rc;
     HIP_TRY(ctx, hipMemcpy(ids.off, off32.data(), (n + 1) * sizeof(uint32_t), hipMemcpyHostToDevice));

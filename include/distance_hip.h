@@ -209,7 +209,10 @@ int dst_partition_rect(uint64_t n_rows, int parts, uint64_t *bounds);
 /* ---- run: replaces generate_pairs_* + the worker pools (src/lib.rs:367-474, 269-365) ----- */
 /* All pairs (i, j), row_begin <= i < row_end, i < j < n of slot 0, canonical order, written to
  * d_out (device memory) starting with pair (row_begin, row_begin+1).  Asynchronous on `stream`
- * (hipStream_t; NULL = context stream, then the call synchronises before returning). */
+ * (hipStream_t; NULL = context stream, then the call synchronises before returning).
+ * A stream of the caller's, here and in every other call that takes one, is used only during that call: the
+ * context keeps events of its own behind the work it queued, never the handle, so the caller may destroy the
+ * stream once the work queued on it has completed (and the context may outlive it). */
 int dst_run_square(dst_ctx *ctx, int measure, uint64_t row_begin, uint64_t row_end, int out_kind,
                    void *d_out, size_t out_capacity_bytes, void *stream);
 /* All pairs (i, j), i in rows [row_begin,row_end) of row_slot, j over every record of col_slot;

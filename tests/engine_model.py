@@ -48,12 +48,14 @@ OP_CLASS = {
     "bad_upload": "error", "err_text_capacity": "error", "err_width": "error", "err_nj_nonfinite": "error",
     "clusters_tiny_slabs": "error",
 }
+# operations only the directed sequences name (the walks draw from OP_CLASS, so the committed seeds stay the same walks)
+DIRECTED_OPS = {"links": "derived", "pair_sites": "derived"}
 # not operations of the library: what a directed sequence asserts about the engine's introspection
 CHECKS = ("expect", "snapshot")
 
 
 def op_class(op):
-    return OP_CLASS.get(op[0])
+    return OP_CLASS.get(op[0]) or DIRECTED_OPS.get(op[0])
 
 
 # ------------------------------------------------------------------------------------------------ inputs
@@ -195,7 +197,8 @@ def _stream_batches(op, model):
 
 
 def perform(eng, op, model, caller_stream=None):
-    """Run `op` on `eng`; the result as plain data, or ("error", status).  Uploads and knobs return None."""
+    """Run `op` on `eng`; the result as plain data, or ("error", status).  Uploads and knobs return None.
+    caller_stream: the Runner's streams, by number (Runner.caller_stream)."""
     import distance_amd as da
     try:
         return _perform(eng, op, model, caller_stream)
@@ -240,13 +243,14 @@ def _perform(eng, op, model, caller_stream):
         return eng.run_square(m, rb, re, tallies=tallies)
     if name == "run_square_device":
         import torch
-        _, m, rb, re = op
+        _, m, rb, re = op[:4]
+        stream = caller_stream(op[4] if len(op) > 4 else 0)      # (name, measure, rows, [which of the caller's streams])
         n, _ = eng.set_info(0)
         pairs = da.square_row_start(n, re) - da.square_row_start(n, rb)
         out = torch.zeros(max(pairs, 1), dtype=torch.float64, device="cuda")
         torch.cuda.synchronize()
-        eng.run_square_device(m, rb, re, out.data_ptr(), out.numel() * 8, stream=caller_stream.cuda_stream)
-        caller_stream.synchronize()
+        eng.run_square_device(m, rb, re, out.data_ptr(), out.numel() * 8, stream=stream.cuda_stream)
+        stream.synchronize()
         got = out[:pairs].cpu().numpy()
         return got.view(np.int64) if m in da.INT_MEASURES else got
     if name == "run_rect":
@@ -306,6 +310,15 @@ def _perform(eng, op, model, caller_stream):
     if name == "nearest":
         _, m, k, square, rs, cs = op
         return list(eng.nearest(m, k, square=square, row_slot=rs, col_slot=cs))
+    if name == "links":
+        _, m, thr, square, rs, cs, values, tallies = op
+        return list(eng.links(m, thr, square=square, row_slot=rs, col_slot=cs, values=values, tallies=tallies))
+    if name == "pair_sites":      # n_pairs pairs drawn from (seed, the sets' sizes): repeats and row == col among them
+        _, m, n_pairs, square, rs, cs, seed = op
+        n_rows, n_cols = eng.set_info(0 if square else rs)[0], eng.set_info(0 if square else cs)[0]
+        rng = np.random.default_rng([seed, 0x51735])
+        return list(eng.pair_sites(m, rng.integers(0, n_rows, n_pairs), rng.integers(0, n_cols, n_pairs), square=square,
+                                   row_slot=rs, col_slot=cs))
     if name == "clusters":
         _, m, thr = op
         labels, links = eng.clusters(m, thr)
@@ -359,7 +372,7 @@ def expected_error(op, model):
         slots = (op[2], op[3])
     elif name == "text_matrix":      # (name, measure, square, row slot, col slot, ...)
         slots = (0,) if op[2] else (op[3], op[4])
-    elif name == "nearest":          # (name, measure, k, square, row slot, col slot)
+    elif name in ("nearest", "links", "pair_sites"):     # (name, measure, k / threshold / pairs, square, row slot, col slot, ...)
         slots = (0,) if op[3] else (op[4], op[5])
     elif name in ("differences", "base_counts", "err_width"):
         slots = (op[1],)
@@ -367,7 +380,7 @@ def expected_error(op, model):
         slots = need[name]
     if any(s[k] is None for k in slots):
         return ERR_STATE
-    if name == "nearest" and not op[3] and slots[0] == slots[1]:
+    if name in ("nearest", "links", "pair_sites") and not op[3] and slots[0] == slots[1]:
         return ERR_ARG
     if name == "text_matrix" and not op[2] and slots[0] == slots[1]:
         return ERR_ARG
@@ -543,16 +556,16 @@ class Runner:
         self.checked_values = 0
         self.snapshot = None
         self.near_ties = 0
-        self._stream = None
+        self._streams = []          # the caller's streams: torch's, from its pool, alive as long as the Runner
 
     def close(self):
         self.eng.close()
 
-    def caller_stream(self):
-        if self._stream is None:
-            import torch
-            self._stream = torch.cuda.Stream()
-        return self._stream
+    def caller_stream(self, k=0):
+        import torch
+        while len(self._streams) <= k:
+            self._streams.append(torch.cuda.Stream())
+        return self._streams[k]
 
     def run(self, seq):
         for op in seq:
@@ -605,17 +618,15 @@ class Runner:
                     p.upload(k, m.slot[k].codes, m.slot[k].counts)
                 if m.ids_ok(k):
                     p.set_ids(k, m.ids[k])
-            return perform(p, op, m, self._stream)
+            return perform(p, op, m, self.caller_stream)
 
     def _step(self, op):
         name = op[0]
         m = self.model
         if name in CHECKS:
             return self._check_op(op)
-        if name == "run_square_device":
-            self.caller_stream()
         want_err = expected_error(op, m)
-        got = perform(self.eng, op, m, self._stream)
+        got = perform(self.eng, op, m, self.caller_stream)
         failed = isinstance(got, tuple) and len(got) == 2 and got[0] == "error"
         if want_err is None:
             assert not failed, ("%s failed with status %d: %s" % (name, got[1], self.eng._lib.dst_last_error(self.eng._h).decode())

@@ -176,8 +176,9 @@ def stream_close_then_schedule_eviction(path):
     stream, so the tile schedule of its geometry (rectangle, rows [0, batch), slot 0's columns) is made with that stream as
     its user (prepare_schedule).  Closing the pipeline destroys the stream; the schedule stays.  It is the oldest of the
     context, so the 19 row ranges that follow — each a new geometry, 16 are kept — evict it, and the eviction waits for the
-    schedule's users: on the destroyed handle the runtime ended the process.  dst_stream's destroy now takes its streams
-    out of every schedule.  Then the first range again, and a second pipeline of the same geometry (its schedule rebuilt)."""
+    schedule's users: on the destroyed handle the runtime ended the process.  The context now keeps a mark of the stream (an
+    event of its own, dst_ctx::Mark) and no handle, and the eviction waits for that event; closing a pipeline tells the
+    context nothing.  Then the first range again, and a second pipeline of the same geometry (its schedule rebuilt)."""
     n = 1300
     b = [int(x) for x in np.linspace(0, n - 1, 20)]
     ranges = [("run_square", "raw", b[k], b[k + 1], False) for k in range(19)]
@@ -185,6 +186,35 @@ def stream_close_then_schedule_eviction(path):
              ("stream", "k80", "low", 19, 8, 3, 122, False, False), ("run_stream_batch", "raw", "low", 40, 123, False, False)] +
             ranges + [ranges[0], ("stream", "k80", "low", 19, 8, 3, 124, True, True), ranges[1],
                       ("run_stream_batch", "tn93", "low", 7, 125, False, False), ("expect", "last_path", path)])
+
+
+def page_locked_buffers_grow_and_are_reused():
+    """The context's four page-locked buffers (links' chunk, pair sites' batch and window, the text's near ties) and the
+    device buffers beside them through small, grow, small: 300 records, 1,300, 300 again, 2,000 sites each — the smallest
+    order in which a grow that left a stale pointer or a stale capacity behind would show.  At each size the links within
+    a threshold with values and tallies (tn93: the chunk is the slab's pair count, 44,850 then 844,350 entries), the
+    difference sites of 64 pairs, and the tn93 text of 200 rows, whose near ties go through the fourth buffer; each
+    answer is the pristine engine's."""
+    ops = []
+    for n, seed in ((300, 141), (1300, 142), (300, 143)):
+        ops += [("upload", 0, "low", n, 2000, seed, False), ("set_ids", 0, "p%d_" % seed),
+                ("links", "tn93", 0.004, True, 0, 1, True, True), ("pair_sites", "tn93", 64, True, 0, 1, seed),
+                ("text_square", "tn93", 0, 200)]
+    return ops
+
+
+def more_streams_than_marks_used_to_hold():
+    """Six streams of the caller's (torch's, from its pool, alive to the end: none is ever destroyed) on one context, which
+    used to remember the runs of four: one row range per stream in turn on the consensus path, the measure changing on
+    the way (every change of family rebuilds the per-record constants behind a wait for the other streams' marks), then
+    other content into the same slot (the rebuild that must wait for all six) and the first range again.
+    Every run is waited for before its answer is read, so no timing can make this fail reliably: what it holds is that
+    the path with more than four streams runs at all, trims its marks, and stays correct."""
+    n = 1300
+    b = [int(x) for x in np.linspace(0, n - 1, 7)]
+    ranges = [("run_square_device", WALK[k], b[k], b[k + 1], k) for k in range(6)]
+    return ([("set_prep", "zero"), ("upload", 0, "clade", n, 2000, 131, False), ("set_path", "consensus")] + ranges +
+            [("upload", 0, "clade", n, 2000, 132, False), ranges[0], ("expect", "last_path", "consensus")])
 
 
 DIRECTED = {
@@ -205,6 +235,8 @@ DIRECTED = {
     "schedule_cache_hybrid": schedule_cache("hybrid"),
     "stream_close_then_schedule_eviction_dense": stream_close_then_schedule_eviction("dense"),
     "stream_close_then_schedule_eviction_consensus": stream_close_then_schedule_eviction("consensus"),
+    "page_locked_buffers_grow_and_are_reused": page_locked_buffers_grow_and_are_reused(),
+    "more_streams_than_marks_used_to_hold": more_streams_than_marks_used_to_hold(),
 }
 SEEDS = (53, 61, 92, 82, 1)       # chosen so that the coverage test below holds (a greedy search over seeds 1..199)
 TOTALS = {"sequences": 0, "answers": 0, "state": 0, "values": 0}
@@ -251,10 +283,12 @@ def test_the_walks_are_deterministic_and_cover_the_vocabulary():
         pairs |= set(zip(classes, classes[1:]))
     missing = sorted({(a, b) for a in em.CLASSES for b in em.CLASSES} - pairs)
     assert not missing, missing
-    # the directed sequences use the same vocabulary (plus the introspection checks)
+    # the directed sequences use the same vocabulary (plus the operations only they name, and the introspection checks)
+    assert not set(em.DIRECTED_OPS) & set(em.OP_CLASS) and set(em.DIRECTED_OPS.values()) <= set(em.CLASSES)
     for name, seq in DIRECTED.items():
         for op in seq:
-            assert op[0] in em.OP_CLASS or op[0] in em.CHECKS, (name, op)
+            assert op[0] in em.OP_CLASS or op[0] in em.DIRECTED_OPS or op[0] in em.CHECKS, (name, op)
+    assert set(em.DIRECTED_OPS) <= {op[0] for seq in DIRECTED.values() for op in seq}
     kinds = {op[2] for seq in list(DIRECTED.values()) + walks for op in seq if op[0] in ("upload", "upload_device")}
     assert kinds == set(em.KINDS), sorted(set(em.KINDS) - kinds)
     assert any(op[0] == "upload" and op[4] >= 65536 for seq in DIRECTED.values() for op in seq)
