@@ -32,7 +32,16 @@ def kruskal(n, vals):
     keep = np.ones(len(vals), bool) if vals.dtype == np.int64 else ~np.isnan(vals)   # NaN edges are dropped
     i, j, key, v = i[keep], j[keep], key[keep], vals[keep]
     order = np.lexsort((j, i, key))
-    parent = list(range(n))
+    i, j, v = i[order], j[order], v[order]
+    taken, _ = kruskal_edges(n, i, j)
+    return np.stack([i[taken], j[taken]], axis=1).astype(np.int64).reshape(-1, 2), v[taken]
+
+
+def kruskal_edges(n, i, j, state=None):
+    """Kruskal's loop over the edges (i[e], j[e]) in the order given (the caller's (key, i, j) order): (the positions of the
+    edges taken, ascending; the union-find state).  `state` from an earlier call continues that forest with edges that
+    come later in the order; the loop ends once the forest has n - 1 edges."""
+    parent, have = (list(range(n)), 0) if state is None else state
 
     def find(x):
         while parent[x] != x:
@@ -41,15 +50,14 @@ def kruskal(n, vals):
         return x
 
     taken = []
-    for e in order:
-        if len(taken) == n - 1:
+    for e, (x, y) in enumerate(zip(np.asarray(i).tolist(), np.asarray(j).tolist())):
+        if have + len(taken) == n - 1:
             break
-        a, b = find(int(i[e])), find(int(j[e]))
+        a, b = find(x), find(y)
         if a != b:
             parent[max(a, b)] = min(a, b)
             taken.append(e)
-    taken = np.array(taken, np.int64)
-    return np.stack([i[taken], j[taken]], axis=1).astype(np.int64).reshape(-1, 2), v[taken]
+    return np.array(taken, np.int64), (parent, have + len(taken))
 
 
 def condensed(matrix):
