@@ -23,6 +23,7 @@ SLAB_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
 LINKS_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 LINKS_VALUES, LINKS_TALLIES = 1, 2
 LINKS_CHUNK = 1 << 22   # DST_LINKS_CHUNK: the most links of one sink call
+STREAM_LINKS_WINDOW = 1 << 20   # DST_STREAM_LINKS_WINDOW: the default most links of one window of a links stream
 PAIR_SITES_BATCH = 1 << 20    # DST_PAIR_SITES_BATCH: the most pairs of one device batch of dst_pair_sites
 PAIR_SITES_WINDOW = 1 << 24   # DST_PAIR_SITES_WINDOW: the most entries of one device output window
 SUMMARY_SCALE_BITS = 37   # DST_SUMMARY_SCALE_BITS: f64 distances are summed as rint(v * 2^37)
@@ -109,6 +110,9 @@ _SIGS = {
     "dst_stream_closest_next_index": (C.c_int, [_vp, C.c_uint64]),
     "dst_stream_closest_result": (C.c_int, [_vp, _vp, _vp, _vp, C.c_size_t, _u32p]),
     "dst_stream_closest_batch": (C.c_int, [_vp, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _u32p]),
+    "dst_stream_open_links": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, C.c_uint64, C.c_size_t, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "dst_stream_links_batch": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "dst_stream_links_stats": (C.c_int, [_vp, _u64p, _u64p]),
     "dst_comm_unique_id": (C.c_int, [_vp, C.c_size_t]),
     "dst_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "dst_comm_create_custom": (C.c_int, [_vp, C.c_int, C.c_int, ALLGATHER_FN, _vp, C.POINTER(_vp)]),

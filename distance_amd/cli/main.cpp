@@ -8,7 +8,8 @@
 // replaced by libdistance_hip.so through its C ABI; -t sizes the host formatting pool and -b is
 // accepted — neither changes the output, as in the reference (src/lib.rs:919-1154).
 // Extra flags: --gpus N (default 1) / --devices LIST, --slab-pairs P (result slab size), --closest K [--closest-for SIDE]
-// (stream mode: the K closest records only, dst_stream_open_closest), --nearest K (the K nearest records
+// (stream mode: the K closest records only, dst_stream_open_closest), --within T (stream mode: only the lines of the pairs
+// within T, dst_stream_open_links), --nearest K (the K nearest records
 // of every record instead of every pair: dst_nearest), --clusters T (single-linkage clusters at threshold T: dst_clusters),
 // --matrix tsv|phylip (a square or rectangular distance matrix instead of the long form: dst_text_matrix), --tree nj (the
 // neighbour-joining tree as one Newick line: dst_nj, dst_newick), --bootstrap B / --seed S (the tree's splits labelled
@@ -121,6 +122,9 @@ void print_help()
         "      --closest-for <side>     Whose closest records --closest prints: loaded (for every loaded record its k closest "
         "streamed records, written when the stream ends) or streamed (for every streamed record its k closest loaded "
         "records, in stream order) [default: loaded]\n"
+        "      --within <T>             Stream mode only: print only the pairs within distance T (a number >= 0, or inf): the "
+        "lines of the full run whose distance is at most T, in the same order and with the same text. Requires --stream, one "
+        "loaded file, one GPU, no other output mode\n"
         "      --clusters <T>           Print the single-linkage cluster of every record instead of distances: records "
         "within distance T (a number >= 0) of each other share a cluster, numbered from 1 in order of first record. One "
         "input, one GPU, no --stream or --nearest\n"
@@ -171,6 +175,8 @@ struct Args {
     size_t closest = 0;                   // --closest k (stream mode)
     bool has_closest = false, has_closest_for = false;
     int closest_side = DST_CLOSEST_FOR_LOADED;   // --closest-for loaded|streamed
+    double within = 0;                    // --within T (stream mode)
+    bool has_within = false;
     double clusters = 0;                  // --clusters T
     bool has_clusters = false;
     double max_distance = 0;              // --max-distance T
@@ -321,6 +327,20 @@ Args parse_args(int argc, char **argv)
                 die_usage("invalid value '" + v + "' for '--max-distance <T>': the threshold must not be negative");
             a.max_distance = t;
             a.has_max_distance = true;
+        } else if (arg == "--within" || arg.rfind("--within=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--within <T>");
+            if (a.has_within)
+                die_usage("the argument '--within <T>' cannot be used multiple times");
+            // the whole word is the number (or inf), as for --max-distance <T>
+            char *end = nullptr;
+            errno = 0;
+            const double t = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
+            if (v.empty() || end != v.c_str() + v.size() || t != t || std::isspace((unsigned char)v[0]))
+                die_usage("invalid value '" + v + "' for '--within <T>': not a number");
+            if (t < 0)
+                die_usage("invalid value '" + v + "' for '--within <T>': the threshold must not be negative");
+            a.within = t;
+            a.has_within = true;
         } else if (arg == "--summary" || arg.rfind("--summary=", 0) == 0) {
             const std::string v = value_of(k, arg, "--summary <T>");
             if (a.has_summary)
@@ -420,7 +440,8 @@ Args parse_args(int argc, char **argv)
                             : a.matrix >= 0 ? "--matrix <format>" : a.has_tree ? "--tree <method>"
                             : a.has_bootstrap ? "--bootstrap <B>" : a.has_mst ? "--mst"
                             : a.dendrogram >= 0 ? "--dendrogram <linkage>" : a.has_max_distance ? "--max-distance <T>"
-                            : a.has_histogram ? "--histogram <W>" : a.has_summary ? "--summary <T>" : nullptr;
+                            : a.has_histogram ? "--histogram <W>" : a.has_summary ? "--summary <T>"
+                            : a.has_within ? "--within <T>" : nullptr;
         if (other)
             die_usage(std::string("the argument '--closest <k>' cannot be used with '") + other + "'");
         if (!a.has_stream)
@@ -429,6 +450,22 @@ Args parse_args(int argc, char **argv)
             die_usage("the argument '--closest <k>' takes one loaded alignment, not two");
         if (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1))
             die_usage(std::string("the argument '--closest <k>' cannot be used with '") +
+                      (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
+    }
+    if (a.has_within) {   // stream mode's --max-distance: like --closest against every other output mode, before their own checks
+        const char *other = a.has_closest ? "--closest <k>" : a.has_nearest ? "--nearest <k>" : a.has_clusters ? "--clusters <T>"
+                            : a.matrix >= 0 ? "--matrix <format>" : a.has_tree ? "--tree <method>"
+                            : a.has_bootstrap ? "--bootstrap <B>" : a.has_mst ? "--mst"
+                            : a.dendrogram >= 0 ? "--dendrogram <linkage>" : a.has_max_distance ? "--max-distance <T>"
+                            : a.has_histogram ? "--histogram <W>" : a.has_summary ? "--summary <T>" : nullptr;
+        if (other)
+            die_usage(std::string("the argument '--within <T>' cannot be used with '") + other + "'");
+        if (!a.has_stream)
+            die_usage("the argument '--within <T>' requires '--stream <stream>'");
+        if (a.flag_inputs.size() + a.pos_inputs.size() > 1)
+            die_usage("the argument '--within <T>' takes one loaded alignment, not two");
+        if (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1))
+            die_usage(std::string("the argument '--within <T>' cannot be used with '") +
                       (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
     }
     for (int mode = 0; mode < 2; ++mode) {   // --summary, then --histogram: each against everything else
@@ -2136,6 +2173,8 @@ int main(int argc, char **argv)
         // --closest: the lists stay on the GPU (dst_stream_open_closest); one GPU, so submission order is stream order
         const bool closest = a.has_closest, closest_loaded = closest && a.closest_side == DST_CLOSEST_FOR_LOADED;
         const size_t TW = (size_t)dst_tally_width(measure);
+        // --within: the batch's links come back instead of its matrix (dst_stream_open_links), with their tallies
+        const bool within = a.has_within;
         // closest for the loaded records: the streamed ids (one arena + offsets) and, for tn93, base counts until the end
         std::vector<char> kept_ids;
         std::vector<uint64_t> kept_off(1, 0);
@@ -2164,6 +2203,8 @@ int main(int argc, char **argv)
         for (int g = 0; g < G; ++g)
             gpus[g].check(closest ? dst_stream_open_closest(gpus[g].h, measure, (uint32_t)a.closest, a.closest_side, batch_records,
                                                             kDepth, nibbles ? DST_WIRE_NIBBLES : DST_WIRE_CODES, &streams[g])
+                          : within ? dst_stream_open_links(gpus[g].h, measure, a.within, DST_LINKS_TALLIES, 0, batch_records, kDepth,
+                                                           nibbles ? DST_WIRE_NIBBLES : DST_WIRE_CODES, &streams[g])
                                   : dst_stream_open_wire(gpus[g].h, measure, DST_OUT_TALLY, batch_records, kDepth,
                                                          nibbles ? DST_WIRE_NIBBLES : DST_WIRE_CODES, &streams[g]), "stream open");
         auto gpu_stream_worker = [&](int g) {
@@ -2174,6 +2215,32 @@ int main(int argc, char **argv)
                 gpus[g].check(dst_stream_collect(streams[g], &n_rec, &res), "stream collect");
                 Item it = std::move(inflight.front());
                 inflight.pop_front();
+                if (within) {   // the batch's links in stream order, window after window, each as the full run's line
+                    std::vector<TextBuf> text;
+                    text.emplace_back();
+                    const Alignment &al = *it.batch;
+                    for (uint64_t first = 0;;) {
+                        uint64_t m = 0, total = 0;
+                        const uint32_t *srec = nullptr, *lrec = nullptr, *tal = nullptr;
+                        gpus[g].check(dst_stream_links_batch(streams[g], first, &m, &total, &srec, &lrec, nullptr, &tal),
+                                      "stream links batch");
+                        for (uint64_t e = 0; e < m; ++e) {
+                            const size_t r = srec[e], j = lrec[e];
+                            closest_line(text.back(), ref.ids[j], al.ids[r].data(), al.ids[r].size(), tal + e * TW,
+                                         measure == DST_TN93 ? al.counts.data() + 4 * r : nullptr,
+                                         measure == DST_TN93 ? counts[0].data() + 4 * j : nullptr);
+                        }
+                        first += m;
+                        if (first >= total)
+                            break;
+                    }
+                    {
+                        std::lock_guard<std::mutex> lk(wmu);
+                        done_text[it.idx] = std::move(text);
+                    }
+                    wcv.notify_all();
+                    return;
+                }
                 if (closest) {
                     std::vector<TextBuf> text;
                     if (!closest_loaded) {   // the batch's records in stream order, each with its k_used closest loaded records

@@ -89,9 +89,11 @@ int matrix_finite(dst_ctx *ctx, const std::string &prefix, const double *d, uint
     return DST_OK;
 }
 
-// The threshold of dst_clusters / dst_links as a payload: int64 payloads link when v <= floor(T) (clamped to the int64
-// range), f64 payloads on their bits through nn_key.  false: floor(T) is below -2^63, nothing links.
-bool threshold_payload(int measure, double threshold, uint64_t &t_bits)
+}  // namespace
+
+// The threshold of dst_clusters / dst_links / a links stream as a payload: int64 payloads link when v <= floor(T) (clamped
+// to the int64 range), f64 payloads on their bits through nn_key.  false: floor(T) is below -2^63, nothing links.
+bool dst::threshold_payload(int measure, double threshold, uint64_t &t_bits)
 {
     if (!measure_is_int(measure)) {
         std::memcpy(&t_bits, &threshold, 8);
@@ -110,6 +112,8 @@ bool threshold_payload(int measure, double threshold, uint64_t &t_bits)
     t_bits = (uint64_t)t;
     return any;
 }
+
+namespace {
 
 size_t links_layout(void *base, uint64_t blocks, uint64_t chunk, bool values, int W, LinksBuffers &b)
 {

@@ -592,6 +592,22 @@ int note_run(dst_ctx *ctx, hipStream_t stream)
     return DST_OK;
 }
 
+// A stream of the library's own is about to be destroyed (dst_stream_close, after its wait for the stream): its mark goes,
+// and with it the mark's entries in the schedules' user lists.  The work behind the mark has finished, so nobody has to
+// wait for it; and the runtime's event keeps a pointer to the stream it was last recorded on, which hipEventSynchronize
+// and hipEventQuery read ("... last recorded in a capturing stream" from whatever the freed stream's memory holds by then).
+void forget_stream(dst_ctx *ctx, hipStream_t stream)
+{
+    for (size_t k = ctx->marks.size(); k-- > 0;) {
+        if (ctx->marks[k].key != stream)
+            continue;
+        const uint64_t id = ctx->marks[k].id;
+        for (auto &s : ctx->schedules)
+            s.users.erase(std::remove(s.users.begin(), s.users.end(), id), s.users.end());
+        ctx->marks.erase(ctx->marks.begin() + (long)k);
+    }
+}
+
 // the reference sequence of `s` (plurality code per site over a sample of its records), its hot sites and the
 // statistics the path choice reads
 int ensure_ref(dst_ctx *ctx, DeviceSet &s, hipStream_t stream)

@@ -85,7 +85,9 @@ struct dst_ctx {
     // latest pair launch (note_run), and the handle's value as a key that is compared and never handed back to the
     // runtime.  So a stream may be destroyed as soon as the work queued on it has completed.  A new stream that gets a
     // destroyed stream's handle value re-records that stream's mark: a later point of a stream whose earlier work was
-    // complete, which is what a waiter wants.
+    // complete, which is what a waiter wants.  A dst_stream takes the marks of its three streams with it when it closes
+    // (forget_stream): the runtime's event remembers the stream it was recorded on, and asking it about an event whose
+    // stream is gone reads freed memory.
     struct Mark {
         uint64_t id = 0;
         hipStream_t key = nullptr;
@@ -209,6 +211,8 @@ int two_sets(dst_ctx *ctx, bool square, int row_slot, int col_slot, TwoSets &out
 // the base planes a deferred upload left out, written before anything but the consensus path reads planes (dst_api.cpp)
 int ensure_planes(dst_ctx *ctx, DeviceSet &s, hipStream_t stream);
 void free_set(DeviceSet &s);
+// forget the mark of a stream that is idle and about to be destroyed (dst_ctx::Mark; dst_api.cpp)
+void forget_stream(dst_ctx *ctx, hipStream_t stream);
 // queue the pack of an n x len byte matrix (device memory) into `s`; *d_first_bad receives the index of the first
 // byte that is not a Paradis code (or stays ~0).  Nothing here waits for the device.
 // nibbles: d_codes holds the 4-bit wire format (two sites per byte) instead of Paradis bytes
@@ -231,5 +235,8 @@ struct SlabPlan {
     uint64_t biggest = 0;
 };
 SlabPlan plan_slabs(bool square, uint64_t n_rows, uint64_t n_cols, uint64_t max_pairs, uint64_t default_pairs);
+// the threshold of dst_clusters / dst_links / dst_stream_open_links as a payload of `measure`; false: nothing can link
+// (dst_analysis.cpp)
+bool threshold_payload(int measure, double threshold, uint64_t &t_bits);
 
 }  // namespace dst

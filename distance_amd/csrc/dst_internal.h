@@ -467,6 +467,8 @@ hipError_t launch_links_count(int measure, bool tally, bool square, const void *
 hipError_t launch_links_write(int measure, bool tally, bool square, const void *slab, uint64_t out_base, uint64_t n_cols,
                               uint64_t rb, uint64_t re, uint64_t t_bits, const uint32_t *q_counts, const uint32_t *t_counts,
                               const LinksBuffers &b, uint64_t lo, uint64_t hi, bool values, bool tallies, hipStream_t stream);
+// a links stream's batch (dst_stream.cpp): hdr[0] = *total (NULL: 0), hdr[1] = *bad, side by side for the one copy back
+hipError_t launch_links_stream_header(const uint64_t *total, const unsigned long long *bad, uint64_t *hdr, hipStream_t stream);
 
 // ---- difference sites of a pair list (dst_pair_sites.hip, driven by dst_pair_sites in dst_api.cpp) ---------------------
 // Per batch of at most DST_PAIR_SITES_BATCH pairs: a count launch (one wave per pair, the lanes along its chunks) and a

@@ -15,6 +15,7 @@
 //                        the __popcll of the lanes below, the steps of a wave in order, the waves' totals through LDS:
 //                        rank order is entry order) and writes row, col and what was asked for at offset + rank - lo.
 //                        Plain vector stores; two links never share a place, so the output's order is entry order.
+//   links_stream_header_kernel   a links stream's batch: the slab's total beside the bad-code word (one thread)
 //
 // The slab is DST_OUT_DISTANCE payloads (8 B per pair), or DST_OUT_TALLY words when the caller wants the links' tallies:
 // then the payload is pair_value<M> of the tallies, the arithmetic of the pair kernels' epilogue, bitwise what a
@@ -238,7 +239,24 @@ __global__ __launch_bounds__(256) void links_write_kernel(const void *__restrict
     }
 }
 
+// A links stream's batch (dst_stream.cpp): the two words its collect needs, side by side, so that one 16-byte copy brings
+// the batch's link total (the scan's last offset; NULL when nothing can link) and the pack's bad-code word.
+__global__ __launch_bounds__(64) void links_stream_header_kernel(const uint64_t *__restrict__ total,
+                                                                 const unsigned long long *__restrict__ bad, uint64_t *__restrict__ hdr)
+{
+    if (threadIdx.x == 0) {
+        hdr[0] = total ? *total : 0;
+        hdr[1] = *bad;
+    }
+}
+
 }  // namespace
+
+hipError_t launch_links_stream_header(const uint64_t *total, const unsigned long long *bad, uint64_t *hdr, hipStream_t stream)
+{
+    hipLaunchKernelGGL(links_stream_header_kernel, dim3(1), dim3(64), 0, stream, total, bad, hdr);
+    return hipGetLastError();
+}
 
 uint64_t links_blocks(bool square, uint64_t n_cols, uint64_t rb, uint64_t re)
 {

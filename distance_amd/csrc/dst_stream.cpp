@@ -19,8 +19,18 @@
 //                             another; only the bad-code word travels back per batch
 //   DST_CLOSEST_FOR_STREAMED  per-slot lists for the batch's records (nearest_init + nearest_rows, rectangle form); their
 //                             D2H takes the place of the results' on the copy-out stream
+//
+// A links stream (dst_stream_open_links) is the third kind: the matrix stays on the device (DST_OUT_TALLY words
+// when the links' tallies are asked for, else DST_OUT_DISTANCE payloads) and dst_links' count, scan and write launches
+// (rectangle form, the batch as rows) follow the pair kernel on the compute stream.  Every slot has its own block counts,
+// offsets and window, two batches being on the device at once.  The write pass stores window 0 straight into the slot's
+// page-locked window through its device address, and a one-thread launch puts the batch's total beside the bad-code word,
+// so that the copy-out stream carries 16 bytes per batch.  (DST_STREAM_LINKS_COPY, a measurement knob: the window in device
+// memory, its present entries copied after collect.)
 #include <algorithm>
+#include <cmath>
 #include <cstdio>
+#include <cstdlib>
 #include <new>
 
 #include "dst_ctx.h"
@@ -37,6 +47,12 @@ struct dst_stream {
         void *d_out = nullptr, *h_out = nullptr;
         void *d_lists = nullptr, *h_lists = nullptr;   // FOR_STREAMED: max_records x k_streamed entries, device and page-locked
         NearestLists nl{}, h_nl{};
+        // a links stream: d_lists = block counts, offsets, header (and the window, copy route), h_lists = header and window
+        LinksBuffers lb{}, h_lb{};           // lb: what the kernels write (its window: h_lb's by device address, or d_lists')
+        LinksBuffers d_win{};                // copy route: the window in device memory (= lb's)
+        uint64_t *d_hdr = nullptr, *h_hdr = nullptr;   // [0] the batch's links, [1] its bad-code word
+        uint64_t total = 0;                  // of the collected batch
+        uint64_t window_first = ~0ull;       // the first link of the window the page-locked buffer holds (~0: none)
         unsigned long long *d_bad = nullptr, *h_bad = nullptr;
         DeviceSet set;
         hipEvent_t h2d = nullptr, computed = nullptr, landed = nullptr;
@@ -47,7 +63,7 @@ struct dst_stream {
     hipStream_t s_in = nullptr, s_compute = nullptr, s_out = nullptr;
     size_t next_acquire = 0, next_collect = 0, in_flight = 0;
     int acquired = -1;
-    // closest streams (closest = the dst_closest_side, -1: a plain stream)
+    // closest streams (closest = the dst_closest_side, -1: a plain stream, kLinksStream: a links stream)
     int closest = -1;
     uint32_t k = 0, k_streamed = 0;   // asked for; min(k, n_loaded): what a FOR_STREAMED batch's lists hold
     size_t n_loaded = 0;
@@ -56,8 +72,17 @@ struct dst_stream {
     NearestLists nl{};
     uint64_t next_ordinal = 0, submitted = 0;
     bool poisoned = false;            // a batch held an invalid code: the lists are not trustworthy
-    int last_collected = -1;          // FOR_STREAMED: the slot dst_stream_closest_batch hands out
+    int last_collected = -1;          // FOR_STREAMED, links: the slot dst_stream_closest_batch / _links_batch hands out
+    // links streams
+    uint64_t t_bits = 0;              // the threshold as a payload (threshold_payload)
+    bool any_links = false;           // false: nothing can link, no compaction is launched
+    int what = 0;
+    uint64_t window = 0;              // links of one window
+    bool via_copy = false;            // DST_STREAM_LINKS_COPY
+    uint64_t links_total = 0, late_windows = 0;   // dst_stream_links_stats
 };
+
+constexpr int kLinksStream = 2;       // dst_stream::closest of a links stream (after the two dst_closest_side values)
 
 namespace {
 
@@ -75,6 +100,23 @@ size_t lists_layout(void *base, uint64_t entries, int W, NearestLists &nl)
     return (size_t)(entries * (12 + 4 * (uint64_t)W));   // (the size alone with base == NULL)
 }
 
+// one window of links in one block: streamed (row), loaded (col), values when asked, W tally words (0: none) per link
+size_t window_layout(void *base, uint64_t window, bool values, int W, LinksBuffers &b)
+{
+    char *p = static_cast<char *>(base);
+    size_t used = 0;
+    auto take = [&](size_t bytes) {
+        char *at = p ? p + used : nullptr;
+        used += (bytes + 255) / 256 * 256;
+        return at;
+    };
+    b.row = reinterpret_cast<uint32_t *>(take(window * 4));
+    b.col = reinterpret_cast<uint32_t *>(take(window * 4));
+    b.val = reinterpret_cast<uint64_t *>(take(values ? window * 8 : 0));
+    b.tal = reinterpret_cast<uint32_t *>(take(window * 4 * (size_t)W));
+    return used;   // (the size alone with base == NULL)
+}
+
 void destroy(dst_stream *s)
 {
     if (!s)
@@ -83,8 +125,12 @@ void destroy(dst_stream *s)
     for (hipStream_t st : {s->s_in, s->s_compute, s->s_out})
         if (st)
             (void)hipStreamSynchronize(st);
-    // (the context keeps marks of these streams, events of its own, and no handle it would hand to the runtime again:
-    // dst_ctx::Mark.  They are idle now, so those events have completed.)
+    // The context keeps marks of these streams: events of its own, recorded on them.  The streams are idle now, so those
+    // events have completed, and the marks go before the streams do: the runtime must not be asked about an event whose
+    // stream is gone (forget_stream).
+    for (hipStream_t st : {s->s_in, s->s_compute, s->s_out})
+        if (st)
+            forget_stream(s->ctx, st);
     for (auto &sl : s->slots) {
         if (sl.h_in) (void)hipHostFree(sl.h_in);
         if (sl.h_out) (void)hipHostFree(sl.h_out);
@@ -109,6 +155,20 @@ void destroy(dst_stream *s)
 
 int open_stream(dst_ctx *ctx, int measure, int out_kind, size_t max_records, int depth, int wire, int closest, uint32_t k,
                 dst_stream **out);
+
+// the copy route of a links stream: the first m entries of the slot's device window into its page-locked one; waits
+int copy_window(dst_stream *s, dst_stream::Slot &sl, uint64_t m, hipStream_t stream)
+{
+    dst_ctx *ctx = s->ctx;
+    HIP_TRY(ctx, hipMemcpyAsync(sl.h_lb.row, sl.d_win.row, m * 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(sl.h_lb.col, sl.d_win.col, m * 4, hipMemcpyDeviceToHost, stream));
+    if (s->what & DST_LINKS_VALUES)
+        HIP_TRY(ctx, hipMemcpyAsync(sl.h_lb.val, sl.d_win.val, m * 8, hipMemcpyDeviceToHost, stream));
+    if (s->what & DST_LINKS_TALLIES)
+        HIP_TRY(ctx, hipMemcpyAsync(sl.h_lb.tal, sl.d_win.tal, m * 4 * (size_t)s->W, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    return DST_OK;
+}
 
 }  // namespace
 
@@ -135,6 +195,71 @@ int dst_stream_open_closest(dst_ctx *ctx, int measure, uint32_t k, int side, siz
     if (k < 1 || k > kNearestMaxK)
         return fail(ctx, DST_ERR_ARG, "k must be between 1 and 256");
     return open_stream(ctx, measure, DST_OUT_TALLY, max_records, depth, wire, side, k, out);
+}
+
+int dst_stream_open_links(dst_ctx *ctx, int measure, double threshold, int what, uint64_t window_links, size_t max_records,
+                          int depth, int wire, dst_stream **out)
+{
+    if (!ctx || !out)
+        return DST_ERR_ARG;
+    *out = nullptr;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (std::isnan(threshold))
+        return fail(ctx, DST_ERR_ARG, "threshold is NaN");
+    if (what & ~(DST_LINKS_VALUES | DST_LINKS_TALLIES))
+        return fail(ctx, DST_ERR_ARG, "unknown bits in what");
+    if (window_links > DST_LINKS_CHUNK)
+        return fail(ctx, DST_ERR_ARG, "window_links is above DST_LINKS_CHUNK");
+    dst_stream *s = nullptr;
+    const bool tallies = (what & DST_LINKS_TALLIES) != 0, values = (what & DST_LINKS_VALUES) != 0;
+    int rc = open_stream(ctx, measure, tallies ? DST_OUT_TALLY : DST_OUT_DISTANCE, max_records, depth, wire, kLinksStream, 0, &s);
+    if (rc)
+        return rc;
+    s->what = what;
+    s->any_links = threshold_payload(measure, threshold, s->t_bits) && s->n_loaded != 0;
+    const uint64_t n_loaded = s->n_loaded;
+    const uint64_t most = n_loaded && max_records > ~0ull / n_loaded ? ~0ull : (uint64_t)max_records * n_loaded;
+    s->window = std::min<uint64_t>(std::max<uint64_t>(std::min<uint64_t>(window_links ? window_links : DST_STREAM_LINKS_WINDOW, most), 1),
+                                   DST_LINKS_CHUNK);
+    s->via_copy = std::getenv("DST_STREAM_LINKS_COPY") != nullptr;   // measurement knob
+    // per slot: the block counts, their offsets, the scan's running total and the header; the window
+    const uint64_t blocks = links_blocks(false, n_loaded, 0, max_records);
+    const int W = tallies ? s->W : 0;
+    LinksBuffers none{};
+    const size_t win_bytes = window_layout(nullptr, s->window, values, W, none);
+    const size_t counts_bytes = (blocks * 4 + 255) / 256 * 256, offsets_bytes = ((blocks + 1) * 8 + 255) / 256 * 256;
+    const size_t work_bytes = counts_bytes + offsets_bytes + 256;
+    hipError_t e = hipSuccess;
+    for (auto &sl : s->slots) {
+        if (e == hipSuccess) e = hipMalloc(&sl.d_lists, work_bytes + (s->via_copy ? win_bytes : 0));
+        if (e == hipSuccess) e = hipHostMalloc(&sl.h_lists, 256 + win_bytes, hipHostMallocDefault);
+        if (e != hipSuccess)
+            break;
+        char *d = static_cast<char *>(sl.d_lists), *h = static_cast<char *>(sl.h_lists);
+        sl.lb.counts = reinterpret_cast<uint32_t *>(d);
+        sl.lb.offsets = reinterpret_cast<uint64_t *>(d + counts_bytes);
+        sl.lb.grand = reinterpret_cast<uint64_t *>(d + counts_bytes + offsets_bytes);
+        sl.d_hdr = sl.lb.grand + 2;
+        sl.h_hdr = reinterpret_cast<uint64_t *>(h);
+        window_layout(h + 256, s->window, values, W, sl.h_lb);
+        if (s->via_copy) {
+            window_layout(d + work_bytes, s->window, values, W, sl.d_win);
+        } else {   // the kernels' view of the page-locked window
+            void *h_dev = nullptr;
+            e = hipHostGetDevicePointer(&h_dev, sl.h_lists, 0);
+            if (e == hipSuccess)
+                window_layout(static_cast<char *>(h_dev) + 256, s->window, values, W, sl.d_win);
+        }
+        sl.lb.row = sl.d_win.row, sl.lb.col = sl.d_win.col, sl.lb.val = sl.d_win.val, sl.lb.tal = sl.d_win.tal;
+        if (e == hipSuccess) e = hipMemsetAsync(sl.lb.grand, 0, 8, s->s_compute);
+    }
+    if (e != hipSuccess) {
+        destroy(s);
+        return fail_hip(ctx, e, "dst_stream_open_links");
+    }
+    *out = s;
+    return DST_OK;
 }
 
 }  // extern "C"
@@ -303,10 +428,28 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
         HIP_TRY(ctx, launch_nearest_rows(s->measure, false, tallies, 0, s->n_loaded, 0, n_records, sl.set.counts, loaded.counts,
                                          sl.nl, s->s_compute));
     }
+    // a links stream: the count, the scan and window 0 behind the pair kernel, then the header for the one copy
+    if (s->closest == kLinksStream) {
+        const bool tally = (s->what & DST_LINKS_TALLIES) != 0;
+        if (s->any_links) {
+            HIP_TRY(ctx, launch_links_count(s->measure, tally, false, sl.d_out, 0, s->n_loaded, 0, n_records, s->t_bits,
+                                            sl.set.counts, loaded.counts, sl.lb, s->s_compute));
+            HIP_TRY(ctx, launch_links_write(s->measure, tally, false, sl.d_out, 0, s->n_loaded, 0, n_records, s->t_bits,
+                                            sl.set.counts, loaded.counts, sl.lb, 0, s->window, (s->what & DST_LINKS_VALUES) != 0,
+                                            tally, s->s_compute));
+        }
+        HIP_TRY(ctx, launch_links_stream_header(s->any_links ? sl.lb.offsets + links_blocks(false, s->n_loaded, 0, n_records) : nullptr,
+                                                sl.d_bad, sl.d_hdr, s->s_compute));
+        sl.window_first = 0;
+        s->last_collected = -1;   // the collected batch's links were valid until this submit
+    }
     HIP_TRY(ctx, hipEventRecord(sl.computed, s->s_compute));
     // copy-out
     HIP_TRY(ctx, hipStreamWaitEvent(s->s_out, sl.computed, 0));
-    HIP_TRY(ctx, hipMemcpyAsync(sl.h_bad, sl.d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, s->s_out));
+    if (s->closest == kLinksStream)
+        HIP_TRY(ctx, hipMemcpyAsync(sl.h_hdr, sl.d_hdr, 16, hipMemcpyDeviceToHost, s->s_out));
+    else
+        HIP_TRY(ctx, hipMemcpyAsync(sl.h_bad, sl.d_bad, sizeof(unsigned long long), hipMemcpyDeviceToHost, s->s_out));
     if (s->closest < 0) {
         if (bytes)
             HIP_TRY(ctx, hipMemcpyAsync(sl.h_out, sl.d_out, bytes, hipMemcpyDeviceToHost, s->s_out));
@@ -343,9 +486,25 @@ int dst_stream_collect(dst_stream *s, size_t *n_records, const void **results)
     s->in_flight -= 1;
     sl.state = 3;
     s->last_collected = (int)((s->next_collect - 1) % s->slots.size());
-    if (*sl.h_bad != ~0ull) {
-        s->poisoned = s->closest >= 0;
-        return invalid_code_error(ctx, *sl.h_bad, s->len);
+    const bool links = s->closest == kLinksStream;
+    const unsigned long long bad = links ? sl.h_hdr[1] : *sl.h_bad;
+    if (bad != ~0ull) {
+        s->poisoned = s->closest >= 0 && !links;   // (a links stream keeps nothing across batches)
+        if (links)
+            s->last_collected = -1;
+        return invalid_code_error(ctx, bad, s->len);
+    }
+    if (links) {
+        sl.total = sl.h_hdr[0];
+        if (sl.total > (uint64_t)sl.n * s->n_loaded) {
+            s->last_collected = -1;
+            return fail(ctx, DST_ERR_STATE, "links stream: more links than pairs in a batch");
+        }
+        s->links_total += sl.total;
+        if (s->via_copy && sl.total) {   // the copy route: what window 0 holds, now that the total is known
+            if (int rc = copy_window(s, sl, std::min(sl.total, s->window), s->s_out))
+                return rc;
+        }
     }
     *n_records = sl.n;
     *results = sl.h_out;   // (NULL for a closest stream: its results never leave the device as a matrix)
@@ -421,6 +580,68 @@ int dst_stream_closest_batch(dst_stream *s, const uint32_t **index, const uint32
     if (values)
         *values = sl.h_nl.val;
     *k_used = s->k_streamed;
+    return DST_OK;
+}
+
+int dst_stream_links_batch(dst_stream *s, uint64_t first_link, uint64_t *n_links, uint64_t *batch_links,
+                           const uint32_t **streamed, const uint32_t **loaded, const void **values, const uint32_t **tallies)
+{
+    if (!s)
+        return DST_ERR_ARG;
+    dst_ctx *ctx = s->ctx;
+    if (s->closest != kLinksStream)
+        return fail(ctx, DST_ERR_ARG, "not a links stream");
+    if (!n_links || !batch_links || !streamed || !loaded)
+        return fail(ctx, DST_ERR_ARG, "null n_links, batch_links, streamed or loaded pointer");
+    *n_links = *batch_links = 0;
+    *streamed = *loaded = nullptr;
+    if (values)
+        *values = nullptr;
+    if (tallies)
+        *tallies = nullptr;
+    if (s->last_collected < 0 || s->slots[(size_t)s->last_collected].state != 3)
+        return fail(ctx, DST_ERR_STATE, "no collected batch: its links are valid from dst_stream_collect to the next submit");
+    auto &sl = s->slots[(size_t)s->last_collected];
+    *batch_links = sl.total;
+    if (first_link > sl.total)
+        return fail(ctx, DST_ERR_ARG, "first_link is above the batch's links");
+    const uint64_t m = std::min(s->window, sl.total - first_link);
+    if (m && sl.window_first != first_link) {
+        // a late window: one write pass over the batch's matrix, still in the slot's device buffer; the compute stream orders
+        // it behind whatever else reads or writes the slot
+        const DeviceSet &set0 = ctx->set[0];
+        const bool tally = (s->what & DST_LINKS_TALLIES) != 0;
+        HIP_TRY(ctx, hipSetDevice(ctx->device));
+        sl.window_first = ~0ull;
+        HIP_TRY(ctx, launch_links_write(s->measure, tally, false, sl.d_out, 0, s->n_loaded, 0, sl.n, s->t_bits, sl.set.counts,
+                                        set0.counts, sl.lb, first_link, first_link + m, (s->what & DST_LINKS_VALUES) != 0, tally,
+                                        s->s_compute));
+        if (s->via_copy) {
+            if (int rc = copy_window(s, sl, m, s->s_compute))
+                return rc;
+        } else
+            HIP_TRY(ctx, hipStreamSynchronize(s->s_compute));
+        sl.window_first = first_link;
+        s->late_windows += 1;
+    }
+    *n_links = m;
+    *streamed = sl.h_lb.row;
+    *loaded = sl.h_lb.col;
+    if (values && (s->what & DST_LINKS_VALUES))
+        *values = sl.h_lb.val;
+    if (tallies && (s->what & DST_LINKS_TALLIES))
+        *tallies = sl.h_lb.tal;
+    return DST_OK;
+}
+
+int dst_stream_links_stats(const dst_stream *s, uint64_t *links, uint64_t *late_windows)
+{
+    if (!s || s->closest != kLinksStream)
+        return DST_ERR_ARG;
+    if (links)
+        *links = s->links_total;
+    if (late_windows)
+        *late_windows = s->late_windows;
     return DST_OK;
 }
 

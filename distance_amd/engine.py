@@ -415,6 +415,13 @@ class Engine:
         side="streamed": every streamed record's k nearest loaded records, per batch (pop())."""
         return ClosestStream(self, measure, k, max_records, side, depth, nibbles)
 
+    def links_stream(self, measure, threshold: float, max_records: int, depth: int = 3, nibbles: bool = False,
+                     values: bool = True, tallies: bool = False, window: int = 0) -> "LinksStream":
+        """A stream that hands back the pairs within `threshold` instead of the result matrix (dst_stream_open_links):
+        per batch (n_records, streamed, loaded[, values][, tallies]), by dst_links' rule, in the stream's own order.
+        window: the most links of one window (0: the default); the result does not depend on it."""
+        return LinksStream(self, measure, threshold, max_records, depth, nibbles, values, tallies, window)
+
     def run_slabs(self, measure, sink, max_pairs: int, square: bool = True, row_slot: int = 0, col_slot: int = 1,
                   tallies: bool = False):
         """In-order slab sink (dst_run_slabs): sink(first_pair, rb, re, array) per slab; a truthy return stops."""
@@ -951,3 +958,63 @@ class ClosestStream(Stream):
         if tallies:
             return index, values, tal[:n * k * self._w].reshape(n, k, self._w).copy()
         return index, values
+
+
+class LinksStream(Stream):
+    """dst_stream_open_links: a Stream whose batches leave the pairs within a threshold behind instead of the result matrix.
+    pop() returns (n_records, streamed uint32[n], loaded uint32[n][, values[n]][, tallies[n, width]]): streamed = the
+    record's index within the batch, loaded = the record of slot 0, streamed record outer, loaded record inner; values int64
+    for n / n_high, float64 otherwise, bitwise the plain stream's; every window of the batch concatenated, as copies."""
+
+    def __init__(self, eng: Engine, measure, threshold: float, max_records: int, depth: int = 3, nibbles: bool = False,
+                 values: bool = True, tallies: bool = False, window: int = 0):
+        self.threshold, self.values, self.tallies, self.window = float(threshold), bool(values), bool(tallies), int(window)
+        super().__init__(eng, measure, max_records, depth, bool(tallies), nibbles)
+        self._w = self._lib.dst_tally_width(self._m)
+        self._vtype = np.int64 if self._m in (0, 1) else np.float64
+
+    def _open(self):
+        h = C.c_void_p()
+        what = (LINKS_VALUES if self.values else 0) | (LINKS_TALLIES if self.tallies else 0)
+        self._eng._check(self._lib.dst_stream_open_links(self._eng._h, self._m, self.threshold, what, self.window,
+                                                         self.max_records, self.depth, int(self.nibbles), C.byref(h)))
+        return h
+
+    def links_batch(self, first: int = 0):
+        """One window of the batch pop() collected last (dst_stream_links_batch): (batch_links, streamed, loaded[, values]
+        [, tallies]) of the links from `first` on, as copies."""
+        n, total = C.c_uint64(), C.c_uint64()
+        sp, lp, vp, tp = C.c_void_p(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._eng._check(self._lib.dst_stream_links_batch(self._h, int(first), C.byref(n), C.byref(total), C.byref(sp),
+                                                          C.byref(lp), C.byref(vp), C.byref(tp)))
+        m = int(n.value)
+
+        def arr(p, ctype, shape, dtype):
+            if m == 0:
+                return np.zeros(shape, dtype)
+            return np.ctypeslib.as_array(C.cast(p, C.POINTER(ctype)), shape=shape).view(dtype).copy()
+
+        out = (int(total.value), arr(sp, C.c_uint32, (m,), np.uint32), arr(lp, C.c_uint32, (m,), np.uint32))
+        if self.values:
+            out += (arr(vp, C.c_int64, (m,), self._vtype),)
+        if self.tallies:
+            out += (arr(tp, C.c_uint32, (m, self._w), np.uint32),)
+        return out
+
+    def pop(self, copy: bool = True):
+        n, p = C.c_size_t(), C.c_void_p()
+        self._eng._check(self._lib.dst_stream_collect(self._h, C.byref(n), C.byref(p)))
+        parts, first = None, 0
+        while True:
+            got = self.links_batch(first)
+            parts = [[a] for a in got[1:]] if parts is None else [q + [a] for q, a in zip(parts, got[1:])]
+            first += len(got[1])
+            if first >= got[0]:
+                break
+        return (int(n.value),) + tuple(np.concatenate(q) if len(q) > 1 else q[0] for q in parts)
+
+    def stats(self):
+        """(links of every batch popped so far, windows written after collect) (dst_stream_links_stats)"""
+        links, late = C.c_uint64(), C.c_uint64()
+        self._eng._check(self._lib.dst_stream_links_stats(self._h, C.byref(links), C.byref(late)))
+        return int(links.value), int(late.value)

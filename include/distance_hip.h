@@ -308,6 +308,51 @@ int dst_stream_closest_result(dst_stream *stream, uint32_t *index, uint32_t *tal
  * required; tallies and values may be NULL.  DST_ERR_STATE when no batch has been collected. */
 int dst_stream_closest_batch(dst_stream *stream, const uint32_t **index, const uint32_t **tallies, const void **values,
                              uint32_t *k_used);
+/* ---- thresholded pairs in stream mode ------------------------------------------------------------ */
+/* A stream that hands back, instead of the result matrix, the pairs within a threshold: which records of a database that
+ * does not fit in memory are within T of mine, and at what distance.  A links stream IS a dst_stream: dst_stream_acquire /
+ * _submit / _collect / _in_flight / _close work on it as on a closest stream, with both wire formats, the caller's base
+ * counts and the ring of `depth` slots (dst_stream_collect returns *results = NULL, but still waits for the batch and still
+ * reports DST_ERR_INVALID_CODE).
+ * Definition.  The pair (streamed s, loaded i) is a link when its payload v - what the same stream would deliver for the
+ * pair as DST_OUT_DISTANCE, bit for bit (tn93: the streamed record's base counts as q, the loaded record's as t; the same
+ * use_base_counts) - satisfies dst_links' rule against `threshold`: n / n_high: v <= floor(threshold), the floor clamped to
+ * the int64 range (a floor below -2^63: nothing links, no compaction is launched); f64 measures: key(v) <= key(threshold)
+ * with dst_nearest's sort key, i.e. IEEE v <= threshold, except that NaN never links, -0.0 links wherever +0.0 does and
+ * threshold = +inf links every non-NaN value.
+ * A batch's links come in the stream's own order, streamed record outer, loaded record inner (the rectangle's canonical
+ * order with the batch as rows).  streamed[e] is the record's index WITHIN THE BATCH, 0 .. n_records - 1 (the caller numbers
+ * its stream); loaded[e] is the record of slot 0; values (DST_LINKS_VALUES) are bitwise the plain stream's DST_OUT_DISTANCE
+ * payloads and tallies (DST_LINKS_TALLIES) bitwise its DST_OUT_TALLY words, dst_tally_width(measure) per link.  The result
+ * depends neither on the kernel path, nor on window_links, nor - once the batch's first ordinal is added to `streamed` - on
+ * how the stream is cut into batches.  A links stream keeps nothing across batches: a batch with an invalid code makes its
+ * dst_stream_collect return DST_ERR_INVALID_CODE and its dst_stream_links_batch DST_ERR_STATE; later batches are unaffected.
+ * Windows.  window = window_links (0: DST_STREAM_LINKS_WINDOW), capped at max_records x n_loaded, at least 1 and at most
+ * DST_LINKS_CHUNK.  Window 0 of a batch is written on the compute stream at submit, directly behind the batch's pair kernel,
+ * count and scan, so the usual sparse batch costs no launch after collect; any other window is one write pass over the
+ * batch's matrix, which stays on the device until the slot is submitted again.  Per batch the bad-code word, the batch's
+ * link total and the links present in the window cross the host link: never the window's capacity, never the matrix.
+ * Open: a NULL ctx or stream pointer, an unknown measure or wire, a NaN threshold, bits in `what` other than
+ * DST_LINKS_VALUES | DST_LINKS_TALLIES, window_links > DST_LINKS_CHUNK, max_records == 0, depth outside 2..16, a loaded set
+ * of 2^32-1 records or more: DST_ERR_ARG; slot 0 not loaded: DST_ERR_STATE.  Submit: DST_ERR_STATE when the loaded set's
+ * record count changed while the stream was open.  Single GPU. */
+#define DST_STREAM_LINKS_WINDOW (1u << 20)   /* default most links of one window */
+int dst_stream_open_links(dst_ctx *ctx, int measure, double threshold, int what, uint64_t window_links,
+                          size_t max_records, int depth, int wire, dst_stream **stream);
+/* Valid from a successful dst_stream_collect until the next dst_stream_submit: links [first_link, min(first_link + window,
+ * *batch_links)) of the collected batch, *n_links of them, in page-locked, library-owned memory that is valid until the
+ * next call of this function or of dst_stream_submit.  first_link may be anything <= *batch_links (== gives *n_links = 0;
+ * above: DST_ERR_ARG, with *batch_links set).  The window the buffer already holds (first_link 0 after collect) costs
+ * nothing; any other is written now and the call waits for it.  values / tallies may be NULL; what was not asked for in
+ * `what` comes back NULL; what == 0 still delivers streamed and loaded.  On a plain or closest stream, or with a NULL
+ * n_links, batch_links, streamed or loaded: DST_ERR_ARG (as are the closest calls on a links stream); no collected
+ * batch: DST_ERR_STATE. */
+int dst_stream_links_batch(dst_stream *stream, uint64_t first_link, uint64_t *n_links, uint64_t *batch_links,
+                           const uint32_t **streamed, const uint32_t **loaded, const void **values,
+                           const uint32_t **tallies);
+/* A diagnostic, like dst_text_stats: the links of every batch collected so far, and how many windows were written after
+ * collect.  Either pointer may be NULL.  DST_ERR_ARG on a NULL, plain or closest stream. */
+int dst_stream_links_stats(const dst_stream *stream, uint64_t *links, uint64_t *late_windows);
 
 /* ---- multi-GPU: the gather of the result slabs (one process per GPU, RCCL over xGMI) --------- */
 /* The pair space shards by contiguous canonical ranges (dst_partition_square / dst_partition_rect): every rank
@@ -461,7 +506,7 @@ int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs
  * unknown measure, a NaN threshold, a bad slot, equal slots with square == 0, unknown bits in `what`, a set of 2^32-1
  * records or more.  DST_ERR_STATE: a set is not uploaded, or the widths differ (dst_nearest's message).  Synchronous on the
  * context's stream; per row slab a count, a scan and one windowed write per DST_LINKS_CHUNK links, no sort.  Slots, the
- * path choice and later results are untouched.  Single GPU, loaded sets only (not dst_stream). */
+ * path choice and later results are untouched.  Single GPU, loaded sets only (stream mode: dst_stream_open_links). */
 #define DST_LINKS_VALUES 1  /* hand the sink the links' DST_OUT_DISTANCE payloads */
 #define DST_LINKS_TALLIES 2 /* and/or dst_tally_width(measure) DST_OUT_TALLY words per link */
 #define DST_LINKS_CHUNK (1u << 22) /* the most links of one sink call */
