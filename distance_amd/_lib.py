@@ -28,6 +28,8 @@ PAIR_SITES_BATCH = 1 << 20    # DST_PAIR_SITES_BATCH: the most pairs of one devi
 PAIR_SITES_WINDOW = 1 << 24   # DST_PAIR_SITES_WINDOW: the most entries of one device output window
 SUMMARY_SCALE_BITS = 37   # DST_SUMMARY_SCALE_BITS: f64 distances are summed as rint(v * 2^37)
 SUMMARY_MAX_BINS = 4096   # DST_SUMMARY_MAX_BINS
+GROUPS_MAX = 1024         # DST_GROUPS_MAX: the most groups of one side of dst_group_summary
+GROUP_NONE = 0xFFFFFFFF   # DST_GROUP_NONE: a record that belongs to no group
 
 
 class LaunchInfo(C.Structure):
@@ -43,6 +45,12 @@ class SummaryTotals(C.Structure):
     """dst_summary_totals"""
     _fields_ = [("pairs", C.c_uint64), ("nan_pairs", C.c_uint64), ("summable_pairs", C.c_uint64), ("links", C.c_uint64),
                 ("sum", C.c_double)]
+
+
+class GroupCell(C.Structure):
+    """dst_group_cell"""
+    _fields_ = [("pairs", C.c_uint64), ("nan_pairs", C.c_uint64), ("summable_pairs", C.c_uint64), ("links", C.c_uint64),
+                ("sum", C.c_double), ("min_bits", C.c_uint64), ("max_bits", C.c_uint64)]
 
 
 class DistanceError(RuntimeError):
@@ -129,6 +137,8 @@ _SIGS = {
     "dst_pair_sites": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_size_t, _u64p]),
     "dst_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint32, C.c_double, _vp, _vp,
                               _vp, _vp, C.c_size_t, _vp]),
+    "dst_group_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, C.c_double,
+                                    C.c_uint64, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t]),
     "dst_mst": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, C.c_size_t, _u64p, _u32p]),
     "dst_nj": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, C.c_size_t]),
     "dst_nj_matrix": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_size_t]),

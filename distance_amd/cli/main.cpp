@@ -19,7 +19,9 @@
 // --max-distance T (the long output filtered on the GPU: only the lines of the pairs within T, in the full run's order:
 // dst_links), --summary T (one line per record: how many records lie within T of it, how many it was compared with and its
 // mean distance to them: dst_summary), --histogram W / --bins B (the histogram of the pairwise distances in B bins of width
-// W, one "lower edge, pairs" line per bin and a last line for the pairs without a distance: dst_summary), --sites (with
+// W, one "lower edge, pairs" line per bin and a last line for the pairs without a distance: dst_summary), --groups FILE /
+// --groups-within T / --per-record (one line per pair of groups of a label file, or per record and group: the pairs, the
+// compared pairs, their mean, smallest and largest distance: dst_group_summary), --sites (with
 // --max-distance or --mst: a fourth field per line, the sites that separate the two records: dst_pair_sites).
 //
 // Exactness: the GPU returns integer site tallies; f64 finalisation is dst_finalize() on the host
@@ -44,6 +46,8 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <unordered_map>
+#include <unordered_set>
 #include <vector>
 
 #include <unistd.h>
@@ -138,6 +142,16 @@ void print_help()
         "of width W (a number > 0; an integer with -m n / n_high), its lower edge and its pairs, the last bin open-ended, then "
         "the pairs without a distance (NaN). One GPU, no --stream and no other output mode\n"
         "      --bins <B>               Bins of the histogram, 1 to 4096 [default: 256]. Requires --histogram\n"
+        "      --groups <FILE>          Print one line per pair of groups instead of one per pair of records: FILE has one "
+        "'id<TAB>group' line per labelled record (no header; at most 1024 groups per input, numbered in order of their first "
+        "record); the line gives the pairs between the two groups, how many were compared (pairs with a distance), their "
+        "mean, smallest and largest distance. With two inputs: the groups of the first against those of the second. For "
+        "jc69 / k80 / tn93 min and max are the device's values and can differ from the long output's text in the 12th "
+        "decimal on a rounding boundary. One GPU, no --stream and no other output mode\n"
+        "      --groups-within <T>      With --groups: a 'within' column, the compared pairs within distance T (a number >= 0, "
+        "or inf)\n"
+        "      --per-record             With --groups: one line per record of the first input and group of the other side "
+        "instead (the record's compared partners in the group and its mean distance to them), labelled or not\n"
         "      --matrix <format>        Print a distance matrix instead of one line per pair: tsv (one or two inputs, rows "
         "from the first, columns from the last) or phylip (relaxed PHYLIP, one input). Not in stream, nearest or "
         "clusters mode\n"
@@ -185,6 +199,11 @@ struct Args {
     bool has_summary = false;
     double histogram = 0;                 // --histogram W
     bool has_histogram = false;
+    std::string groups;                   // --groups FILE
+    bool has_groups = false;
+    double groups_within = 0;             // --groups-within T
+    bool has_groups_within = false;
+    bool per_record = false;              // --per-record
     size_t bins = 256;                    // --bins B
     bool has_bins = false;
     int matrix = -1;                      // --matrix: DST_MATRIX_TSV / DST_MATRIX_PHYLIP (-1: the long form)
@@ -355,6 +374,28 @@ Args parse_args(int argc, char **argv)
                 die_usage("invalid value '" + v + "' for '--summary <T>': the threshold must not be negative");
             a.summary = t;
             a.has_summary = true;
+        } else if (arg == "--groups" || arg.rfind("--groups=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--groups <FILE>");
+            if (a.has_groups)
+                die_usage("the argument '--groups <FILE>' cannot be used multiple times");
+            a.groups = v;
+            a.has_groups = true;
+        } else if (arg == "--groups-within" || arg.rfind("--groups-within=", 0) == 0) {
+            const std::string v = value_of(k, arg, "--groups-within <T>");
+            if (a.has_groups_within)
+                die_usage("the argument '--groups-within <T>' cannot be used multiple times");
+            // the whole word is the number (or inf), as for --summary <T>
+            char *end = nullptr;
+            errno = 0;
+            const double t = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
+            if (v.empty() || end != v.c_str() + v.size() || t != t || std::isspace((unsigned char)v[0]))
+                die_usage("invalid value '" + v + "' for '--groups-within <T>': not a number");
+            if (t < 0)
+                die_usage("invalid value '" + v + "' for '--groups-within <T>': the threshold must not be negative");
+            a.groups_within = t;
+            a.has_groups_within = true;
+        } else if (arg == "--per-record") {
+            a.per_record = true;
         } else if (arg == "--histogram" || arg.rfind("--histogram=", 0) == 0) {
             const std::string v = value_of(k, arg, "--histogram <W>");
             if (a.has_histogram)
@@ -424,6 +465,24 @@ Args parse_args(int argc, char **argv)
         die_usage("unexpected argument '" + a.pos_inputs[2] + "' found");
     if (a.has_closest_for && !a.has_closest)
         die_usage("the argument '--closest-for <side>' requires '--closest <k>'");
+    if (a.has_groups_within && !a.has_groups)
+        die_usage("the argument '--groups-within <T>' requires '--groups <FILE>'");
+    if (a.per_record && !a.has_groups)
+        die_usage("the argument '--per-record' requires '--groups <FILE>'");
+    if (a.has_groups) {   // against every other output mode, before their own checks
+        const char *other = a.has_stream ? "--stream <stream>" : a.has_nearest ? "--nearest <k>" : a.has_closest ? "--closest <k>"
+                            : a.has_within ? "--within <T>" : a.has_clusters ? "--clusters <T>"
+                            : a.matrix >= 0 ? "--matrix <format>" : a.has_tree ? "--tree <method>"
+                            : a.has_bootstrap ? "--bootstrap <B>" : a.has_mst ? "--mst"
+                            : a.dendrogram >= 0 ? "--dendrogram <linkage>" : a.has_max_distance ? "--max-distance <T>"
+                            : a.has_sites ? "--sites" : a.has_histogram ? "--histogram <W>" : a.has_summary ? "--summary <T>"
+                            : nullptr;
+        if (other)
+            die_usage(std::string("the argument '--groups <FILE>' cannot be used with '") + other + "'");
+        if (a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1))
+            die_usage(std::string("the argument '--groups <FILE>' cannot be used with '") +
+                      (a.devices.size() > 1 ? "--devices <list>" : "--gpus <n>") + "' naming more than one GPU");
+    }
     if (a.has_sites) {   // a modifier of the two pair-list outputs: no other output mode, and one of the two
         const char *other = a.has_stream ? "--stream <stream>" : a.has_nearest ? "--nearest <k>" : a.has_closest ? "--closest <k>"
                             : a.has_clusters ? "--clusters <T>" : a.matrix >= 0 ? "--matrix <format>"
@@ -1708,6 +1767,165 @@ void write_summary(const Ctx &gpu, const std::vector<Alignment> &loaded, int mea
     wr.write(out.data(), out.size());
 }
 
+// --groups: the label file, read before any input is opened.  One "id<TAB>group" per line, empty lines skipped, no header.
+struct GroupFile {
+    std::string path;
+    std::unordered_map<std::string, std::pair<std::string, size_t>> of;   // id -> (group, the line that set it)
+};
+
+GroupFile read_group_file(const std::string &path)
+{
+    GroupFile gf;
+    gf.path = path;
+    FILE *fh = open_input(path);
+    std::string text;
+    char buf[1 << 16];
+    for (size_t got; (got = std::fread(buf, 1, sizeof buf, fh)) > 0;)
+        text.append(buf, got);
+    std::fclose(fh);
+    size_t line_no = 0;
+    for (size_t at = 0; at < text.size();) {
+        size_t end = text.find('\n', at);
+        if (end == std::string::npos)
+            end = text.size();
+        std::string line = text.substr(at, end - at);
+        at = end + 1;
+        ++line_no;
+        if (!line.empty() && line.back() == '\r')
+            line.pop_back();
+        if (line.empty())
+            continue;
+        const std::string where = "--groups: line " + std::to_string(line_no) + " of '" + path + "' ";
+        const size_t tab = line.find('\t');
+        if (tab == std::string::npos)
+            die_message(where + "has no tab: expected 'id<TAB>group'");
+        const std::string id = line.substr(0, tab), group = line.substr(tab + 1);
+        if (group.empty())
+            die_message(where + "has an empty group");
+        if (group.find('\t') != std::string::npos)
+            die_message(where + "has more than two fields");
+        const auto ins = gf.of.emplace(id, std::make_pair(group, line_no));
+        if (!ins.second && ins.first->second.first != group)
+            die_message(where + "gives '" + id + "' the group '" + group + "', line " + std::to_string(ins.first->second.second) +
+                        " gave it '" + ins.first->second.first + "'");
+    }
+    return gf;
+}
+
+// the labels of one input: groups numbered in order of their first record, as --clusters numbers its clusters
+struct GroupLabels {
+    std::vector<uint32_t> label;       // per record, DST_GROUP_NONE: not in the file
+    std::vector<std::string> names;    // per group
+    size_t assigned = 0;
+};
+
+GroupLabels label_records(const GroupFile &gf, const Alignment &set, const char *which, std::unordered_set<std::string> &seen)
+{
+    GroupLabels gl;
+    gl.label.assign(set.n, DST_GROUP_NONE);
+    std::unordered_map<std::string, uint32_t> number;
+    for (size_t r = 0; r < set.n; ++r) {
+        const auto it = gf.of.find(set.ids[r]);
+        if (it == gf.of.end())
+            continue;
+        seen.insert(set.ids[r]);
+        const auto ins = number.emplace(it->second.first, (uint32_t)gl.names.size());
+        if (ins.second) {
+            if (gl.names.size() == DST_GROUPS_MAX)
+                die_message("--groups: line " + std::to_string(it->second.second) + " of '" + gf.path + "' starts group " +
+                            std::to_string(DST_GROUPS_MAX + 1) + " of the " + which + " input: more than " +
+                            std::to_string(DST_GROUPS_MAX) + " groups");
+            gl.names.push_back(it->second.first);
+        }
+        gl.label[r] = ins.first->second;
+        ++gl.assigned;
+    }
+    if (gl.assigned == 0)
+        die_message("--groups: no record of the " + std::string(which) + " input has a group in '" + gf.path + "'");
+    return gl;
+}
+
+void append_distance(std::string &out, int measure, bool known, double v, int64_t iv)
+{
+    if (!known) {
+        out += "NaN";
+        return;
+    }
+    char num[64];
+    const int len = dst_format_distance(measure, v, iv, num, sizeof num);
+    out.append(num, (size_t)std::min<int>(len, (int)sizeof num - 1));
+}
+
+// --groups: one line per cell (one input: a <= b; two: every cell), or with --per-record one line per record of the first
+// input and group of the other side, from dst_group_summary.  mean = sum / compared as --summary prints its mean.
+void write_groups(const Ctx &gpu, const std::vector<Alignment> &loaded, const std::vector<GroupLabels> &labels, int measure,
+                  bool has_within, double threshold, uint64_t max_pairs, bool per_record, Writer &wr)
+{
+    const bool square = loaded.size() == 1;
+    const GroupLabels &rl = labels[0], &cl = labels.back();
+    const uint32_t Gr = (uint32_t)rl.names.size(), Gc = (uint32_t)cl.names.size();
+    const size_t n_rows = loaded[0].n;
+    std::vector<dst_group_cell> cells(per_record ? 0 : (size_t)Gr * Gc);
+    std::vector<uint32_t> within(per_record ? n_rows * Gc : 0), summable(per_record ? n_rows * Gc : 0);
+    std::vector<double> sum(per_record ? n_rows * Gc : 0);
+    gpu.check(dst_group_summary(gpu.h, measure, square ? 1 : 0, 0, 1, rl.label.data(), Gr, cl.label.data(), Gc,
+                                has_within ? threshold : HUGE_VAL, max_pairs, per_record ? nullptr : cells.data(), cells.size(),
+                                per_record ? within.data() : nullptr, per_record ? summable.data() : nullptr,
+                                per_record ? sum.data() : nullptr, sum.size()),
+              "group summary");
+    const bool int_payload = measure == DST_N || measure == DST_N_HIGH;
+    std::string out = per_record ? "sequence\tgroup\tcompared" : "group1\tgroup2\tpairs\tcompared";
+    if (has_within)
+        out += "\twithin";
+    out += per_record ? "\tmean\n" : "\tmean\tmin\tmax\n";
+    auto flush = [&](bool all) {
+        if (all || out.size() >= ((size_t)1 << 20)) {
+            wr.write(out.data(), out.size());
+            out.clear();
+        }
+    };
+    if (per_record) {
+        for (size_t x = 0; x < n_rows; ++x)
+            for (uint32_t g = 0; g < Gc; ++g) {
+                const size_t e = x * Gc + g;
+                out += loaded[0].ids[x];
+                out += '\t';
+                out += cl.names[g];
+                out += '\t';
+                out += std::to_string(summable[e]);
+                if (has_within)
+                    out += '\t' + std::to_string(within[e]);
+                out += '\t';
+                append_distance(out, DST_RAW, summable[e] != 0, summable[e] ? sum[e] / (double)summable[e] : 0.0, 0);
+                out += '\n';
+                flush(false);
+            }
+    } else {
+        for (uint32_t a = 0; a < Gr; ++a)
+            for (uint32_t b = square ? a : 0; b < Gc; ++b) {
+                const dst_group_cell &c = cells[(size_t)a * Gc + b];
+                out += rl.names[a];
+                out += '\t';
+                out += cl.names[b];
+                out += '\t' + std::to_string(c.pairs) + '\t' + std::to_string(c.summable_pairs);
+                if (has_within)
+                    out += '\t' + std::to_string(c.links);
+                out += '\t';
+                append_distance(out, DST_RAW, c.summable_pairs != 0, c.summable_pairs ? c.sum / (double)c.summable_pairs : 0.0, 0);
+                const bool known = c.pairs > c.nan_pairs;   // a pair whose payload is not NaN
+                for (const uint64_t bits : {c.min_bits, c.max_bits}) {
+                    double v = 0;
+                    std::memcpy(&v, &bits, 8);
+                    out += '\t';
+                    append_distance(out, measure, known, int_payload ? 0.0 : v, int_payload ? (int64_t)bits : 0);
+                }
+                out += '\n';
+                flush(false);
+            }
+    }
+    flush(true);
+}
+
 // --histogram: one line per bin, "lower edge, pairs" (the edge b W as the measure's distances are printed; the last bin is
 // open-ended), then "NaN, pairs without a distance"
 void write_histogram(const Ctx &gpu, const std::vector<Alignment> &loaded, int measure, double width, uint32_t bins,
@@ -1961,6 +2179,10 @@ int main(int argc, char **argv)
         die_message("For loading input files, don't use both positional arguments and the -i/--input flag");
     std::vector<std::string> inputs = a.flag_inputs;
     inputs.insert(inputs.end(), a.pos_inputs.begin(), a.pos_inputs.end());
+    // --groups: the label file's own errors come before anything else is opened
+    GroupFile group_file;
+    if (a.has_groups)
+        group_file = read_group_file(a.groups);
     std::vector<FILE *> files;
     if (inputs.empty())
         files.push_back(stdin);
@@ -2009,6 +2231,16 @@ int main(int argc, char **argv)
             die_message(err_lengths(loaded[0].width, loaded[1].width));
     }
     timer.mark("parse + encode loaded files");
+    // --groups: the records' labels, and what can be wrong with them, before the device is looked at
+    std::vector<GroupLabels> group_labels;
+    if (a.has_groups) {
+        std::unordered_set<std::string> seen;
+        for (size_t k = 0; k < loaded.size(); ++k)
+            group_labels.push_back(label_records(group_file, loaded[k], k == 0 ? "first" : "second", seen));
+        if (seen.size() < group_file.of.size())
+            std::fprintf(stderr, "warning: --groups: %zu ids of '%s' are not in the input and were skipped\n",
+                         group_file.of.size() - seen.size(), group_file.path.c_str());
+    }
     Writer wr;
     if (a.has_output) {
         wr.fh = std::fopen(a.output.c_str(), "wb");
@@ -2061,7 +2293,7 @@ int main(int argc, char **argv)
     } else if (a.has_sites) {
         static const char sites_header[] = "sequence1\tsequence2\tdistance\tsites\n";
         wr.write(sites_header, sizeof sites_header - 1);
-    } else if (!a.has_clusters && !a.has_tree && a.dendrogram < 0 && !a.has_summary && !a.has_histogram) {
+    } else if (!a.has_clusters && !a.has_tree && a.dendrogram < 0 && !a.has_summary && !a.has_histogram && !a.has_groups) {
         wr.write(header, sizeof header - 1);
     }
 
@@ -2083,6 +2315,9 @@ int main(int argc, char **argv)
             write_links(gpus[0], loaded, counts, measure, a.max_distance, a.has_slab_pairs ? a.slab_pairs : 0, wr);
     } else if (a.has_summary) {
         write_summary(gpus[0], loaded, measure, a.summary, a.has_slab_pairs ? a.slab_pairs : 0, wr);
+    } else if (a.has_groups) {
+        write_groups(gpus[0], loaded, group_labels, measure, a.has_groups_within, a.groups_within,
+                     a.has_slab_pairs ? a.slab_pairs : 0, a.per_record, wr);
     } else if (a.has_histogram) {
         write_histogram(gpus[0], loaded, measure, a.histogram, (uint32_t)a.bins, a.has_slab_pairs ? a.slab_pairs : 0, wr);
     } else if (a.has_nearest) {

@@ -777,6 +777,227 @@ int dst_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slo
     return DST_OK;
 }
 
+namespace {
+
+// the labels, then what comes back (the cells; behind them the per-record table), as one allocation
+size_t group_layout(void *base, bool square, uint64_t n_rows, uint64_t n_cols, uint32_t g_rows, uint32_t g_cols, GroupBuffers &b,
+                    size_t &cells_at, size_t &table_at)
+{
+    Carve c(base);
+    b.g_rows = g_rows;
+    b.g_cols = g_cols;
+    b.row_group = c.take<uint32_t>(n_rows);
+    b.col_group = square ? b.row_group : c.take<uint32_t>(n_cols);
+    b.order = c.take<uint32_t>(n_rows);
+    cells_at = c.used;
+    b.cell = c.take<uint64_t>((size_t)kGroupCellWords * g_rows * g_cols);
+    table_at = c.used;
+    b.counts = c.take<uint64_t>(n_rows * g_cols);
+    b.hi = c.take<int64_t>(n_rows * g_cols);
+    b.lo = c.take<uint64_t>(n_rows * g_cols);
+    return c.used;
+}
+
+// the payload of a sort key (nn_key, dst_device.hpp): -0.0 has the key of +0.0 and comes back as +0.0
+uint64_t payload_of_key(uint64_t key, bool int_payload)
+{
+    const uint64_t top = 0x8000000000000000ull;
+    if (int_payload)
+        return key ^ top;
+    return (key & top) ? key & ~top : ~key;
+}
+
+int group_labels(dst_ctx *ctx, const uint32_t *group, uint64_t n, uint32_t count, const char *side, std::vector<uint64_t> &size)
+{
+    size.assign(count, 0);
+    for (uint64_t x = 0; x < n; ++x) {
+        if (group[x] == DST_GROUP_NONE)
+            continue;
+        if (group[x] >= count)
+            return fail(ctx, DST_ERR_ARG, "group summary: " + std::string(side) + " record " + std::to_string(x) + " has label " +
+                                              std::to_string(group[x]) + ", which is neither below the group count " +
+                                              std::to_string(count) + " nor DST_GROUP_NONE");
+        ++size[group[x]];
+    }
+    return DST_OK;
+}
+
+}  // namespace
+
+int dst_group_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, const uint32_t *row_group,
+                      uint32_t n_row_groups, const uint32_t *col_group, uint32_t n_col_groups, double threshold,
+                      uint64_t max_pairs, dst_group_cell *cells, size_t cells_cap, uint32_t *rec_within, uint32_t *rec_summable,
+                      double *rec_sum, size_t rec_cap)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (!row_group)
+        return fail(ctx, DST_ERR_ARG, "null row_group pointer");
+    const bool per_record = rec_within || rec_summable || rec_sum;
+    if (!cells && !per_record)
+        return fail(ctx, DST_ERR_ARG, "null cells pointer and no per-record array");
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (std::isnan(threshold))
+        return fail(ctx, DST_ERR_ARG, "threshold is NaN");
+    if (square) {
+        col_group = row_group;
+        n_col_groups = n_row_groups;
+    } else if (!col_group)
+        return fail(ctx, DST_ERR_ARG, "null col_group pointer");
+    if (n_row_groups == 0 || n_row_groups > DST_GROUPS_MAX || n_col_groups == 0 || n_col_groups > DST_GROUPS_MAX)
+        return fail(ctx, DST_ERR_ARG, "a group count must be between 1 and " + std::to_string(DST_GROUPS_MAX));
+    const bool int_payload = measure_is_int(measure);
+    TwoSets ts;
+    if (int rc = two_sets(ctx, square != 0, row_slot, col_slot, ts, true, true))
+        return rc;
+    DeviceSet &rows = *ts.rows, &cols = *ts.cols;
+    const uint64_t n_rows = rows.n, n_cols = cols.n;
+    const uint32_t Gr = n_row_groups, Gc = n_col_groups;
+    std::vector<uint64_t> row_size, col_size_own;
+    if (int rc = group_labels(ctx, row_group, n_rows, Gr, square ? "set" : "row", row_size))
+        return rc;
+    if (!square)
+        if (int rc = group_labels(ctx, col_group, n_cols, Gc, "column", col_size_own))
+            return rc;
+    const std::vector<uint64_t> &col_size = square ? row_size : col_size_own;
+    const size_t n_cells = (size_t)Gr * Gc;
+    if (cells && cells_cap < n_cells)
+        return fail(ctx, DST_ERR_CAPACITY, "cells_cap is below " + std::to_string(n_cells) + " entries (row groups x column groups)");
+    if (per_record && rec_cap < n_rows * Gc)
+        return fail(ctx, DST_ERR_CAPACITY, "rec_cap is below " + std::to_string(n_rows * Gc) +
+                                               " entries (the row set's records x column groups)");
+    // what an empty call returns; `pairs` from the group sizes
+    const uint64_t none = int_payload ? 0 : 0x7FF8000000000000ull;
+    if (cells)
+        for (uint32_t a = 0; a < Gr; ++a)
+            for (uint32_t b = 0; b < Gc; ++b) {
+                const uint64_t p = square && a == b ? row_size[a] * (row_size[a] - (row_size[a] ? 1 : 0)) / 2 : row_size[a] * col_size[b];
+                cells[(size_t)a * Gc + b] = dst_group_cell{p, 0, 0, 0, 0.0, none, none};
+            }
+    for (uint64_t e = 0; per_record && e < n_rows * Gc; ++e) {
+        if (rec_within)
+            rec_within[e] = 0;
+        if (rec_summable)
+            rec_summable[e] = 0;
+        if (rec_sum)
+            rec_sum[e] = 0.0;
+    }
+    if (square ? n_rows < 2 : (n_rows == 0 || n_cols == 0))
+        return DST_OK;   // (no pair: no slab is run)
+    uint64_t rows_assigned = 0, cols_assigned = 0;
+    for (uint64_t s : row_size)
+        rows_assigned += s;
+    for (uint64_t s : col_size)
+        cols_assigned += s;
+    if (cols_assigned == 0 || (rows_assigned == 0 && !per_record))
+        return DST_OK;   // (no partner has a group, or no cell has a pair and only the cells are wanted)
+    uint64_t t_bits;
+    const bool any = threshold_payload(measure, threshold, t_bits);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const SlabPlan plan = plan_slabs(square != 0, n_rows, n_cols, max_pairs, kClusterSlabPairs);
+    GroupBuffers b{};
+    size_t cells_at = 0, table_at = 0;
+    const size_t state_bytes = group_layout(nullptr, square != 0, n_rows, n_cols, Gr, Gc, b, cells_at, table_at);
+    int rc = slab_scratch(ctx, dst_out_bytes(measure, DST_OUT_DISTANCE, plan.biggest));
+    if (rc)
+        return rc;
+    if (ctx->group_work.grow(ctx, state_bytes)) {
+        (void)hipGetLastError();
+        return fail(ctx, DST_ERR_NOMEM, "group summary: cannot allocate " + std::to_string(state_bytes) + " bytes of device memory");
+    }
+    // the labels and the row records in order of their group (a counting sort), through page-locked staging
+    const size_t label_bytes = cells_at;
+    rc = ctx->group_host.grow(ctx, label_bytes, "group summary");
+    if (rc)
+        return rc;
+    GroupBuffers st{};
+    size_t unused_a = 0, unused_b = 0;
+    group_layout(ctx->group_host, square != 0, n_rows, n_cols, Gr, Gc, st, unused_a, unused_b);
+    std::memcpy(st.row_group, row_group, n_rows * 4);
+    if (!square)
+        std::memcpy(st.col_group, col_group, n_cols * 4);
+    {
+        std::vector<uint64_t> next(Gr, 0);
+        for (uint32_t a = 1; a < Gr; ++a)
+            next[a] = next[a - 1] + row_size[a - 1];
+        for (uint64_t x = 0; x < n_rows; ++x)
+            if (row_group[x] != DST_GROUP_NONE)
+                st.order[next[row_group[x]]++] = (uint32_t)x;
+    }
+    group_layout(ctx->group_work, square != 0, n_rows, n_cols, Gr, Gc, b, cells_at, table_at);
+    static const bool no_aggregation = std::getenv("DST_GROUPS_NO_AGGREGATION") != nullptr;   // measurement knob
+    char *dev = static_cast<char *>(ctx->group_work.ptr);
+    HIP_TRY(ctx, hipMemcpyAsync(dev, ctx->group_host.ptr, label_bytes, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipMemsetAsync(dev + cells_at, 0, state_bytes - cells_at, stream));
+    HIP_TRY(ctx, hipMemsetAsync(b.cell + 5 * n_cells, 0xFF, n_cells * 8, stream));   // (the min keys: none yet)
+    const uint64_t *slab = static_cast<const uint64_t *>(ctx->pair_slab.ptr);
+    rc = walk_slabs(ctx, measure, square != 0, rows, cols, plan.slabs, DST_OUT_DISTANCE, [&](const RowSlab &s) -> int {
+        HIP_TRY(ctx, launch_group_rows(measure, square != 0, slab, s.first, n_cols, s.rb, s.re, t_bits, any, !no_aggregation, b, stream));
+        if (square)
+            HIP_TRY(ctx, launch_group_cols(measure, slab, s.first, n_cols, s.rb, s.re, t_bits, any, b, stream));
+        return DST_OK;
+    });
+    if (rc)
+        return rc;
+    HIP_TRY(ctx, launch_group_fold(b, rows_assigned, stream));
+    // the cells, and the table behind them when it is wanted, back in one copy
+    const size_t back = (per_record ? state_bytes : table_at) - cells_at;
+    std::vector<char> host(back);
+    HIP_TRY(ctx, hipMemcpyAsync(host.data(), dev + cells_at, back, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    GroupBuffers h{};   // (the copy starts at the cells: the layout's pieces from there)
+    const size_t piece = (n_rows * Gc * 8 + 255) / 256 * 256;
+    h.cell = reinterpret_cast<uint64_t *>(host.data());
+    if (per_record) {
+        h.counts = reinterpret_cast<uint64_t *>(host.data() + (table_at - cells_at));
+        h.hi = reinterpret_cast<int64_t *>(host.data() + (table_at - cells_at) + piece);
+        h.lo = reinterpret_cast<uint64_t *>(host.data() + (table_at - cells_at) + 2 * piece);
+    }
+    if (cells) {
+        const uint64_t *nan = h.cell, *links = h.cell + n_cells, *summ = h.cell + 2 * n_cells, *high = h.cell + 3 * n_cells,
+                       *low = h.cell + 4 * n_cells, *kmin = h.cell + 5 * n_cells, *kmax = h.cell + 6 * n_cells;
+        for (uint32_t a = 0; a < Gr; ++a)
+            for (uint32_t g = 0; g < Gc; ++g) {
+                const size_t c = (size_t)a * Gc + g, m = (size_t)g * Gc + a;   // (m: the mirror cell of the square)
+                dst_group_cell &out = cells[c];
+                __int128 S = (__int128)(((unsigned __int128)high[c] << 64) | low[c]);
+                uint64_t n_links = links[c], n_summ = summ[c], n_nan = nan[c], lo_key = kmin[c], hi_key = kmax[c];
+                if (square && a == g) {
+                    // the fold met every pair of the diagonal cell from both of its records
+                    if (n_links % 2 || n_summ % 2 || S % 2)
+                        return fail(ctx, DST_ERR_STATE, "group summary: internal error, the two sides of the square disagree");
+                    n_links /= 2, n_summ /= 2, S /= 2;
+                } else if (square) {
+                    // the row pass met a pair as (group of i, group of j), i < j: either order may hold it
+                    n_nan += nan[m];
+                    lo_key = std::min(lo_key, kmin[m]);
+                    hi_key = std::max(hi_key, kmax[m]);
+                }
+                if (n_nan + n_summ > out.pairs || n_links > out.pairs)
+                    return fail(ctx, DST_ERR_STATE, "group summary: internal error, a cell counts more than its pairs");
+                out.nan_pairs = n_nan;
+                out.summable_pairs = n_summ;
+                out.links = n_links;
+                out.sum = summary_value(S, int_payload);
+                if (out.pairs > n_nan) {
+                    out.min_bits = payload_of_key(lo_key, int_payload);
+                    out.max_bits = payload_of_key(hi_key, int_payload);
+                }
+            }
+    }
+    for (uint64_t e = 0; per_record && e < n_rows * Gc; ++e) {
+        if (rec_within)
+            rec_within[e] = (uint32_t)(h.counts[e] >> 32);
+        if (rec_summable)
+            rec_summable[e] = (uint32_t)h.counts[e];
+        if (rec_sum)
+            rec_sum[e] = summary_value((__int128)h.hi[e] * ((__int128)1 << 32) + (__int128)h.lo[e], int_payload);
+    }
+    return DST_OK;
+}
+
 int dst_mst(dst_ctx *ctx, int measure, uint64_t max_pairs, uint32_t *edge_i, uint32_t *edge_j, void *values,
             uint32_t *tallies, size_t cap, uint64_t *n_edges, uint32_t *rounds)
 {

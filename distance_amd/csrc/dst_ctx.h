@@ -166,6 +166,9 @@ struct dst_ctx {
     Grown<char> ps_batch, ps_window;
     Grown<char, true> ps_batch_host, ps_window_host;
     Grown<> summary_work;   // dst_summary: the per-record counters and accumulators, the histogram and the totals
+    // dst_group_summary: the labels, the cells and the per-record table; the labels' page-locked staging
+    Grown<> group_work;
+    Grown<char, true> group_host;
     // HIP events around the pair kernel ([0]) and the pack kernel ([1]) of the most recent launches, recorded on the launch
     // stream: a ring, so that a caller timing many steps reads them ONCE at the end (dst_kernel_ms_mean) instead of
     // waiting for the device after every step

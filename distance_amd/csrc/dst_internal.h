@@ -516,6 +516,32 @@ hipError_t launch_summary_cols(int measure, const uint64_t *slab, uint64_t out_b
 hipError_t launch_summary_hist(int measure, const uint64_t *slab, uint64_t pairs, uint32_t bins, uint64_t width_q,
                                uint64_t t_bits, bool any, bool aggregate, const SummaryBuffers &b, hipStream_t stream);
 
+// ---- group summaries (dst_group_summary.hip, driven by dst_group_summary in dst_analysis.cpp) --------------------------
+// dst_summary's per-pair quantities keyed by group.  Per row slab a row pass (the per-record table's entry (row, group of
+// the column) and the cell's NaN count, smallest and largest key) and, in the square, a column pass (entry (column, group
+// of the row)); after the walk one fold of the table into the cells' links, summable pairs and 128-bit sums.  All integer.
+constexpr int kGroupCellWords = 7;   // planes of `cell`: NaN pairs, links, summable pairs, the high and the low word of the
+                                     // 128-bit sum, the smallest nn_key (~0: none), the largest (0: none)
+struct GroupBuffers {
+    uint32_t *row_group;   // [n_rows] labels below g_rows, or DST_GROUP_NONE
+    uint32_t *col_group;   // [n_cols] labels below g_cols (the square: row_group again)
+    uint32_t *order;       // [n_rows] the row records that have a group, in order of it
+    uint64_t *cell;        // [kGroupCellWords][g_rows g_cols]
+    uint64_t *counts;      // [n_rows g_cols] within << 32 | summable of (record, column group)
+    int64_t *hi;           // [n_rows g_cols] sum of (q >> 32)
+    uint64_t *lo;          // [n_rows g_cols] sum of (q & 0xFFFFFFFF)
+    uint32_t g_rows, g_cols;
+};
+// rows [rb, re) of the slab, indexed as launch_summary_rows'; aggregate: a wave adds its entries of one group to the
+// workgroup's table once (false: the measurement's other side)
+hipError_t launch_group_rows(int measure, bool square, const uint64_t *slab, uint64_t out_base, uint64_t n_cols, uint64_t rb,
+                             uint64_t re, uint64_t t_bits, bool any, bool aggregate, const GroupBuffers &b, hipStream_t stream);
+// the same rows of the square, pairs (i, j > i), added to entry (j, group of i)
+hipError_t launch_group_cols(int measure, const uint64_t *slab, uint64_t out_base, uint64_t n, uint64_t rb, uint64_t re,
+                             uint64_t t_bits, bool any, const GroupBuffers &b, hipStream_t stream);
+// the table of the first `assigned` records of b.order into the cells
+hipError_t launch_group_fold(const GroupBuffers &b, uint64_t assigned, hipStream_t stream);
+
 // ---- minimum spanning forest (dst_mst.hip, driven by dst_mst in dst_analysis.cpp) -------------------------------------
 // Boruvka rounds: every round runs each row slab of the triangle into the DST_OUT_DISTANCE scratch (as dst_clusters) and
 // scans it twice (the minimal key of every component's outgoing edges, then the smallest pair of that key), hooks every

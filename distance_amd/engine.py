@@ -11,8 +11,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (ALLGATHER_FN, LINKS_CHUNK, LINKS_SINK, LINKS_TALLIES, LINKS_VALUES, SLAB_SINK, DistanceError, LaunchInfo,
-                   SummaryTotals, load)
+from ._lib import (ALLGATHER_FN, GROUP_NONE, LINKS_CHUNK, LINKS_SINK, LINKS_TALLIES, LINKS_VALUES, SLAB_SINK, DistanceError,
+                   GroupCell, LaunchInfo, SummaryTotals, load)
 
 MEASURES = {"n": 0, "n_high": 1, "raw": 2, "jc69": 3, "k80": 4, "tn93": 5}
 INT_MEASURES = ("n", "n_high")
@@ -578,6 +578,65 @@ class Engine:
             out.update(within=within[:n_rows], summable=summable[:n_rows], sum=sums[:n_rows])
         if bins:
             out["hist"] = hist[:bins]
+        return out
+
+    def group_summary(self, measure, groups, n_groups=None, threshold: float = float("inf"), square: bool = True,
+                      row_slot: int = 0, col_slot: int = 1, col_groups=None, n_col_groups=None, max_pairs: int = 0,
+                      per_record: bool = False) -> dict:
+        """dst_summary's sums keyed by group (dst_group_summary).  `groups`: one integer label per row record (square: per
+        record of slot 0), -1 or 2^32-1 for a record that belongs to no group; n_groups defaults to the largest label + 1.
+        A rectangle takes col_groups / n_col_groups for the column set too.  Returns a dict of (G_r, G_c) arrays: `pairs`,
+        `nan_pairs`, `summable_pairs`, `links` (uint64), `sum` (float64, the exact fixed-point sum rounded once), `min` and
+        `max` (int64 or float64 by measure; NaN, or 0 for n / n_high, in a cell without a pair that is not NaN).  The square
+        stores both orders of a cell; cell (a, a) holds the pairs inside a.  per_record=True adds `rec_within`,
+        `rec_summable` (uint32) and `rec_sum` (float64) of shape (n_rows, G_c): dst_summary's per-record results restricted
+        to the partners in each group, for every row record, assigned or not."""
+        m = _measure_id(measure)
+        n_rows, _ = self.set_info(0 if square else row_slot)
+
+        def labels(g, n, count, side):
+            g = np.asarray(g)
+            if g.ndim != 1 or len(g) != n or not np.issubdtype(g.dtype, np.integer):
+                raise ValueError(f"{side} must be a 1-D integer array with one label per record ({n})")
+            g64 = g.astype(np.int64)
+            g64 = np.where(g64 == -1, GROUP_NONE, g64)
+            if ((g64 < 0) | (g64 > GROUP_NONE)).any():
+                raise ValueError(f"{side}: a label is neither -1 nor a 32-bit unsigned value")
+            if count is None:
+                assigned = g64[g64 != GROUP_NONE]
+                count = int(assigned.max()) + 1 if len(assigned) else 1
+            return np.ascontiguousarray(g64.astype(np.uint32)), int(count)
+
+        rg, Gr = labels(groups, n_rows, n_groups, "groups")
+        if square:
+            cg, Gc = rg, Gr
+        else:
+            if col_groups is None:
+                raise ValueError("the rectangle form needs col_groups")
+            cg, Gc = labels(col_groups, self.set_info(col_slot)[0], n_col_groups, "col_groups")
+        for count in (Gr, Gc):
+            if not 0 <= count <= GROUP_NONE:
+                raise ValueError("a group count must fit 32 bits")
+        cells = (GroupCell * max(Gr * Gc, 1))()
+        n_rec = n_rows * Gc
+        within = np.zeros(max(n_rec, 1), np.uint32) if per_record else None
+        summable = np.zeros(max(n_rec, 1), np.uint32) if per_record else None
+        sums = np.zeros(max(n_rec, 1), np.float64) if per_record else None
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data
+
+        self._check(self._lib.dst_group_summary(self._h, m, int(square), row_slot, col_slot, rg.ctypes.data, Gr,
+                                                None if square else cg.ctypes.data, Gc, float(threshold), int(max_pairs),
+                                                C.addressof(cells), Gr * Gc, ptr(within), ptr(summable), ptr(sums), n_rec))
+        raw = np.frombuffer(cells, dtype=np.uint64, count=Gr * Gc * 7).reshape(Gr, Gc, 7)
+        value = np.int64 if m in (0, 1) else np.float64
+        out = {"pairs": raw[:, :, 0].copy(), "nan_pairs": raw[:, :, 1].copy(), "summable_pairs": raw[:, :, 2].copy(),
+               "links": raw[:, :, 3].copy(), "sum": raw[:, :, 4].copy().view(np.float64),
+               "min": raw[:, :, 5].copy().view(value), "max": raw[:, :, 6].copy().view(value)}
+        if per_record:
+            out.update(rec_within=within[:n_rec].reshape(n_rows, Gc), rec_summable=summable[:n_rec].reshape(n_rows, Gc),
+                       rec_sum=sums[:n_rec].reshape(n_rows, Gc))
         return out
 
     def mst(self, measure, max_pairs: int = 0, tallies: bool = False):

@@ -604,6 +604,64 @@ typedef struct dst_summary_totals {
 int dst_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, double threshold, uint64_t max_pairs,
                 uint32_t bins, double width, uint64_t *hist, uint32_t *within, uint32_t *summable, double *sum, size_t cap,
                 dst_summary_totals *totals);
+/* ---- group summaries ------------------------------------------------------------------------------ */
+/* dst_summary's exact sums keyed by a labelling of the records (lineages, sites, sampling months): per pair of groups the
+ * number of pairs, of links and of summable pairs, the sum of the distances, the smallest and the largest distance ("within
+ * group" and "between group" mean distance, pi and d_xy; the input of silhouettes and medoids); and per record and group
+ * the same sums over the record's partners in that group (which places an unlabelled record next to its closest group).
+ * O(n G + G^2) of state; the full result is never written.
+ *   pairs    dst_summary's.  square != 0: slot 0 against itself (row_slot / col_slot ignored), the pairs i < j;
+ *            square == 0: every record of row_slot against every record of col_slot, row_slot == col_slot is DST_ERR_ARG.
+ *   labels   row_group[x] for every record x of the row set: a group below n_row_groups, or DST_GROUP_NONE (the record
+ *            belongs to no group); col_group / n_col_groups the same for the column set.  In the square form the one label
+ *            array is row_group and the one count n_row_groups = G; col_group and n_col_groups are ignored.
+ * Per pair the link against `threshold`, the fixed-point value q, "summable" and NaN are dst_summary's, word for word.
+ * cells (may be NULL when a rec_* array is given): row-major n_row_groups x n_col_groups (square: G x G).  Cell (a, b)
+ * covers the pairs with one record in group a and the other in group b, each pair once: in a rectangle the row record in a
+ * and the column record in b; in the square both orders are stored, cells[a][b] == cells[b][a] byte for byte, and cell
+ * (a, a) holds the pairs i < j inside a.  A pair with an unassigned record is in no cell.
+ *   pairs            from the group sizes alone: |a| |b|, or |a| (|a| - 1) / 2 on the square's diagonal
+ *   nan_pairs, summable_pairs, links   counts over the cell's pairs; nan_pairs + summable_pairs <= pairs
+ *   sum              dst_summary's conversion of the exact integer sum of q over the cell's summable pairs (kept in 128
+ *                    bits: a cell can hold 2^32 pairs and more)
+ *   min_bits, max_bits   over the cell's pairs whose payload is not NaN: the payloads with the smallest and the largest
+ *                    dst_nearest sort key, decoded back from the key (so a -0.0 is reported as +0.0).  A cell without such
+ *                    a pair: the quiet NaN 0x7FF8000000000000 for the f64 measures, 0 for n / n_high (there it means
+ *                    pairs == 0).
+ * rec_within, rec_summable, rec_sum (each may be NULL: not wanted): row-major n_rows x n_col_groups (square: n x G).  Entry
+ * (x, g) is dst_summary's within / summable / sum of record x restricted to its partners in group g.  Every record x has
+ * a row, assigned or not; a record is never its own partner; the square form counts a pair for both of its records;
+ * partners that are unassigned appear nowhere.
+ * Consequences: for a != b cell (a, b) is the sum of rec_*[x][b] over the x in a; cell (a, a) is half of that sum, which
+ * is even.  With every record assigned the cells' totals (square: over a <= b; rectangle: over all cells) are
+ * dst_summary's totals and the sum over g of rec_*[x][g] is dst_summary's per-record result (the sums before their
+ * conversion).  Every accumulation is an integer one: the result depends neither on the path, nor on max_pairs, nor on
+ * the order the pairs are met in.
+ *   threshold   any non-NaN double
+ *   max_pairs   0: the default slab bound (2^25 pairs); else the most pairs of one row slab
+ *   cells_cap   the room of cells in entries; rec_cap the room of each non-NULL rec_* array in entries
+ * DST_ERR_ARG: a NULL ctx or row_group; NULL cells with all three rec_* NULL; an unknown measure; a NaN threshold; a NULL
+ * col_group in the rectangle form; a group count of 0 or above DST_GROUPS_MAX; a bad slot, equal slots with square == 0, a
+ * set of 2^32-1 records or more (dst_summary's messages); a label that is neither below its count nor DST_GROUP_NONE (the
+ * message names the first such record and its side).  DST_ERR_CAPACITY: cells_cap or rec_cap too small.  DST_ERR_STATE: a
+ * set is not uploaded, or the widths differ.  DST_ERR_NOMEM: the state does not fit in device memory (the message gives
+ * the byte count).  A square set of fewer than 2 records, an empty row or column set, and a call in which no record of
+ * the column side (the square: of the set) is assigned or whose cells alone are wanted while no row record is assigned:
+ * DST_OK, zero counts and sums, min / max as for an empty cell, no slab run.  Synchronous on the context's stream; slots,
+ * the path choice and later results are untouched.  Single GPU, loaded sets only (not dst_stream). */
+#define DST_GROUPS_MAX 1024u          /* most groups of one side */
+#define DST_GROUP_NONE 0xFFFFFFFFu    /* a record that belongs to no group */
+typedef struct dst_group_cell {
+    uint64_t pairs, nan_pairs, summable_pairs, links;
+    double   sum;                     /* dst_summary's conversion of the exact integer sum of q */
+    uint64_t min_bits, max_bits;      /* DST_OUT_DISTANCE payloads (int64 or f64 bits) */
+} dst_group_cell;
+int dst_group_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
+                      const uint32_t *row_group, uint32_t n_row_groups,
+                      const uint32_t *col_group, uint32_t n_col_groups,
+                      double threshold, uint64_t max_pairs,
+                      dst_group_cell *cells, size_t cells_cap,
+                      uint32_t *rec_within, uint32_t *rec_summable, double *rec_sum, size_t rec_cap);
 /* ---- minimum spanning tree --------------------------------------------------------------------- */
 /* The single-linkage picture for every threshold at once: the minimum spanning tree (forest) of one set (slot 0, n
  * records), as GrapeTree- and PHYLOViZ-style viewers draw it, computed next to the values on the GPU by Boruvka rounds
