@@ -1,6 +1,8 @@
 // dst_kernels.hip — hand-written gfx950 (MI355X, CDNA4) kernels of the all-pairs distance path.
 //
 //   pack_kernel      Paradis bytes (src/encoding.rs:4-41)  ->  8 bit-planes, validates codes
+//   pack_stream_kernel   the same for what the consensus path uploads: rows read as streams and
+//                    compared with the reference sequence first, pack_chunk only where they differ
 //   counts_kernel    per-record {A,T,G,C} counts            (src/fastaio.rs:53-66)
 //   pair_kernel<M>   site tallies of every pair of a tile   (src/measures.rs:14-23, 56-66,
 //                                                            85-107, 156-175)
@@ -59,21 +61,20 @@ __device__ __forceinline__ void derive_planes(uint32_t A, uint32_t G, uint32_t C
     X0 = K & (G | T);
 }
 
-// One thread = one (record, 128-site chunk).  Lanes run along records, so the eight 16-byte
-// plane stores of a wave are 1 KiB contiguous each; every lane reads its own 128-byte line.
+// One (record s, 128-site chunk c) of the pack, whole: the thread reads the chunk's 128-byte line, validates it and writes
+// the planes, the slot and the record's counters.  Both forms of the pack run this (pack_kernel for every chunk,
+// pack_stream_kernel for the chunks its compare found something in).
 // Sites >= len and records >= n are filled with N (0xF0): N contributes nothing to any tally.
-__global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ codes,
-                                                   size_t row_stride, uint32_t n, uint32_t len,
-                                                   uint32_t nchunks, uint32_t npad,
-                                                   uint4 *__restrict__ planes,
-                                                   unsigned long long *__restrict__ first_bad,
-                                                   int aligned16, PackLists lists, uint32_t rec_first, uint32_t rec_last)
+// The record's counters are added to at ctr.*[ci]: the lists' own at the record's index (pack_kernel), or a block's
+// sums in LDS (pack_stream_kernel).
+struct PackCounters {
+    uint32_t *cold, *hot, *run, *run_cold, *run_hot;
+};
+__device__ __forceinline__ void pack_chunk(const uint8_t *__restrict__ codes, size_t row_stride, uint32_t n, uint32_t len,
+                                           uint32_t nchunks, uint32_t npad, uint4 *__restrict__ planes,
+                                           unsigned long long *__restrict__ first_bad, int aligned16, const PackLists &lists,
+                                           uint32_t s, uint32_t c, const PackCounters &ctr, uint32_t ci)
 {
-    // records [rec_first, rec_last): the whole padded set, or one rank's share of it (dst_upload_shared)
-    const uint32_t s = rec_first + blockIdx.y * blockDim.x + threadIdx.x;
-    const uint32_t c = blockIdx.x;
-    if (s >= rec_last)
-        return;
     uint32_t out[PL_COUNT][4];
 #pragma unroll
     for (int p = 0; p < PL_COUNT; ++p)
@@ -207,11 +208,11 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ c
                 run_chunk = all_n == 0xFFFFFFFFu;   // (cold + hot != 0: the reference is not all N-class here)
             }
             if (run_chunk) {
-                atomicAdd(&lists.cnt_run[s], 1u);
+                atomicAdd(&ctr.run[ci], 1u);
                 if (cold)
-                    atomicAdd(&lists.run_cold[s], cold);
+                    atomicAdd(&ctr.run_cold[ci], cold);
                 if (hot)
-                    atomicAdd(&lists.run_hot[s], hot);
+                    atomicAdd(&ctr.run_hot[ci], hot);
                 slot[0] = min(cold + hot, 255u) | 0x100u;
             } else if (cold + hot) {
 #pragma unroll
@@ -231,9 +232,9 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ c
                     }
                 }
                 slot[0] |= min(cold + hot, 255u);
-                atomicAdd(&lists.cnt_cold[s], cold);   // (adding 0 for an all-hot chunk is harmless)
+                atomicAdd(&ctr.cold[ci], cold);   // (adding 0 for an all-hot chunk is harmless)
                 if (hot)
-                    atomicAdd(&lists.cnt_hot[s], hot);
+                    atomicAdd(&ctr.hot[ci], hot);
             }
             inline_slot = inline_slot && slot_is_inline(slot[0]);
         }
@@ -250,6 +251,246 @@ __global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ c
     for (int p = 0; p < PL_COUNT; ++p)
         if (p <= PL_T ? !inline_slot : !low_diversity)
             planes[((size_t)p * nchunks + c) * npad + s] = make_uint4(out[p][0], out[p][1], out[p][2], out[p][3]);
+}
+
+// One thread = one (record, 128-site chunk).  Lanes run along records, so the eight 16-byte
+// plane stores of a wave are 1 KiB contiguous each; every lane reads its own 128-byte line.
+__global__ __launch_bounds__(256) void pack_kernel(const uint8_t *__restrict__ codes,
+                                                   size_t row_stride, uint32_t n, uint32_t len,
+                                                   uint32_t nchunks, uint32_t npad,
+                                                   uint4 *__restrict__ planes,
+                                                   unsigned long long *__restrict__ first_bad,
+                                                   int aligned16, PackLists lists, uint32_t rec_first, uint32_t rec_last)
+{
+    // records [rec_first, rec_last): the whole padded set, or one rank's share of it (dst_upload_shared)
+    const uint32_t s = rec_first + blockIdx.y * blockDim.x + threadIdx.x;
+    const uint32_t c = blockIdx.x;
+    if (s >= rec_last)
+        return;
+    const PackCounters ctr{lists.cnt_cold, lists.cnt_hot, lists.cnt_run, lists.run_cold, lists.run_hot};
+    pack_chunk(codes, row_stride, n, len, nchunks, npad, planes, first_bad, aligned16, lists, s, c, ctr, s);
+}
+
+// The second form of the pack, for what the consensus path uploads: lists wanted, planes deferred, rows on 16-byte
+// boundaries.  On such a set nearly every byte equals the reference sequence's, and a chunk whose 128 bytes all do has a zero
+// slot, no counts and no planes: finding that out needs a compare, not pack_chunk's gather of eight bit planes, and it can
+// read the matrix as streams.  A block = kStreamRows records x one 1 KiB span (8 chunks) of each.
+//   0. the span's reference bytes, once per block into LDS (the site's base as 0x88 / 0x48 / 0x28 / 0x18, the N class as
+//      0xF0: a byte that equals it is a valid code and no difference), and its hot bits.
+//   1. stream: a wave takes kStreamWaveRows records; one load instruction reads one record's KiB (lane l = the piece of
+//      sites 16 l .. 16 l + 15, whole lines, where pack_kernel's lanes touch 64 rows a row apart).  The lane holds its 16
+//      reference bytes in registers; per record it compares, the wave ballots "not all equal" and lane k keeps the
+//      ballot of the wave's record k (a compare, a ballot and a conditional move per row: no prefix, no LDS traffic).
+//   2. the (record, chunk)s with a marked piece are queued in LDS — chunk by chunk, records side by side.
+//   3. one thread per queued (record, chunk) reads the marked pieces again, byte by differing byte: the validity rule,
+//      the entry, the counts — the slot as pack_chunk builds it, into LDS.  What does not end in an inline slot (more
+//      than kSlotEntries differences, a chunk of N: planes to store, run counters) is queued once more ...
+//   4. the block's slots leave LDS as 1 KiB stores along the records (the zero slots of the chunks with nothing in them
+//      among them: left to the threads that found something, they were stores of partial lines, 0.1 ms at 50,000 x 30,000),
+//   5. ... pack_chunk itself for the second queue,
+//   6. and the records' counters, summed over the block in LDS, are added to the lists' with one atomic per record and
+//      block (one per chunk, from a wave whose lanes are a few records' chunks, cost 0.06 ms and far more with runs of N).
+// A set the sample calls diverse (the device-side test; the host cannot know at launch) skips 0 to 4 and queues
+// everything for 5: the block then is pack_kernel's shape, a wave = 64 records x one chunk.  So do the blocks of the
+// chunks behind a row's last whole span (span index nspans: up to 7 whole chunks and a partial one).
+constexpr uint32_t kStreamWaveRows = 16, kStreamRows = 4 * kStreamWaveRows, kStreamChunks = 8;
+constexpr uint32_t kStreamSpan = kStreamChunks * kChunkSites;
+
+__global__ __launch_bounds__(256, 6) void pack_stream_kernel(const uint8_t *__restrict__ codes, size_t row_stride, uint32_t n,
+                                                          uint32_t len, uint32_t nchunks, uint32_t npad,
+                                                          uint4 *__restrict__ planes,
+                                                          unsigned long long *__restrict__ first_bad, int aligned16,
+                                                          PackLists lists, uint32_t rec_first, uint32_t rec_last, uint32_t nspans,
+                                                          uint32_t grid_spans)
+{
+    static_assert(kStreamRows == 64 && kStreamWaveRows == 16 && kStreamSpan == 4 * 256, "item = chunk * 64 + record; a thread = a word");
+    constexpr uint32_t kItems = kStreamRows * kStreamChunks, kWhole = 0xFFFFFFFFu;
+    __shared__ uint4 s_ref[64];                              // the span's reference bytes, a lane's 16 at a time
+    __shared__ uint32_t s_hot[4 * kStreamChunks];            // its hot bits
+    __shared__ unsigned long long s_ref_n;                   // pieces (lanes) whose 16 reference sites are all N class
+    __shared__ unsigned long long s_piece[kStreamRows];      // per record: the pieces that do not equal the reference
+    __shared__ uint32_t s_count, s_count_whole;
+    __shared__ uint16_t s_list[kItems], s_whole[kItems];
+    __shared__ uint4 s_slot[kItems];
+    __shared__ uint32_t s_ctr[5][kStreamRows];               // cold, hot, run chunks, their cold, their hot
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint32_t span = blockIdx.x % grid_spans, row0 = rec_first + (blockIdx.x / grid_spans) * kStreamRows;
+    const uint32_t c0 = span * kStreamChunks;
+    const bool low_diversity = lists.stats[1] <= lists.max_dev_sum;
+    bool streamed = false;
+    if (threadIdx.x == 0)
+        s_count = s_count_whole = 0;
+    for (uint32_t i = threadIdx.x; i < 5 * kStreamRows; i += 256)
+        (&s_ctr[0][0])[i] = 0;
+    if (low_diversity && span < nspans) {
+        // 1. (the first loads first: phase 0 runs under them)
+        const uint32_t wrow0 = row0 + wave * kStreamWaveRows, wrow_end = min(n, rec_last);
+        const uint8_t *p = codes + (size_t)wrow0 * row_stride + (size_t)span * kStreamSpan + 16u * lane;
+        uint4 v[8];
+#pragma unroll
+        for (uint32_t k = 0; k < 8; ++k) {
+            v[k] = make_uint4(0, 0, 0, 0);
+            if (wrow0 + k < wrow_end)   // (wave-uniform)
+                v[k] = *reinterpret_cast<const uint4 *>(p + (size_t)k * row_stride);
+        }
+        // 0. thread t = sites 4 t .. 4 t + 3 of the span, from the reference's base planes.  (A site whose reference has
+        // two or three bases has one valid code too, nibble << 4; one with none has no valid code: never sampled, and
+        // such a block goes to pack_chunk whole.)
+        bool none = false;
+        {
+            const uint32_t t = threadIdx.x, c = c0 + (t >> 5), w = (t >> 3) & 3u, sh = (t & 7u) * 4u;
+            uint32_t rp[4], word = 0;
+#pragma unroll
+            for (int q = 0; q <= PL_T; ++q)
+                rp[q] = reinterpret_cast<const uint32_t *>(&lists.ref_planes[(size_t)q * nchunks + c])[w] >> sh;
+#pragma unroll
+            for (int b = 0; b < 4; ++b) {
+                const uint32_t nib = ((rp[PL_A] >> b) & 1u) << 3 | ((rp[PL_G] >> b) & 1u) << 2 | ((rp[PL_C] >> b) & 1u) << 1 |
+                                     ((rp[PL_T] >> b) & 1u);
+                none = none || nib == 0u;
+                word |= (nib << 4 | (__builtin_popcount(nib) == 1 ? 8u : 0u)) << (8 * b);
+            }
+            reinterpret_cast<uint32_t *>(s_ref)[t] = word;
+            if (t < 4 * kStreamChunks)
+                s_hot[t] = reinterpret_cast<const uint32_t *>(&lists.hot_planes[c0])[t];
+        }
+        streamed = !__syncthreads_or(none ? 1 : 0);
+        if (streamed) {
+            const uint4 ref = s_ref[lane];
+            if (wave == 0) {
+                const unsigned long long ref_n = __ballot((ref.x & ref.y & ref.z & ref.w) == 0xF0F0F0F0u);
+                if (lane == 0)
+                    s_ref_n = ref_n;
+            }
+            unsigned long long mine = 0;
+#pragma unroll
+            for (uint32_t u = 0; u < kStreamWaveRows; u += 8) {
+                if (u) {
+#pragma unroll
+                    for (uint32_t k = 0; k < 8; ++k) {
+                        v[k] = make_uint4(0, 0, 0, 0);
+                        if (wrow0 + u + k < wrow_end)
+                            v[k] = *reinterpret_cast<const uint4 *>(p + (size_t)(u + k) * row_stride);
+                    }
+                }
+#pragma unroll
+                for (uint32_t k = 0; k < 8; ++k) {
+                    const bool differs = wrow0 + u + k < wrow_end &&
+                                         ((v[k].x ^ ref.x) | (v[k].y ^ ref.y) | (v[k].z ^ ref.z) | (v[k].w ^ ref.w)) != 0u;
+                    const unsigned long long pieces = __ballot(differs);
+                    if (lane == u + k)
+                        mine = pieces;
+                }
+            }
+            if (lane < kStreamWaveRows)
+                s_piece[wave * kStreamWaveRows + lane] = mine;
+        }
+    }
+    __syncthreads();
+    if (streamed) {
+        // 2.
+#pragma unroll
+        for (uint32_t i = threadIdx.x; i < kItems; i += 256) {
+            const uint32_t j = i / kStreamRows, r = i % kStreamRows;
+            const bool queued = ((s_piece[r] >> (8u * j)) & 0xFFull) != 0;
+            s_slot[i] = make_uint4(0, 0, 0, 0);   // nothing in the chunk (or a padding record): pack_chunk's slot for it
+            const unsigned long long q = __ballot(queued);
+            uint32_t at = 0;
+            if (lane == 0 && q)
+                at = atomicAdd(&s_count, (uint32_t)__builtin_popcountll(q));
+            at = (uint32_t)__shfl((int)at, 0);
+            if (queued)
+                s_list[at + (uint32_t)__builtin_popcountll(q & ((1ull << lane) - 1ull))] = (uint16_t)i;
+        }
+        __syncthreads();
+        // 3.
+        const uint32_t count = s_count;
+        for (uint32_t k = threadIdx.x; k < count; k += 256) {
+            const uint32_t i = s_list[k], j = i / kStreamRows, r = i % kStreamRows, s = row0 + r, c = c0 + j;
+            const uint32_t pm = (uint32_t)(s_piece[r] >> (8u * j)) & 0xFFu;
+            // every site N class: the untouched pieces are the reference's, the marked ones are looked at below
+            bool all_n = (((uint32_t)(s_ref_n >> (8u * j)) | pm) & 0xFFu) == 0xFFu;
+            const uint4 *src = reinterpret_cast<const uint4 *>(codes + (size_t)s * row_stride + (size_t)c * kChunkSites);
+            uint32_t cold = 0, hot = 0, bad_at = 0xFFFFFFFFu, slot[4] = {0, 0, 0, 0};
+            for (uint32_t m = pm; m && cold + hot <= kSlotEntries; m &= m - 1) {   // (a chunk past its slot is pack_chunk's)
+                const uint32_t q = (uint32_t)__builtin_ctz(m);
+                const uint4 x4 = src[q], r4 = s_ref[j * 8u + q];
+                const uint32_t hot16 = s_hot[j * 4u + (q >> 1)] >> ((q & 1u) * 16u);
+                const uint32_t x[4] = {x4.x, x4.y, x4.z, x4.w}, rf[4] = {r4.x, r4.y, r4.z, r4.w};
+#pragma unroll
+                for (uint32_t w = 0; w < 4; ++w) {
+                    all_n = all_n && (x[w] & 0xF0F0F0F0u) == 0xF0F0F0F0u;
+                    const uint32_t d = x[w] ^ rf[w];
+                    if (d == 0)
+                        continue;
+#pragma unroll
+                    for (uint32_t b = 0; b < 4; ++b) {
+                        const uint32_t db = (d >> (8u * b)) & 0xFFu;
+                        if (db == 0)
+                            continue;
+                        const uint32_t site = 16u * q + 4u * w + b, byte = (x[w] >> (8u * b)) & 0xFFu;
+                        const uint32_t nib = byte >> 4, low = byte & 15u, bases = (uint32_t)__builtin_popcount(nib);
+                        // (pack_chunk's rule) one base: low nibble 8; two or three: 0; all four: 0 (N), 4 (-) or 2 (?)
+                        const bool ok = bases == 1 ? low == 8u : bases == 4 ? (low == 0u || low == 4u || low == 2u) : bases != 0 && low == 0u;
+                        if (!ok)
+                            bad_at = min(bad_at, site);
+                        if (db & 0xF0u) {
+                            const uint32_t rnib = (rf[w] >> (8u * b + 4u)) & 15u, h = (hot16 >> (4u * w + b)) & 1u;
+                            const uint32_t cls = rnib == 8 ? 0u : rnib == 4 ? 1u : rnib == 2 ? 2u : rnib == 1 ? 3u : 4u;
+                            const uint32_t e = site | cls << 7 | nib << 10 | h << 14;
+                            hot += h;
+                            cold += 1u - h;
+                            const uint32_t at = cold + hot;   // halfword `at` of the slot
+                            if (at <= kSlotEntries)
+                                slot[at >> 1] |= e << (16u * (at & 1u));
+                        }
+                    }
+                }
+            }
+            const uint32_t cnt = cold + hot;
+            if (cnt > kSlotEntries || (all_n && cnt)) {   // (all_n may be of the pieces seen so far only when cnt is past the slot)
+                s_whole[atomicAdd(&s_count_whole, 1u)] = (uint16_t)i;
+                s_slot[i].x = kWhole;   // (no slot's first word: bit 15 of an entry is never set)
+            } else {
+                if (bad_at != 0xFFFFFFFFu)   // (pack_chunk finds its own)
+                    atomicMin(first_bad, (unsigned long long)s * len + c * kChunkSites + bad_at);
+                s_slot[i] = make_uint4(slot[0] | cnt, slot[1], slot[2], slot[3]);
+                if (cnt)
+                    atomicAdd(&s_ctr[0][r], cold);
+                if (hot)
+                    atomicAdd(&s_ctr[1][r], hot);
+            }
+        }
+        __syncthreads();
+        // 4.
+#pragma unroll
+        for (uint32_t i = threadIdx.x; i < kItems; i += 256) {
+            const uint32_t s = row0 + i % kStreamRows;
+            const uint4 slot = s_slot[i];
+            if (s < rec_last && slot.x != kWhole)
+                lists.slots[(size_t)(c0 + i / kStreamRows) * npad + s] = slot;
+        }
+    }
+    // 5.
+    const uint32_t whole = streamed ? s_count_whole : kItems;
+    const PackCounters ctr{s_ctr[0], s_ctr[1], s_ctr[2], s_ctr[3], s_ctr[4]};
+    for (uint32_t k = threadIdx.x; k < whole; k += 256) {
+        const uint32_t i = streamed ? s_whole[k] : k;
+        const uint32_t r = i % kStreamRows, s = row0 + r, c = c0 + i / kStreamRows;
+        if (s < rec_last && c < nchunks)
+            pack_chunk(codes, row_stride, n, len, nchunks, npad, planes, first_bad, aligned16, lists, s, c, ctr, r);
+    }
+    // 6.
+    if (!low_diversity)   // (pack_chunk counts nothing then)
+        return;
+    __syncthreads();
+    uint32_t *const dst[5] = {lists.cnt_cold, lists.cnt_hot, lists.cnt_run, lists.run_cold, lists.run_hot};
+#pragma unroll
+    for (uint32_t i = threadIdx.x; i < 5 * kStreamRows; i += 256) {
+        const uint32_t v = (&s_ctr[0][0])[i];
+        if (v)   // (records >= n never count; a counter the lists do not have is never added to)
+            atomicAdd(&dst[i / kStreamRows][row0 + i % kStreamRows], v);
+    }
 }
 
 // The same from the 4-bit wire format of the stream pipeline (dst_stream_open_wire, DST_WIRE_NIBBLES): a site is the
@@ -851,6 +1092,18 @@ hipError_t launch_pack(const uint8_t *d_codes, size_t row_stride, const DeviceSe
     // bit 0: every row starts on a 16-byte boundary; bit 1: the matrix itself starts on a 4-byte boundary
     const int aligned16 = ((reinterpret_cast<uintptr_t>(d_codes) % 16 == 0) && (row_stride % 16 == 0) ? 1 : 0) |
                           (reinterpret_cast<uintptr_t>(d_codes) % 4 == 0 ? 2 : 0);
+    // what the consensus path uploads goes to the streaming form: the whole 1 KiB spans of the rows, and in the same grid
+    // the chunks behind the last whole span; every other upload to pack_kernel.  (A set the device-side test calls diverse
+    // is packed by that same launch, in pack_kernel's shape.)
+    const uint32_t nspans = lists && lists->ref_planes && lists->defer_planes && (aligned16 & 1) ? (uint32_t)(set.len / kStreamSpan) : 0u;
+    const uint64_t row_blocks = (last - first + kStreamRows - 1) / kStreamRows;
+    const uint32_t grid_spans = (uint32_t)((set.nchunks + kStreamChunks - 1) / kStreamChunks);
+    if (nspans && row_blocks * grid_spans <= 0x7FFFFFFFull) {
+        hipLaunchKernelGGL(pack_stream_kernel, dim3((unsigned)(row_blocks * grid_spans)), dim3(256), 0, stream, d_codes, row_stride,
+                           (uint32_t)set.n, (uint32_t)set.len, (uint32_t)set.nchunks, (uint32_t)set.npad, set.planes, d_first_bad,
+                           aligned16, *lists, first, last, nspans, grid_spans);
+        return hipGetLastError();
+    }
     dim3 grid((unsigned)set.nchunks, (unsigned)((last - first + 255) / 256));
     hipLaunchKernelGGL(pack_kernel, grid, dim3(256), 0, stream, d_codes, row_stride, (uint32_t)set.n,
                        (uint32_t)set.len, (uint32_t)set.nchunks, (uint32_t)set.npad, set.planes,

@@ -7,6 +7,10 @@
 //   r4c16    wave = 4 records x 16 chunks (2 KiB contiguous), block = 16 records x 16 chunks
 //   r1c64    wave = 1 record x 64 chunks (8 KiB contiguous), block = 4 records x 64 chunks
 //   rowstrU  wave = 1 record x 1 KiB per load instruction (a lane = 16 bytes), U such pieces per wave; results by record
+//   cmpstrR  pack_stream_kernel's first phase and nothing else: a block = R records x one 1 KiB span, a wave = R / 4 of
+//            them, one record's KiB per load instruction; a lane compares its 16 bytes with 16 reference bytes it holds in
+//            registers, the wave ballots "differs" and lane k keeps the ballot of the wave's record k, as the kernel does;
+//            the masks leave once per block (whole 1 KiB spans only: 29 of them)
 // Build: make -C tools/ubench read_rate ; run on the GPU box: tools/ubench/read_rate
 #include <hip/hip_runtime.h>
 
@@ -107,6 +111,33 @@ __global__ __launch_bounds__(256) void rowstream_kernel(const uint8_t *in, size_
     }
 }
 
+template <int RW>
+__global__ __launch_bounds__(256) void cmpstream_kernel(const uint8_t *in, size_t stride, uint32_t n, const uint4 *ref, uint32_t *out)
+{
+    const uint32_t lane = threadIdx.x & 63u, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const uint4 r = ref[blockIdx.x * 64u + lane];
+    const uint32_t s0 = (blockIdx.y * 4u + wave) * RW;
+    const uint8_t *p = in + (size_t)s0 * stride + (size_t)blockIdx.x * 1024 + 16u * lane;
+    unsigned long long mine = 0;
+#pragma unroll
+    for (int u = 0; u < RW; u += 8) {
+        uint4 v[8];
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            v[k] = r;
+            if (s0 + u + k < n)
+                v[k] = *reinterpret_cast<const uint4 *>(p + (size_t)(u + k) * stride);
+        }
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const unsigned long long pieces = __ballot(((v[k].x ^ r.x) | (v[k].y ^ r.y) | (v[k].z ^ r.z) | (v[k].w ^ r.w)) != 0u);
+            if (lane == (uint32_t)(u + k))
+                mine = pieces;
+        }
+    }
+    out[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 256u + threadIdx.x] = (uint32_t)mine ^ (uint32_t)(mine >> 32);
+}
+
 int main()
 {
     const uint32_t n = 50000, len = 30000, nchunks = len / 128, npad = 50048;   // 234 whole chunks
@@ -115,6 +146,9 @@ int main()
     CHECK(hipMalloc((void **)&in, (size_t)n * len));
     CHECK(hipMemset(in, 0x88, (size_t)n * len));
     CHECK(hipMalloc((void **)&out, (size_t)(nchunks + 1) * npad * sizeof(uint4)));
+    uint4 *ref = nullptr;   // the reference bytes of a row's whole spans (the matrix is 0x88 throughout: nothing differs)
+    CHECK(hipMalloc((void **)&ref, (size_t)(len / 1024) * 1024));
+    CHECK(hipMemset(ref, 0x88, (size_t)(len / 1024) * 1024));
     hipEvent_t e0, e1;
     CHECK(hipEventCreate(&e0));
     CHECK(hipEventCreate(&e1));
@@ -164,6 +198,19 @@ int main()
     CHECK(hipEventElapsedTime(&ms, e0, e1));                                                                                    \
     if (rep)                                                                                                                    \
         report(NAME, ms / 5);
+#define RUNC(NAME, RW)                                                                                                          \
+    CHECK(hipEventRecord(e0));                                                                                                  \
+    for (int k = 0; k < 5; ++k)                                                                                                 \
+        hipLaunchKernelGGL((cmpstream_kernel<RW>), dim3(len / 1024, (n + 4 * RW - 1) / (4 * RW)), dim3(256), 0, 0, in, (size_t)len, \
+                           n, ref, reinterpret_cast<uint32_t *>(out));                                                          \
+    CHECK(hipEventRecord(e1));                                                                                                  \
+    CHECK(hipEventSynchronize(e1));                                                                                             \
+    CHECK(hipEventElapsedTime(&ms, e0, e1));                                                                                    \
+    if (rep)                                                                                                                    \
+        std::printf("%-9s %8.3f ms  %6.2f TB/s read (%u of %u bytes of a row; masks only)\n", NAME, ms / 5,                     \
+                    (double)n * (len / 1024) * 1024 / (ms / 5) / 1e9, len / 1024 * 1024, len);
+        RUNC("cmpstr16", 16)
+        RUNC("cmpstr32", 32)
         RUNK("lanerow2", 2)
         RUNK("lanerow4", 4)
         RUNK("lanerow8", 8)
