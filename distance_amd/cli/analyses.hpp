@@ -1,0 +1,498 @@
+// The analyses of the loaded sets: one write_* per output mode that is not the long form, and the --groups label file.
+#pragma once
+#include <cmath>
+#include <unordered_map>
+#include <unordered_set>
+
+#include "load.hpp"
+#include "output.hpp"
+
+namespace {
+
+// what every analysis is given: one GPU with the loaded sets uploaded (slots 0 and 1), the measure, the lines' way out
+struct Run {
+    const Ctx &gpu;
+    const std::vector<Alignment> &loaded;
+    Tn93Counts tn93;      // of rows() / cols()
+    int measure;
+    uint64_t max_pairs;   // Args::analysis_slab()
+    Writer &wr;
+    bool square() const { return loaded.size() == 1; }
+    const Alignment &rows() const { return loaded[0]; }
+    const Alignment &cols() const { return loaded.back(); }
+    size_t tally_width() const { return (size_t)dst_tally_width(measure); }
+    void header(const char *line) const { wr.write(line, std::strlen(line)); }
+};
+
+// --nearest: per record of the first file (in input order) its k_used nearest records — of the same file (one input,
+// the square) or of the second — from dst_nearest, each line "own id, neighbour id, value" for the canonical pair
+void write_nearest(const Run &run, uint32_t k)
+{
+    const bool square = run.square();
+    const Alignment &rows = run.rows(), &cols = run.cols();
+    const size_t W = run.tally_width();
+    const size_t cap = rows.n * std::min<size_t>(k, square ? (rows.n ? rows.n - 1 : 0) : cols.n);
+    std::vector<uint32_t> index(std::max<size_t>(cap, 1)), tallies(std::max<size_t>(cap * W, 1));
+    uint32_t ku = 0;
+    run.gpu.check(dst_nearest(run.gpu.h, run.measure, square ? 1 : 0, 0, 1, k, index.data(), tallies.data(), nullptr, cap, &ku),
+                  "nearest");
+    LineWriter out(run.wr);
+    for (size_t i = 0; i < rows.n; ++i)
+        for (size_t e = 0; e < ku; ++e) {
+            const size_t at = i * ku + e, j = index[at];
+            const size_t q = square ? std::min(i, j) : i, t = square ? std::max(i, j) : j;
+            out.pair_line(rows.ids[i], cols.ids[j], run.measure, &tallies[at * W], run.tn93.row(q), run.tn93.col(t));
+            out.end_line();
+        }
+    out.finish();
+}
+
+// --clusters: one line per record in input order, "id, cluster", from dst_clusters' labels (the smallest record of the
+// cluster); clusters are numbered from 1 in order of their first record, which is the record its label names.
+void write_clusters(const Run &run, double threshold)
+{
+    const Alignment &set = run.rows();
+    std::vector<uint32_t> label(std::max<size_t>(set.n, 1)), number(std::max<size_t>(set.n, 1), 0);
+    uint64_t n_clusters = 0, links = 0;
+    run.gpu.check(dst_clusters(run.gpu.h, run.measure, threshold, 0, label.data(), set.n, &n_clusters, &links), "clusters");
+    run.header("sequence\tcluster\n");
+    LineWriter out(run.wr);
+    uint32_t next = 0;
+    for (size_t i = 0; i < set.n; ++i) {
+        if (label[i] == i)
+            number[i] = ++next;
+        out.put(set.ids[i]);
+        out.put('\t');
+        out.number(number[label[i]]);
+        out.end_line();
+    }
+    out.finish();
+}
+
+// --sites: the fourth field of a --max-distance / --mst line.  The pairs of dst_pair_sites' entries, each "X<pos>Y": pos
+// 1-based, X / Y the IUPAC letter of the first / second record's nibble; "." for a pair without listed sites.
+// diff_tally: how many entries a pair has, from its DST_OUT_TALLY words (dst_pair_sites' first consequence), which sizes
+// the buffers without a counting call.
+uint64_t diff_tally(int measure, const uint32_t *t)
+{
+    return measure == DST_K80 ? (uint64_t)t[1] + t[2] : measure == DST_TN93 ? t[1] : t[0];
+}
+
+void put_sites(LineWriter &out, const uint32_t *sites, const uint8_t *bases, uint64_t begin, uint64_t end)
+{
+    static const char letter[] = "?TCYGKSBAWMHRDVN";   // by nibble: A 8, G 4, C 2, T 1
+    if (begin == end)
+        out.put('.');
+    for (uint64_t k = begin; k < end; ++k) {
+        if (k != begin)
+            out.put(',');
+        out.put(letter[bases[k] >> 4]);
+        out.number((uint64_t)sites[k] + 1);
+        out.put(letter[bases[k] & 15]);
+    }
+}
+
+// The lines of pairs (row[e], col[e]), e < n: "id_row, id_col, value" from the pair's tallies, and with --sites their
+// sites: dst_pair_sites in batches of DST_PAIR_SITES_BATCH pairs, each batch's buffers sized from the pairs' tallies.
+void write_pairs(const Run &run, LineWriter &out, const uint32_t *row, const uint32_t *col, const uint32_t *tallies, uint64_t n,
+                 bool with_sites)
+{
+    const size_t W = run.tally_width();
+    std::vector<uint64_t> offsets;
+    std::vector<uint32_t> sites;
+    std::vector<uint8_t> bases;
+    for (uint64_t e0 = 0; e0 < n; e0 += DST_PAIR_SITES_BATCH) {
+        const uint64_t m = std::min<uint64_t>(DST_PAIR_SITES_BATCH, n - e0);
+        if (with_sites) {
+            uint64_t cap = 0, total = 0;
+            for (uint64_t e = e0; e < e0 + m; ++e)
+                cap += diff_tally(run.measure, tallies + e * W);
+            offsets.assign(m + 1, 0);
+            sites.resize(std::max<uint64_t>(cap, 1));
+            bases.resize(std::max<uint64_t>(cap, 1));
+            run.gpu.check(dst_pair_sites(run.gpu.h, run.measure, run.square() ? 1 : 0, 0, 1, row + e0, col + e0, m, offsets.data(),
+                                         sites.data(), bases.data(), cap, &total),
+                          "pair sites");
+        }
+        for (uint64_t k = 0; k < m; ++k) {
+            const size_t i = row[e0 + k], j = col[e0 + k];
+            out.pair_line(run.rows().ids[i], run.cols().ids[j], run.measure, tallies + (e0 + k) * W, run.tn93.row(i),
+                          run.tn93.col(j));
+            if (with_sites) {
+                out.put('\t');
+                put_sites(out, sites.data(), bases.data(), offsets[k], offsets[k + 1]);
+            }
+            out.end_line();
+        }
+    }
+}
+
+// --mst: the edges of dst_mst in its order, each as the line the full run prints for that pair
+void write_mst(const Run &run, bool with_sites)
+{
+    const size_t cap = std::max<size_t>(run.rows().n, 1);
+    std::vector<uint32_t> ei(cap), ej(cap), tallies(cap * run.tally_width());
+    uint64_t n_edges = 0;
+    run.gpu.check(dst_mst(run.gpu.h, run.measure, run.max_pairs, ei.data(), ej.data(), nullptr, tallies.data(), cap, &n_edges,
+                          nullptr),
+                  "mst");
+    LineWriter out(run.wr);
+    write_pairs(run, out, ei.data(), ej.data(), tallies.data(), n_edges, with_sites);
+    out.finish();
+}
+
+// --max-distance: the lines of the full run whose pair is a link of dst_links at T, in its (the full run's) order.  The
+// sink formats one chunk of links at a time.  With --sites it only keeps them (row, col, tallies: 12 + 4 W bytes each):
+// the context is not re-entrant, so the lines are written, with their sites, after dst_links has returned.
+struct LinksSink {
+    const Run &run;
+    LineWriter out;
+    bool keep;
+    std::vector<uint32_t> row, col, tallies;
+};
+
+int links_sink(void *user, uint64_t, uint64_t n_links, const uint32_t *row, const uint32_t *col, const void *,
+               const uint32_t *tallies)
+{
+    LinksSink &s = *static_cast<LinksSink *>(user);
+    if (s.keep) {
+        s.row.insert(s.row.end(), row, row + n_links);
+        s.col.insert(s.col.end(), col, col + n_links);
+        s.tallies.insert(s.tallies.end(), tallies, tallies + n_links * s.run.tally_width());
+    } else {
+        write_pairs(s.run, s.out, row, col, tallies, n_links, false);
+    }
+    return 0;
+}
+
+void write_links(const Run &run, double threshold, bool with_sites)
+{
+    LinksSink s{run, LineWriter(run.wr), with_sites, {}, {}, {}};
+    run.gpu.check(dst_links(run.gpu.h, run.measure, run.square() ? 1 : 0, 0, 1, threshold, run.max_pairs, DST_LINKS_TALLIES,
+                            links_sink, &s, nullptr),
+                  "links");
+    if (with_sites)
+        write_pairs(run, s.out, s.row.data(), s.col.data(), s.tallies.data(), s.row.size(), true);
+    s.out.finish();
+}
+
+// --summary: one line per record of the first input in input order, "id, within, compared, mean" from dst_summary: the
+// records within T, the partners with a summable distance, and sum / compared printed as an f64 distance (NaN: none)
+void write_summary(const Run &run, double threshold)
+{
+    const Alignment &set = run.rows();
+    const size_t cap = std::max<size_t>(set.n, 1);
+    std::vector<uint32_t> within(cap), summable(cap);
+    std::vector<double> sum(cap);
+    run.gpu.check(dst_summary(run.gpu.h, run.measure, run.square() ? 1 : 0, 0, 1, threshold, run.max_pairs, 0, 0.0, nullptr,
+                              within.data(), summable.data(), sum.data(), set.n, nullptr),
+                  "summary");
+    run.header("sequence\twithin\tcompared\tmean\n");
+    LineWriter out(run.wr);
+    for (size_t i = 0; i < set.n; ++i) {
+        out.put(set.ids[i]);
+        out.put('\t');
+        out.number(within[i]);
+        out.put('\t');
+        out.number(summable[i]);
+        out.put('\t');
+        out.distance(DST_RAW, summable[i] ? sum[i] / (double)summable[i] : std::nan(""), 0);
+        out.end_line();
+    }
+    out.finish();
+}
+
+// --groups: the label file, read before any input is opened.  One "id<TAB>group" per line, empty lines skipped, no header.
+struct GroupFile {
+    std::string path;
+    std::unordered_map<std::string, std::pair<std::string, size_t>> of;   // id -> (group, the line that set it)
+};
+
+GroupFile read_group_file(const std::string &path)
+{
+    GroupFile gf;
+    gf.path = path;
+    FILE *fh = open_input(path);
+    std::string text;
+    char buf[1 << 16];
+    for (size_t got; (got = std::fread(buf, 1, sizeof buf, fh)) > 0;)
+        text.append(buf, got);
+    std::fclose(fh);
+    size_t line_no = 0;
+    for (size_t at = 0; at < text.size();) {
+        size_t end = text.find('\n', at);
+        if (end == std::string::npos)
+            end = text.size();
+        std::string line = text.substr(at, end - at);
+        at = end + 1;
+        ++line_no;
+        if (!line.empty() && line.back() == '\r')
+            line.pop_back();
+        if (line.empty())
+            continue;
+        const std::string where = "--groups: line " + std::to_string(line_no) + " of '" + path + "' ";
+        const size_t tab = line.find('\t');
+        if (tab == std::string::npos)
+            die_message(where + "has no tab: expected 'id<TAB>group'");
+        const std::string id = line.substr(0, tab), group = line.substr(tab + 1);
+        if (group.empty())
+            die_message(where + "has an empty group");
+        if (group.find('\t') != std::string::npos)
+            die_message(where + "has more than two fields");
+        const auto ins = gf.of.emplace(id, std::make_pair(group, line_no));
+        if (!ins.second && ins.first->second.first != group)
+            die_message(where + "gives '" + id + "' the group '" + group + "', line " + std::to_string(ins.first->second.second) +
+                        " gave it '" + ins.first->second.first + "'");
+    }
+    return gf;
+}
+
+// the labels of one input: groups numbered in order of their first record, as --clusters numbers its clusters
+struct GroupLabels {
+    std::vector<uint32_t> label;       // per record, DST_GROUP_NONE: not in the file
+    std::vector<std::string> names;    // per group
+    size_t assigned = 0;
+};
+
+GroupLabels label_records(const GroupFile &gf, const Alignment &set, const char *which, std::unordered_set<std::string> &seen)
+{
+    GroupLabels gl;
+    gl.label.assign(set.n, DST_GROUP_NONE);
+    std::unordered_map<std::string, uint32_t> number;
+    for (size_t r = 0; r < set.n; ++r) {
+        const auto it = gf.of.find(set.ids[r]);
+        if (it == gf.of.end())
+            continue;
+        seen.insert(set.ids[r]);
+        const auto ins = number.emplace(it->second.first, (uint32_t)gl.names.size());
+        if (ins.second) {
+            if (gl.names.size() == DST_GROUPS_MAX)
+                die_message("--groups: line " + std::to_string(it->second.second) + " of '" + gf.path + "' starts group " +
+                            std::to_string(DST_GROUPS_MAX + 1) + " of the " + which + " input: more than " +
+                            std::to_string(DST_GROUPS_MAX) + " groups");
+            gl.names.push_back(it->second.first);
+        }
+        gl.label[r] = ins.first->second;
+        ++gl.assigned;
+    }
+    if (gl.assigned == 0)
+        die_message("--groups: no record of the " + std::string(which) + " input has a group in '" + gf.path + "'");
+    return gl;
+}
+
+// the records' labels, and what can be wrong with them: every input against the one label file
+std::vector<GroupLabels> label_inputs(const GroupFile &gf, const std::vector<Alignment> &loaded)
+{
+    std::vector<GroupLabels> labels;
+    std::unordered_set<std::string> seen;
+    for (size_t k = 0; k < loaded.size(); ++k)
+        labels.push_back(label_records(gf, loaded[k], k == 0 ? "first" : "second", seen));
+    if (seen.size() < gf.of.size())
+        std::fprintf(stderr, "warning: --groups: %zu ids of '%s' are not in the input and were skipped\n",
+                     gf.of.size() - seen.size(), gf.path.c_str());
+    return labels;
+}
+
+// --groups: one line per cell (one input: a <= b; two: every cell), or with --per-record one line per record of the first
+// input and group of the other side, from dst_group_summary.  mean = sum / compared as --summary prints its mean.
+void write_groups(const Run &run, const std::vector<GroupLabels> &labels, bool has_within, double threshold, bool per_record)
+{
+    const bool square = run.square();
+    const GroupLabels &rl = labels[0], &cl = labels.back();
+    const uint32_t Gr = (uint32_t)rl.names.size(), Gc = (uint32_t)cl.names.size();
+    const size_t n_rows = run.rows().n;
+    std::vector<dst_group_cell> cells(per_record ? 0 : (size_t)Gr * Gc);
+    std::vector<uint32_t> within(per_record ? n_rows * Gc : 0), summable(per_record ? n_rows * Gc : 0);
+    std::vector<double> sum(per_record ? n_rows * Gc : 0);
+    run.gpu.check(dst_group_summary(run.gpu.h, run.measure, square ? 1 : 0, 0, 1, rl.label.data(), Gr, cl.label.data(), Gc,
+                                    has_within ? threshold : HUGE_VAL, run.max_pairs, per_record ? nullptr : cells.data(),
+                                    cells.size(), per_record ? within.data() : nullptr, per_record ? summable.data() : nullptr,
+                                    per_record ? sum.data() : nullptr, sum.size()),
+                  "group summary");
+    const bool int_payload = run.measure == DST_N || run.measure == DST_N_HIGH;
+    LineWriter out(run.wr);
+    out.put(per_record ? "sequence\tgroup\tcompared" : "group1\tgroup2\tpairs\tcompared");
+    if (has_within)
+        out.put("\twithin");
+    out.put(per_record ? "\tmean" : "\tmean\tmin\tmax");
+    out.end_line();
+    auto tab_number = [&](uint64_t v) {
+        out.put('\t');
+        out.number(v);
+    };
+    auto tab_distance = [&](int measure, bool known, double v, int64_t iv) {
+        out.put('\t');
+        if (known)
+            out.distance(measure, v, iv);
+        else
+            out.put("NaN");
+    };
+    if (per_record) {
+        for (size_t x = 0; x < n_rows; ++x)
+            for (uint32_t g = 0; g < Gc; ++g) {
+                const size_t e = x * Gc + g;
+                out.put(run.rows().ids[x]);
+                out.put('\t');
+                out.put(cl.names[g]);
+                tab_number(summable[e]);
+                if (has_within)
+                    tab_number(within[e]);
+                tab_distance(DST_RAW, summable[e] != 0, summable[e] ? sum[e] / (double)summable[e] : 0.0, 0);
+                out.end_line();
+            }
+    } else {
+        for (uint32_t a = 0; a < Gr; ++a)
+            for (uint32_t b = square ? a : 0; b < Gc; ++b) {
+                const dst_group_cell &c = cells[(size_t)a * Gc + b];
+                out.put(rl.names[a]);
+                out.put('\t');
+                out.put(cl.names[b]);
+                tab_number(c.pairs);
+                tab_number(c.summable_pairs);
+                if (has_within)
+                    tab_number(c.links);
+                tab_distance(DST_RAW, c.summable_pairs != 0, c.summable_pairs ? c.sum / (double)c.summable_pairs : 0.0, 0);
+                const bool known = c.pairs > c.nan_pairs;   // a pair whose payload is not NaN
+                for (const uint64_t bits : {c.min_bits, c.max_bits}) {
+                    double v = 0;
+                    std::memcpy(&v, &bits, 8);
+                    tab_distance(run.measure, known, int_payload ? 0.0 : v, int_payload ? (int64_t)bits : 0);
+                }
+                out.end_line();
+            }
+    }
+    out.finish();
+}
+
+// --histogram: one line per bin, "lower edge, pairs" (the edge b W as the measure's distances are printed; the last bin is
+// open-ended), then "NaN, pairs without a distance"
+void write_histogram(const Run &run, double width, uint32_t bins)
+{
+    std::vector<uint64_t> hist(bins);
+    dst_summary_totals totals;
+    run.gpu.check(dst_summary(run.gpu.h, run.measure, run.square() ? 1 : 0, 0, 1, 0.0, run.max_pairs, bins, width, hist.data(),
+                              nullptr, nullptr, nullptr, 0, &totals),
+                  "histogram");
+    run.header("distance\tpairs\n");
+    LineWriter out(run.wr);
+    for (uint32_t b = 0; b < bins; ++b) {
+        out.distance(run.measure, (double)b * width, (int64_t)b * (int64_t)width);
+        out.put('\t');
+        out.number(hist[b]);
+        out.end_line();
+    }
+    out.put("NaN\t");
+    out.number(totals.nan_pairs);
+    out.end_line();
+    out.finish();
+}
+
+// a DST_ERR_STATE message "... the distance of records I and J is not finite" of the NJ calls, with the pair named by
+// its ids; false when the message names no pair of the set
+bool non_finite_pair(const Ctx &gpu, const Alignment &set, const char *prefix, const char *suffix)
+{
+    const std::string msg = dst_last_error(gpu.h);
+    unsigned long long i = 0, j = 0;
+    const size_t at = msg.find("records ");
+    if (at == std::string::npos || std::sscanf(msg.c_str() + at, "records %llu and %llu", &i, &j) != 2 || i >= set.n ||
+        j >= set.n)
+        return false;
+    std::fprintf(stderr, "error: %sthe distance of '%s' and '%s' is not finite%s\n", prefix, set.ids[i].c_str(),
+                 set.ids[j].c_str(), suffix);
+    return true;
+}
+
+// every id of a set in one arena with its offsets, as the library's id and Newick calls take them
+struct IdArena {
+    std::string chars;
+    std::vector<uint64_t> offsets;
+    explicit IdArena(const Alignment &set) : offsets(set.n + 1, 0)
+    {
+        for (size_t r = 0; r < set.n; ++r) {
+            chars += set.ids[r];
+            offsets[r + 1] = chars.size();
+        }
+    }
+};
+
+// one Newick line: `newick(buffer, capacity, &length)` is asked for the length first, then for the text
+template <class Newick>
+void write_newick(Writer &wr, Newick newick)
+{
+    size_t len = 0;
+    newick(nullptr, 0, &len);
+    std::string out(len, '\0');
+    if (newick(out.data(), out.size(), &len) != DST_OK) {
+        std::fprintf(stderr, "error: the Newick text of the tree could not be written\n");
+        leave(1);
+    }
+    wr.write(out.data(), len);
+}
+
+// --tree nj: the neighbour-joining tree of one set as one Newick line (dst_nj on the GPU, dst_newick on the host);
+// with --bootstrap B its internal nodes carry their support in B replicates (dst_nj_bootstrap, dst_newick_support),
+// and nothing is written unless every replicate succeeded
+void write_tree(const Run &run, uint32_t bootstrap, uint64_t seed)
+{
+    const Ctx &gpu = run.gpu;
+    const Alignment &set = run.rows();
+    if (set.n < 3) {
+        std::fprintf(stderr, "error: a neighbour-joining tree needs at least 3 records, the input has %zu\n", (size_t)set.n);
+        leave(1);
+    }
+    std::vector<uint32_t> parent(2 * set.n - 2);
+    std::vector<double> length(2 * set.n - 2);
+    int rc = dst_nj(gpu.h, run.measure, run.max_pairs, parent.data(), length.data(), parent.size());
+    if (rc == DST_ERR_STATE && non_finite_pair(gpu, set, "", ": no neighbour-joining tree"))
+        leave(1);
+    gpu.check(rc, "neighbour joining");
+    std::vector<uint32_t> support;
+    if (bootstrap) {
+        support.resize(parent.size());
+        rc = dst_nj_bootstrap(gpu.h, run.measure, set.codes.data(), set.n, set.width, set.width, bootstrap, seed, run.max_pairs,
+                              parent.data(), support.data(), nullptr, support.size());
+        if (rc == DST_ERR_STATE) {
+            // "bootstrap replicate R: the distance of records I and J is not finite"
+            unsigned long long r = 0;
+            const std::string msg = dst_last_error(gpu.h);
+            if (std::sscanf(msg.c_str(), "bootstrap replicate %llu", &r) == 1) {
+                const std::string prefix = "bootstrap replicate " + std::to_string(r) + ": ";
+                if (non_finite_pair(gpu, set, prefix.c_str(), ""))
+                    leave(1);
+            }
+        }
+        if (rc != DST_OK) {
+            std::fprintf(stderr, "error: bootstrap: %s\n", dst_last_error(gpu.h));
+            leave(1);
+        }
+    }
+    const IdArena ids(set);
+    const uint32_t *sup = bootstrap ? support.data() : nullptr;
+    write_newick(run.wr, [&](char *buf, size_t cap, size_t *len) {
+        return dst_newick_support(set.n, parent.data(), length.data(), ids.chars.data(), ids.offsets.data(), sup, buf, cap, len);
+    });
+}
+
+// --dendrogram: the UPGMA / WPGMA / complete-linkage tree of one set as one Newick line with a binary root
+// (dst_dendrogram on the GPU, dst_newick_rooted on the host)
+void write_dendrogram(const Run &run, int linkage)
+{
+    const Alignment &set = run.rows();
+    if (set.n < 2) {
+        std::fprintf(stderr, "error: a dendrogram needs at least 2 records, the input has %zu\n", (size_t)set.n);
+        leave(1);
+    }
+    std::vector<uint32_t> parent(2 * set.n - 1);
+    std::vector<double> length(2 * set.n - 1);
+    const int rc = dst_dendrogram(run.gpu.h, run.measure, linkage, run.max_pairs, parent.data(), length.data(), nullptr,
+                                  parent.size(), nullptr);
+    if (rc == DST_ERR_STATE && non_finite_pair(run.gpu, set, "", ": no dendrogram"))
+        leave(1);
+    run.gpu.check(rc, "dendrogram");
+    const IdArena ids(set);
+    write_newick(run.wr, [&](char *buf, size_t cap, size_t *len) {
+        return dst_newick_rooted(set.n, parent.data(), length.data(), ids.chars.data(), ids.offsets.data(), buf, cap, len);
+    });
+}
+
+}  // namespace

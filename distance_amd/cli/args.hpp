@@ -1,0 +1,405 @@
+// The command line: help text, the flags, the scan, and the one table of what may not be combined.
+#pragma once
+#include <cctype>
+#include <cmath>
+#include <initializer_list>
+#include <string>
+#include <utility>
+#include <vector>
+
+#include "base.hpp"
+
+namespace {
+
+void print_help()
+{
+    std::puts(
+        "Calculate genetic distances within/between fasta-format alignments of DNA sequences\n\n"
+        "Usage: All sequences across all input files must be the same length.\n\n"
+        "       distance alignment.fasta\n"
+        "       cat alignment.fasta | distance\n"
+        "       distance alignment.fasta -o distances.tsv\n"
+        "       distance -t 8 -m jc69 alignment.fasta -o jc69.tsv\n"
+        "       distance alignment1.fasta alignment2.fasta > distances2.tsv\n"
+        "       distance -i smallAlignment.fasta -s bigAlignment.fasta -o distances3.tsv\n"
+        "       cat bigAlignment.fasta | distance smallAlignment.fasta -s - > distances3.tsv\n"
+        "       \n\n"
+        "Options:\n"
+        "  -i, --input [<input>...]     One or two input alignment files in fasta format. Loaded into memory. "
+        "This flag can be omitted and the files passed as positional arguments\n"
+        "  -s, --stream <stream>        One input alignment file in fasta format. Streamed from disk (or stdin "
+        "using \"-s -\"). Requires exactly one file also be loaded\n"
+        "  -m, --measure <measure>      Which distance measure to use [default: raw] [possible values: n, n_high, "
+        "raw, jc69, k80, tn93]\n"
+        "  -o, --output <output>        Output file in tab-separated-value format. Omit this option to print to "
+        "stdout\n"
+        "  -t, --threads <threads>      How many threads to spin up for pairwise comparisons. Omitting this option "
+        "spins up the number of available CPUs\n"
+        "  -b, --batchsize <batchsize>  Try setting this >(>) 1 to tune the workload per thread [default: 1]\n"
+        "  -l, --licenses               Print licence information and exit\n"
+        "      --gpus <n>               MI355X GPUs to use (default 1)\n"
+        "      --devices <list>         Explicit device ordinals, e.g. 0,1,2,3 (overrides --gpus)\n"
+        "      --nearest <k>            Print only the k (1-256) nearest records of every record: of the same file with one "
+        "input, of the second file with two. One GPU, no --stream\n"
+        "      --closest <k>            Stream mode only: print only the k (1-256) closest records instead of every pair, "
+        "each as the line the full run prints for that pair. Requires --stream, one loaded file, one GPU, no other output mode\n"
+        "      --closest-for <side>     Whose closest records --closest prints: loaded (for every loaded record its k closest "
+        "streamed records, written when the stream ends) or streamed (for every streamed record its k closest loaded "
+        "records, in stream order) [default: loaded]\n"
+        "      --within <T>             Stream mode only: print only the pairs within distance T (a number >= 0, or inf): the "
+        "lines of the full run whose distance is at most T, in the same order and with the same text. Requires --stream, one "
+        "loaded file, one GPU, no other output mode\n"
+        "      --clusters <T>           Print the single-linkage cluster of every record instead of distances: records "
+        "within distance T (a number >= 0) of each other share a cluster, numbered from 1 in order of first record. One "
+        "input, one GPU, no --stream or --nearest\n"
+        "      --max-distance <T>       Print only the pairs within distance T (a number >= 0, or inf): the lines of the full "
+        "run whose distance is at most T, in the same order and with the same text. One or two inputs, one GPU, no --stream "
+        "and no other output mode\n"
+        "      --summary <T>            Print one line per record instead of one per pair: how many records lie within distance "
+        "T (a number >= 0, or inf) of it, how many it was compared with (pairs with a distance) and its mean distance to "
+        "those. With two inputs: the records of the first against the second. One GPU, no --stream and no other output mode\n"
+        "      --histogram <W>          Print the histogram of the pairwise distances instead of the pairs: one line per bin "
+        "of width W (a number > 0; an integer with -m n / n_high), its lower edge and its pairs, the last bin open-ended, then "
+        "the pairs without a distance (NaN). One GPU, no --stream and no other output mode\n"
+        "      --bins <B>               Bins of the histogram, 1 to 4096 [default: 256]. Requires --histogram\n"
+        "      --groups <FILE>          Print one line per pair of groups instead of one per pair of records: FILE has one "
+        "'id<TAB>group' line per labelled record (no header; at most 1024 groups per input, numbered in order of their first "
+        "record); the line gives the pairs between the two groups, how many were compared (pairs with a distance), their "
+        "mean, smallest and largest distance. With two inputs: the groups of the first against those of the second. For "
+        "jc69 / k80 / tn93 min and max are the device's values and can differ from the long output's text in the 12th "
+        "decimal on a rounding boundary. One GPU, no --stream and no other output mode\n"
+        "      --groups-within <T>      With --groups: a 'within' column, the compared pairs within distance T (a number >= 0, "
+        "or inf)\n"
+        "      --per-record             With --groups: one line per record of the first input and group of the other side "
+        "instead (the record's compared partners in the group and its mean distance to them), labelled or not\n"
+        "      --matrix <format>        Print a distance matrix instead of one line per pair: tsv (one or two inputs, rows "
+        "from the first, columns from the last) or phylip (relaxed PHYLIP, one input). Not in stream, nearest or "
+        "clusters mode\n"
+        "      --tree <method>          Print the tree of the records as one Newick line instead of distances: method nj "
+        "(neighbour joining). One input, one GPU, no --stream and no other output mode\n"
+        "      --bootstrap <B>          Label each internal edge of the neighbour-joining tree with the number of B "
+        "(1-10000) bootstrap replicates (alignments of columns drawn with replacement) whose tree holds its split\n"
+        "      --seed <S>               Seed of the bootstrap's column draws, 0 to 2^64-1 [default: 1]\n"
+        "      --mst                    Print only the edges of the minimum spanning tree of the records (pairs without a "
+        "distance, NaN, are no edges: a forest then), in ascending order of (distance, first record, second record), each "
+        "as the line the full run prints for that pair. One input, one GPU, no --stream and no other output mode\n"
+        "      --sites                  With one of the two pair-list outputs (the pairs within a distance, the minimum spanning "
+        "tree): a fourth field per line, the sites that separate the two "
+        "records as a comma-separated list of X<pos>Y (pos 1-based, X the first record's IUPAC letter, Y the second's; '.' "
+        "when there are none): the sites the measure counts as differences\n"
+        "      --dendrogram <linkage>   Print the rooted hierarchical-clustering tree of the records as one Newick line instead "
+        "of distances: linkage average (UPGMA), weighted (WPGMA) or complete. One input, one GPU, no --stream and no other "
+        "output mode\n"
+        "  -h, --help                   Print help\n"
+        "  -V, --version                Print version");
+}
+
+const char *kLicences =
+    "\nCopyright 2022, Ben Jackson (distance, GNU LIBRARY GENERAL PUBLIC LICENSE, Version 2): this program is an\n"
+    "independent MI355X re-implementation of its command-line surface and output format.\n"
+    "FASTA tokenisation follows Rust-Bio (MIT licence, Copyright (c) 2016 Johannes Koester, the Rust-Bio team,\n"
+    "Google Inc.).  Nucleotide coding scheme: Emmanuel Paradis, as used in ape.\n";
+
+// ---------------------------------------------------------------- arguments -------------------
+// Every flag the checks below speak about, by the name the messages print.
+enum Flag {
+    F_STREAM, F_MEASURE, F_OUTPUT, F_THREADS, F_BATCHSIZE, F_GPUS, F_DEVICES, F_SLAB_PAIRS, F_NEAREST, F_CLOSEST, F_CLOSEST_FOR,
+    F_WITHIN, F_CLUSTERS, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS, F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX,
+    F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM, F_SELFTEST, F_COUNT
+};
+struct FlagDef {
+    const char *shown;   // "--name <value>": its first word is the flag itself
+    const char *letter;  // "-s", or null
+    bool once;           // a second one is refused (the others keep their last value)
+};
+const FlagDef kFlags[F_COUNT] = {
+    {"--stream <stream>", "-s", false}, {"--measure <measure>", "-m", false}, {"--output <output>", "-o", false},
+    {"--threads <threads>", "-t", false}, {"--batchsize <batchsize>", "-b", false}, {"--gpus <n>", nullptr, false},
+    {"--devices <list>", nullptr, false}, {"--slab-pairs <p>", nullptr, false}, {"--nearest <k>", nullptr, false},
+    {"--closest <k>", nullptr, false}, {"--closest-for <side>", nullptr, false}, {"--within <T>", nullptr, true},
+    {"--clusters <T>", nullptr, false}, {"--max-distance <T>", nullptr, true}, {"--summary <T>", nullptr, true},
+    {"--groups <FILE>", nullptr, true}, {"--groups-within <T>", nullptr, true}, {"--per-record", nullptr, false},
+    {"--histogram <W>", nullptr, true}, {"--bins <B>", nullptr, false}, {"--matrix <format>", nullptr, false},
+    {"--tree <method>", nullptr, false}, {"--bootstrap <B>", nullptr, false}, {"--seed <S>", nullptr, false},
+    {"--mst", nullptr, false}, {"--sites", nullptr, false}, {"--dendrogram <linkage>", nullptr, false},
+    {"--host-selftest <what>", nullptr, false},
+};
+
+// what the run prints, decided once by parse_args
+enum class Mode { Pairs, Stream, Closest, Within, Nearest, Clusters, MaxDistance, Summary, Histogram, Groups, Matrix, Tree, Mst,
+                  Dendrogram };
+
+struct Args {
+    bool has[F_COUNT] = {};               // the flag was given
+    Mode mode = Mode::Pairs;
+    std::vector<std::string> flag_inputs, pos_inputs;
+    std::string stream, measure = "raw", output;
+    bool licenses = false;
+    size_t threads = 0, batchsize = 1;
+    int gpus = 1;
+    std::vector<int> devices;  // explicit device ordinals (--devices 0,1,..); empty: 0..gpus-1
+    size_t slab_pairs = (size_t)1 << 22;  // result slab: 4 Mi pairs pipelines GPU, formatters and writer well
+    size_t nearest = 0;                   // --nearest k
+    size_t closest = 0;                   // --closest k (stream mode)
+    int closest_side = DST_CLOSEST_FOR_LOADED;   // --closest-for loaded|streamed
+    double within = 0;                    // --within T (stream mode)
+    double clusters = 0;                  // --clusters T
+    double max_distance = 0;              // --max-distance T
+    double summary = 0;                   // --summary T
+    double histogram = 0;                 // --histogram W
+    std::string groups;                   // --groups FILE
+    double groups_within = 0;             // --groups-within T
+    size_t bins = 256;                    // --bins B
+    int matrix = -1;                      // --matrix: DST_MATRIX_TSV / DST_MATRIX_PHYLIP (-1: the long form)
+    size_t bootstrap = 0;                 // --bootstrap B (0: none)
+    size_t seed = 1;                      // --seed S
+    int dendrogram = -1;                  // --dendrogram: DST_LINK_* (-1: none)
+    std::string selftest;
+    size_t n_inputs() const { return flag_inputs.size() + pos_inputs.size(); }
+    // the slab size an analysis is given: the library's own choice unless --slab-pairs was passed
+    uint64_t analysis_slab() const { return has[F_SLAB_PAIRS] ? slab_pairs : 0; }
+};
+
+[[noreturn]] void die_value(const std::string &v, const char *shown, const std::string &why)
+{
+    die_usage("invalid value '" + v + "' for '" + shown + "'" + why);
+}
+
+size_t parse_usize(const std::string &v, const char *shown)
+{
+    if (v.empty() || v.find_first_not_of("0123456789") != std::string::npos)
+        die_value(v, shown, ": invalid digit found in string");
+    errno = 0;
+    unsigned long long x = std::strtoull(v.c_str(), nullptr, 10);
+    if (errno)
+        die_value(v, shown, ": number too large to fit in target type");
+    return (size_t)x;
+}
+
+size_t parse_in_range(const std::string &v, const char *shown, size_t lo, size_t hi)
+{
+    const size_t x = parse_usize(v, shown);
+    if (x < lo || x > hi)
+        die_value(v, shown, ": " + v + " is not in " + std::to_string(lo) + "..=" + std::to_string(hi));
+    return x;
+}
+
+// the whole word is the number (or inf): strtod, nothing left over, not NaN
+double parse_number(const std::string &v, const char *shown)
+{
+    char *end = nullptr;
+    const double t = v.empty() ? 0.0 : std::strtod(v.c_str(), &end);
+    if (v.empty() || end != v.c_str() + v.size() || t != t || std::isspace((unsigned char)v[0]))
+        die_value(v, shown, ": not a number");
+    return t;
+}
+
+double parse_threshold(const std::string &v, const char *shown)
+{
+    const double t = parse_number(v, shown);
+    if (t < 0)
+        die_value(v, shown, ": the threshold must not be negative");
+    return t;
+}
+
+// one of an enumerated list of words -> its value
+int parse_choice(const std::string &v, const char *shown, std::initializer_list<std::pair<const char *, int>> choices,
+                 const char *note = "")
+{
+    std::string words;
+    for (const auto &c : choices) {
+        if (v == c.first)
+            return c.second;
+        words += std::string(words.empty() ? "" : ", ") + c.first;
+    }
+    die_value(v, shown, "\n  [possible values: " + words + "]" + note);
+}
+
+// The checks that follow the scan, as one table walked top to bottom.  A row speaks when its flag was given, and says the
+// first thing that is wrong, in this order: a flag of `refuses` is present (the first one in the row's order is named); none
+// of `needs` is; a second loaded file; more than one GPU.  The rows' order and each row's own order are the order the
+// messages have always had: which of two modes names the other, and which of several flags is named, is behaviour.
+enum TwoInputs { TWO_OK, ONE_INPUT, ONE_LOADED, ONE_FOR_PHYLIP };
+struct Rule {
+    Flag flag;
+    Mode mode;                  // the output mode the flag selects (Mode::Pairs: it is a modifier)
+    std::vector<Flag> refuses;
+    std::vector<Flag> needs;    // any one of them will do
+    const char *needs_shown;    // how the message names them
+    TwoInputs two_inputs;
+    bool one_gpu;
+};
+const std::vector<Flag> kNone;
+const Rule kRules[] = {
+    {F_CLOSEST_FOR, Mode::Pairs, kNone, {F_CLOSEST}, "'--closest <k>'", TWO_OK, false},
+    {F_GROUPS_WITHIN, Mode::Pairs, kNone, {F_GROUPS}, "'--groups <FILE>'", TWO_OK, false},
+    {F_PER_RECORD, Mode::Pairs, kNone, {F_GROUPS}, "'--groups <FILE>'", TWO_OK, false},
+    {F_GROUPS, Mode::Groups,
+     {F_STREAM, F_NEAREST, F_CLOSEST, F_WITHIN, F_CLUSTERS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_MST, F_DENDROGRAM, F_MAX_DISTANCE,
+      F_SITES, F_HISTOGRAM, F_SUMMARY}, kNone, nullptr, TWO_OK, true},
+    {F_SITES, Mode::Pairs,
+     {F_STREAM, F_NEAREST, F_CLOSEST, F_CLUSTERS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_DENDROGRAM, F_SUMMARY, F_HISTOGRAM},
+     {F_MAX_DISTANCE, F_MST}, "'--max-distance <T>' or '--mst'", TWO_OK, false},
+    {F_CLOSEST, Mode::Closest,
+     {F_NEAREST, F_CLUSTERS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_MST, F_DENDROGRAM, F_MAX_DISTANCE, F_HISTOGRAM, F_SUMMARY, F_WITHIN},
+     {F_STREAM}, "'--stream <stream>'", ONE_LOADED, true},
+    {F_WITHIN, Mode::Within,
+     {F_CLOSEST, F_NEAREST, F_CLUSTERS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_MST, F_DENDROGRAM, F_MAX_DISTANCE, F_HISTOGRAM, F_SUMMARY},
+     {F_STREAM}, "'--stream <stream>'", ONE_LOADED, true},
+    {F_SUMMARY, Mode::Summary,
+     {F_STREAM, F_NEAREST, F_CLUSTERS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_MST, F_DENDROGRAM, F_MAX_DISTANCE, F_HISTOGRAM}, kNone,
+     nullptr, TWO_OK, true},
+    {F_HISTOGRAM, Mode::Histogram,
+     {F_STREAM, F_NEAREST, F_CLUSTERS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_MST, F_DENDROGRAM, F_MAX_DISTANCE}, kNone, nullptr, TWO_OK,
+     true},
+    {F_BINS, Mode::Pairs, kNone, {F_HISTOGRAM}, "'--histogram <W>'", TWO_OK, false},
+    {F_MAX_DISTANCE, Mode::MaxDistance, {F_STREAM, F_NEAREST, F_CLUSTERS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_MST, F_DENDROGRAM},
+     kNone, nullptr, TWO_OK, true},
+    // (--dendrogram with --bootstrap or --seed: their own rows below, which ask for '--tree nj')
+    {F_DENDROGRAM, Mode::Dendrogram, {F_STREAM, F_NEAREST, F_CLUSTERS, F_MATRIX, F_TREE, F_MST, F_MAX_DISTANCE}, kNone, nullptr,
+     ONE_INPUT, true},
+    {F_NEAREST, Mode::Nearest, {F_STREAM}, kNone, nullptr, TWO_OK, true},
+    {F_CLUSTERS, Mode::Clusters, {F_STREAM, F_NEAREST}, kNone, nullptr, ONE_INPUT, true},
+    {F_MATRIX, Mode::Matrix, {F_STREAM, F_NEAREST, F_CLUSTERS}, kNone, nullptr, ONE_FOR_PHYLIP, false},
+    {F_TREE, Mode::Tree, {F_STREAM, F_NEAREST, F_CLUSTERS, F_MATRIX}, kNone, nullptr, ONE_INPUT, true},
+    {F_MST, Mode::Mst, {F_STREAM, F_NEAREST, F_CLUSTERS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_MAX_DISTANCE}, kNone, nullptr, ONE_INPUT,
+     true},
+    {F_BOOTSTRAP, Mode::Pairs, kNone, {F_TREE}, "'--tree nj'", TWO_OK, false},
+    {F_SEED, Mode::Pairs, kNone, {F_BOOTSTRAP}, "'--bootstrap <B>'", TWO_OK, false},
+};
+
+void check_rules(Args &a)
+{
+    const bool many_gpus = a.devices.size() > 1 || (a.devices.empty() && a.gpus > 1);
+    for (const Rule &r : kRules) {
+        if (!a.has[r.flag])
+            continue;
+        const std::string self = std::string("the argument '") + kFlags[r.flag].shown + "'";
+        for (const Flag other : r.refuses)
+            if (a.has[other])
+                die_usage(self + " cannot be used with '" + kFlags[other].shown + "'");
+        if (!r.needs.empty() && std::none_of(r.needs.begin(), r.needs.end(), [&](Flag f) { return a.has[f]; }))
+            die_usage(self + " requires " + r.needs_shown);
+        if (a.n_inputs() > 1 && r.two_inputs == ONE_FOR_PHYLIP && a.matrix == DST_MATRIX_PHYLIP)
+            die_usage("the argument '--matrix phylip' takes one input alignment (a square matrix), not two");
+        if (a.n_inputs() > 1 && (r.two_inputs == ONE_INPUT || r.two_inputs == ONE_LOADED))
+            die_usage(self + " takes one " + (r.two_inputs == ONE_INPUT ? "input" : "loaded") + " alignment, not two");
+        if (r.one_gpu && many_gpus)
+            die_usage(self + " cannot be used with '" + kFlags[a.devices.size() > 1 ? F_DEVICES : F_GPUS].shown +
+                      "' naming more than one GPU");
+        if (r.mode != Mode::Pairs)
+            a.mode = r.mode;   // the modes refuse each other: at most one row gets here
+    }
+}
+
+Args parse_args(int argc, char **argv)
+{
+    Args a;
+    int k = 1;
+    std::string arg, v;
+    // "--name value", "--name=value", "-n value", "-nvalue": true when `arg` is flag f, with its value in v
+    auto opt = [&](Flag f) -> bool {
+        const FlagDef &d = kFlags[f];
+        const std::string name(d.shown, std::strcspn(d.shown, " "));
+        const bool is_long = arg == name || arg.rfind(name + "=", 0) == 0;
+        if (!is_long && !(d.letter && arg.rfind(d.letter, 0) == 0 && arg.rfind("--", 0) != 0))
+            return false;
+        const size_t eq = arg.find('=');
+        if (is_long && eq != std::string::npos)
+            v = arg.substr(eq + 1);
+        else if (!is_long && arg.size() > 2)
+            v = arg.substr(2);  // -mraw
+        else if (k + 1 >= argc)
+            die_usage(std::string("a value is required for '") + d.shown + "' but none was supplied");
+        else
+            v = argv[++k];
+        if (d.once && a.has[f])
+            die_usage(std::string("the argument '") + d.shown + "' cannot be used multiple times");
+        a.has[f] = true;
+        return true;
+    };
+    auto shown = [](Flag f) { return kFlags[f].shown; };
+    auto text = [&](Flag f, std::string &into) { return opt(f) && (into = v, true); };
+    auto count = [&](Flag f, size_t &into, size_t lo, size_t hi) {
+        return opt(f) && (into = parse_in_range(v, shown(f), lo, hi), true);
+    };
+    auto threshold = [&](Flag f, double &into) { return opt(f) && (into = parse_threshold(v, shown(f)), true); };
+    bool only_pos = false;
+    for (; k < argc; ++k) {
+        arg = argv[k];
+        if (only_pos || arg == "-" || arg.empty() || arg[0] != '-') {
+            a.pos_inputs.push_back(arg);
+        } else if (arg == "--") {
+            only_pos = true;
+        } else if (arg == "-h" || arg == "--help") {
+            print_help();
+            std::exit(0);
+        } else if (arg == "-V" || arg == "--version") {
+            std::printf("distance %s\n", kVersion);
+            std::exit(0);
+        } else if (arg == "-l" || arg == "--licenses") {
+            a.licenses = true;
+        } else if (arg == "--input" || arg.rfind("--input=", 0) == 0 || (arg.rfind("-i", 0) == 0 && arg.rfind("--", 0) != 0)) {
+            // num_args(0..=2): takes following non-flag words, at most two
+            const size_t eq = arg.find('=');
+            if (arg.rfind("--", 0) == 0 && eq != std::string::npos)
+                a.flag_inputs.push_back(arg.substr(eq + 1));
+            else if (arg.rfind("--", 0) != 0 && arg.size() > 2)
+                a.flag_inputs.push_back(arg.substr(2));
+            while (a.flag_inputs.size() < 2 && k + 1 < argc && (argv[k + 1][0] != '-' || !std::strcmp(argv[k + 1], "-")))
+                a.flag_inputs.push_back(argv[++k]);
+        } else if (text(F_STREAM, a.stream) || text(F_MEASURE, a.measure) || text(F_OUTPUT, a.output) ||
+                   text(F_GROUPS, a.groups) || count(F_THREADS, a.threads, 0, SIZE_MAX) ||
+                   count(F_BATCHSIZE, a.batchsize, 0, SIZE_MAX) || count(F_SEED, a.seed, 0, SIZE_MAX) ||
+                   count(F_NEAREST, a.nearest, 1, 256) || count(F_CLOSEST, a.closest, 1, 256) ||
+                   count(F_BINS, a.bins, 1, DST_SUMMARY_MAX_BINS) || count(F_BOOTSTRAP, a.bootstrap, 1, 10000) ||
+                   threshold(F_CLUSTERS, a.clusters) || threshold(F_MAX_DISTANCE, a.max_distance) ||
+                   threshold(F_WITHIN, a.within) || threshold(F_SUMMARY, a.summary) ||
+                   threshold(F_GROUPS_WITHIN, a.groups_within)) {
+            // a word, a count in a range or a threshold: stored
+        } else if (opt(F_GPUS)) {
+            a.gpus = (int)parse_usize(v, shown(F_GPUS));
+        } else if (opt(F_DEVICES)) {
+            for (size_t p = 0; p <= v.size();) {
+                const size_t q = std::min(v.find(',', p), v.size());
+                a.devices.push_back((int)parse_usize(v.substr(p, q - p), shown(F_DEVICES)));
+                p = q + 1;
+            }
+        } else if (opt(F_SLAB_PAIRS)) {
+            a.slab_pairs = std::max<size_t>(1, parse_usize(v, shown(F_SLAB_PAIRS)));
+        } else if (opt(F_CLOSEST_FOR)) {
+            a.closest_side = parse_choice(v, shown(F_CLOSEST_FOR), {{"loaded", DST_CLOSEST_FOR_LOADED},
+                                          {"streamed", DST_CLOSEST_FOR_STREAMED}});
+        } else if (opt(F_HISTOGRAM)) {
+            a.histogram = parse_number(v, shown(F_HISTOGRAM));
+            // dst_summary's bounds: the width as a fixed-point value is at least one unit (2^-37) and below 2^62
+            if (!(a.histogram > 0) || !(a.histogram < 0x1p25) || std::rint(std::ldexp(a.histogram, DST_SUMMARY_SCALE_BITS)) < 1)
+                die_value(v, shown(F_HISTOGRAM), ": the bin width must be above 0 and below 2^25");
+        } else if (opt(F_MATRIX)) {
+            a.matrix = parse_choice(v, shown(F_MATRIX), {{"tsv", DST_MATRIX_TSV}, {"phylip", DST_MATRIX_PHYLIP}});
+        } else if (opt(F_TREE)) {
+            parse_choice(v, shown(F_TREE), {{"nj", 0}},
+                         "\n  (UPGMA and the other rooted linkage trees: see '--dendrogram average')");
+        } else if (opt(F_DENDROGRAM)) {
+            a.dendrogram = parse_choice(v, shown(F_DENDROGRAM), {{"average", DST_LINK_AVERAGE}, {"weighted", DST_LINK_WEIGHTED},
+                                        {"complete", DST_LINK_COMPLETE}});
+        } else if (opt(F_SELFTEST)) {
+            a.selftest = v;
+        } else if (arg == "--per-record" || arg == "--mst" || arg == "--sites") {
+            a.has[arg == "--per-record" ? F_PER_RECORD : arg == "--mst" ? F_MST : F_SITES] = true;
+        } else {
+            die_usage("unexpected argument '" + arg + "' found");
+        }
+    }
+    if (a.pos_inputs.size() > 2)
+        die_usage("unexpected argument '" + a.pos_inputs[2] + "' found");
+    a.mode = a.has[F_STREAM] ? Mode::Stream : Mode::Pairs;
+    check_rules(a);
+    if (dst_measure_from_name(a.measure.c_str()) < 0)
+        die_value(a.measure, shown(F_MEASURE), "\n  [possible values: n, n_high, raw, jc69, k80, tn93]");
+    if (a.has[F_HISTOGRAM] && dst_measure_from_name(a.measure.c_str()) <= DST_N_HIGH && a.histogram != std::floor(a.histogram))
+        die_usage("invalid value for '--histogram <W>': the bin width must be an integer with '--measure " + a.measure + "'");
+    return a;
+}
+
+}  // namespace
