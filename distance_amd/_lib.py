@@ -133,6 +133,7 @@ _SIGS = {
     "dst_gather_slabs": (C.c_int, [_vp, _vp, _vp, _u64p, _u64p, C.c_int, _vp]),
     "dst_nearest": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint32, _vp, _vp, _vp, C.c_size_t, _u32p]),
     "dst_clusters": (C.c_int, [_vp, C.c_int, C.c_double, C.c_uint64, _vp, C.c_size_t, _u64p, _u64p]),
+    "dst_representatives": (C.c_int, [_vp, C.c_int, C.c_double, C.c_uint64, _vp, _vp, _vp, C.c_size_t, _u64p]),
     "dst_links": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_int, _vp, _vp, _u64p]),
     "dst_pair_sites": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_size_t, _u64p]),
     "dst_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint32, C.c_double, _vp, _vp,

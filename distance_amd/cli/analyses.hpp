@@ -69,6 +69,34 @@ void write_clusters(const Run &run, double threshold)
     out.finish();
 }
 
+// --representatives: one line per record in input order, "id, representative's id, value", from dst_representatives.  A
+// member's value is the text the full run prints for the pair (representative, record), from the pair's tallies as
+// write_nearest's; a representative names itself and its third field is empty.
+void write_representatives(const Run &run, double threshold)
+{
+    const Alignment &set = run.rows();
+    const size_t W = run.tally_width(), cap = std::max<size_t>(set.n, 1);
+    std::vector<uint32_t> rep(cap), tallies(cap * W);
+    run.gpu.check(dst_representatives(run.gpu.h, run.measure, threshold, run.max_pairs, rep.data(), tallies.data(), nullptr, set.n,
+                                      nullptr),
+                  "representatives");
+    run.header("sequence\trepresentative\tdistance\n");
+    LineWriter out(run.wr);
+    for (size_t j = 0; j < set.n; ++j) {
+        const size_t r = rep[j];
+        if (r == j) {
+            out.put(set.ids[j]);
+            out.put('\t');
+            out.put(set.ids[j]);
+            out.put('\t');
+        } else {
+            out.pair_line(set.ids[j], set.ids[r], run.measure, &tallies[j * W], run.tn93.row(r), run.tn93.col(j));
+        }
+        out.end_line();
+    }
+    out.finish();
+}
+
 // --sites: the fourth field of a --max-distance / --mst line.  The pairs of dst_pair_sites' entries, each "X<pos>Y": pos
 // 1-based, X / Y the IUPAC letter of the first / second record's nibble; "." for a pair without listed sites.
 // diff_tally: how many entries a pair has, from its DST_OUT_TALLY words (dst_pair_sites' first consequence), which sizes

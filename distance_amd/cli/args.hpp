@@ -52,6 +52,10 @@ void print_help()
         "      --clusters <T>           Print the single-linkage cluster of every record instead of distances: records "
         "within distance T (a number >= 0) of each other share a cluster, numbered from 1 in order of first record. One "
         "input, one GPU, no --stream or --nearest\n"
+        "      --representatives <T>    Print the greedy representative of every record instead of distances: in input order a "
+        "record is kept (a representative) unless a record kept before it lies within distance T (a number >= 0, or inf); every "
+        "other record is listed with the first kept record within T of it and their distance. No two kept records are within "
+        "T of each other. One input, one GPU, no --stream and no other output mode\n"
         "      --max-distance <T>       Print only the pairs within distance T (a number >= 0, or inf): the lines of the full "
         "run whose distance is at most T, in the same order and with the same text. One or two inputs, one GPU, no --stream "
         "and no other output mode\n"
@@ -105,7 +109,7 @@ const char *kLicences =
 enum Flag {
     F_STREAM, F_MEASURE, F_OUTPUT, F_THREADS, F_BATCHSIZE, F_GPUS, F_DEVICES, F_SLAB_PAIRS, F_NEAREST, F_CLOSEST, F_CLOSEST_FOR,
     F_WITHIN, F_CLUSTERS, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS, F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX,
-    F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM, F_SELFTEST, F_COUNT
+    F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM, F_SELFTEST, F_REPRESENTATIVES, F_COUNT
 };
 struct FlagDef {
     const char *shown;   // "--name <value>": its first word is the flag itself
@@ -122,12 +126,12 @@ const FlagDef kFlags[F_COUNT] = {
     {"--histogram <W>", nullptr, true}, {"--bins <B>", nullptr, false}, {"--matrix <format>", nullptr, false},
     {"--tree <method>", nullptr, false}, {"--bootstrap <B>", nullptr, false}, {"--seed <S>", nullptr, false},
     {"--mst", nullptr, false}, {"--sites", nullptr, false}, {"--dendrogram <linkage>", nullptr, false},
-    {"--host-selftest <what>", nullptr, false},
+    {"--host-selftest <what>", nullptr, false}, {"--representatives <T>", nullptr, true},
 };
 
 // what the run prints, decided once by parse_args
 enum class Mode { Pairs, Stream, Closest, Within, Nearest, Clusters, MaxDistance, Summary, Histogram, Groups, Matrix, Tree, Mst,
-                  Dendrogram };
+                  Dendrogram, Representatives };
 
 struct Args {
     bool has[F_COUNT] = {};               // the flag was given
@@ -144,6 +148,7 @@ struct Args {
     int closest_side = DST_CLOSEST_FOR_LOADED;   // --closest-for loaded|streamed
     double within = 0;                    // --within T (stream mode)
     double clusters = 0;                  // --clusters T
+    double representatives = 0;           // --representatives T
     double max_distance = 0;              // --max-distance T
     double summary = 0;                   // --summary T
     double histogram = 0;                 // --histogram W
@@ -231,6 +236,11 @@ struct Rule {
 };
 const std::vector<Flag> kNone;
 const Rule kRules[] = {
+    // (first: every combination with it is refused here, so no other row's message changes)
+    {F_REPRESENTATIVES, Mode::Representatives,
+     {F_STREAM, F_NEAREST, F_CLOSEST, F_CLOSEST_FOR, F_WITHIN, F_CLUSTERS, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS, F_GROUPS_WITHIN,
+      F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM}, kNone, nullptr,
+     ONE_INPUT, true},
     {F_CLOSEST_FOR, Mode::Pairs, kNone, {F_CLOSEST}, "'--closest <k>'", TWO_OK, false},
     {F_GROUPS_WITHIN, Mode::Pairs, kNone, {F_GROUPS}, "'--groups <FILE>'", TWO_OK, false},
     {F_PER_RECORD, Mode::Pairs, kNone, {F_GROUPS}, "'--groups <FILE>'", TWO_OK, false},
@@ -353,7 +363,7 @@ Args parse_args(int argc, char **argv)
                    count(F_BATCHSIZE, a.batchsize, 0, SIZE_MAX) || count(F_SEED, a.seed, 0, SIZE_MAX) ||
                    count(F_NEAREST, a.nearest, 1, 256) || count(F_CLOSEST, a.closest, 1, 256) ||
                    count(F_BINS, a.bins, 1, DST_SUMMARY_MAX_BINS) || count(F_BOOTSTRAP, a.bootstrap, 1, 10000) ||
-                   threshold(F_CLUSTERS, a.clusters) || threshold(F_MAX_DISTANCE, a.max_distance) ||
+                   threshold(F_CLUSTERS, a.clusters) || threshold(F_REPRESENTATIVES, a.representatives) || threshold(F_MAX_DISTANCE, a.max_distance) ||
                    threshold(F_WITHIN, a.within) || threshold(F_SUMMARY, a.summary) ||
                    threshold(F_GROUPS_WITHIN, a.groups_within)) {
             // a word, a count in a range or a threshold: stored

@@ -232,6 +232,7 @@ int main(int argc, char **argv)
     case Mode::Tree: write_tree(run, (uint32_t)a.bootstrap, a.seed); break;
     case Mode::Dendrogram: write_dendrogram(run, a.dendrogram); break;
     case Mode::Clusters: write_clusters(run, a.clusters); break;
+    case Mode::Representatives: write_representatives(run, a.representatives); break;
     case Mode::Mst: write_mst(run, a.has[F_SITES]); break;
     case Mode::MaxDistance: write_links(run, a.max_distance, a.has[F_SITES]); break;
     case Mode::Summary: write_summary(run, a.summary); break;

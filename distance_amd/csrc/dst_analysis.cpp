@@ -1,6 +1,6 @@
 // dst_analysis.cpp — the analyses of the C ABI that consume a set's pairs slab by slab on the device and return an O(n)
-// or O(n k) result: dst_nearest, dst_clusters, dst_mst, dst_nj (+ _matrix, _bootstrap), dst_dendrogram (+ _matrix),
-// dst_summary; and dst_links, which hands the pairs that pass a threshold to a sink.
+// or O(n k) result: dst_nearest, dst_clusters, dst_representatives, dst_mst, dst_nj (+ _matrix, _bootstrap), dst_dendrogram
+// (+ _matrix), dst_summary; and dst_links, which hands the pairs that pass a threshold to a sink.
 // Each one is the same program: plan the row slabs, grow the context's slab scratch, walk the slabs (the
 // pair kernel of a slab into the scratch, the analysis' kernels directly behind it), carve its O(n) state out of one
 // allocation, copy the result back.  Everything runs on the context's stream and waits before it returns.
@@ -542,6 +542,90 @@ int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs
         *n_clusters = roots;
     if (links)
         *links = h_links;
+    return DST_OK;
+}
+
+int dst_representatives(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs, uint32_t *rep, uint32_t *tallies,
+                        void *values, size_t cap, uint64_t *n_representatives)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (n_representatives)
+        *n_representatives = 0;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (std::isnan(threshold))
+        return fail(ctx, DST_ERR_ARG, "threshold is NaN");
+    if (!rep)
+        return fail(ctx, DST_ERR_ARG, "null rep pointer");
+    DeviceSet &set = ctx->set[0];
+    if (!set.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    const uint64_t n = set.n;
+    if (n >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    if (cap < n)
+        return fail(ctx, DST_ERR_CAPACITY, "cap is below the set's record count");
+    uint64_t t_bits;
+    const bool any = threshold_payload(measure, threshold, t_bits);
+    const int W = tally_width(measure);
+    if (n < 2 || !any) {   // (nothing can link: every record its own representative, no slab is run)
+        for (uint64_t i = 0; i < n; ++i)
+            rep[i] = (uint32_t)i;
+        if (values)
+            std::memset(values, 0, n * 8);
+        if (tallies)
+            std::memset(tallies, 0, n * 4 * (size_t)W);
+        if (n_representatives)
+            *n_representatives = n;
+        return DST_OK;
+    }
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    const bool tally = tallies != nullptr;
+    if (tally && measure == DST_TN93)
+        if (int rc = need_counts(ctx, set, stream))
+            return rc;
+    const int kind = tally ? DST_OUT_TALLY : DST_OUT_DISTANCE;
+    const SlabPlan plan = plan_slabs(true, n, n, max_pairs, kClusterSlabPairs);
+    RepBuffers b{};
+    auto layout = [&](void *base) {
+        Carve c(base);
+        b.rep = c.take<uint32_t>(n);
+        b.bits = c.take<uint32_t>(n * (size_t)(kRepBlockRows / 32));
+        b.val = values ? c.take<uint64_t>(n) : nullptr;
+        b.tal = tally ? c.take<uint32_t>(n * (size_t)W) : nullptr;
+        return c.used;
+    };
+    const size_t state_bytes = layout(nullptr);
+    int rc = slab_scratch(ctx, dst_out_bytes(measure, kind, plan.biggest));
+    if (!rc)
+        rc = ctx->rep_work.grow(ctx, state_bytes);
+    if (rc)
+        return rc;
+    layout(ctx->rep_work);
+    // rep: unset (2^32-1) everywhere; values and tallies: the representatives' zero bits everywhere
+    HIP_TRY(ctx, hipMemsetAsync(ctx->rep_work, 0, state_bytes, stream));
+    HIP_TRY(ctx, hipMemsetAsync(b.rep, 0xFF, n * 4, stream));
+    // the slab, then behind the pair kernel its link bits and its sub-blocks in order: resolve, cover and (when wanted) values each
+    rc = walk_slabs(ctx, measure, true, set, set, plan.slabs, kind, [&](const RowSlab &s) -> int {
+        HIP_TRY(ctx, launch_rep_slab(measure, tally, ctx->pair_slab.ptr, s.first, n, s.rb, s.re, t_bits, set.counts, b, stream));
+        return DST_OK;
+    });
+    if (rc)
+        return rc;
+    HIP_TRY(ctx, launch_rep_final(b.rep, n, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(rep, b.rep, n * 4, hipMemcpyDeviceToHost, stream));
+    if (values)
+        HIP_TRY(ctx, hipMemcpyAsync(values, b.val, n * 8, hipMemcpyDeviceToHost, stream));
+    if (tally)
+        HIP_TRY(ctx, hipMemcpyAsync(tallies, b.tal, n * 4 * (size_t)W, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    uint64_t count = 0;
+    for (uint64_t i = 0; i < n; ++i)
+        count += rep[i] == i;
+    if (n_representatives)
+        *n_representatives = count;
     return DST_OK;
 }
 

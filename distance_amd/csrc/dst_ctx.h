@@ -156,6 +156,7 @@ struct dst_ctx {
     Grown<> pair_slab;
     Grown<> nn_lists;       // dst_nearest: the running lists
     Grown<> cl_work;        // dst_clusters: the parent array + link counter
+    Grown<> rep_work;       // dst_representatives: rep, and the values and tallies when they are wanted
     Grown<> mst_work;       // dst_mst: the component, best-edge and edge-list arrays
     Grown<> dg_work;        // dst_dendrogram: the O(n) state beside the per-call square
     // dst_links: the block counts / offsets and one chunk of outputs on the device, the same chunk in page-locked host memory

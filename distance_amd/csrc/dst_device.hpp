@@ -330,6 +330,28 @@ __device__ __forceinline__ uint64_t pair_value(const uint32_t *o, uint4 qc, uint
         return (uint64_t)__double_as_longlong(finalize_pair<M>(o, qc, tc));
 }
 
+// the payload of entry `at` of an analysis' slab (dst_links, dst_representatives): read from a DST_OUT_DISTANCE slab (TALLY
+// false) or computed from the entry's W DST_OUT_TALLY words; qc: tn93's base counts of the row record, t_counts[j]: of
+// the column record
+template <int M, int W, bool TALLY>
+__device__ __forceinline__ uint64_t entry_value(const void *__restrict__ slab, uint64_t at, uint4 qc, const uint32_t *t_counts,
+                                                uint32_t j)
+{
+    if constexpr (!TALLY) {
+        return __builtin_nontemporal_load(static_cast<const uint64_t *>(slab) + at);
+    } else {
+        const uint32_t *p = static_cast<const uint32_t *>(slab) + at * W;
+        uint32_t o[W];
+#pragma unroll
+        for (int t = 0; t < W; ++t)
+            o[t] = p[t];
+        uint4 tc = make_uint4(0, 0, 0, 0);
+        if constexpr (M == DST_TN93)
+            tc = reinterpret_cast<const uint4 *>(t_counts)[j];
+        return pair_value<M>(o, qc, tc);
+    }
+}
+
 // the sort key of a DST_OUT_DISTANCE payload (dst_nearest's order, dst_clusters' threshold test): int64 -> offset
 // binary; f64 -> the order-preserving bit flip, every NaN ~0 (after +inf, equal to each other), -0.0 the key of +0.0
 template <bool INT>

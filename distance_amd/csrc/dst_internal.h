@@ -442,6 +442,23 @@ hipError_t launch_clusters_link(int measure, const uint64_t *slab, uint64_t out_
                                 uint64_t t_bits, uint32_t *parent, unsigned long long *links, hipStream_t stream);
 hipError_t launch_clusters_final(uint32_t *parent, uint64_t n, hipStream_t stream);
 
+// ---- greedy representatives (dst_representatives.hip, driven by dst_representatives in dst_analysis.cpp) -----------------
+// Slabs as for dst_clusters (DST_OUT_DISTANCE payloads, or DST_OUT_TALLY words when the tallies are wanted: `tally`).  A slab's
+// rows are taken in sub-blocks of kRepBlockRows rows, in order: 512 x 512 link bits are 32 KiB of one workgroup's LDS.
+constexpr uint32_t kRepBlockRows = 512;
+struct RepBuffers {
+    uint32_t *rep;    // [n] 2^32-1: unset
+    uint32_t *bits;   // [n][kRepBlockRows / 32] the slab's rows' links inside their own sub-block
+    uint64_t *val;    // [n] the DST_OUT_DISTANCE payload of (rep[j], j), or NULL
+    uint32_t *tal;    // [n][tally_width] its DST_OUT_TALLY words, or NULL
+};
+// rows [rb, re) of the slab (every earlier row has been through this): the bits launch, then per sub-block the resolve
+// launch, the cover launch, and the values launch when b.val or b.tal is set.  counts: tn93's base counts of the set
+// (tally slabs)
+hipError_t launch_rep_slab(int measure, bool tally, const void *slab, uint64_t out_base, uint64_t n, uint64_t rb, uint64_t re,
+                           uint64_t t_bits, const uint32_t *counts, const RepBuffers &b, hipStream_t stream);
+hipError_t launch_rep_final(uint32_t *rep, uint64_t n, hipStream_t stream);   // behind the last slab: unset -> itself
+
 // ---- pairs within a threshold (dst_links.hip, driven by dst_links in dst_analysis.cpp) --------------------------------
 // Per row slab (cut as for dst_clusters; DST_OUT_DISTANCE payloads, or DST_OUT_TALLY words when the links' tallies are
 // wanted: `tally`) a count launch with dst_clusters' geometry, one count per workgroup, the workgroups numbered in canonical

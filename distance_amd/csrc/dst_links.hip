@@ -49,26 +49,6 @@ __device__ __forceinline__ uint64_t row_base_of(const LinkRows &g, uint32_t i)
     return g.square ? tri_row_start(g.n_cols, i) - g.out_base : (uint64_t)(i - g.rb) * g.n_cols;
 }
 
-// the payload of slab entry `at`: read (TALLY false) or computed from the entry's W tally words
-template <int M, int W, bool TALLY>
-__device__ __forceinline__ uint64_t entry_value(const void *__restrict__ slab, uint64_t at, uint4 qc, const uint32_t *t_counts,
-                                                uint32_t j)
-{
-    if constexpr (!TALLY) {
-        return __builtin_nontemporal_load(static_cast<const uint64_t *>(slab) + at);
-    } else {
-        const uint32_t *p = static_cast<const uint32_t *>(slab) + at * W;
-        uint32_t o[W];
-#pragma unroll
-        for (int t = 0; t < W; ++t)
-            o[t] = p[t];
-        uint4 tc = make_uint4(0, 0, 0, 0);
-        if constexpr (M == DST_TN93)
-            tc = reinterpret_cast<const uint4 *>(t_counts)[j];
-        return pair_value<M>(o, qc, tc);
-    }
-}
-
 // The test of this thread's kLinkSteps entries: v[t] their payloads, the result bit t = the entry of step t is a link.
 template <int M, int W, bool TALLY>
 __device__ __forceinline__ uint32_t test_entries(const void *__restrict__ slab, const LinkRows &g, uint32_t i, uint64_t q0, int lane,

@@ -473,6 +473,31 @@ class Engine:
                                            C.byref(n_clusters), C.byref(links)))
         return labels[:n], int(links.value)
 
+    def representatives(self, measure, threshold: float, max_pairs: int = 0, values: bool = True, tallies: bool = False):
+        """Greedy representatives of slot 0 (dst_representatives): (rep uint32[n], values[n][, tallies[n, width]]).  In input
+        order a record is a representative unless an earlier representative is linked to it (dst_clusters' rule against
+        `threshold`); rep[j] = j then, otherwise the smallest representative linked to j.  values (int64 for n / n_high,
+        float64 otherwise) and tallies (uint32) are those of the pair (rep[j], j), bitwise run_square's, and all-zero bits for a
+        representative.  max_pairs: the most pairs of one row slab (0: the default); the result does not depend on it.
+        last_representatives keeps the number of representatives."""
+        m = _measure_id(measure)
+        n, _ = self.set_info(0)
+        width = self._lib.dst_tally_width(m)
+        rep = np.zeros(max(n, 1), np.uint32)   # (never a NULL rep, also for an empty set)
+        val = np.zeros(max(n, 1), np.int64 if m in (0, 1) else np.float64) if values else None
+        tal = np.zeros((max(n, 1), width), np.uint32) if tallies else None
+        count = C.c_uint64()
+        self._check(self._lib.dst_representatives(self._h, m, float(threshold), int(max_pairs), rep.ctypes.data,
+                                                  None if tal is None else tal.ctypes.data,
+                                                  None if val is None else val.ctypes.data, n, C.byref(count)))
+        self.last_representatives = int(count.value)
+        out = (rep[:n],)
+        if values:
+            out += (val[:n],)
+        if tallies:
+            out += (tal[:n],)
+        return out
+
     def links(self, measure, threshold: float, square: bool = True, row_slot: int = 0, col_slot: int = 1, max_pairs: int = 0,
               values: bool = True, tallies: bool = False, count_only: bool = False):
         """The pairs within `threshold` (dst_links), in canonical pair order: (row uint32[n_links], col uint32[n_links]), then

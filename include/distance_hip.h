@@ -469,6 +469,39 @@ int dst_nearest(dst_ctx *ctx, int measure, int square, int row_slot, int col_slo
  * in row slabs whose payloads a lock-free union-find on the device consumes.  Single GPU, loaded set only (not dst_stream). */
 int dst_clusters(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs, uint32_t *label, size_t cap,
                  uint64_t *n_clusters, uint64_t *links);
+/* ---- greedy representatives -------------------------------------------------------------------- */
+/* A subset in which no two records are within `threshold` of each other, and for every other record the kept record that
+ * stands for it (dereplication, downsampling before a tree; greedy incremental clustering): the only grouping here with
+ * a guaranteed radius, where single linkage chains.  One set (slot 0, n records, input order 0..n-1).
+ *   link             records i < j are linked when the pair's DST_OUT_DISTANCE payload v satisfies dst_clusters' rule
+ *                    against T = threshold: n / n_high v <= floor(T) (clamped to the int64 range; below -2^63 nothing
+ *                    links); f64 measures on dst_nearest's sort key: NaN never links, -0.0 links wherever +0.0 does, +inf
+ *                    links every pair whose value is not NaN
+ *   representatives  record j is a representative iff no representative i < j is linked to j: the lexicographically first
+ *                    maximal independent set of the dst_links(T) graph, what a sequential pass over the records in input
+ *                    order builds.  It is unique, and depends neither on the kernel path nor on max_pairs.
+ *   rep        n entries (host memory, required): rep[j] = j for a representative, otherwise the smallest representative
+ *              linked to j, which is always < j
+ *   values     n DST_OUT_DISTANCE payloads (int64 for n / n_high, else f64), or NULL: for a member the payload of the pair
+ *              (rep[j], j), bitwise what dst_run_square returns for it; for a representative all-zero bits
+ *   tallies    n x dst_tally_width(measure) DST_OUT_TALLY words, or NULL: for a member the pair's words (tn93 base counts
+ *              in (rep[j], j) order; dst_finalize -> the reference's bits); for a representative all-zero words
+ *   cap        the room of every non-NULL array in entries, below n DST_ERR_CAPACITY
+ *   n_representatives   the number of representatives, or NULL
+ *   threshold, max_pairs   as in dst_clusters
+ * Consequences: no two representatives are linked; every member is linked to its rep[j] and to no smaller representative;
+ * record 0 is always a representative; every member lies in the dst_clusters(T) cluster of its representative; the
+ * smallest record of every dst_clusters(T) cluster is a representative; *n_representatives >= the number of clusters.
+ * Distance 0 is not transitive under ambiguity codes, so even T = 0 can keep two representatives in one cluster.
+ * n < 2: the trivial answer; a threshold below which nothing links: every record its own representative; neither runs a
+ * slab.  The checks and messages are dst_clusters': DST_ERR_ARG for a NULL ctx or rep, an unknown measure, a NaN threshold,
+ * n >= 2^32-1; DST_ERR_STATE: slot 0 is not uploaded.  Synchronous on the context's stream.  The pairs are computed once
+ * (the triangle), in row slabs; behind each slab's pair kernel its rows are resolved in sub-blocks of 512 (one workgroup
+ * settles a sub-block's own dependencies in LDS, a wide launch marks what the new representatives cover) and the host
+ * never waits inside the sweep.  Slots, the path choice and later dst_run_square results are untouched.  Single GPU,
+ * loaded set only (not dst_stream). */
+int dst_representatives(dst_ctx *ctx, int measure, double threshold, uint64_t max_pairs, uint32_t *rep, uint32_t *tallies,
+                        void *values, size_t cap, uint64_t *n_representatives);
 /* ---- pairs within a threshold ------------------------------------------------------------------ */
 /* Which pairs are within `threshold` (the edge list of a transmission network, the sparse output of a thresholded run),
  * selected next to the values on the GPU and handed to a sink in chunks: the full result is never written.  The
