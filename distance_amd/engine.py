@@ -385,12 +385,14 @@ class Engine:
         return out
 
     def run_rect(self, measure, row_slot: int = 0, col_slot: int = 1, row_begin: int = 0,
-                 row_end: int | None = None, tallies: bool = False) -> np.ndarray:
+                 row_end: int | None = None, tallies: bool = False, tallies16: bool = False) -> np.ndarray:
+        """Distances (or tallies) of rows [row_begin, row_end) of row_slot against every record of col_slot:
+        [row - row_begin][column]."""
         m = _measure_id(measure)
         n_rows, _ = self.set_info(row_slot)
         n_cols, _ = self.set_info(col_slot)
         row_end = n_rows if row_end is None else row_end
-        kind = OUT_TALLY if tallies else OUT_DISTANCE
+        kind = OUT_TALLY16 if tallies16 else OUT_TALLY if tallies else OUT_DISTANCE
         out = self._alloc(m, kind, max(row_end - row_begin, 0) * n_cols)
         self._check(self._lib.dst_run_rect_host(self._h, m, row_slot, col_slot, row_begin, row_end, kind,
                                                 out.ctypes.data, out.nbytes))
@@ -780,10 +782,11 @@ class Engine:
                                                   tally_kind | (FIN_CLOSE if close else 0), d_tallies, d_out, capacity, stream))
 
     def run_rect_device(self, measure, row_slot: int, col_slot: int, row_begin: int, row_end: int,
-                        d_out: int, capacity: int, tallies: bool = False, stream: int | None = None):
+                        d_out: int, capacity: int, tallies: bool = False, stream: int | None = None,
+                        out_kind: int | None = None):
         m = _measure_id(measure)
-        self._check(self._lib.dst_run_rect(self._h, m, row_slot, col_slot, row_begin, row_end,
-                                           OUT_TALLY if tallies else OUT_DISTANCE, d_out, capacity, stream))
+        kind = out_kind if out_kind is not None else (OUT_TALLY if tallies else OUT_DISTANCE)
+        self._check(self._lib.dst_run_rect(self._h, m, row_slot, col_slot, row_begin, row_end, kind, d_out, capacity, stream))
 
     def set_prep_threshold(self, site_comparisons: float):
         """dst_set_prep_threshold: 0 sends every upload through the consensus path's fused preparation."""

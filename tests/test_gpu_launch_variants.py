@@ -19,7 +19,7 @@ import pytest
 
 import distance_amd as da
 import oracle
-from helpers import CODES
+from helpers import CODES, check_f64
 
 pytestmark = pytest.mark.gpu
 ALL = ("n", "n_high", "raw", "jc69", "k80", "tn93")
@@ -196,16 +196,6 @@ def make_case(name):
     return a, b
 
 
-def exact_of(fr, measure, tl, q, t):
-    """finalise_reference's exact value of every pair; jc69 / k80 on the distinct tallies only (low-diversity rows repeat)"""
-    if measure == "tn93":
-        return fr.exact(measure, tl, q, t)
-    uniq, inv = np.unique(tl, axis=0, return_inverse=True)
-    inv = inv.reshape(-1)
-    ex = fr.exact(measure, uniq)
-    return fr.Exact(ex.value[inv], ex.scale[inv], ex.e[inv], ex.k[inv])
-
-
 def check_tally_row(measure, kind, got, i, j0, a, cols, tal32, rng):
     """one row of a tally launch against the oracle.  DST_OUT_TALLY: exactly, on one column of every 64 (any run of 128
     columns, however aligned, holds one: a lost group of a wave's line-groups shows in every row) and on the panel edges;
@@ -230,37 +220,6 @@ def check_tally_row(measure, kind, got, i, j0, a, cols, tal32, rng):
         with np.errstate(invalid="ignore", divide="ignore"):
             mine = got[:, 0].astype(np.float64) / got[:, 1].astype(np.float64)
         assert np.array_equal(mine, raw, equal_nan=True), (measure, kind, i)
-
-
-def check_f64(measure, got, want, tl, q, t):
-    """jc69 / k80 / tn93 distances of whole rows (concatenated) within test_gpu_finalise_accuracy's bars.  The exact value x
-    comes from the launch's own tally rows, which are first tied to the ORACLE's distances of the same pairs: a tally off
-    by one moves some e_i, and the value, by 2^-17 of itself or more (tallies stay below 2^17 at 70,001 sites), while the
-    host's formula is within 2^-53 / e_i <= 2^-36 of x — so |want - x| <= 2^-27 |x| holds for the right integers only.
-    Then: NaN, inf and zeros as the host gives them; where every series argument lies below the switch |got - x| <= BAR S;
-    past it the close arithmetic, within CLOSE_ULP of the host's bits."""
-    import finalise_reference as fr
-    from test_gpu_finalise_accuracy import BAR, CLOSE_ULP
-    ex = exact_of(fr, measure, tl, q, t)
-    x = ex.value.astype(np.float64)
-    special = ~np.isfinite(x) | (x == 0)
-    assert np.array_equal(np.isnan(x), np.isnan(want)) and np.array_equal(np.isinf(x), np.isinf(want)), measure
-    assert np.array_equal(x == 0, want == 0), measure
-    with np.errstate(all="ignore"):
-        tied = np.abs(want.astype(fr.LD) - ex.value) <= np.abs(ex.value) * fr.LD(2.0 ** -27)
-    assert tied[~special].all(), (measure, int((~tied[~special]).sum()))
-    assert np.array_equal(np.isnan(got[special]), np.isnan(want[special])), measure
-    keep = special & ~np.isnan(want)
-    assert np.array_equal(got[keep].view(np.uint64), want[keep].view(np.uint64)), measure
-    sm = fr.LD(fr.SERIES_MAX)
-    with np.errstate(all="ignore"):
-        unsure = (np.abs(ex.e / sm - 1) < fr.LD(1e-9)).any(axis=1)       # the device's rounded e_i may fall on either side
-        series = ~special & ~unsure & (ex.e < sm).all(axis=1)
-        err = (np.abs(got.astype(fr.LD) - ex.value) / ex.scale).astype(np.float64)
-    assert (err[series] <= BAR[measure]).all(), (measure, float(err[series].max()))
-    rest = ~special & ~unsure & ~series
-    ulp = np.abs(got[rest].view(np.int64) - want[rest].view(np.int64))
-    assert (ulp <= CLOSE_ULP[measure]).all(), (measure, int(ulp.max()))
 
 
 def check_rows_against_the_oracle(measure, kind, buf, width, rows, a, b, counts_a, counts_b, tal_rows):
