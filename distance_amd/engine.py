@@ -927,23 +927,27 @@ class Stream:
                                                         int(self.nibbles), C.byref(h)))
         return h
 
-    def buffer(self):
-        """(codes view (max_records, width) into the page-locked input buffer, counts view (max_records, 4))"""
+    def buffer(self, padded: bool = False):
+        """(codes view (max_records, width) into the page-locked input buffer, counts view (max_records, 4));
+        padded: the rows whole, (max_records, pitch) — the bytes behind a row's width that no result depends on"""
         p, pitch, cnt = C.c_void_p(), C.c_size_t(), C.c_void_p()
         self._eng._check(self._lib.dst_stream_acquire(self._h, C.byref(p), C.byref(pitch), C.byref(cnt)))
         raw = np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint8)), shape=(self.max_records, pitch.value))
         counts = np.ctypeslib.as_array(C.cast(cnt, C.POINTER(C.c_uint32)), shape=(self.max_records, 4))
+        if padded:
+            return raw, counts
         return raw[:, :((self._len + 1) // 2 if self.nibbles else self._len)], counts
 
     def submit(self, n_records: int, use_counts: bool = False):
         self._eng._check(self._lib.dst_stream_submit(self._h, n_records, int(use_counts)))
 
     @staticmethod
-    def to_nibbles(codes: np.ndarray) -> np.ndarray:
-        """Paradis codes (n, L) -> the 4-bit wire format (n, ceil(L / 2)): site 2k in the low nibble of byte k"""
+    def to_nibbles(codes: np.ndarray, pad: int = 15) -> np.ndarray:
+        """Paradis codes (n, L) -> the 4-bit wire format (n, ceil(L / 2)): site 2k in the low nibble of byte k.
+        pad: the unused high nibble of an odd width's last byte (ignored by the pack, whatever it holds)"""
         hi = np.ascontiguousarray(codes, np.uint8) >> 4
         if hi.shape[1] % 2:
-            hi = np.concatenate([hi, np.full((hi.shape[0], 1), 15, np.uint8)], axis=1)
+            hi = np.concatenate([hi, np.full((hi.shape[0], 1), pad & 15, np.uint8)], axis=1)
         return hi[:, 0::2] | (hi[:, 1::2] << 4)
 
     def push(self, codes: np.ndarray, counts=None):
