@@ -26,7 +26,8 @@ LINKS_CHUNK = 1 << 22   # DST_LINKS_CHUNK: the most links of one sink call
 STREAM_LINKS_WINDOW = 1 << 20   # DST_STREAM_LINKS_WINDOW: the default most links of one window of a links stream
 PAIR_SITES_BATCH = 1 << 20    # DST_PAIR_SITES_BATCH: the most pairs of one device batch of dst_pair_sites
 PAIR_SITES_WINDOW = 1 << 24   # DST_PAIR_SITES_WINDOW: the most entries of one device output window
-SUMMARY_SCALE_BITS = 37   # DST_SUMMARY_SCALE_BITS: f64 distances are summed as rint(v * 2^37)
+WINDOWS_MAX = 65536           # DST_WINDOWS_MAX: the most windows of one dst_run_windows call
+SUMMARY_SCALE_BITS = 37  # DST_SUMMARY_SCALE_BITS: f64 distances are summed as rint(v * 2^37)
 SUMMARY_MAX_BINS = 4096   # DST_SUMMARY_MAX_BINS
 GROUPS_MAX = 1024         # DST_GROUPS_MAX: the most groups of one side of dst_group_summary
 GROUP_NONE = 0xFFFFFFFF   # DST_GROUP_NONE: a record that belongs to no group
@@ -136,6 +137,12 @@ _SIGS = {
     "dst_representatives": (C.c_int, [_vp, C.c_int, C.c_double, C.c_uint64, _vp, _vp, _vp, C.c_size_t, _u64p]),
     "dst_links": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_int, _vp, _vp, _u64p]),
     "dst_pair_sites": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_size_t, _u64p]),
+    "dst_run_windows": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint32, C.c_int,
+                                  _vp, C.c_size_t, _vp]),
+    "dst_run_windows_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint32,
+                                       C.c_int, _vp, C.c_size_t]),
+    "dst_window_base_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_size_t]),
+    "dst_sliding_windows": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, C.c_size_t, _u32p]),
     "dst_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint32, C.c_double, _vp, _vp,
                               _vp, _vp, C.c_size_t, _vp]),
     "dst_group_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, C.c_double,

@@ -523,4 +523,162 @@ void write_dendrogram(const Run &run, int linkage)
     });
 }
 
+// --windows / --regions: the column windows [begin, end) of the run, 0-based and half-open as dst_run_windows takes them,
+// and the name each line carries (--windows: the window's 1-based ordinal)
+struct WindowList {
+    std::string path;   // --regions FILE
+    std::vector<uint64_t> begin, end;
+    std::vector<std::string> names;
+    std::vector<size_t> line;   // --regions: the line that gave the region
+};
+
+// --regions: the file, read before any input is opened.  One "name<TAB>start<TAB>end" per line (1-based, inclusive), empty
+// lines skipped, no header.
+WindowList read_region_file(const std::string &path)
+{
+    WindowList wl;
+    wl.path = path;
+    FILE *fh = open_input(path);
+    std::string text;
+    char buf[1 << 16];
+    for (size_t got; (got = std::fread(buf, 1, sizeof buf, fh)) > 0;)
+        text.append(buf, got);
+    std::fclose(fh);
+    auto position = [](const std::string &v, uint64_t &out) {
+        if (v.empty() || v.size() > 19 || v.find_first_not_of("0123456789") != std::string::npos)
+            return false;
+        out = std::strtoull(v.c_str(), nullptr, 10);
+        return true;
+    };
+    size_t line_no = 0;
+    for (size_t at = 0; at < text.size();) {
+        size_t stop = text.find('\n', at);
+        if (stop == std::string::npos)
+            stop = text.size();
+        std::string line = text.substr(at, stop - at);
+        at = stop + 1;
+        ++line_no;
+        if (!line.empty() && line.back() == '\r')
+            line.pop_back();
+        if (line.empty())
+            continue;
+        const std::string where = "--regions: line " + std::to_string(line_no) + " of '" + path + "' ";
+        const size_t t1 = line.find('\t'), t2 = t1 == std::string::npos ? t1 : line.find('\t', t1 + 1);
+        if (t2 == std::string::npos)
+            die_message(where + "has fewer than three fields: expected 'name<TAB>start<TAB>end'");
+        if (line.find('\t', t2 + 1) != std::string::npos)
+            die_message(where + "has more than three fields");
+        if (t1 == 0)
+            die_message(where + "has an empty name");
+        uint64_t first = 0, last = 0;
+        if (!position(line.substr(t1 + 1, t2 - t1 - 1), first) || !position(line.substr(t2 + 1), last))
+            die_message(where + "has a start or an end that is not a whole number");
+        if (first < 1 || first > last)
+            die_message(where + "must have 1 <= start <= end");
+        if (wl.begin.size() == DST_WINDOWS_MAX)
+            die_message(where + "starts region " + std::to_string(DST_WINDOWS_MAX + 1) + ": more than " +
+                        std::to_string(DST_WINDOWS_MAX) + " regions");
+        wl.names.push_back(line.substr(0, t1));
+        wl.begin.push_back(first - 1);
+        wl.end.push_back(last);
+        wl.line.push_back(line_no);
+    }
+    if (wl.begin.empty())
+        die_message("--regions: '" + path + "' names no region");
+    return wl;
+}
+
+// ... against the alignment's width, once the inputs are loaded and before the device is looked at
+void check_regions(const WindowList &wl, size_t width)
+{
+    for (size_t w = 0; w < wl.begin.size(); ++w)
+        if (wl.end[w] > width)
+            die_message("--regions: line " + std::to_string(wl.line[w]) + " of '" + wl.path + "' ends at " +
+                        std::to_string(wl.end[w]) + ", past the alignment's " + std::to_string(width) + " sites");
+}
+
+// --windows W --step S over an alignment of `width` sites (dst_sliding_windows)
+WindowList sliding_windows(size_t width, size_t window, size_t step)
+{
+    WindowList wl;
+    uint32_t count = 0;
+    if (dst_sliding_windows(width, window, step, nullptr, nullptr, 0, &count) != DST_OK)
+        die_message("--windows: " + std::to_string(count) + (count == 0xFFFFFFFFu ? " or more" : "") + " windows, more than " +
+                    std::to_string(DST_WINDOWS_MAX));
+    wl.begin.resize(count);
+    wl.end.resize(count);
+    if (count)
+        dst_sliding_windows(width, window, step, wl.begin.data(), wl.end.data(), count, &count);
+    for (uint32_t w = 0; w < count; ++w)
+        wl.names.push_back(std::to_string(w + 1));
+    return wl;
+}
+
+// --windows / --regions: per pair in canonical order and per window in the given order one line "id1, id2, window, start,
+// end, value": the value from the pair's DST_OUT_TALLY words in the window (dst_run_windows) and, for tn93, the two
+// records' base counts inside it (dst_window_base_counts), through dst_finalize and the long output's formatter.  Rows are
+// walked in ranges whose pair-windows stay within max_entries (at least one row each).
+void write_windows(const Run &run, const WindowList &wl, uint64_t max_entries)
+{
+    const bool square = run.square();
+    const Alignment &rows = run.rows(), &cols = run.cols();
+    const size_t W = run.tally_width(), nw = wl.begin.size();
+    run.header("sequence1\tsequence2\twindow\tstart\tend\tdistance\n");
+    if (nw == 0)
+        return;
+    std::vector<uint32_t> row_counts, col_counts;
+    if (run.measure == DST_TN93) {
+        row_counts.resize(nw * rows.n * 4);
+        run.gpu.check(dst_window_base_counts(run.gpu.h, 0, wl.begin.data(), wl.end.data(), (uint32_t)nw, row_counts.data(),
+                                             row_counts.size()),
+                      "window base counts");
+        if (!square) {
+            col_counts.resize(nw * cols.n * 4);
+            run.gpu.check(dst_window_base_counts(run.gpu.h, 1, wl.begin.data(), wl.end.data(), (uint32_t)nw, col_counts.data(),
+                                                 col_counts.size()),
+                          "window base counts");
+        }
+    }
+    const std::vector<uint32_t> &ccounts = square ? row_counts : col_counts;
+    auto pairs_of_row = [&](size_t i) -> uint64_t { return square ? rows.n - 1 - i : cols.n; };
+    std::vector<uint32_t> tallies;
+    LineWriter out(run.wr);
+    for (size_t rb = 0; rb < rows.n;) {
+        uint64_t P = pairs_of_row(rb);
+        size_t re = rb + 1;
+        while (re < rows.n && (P + pairs_of_row(re)) * nw <= max_entries)
+            P += pairs_of_row(re++);
+        if (P) {
+            tallies.resize((size_t)P * nw * W);
+            run.gpu.check(dst_run_windows_host(run.gpu.h, run.measure, square ? 1 : 0, 0, 1, rb, re, wl.begin.data(), wl.end.data(),
+                                               (uint32_t)nw, DST_OUT_TALLY, tallies.data(), tallies.size() * sizeof(uint32_t)),
+                          "windows");
+        }
+        uint64_t p = 0;
+        for (size_t i = rb; i < re; ++i)
+            for (size_t j = square ? i + 1 : 0; j < cols.n; ++j, ++p)
+                for (size_t w = 0; w < nw; ++w) {
+                    double f = 0;
+                    int64_t iv = 0;
+                    dst_finalize(run.measure, &tallies[((size_t)w * P + p) * W],
+                                 row_counts.empty() ? nullptr : &row_counts[(w * rows.n + i) * 4],
+                                 ccounts.empty() ? nullptr : &ccounts[(w * cols.n + j) * 4], &f, &iv);
+                    out.put(rows.ids[i]);
+                    out.put('\t');
+                    out.put(cols.ids[j]);
+                    out.put('\t');
+                    out.put(wl.names[w]);
+                    out.put('\t');
+                    out.number(wl.begin[w] + 1);
+                    out.put('\t');
+                    out.number(wl.end[w]);
+                    out.put('\t');
+                    out.distance(run.measure, f, iv);
+                    out.end_line();
+                }
+        rb = re;
+    }
+    out.finish();
+}
+
 }  // namespace

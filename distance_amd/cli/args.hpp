@@ -91,6 +91,16 @@ void print_help()
         "tree): a fourth field per line, the sites that separate the two "
         "records as a comma-separated list of X<pos>Y (pos 1-based, X the first record's IUPAC letter, Y the second's; '.' "
         "when there are none): the sites the measure counts as differences\n"
+        "      --windows <W>            Print every pair's distance per column window instead of over the whole width: windows "
+        "of W sites (an integer >= 1) starting every S sites, the last one cut at the alignment's end; a line per pair and "
+        "window, 'id1, id2, window number, start, end (1-based, inclusive), distance', the distance exactly what the long "
+        "output prints for the pair on the input cut to those columns. One input, or two (the records of the first "
+        "against the second). One GPU, no --stream and no other output mode\n"
+        "      --step <S>               The distance between the starts of consecutive windows (an integer >= 1) [default: W]. "
+        "Requires --windows\n"
+        "      --regions <FILE>         As --windows, for named column ranges: FILE has one 'name<TAB>start<TAB>end' line per "
+        "region (no header; positions 1-based and inclusive; at most 65536 regions); the window field of a line is the "
+        "region's name\n"
         "      --dendrogram <linkage>   Print the rooted hierarchical-clustering tree of the records as one Newick line instead "
         "of distances: linkage average (UPGMA), weighted (WPGMA) or complete. One input, one GPU, no --stream and no other "
         "output mode\n"
@@ -109,7 +119,8 @@ const char *kLicences =
 enum Flag {
     F_STREAM, F_MEASURE, F_OUTPUT, F_THREADS, F_BATCHSIZE, F_GPUS, F_DEVICES, F_SLAB_PAIRS, F_NEAREST, F_CLOSEST, F_CLOSEST_FOR,
     F_WITHIN, F_CLUSTERS, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS, F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX,
-    F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM, F_SELFTEST, F_REPRESENTATIVES, F_COUNT
+    F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM, F_SELFTEST, F_REPRESENTATIVES,
+    F_WINDOWS, F_STEP, F_REGIONS, F_COUNT
 };
 struct FlagDef {
     const char *shown;   // "--name <value>": its first word is the flag itself
@@ -127,11 +138,12 @@ const FlagDef kFlags[F_COUNT] = {
     {"--tree <method>", nullptr, false}, {"--bootstrap <B>", nullptr, false}, {"--seed <S>", nullptr, false},
     {"--mst", nullptr, false}, {"--sites", nullptr, false}, {"--dendrogram <linkage>", nullptr, false},
     {"--host-selftest <what>", nullptr, false}, {"--representatives <T>", nullptr, true},
+    {"--windows <W>", nullptr, true}, {"--step <S>", nullptr, true}, {"--regions <FILE>", nullptr, true},
 };
 
 // what the run prints, decided once by parse_args
 enum class Mode { Pairs, Stream, Closest, Within, Nearest, Clusters, MaxDistance, Summary, Histogram, Groups, Matrix, Tree, Mst,
-                  Dendrogram, Representatives };
+                  Dendrogram, Representatives, Windows };
 
 struct Args {
     bool has[F_COUNT] = {};               // the flag was given
@@ -159,6 +171,8 @@ struct Args {
     size_t bootstrap = 0;                 // --bootstrap B (0: none)
     size_t seed = 1;                      // --seed S
     int dendrogram = -1;                  // --dendrogram: DST_LINK_* (-1: none)
+    size_t windows = 0, step = 0;         // --windows W --step S (step 0: W)
+    std::string regions;                  // --regions FILE
     std::string selftest;
     size_t n_inputs() const { return flag_inputs.size() + pos_inputs.size(); }
     // the slab size an analysis is given: the library's own choice unless --slab-pairs was passed
@@ -235,7 +249,21 @@ struct Rule {
     bool one_gpu;
 };
 const std::vector<Flag> kNone;
+// everything --windows / --regions cannot go with: stream mode, every other output mode and every modifier of one
+const std::vector<Flag> kWindowRefuses = {
+    F_STREAM, F_NEAREST, F_CLOSEST, F_CLOSEST_FOR, F_WITHIN, F_CLUSTERS, F_REPRESENTATIVES, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS,
+    F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM};
+std::vector<Flag> after(Flag first, std::vector<Flag> rest)
+{
+    rest.insert(rest.begin(), first);
+    return rest;
+}
 const Rule kRules[] = {
+    // (before every older row: a command line with one of these three flags is judged here, and no other line's outcome
+    // changes; --windows names --regions, the one mode flag the list does not hold)
+    {F_STEP, Mode::Pairs, kNone, {F_WINDOWS}, "'--windows <W>'", TWO_OK, false},
+    {F_WINDOWS, Mode::Windows, after(F_REGIONS, kWindowRefuses), kNone, nullptr, TWO_OK, true},
+    {F_REGIONS, Mode::Windows, kWindowRefuses, kNone, nullptr, TWO_OK, true},
     // (first: every combination with it is refused here, so no other row's message changes)
     {F_REPRESENTATIVES, Mode::Representatives,
      {F_STREAM, F_NEAREST, F_CLOSEST, F_CLOSEST_FOR, F_WITHIN, F_CLUSTERS, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS, F_GROUPS_WITHIN,
@@ -359,7 +387,8 @@ Args parse_args(int argc, char **argv)
             while (a.flag_inputs.size() < 2 && k + 1 < argc && (argv[k + 1][0] != '-' || !std::strcmp(argv[k + 1], "-")))
                 a.flag_inputs.push_back(argv[++k]);
         } else if (text(F_STREAM, a.stream) || text(F_MEASURE, a.measure) || text(F_OUTPUT, a.output) ||
-                   text(F_GROUPS, a.groups) || count(F_THREADS, a.threads, 0, SIZE_MAX) ||
+                   text(F_GROUPS, a.groups) || text(F_REGIONS, a.regions) || count(F_WINDOWS, a.windows, 1, SIZE_MAX) ||
+                   count(F_STEP, a.step, 1, SIZE_MAX) || count(F_THREADS, a.threads, 0, SIZE_MAX) ||
                    count(F_BATCHSIZE, a.batchsize, 0, SIZE_MAX) || count(F_SEED, a.seed, 0, SIZE_MAX) ||
                    count(F_NEAREST, a.nearest, 1, 256) || count(F_CLOSEST, a.closest, 1, 256) ||
                    count(F_BINS, a.bins, 1, DST_SUMMARY_MAX_BINS) || count(F_BOOTSTRAP, a.bootstrap, 1, 10000) ||

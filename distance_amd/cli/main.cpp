@@ -155,6 +155,10 @@ int main(int argc, char **argv)
     GroupFile group_file;
     if (a.mode == Mode::Groups)
         group_file = read_group_file(a.groups);
+    // --regions: likewise
+    WindowList windows;
+    if (a.has[F_REGIONS])
+        windows = read_region_file(a.regions);
     std::vector<FILE *> files;
     if (inputs.empty())
         files.push_back(stdin);
@@ -184,6 +188,11 @@ int main(int argc, char **argv)
     std::vector<GroupLabels> group_labels;
     if (a.mode == Mode::Groups)
         group_labels = label_inputs(group_file, loaded);
+    // --windows / --regions: the windows over the width the inputs turned out to have
+    if (a.has[F_REGIONS])
+        check_regions(windows, loaded[0].width);
+    else if (a.mode == Mode::Windows)
+        windows = sliding_windows(loaded[0].width, a.windows, a.has[F_STEP] ? a.step : a.windows);
     Writer wr;
     if (a.has[F_OUTPUT]) {
         wr.fh = std::fopen(a.output.c_str(), "wb");
@@ -239,6 +248,7 @@ int main(int argc, char **argv)
     case Mode::Groups: write_groups(run, group_labels, a.has[F_GROUPS_WITHIN], a.groups_within, a.has[F_PER_RECORD]); break;
     case Mode::Histogram: write_histogram(run, a.histogram, (uint32_t)a.bins); break;
     case Mode::Nearest: write_nearest(run, (uint32_t)a.nearest); break;
+    case Mode::Windows: write_windows(run, windows, a.slab_pairs); break;
     case Mode::Matrix: {
         // tsv: an empty corner cell, then the column ids (the last input's records); phylip: the number of records
         std::string h = a.matrix == DST_MATRIX_PHYLIP ? std::to_string(loaded[0].n) : "";

@@ -166,6 +166,11 @@ struct dst_ctx {
     // host memory
     Grown<char> ps_batch, ps_window;
     Grown<char, true> ps_batch_host, ps_window_host;
+    // dst_run_windows / dst_window_base_counts: the window table on the device and in page-locked memory, and the per
+    // (window, record) base counts (tn93)
+    Grown<uint2> win_table;
+    Grown<uint2, true> win_table_host;
+    Grown<uint4> win_counts;
     Grown<> summary_work;   // dst_summary: the per-record counters and accumulators, the histogram and the totals
     // dst_group_summary: the labels, the cells and the per-record table; the labels' page-locked staging
     Grown<> group_work;
@@ -214,6 +219,10 @@ struct TwoSets {
 int two_sets(dst_ctx *ctx, bool square, int row_slot, int col_slot, TwoSets &out, bool same_len = true, bool count_32 = false);
 // the base planes a deferred upload left out, written before anything but the consensus path reads planes (dst_api.cpp)
 int ensure_planes(dst_ctx *ctx, DeviceSet &s, hipStream_t stream);
+// ... and the four derived planes of a set that was packed lean: what the dense kernels' measures read (dst_api.cpp)
+int ensure_derived(dst_ctx *ctx, DeviceSet &s, hipStream_t stream);
+// data another run's stream derived (lists, constants, counts, planes): `stream` waits for it on the device (dst_api.cpp)
+int order_after_prep(dst_ctx *ctx, hipStream_t stream);
 void free_set(DeviceSet &s);
 // forget the mark of a stream that is idle and about to be destroyed (dst_ctx::Mark; dst_api.cpp)
 void forget_stream(dst_ctx *ctx, hipStream_t stream);

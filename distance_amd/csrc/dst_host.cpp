@@ -556,6 +556,36 @@ int dst_partition_rect(uint64_t n_rows, int parts, uint64_t *bounds)
     return DST_OK;
 }
 
+// the windows of `--windows W --step S`: [k step, min(k step + width, len)), up to the first that ends at len
+int dst_sliding_windows(uint64_t len, uint64_t width, uint64_t step, uint64_t *begin, uint64_t *end, size_t cap, uint32_t *count)
+{
+    if (count)
+        *count = 0;
+    if (!count || width == 0 || step == 0 || (begin == nullptr) != (end == nullptr))
+        return DST_ERR_ARG;
+    if (len == 0)
+        return DST_OK;
+    // the last window is the first whose end reaches len: k step + width >= len
+    const uint64_t rest = len <= width ? 0 : len - width;
+    // ... or, with a step above the width, the last that still begins inside the alignment
+    const uint64_t k_last = std::min(rest / step + (rest % step ? 1 : 0), (len - 1) / step);
+    if (k_last >= DST_WINDOWS_MAX) {
+        *count = k_last >= 0xFFFFFFFFull ? 0xFFFFFFFFu : (uint32_t)(k_last + 1);   // (what it would take, saturated)
+        return DST_ERR_CAPACITY;
+    }
+    const uint32_t n = (uint32_t)(k_last + 1);
+    *count = n;
+    if (!begin)
+        return DST_OK;
+    if (cap < n)
+        return DST_ERR_CAPACITY;
+    for (uint32_t k = 0; k < n; ++k) {
+        begin[k] = (uint64_t)k * step;
+        end[k] = len - begin[k] <= width ? len : begin[k] + width;
+    }
+    return DST_OK;
+}
+
 int dst_shared_range(uint64_t n, int rank, int world, uint64_t *begin, uint64_t *end)
 {
     if (world < 1 || rank < 0 || rank >= world || !begin || !end)

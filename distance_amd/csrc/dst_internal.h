@@ -648,6 +648,22 @@ hipError_t launch_dg_rounds(const DgBuffers &b, uint64_t n, int linkage, hipStre
 hipError_t launch_boot_resample(const uint8_t *src, uint64_t pitch, uint8_t *out, uint64_t n, uint64_t len, uint64_t seed,
                                 uint32_t replicate, uint32_t *map, hipStream_t stream);
 
+// ---- per-window distances (dst_windows.hip: the kernels and dst_run_windows / dst_window_base_counts) -----------------
+struct WindowLaunch {
+    const DeviceSet *rows, *cols;
+    bool square;
+    uint64_t row_begin, row_end;   // rows of `rows`
+    uint64_t pairs;                // P: the pairs of the row range (an entry of window w lies at w * P + canonical index)
+    int out_kind;                  // DST_OUT_DISTANCE or DST_OUT_TALLY
+    void *d_out;
+    const uint2 *d_windows;        // [n_windows] {begin, end}
+    uint32_t n_windows;
+    const uint4 *q_counts, *t_counts;   // tn93 distances: [n_windows][rows.n] / [n_windows][cols.n] {A,T,G,C} inside the window
+};
+hipError_t launch_window_pairs(int measure, const WindowLaunch &wl, hipStream_t stream);
+// counts[w * set.n + record] = the record's {A,T,G,C}, counted by code, inside window w
+hipError_t launch_window_counts(const DeviceSet &set, const uint2 *d_windows, uint32_t n_windows, uint4 *counts, hipStream_t stream);
+
 // ---- host-only logic (dst_host.cpp) ----------------------------------------------------------
 int tally_width(int measure);
 bool measure_is_int(int measure);

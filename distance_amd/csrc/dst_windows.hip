@@ -1,0 +1,559 @@
+// dst_windows.hip — distances per column window (dst_run_windows, dst_window_base_counts): the dense pair
+// kernel's sweep (dst_kernels.hip) restricted to the 128-site chunks a window [begin, end) meets, with a site mask on
+// the at most two chunks the window's edges cut.
+//
+// Mapping (window_pair_kernel): one block = kWinRows row records x 256 column records x ONE window.  grid.x walks the
+// column tiles, grid.y the row tiles, grid.z the windows; y and z hold at most 65,535 each, so the launcher cuts both
+// (for_row_grids).  The lanes run along the column records: a lane's 16 bytes of a (plane, chunk) are contiguous with its
+// neighbours' (1 KiB per wave instruction), and stay in VGPRs for all the rows of the tile.  A row record's 16 bytes are
+// the same for the whole block: wave-uniform loads, which reach the kernel as scalar loads and SGPR operands.
+// Tallies live in VGPRs for the sweep; the epilogue is the dense kernel's (M::tallies, then the tally words, the int64, or
+// finalize_pair).  Every entry has one writer: plain vector stores.
+//
+// The mask rule.  n / n_high / raw count the sites whose base sets SHARE a member and subtract from `total`; so a site
+// outside the window is taken out of the counted word, and total = end - begin (never the chunks' span).  Zeroing a
+// record's planes instead would make its masked sites certain differences.  k80 / tn93 count known sites only: every
+// counted word derives from one that the mask went into.
+#include "dst_ctx.h"
+#include "dst_device.hpp"
+#include "dst_measures.hpp"
+
+namespace dst {
+namespace {
+
+constexpr int kWinRows = 8;          // row records of one block
+constexpr int kWinCols = 256;        // column records of one block: one per thread
+
+__device__ __forceinline__ uint32_t bits_below(uint32_t x) { return x >= 32u ? 0xFFFFFFFFu : (1u << x) - 1u; }
+
+// the sites of chunk c inside [begin, end), one bit per site (wave-uniform: SALU)
+__device__ __forceinline__ void window_mask(uint32_t c, uint32_t begin, uint32_t end, uint32_t (&m)[4])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        const uint64_t ws = (uint64_t)c * kChunkSites + 32u * k;   // the word's first site
+        const uint32_t lo = begin <= ws ? 0u : begin - ws >= 32u ? 32u : (uint32_t)(begin - ws);
+        const uint32_t hi = end <= ws ? 0u : end - ws >= 32u ? 32u : (uint32_t)(end - ws);
+        m[k] = bits_below(hi) & ~bits_below(lo);   // (lo >= hi: empty)
+    }
+}
+
+// M::step with the sites outside m left out of every counted word
+template <class M>
+struct Masked;
+template <>
+struct Masked<MNHigh> {
+    static __device__ __forceinline__ void step(uint32_t *a, const uint32_t *q, const uint32_t *t, uint32_t m)
+    {
+        bcnt_acc(a[0], share_bits(q, t) & m);
+    }
+};
+template <>
+struct Masked<MRaw> {
+    static __device__ __forceinline__ void step(uint32_t *a, const uint32_t *q, const uint32_t *t, uint32_t m)
+    {
+        const uint32_t share = share_bits(q, t) & m;
+        bcnt_acc(a[0], share);
+        bcnt_acc(a[1], bitop3<TT_AND3>(share, q[4], t[4]));
+    }
+};
+template <>
+struct Masked<MK80> {
+    static __device__ __forceinline__ void step(uint32_t *a, const uint32_t *q, const uint32_t *t, uint32_t m)
+    {
+        const uint32_t e1 = q[1] ^ t[1];
+        const uint32_t sc = bitop3<TT_A_AND_B_ANDN_C>(q[0] & m, t[0], e1);   // (q and m are scalars: the AND is SALU)
+        const uint32_t ts = bitop3<TT_A_AND_B_NE_C>(sc, q[2], t[2]);
+        const uint32_t tv = bitop3<TT_AND3>(q[3] & m, t[3], e1);
+        bcnt_acc(a[0], sc);
+        bcnt_acc(a[1], ts);
+        bcnt_acc(a[2], tv);
+    }
+};
+template <>
+struct Masked<MTN93> {
+    static __device__ __forceinline__ void step(uint32_t *a, const uint32_t *q, const uint32_t *t, uint32_t m)
+    {
+        const uint32_t bk = bitop3<TT_AND3>(q[0], t[0], m);
+        const uint32_t sc = bitop3<TT_A_AND_B_EQ_C>(bk, q[1], t[1]);
+        const uint32_t ts = bitop3<TT_A_AND_B_NE_C>(sc, q[2], t[2]);
+        const uint32_t p2 = ts & q[1];
+        bcnt_acc(a[0], bk);
+        bcnt_acc(a[1], sc);
+        bcnt_acc(a[2], ts);
+        bcnt_acc(a[3], p2);
+    }
+};
+
+__device__ __forceinline__ uint32_t word_of(const uint4 &v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
+
+// OUT: OUT_TALLY, OUT_INT, or the measure id whose f64 the epilogue writes (as pair_kernel)
+template <class M, int OUT>
+__global__ __launch_bounds__(kWinCols) void window_pair_kernel(
+    const uint4 *__restrict__ qpl, const uint4 *__restrict__ tpl, const uint2 *__restrict__ windows, void *__restrict__ out_v,
+    const uint4 *__restrict__ q_counts, const uint4 *__restrict__ t_counts, uint32_t nchunks, uint32_t q_npad, uint32_t t_npad,
+    uint32_t q_n, uint32_t n_cols, uint32_t row_begin, uint32_t row_end, uint32_t row0, uint32_t win0, uint64_t pairs,
+    uint64_t out_base, int square)
+{
+    constexpr int NP = M::NP, NC = M::NC, NT = M::NT;
+    constexpr int STAGE_WORDS = OUT >= 0 ? kWinRows * NT * kWinCols : 1;
+    __shared__ uint32_t stage[STAGE_WORDS];
+
+    const uint32_t i0 = row0 + blockIdx.y * kWinRows;   // (< row_end by the grid)
+    const uint32_t j0 = blockIdx.x * kWinCols;
+    if (square && j0 + (kWinCols - 1) <= i0)
+        return;   // every column of the tile is at or below its first row: no pair j > i
+    const uint32_t w = win0 + blockIdx.z;
+    const uint2 win = windows[w];
+    const uint32_t wb = win.x, we = win.y;
+    const uint32_t j = j0 + threadIdx.x;
+    const uint32_t jl = j < n_cols ? j : n_cols - 1;   // a lane past the last column reads the last one and stores nothing
+
+    uint32_t acc[kWinRows][NC];
+#pragma unroll
+    for (int r = 0; r < kWinRows; ++r)
+#pragma unroll
+        for (int k = 0; k < NC; ++k)
+            acc[r][k] = 0;
+
+    const size_t q_ps = (size_t)nchunks * q_npad, t_ps = (size_t)nchunks * t_npad;   // plane strides, in uint4
+    const uint4 *qbase = qpl + (size_t)M::P0 * q_ps;
+    const uint4 *tbase = tpl + (size_t)M::P0 * t_ps + jl;
+
+    if (we > wb) {
+        const uint32_t c_first = wb / kChunkSites, c_last = (we - 1u) / kChunkSites;
+#pragma unroll 1
+        for (uint32_t c = c_first; c <= c_last; ++c) {
+            uint4 tv[NP];
+#pragma unroll
+            for (int p = 0; p < NP; ++p)
+                tv[p] = tbase[(size_t)p * t_ps + (size_t)c * t_npad];
+            const bool whole = (uint64_t)c * kChunkSites >= wb && (uint64_t)c * kChunkSites + kChunkSites <= we;
+            if (whole) {
+#pragma unroll
+                for (int r = 0; r < kWinRows; ++r) {
+                    const uint32_t i = i0 + r < row_end ? i0 + r : row_end - 1u;   // (wave-uniform)
+                    uint4 qv[NP];
+#pragma unroll
+                    for (int p = 0; p < NP; ++p)
+                        qv[p] = qbase[(size_t)p * q_ps + (size_t)c * q_npad + i];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        uint32_t q[NP], t[NP];
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) {
+                            q[p] = word_of(qv[p], k);
+                            t[p] = word_of(tv[p], k);
+                        }
+                        M::step(acc[r], q, t);
+                    }
+                }
+            } else {
+                uint32_t m[4];
+                window_mask(c, wb, we, m);
+#pragma unroll
+                for (int r = 0; r < kWinRows; ++r) {
+                    const uint32_t i = i0 + r < row_end ? i0 + r : row_end - 1u;
+                    uint4 qv[NP];
+#pragma unroll
+                    for (int p = 0; p < NP; ++p)
+                        qv[p] = qbase[(size_t)p * q_ps + (size_t)c * q_npad + i];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        uint32_t q[NP], t[NP];
+#pragma unroll
+                        for (int p = 0; p < NP; ++p) {
+                            q[p] = word_of(qv[p], k);
+                            t[p] = word_of(tv[p], k);
+                        }
+                        Masked<M>::step(acc[r], q, t, m[k]);
+                    }
+                }
+            }
+        }
+    }
+
+    const uint32_t total = we - wb;
+    const uint64_t win_at = (uint64_t)w * pairs;
+    if constexpr (OUT < 0) {
+#pragma unroll
+        for (int r = 0; r < kWinRows; ++r) {
+            const uint32_t i = i0 + r;
+            if (i >= row_end)
+                break;
+            if (j < n_cols && (!square || j > i)) {
+                const uint64_t at = win_at + (square ? (tri_row_start(n_cols, i) - out_base) + (j - i - 1)
+                                                     : (uint64_t)(i - row_begin) * n_cols + j);
+                uint32_t o[NT];
+                M::tallies(acc[r], total, o);
+                if constexpr (OUT == OUT_INT) {
+                    static_cast<int64_t *>(out_v)[at] = (int64_t)o[0];
+                } else {
+#pragma unroll
+                    for (int k = 0; k < NT; ++k)
+                        static_cast<uint32_t *>(out_v)[at * NT + k] = o[k];
+                }
+            }
+        }
+    } else {
+        // the dense kernel's scheme: the lane's tallies go through a lane-private LDS slot, so that ONE copy of the
+        // finalisation runs in a rolled loop.  A lane only touches its own column: no barrier.
+#pragma unroll
+        for (int r = 0; r < kWinRows; ++r) {
+            uint32_t o[NT];
+            M::tallies(acc[r], total, o);
+#pragma unroll
+            for (int k = 0; k < NT; ++k)
+                stage[(r * NT + k) * kWinCols + threadIdx.x] = o[k];
+        }
+        double *out = static_cast<double *>(out_v);
+#pragma unroll 1
+        for (int r = 0; r < kWinRows; ++r) {
+            const uint32_t i = i0 + r;
+            if (i >= row_end)
+                break;
+            if (j < n_cols && (!square || j > i)) {
+                uint32_t o[NT];
+#pragma unroll
+                for (int k = 0; k < NT; ++k)
+                    o[k] = stage[(r * NT + k) * kWinCols + threadIdx.x];
+                uint4 qc = make_uint4(0, 0, 0, 0), tc = qc;
+                if constexpr (OUT == DST_TN93) {
+                    qc = q_counts[(uint64_t)w * q_n + i];
+                    tc = t_counts[(uint64_t)w * n_cols + j];
+                }
+                const uint64_t at = win_at + (square ? (tri_row_start(n_cols, i) - out_base) + (j - i - 1)
+                                                     : (uint64_t)(i - row_begin) * n_cols + j);
+                out[at] = finalize_pair<OUT>(o, qc, tc);
+            }
+        }
+    }
+}
+
+// {A,T,G,C} counted by code (a known base is K & its own plane, K from the four base planes as counts_kernel takes it)
+// inside every window: one thread per record (16 contiguous bytes per lane and plane), grid.y = the windows.
+__global__ __launch_bounds__(256) void window_counts_kernel(const uint4 *__restrict__ planes, const uint2 *__restrict__ windows,
+                                                            uint32_t n, uint32_t nchunks, uint32_t npad, uint32_t win0,
+                                                            uint4 *__restrict__ counts)
+{
+    const uint32_t s = blockIdx.x * 256u + threadIdx.x;
+    const uint32_t w = win0 + blockIdx.y;
+    if (s >= n)
+        return;
+    const uint2 win = windows[w];
+    const uint32_t wb = win.x, we = win.y;
+    const size_t ps = (size_t)nchunks * npad;
+    uint32_t cnt[4] = {0, 0, 0, 0};   // A, T, G, C
+    if (we > wb) {
+        const uint32_t c_first = wb / kChunkSites, c_last = (we - 1u) / kChunkSites;
+        for (uint32_t c = c_first; c <= c_last; ++c) {
+            const size_t at = (size_t)c * npad + s;
+            const uint4 A = planes[PL_A * ps + at], G = planes[PL_G * ps + at], C = planes[PL_C * ps + at], T = planes[PL_T * ps + at];
+            uint32_t m[4];
+            window_mask(c, wb, we, m);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t a = word_of(A, k), g = word_of(G, k), cc = word_of(C, k), t = word_of(T, k);
+                const uint32_t K = (a ^ g ^ cc ^ t) & ~((a & g) | (cc & t)) & m[k];   // exactly one base, inside the window
+                cnt[0] += (uint32_t)__builtin_popcount(K & a);
+                cnt[1] += (uint32_t)__builtin_popcount(K & t);
+                cnt[2] += (uint32_t)__builtin_popcount(K & g);
+                cnt[3] += (uint32_t)__builtin_popcount(K & cc);
+            }
+        }
+    }
+    counts[(uint64_t)w * n + s] = make_uint4(cnt[0], cnt[1], cnt[2], cnt[3]);
+}
+
+template <class M, int OUT>
+hipError_t launch_windows_one(const WindowLaunch &wl, hipStream_t stream)
+{
+    const uint64_t rows = wl.row_end - wl.row_begin;
+    const uint64_t row_tiles = (rows + kWinRows - 1) / kWinRows;
+    const unsigned col_tiles = (unsigned)((wl.cols->n + kWinCols - 1) / kWinCols);
+    // windows and row tiles each in grids of at most 65,535
+    return for_row_grids(0, wl.n_windows, [&](uint64_t win0, unsigned nwin) {
+        return for_row_grids(0, row_tiles, [&](uint64_t tile0, unsigned ntiles) {
+            hipLaunchKernelGGL((window_pair_kernel<M, OUT>), dim3(col_tiles, ntiles, nwin), dim3(kWinCols), 0, stream,
+                               wl.rows->planes, wl.cols->planes, wl.d_windows, wl.d_out, wl.q_counts, wl.t_counts,
+                               (uint32_t)wl.rows->nchunks, (uint32_t)wl.rows->npad, (uint32_t)wl.cols->npad, (uint32_t)wl.rows->n,
+                               (uint32_t)wl.cols->n, (uint32_t)wl.row_begin, (uint32_t)wl.row_end,
+                               (uint32_t)(wl.row_begin + tile0 * kWinRows), (uint32_t)win0, wl.pairs,
+                               wl.square ? square_row_start(wl.cols->n, wl.row_begin) : (uint64_t)0, wl.square ? 1 : 0);
+            return hipGetLastError();
+        });
+    });
+}
+
+}  // namespace
+
+hipError_t launch_window_pairs(int measure, const WindowLaunch &wl, hipStream_t stream)
+{
+    if (wl.n_windows == 0 || wl.n_windows > DST_WINDOWS_MAX || wl.row_end <= wl.row_begin || wl.row_end > wl.rows->n ||
+        wl.cols->n == 0 || wl.rows->n > 0xFFFFFFFFull || wl.cols->n > 0xFFFFFFFFull || wl.rows->nchunks != wl.cols->nchunks ||
+        wl.rows->len != wl.cols->len || wl.rows->len > 0xFFFFFFFFull)
+        return hipErrorInvalidValue;
+    const bool tally = wl.out_kind == DST_OUT_TALLY;
+    switch (measure) {
+    case DST_N:
+    case DST_N_HIGH:
+        return tally ? launch_windows_one<MNHigh, OUT_TALLY>(wl, stream) : launch_windows_one<MNHigh, OUT_INT>(wl, stream);
+    case DST_RAW:
+        return tally ? launch_windows_one<MRaw, OUT_TALLY>(wl, stream) : launch_windows_one<MRaw, DST_RAW>(wl, stream);
+    case DST_JC69:
+        return tally ? launch_windows_one<MRaw, OUT_TALLY>(wl, stream) : launch_windows_one<MRaw, DST_JC69>(wl, stream);
+    case DST_K80:
+        return tally ? launch_windows_one<MK80, OUT_TALLY>(wl, stream) : launch_windows_one<MK80, DST_K80>(wl, stream);
+    case DST_TN93:
+        return tally ? launch_windows_one<MTN93, OUT_TALLY>(wl, stream) : launch_windows_one<MTN93, DST_TN93>(wl, stream);
+    default: return hipErrorInvalidValue;
+    }
+}
+
+hipError_t launch_window_counts(const DeviceSet &set, const uint2 *d_windows, uint32_t n_windows, uint4 *counts, hipStream_t stream)
+{
+    if (n_windows == 0 || set.n == 0)
+        return hipSuccess;
+    if (n_windows > DST_WINDOWS_MAX || set.n > 0xFFFFFFFFull || set.len > 0xFFFFFFFFull)
+        return hipErrorInvalidValue;
+    return for_row_grids(0, n_windows, [&](uint64_t win0, unsigned nwin) {
+        hipLaunchKernelGGL(window_counts_kernel, dim3((unsigned)((set.n + 255) / 256), nwin), dim3(256), 0, stream, set.planes,
+                           d_windows, (uint32_t)set.n, (uint32_t)set.nchunks, (uint32_t)set.npad, (uint32_t)win0, counts);
+        return hipGetLastError();
+    });
+}
+
+// =============================================================================================
+// the calls
+// =============================================================================================
+namespace {
+
+const char *const kSharedRefusal = "a set uploaded with dst_upload_shared runs on the consensus path only (this rank holds "
+                                   "the planes of its own records)";
+
+int windows_valid(dst_ctx *ctx, const uint64_t *wb, const uint64_t *we, uint32_t n_windows, uint64_t len)
+{
+    for (uint32_t w = 0; w < n_windows; ++w)
+        if (wb[w] > we[w] || we[w] > len) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "window %u [%llu, %llu) is not a column range of an alignment of %llu sites", w,
+                          (unsigned long long)wb[w], (unsigned long long)we[w], (unsigned long long)len);
+            return fail(ctx, DST_ERR_ARG, msg);
+        }
+    return DST_OK;
+}
+
+int grow_or_nomem(dst_ctx *ctx, GrownBase &buf, size_t want, const char *what)
+{
+    const int rc = buf.grow(ctx, want);
+    if (rc == DST_ERR_NOMEM)
+        return fail(ctx, DST_ERR_NOMEM, std::string("windows: cannot allocate ") + std::to_string(want) + " bytes for " + what);
+    return rc;
+}
+
+// the window table on the device, by way of its page-locked copy (the caller has waited for every earlier reader)
+int upload_windows(dst_ctx *ctx, const uint64_t *wb, const uint64_t *we, uint32_t n_windows, hipStream_t stream)
+{
+    const size_t bytes = (size_t)n_windows * sizeof(uint2);
+    if (int rc = grow_or_nomem(ctx, ctx->win_table, bytes, "the window table"))
+        return rc;
+    if (ctx->win_table_host.bytes < bytes) {
+        const int rc = ctx->win_table_host.grow(ctx, bytes, "windows");
+        if (rc)
+            return rc;
+    }
+    uint2 *h = ctx->win_table_host;
+    for (uint32_t w = 0; w < n_windows; ++w)
+        h[w] = make_uint2((uint32_t)wb[w], (uint32_t)we[w]);
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->win_table, h, bytes, hipMemcpyHostToDevice, stream));
+    return DST_OK;
+}
+
+// what both forms of dst_run_windows check, in the documented order; *bytes = the output's size (0: nothing to do)
+int windows_args(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, uint64_t rb, uint64_t re, const uint64_t *wb,
+                 const uint64_t *we, uint32_t n_windows, int out_kind, const void *out, size_t cap, TwoSets &ts, uint64_t &pairs,
+                 size_t &bytes)
+{
+    bytes = 0;
+    pairs = 0;
+    if (n_windows > DST_WINDOWS_MAX)
+        return fail(ctx, DST_ERR_ARG, "more than DST_WINDOWS_MAX (65,536) windows");
+    if (n_windows && (!wb || !we))
+        return fail(ctx, DST_ERR_ARG, "null pointer");
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (out_kind == DST_OUT_TALLY16)
+        return fail(ctx, DST_ERR_ARG, "dst_run_windows writes DST_OUT_DISTANCE or DST_OUT_TALLY (no DST_OUT_TALLY16)");
+    if (out_kind != DST_OUT_DISTANCE && out_kind != DST_OUT_TALLY)
+        return fail(ctx, DST_ERR_ARG, "unknown output kind");
+    if (int rc = two_sets(ctx, square != 0, row_slot, col_slot, ts))
+        return rc;
+    const DeviceSet &rows = *ts.rows, &cols = *ts.cols;
+    if (rows.partial || cols.partial)
+        return fail(ctx, DST_ERR_STATE, kSharedRefusal);
+    if (rows.len >= ((uint64_t)1 << 32))
+        return fail(ctx, DST_ERR_ARG, "alignments of 2^32 sites or more are beyond dst_run_windows");
+    if (int rc = windows_valid(ctx, wb, we, n_windows, rows.len))
+        return rc;
+    if (rb > re || re > rows.n)
+        return fail(ctx, DST_ERR_ARG, "row range out of bounds");
+    if (rows.n >= 0xFFFFFFFFull || cols.n >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    pairs = pairs_in_rows(square != 0, cols.n, rb, re);
+    if (n_windows == 0 || pairs == 0)
+        return DST_OK;
+    const unsigned __int128 need = (unsigned __int128)n_windows * dst_out_bytes(measure, out_kind, pairs);
+    if (need > (unsigned __int128)cap)
+        return fail(ctx, DST_ERR_CAPACITY, "output buffer too small for the requested rows and windows");
+    if (!out)
+        return fail(ctx, DST_ERR_ARG, "null output pointer");
+    bytes = (size_t)need;
+    return DST_OK;
+}
+
+int windows_run(dst_ctx *ctx, int measure, const TwoSets &ts, bool square, uint64_t rb, uint64_t re, uint64_t pairs,
+                const uint64_t *wb, const uint64_t *we, uint32_t n_windows, int out_kind, void *d_out, hipStream_t stream)
+{
+    DeviceSet &rows = *ts.rows, &cols = *ts.cols;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    // the window and count tables are the context's: nothing queued earlier may still read them
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if (stream != ctx->stream)
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (int rc = order_after_prep(ctx, stream))
+        return rc;
+    int rc = ensure_derived(ctx, cols, stream);
+    if (!rc && &rows != &cols)
+        rc = ensure_derived(ctx, rows, stream);
+    if (!rc)
+        rc = upload_windows(ctx, wb, we, n_windows, stream);
+    if (rc)
+        return rc;
+    WindowLaunch wl{};
+    wl.rows = &rows;
+    wl.cols = &cols;
+    wl.square = square;
+    wl.row_begin = rb;
+    wl.row_end = re;
+    wl.pairs = pairs;
+    wl.out_kind = out_kind;
+    wl.d_out = d_out;
+    wl.d_windows = ctx->win_table;
+    wl.n_windows = n_windows;
+    if (measure == DST_TN93 && out_kind == DST_OUT_DISTANCE) {
+        const size_t per_row = (size_t)n_windows * rows.n, per_col = &rows != &cols ? (size_t)n_windows * cols.n : 0;
+        if ((rc = grow_or_nomem(ctx, ctx->win_counts, (per_row + per_col) * sizeof(uint4), "tn93's per-window base counts")))
+            return rc;
+        uint4 *q = ctx->win_counts, *t = per_col ? q + per_row : q;
+        HIP_TRY(ctx, launch_window_counts(rows, wl.d_windows, n_windows, q, stream));
+        if (per_col)
+            HIP_TRY(ctx, launch_window_counts(cols, wl.d_windows, n_windows, t, stream));
+        wl.q_counts = q;
+        wl.t_counts = t;
+    }
+    HIP_TRY(ctx, launch_window_pairs(measure, wl, stream));
+    return DST_OK;
+}
+
+}  // namespace
+}  // namespace dst
+
+extern "C" {
+
+int dst_run_windows(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, uint64_t row_begin, uint64_t row_end,
+                    const uint64_t *win_begin, const uint64_t *win_end, uint32_t n_windows, int out_kind, void *d_out,
+                    size_t out_capacity_bytes, void *stream_v)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    TwoSets ts;
+    uint64_t pairs = 0;
+    size_t bytes = 0;
+    if (int rc = windows_args(ctx, measure, square, row_slot, col_slot, row_begin, row_end, win_begin, win_end, n_windows, out_kind,
+                              d_out, out_capacity_bytes, ts, pairs, bytes))
+        return rc;
+    if (bytes == 0)
+        return DST_OK;
+    hipStream_t stream = stream_v ? (hipStream_t)stream_v : ctx->stream;
+    if (int rc = windows_run(ctx, measure, ts, square != 0, row_begin, row_end, pairs, win_begin, win_end, n_windows, out_kind,
+                             d_out, stream))
+        return rc;
+    if (!stream_v)
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+    return DST_OK;
+}
+
+int dst_run_windows_host(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, uint64_t row_begin, uint64_t row_end,
+                         const uint64_t *win_begin, const uint64_t *win_end, uint32_t n_windows, int out_kind, void *h_out,
+                         size_t out_capacity_bytes)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    TwoSets ts;
+    uint64_t pairs = 0;
+    size_t bytes = 0;
+    if (int rc = windows_args(ctx, measure, square, row_slot, col_slot, row_begin, row_end, win_begin, win_end, n_windows, out_kind,
+                              h_out, out_capacity_bytes, ts, pairs, bytes))
+        return rc;
+    if (bytes == 0)
+        return DST_OK;
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (the staging buffer's earlier readers)
+    if (int rc = ctx->host_out.grow(ctx, bytes))
+        return rc;
+    if (int rc = windows_run(ctx, measure, ts, square != 0, row_begin, row_end, pairs, win_begin, win_end, n_windows, out_kind,
+                             ctx->host_out, ctx->stream))
+        return rc;
+    HIP_TRY(ctx, hipMemcpyAsync(h_out, ctx->host_out, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return DST_OK;
+}
+
+int dst_window_base_counts(dst_ctx *ctx, int slot, const uint64_t *win_begin, const uint64_t *win_end, uint32_t n_windows,
+                           uint32_t *counts, size_t cap_entries)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (n_windows > DST_WINDOWS_MAX)
+        return fail(ctx, DST_ERR_ARG, "more than DST_WINDOWS_MAX (65,536) windows");
+    if (n_windows && (!win_begin || !win_end))
+        return fail(ctx, DST_ERR_ARG, "null pointer");
+    if (slot < 0 || slot > 1)
+        return fail(ctx, DST_ERR_ARG, "slot must be 0 or 1");
+    DeviceSet &s = ctx->set[slot];
+    if (!s.loaded)
+        return fail(ctx, DST_ERR_STATE, "set not uploaded");
+    if (s.partial)
+        return fail(ctx, DST_ERR_STATE, kSharedRefusal);
+    if (s.len >= ((uint64_t)1 << 32))
+        return fail(ctx, DST_ERR_ARG, "alignments of 2^32 sites or more are beyond dst_window_base_counts");
+    if (s.n >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    if (int rc = windows_valid(ctx, win_begin, win_end, n_windows, s.len))
+        return rc;
+    const unsigned __int128 entries = (unsigned __int128)n_windows * s.n * 4;
+    if (entries == 0)
+        return DST_OK;
+    if (entries > (unsigned __int128)cap_entries)
+        return fail(ctx, DST_ERR_CAPACITY, "counts buffer too small: n_windows x n x 4 entries");
+    if (!counts)
+        return fail(ctx, DST_ERR_ARG, "null pointer");
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    hipStream_t stream = ctx->stream;
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    if (int rc = order_after_prep(ctx, stream))
+        return rc;
+    int rc = ensure_planes(ctx, s, stream);
+    if (!rc)
+        rc = upload_windows(ctx, win_begin, win_end, n_windows, stream);
+    if (!rc)
+        rc = grow_or_nomem(ctx, ctx->win_counts, (size_t)entries * sizeof(uint32_t), "the per-window base counts");
+    if (rc)
+        return rc;
+    HIP_TRY(ctx, launch_window_counts(s, ctx->win_table, n_windows, ctx->win_counts, stream));
+    HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->win_counts, (size_t)entries * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    return DST_OK;
+}
+
+}  // extern "C"

@@ -61,6 +61,37 @@ def partition_rect(n_rows: int, parts: int) -> list[int]:
     return [int(x) for x in b]
 
 
+def sliding_windows(length: int, width: int, step: int) -> np.ndarray:
+    """The (k, 2) windows [begin, end) of `--windows width --step step` over `length` columns (dst_sliding_windows)."""
+    count = C.c_uint32()
+    rc = load().dst_sliding_windows(length, width, step, None, None, 0, C.byref(count))
+    if rc:
+        raise DistanceError(rc, f"dst_sliding_windows: {int(count.value)} windows")
+    k = int(count.value)
+    begin, end = np.zeros(max(k, 1), np.uint64), np.zeros(max(k, 1), np.uint64)
+    rc = load().dst_sliding_windows(length, width, step, begin.ctypes.data, end.ctypes.data, k, C.byref(count))
+    if rc:
+        raise DistanceError(rc, "dst_sliding_windows")
+    return np.stack([begin[:k], end[:k]], axis=1)
+
+
+def _window_arrays(windows):
+    w = np.asarray(windows)
+    if w.size == 0:
+        w = np.zeros((0, 2), np.uint64)
+    if w.ndim != 2 or w.shape[1] != 2:
+        raise ValueError("windows must be an (n_windows, 2) array of [begin, end)")
+    if w.dtype.kind not in "iu":
+        raise ValueError("windows must be integers")
+    if w.dtype.kind == "i" and w.size and int(w.min()) < 0:
+        raise ValueError("windows must not be negative")
+    begin = np.ascontiguousarray(w[:, 0], np.uint64)
+    end = np.ascontiguousarray(w[:, 1], np.uint64)
+    if begin.size == 0:   # (never a NULL array, also for an empty list)
+        return np.zeros(1, np.uint64), np.zeros(1, np.uint64), 0
+    return begin, end, int(begin.size)
+
+
 def shared_range(n: int, rank: int, world: int) -> tuple[int, int]:
     """The records rank `rank` of `world` packs and lists in a shared upload (dst_shared_range)."""
     b, e = C.c_uint64(), C.c_uint64()
@@ -574,6 +605,37 @@ class Engine:
                                              n_pairs, offsets.ctypes.data, sites.ctypes.data, bases.ctypes.data, cap,
                                              C.byref(total)))
         return offsets, sites[:int(total.value)], bases[:int(total.value)]
+
+    def run_windows(self, measure, windows, square: bool = True, row_slot: int = 0, col_slot: int = 1, row_begin: int = 0,
+                    row_end: int | None = None, tallies: bool = False) -> np.ndarray:
+        """Per column window [begin, end) of `windows` ((n_windows, 2) integers) what run_square / run_rect gives for rows
+        [row_begin, row_end) on the sets cut to those columns (dst_run_windows): (n_windows, P) int64 / f64 in the
+        canonical order of the range, or (n_windows, P, width) uint32 tallies."""
+        m = _measure_id(measure)
+        begin, end, nw = _window_arrays(windows)
+        n_rows, _ = self.set_info(0 if square else row_slot)
+        n_cols, _ = self.set_info(0 if square else col_slot)
+        row_end = n_rows if row_end is None else row_end
+        if row_end <= row_begin:
+            pairs = 0
+        elif square:
+            pairs = square_row_start(n_cols, min(row_end, n_cols)) - square_row_start(n_cols, min(row_begin, n_cols))
+        else:
+            pairs = (row_end - row_begin) * n_cols
+        kind = OUT_TALLY if tallies else OUT_DISTANCE
+        out = self._alloc(m, kind, nw * pairs)
+        self._check(self._lib.dst_run_windows_host(self._h, m, int(square), row_slot, col_slot, row_begin, row_end,
+                                                   begin.ctypes.data, end.ctypes.data, nw, kind, out.ctypes.data, out.nbytes))
+        return out.reshape((nw, pairs) + out.shape[1:])
+
+    def window_base_counts(self, slot: int, windows) -> np.ndarray:
+        """(n_windows, n, 4) {A,T,G,C} of every record of `slot`, counted by code inside every window."""
+        begin, end, nw = _window_arrays(windows)
+        n, _ = self.set_info(slot)
+        out = np.zeros((nw, n, 4), np.uint32)
+        self._check(self._lib.dst_window_base_counts(self._h, slot, begin.ctypes.data, end.ctypes.data, nw, out.ctypes.data,
+                                                     out.size))
+        return out
 
     def summary(self, measure, threshold: float = 0.0, square: bool = True, row_slot: int = 0, col_slot: int = 1,
                 max_pairs: int = 0, bins: int = 0, width: float = 1.0, per_record: bool = True) -> dict:

@@ -582,6 +582,56 @@ int dst_links(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
 int dst_pair_sites(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
                    const uint32_t *row, const uint32_t *col, uint64_t n_pairs,
                    uint64_t *offsets, uint32_t *sites, uint8_t *bases, size_t cap_entries, uint64_t *total);
+/* ---- distances per column window ------------------------------------------------------------------- */
+/* Distances ALONG the alignment (recombination scans: a query against a panel in windows of 500-1,000 sites sliding by
+ * 100-200; per-gene or per-region distances; the genome without its masked ends), from the bit-planes the GPU already
+ * holds: no cut, upload and run per window.  The definition is fixed to the bit.
+ *   window   a half-open column range [begin, end), 0 <= begin <= end <= len.  Windows may overlap, repeat, be empty and
+ *            come in any order; 1 <= n_windows <= DST_WINDOWS_MAX.
+ *   restriction of a set to a window: the set with every record cut to those columns, as dst_upload(..., base_counts =
+ *            NULL) would hold it — tn93's {A,T,G,C} counts are counted by code, per window.
+ *   result of window w: bitwise what dst_run_square / dst_run_rect returns for the same row range and out_kind on the
+ *            restricted sets.  Tallies are the exact integers; DST_OUT_DISTANCE payloads come from the same device
+ *            finalisation as the pair kernels' epilogue, and since every path is bit-identical the result does not depend
+ *            on the path.  An empty window: all tallies and base counts zero, n / n_high give 0, the f64 measures what that
+ *            finalisation gives for zeros (NaN for raw).
+ *   layout   out[w * P + p]: P = the pairs of the row range (square: i < j row-major over rows [row_begin, row_end);
+ *            rectangle: (row_end - row_begin) x n_col), p = the canonical index exactly as dst_run_square / dst_run_rect
+ *            lay the range out, an entry dst_out_bytes(measure, out_kind, 1) bytes.  out_kind is DST_OUT_DISTANCE or
+ *            DST_OUT_TALLY (DST_OUT_TALLY16: DST_ERR_ARG).  DST_OUT_TALLY + dst_window_base_counts + dst_finalize gives
+ *            the reference's bits for the restricted alignment.
+ * The sets are resolved as in dst_nearest (square != 0: slot 0 against itself; else two different slots): a bad slot, equal
+ * slots, a set not uploaded, different widths fail with its messages.  DST_ERR_ARG: a NULL ctx, window array or output; an
+ * unknown measure or out_kind; n_windows above the maximum; a window with begin > end or end > len (the message names the
+ * first); row_begin > row_end or row_end > n; len >= 2^32.  n_windows == 0 or an empty row range: DST_OK, nothing written.
+ * DST_ERR_CAPACITY: n_windows x dst_out_bytes(measure, out_kind, P) exceeds the capacity (nothing written).
+ * DST_ERR_STATE: a set came from dst_upload_shared (it holds no planes: the dense kernels' refusal).  DST_ERR_NOMEM, with
+ * the byte count, when the window table or tn93's count table (n_windows x records x 16 bytes per set) does not fit.
+ * A set with deferred planes gets them first, as for any plane reader; slots, the path choice, dst_last_path,
+ * dst_last_launch and later results are untouched.  stream == NULL: the context's stream, and the call returns when the
+ * results are there; else the work is queued on that stream after a wait for it (the window table is the context's: one
+ * call at a time per context).  Work ~ P x the chunks (128 sites) the windows meet.  Single GPU, loaded sets only. */
+#define DST_WINDOWS_MAX 65536u
+int dst_run_windows(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
+                    uint64_t row_begin, uint64_t row_end,
+                    const uint64_t *win_begin, const uint64_t *win_end, uint32_t n_windows,
+                    int out_kind, void *d_out, size_t out_capacity_bytes, void *stream);
+/* the same into host memory (synchronous, through the context's staging buffer) */
+int dst_run_windows_host(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
+                         uint64_t row_begin, uint64_t row_end,
+                         const uint64_t *win_begin, const uint64_t *win_end, uint32_t n_windows,
+                         int out_kind, void *h_out, size_t out_capacity_bytes);
+/* per (window, record) the {A,T,G,C} counted by code inside the window: counts[(w * n + record) * 4 ..], host memory,
+ * cap_entries >= n_windows x n x 4 uint32 (else DST_ERR_CAPACITY).  Errors as above. */
+int dst_window_base_counts(dst_ctx *ctx, int slot, const uint64_t *win_begin, const uint64_t *win_end,
+                           uint32_t n_windows, uint32_t *counts, size_t cap_entries);
+/* Pure host code: the windows of `distance --windows W --step S`.  begin_k = k step, end_k = min(begin_k + width, len), for
+ * k = 0, 1, ... up to the first k whose end_k == len (no window is a subset of its predecessor) — with a step above the
+ * width, which leaves columns between windows out, also no further than the last k with begin_k < len; len == 0: no window.
+ * begin == NULL and end == NULL: *count only.  width == 0, step == 0, a NULL count or exactly one NULL array: DST_ERR_ARG.
+ * More than DST_WINDOWS_MAX windows, or more than cap: DST_ERR_CAPACITY with *count set (saturated at 2^32-1). */
+int dst_sliding_windows(uint64_t len, uint64_t width, uint64_t step, uint64_t *begin, uint64_t *end,
+                        size_t cap, uint32_t *count);
 /* ---- per-record and histogram summaries ---------------------------------------------------------- */
 /* What the distances of a set look like, computed next to the values on the GPU: the histogram of the pairwise distances
  * (from which a threshold is chosen) and, per record, how many records lie within `threshold` of it (its degree in the
