@@ -142,6 +142,8 @@ _SIGS = {
     "dst_run_windows_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint32,
                                        C.c_int, _vp, C.c_size_t]),
     "dst_window_base_counts": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_size_t]),
+    "dst_nearest_windows": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint32,
+                                      C.c_uint32, C.c_uint64, _vp, _vp, _vp, C.c_size_t, _u32p]),
     "dst_sliding_windows": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, C.c_size_t, _u32p]),
     "dst_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint32, C.c_double, _vp, _vp,
                               _vp, _vp, C.c_size_t, _vp]),

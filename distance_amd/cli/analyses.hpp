@@ -681,4 +681,75 @@ void write_windows(const Run &run, const WindowList &wl, uint64_t max_entries)
     out.finish();
 }
 
+// --window-nearest K: per record of the first input in input order and per window in the given order the K nearest
+// records of the other side (dst_nearest_windows), each as the line the plain --windows / --regions run prints for that pair
+// and window: the value from the entry's DST_OUT_TALLY words and, for tn93, the two records' base counts inside the window,
+// through dst_finalize and the long output's formatter.  A square run's neighbour j < i is the canonical pair (j, i): the
+// two ids and the two records' counts change places.  Rows are walked in ranges of at most 2^24 result entries (at least
+// one row each); max_entries is the library's device slab.
+void write_window_nearest(const Run &run, const WindowList &wl, uint32_t k, uint64_t max_entries)
+{
+    const bool square = run.square();
+    const Alignment &rows = run.rows(), &cols = run.cols();
+    const size_t W = run.tally_width(), nw = wl.begin.size();
+    run.header("sequence1\tsequence2\twindow\tstart\tend\tdistance\n");
+    if (nw == 0 || rows.n == 0)
+        return;
+    std::vector<uint32_t> row_counts, col_counts;
+    if (run.measure == DST_TN93) {
+        row_counts.resize(nw * rows.n * 4);
+        run.gpu.check(dst_window_base_counts(run.gpu.h, 0, wl.begin.data(), wl.end.data(), (uint32_t)nw, row_counts.data(),
+                                             row_counts.size()),
+                      "window base counts");
+        if (!square) {
+            col_counts.resize(nw * cols.n * 4);
+            run.gpu.check(dst_window_base_counts(run.gpu.h, 1, wl.begin.data(), wl.end.data(), (uint32_t)nw, col_counts.data(),
+                                                 col_counts.size()),
+                          "window base counts");
+        }
+    }
+    const std::vector<uint32_t> &ccounts = square ? row_counts : col_counts;
+    const size_t candidates = square ? cols.n - 1 : cols.n;
+    const size_t ku = std::min<size_t>(k, candidates);
+    if (ku == 0)
+        return;
+    const size_t rows_per_call = std::max<size_t>(((size_t)1 << 24) / (nw * ku), 1);
+    std::vector<uint32_t> index, tallies;
+    LineWriter out(run.wr);
+    for (size_t rb = 0; rb < rows.n; rb += rows_per_call) {
+        const size_t re = std::min(rows.n, rb + rows_per_call), entries = (re - rb) * nw * ku;
+        index.resize(entries);
+        tallies.resize(entries * W);
+        uint32_t k_used = 0;
+        run.gpu.check(dst_nearest_windows(run.gpu.h, run.measure, square ? 1 : 0, 0, 1, rb, re, wl.begin.data(), wl.end.data(),
+                                          (uint32_t)nw, k, max_entries, index.data(), tallies.data(), nullptr, entries, &k_used),
+                      "window nearest");
+        size_t e = 0;
+        for (size_t i = rb; i < re; ++i)
+            for (size_t w = 0; w < nw; ++w)
+                for (size_t r = 0; r < ku; ++r, ++e) {
+                    const size_t j = index[e];
+                    const bool swapped = square && j < i;   // the canonical pair comes first record first
+                    const uint32_t *ic = row_counts.empty() ? nullptr : &row_counts[(w * rows.n + i) * 4];
+                    const uint32_t *jc = ccounts.empty() ? nullptr : &ccounts[(w * cols.n + j) * 4];
+                    double f = 0;
+                    int64_t iv = 0;
+                    dst_finalize(run.measure, &tallies[e * W], swapped ? jc : ic, swapped ? ic : jc, &f, &iv);
+                    out.put(swapped ? cols.ids[j] : rows.ids[i]);
+                    out.put('\t');
+                    out.put(swapped ? rows.ids[i] : cols.ids[j]);
+                    out.put('\t');
+                    out.put(wl.names[w]);
+                    out.put('\t');
+                    out.number(wl.begin[w] + 1);
+                    out.put('\t');
+                    out.number(wl.end[w]);
+                    out.put('\t');
+                    out.distance(run.measure, f, iv);
+                    out.end_line();
+                }
+    }
+    out.finish();
+}
+
 }  // namespace

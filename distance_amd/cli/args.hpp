@@ -101,6 +101,10 @@ void print_help()
         "      --regions <FILE>         As --windows, for named column ranges: FILE has one 'name<TAB>start<TAB>end' line per "
         "region (no header; positions 1-based and inclusive; at most 65536 regions); the window field of a line is the "
         "region's name\n"
+        "      --window-nearest <K>     With --windows or --regions: print only the K (1-256) nearest records of every record "
+        "of the first input in every window (of the same file with one input, of the second file with two): per record and "
+        "window the K lines of the plain --windows / --regions run with the smallest distance, nearest first, ties in input "
+        "order\n"
         "      --dendrogram <linkage>   Print the rooted hierarchical-clustering tree of the records as one Newick line instead "
         "of distances: linkage average (UPGMA), weighted (WPGMA) or complete. One input, one GPU, no --stream and no other "
         "output mode\n"
@@ -120,7 +124,7 @@ enum Flag {
     F_STREAM, F_MEASURE, F_OUTPUT, F_THREADS, F_BATCHSIZE, F_GPUS, F_DEVICES, F_SLAB_PAIRS, F_NEAREST, F_CLOSEST, F_CLOSEST_FOR,
     F_WITHIN, F_CLUSTERS, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS, F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX,
     F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM, F_SELFTEST, F_REPRESENTATIVES,
-    F_WINDOWS, F_STEP, F_REGIONS, F_COUNT
+    F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_COUNT
 };
 struct FlagDef {
     const char *shown;   // "--name <value>": its first word is the flag itself
@@ -139,6 +143,7 @@ const FlagDef kFlags[F_COUNT] = {
     {"--mst", nullptr, false}, {"--sites", nullptr, false}, {"--dendrogram <linkage>", nullptr, false},
     {"--host-selftest <what>", nullptr, false}, {"--representatives <T>", nullptr, true},
     {"--windows <W>", nullptr, true}, {"--step <S>", nullptr, true}, {"--regions <FILE>", nullptr, true},
+    {"--window-nearest <K>", nullptr, true},
 };
 
 // what the run prints, decided once by parse_args
@@ -173,6 +178,7 @@ struct Args {
     int dendrogram = -1;                  // --dendrogram: DST_LINK_* (-1: none)
     size_t windows = 0, step = 0;         // --windows W --step S (step 0: W)
     std::string regions;                  // --regions FILE
+    size_t window_nearest = 0;            // --window-nearest K (0: every pair)
     std::string selftest;
     size_t n_inputs() const { return flag_inputs.size() + pos_inputs.size(); }
     // the slab size an analysis is given: the library's own choice unless --slab-pairs was passed
@@ -259,6 +265,8 @@ std::vector<Flag> after(Flag first, std::vector<Flag> rest)
     return rest;
 }
 const Rule kRules[] = {
+    // (before every other row: a command line with --window-nearest is judged here first, and no other line's outcome changes)
+    {F_WINDOW_NEAREST, Mode::Pairs, kWindowRefuses, {F_WINDOWS, F_REGIONS}, "'--windows <W>' or '--regions <FILE>'", TWO_OK, true},
     // (before every older row: a command line with one of these three flags is judged here, and no other line's outcome
     // changes; --windows names --regions, the one mode flag the list does not hold)
     {F_STEP, Mode::Pairs, kNone, {F_WINDOWS}, "'--windows <W>'", TWO_OK, false},
@@ -391,6 +399,7 @@ Args parse_args(int argc, char **argv)
                    count(F_STEP, a.step, 1, SIZE_MAX) || count(F_THREADS, a.threads, 0, SIZE_MAX) ||
                    count(F_BATCHSIZE, a.batchsize, 0, SIZE_MAX) || count(F_SEED, a.seed, 0, SIZE_MAX) ||
                    count(F_NEAREST, a.nearest, 1, 256) || count(F_CLOSEST, a.closest, 1, 256) ||
+                   count(F_WINDOW_NEAREST, a.window_nearest, 1, 256) ||
                    count(F_BINS, a.bins, 1, DST_SUMMARY_MAX_BINS) || count(F_BOOTSTRAP, a.bootstrap, 1, 10000) ||
                    threshold(F_CLUSTERS, a.clusters) || threshold(F_REPRESENTATIVES, a.representatives) || threshold(F_MAX_DISTANCE, a.max_distance) ||
                    threshold(F_WITHIN, a.within) || threshold(F_SUMMARY, a.summary) ||

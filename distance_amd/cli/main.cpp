@@ -248,7 +248,12 @@ int main(int argc, char **argv)
     case Mode::Groups: write_groups(run, group_labels, a.has[F_GROUPS_WITHIN], a.groups_within, a.has[F_PER_RECORD]); break;
     case Mode::Histogram: write_histogram(run, a.histogram, (uint32_t)a.bins); break;
     case Mode::Nearest: write_nearest(run, (uint32_t)a.nearest); break;
-    case Mode::Windows: write_windows(run, windows, a.slab_pairs); break;
+    case Mode::Windows:
+        if (a.has[F_WINDOW_NEAREST])
+            write_window_nearest(run, windows, (uint32_t)a.window_nearest, a.analysis_slab());
+        else
+            write_windows(run, windows, a.slab_pairs);
+        break;
     case Mode::Matrix: {
         // tsv: an empty corner cell, then the column ids (the last input's records); phylip: the number of records
         std::string h = a.matrix == DST_MATRIX_PHYLIP ? std::to_string(loaded[0].n) : "";

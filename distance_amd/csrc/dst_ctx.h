@@ -154,7 +154,7 @@ struct dst_ctx {
     // the analyses (dst_analysis.cpp): the one slab scratch their pair kernels write, DST_OUT_TALLY or DST_OUT_DISTANCE as
     // the call needs (a call owns it until it returns, and every call waits for the stream before it does)
     Grown<> pair_slab;
-    Grown<> nn_lists;       // dst_nearest: the running lists
+    Grown<> nn_lists;       // dst_nearest: the running lists; dst_nearest_windows: the lists of one slab
     Grown<> cl_work;        // dst_clusters: the parent array + link counter
     Grown<> rep_work;       // dst_representatives: rep, and the values and tallies when they are wanted
     Grown<> mst_work;       // dst_mst: the component, best-edge and edge-list arrays

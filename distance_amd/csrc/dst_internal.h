@@ -657,12 +657,24 @@ struct WindowLaunch {
     int out_kind;                  // DST_OUT_DISTANCE or DST_OUT_TALLY
     void *d_out;
     const uint2 *d_windows;        // [n_windows] {begin, end}
-    uint32_t n_windows;
+    uint32_t n_windows;            // the launch sweeps windows [win_first, win_first + n_windows) of the table ...
     const uint4 *q_counts, *t_counts;   // tn93 distances: [n_windows][rows.n] / [n_windows][cols.n] {A,T,G,C} inside the window
+    uint32_t win_first;            // ... and lays window w out at (w - win_first) * P (dst_run_windows: 0, the whole table)
 };
 hipError_t launch_window_pairs(int measure, const WindowLaunch &wl, hipStream_t stream);
 // counts[w * set.n + record] = the record's {A,T,G,C}, counted by code, inside window w
 hipError_t launch_window_counts(const DeviceSet &set, const uint2 *d_windows, uint32_t n_windows, uint4 *counts, hipStream_t stream);
+
+// ---- k nearest records per window (dst_window_nearest.hip, driven by dst_nearest_windows in dst_windows.hip) ----------
+// A slab is rows [row0, row0 + nr) x windows [win0, win0 + nw) x all n_cols column records as DST_OUT_TALLY words, entry
+// (w_local * nr + i_local) * n_cols + j (launch_window_pairs with win_first = win0 on the rectangle; a square job sweeps
+// slot 0 against itself).  One wave per (row, window) list; list i_local * nw + w_local of nl (k entries each) is written
+// whole.  q_counts / t_counts: tn93's per-window tables [window][record] of the row and the column set.
+constexpr uint64_t kWindowNearestPairs = (uint64_t)1 << 25;      // pair-windows of a slab unless the caller says otherwise
+constexpr uint64_t kWindowNearestListsMax = (uint64_t)1 << 31;   // lists of one slab: a list number is 32 bits on the device
+hipError_t launch_window_nearest(int measure, const uint32_t *slab, const uint4 *q_counts, const uint4 *t_counts, uint64_t q_n,
+                                 uint64_t n_cols, uint64_t row0, uint64_t nr, uint32_t win0, uint32_t nw, bool square,
+                                 const NearestLists &nl, hipStream_t stream);
 
 // ---- host-only logic (dst_host.cpp) ----------------------------------------------------------
 int tally_width(int measure);

@@ -1,6 +1,8 @@
 // dst_windows.hip — distances per column window (dst_run_windows, dst_window_base_counts): the dense pair
 // kernel's sweep (dst_kernels.hip) restricted to the 128-site chunks a window [begin, end) meets, with a site mask on
 // the at most two chunks the window's edges cut.
+// dst_nearest_windows is here too: it runs the same sweep slab by slab into the context's slab scratch and
+// dst_window_nearest.hip's selection directly behind it.
 //
 // Mapping (window_pair_kernel): one block = kWinRows row records x 256 column records x ONE window.  grid.x walks the
 // column tiles, grid.y the row tiles, grid.z the windows; y and z hold at most 65,535 each, so the launcher cuts both
@@ -92,8 +94,8 @@ template <class M, int OUT>
 __global__ __launch_bounds__(kWinCols) void window_pair_kernel(
     const uint4 *__restrict__ qpl, const uint4 *__restrict__ tpl, const uint2 *__restrict__ windows, void *__restrict__ out_v,
     const uint4 *__restrict__ q_counts, const uint4 *__restrict__ t_counts, uint32_t nchunks, uint32_t q_npad, uint32_t t_npad,
-    uint32_t q_n, uint32_t n_cols, uint32_t row_begin, uint32_t row_end, uint32_t row0, uint32_t win0, uint64_t pairs,
-    uint64_t out_base, int square)
+    uint32_t q_n, uint32_t n_cols, uint32_t row_begin, uint32_t row_end, uint32_t row0, uint32_t win0, uint32_t win_first,
+    uint64_t pairs, uint64_t out_base, int square)
 {
     constexpr int NP = M::NP, NC = M::NC, NT = M::NT;
     constexpr int STAGE_WORDS = OUT >= 0 ? kWinRows * NT * kWinCols : 1;
@@ -174,7 +176,7 @@ __global__ __launch_bounds__(kWinCols) void window_pair_kernel(
     }
 
     const uint32_t total = we - wb;
-    const uint64_t win_at = (uint64_t)w * pairs;
+    const uint64_t win_at = (uint64_t)(w - win_first) * pairs;   // (the launch's first window lies at 0)
     if constexpr (OUT < 0) {
 #pragma unroll
         for (int r = 0; r < kWinRows; ++r) {
@@ -272,13 +274,13 @@ hipError_t launch_windows_one(const WindowLaunch &wl, hipStream_t stream)
     const uint64_t row_tiles = (rows + kWinRows - 1) / kWinRows;
     const unsigned col_tiles = (unsigned)((wl.cols->n + kWinCols - 1) / kWinCols);
     // windows and row tiles each in grids of at most 65,535
-    return for_row_grids(0, wl.n_windows, [&](uint64_t win0, unsigned nwin) {
+    return for_row_grids(wl.win_first, (uint64_t)wl.win_first + wl.n_windows, [&](uint64_t win0, unsigned nwin) {
         return for_row_grids(0, row_tiles, [&](uint64_t tile0, unsigned ntiles) {
             hipLaunchKernelGGL((window_pair_kernel<M, OUT>), dim3(col_tiles, ntiles, nwin), dim3(kWinCols), 0, stream,
                                wl.rows->planes, wl.cols->planes, wl.d_windows, wl.d_out, wl.q_counts, wl.t_counts,
                                (uint32_t)wl.rows->nchunks, (uint32_t)wl.rows->npad, (uint32_t)wl.cols->npad, (uint32_t)wl.rows->n,
                                (uint32_t)wl.cols->n, (uint32_t)wl.row_begin, (uint32_t)wl.row_end,
-                               (uint32_t)(wl.row_begin + tile0 * kWinRows), (uint32_t)win0, wl.pairs,
+                               (uint32_t)(wl.row_begin + tile0 * kWinRows), (uint32_t)win0, wl.win_first, wl.pairs,
                                wl.square ? square_row_start(wl.cols->n, wl.row_begin) : (uint64_t)0, wl.square ? 1 : 0);
             return hipGetLastError();
         });
@@ -289,7 +291,7 @@ hipError_t launch_windows_one(const WindowLaunch &wl, hipStream_t stream)
 
 hipError_t launch_window_pairs(int measure, const WindowLaunch &wl, hipStream_t stream)
 {
-    if (wl.n_windows == 0 || wl.n_windows > DST_WINDOWS_MAX || wl.row_end <= wl.row_begin || wl.row_end > wl.rows->n ||
+    if (wl.n_windows == 0 || (uint64_t)wl.win_first + wl.n_windows > DST_WINDOWS_MAX || wl.row_end <= wl.row_begin || wl.row_end > wl.rows->n ||
         wl.cols->n == 0 || wl.rows->n > 0xFFFFFFFFull || wl.cols->n > 0xFFFFFFFFull || wl.rows->nchunks != wl.cols->nchunks ||
         wl.rows->len != wl.cols->len || wl.rows->len > 0xFFFFFFFFull)
         return hipErrorInvalidValue;
@@ -411,8 +413,8 @@ int windows_args(dst_ctx *ctx, int measure, int square, int row_slot, int col_sl
     return DST_OK;
 }
 
-int windows_run(dst_ctx *ctx, int measure, const TwoSets &ts, bool square, uint64_t rb, uint64_t re, uint64_t pairs,
-                const uint64_t *wb, const uint64_t *we, uint32_t n_windows, int out_kind, void *d_out, hipStream_t stream)
+// what a window call queues first: the planes its kernels read and the window table on the device
+int windows_prepare(dst_ctx *ctx, const TwoSets &ts, const uint64_t *wb, const uint64_t *we, uint32_t n_windows, hipStream_t stream)
 {
     DeviceSet &rows = *ts.rows, &cols = *ts.cols;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
@@ -427,7 +429,30 @@ int windows_run(dst_ctx *ctx, int measure, const TwoSets &ts, bool square, uint6
         rc = ensure_derived(ctx, rows, stream);
     if (!rc)
         rc = upload_windows(ctx, wb, we, n_windows, stream);
-    if (rc)
+    return rc;
+}
+
+// tn93's per-window base counts of both sets, [n_windows][rows.n] and [n_windows][cols.n] (one table when they are one set)
+int window_count_tables(dst_ctx *ctx, const DeviceSet &rows, const DeviceSet &cols, uint32_t n_windows, hipStream_t stream,
+                        const uint4 *&q_counts, const uint4 *&t_counts)
+{
+    const size_t per_row = (size_t)n_windows * rows.n, per_col = &rows != &cols ? (size_t)n_windows * cols.n : 0;
+    if (int rc = grow_or_nomem(ctx, ctx->win_counts, (per_row + per_col) * sizeof(uint4), "tn93's per-window base counts"))
+        return rc;
+    uint4 *q = ctx->win_counts, *t = per_col ? q + per_row : q;
+    HIP_TRY(ctx, launch_window_counts(rows, ctx->win_table, n_windows, q, stream));
+    if (per_col)
+        HIP_TRY(ctx, launch_window_counts(cols, ctx->win_table, n_windows, t, stream));
+    q_counts = q;
+    t_counts = t;
+    return DST_OK;
+}
+
+int windows_run(dst_ctx *ctx, int measure, const TwoSets &ts, bool square, uint64_t rb, uint64_t re, uint64_t pairs,
+                const uint64_t *wb, const uint64_t *we, uint32_t n_windows, int out_kind, void *d_out, hipStream_t stream)
+{
+    DeviceSet &rows = *ts.rows, &cols = *ts.cols;
+    if (int rc = windows_prepare(ctx, ts, wb, we, n_windows, stream))
         return rc;
     WindowLaunch wl{};
     wl.rows = &rows;
@@ -440,19 +465,33 @@ int windows_run(dst_ctx *ctx, int measure, const TwoSets &ts, bool square, uint6
     wl.d_out = d_out;
     wl.d_windows = ctx->win_table;
     wl.n_windows = n_windows;
-    if (measure == DST_TN93 && out_kind == DST_OUT_DISTANCE) {
-        const size_t per_row = (size_t)n_windows * rows.n, per_col = &rows != &cols ? (size_t)n_windows * cols.n : 0;
-        if ((rc = grow_or_nomem(ctx, ctx->win_counts, (per_row + per_col) * sizeof(uint4), "tn93's per-window base counts")))
+    if (measure == DST_TN93 && out_kind == DST_OUT_DISTANCE)
+        if (int rc = window_count_tables(ctx, rows, cols, n_windows, stream, wl.q_counts, wl.t_counts))
             return rc;
-        uint4 *q = ctx->win_counts, *t = per_col ? q + per_row : q;
-        HIP_TRY(ctx, launch_window_counts(rows, wl.d_windows, n_windows, q, stream));
-        if (per_col)
-            HIP_TRY(ctx, launch_window_counts(cols, wl.d_windows, n_windows, t, stream));
-        wl.q_counts = q;
-        wl.t_counts = t;
-    }
     HIP_TRY(ctx, launch_window_pairs(measure, wl, stream));
     return DST_OK;
+}
+
+// The (row, window) lists of a dst_nearest_windows call cut into slabs of rows x windows: whole row ranges of all the
+// windows while a row's windows fit the budget, else a few rows (the sweep's tile holds eight) of a range of windows.
+struct WindowSlabs {
+    uint64_t rows;   // rows of a slab (the last one of a job may hold fewer)
+    uint32_t wins;   // windows of a slab (likewise)
+};
+WindowSlabs cut_window_slabs(uint64_t n_rows, uint32_t n_windows, uint64_t n_cols, uint64_t max_entries)
+{
+    // (no more than 2^40 entries, 16 TB of tn93 tallies: a slab's byte count stays far inside 64 bits)
+    const uint64_t budget = max_entries ? std::min<uint64_t>(max_entries, (uint64_t)1 << 40) : kWindowNearestPairs;
+    const uint64_t lists = std::min<uint64_t>(std::max<uint64_t>(budget / n_cols, 1), kWindowNearestListsMax);
+    WindowSlabs s;
+    if (lists >= n_windows) {
+        s.rows = std::min<uint64_t>(lists / n_windows, n_rows);
+        s.wins = n_windows;
+    } else {
+        s.rows = std::min<uint64_t>(std::min<uint64_t>(lists, 8), n_rows);
+        s.wins = (uint32_t)(lists / s.rows);
+    }
+    return s;
 }
 
 }  // namespace
@@ -552,6 +591,116 @@ int dst_window_base_counts(dst_ctx *ctx, int slot, const uint64_t *win_begin, co
         return rc;
     HIP_TRY(ctx, launch_window_counts(s, ctx->win_table, n_windows, ctx->win_counts, stream));
     HIP_TRY(ctx, hipMemcpyAsync(counts, ctx->win_counts, (size_t)entries * sizeof(uint32_t), hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    return DST_OK;
+}
+
+int dst_nearest_windows(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, uint64_t row_begin, uint64_t row_end,
+                        const uint64_t *win_begin, const uint64_t *win_end, uint32_t n_windows, uint32_t k, uint64_t max_entries,
+                        uint32_t *index, uint32_t *tallies, void *values, size_t cap_entries, uint32_t *k_used)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (k_used)
+        *k_used = 0;
+    if (n_windows > DST_WINDOWS_MAX)
+        return fail(ctx, DST_ERR_ARG, "more than DST_WINDOWS_MAX (65,536) windows");
+    if (n_windows && (!win_begin || !win_end))
+        return fail(ctx, DST_ERR_ARG, "null pointer");
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (k < 1 || k > kNearestMaxK)
+        return fail(ctx, DST_ERR_ARG, "k must be between 1 and 256");
+    if (!index || !k_used)
+        return fail(ctx, DST_ERR_ARG, "null index or k_used pointer");
+    TwoSets ts;
+    if (int rc = two_sets(ctx, square != 0, row_slot, col_slot, ts))
+        return rc;
+    DeviceSet &rows = *ts.rows, &cols = *ts.cols;
+    if (rows.partial || cols.partial)
+        return fail(ctx, DST_ERR_STATE, kSharedRefusal);
+    if (rows.len >= ((uint64_t)1 << 32))
+        return fail(ctx, DST_ERR_ARG, "alignments of 2^32 sites or more are beyond dst_nearest_windows");
+    if (int rc = windows_valid(ctx, win_begin, win_end, n_windows, rows.len))
+        return rc;
+    if (row_begin > row_end || row_end > rows.n)
+        return fail(ctx, DST_ERR_ARG, "row range out of bounds");
+    if (rows.n >= 0xFFFFFFFFull || cols.n >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    const uint64_t n_rows = row_end - row_begin, n_cols = cols.n;
+    const uint64_t candidates = square ? (n_cols > 0 ? n_cols - 1 : 0) : n_cols;
+    const uint32_t ku = (uint32_t)std::min<uint64_t>(k, candidates);
+    *k_used = ku;
+    const unsigned __int128 entries = (unsigned __int128)n_rows * n_windows * ku;
+    if (entries == 0)
+        return DST_OK;
+    if (entries > (unsigned __int128)cap_entries)
+        return fail(ctx, DST_ERR_CAPACITY, "cap_entries is below rows x n_windows x k_used");
+    hipStream_t stream = ctx->stream;
+    if (int rc = windows_prepare(ctx, ts, win_begin, win_end, n_windows, stream))
+        return rc;
+    const int W = tally_width(measure);
+    const WindowSlabs cut = cut_window_slabs(n_rows, n_windows, n_cols, max_entries);
+    // the slab's tallies, and its lists: payloads, indices and tallies of rows x wins x k_used entries, each 256-byte aligned
+    const uint64_t slab_lists = cut.rows * cut.wins, slab_entries = slab_lists * ku;
+    const auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t val_bytes = pad(slab_entries * 8), idx_bytes = pad(slab_entries * 4), tal_bytes = pad(slab_entries * W * 4);
+    if (int rc = grow_or_nomem(ctx, ctx->pair_slab, std::max<size_t>(dst_out_bytes(measure, DST_OUT_TALLY, slab_lists * n_cols), 256),
+                               "a slab of window tallies"))
+        return rc;
+    if (int rc = grow_or_nomem(ctx, ctx->nn_lists, val_bytes + idx_bytes + tal_bytes, "a slab's lists"))
+        return rc;
+    NearestLists nl{};
+    char *lists = static_cast<char *>(ctx->nn_lists.ptr);
+    nl.val = reinterpret_cast<uint64_t *>(lists);
+    nl.idx = reinterpret_cast<uint32_t *>(lists + val_bytes);
+    nl.tal = reinterpret_cast<uint32_t *>(lists + val_bytes + idx_bytes);
+    nl.k = ku;
+    WindowLaunch wl{};
+    wl.rows = &rows;
+    wl.cols = &cols;
+    wl.square = false;   // a square job too: slot 0 against itself, so that a row finds all its j != i in the slab
+    wl.out_kind = DST_OUT_TALLY;
+    wl.d_out = ctx->pair_slab;
+    wl.d_windows = ctx->win_table;
+    const uint4 *q_counts = nullptr, *t_counts = nullptr;
+    if (measure == DST_TN93)
+        if (int rc = window_count_tables(ctx, rows, cols, n_windows, stream, q_counts, t_counts))
+            return rc;
+    // Slab after slab on the stream: sweep, select, copy the lists back.  A slab of all the windows is one contiguous
+    // piece of the result; a slab of some windows is one piece per row.  Nothing waits but the copies into host memory.
+    const size_t row_pitch = (size_t)n_windows * ku;   // entries of a row record in the result
+    const auto copy_back = [&](void *host, const void *dev, size_t entry_bytes, uint64_t r0, uint64_t nr, uint32_t w0,
+                               uint32_t nw) -> hipError_t {
+        char *h = static_cast<char *>(host) + ((size_t)(r0 - row_begin) * row_pitch + (size_t)w0 * ku) * entry_bytes;
+        const char *d = static_cast<const char *>(dev);
+        const size_t piece = (size_t)nw * ku * entry_bytes;
+        if (nw == n_windows)
+            return hipMemcpyAsync(h, d, piece * nr, hipMemcpyDeviceToHost, stream);
+        for (uint64_t r = 0; r < nr; ++r)
+            if (const hipError_t e = hipMemcpyAsync(h + r * row_pitch * entry_bytes, d + r * piece, piece, hipMemcpyDeviceToHost, stream))
+                return e;
+        return hipSuccess;
+    };
+    for (uint64_t r0 = row_begin; r0 < row_end; r0 += cut.rows) {
+        const uint64_t nr = std::min<uint64_t>(cut.rows, row_end - r0);
+        for (uint32_t w0 = 0; w0 < n_windows; w0 += cut.wins) {
+            const uint32_t nw = std::min<uint32_t>(cut.wins, n_windows - w0);
+            wl.row_begin = r0;
+            wl.row_end = r0 + nr;
+            wl.pairs = nr * n_cols;
+            wl.win_first = w0;
+            wl.n_windows = nw;
+            HIP_TRY(ctx, launch_window_pairs(measure, wl, stream));
+            HIP_TRY(ctx, launch_window_nearest(measure, static_cast<const uint32_t *>(ctx->pair_slab.ptr), q_counts, t_counts, rows.n,
+                                               n_cols, r0, nr, w0, nw, square != 0, nl, stream));
+            HIP_TRY(ctx, copy_back(index, nl.idx, 4, r0, nr, w0, nw));
+            if (values)
+                HIP_TRY(ctx, copy_back(values, nl.val, 8, r0, nr, w0, nw));
+            if (tallies)
+                HIP_TRY(ctx, copy_back(tallies, nl.tal, (size_t)W * 4, r0, nr, w0, nw));
+        }
+    }
     HIP_TRY(ctx, hipStreamSynchronize(stream));
     return DST_OK;
 }

@@ -637,6 +637,32 @@ class Engine:
                                                      out.size))
         return out
 
+    def nearest_windows(self, measure, windows, k: int, square: bool = True, row_slot: int = 0, col_slot: int = 1,
+                        row_begin: int = 0, row_end: int | None = None, tallies: bool = False, max_entries: int = 0):
+        """The k nearest records of every row record in every column window (dst_nearest_windows):
+        (index[n_rows, n_windows, k_used], values[n_rows, n_windows, k_used]), plus tallies[..., width] when asked.  Per
+        (row, window) ascending by (key of the window's value, index); square: slot 0 against itself without the diagonal,
+        the canonical pair's value; else rows [row_begin, row_end) of row_slot against every record of col_slot.
+        max_entries: the most pair-windows of one device slab (0: the default); the result does not depend on it."""
+        m = _measure_id(measure)
+        begin, end, nw = _window_arrays(windows)
+        n_rows, _ = self.set_info(0 if square else row_slot)
+        n_cols, _ = self.set_info(0 if square else col_slot)
+        row_end = n_rows if row_end is None else row_end
+        rows = max(row_end - row_begin, 0)
+        ku = min(int(k), max(n_cols - 1, 0) if square else n_cols) if 1 <= int(k) <= 256 else 0
+        width = self._lib.dst_tally_width(m)
+        index = np.zeros((rows, nw, ku), np.uint32)
+        values = np.zeros((rows, nw, ku), np.int64 if m in (0, 1) else np.float64)
+        tal = np.zeros((rows, nw, ku, width), np.uint32) if tallies else None
+        k_used = C.c_uint32()
+        self._check(self._lib.dst_nearest_windows(self._h, m, int(square), row_slot, col_slot, row_begin, row_end,
+                                                  begin.ctypes.data, end.ctypes.data, nw, int(k), int(max_entries),
+                                                  index.ctypes.data, None if tal is None else tal.ctypes.data,
+                                                  values.ctypes.data, rows * nw * ku, C.byref(k_used)))
+        assert k_used.value == ku
+        return (index, values, tal) if tallies else (index, values)
+
     def summary(self, measure, threshold: float = 0.0, square: bool = True, row_slot: int = 0, col_slot: int = 1,
                 max_pairs: int = 0, bins: int = 0, width: float = 1.0, per_record: bool = True) -> dict:
         """Per-record and histogram summaries of the pairwise distances (dst_summary), a dict: `within` (uint32[n_rows], the

@@ -625,6 +625,48 @@ int dst_run_windows_host(dst_ctx *ctx, int measure, int square, int row_slot, in
  * cap_entries >= n_windows x n x 4 uint32 (else DST_ERR_CAPACITY).  Errors as above. */
 int dst_window_base_counts(dst_ctx *ctx, int slot, const uint64_t *win_begin, const uint64_t *win_end,
                            uint32_t n_windows, uint32_t *counts, size_t cap_entries);
+/* ---- k nearest records per column window ------------------------------------------------------------ */
+/* For every (row record, window) the k column records with the smallest distance INSIDE that window, selected next to the
+ * tallies on the GPU: a recombination scan asks which panel records are nearest to a query in each window, a few
+ * neighbours per (query, window), never the matrix dst_run_windows returns.  The definition is fixed to the bit.
+ *   sets, windows, row range   exactly dst_run_windows': square != 0 is slot 0 against itself (row_slot / col_slot
+ *            ignored), else two different slots; a window is a half-open [begin, end), 0 <= begin <= end <= len, windows
+ *            may overlap, repeat, be empty and come in any order; 1 <= n_windows <= DST_WINDOWS_MAX; rows [row_begin,
+ *            row_end) of the row set.
+ *   candidates of row record i in window w   rectangle: every record j of col_slot, none excluded; square: every j != i
+ *            of slot 0 (identical sequences stay in).
+ *   value of candidate j   the DST_OUT_DISTANCE payload dst_run_windows writes for window w: rectangle, of the pair
+ *            (i, j); square, of the canonical pair (min(i, j), max(i, j)) — tn93 takes the two records' per-window base
+ *            counts in that order, as dst_nearest does for the whole width.  Its tallies are that entry's DST_OUT_TALLY
+ *            words.
+ *   order    ascending (key(value), j) with dst_nearest's key (int64: v ^ 2^63; f64: NaN after +inf, -0.0 as +0.0): a
+ *            strict total order, so the answer is unique.  1 <= k <= 256, else DST_ERR_ARG.  *k_used = min(k, candidates
+ *            per row).  An empty window makes every candidate equal (0 for n / n_high, NaN for raw, whatever the
+ *            finalisation gives for zeros otherwise): it lists the first k_used candidates in index order.
+ *   layout   (host memory) entry ((i - row_begin) * n_windows + w) * k_used + e, e ascending:
+ *              index    the column record (required)
+ *              values   the 8-byte DST_OUT_DISTANCE payloads, or NULL
+ *              tallies  dst_tally_width(measure) DST_OUT_TALLY words per entry, or NULL
+ *            cap_entries below (row_end - row_begin) * n_windows * k_used: DST_ERR_CAPACITY, nothing written but *k_used.
+ *   max_entries   the most pair-windows (rows x windows x column records) of one device slab, 0: 2^25.  A slab is a range
+ *            of rows x a range of windows, at least one (row, window).  The result does not depend on it.  Device memory
+ *            beside the sets, the window table and tn93's per-window count table (n_windows x records x 16 bytes per set,
+ *            as dst_run_windows) is bounded by the slab's tallies and its lists, whatever the job's size.
+ * n_windows == 0, an empty row range, or no candidates (a square set of fewer than 2 records, an empty column set): DST_OK
+ * with *k_used set and nothing written.  Errors are dst_run_windows', in its order and with its messages: DST_ERR_ARG for a
+ * NULL ctx; more than DST_WINDOWS_MAX windows; a NULL window array; an unknown measure; k outside 1..256; a NULL index or
+ * k_used; a bad slot or equal slots; then DST_ERR_STATE for a set not uploaded, different widths, or a set from
+ * dst_upload_shared (the dense kernels' refusal); DST_ERR_ARG for len >= 2^32, a bad window (the message names the first),
+ * row_begin > row_end or row_end > n, sets of 2^32-1 records or more; DST_ERR_CAPACITY; DST_ERR_NOMEM with the byte count.
+ * Synchronous on the context's stream: per slab the window sweep of the rectangle rows x ALL column records (a square job
+ * sweeps slot 0 against itself: every row needs all its j != i, at twice the triangle's work for a whole square), then one
+ * wave per (row, window) list, then the copy of the finished lists.  A set with deferred planes gets them first; slots, the
+ * path choice, dst_last_path, dst_last_launch and later results are untouched.  Single GPU, loaded sets only. */
+int dst_nearest_windows(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
+                        uint64_t row_begin, uint64_t row_end,
+                        const uint64_t *win_begin, const uint64_t *win_end, uint32_t n_windows,
+                        uint32_t k, uint64_t max_entries,
+                        uint32_t *index, uint32_t *tallies, void *values, size_t cap_entries, uint32_t *k_used);
 /* Pure host code: the windows of `distance --windows W --step S`.  begin_k = k step, end_k = min(begin_k + width, len), for
  * k = 0, 1, ... up to the first k whose end_k == len (no window is a subset of its predecessor) — with a step above the
  * width, which leaves columns between windows out, also no further than the last k with begin_k < len; len == 0: no window.
