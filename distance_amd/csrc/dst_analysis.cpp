@@ -174,31 +174,17 @@ size_t mst_layout(void *base, uint64_t n, int W, MstBuffers &b)
 
 // The device memory of one n x n f64 square (dst_nj, dst_dendrogram and their forms): the two matrix buffers and one
 // block for the rest.  Per call, not grow-only: the square of 50,000 records is 20 GB.  Freed behind the context's
-// stream.  A dendrogram needs no compaction: setup(n, false) leaves the second matrix buffer out.
+// stream: the members go after the destructor's wait.  A dendrogram needs no compaction: setup(n, false) leaves the second
+// matrix buffer out.
 struct SquareAlloc {
     dst_ctx *ctx;
     const char *what;
-    void *D0 = nullptr, *D1 = nullptr, *work = nullptr;
+    Grown<double> D0, D1;
+    Grown<> work;
     NjBuffers b{};
     unsigned long long *bad = nullptr;
     explicit SquareAlloc(dst_ctx *c, const char *w = "neighbour joining") : ctx(c), what(w) {}
-    ~SquareAlloc()
-    {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (void *p : {D0, D1, work})
-            if (p)
-                (void)hipFree(p);
-    }
-    int alloc(void **p, size_t bytes)
-    {
-        if (hipMalloc(p, bytes) != hipSuccess) {
-            *p = nullptr;
-            (void)hipGetLastError();   // (clear the out-of-memory status: later launches check hipGetLastError)
-            return fail(ctx, DST_ERR_NOMEM, std::string(what) + ": cannot allocate " + std::to_string(bytes) +
-                                                " bytes of device memory");
-        }
-        return DST_OK;
-    }
+    ~SquareAlloc() { (void)hipStreamSynchronize(ctx->stream); }
     size_t layout(void *base, uint64_t n)
     {
         const size_t nodes = 2 * n - 2;
@@ -219,16 +205,16 @@ struct SquareAlloc {
     int setup(uint64_t n, bool compaction = true)
     {
         const uint64_t n1 = std::max<uint64_t>(3 * n / 4, 1);
-        int rc = alloc(&D0, n * n * 8);
+        int rc = D0.grow(ctx, n * n * 8, what);
         if (!rc && compaction)
-            rc = alloc(&D1, n1 * n1 * 8);
+            rc = D1.grow(ctx, n1 * n1 * 8, what);
         if (!rc)
-            rc = alloc(&work, layout(nullptr, n));
+            rc = work.grow(ctx, layout(nullptr, n), what);
         if (rc)
             return rc;
         layout(work, n);
-        b.D[0] = static_cast<double *>(D0);
-        b.D[1] = static_cast<double *>(D1);
+        b.D[0] = D0;
+        b.D[1] = D1;
         return DST_OK;
     }
 };
@@ -294,33 +280,26 @@ int nj_finish(dst_ctx *ctx, SquareAlloc &al, uint64_t n, uint32_t *parent, doubl
 }
 
 // dst_nj_bootstrap's device memory beside SquareAlloc: the original codes, the replicate's codes (both n x pitch) and
-// the column map.  Freed behind the context's stream, with the replicate's packed set.
+// the column map.  Freed behind the context's stream (the members go after the destructor's wait), with the replicate's
+// packed set.
 struct BootAlloc {
     dst_ctx *ctx;
-    uint8_t *src = nullptr, *rep = nullptr;
-    uint32_t *map = nullptr;
+    Grown<uint8_t> src, rep;
+    Grown<uint32_t> map;
     explicit BootAlloc(dst_ctx *c) : ctx(c) {}
     ~BootAlloc()
     {
         (void)hipStreamSynchronize(ctx->stream);
-        for (void *p : {(void *)src, (void *)rep, (void *)map})
-            if (p)
-                (void)hipFree(p);
         free_set(ctx->boot);
     }
     int setup(uint64_t n, uint64_t pitch, uint64_t len)
     {
-        const size_t bytes[3] = {std::max<size_t>(n * pitch, 128), std::max<size_t>(n * pitch, 128),
-                                 std::max<size_t>(len * 4, 4)};
-        void **ptrs[3] = {(void **)&src, (void **)&rep, (void **)&map};
-        for (int k = 0; k < 3; ++k)
-            if (hipMalloc(ptrs[k], bytes[k]) != hipSuccess) {
-                *ptrs[k] = nullptr;
-                (void)hipGetLastError();
-                return fail(ctx, DST_ERR_NOMEM, "bootstrap: cannot allocate " + std::to_string(bytes[k]) +
-                                                    " bytes of device memory");
-            }
-        return DST_OK;
+        int rc = src.grow(ctx, std::max<size_t>(n * pitch, 128), "bootstrap");
+        if (!rc)
+            rc = rep.grow(ctx, std::max<size_t>(n * pitch, 128), "bootstrap");
+        if (!rc)
+            rc = map.grow(ctx, std::max<size_t>(len * 4, 4), "bootstrap");
+        return rc;
     }
 };
 

@@ -55,22 +55,8 @@ int timer_end(dst_ctx *ctx, int which, hipStream_t stream)
     return DST_OK;
 }
 
-int ensure_bytes(dst_ctx *ctx, void **ptr, size_t *have, size_t want)
-{
-    if (*have >= want)
-        return DST_OK;
-    if (*ptr) {
-        HIP_TRY(ctx, hipFree(*ptr));
-        *ptr = nullptr;
-        *have = 0;
-    }
-    HIP_TRY(ctx, hipMalloc(ptr, want));
-    *have = want;
-    return DST_OK;
-}
-
-// the one place a context-level buffer is allocated and the one place it is freed (Grown, dst_ctx.h); the device path
-// fails as ensure_bytes does, a page-locked buffer with the caller's `what`
+// the one place a buffer of the library's own is allocated and the one place it is freed (Grown, dst_owner.h): as the
+// runtime's failure, or with the caller's `what` as a refusal that names the kind of memory
 int GrownBase::grow(dst_ctx *ctx, size_t want, const char *what)
 {
     if (bytes >= want)
@@ -82,8 +68,9 @@ int GrownBase::grow(dst_ctx *ctx, size_t want, const char *what)
         ptr = nullptr;
         if (!what)
             return fail_hip(ctx, e, pinned ? "hipHostMalloc(ptr, want)" : "hipMalloc(ptr, want)");
-        (void)hipGetLastError();
-        return fail(ctx, DST_ERR_NOMEM, std::string(what) + ": cannot allocate " + std::to_string(want) + " bytes of page-locked memory");
+        (void)hipGetLastError();   // (clear the out-of-memory status: later launches check hipGetLastError)
+        return fail(ctx, DST_ERR_NOMEM, std::string(what) + ": cannot allocate " + std::to_string(want) + " bytes of " +
+                                            (pinned ? "page-locked" : "device") + " memory");
     }
     bytes = want;
     return DST_OK;
@@ -126,18 +113,8 @@ int two_sets(dst_ctx *ctx, bool square, int row_slot, int col_slot, TwoSets &out
 
 void free_set(DeviceSet &s)
 {
-    void *bufs[] = {s.planes, s.counts, s.ref.planes, s.ref.hot_planes, s.ref.hot_sites, s.ref.stats, s.ref.partials, s.rec.off, s.rec.ent, s.rec.range_start, s.rec.pre_cold, s.rec.pre_slots,
-                    s.site.inl, s.site.ent, s.aconst, s.runs.index, s.runs.mask, s.runs.known, s.runs.panel_first, s.runs.state,
-                    s.runs.aent, s.runs.corr, s.runs.corr_t, s.runs.s7};   // (runs.cnt_run / run_cold / run_hot / ids live in the pre_cold and index blocks)
-    for (void *b : bufs)
-        if (b)
-            (void)hipFree(b);
-    if (s.hot) {
-        free_set(*s.hot);
-        delete s.hot;
-    }
     const uint64_t epoch = s.epoch;
-    s = DeviceSet{};
+    s = DeviceSet{};      // (every buffer goes with what was here, the hot columns' set too)
     s.epoch = epoch + 1;  // lists other sets hold against this set's reference are stale from now on
 }
 
@@ -150,16 +127,16 @@ int shape_set(dst_ctx *ctx, DeviceSet &s, size_t n, size_t len)
     const size_t bytes = (size_t)PL_COUNT * nchunks * npad * sizeof(uint4);
     // (a set keeps the largest planes it ever needed: the batches of a stream differ in size, and hipFree would stall
     // every stream of the device — the layout depends on npad and nchunks, the allocation only on their product)
-    if (!s.planes || !s.counts || s.planes_bytes < bytes || s.counts_cap < npad) {
-        free_set(s);
-        HIP_TRY(ctx, hipMalloc((void **)&s.planes, bytes ? bytes : 16));
-        s.planes_bytes = bytes;
-        const hipError_t e = hipMalloc((void **)&s.counts, npad * 4 * sizeof(uint32_t));
-        if (e != hipSuccess) {
+    const size_t counts_bytes = npad * 4 * sizeof(uint32_t);
+    if (!s.planes || !s.counts || s.planes.bytes < bytes || s.counts.bytes < counts_bytes) {
+        free_set(s);   // (the derived buffers too: a set that grows starts over)
+        int rc = s.planes.grow(ctx, bytes);
+        if (!rc)
+            rc = s.counts.grow(ctx, counts_bytes);
+        if (rc) {
             free_set(s);  // never leave a set with planes but no counts behind
-            return fail_hip(ctx, e, "hipMalloc(base counts)");
+            return rc;
         }
-        s.counts_cap = npad;
     }
     s.n = n;
     s.len = len;
@@ -181,24 +158,40 @@ int shape_set(dst_ctx *ctx, DeviceSet &s, size_t n, size_t len)
 }
 
 // buffers of a set's reference sequence (dst_consensus.hip)
+// (grow-only like every other buffer of a set; a failure half way leaves the rest empty, for the next call to grow)
 int alloc_ref(dst_ctx *ctx, DeviceSet &s)
 {
-    if (s.ref.nchunks == s.nchunks && s.ref.planes)
-        return DST_OK;
-    for (void *b : {(void *)s.ref.planes, (void *)s.ref.hot_planes, (void *)s.ref.hot_sites, (void *)s.ref.stats, (void *)s.ref.partials})
-        if (b)
-            HIP_TRY(ctx, hipFree(b));
-    s.ref.planes = nullptr;
-    s.ref.hot_planes = nullptr;
-    s.ref.hot_sites = nullptr;
-    s.ref.stats = nullptr;
-    s.ref.partials = nullptr;
-    HIP_TRY(ctx, hipMalloc((void **)&s.ref.planes, 4 * s.nchunks * sizeof(uint4)));
-    HIP_TRY(ctx, hipMalloc((void **)&s.ref.hot_planes, s.nchunks * sizeof(uint4)));
-    HIP_TRY(ctx, hipMalloc((void **)&s.ref.hot_sites, s.nchunks * kChunkSites * sizeof(uint32_t)));
-    HIP_TRY(ctx, hipMalloc((void **)&s.ref.stats, 8 * sizeof(uint64_t)));
-    HIP_TRY(ctx, hipMalloc((void **)&s.ref.partials, s.nchunks * 16 * sizeof(uint32_t)));
-    s.ref.nchunks = s.nchunks;
+    int rc = s.ref.planes.grow(ctx, 4 * s.nchunks * sizeof(uint4));
+    if (!rc)
+        rc = s.ref.hot_planes.grow(ctx, s.nchunks * sizeof(uint4));
+    if (!rc)
+        rc = s.ref.hot_sites.grow(ctx, s.nchunks * kChunkSites * sizeof(uint32_t));
+    if (!rc)
+        rc = s.ref.stats.grow(ctx, 8 * sizeof(uint64_t));
+    if (!rc)
+        rc = s.ref.partials.grow(ctx, s.nchunks * 16 * sizeof(uint32_t));
+    return rc;
+}
+
+// The pack's counters of `s`, one block that the sample kernel clears per upload: [cap] cold counts, [cap] hot counts, four
+// 64-bit totals (2 cap words in: an 8-byte boundary), then the run-chunk counters (RunIndex): [cap] run chunks, [cap] their
+// cold entries, [cap] their hot entries.  cap >= n + 1: the records the block was grown for.  Sets the views into it;
+// *words: what there is to clear.
+int pack_counters(dst_ctx *ctx, DeviceSet &s, size_t n, size_t *words)
+{
+    RecordIndex &rec = s.rec;
+    RunIndex &ru = s.runs;
+    rec.pre_hot = ru.cnt_run = ru.run_cold = ru.run_hot = nullptr;
+    rec.pre_totals = nullptr;
+    if (int rc = rec.pre_cold.grow(ctx, (5 * (n + 1) + 8) * sizeof(uint32_t)))
+        return rc;
+    const size_t cap = (rec.pre_cold.bytes / sizeof(uint32_t) - 8) / 5;
+    rec.pre_hot = rec.pre_cold + cap;
+    rec.pre_totals = reinterpret_cast<unsigned long long *>(rec.pre_cold + 2 * cap);
+    ru.cnt_run = rec.pre_cold + 2 * cap + 8;
+    ru.run_cold = ru.cnt_run + cap;
+    ru.run_hot = ru.run_cold + cap;
+    *words = 5 * cap + 8;
     return DST_OK;
 }
 
@@ -224,47 +217,26 @@ int pack_queue(dst_ctx *ctx, DeviceSet &s, const uint8_t *d_codes, size_t n, siz
     PackLists pl{};
     if (want_lists) {
         rc = alloc_ref(ctx, s);
-        if (!rc && s.rec.pre_cap < n + 1) {
-            // one block: [n + 1] cold counts, [n + 1] hot counts, the two totals, then the run-chunk counters (RunIndex):
-            // [n + 1] run chunks, [n + 1] their cold entries, [n + 1] their hot entries — one allocation, cleared per upload
-            if (s.rec.pre_cold)
-                HIP_TRY(ctx, hipFree(s.rec.pre_cold));
-            s.rec.pre_cold = s.rec.pre_hot = nullptr;
-            s.rec.pre_totals = nullptr;
-            s.rec.pre_cap = 0;
-            const size_t words = 5 * (n + 1) + 8 + ((2 * (n + 1)) & 1);   // four 64-bit totals on an 8-byte boundary
-            HIP_TRY(ctx, hipMalloc((void **)&s.rec.pre_cold, words * sizeof(uint32_t)));
-            s.rec.pre_cap = n + 1;
-        }
-        if (!rc && s.runs.n_alloc < n + 1) {   // the run records' numbers and ids, and what the report kernel decides
-            if (s.runs.index)
-                HIP_TRY(ctx, hipFree(s.runs.index));
-            s.runs.index = s.runs.ids = nullptr;
-            s.runs.n_alloc = 0;
-            HIP_TRY(ctx, hipMalloc((void **)&s.runs.index, 2 * (n + 1) * sizeof(uint32_t)));
-            s.runs.n_alloc = n + 1;
-            if (!s.runs.state)
-                HIP_TRY(ctx, hipMalloc((void **)&s.runs.state, 4 * sizeof(uint32_t)));
-        }
+        size_t counter_words = 0;
         if (!rc)
-            rc = ensure_bytes(ctx, (void **)&s.rec.pre_slots, &s.rec.pre_slots_cap, s.nchunks * s.npad * sizeof(uint4));
+            rc = pack_counters(ctx, s, n, &counter_words);
+        // the run records' numbers and their ids, two halves of one block, and what the report kernel decides
+        s.runs.ids = nullptr;
+        if (!rc)
+            rc = s.runs.index.grow(ctx, 2 * (n + 1) * sizeof(uint32_t));
+        if (!rc)
+            rc = s.runs.state.grow(ctx, 4 * sizeof(uint32_t));
+        if (!rc)
+            rc = s.rec.pre_slots.grow(ctx, s.nchunks * s.npad * sizeof(uint4));
         if (rc)
             return rc;
-        {
-            const size_t cap = s.rec.pre_cap, pad = (2 * cap) & 1;
-            s.rec.pre_hot = s.rec.pre_cold + cap;
-            s.rec.pre_totals = reinterpret_cast<unsigned long long *>(s.rec.pre_cold + 2 * cap + pad);
-            s.runs.cnt_run = s.rec.pre_cold + 2 * cap + pad + 8;
-            s.runs.run_cold = s.runs.cnt_run + cap;
-            s.runs.run_hot = s.runs.run_cold + cap;
-            s.runs.ids = s.runs.index + s.runs.n_alloc;
-            // (the pack's counts and first-invalid-byte cell are cleared on the sample's way: no fills of their own)
-            HIP_TRY(ctx, launch_ref_sample_bytes(d_codes, row_stride, s, stream, s.rec.pre_cold, 5 * cap + pad + 8, d_first_bad));
-            HIP_TRY(ctx, launch_hot_list(s, stream));
-        }
+        s.runs.ids = s.runs.index + s.runs.index.bytes / (2 * sizeof(uint32_t));
+        // (the pack's counts and first-invalid-byte cell are cleared on the sample's way: no fills of their own)
+        HIP_TRY(ctx, launch_ref_sample_bytes(d_codes, row_stride, s, stream, s.rec.pre_cold, counter_words, d_first_bad));
+        HIP_TRY(ctx, launch_hot_list(s, stream));
         pl.ref_planes = s.ref.planes;
         pl.hot_planes = s.ref.hot_planes;
-        pl.stats = reinterpret_cast<const unsigned long long *>(s.ref.stats);
+        pl.stats = reinterpret_cast<const unsigned long long *>(s.ref.stats.ptr);
         pl.max_dev_sum = (unsigned long long)(kListsMaxDeviation * (double)len * (double)std::min<size_t>(n, kRefSamples));
         pl.cnt_cold = s.rec.pre_cold;
         pl.cnt_hot = s.rec.pre_hot;
@@ -329,7 +301,7 @@ int pack_set(dst_ctx *ctx, DeviceSet &s, const uint8_t *d_codes, size_t n, size_
     // took 35 ms where 20,000 such records took 1.7)
     const uint32_t max_run = (uint32_t)std::min<uint64_t>(n / 3, 24000000000ull / (32ull * std::max<size_t>(n, 1)));
     HIP_TRY(ctx, launch_report(ctx->d_first_bad,
-                               want_lists ? reinterpret_cast<const unsigned long long *>(s.ref.stats) : nullptr,
+                               want_lists ? reinterpret_cast<const unsigned long long *>(s.ref.stats.ptr) : nullptr,
                                want_lists ? s.rec.pre_cold : nullptr, want_lists ? s.rec.pre_hot : nullptr, n, ctx->d_report, stream,
                                want_lists ? &s.runs : nullptr, max_run, want_lists ? s.rec.pre_totals : nullptr));
     HIP_TRY(ctx, hipStreamSynchronize(stream));
@@ -637,7 +609,7 @@ int ensure_hot(dst_ctx *ctx, DeviceSet &s, DeviceSet &refset, hipStream_t stream
     if (rc0)
         return rc0;
     if (!s.hot)
-        s.hot = new (std::nothrow) DeviceSet;
+        s.hot.reset(new (std::nothrow) DeviceSet);
     if (!s.hot)
         return DST_ERR_NOMEM;
     int rc = shape_set(ctx, *s.hot, s.n, n_hot);
@@ -676,9 +648,9 @@ int ensure_index(dst_ctx *ctx, DeviceSet &s, DeviceSet &refset, bool want_sites,
         return fail(ctx, DST_ERR_CAPACITY, "too many sites x panels for the consensus path's lookup table");
     if (lists_ok && s.rec.ranges_valid) {
         // the lists are there with their range marks (they came by dst_upload_shared's exchange): only the site buckets
-        rc = ensure_bytes(ctx, (void **)&s.site.inl, &s.site.inl_cap, std::max<size_t>(n_buckets, 1) * 2 * sizeof(uint4));
+        rc = s.site.inl.grow(ctx, std::max<size_t>(n_buckets, 1) * 2 * sizeof(uint4));
         if (!rc)
-            rc = ensure_bytes(ctx, (void **)&s.site.ent, &s.site.ent_cap, std::max<size_t>(s.rec.total, 1) * sizeof(uint32_t));
+            rc = s.site.ent.grow(ctx, std::max<size_t>(s.rec.total, 1) * sizeof(uint32_t));
         if (rc)
             return rc;
         HIP_TRY(ctx, hipMemsetAsync(ctx->d_total, 0, 2 * sizeof(unsigned long long), stream));
@@ -693,9 +665,9 @@ int ensure_index(dst_ctx *ctx, DeviceSet &s, DeviceSet &refset, bool want_sites,
     if (s.partial)
         return fail(ctx, DST_ERR_STATE, "a set uploaded with dst_upload_shared holds the lists the exchange brought; they cannot be "
                                         "rebuilt here (another reference, the hybrid path): upload it with dst_upload_device");
-    rc = ensure_bytes(ctx, (void **)&s.rec.off, &s.rec.off_cap, (s.n + 1) * sizeof(uint32_t));
+    rc = s.rec.off.grow(ctx, (s.n + 1) * sizeof(uint32_t));
     if (!rc && want_sites)
-        rc = ensure_bytes(ctx, (void **)&s.site.inl, &s.site.inl_cap, std::max<size_t>(n_buckets, 1) * 2 * sizeof(uint4));
+        rc = s.site.inl.grow(ctx, std::max<size_t>(n_buckets, 1) * 2 * sizeof(uint4));
     if (!rc)
         rc = ctx->scan_tmp.grow(ctx, scan_tmp_words(s.n + 1) * sizeof(uint32_t));
     if (rc)
@@ -738,12 +710,11 @@ int ensure_index(dst_ctx *ctx, DeviceSet &s, DeviceSet &refset, bool want_sites,
         return fail(ctx, DST_ERR_CAPACITY, "too many differences from the reference sequence for the consensus path");
     s.rec.total = total;
     const size_t cap = std::max<size_t>(total, 1);
-    rc = ensure_bytes(ctx, (void **)&s.rec.ent, &s.rec.ent_cap, (cap + 4) * sizeof(uint32_t));  // 16-byte reads past the end
+    rc = s.rec.ent.grow(ctx, (cap + 4) * sizeof(uint32_t));  // 16-byte reads past the end
     if (!rc && want_sites)
-        rc = ensure_bytes(ctx, (void **)&s.site.ent, &s.site.ent_cap, cap * sizeof(uint32_t));
+        rc = s.site.ent.grow(ctx, cap * sizeof(uint32_t));
     if (!rc && want_sites)
-        rc = ensure_bytes(ctx, (void **)&s.rec.range_start, &s.rec.range_cap,
-                          ((s.nchunks * kChunkSites + kBucketSites - 1) / kBucketSites) * s.npad * sizeof(uint32_t));
+        rc = s.rec.range_start.grow(ctx, ((s.nchunks * kChunkSites + kBucketSites - 1) / kBucketSites) * s.npad * sizeof(uint32_t));
     if (rc)
         return rc;
     // (the scan also clears the counters behind it: [0..1] the list total of the count pass, [2..3] the overflow entries)
@@ -762,11 +733,11 @@ int ensure_index(dst_ctx *ctx, DeviceSet &s, DeviceSet &refset, bool want_sites,
         // these lists' flavour (the hybrid path's lists leave the hot sites to the dense kernels)
         RunIndex &ru = s.runs;
         ru.mask_words = (s.nchunks + 31) / 32;
-        rc = ensure_bytes(ctx, (void **)&ru.mask, &ru.mask_cap, 2 * (size_t)ru.n_run * ru.mask_words * sizeof(uint32_t));   // by record, then transposed
+        rc = ru.mask.grow(ctx, 2 * (size_t)ru.n_run * ru.mask_words * sizeof(uint32_t));   // by record, then transposed
         if (!rc)
-            rc = ensure_bytes(ctx, (void **)&ru.known, &ru.known_cap, ((s.nchunks + 31) / 32 * 32) * sizeof(uint32_t));
+            rc = ru.known.grow(ctx, ((s.nchunks + 31) / 32 * 32) * sizeof(uint32_t));
         if (!rc)
-            rc = ensure_bytes(ctx, (void **)&ru.panel_first, &ru.panel_cap, ((size_t)n_panels + 2) * sizeof(uint32_t));
+            rc = ru.panel_first.grow(ctx, ((size_t)n_panels + 2) * sizeof(uint32_t));
         if (rc)
             return rc;
         HIP_TRY(ctx, launch_run_masks(s, stream));
@@ -798,20 +769,20 @@ int ensure_aconst(dst_ctx *ctx, DeviceSet &s, DeviceSet &refset, int family, boo
         return DST_OK;
     int rc = wait_for_other_runs(ctx, stream);  // a run on another stream may still read the old words
     if (!rc)
-        rc = ensure_bytes(ctx, (void **)&s.aconst, &s.aconst_cap, s.npad * kMaxWords * sizeof(uint32_t));
+        rc = s.aconst.grow(ctx, s.npad * kMaxWords * sizeof(uint32_t));
     if (rc)
         return rc;
     if (s.runs.active) {
         // the entries' a-words (what corr_kernel sums) and the two correction tables of this (family, packing)
         RunIndex &ru = s.runs;
         const size_t words = (size_t)family_words(family, wide);
-        rc = ensure_bytes(ctx, (void **)&ru.aent, &ru.aent_cap, (size_t)kMaxWords * std::max<size_t>(s.rec.total, 1) * sizeof(uint32_t));
+        rc = ru.aent.grow(ctx, (size_t)kMaxWords * std::max<size_t>(s.rec.total, 1) * sizeof(uint32_t));
         if (!rc)
-            rc = ensure_bytes(ctx, (void **)&ru.corr, &ru.corr_cap, words * ru.n_run * s.n * sizeof(uint32_t));
+            rc = ru.corr.grow(ctx, words * ru.n_run * s.n * sizeof(uint32_t));
         if (!rc)
-            rc = ensure_bytes(ctx, (void **)&ru.corr_t, &ru.corr_t_cap, words * ru.n_run * s.n * sizeof(uint32_t));
+            rc = ru.corr_t.grow(ctx, words * ru.n_run * s.n * sizeof(uint32_t));
         if (!rc)   // the records' per-chunk sums in 7-bit pieces: the B operand of the correction tables' matrix product
-            rc = ensure_bytes(ctx, (void **)&ru.s7, &ru.s7_cap, words * 5 * ((s.n + 31) / 32) * 1024 * ru.mask_words + 64);   // whole tiles of 32 records
+            rc = ru.s7.grow(ctx, words * 5 * ((s.n + 31) / 32) * 1024 * ru.mask_words + 64);   // whole tiles of 32 records
         if (rc)
             return rc;
     }
@@ -1275,12 +1246,10 @@ int run_host(dst_ctx *ctx, int measure, bool square, int row_slot, int col_slot,
 
 }  // namespace dst
 
-// what is no Grown or Event member: the sets, the timing events, the stream
+// what is no Grown or Event member: the timing events, the stream.  (The members, the sets' buffers among them, go after
+// this body: memory freed behind a destroyed stream, which dst_destroy's wait for the device has left idle.)
 dst_ctx::~dst_ctx()
 {
-    free_set(set[0]);
-    free_set(set[1]);
-    free_set(boot);
     for (auto &t : timer)
         for (int k = 0; k < kTimerRing; ++k) {
             if (t.begin[k])
@@ -1566,17 +1535,16 @@ int dst_consensus(dst_ctx *ctx, int both_slots, uint8_t *cons, size_t cap)
     if (a.len == 0)
         return DST_OK;
     HIP_TRY(ctx, hipSetDevice(ctx->device));
-    uint32_t *d_hist = nullptr;
+    Grown<uint32_t> d_hist;   // (this call's own: released on return, behind the wait below)
     const size_t bytes = a.len * 3 * sizeof(uint32_t);
-    HIP_TRY(ctx, hipMalloc((void **)&d_hist, bytes));
+    if (int rc = d_hist.grow(ctx, bytes))
+        return rc;
     std::vector<uint32_t> hist(a.len * 3);
     int rc_p = ensure_planes(ctx, a, ctx->stream);
     if (!rc_p && two)
         rc_p = ensure_planes(ctx, ctx->set[1], ctx->stream);
-    if (rc_p) {
-        (void)hipFree(d_hist);
+    if (rc_p)
         return rc_p;
-    }
     hipError_t e = hipMemsetAsync(d_hist, 0, bytes, ctx->stream);
     if (e == hipSuccess)
         e = launch_site_hist(a, d_hist, ctx->stream);
@@ -1586,7 +1554,6 @@ int dst_consensus(dst_ctx *ctx, int both_slots, uint8_t *cons, size_t cap)
         e = hipMemcpyAsync(hist.data(), d_hist, bytes, hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess)
         e = hipStreamSynchronize(ctx->stream);
-    (void)hipFree(d_hist);
     if (e != hipSuccess)
         return fail_hip(ctx, e, "consensus counts");
     const uint64_t records = a.n + (two ? ctx->set[1].n : 0);
@@ -1635,23 +1602,19 @@ int dst_differences(dst_ctx *ctx, int slot, const uint8_t *other, size_t len, ui
         for (int p = 0; p < 4; ++p)
             if (!((other[i] >> (7 - p)) & 1u))
                 planes[(p * s.nchunks + i / kChunkSites) * 4 + (i % kChunkSites) / 32] &= ~(1u << (i % 32));
-    uint4 *d_ref = nullptr;
-    uint32_t *d_off = nullptr, *d_ent = nullptr, *d_tmp = nullptr;
+    // this call's own buffers, released on return: every pass below ends with a wait for the stream
+    Grown<uint4> d_ref;
+    Grown<uint32_t> d_off, d_ent, d_tmp;
     std::vector<uint32_t> off32(s.n + 1);
     unsigned long long total = 0;
-    hipError_t e = hipMalloc((void **)&d_ref, planes.size() * sizeof(uint32_t));
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&d_off, (s.n + 1) * sizeof(uint32_t));
-    if (e == hipSuccess)
-        e = hipMalloc((void **)&d_tmp, scan_tmp_words(s.n + 1) * sizeof(uint32_t));
-    auto done = [&](int status) {
-        for (void *b : {(void *)d_ref, (void *)d_off, (void *)d_ent, (void *)d_tmp})
-            if (b)
-                (void)hipFree(b);
-        return status;
-    };
-    if (e == hipSuccess)
-        e = hipMemcpyAsync(d_ref, planes.data(), planes.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
+    rc = d_ref.grow(ctx, planes.size() * sizeof(uint32_t));
+    if (!rc)
+        rc = d_off.grow(ctx, (s.n + 1) * sizeof(uint32_t));
+    if (!rc)
+        rc = d_tmp.grow(ctx, scan_tmp_words(s.n + 1) * sizeof(uint32_t));
+    if (rc)
+        return rc;
+    hipError_t e = hipMemcpyAsync(d_ref, planes.data(), planes.size() * sizeof(uint32_t), hipMemcpyHostToDevice, ctx->stream);
     if (e == hipSuccess)
         e = hipMemsetAsync(d_off, 0, (s.n + 1) * sizeof(uint32_t), ctx->stream);
     if (e == hipSuccess)
@@ -1664,38 +1627,38 @@ int dst_differences(dst_ctx *ctx, int slot, const uint8_t *other, size_t len, ui
     if (e == hipSuccess)
         e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess)
-        return done(fail_hip(ctx, e, "differences (count)"));
+        return fail_hip(ctx, e, "differences (count)");
     if (total > kMaxListEntries)
-        return done(fail(ctx, DST_ERR_CAPACITY, "more than 2^31 differences"));
+        return fail(ctx, DST_ERR_CAPACITY, "more than 2^31 differences");
     e = launch_exclusive_scan(d_off, s.n + 1, d_tmp, ctx->stream);
     if (e == hipSuccess)
         e = hipMemcpyAsync(off32.data(), d_off, (s.n + 1) * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess)
         e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess)
-        return done(fail_hip(ctx, e, "differences (scan)"));
+        return fail_hip(ctx, e, "differences (scan)");
     for (size_t r = 0; r <= s.n; ++r)
         offsets[r] = off32[r];
     *total_out = total;
     if (!sites)
-        return done(DST_OK);
+        return DST_OK;
     if (cap_sites < total)
-        return done(fail(ctx, DST_ERR_CAPACITY, "sites buffer too small"));
+        return fail(ctx, DST_ERR_CAPACITY, "sites buffer too small");
     if (total == 0)
-        return done(DST_OK);
-    e = hipMalloc((void **)&d_ent, total * sizeof(uint32_t));
-    if (e == hipSuccess)
-        e = launch_index(s, d_ref, nullptr, true, true, d_off, d_ent, ctx->d_total,
+        return DST_OK;
+    if ((rc = d_ent.grow(ctx, total * sizeof(uint32_t))))
+        return rc;
+    e = launch_index(s, d_ref, nullptr, true, true, d_off, d_ent, ctx->d_total,
                          ctx->stream);
     if (e == hipSuccess)
         e = hipMemcpyAsync(sites, d_ent, total * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream);
     if (e == hipSuccess)
         e = hipStreamSynchronize(ctx->stream);
     if (e != hipSuccess)
-        return done(fail_hip(ctx, e, "differences (fill)"));
+        return fail_hip(ctx, e, "differences (fill)");
     for (uint64_t k = 0; k < total; ++k)
         sites[k] &= kSiteMask;  // drop the reference class and the nibble the pair kernel's lists carry
-    return done(DST_OK);
+    return DST_OK;
 }
 
 int dst_pair_sites(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, const uint32_t *row, const uint32_t *col,
@@ -1906,34 +1869,22 @@ int dst_run_slabs(dst_ctx *ctx, int measure, int square, int row_slot, int col_s
     if (slabs.empty())
         return DST_OK;
     const size_t bytes = dst_out_bytes(measure, out_kind, plan.biggest);
-    void *d_buf[2] = {nullptr, nullptr}, *h_buf[2] = {nullptr, nullptr};
-    hipEvent_t done[2] = {nullptr, nullptr};
+    Grown<> d_buf[2];
+    Grown<void, true> h_buf[2];
+    Event done[2];
+    // every way out waits for the stream before the buffers above are released: what is still queued may read them
+    struct WaitOnExit {
+        hipStream_t stream;
+        ~WaitOnExit() { (void)hipStreamSynchronize(stream); }
+    } const wait{ctx->stream};
     int rc = DST_OK;
-    auto cleanup = [&]() {
-        (void)hipStreamSynchronize(ctx->stream);
-        for (int k = 0; k < 2; ++k) {
-            if (d_buf[k])
-                (void)hipFree(d_buf[k]);
-            if (h_buf[k])
-                (void)hipHostFree(h_buf[k]);
-            if (done[k])
-                (void)hipEventDestroy(done[k]);
-        }
-    };
-#define SLAB_TRY(call)                                   \
-    do {                                                 \
-        hipError_t e_ = (call);                          \
-        if (e_ != hipSuccess) {                          \
-            rc = fail_hip(ctx, e_, #call);               \
-            cleanup();                                   \
-            return rc;                                   \
-        }                                                \
-    } while (0)
-    for (int k = 0; k < 2; ++k) {
-        SLAB_TRY(hipMalloc(&d_buf[k], bytes));
-        SLAB_TRY(hipHostMalloc(&h_buf[k], bytes, hipHostMallocDefault));
-        SLAB_TRY(hipEventCreateWithFlags(&done[k], hipEventDisableTiming));
+    for (int k = 0; k < 2 && !rc; ++k) {
+        rc = d_buf[k].grow(ctx, bytes);
+        if (!rc)
+            rc = h_buf[k].grow(ctx, bytes);
     }
+    if (rc)
+        return rc;
     auto issue = [&](size_t k) -> int {  // compute slab k and start its copy back, all on ctx->stream
         const RowSlab &s = slabs[k];
         const size_t nb = dst_out_bytes(measure, out_kind, s.pairs);
@@ -1943,7 +1894,7 @@ int dst_run_slabs(dst_ctx *ctx, int measure, int square, int row_slot, int col_s
             return r;
         hipError_t e = hipMemcpyAsync(h_buf[k & 1], d_buf[k & 1], nb, hipMemcpyDeviceToHost, ctx->stream);
         if (e == hipSuccess)
-            e = hipEventRecord(done[k & 1], ctx->stream);
+            e = done[k & 1].record(ctx->stream);
         return e == hipSuccess ? DST_OK : fail_hip(ctx, e, "copy back");
     };
     rc = issue(0);
@@ -1952,12 +1903,10 @@ int dst_run_slabs(dst_ctx *ctx, int measure, int square, int row_slot, int col_s
             rc = issue(k + 1);  // the other buffer pair: slab k-1's sink call has returned
         if (rc)
             break;
-        SLAB_TRY(hipEventSynchronize(done[k & 1]));
+        HIP_TRY(ctx, hipEventSynchronize(done[k & 1]));
         if (sink(user, slabs[k].first, slabs[k].pairs, slabs[k].rb, slabs[k].re, h_buf[k & 1]) != 0)
             rc = fail(ctx, DST_ERR_STATE, "stopped by sink");
     }
-#undef SLAB_TRY
-    cleanup();
     return rc;
 }
 

@@ -2394,7 +2394,7 @@ hipError_t launch_ref_sample(const DeviceSet &set, hipStream_t stream)
 {
     const uint32_t samples = (uint32_t)std::min<size_t>(set.n, kRefSamples);
     hipLaunchKernelGGL(ref_sample_kernel<false>, dim3((unsigned)set.nchunks), dim3(512), 0, stream,
-                       reinterpret_cast<const uint32_t *>(set.planes), nullptr, 0, (uint32_t)set.n, (uint32_t)set.len,
+                       reinterpret_cast<const uint32_t *>(set.planes.ptr), nullptr, 0, (uint32_t)set.n, (uint32_t)set.len,
                        (uint32_t)set.nchunks, (uint32_t)set.npad, samples, set.ref.planes, set.ref.hot_planes,
                        set.ref.partials, nullptr, 0u, nullptr);
     return hipGetLastError();
@@ -2414,14 +2414,14 @@ hipError_t launch_hot_list(const DeviceSet &set, hipStream_t stream)
 {
     hipLaunchKernelGGL(hot_list_kernel, dim3(1), dim3(1024), 0, stream, set.ref.hot_planes, (uint32_t)set.nchunks,
                        set.ref.hot_sites, set.ref.partials, (uint32_t)std::min<size_t>(set.n, kRefSamples),
-                       reinterpret_cast<unsigned long long *>(set.ref.stats));
+                       reinterpret_cast<unsigned long long *>(set.ref.stats.ptr));
     return hipGetLastError();
 }
 
 hipError_t launch_compact(const DeviceSet &src, const uint32_t *hot_sites, uint32_t n_hot, DeviceSet &dst, hipStream_t stream)
 {
     dim3 grid((unsigned)dst.nchunks, (unsigned)((dst.npad + 255) / 256));
-    hipLaunchKernelGGL(compact_kernel, grid, dim3(256), 0, stream, reinterpret_cast<const uint32_t *>(src.planes),
+    hipLaunchKernelGGL(compact_kernel, grid, dim3(256), 0, stream, reinterpret_cast<const uint32_t *>(src.planes.ptr),
                        (uint32_t)src.n, (uint32_t)src.nchunks, (uint32_t)src.npad, hot_sites, n_hot, (uint32_t)dst.nchunks,
                        (uint32_t)dst.npad, dst.planes);
     return hipGetLastError();
@@ -2546,7 +2546,7 @@ hipError_t launch_aconst(const DeviceSet &set, int family, bool wide, const Cons
 {
     RunConst rc{nullptr, 0, nullptr, nullptr, nullptr, 0};
     if (set.runs.active)
-        rc = RunConst{set.runs.aent, set.runs.aent_cap / (kMaxWords * sizeof(uint32_t)), set.runs.index, set.runs.mask, set.runs.known,
+        rc = RunConst{set.runs.aent, set.runs.aent.bytes / (kMaxWords * sizeof(uint32_t)), set.runs.index, set.runs.mask, set.runs.known,
                       (uint32_t)set.runs.mask_words};
     hipLaunchKernelGGL(aconst_kernel, dim3((unsigned)((set.n + 3) / 4)), dim3(256), 0, stream, set.rec.off,
                        set.rec.ent, d_lut, family, wide ? 1 : 0, family_words(family, wide),
@@ -2575,7 +2575,7 @@ hipError_t launch_run_tables(const DeviceSet &set, int family, bool wide, const 
         *failed = "run_panels_kernel";
         return e;
     }
-    const size_t stride = ru.aent_cap / (kMaxWords * sizeof(uint32_t));
+    const size_t stride = ru.aent.bytes / (kMaxWords * sizeof(uint32_t));
     const dim3 grid((n + 127) / 128, (ru.n_run + 127) / 128);   // corr_mfma_kernel: 128 records x 128 run records per block
 #define DST_LAUNCHED(NAME)                        \
     if ((e = hipGetLastError()) != hipSuccess) {  \
@@ -2754,7 +2754,7 @@ hipError_t launch_shared_splice(const uint32_t *gathered, const SharedLayout &la
                                 uint32_t *scan_tmp, bool with_counts, unsigned long long *report, hipStream_t stream)
 {
     const uint32_t n = (uint32_t)set.n, npad = (uint32_t)set.npad;
-    const uint32_t ent_room = (uint32_t)std::min<size_t>(set.rec.ent_cap / sizeof(uint32_t), 0xFFFFFFFFu);
+    const uint32_t ent_room = (uint32_t)std::min<size_t>(set.rec.ent.bytes / sizeof(uint32_t), 0xFFFFFFFFu);
     hipLaunchKernelGGL(shared_lengths_kernel, dim3((n + 256) / 256), dim3(256), 0, stream, gathered, lay, n, len_all,
                        with_counts ? set.counts : nullptr);
     hipError_t e = hipGetLastError();
@@ -2768,7 +2768,7 @@ hipError_t launch_shared_splice(const uint32_t *gathered, const SharedLayout &la
     hipLaunchKernelGGL(range_marks_kernel, dim3((n + 3) / 4), dim3(256), 0, stream, set.rec.off, set.rec.ent, n, npad, n_ranges,
                        set.rec.range_start, ent_room);
     hipLaunchKernelGGL(shared_report_kernel, dim3(1), dim3(64), 0, stream, gathered, lay,
-                       reinterpret_cast<const unsigned long long *>(set.ref.stats), report);
+                       reinterpret_cast<const unsigned long long *>(set.ref.stats.ptr), report);
     return hipGetLastError();
 }
 
@@ -2805,7 +2805,7 @@ hipError_t launch_site_hist(const DeviceSet &set, uint32_t *hist, hipStream_t st
     const size_t blocks = set.nchunks * ((set.n + kHistRecords - 1) / kHistRecords);
     if (blocks > 0x7FFFFFFFull)
         return hipErrorInvalidValue;
-    hipLaunchKernelGGL(site_hist_kernel, dim3((unsigned)blocks), dim3(128), 0, stream, reinterpret_cast<const uint32_t *>(set.planes),
+    hipLaunchKernelGGL(site_hist_kernel, dim3((unsigned)blocks), dim3(128), 0, stream, reinterpret_cast<const uint32_t *>(set.planes.ptr),
                        (uint32_t)set.n, (uint32_t)set.len, (uint32_t)set.nchunks, (uint32_t)set.npad, hist);
     return hipGetLastError();
 }

@@ -9,64 +9,6 @@
 
 using namespace dst;
 
-struct dst_ctx;
-
-namespace dst {
-
-// A buffer the context owns: device memory, or page-locked host memory.  Grow-only between uses: grow() keeps what is
-// big enough, else frees and allocates exactly `want` bytes (a caller that wants slack asks for it).  A failure leaves it
-// empty (capacity 0), with the runtime's sticky error cleared; `what` names the caller in the page-locked refusal
-// ("links: cannot allocate N bytes of page-locked memory").  Released when its owner goes (dst_destroy has waited for
-// the device by then), so a new buffer of the context is one member and its grow() calls, nothing else.
-struct GrownBase {
-    void *ptr = nullptr;
-    size_t bytes = 0;   // capacity
-    const bool pinned;
-    explicit GrownBase(bool pinned_) : pinned(pinned_) {}
-    GrownBase(GrownBase &&o) noexcept : ptr(o.ptr), bytes(o.bytes), pinned(o.pinned) { o.ptr = nullptr, o.bytes = 0; }
-    GrownBase &operator=(GrownBase &&o) noexcept
-    {
-        std::swap(ptr, o.ptr);   // (both of one kind: what was here goes with `o`)
-        std::swap(bytes, o.bytes);
-        return *this;
-    }
-    ~GrownBase() { (void)release(); }
-    int grow(dst_ctx *ctx, size_t want, const char *what = nullptr);
-    hipError_t release();
-};
-template <typename T = void, bool kPinned = false>
-struct Grown : GrownBase {
-    Grown() : GrownBase(kPinned) {}
-    operator T *() const { return static_cast<T *>(ptr); }
-};
-
-// An ordering event (no timing) of the context: made by its first record, destroyed with its owner.
-struct Event {
-    hipEvent_t e = nullptr;   // NULL: never recorded, nothing to wait for
-    Event() = default;
-    Event(Event &&o) noexcept : e(o.e) { o.e = nullptr; }
-    Event &operator=(Event &&o) noexcept
-    {
-        std::swap(e, o.e);
-        return *this;
-    }
-    ~Event()
-    {
-        if (e)
-            (void)hipEventDestroy(e);
-    }
-    hipError_t record(hipStream_t stream)
-    {
-        if (!e)
-            if (const hipError_t err = hipEventCreateWithFlags(&e, hipEventDisableTiming))
-                return err;
-        return hipEventRecord(e, stream);
-    }
-    operator hipEvent_t() const { return e; }
-};
-
-}  // namespace dst
-
 struct dst_ctx {
     ~dst_ctx();   // (dst_api.cpp; after dst_destroy's wait for the device)
     int device = 0;
@@ -209,7 +151,6 @@ int fail_hip(dst_ctx *ctx, hipError_t e, const char *what);
             return dst::fail_hip((ctx), e_, #call); \
     } while (0)
 
-int ensure_bytes(dst_ctx *ctx, void **ptr, size_t *have, size_t want);   // (a DeviceSet's own buffers and their *_cap)
 // The two sets of a call that takes (square, row_slot, col_slot): square means slot 0 against itself; else two different
 // slots in range.  Both must be loaded; same_len: and of one width; count_32: and of fewer than 2^32-1 records each.
 struct TwoSets {

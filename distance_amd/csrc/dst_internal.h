@@ -5,6 +5,7 @@
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
+#include <memory>
 #include <string>
 #include <unordered_map>
 #include <vector>
@@ -12,6 +13,7 @@
 #include <hip/hip_runtime.h>
 
 #include "../../include/distance_hip.h"
+#include "dst_owner.h"
 
 namespace dst {
 
@@ -68,34 +70,35 @@ constexpr int kMaxWords = 4;               // packed accumulator words per pair
 constexpr uint32_t kHotPermille = 50;      // hybrid path: a site is "hot" when more than 5 % of the sampled records deviate
                                            // (p^2 x 1.85 ps per event against 1 / 1.95e14 s per dense site and pair; 33 while an event cost 4.5 ps)
 
-struct ConsensusRef {             // the reference sequence, sampled from the set that owns it
-    uint4 *planes = nullptr;      // [4][nchunks] A,G,C,T planes of it (chunk-packed like the records'); N past len
-    uint4 *hot_planes = nullptr;  // [nchunks] bit = 1: a hot site (kHotPermille), handed to the dense kernels by the hybrid path
-    uint32_t *hot_sites = nullptr;  // [n_hot] the hot sites, ascending
-    uint32_t *partials = nullptr;   // [nchunks][2][8] every chunk's two shares of `stats` (summed by hot_list_kernel)
+// Every buffer of a set is a Grown (dst_owner.h): grown where it is needed, released with the set (free_set), read by the
+// launchers through its pointer conversion.  A capacity, where one matters, is the owner's `bytes`.
+struct ConsensusRef {             // the reference sequence, sampled from the set that owns it (buffers: alloc_ref, grow-only)
+    Grown<uint4> planes;          // [4][nchunks] A,G,C,T planes of it (chunk-packed like the records'); N past len
+    Grown<uint4> hot_planes;      // [nchunks] bit = 1: a hot site (kHotPermille), handed to the dense kernels by the hybrid path
+    Grown<uint32_t> hot_sites;    // [n_hot] the hot sites, ascending
+    Grown<uint32_t> partials;     // [nchunks][2][8] every chunk's two shares of `stats` (summed by hot_list_kernel)
     // device: {known sites, sum of deviants, sum of deviants^2, sample size, hot sites, known hot sites,
     //          sum of deviants over the cold sites, sum of deviants^2 over the cold sites}
-    uint64_t *stats = nullptr;
+    Grown<uint64_t> stats;
     uint64_t h_stats[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-    size_t nchunks = 0;
     bool valid = false;
 };
 
 struct RecordIndex {              // per record: the sites where it differs from the reference, ascending
-    uint32_t *off = nullptr;      // [n + 1]
-    uint32_t *ent = nullptr;      // site | class of the reference there << 25 | the record's nibble << 28
+    Grown<uint32_t> off;          // [n + 1]
+    Grown<uint32_t> ent;          // site | class of the reference there << 25 | the record's nibble << 28
     // list lengths counted by the pack itself against the set's own reference (cold sites / hot sites apart), with
     // their sums {cold, hot} — valid while pre_epoch == the set's epoch
-    uint4 *pre_slots = nullptr;   // [nchunks][npad] the entries themselves, by (record, chunk) (PackLists::slots)
-    size_t pre_slots_cap = 0;
-    uint32_t *pre_cold = nullptr, *pre_hot = nullptr;
+    Grown<uint4> pre_slots;       // [nchunks][npad] the entries themselves, by (record, chunk) (PackLists::slots)
+    // the pack's counters, one block cleared per upload (pack_counters, dst_api.cpp, lays it out and sets the views):
+    // pre_cold owns it and is its first array, pre_hot, pre_totals and RunIndex's cnt_run / run_cold / run_hot point into it
+    Grown<uint32_t> pre_cold;
+    uint32_t *pre_hot = nullptr;
     unsigned long long *pre_totals = nullptr;
-    size_t pre_cap = 0;
     uint64_t pre_epoch = 0, pre_total_cold = 0, pre_total_hot = 0;
     bool pre_valid = false;
-    size_t off_cap = 0, ent_cap = 0, range_cap = 0;
     // column sets: [ceil(nchunks / 8)][npad] where the record's list crosses every multiple of kBucketSites sites
-    uint32_t *range_start = nullptr;
+    Grown<uint32_t> range_start;
     uint64_t total = 0;
     const void *ref_owner = nullptr;  // the DeviceSet whose reference these lists are relative to
     uint64_t ref_epoch = 0;
@@ -117,21 +120,22 @@ struct RecordIndex {              // per record: the sites where it differs from
 // pair kernel's event waves add them to the accumulators).  Records with runs: "run records" (hot records in DESIGN.md).
 constexpr uint32_t kRunMin = 4;            // run chunks (512 sites of N) that make a record a run record
 struct RunIndex {
-    uint32_t *cnt_run = nullptr;     // [n] run chunks of every record          } counted by the pack, one block with
-    uint32_t *run_cold = nullptr;    // [n] their entries at cold sites         } the arrays below: n_alloc records
+    uint32_t *cnt_run = nullptr;     // [n] run chunks of every record          } counted by the pack: views into the
+    uint32_t *run_cold = nullptr;    // [n] their entries at cold sites         } block RecordIndex::pre_cold owns
     uint32_t *run_hot = nullptr;     // [n] ... at hot sites
-    uint32_t *index = nullptr;       // [n] run record number of a record, or 0xFFFFFFFF
-    uint32_t *ids = nullptr;         // [n] the run records, ascending
-    uint32_t *mask = nullptr;        // [n_run][mask_words] bit c: chunk c of the run record is a run chunk (from the slots' flags),
+    Grown<uint32_t> index;           // [n] run record number of a record, or 0xFFFFFFFF; owns the block `ids` is the other half of
+    uint32_t *ids = nullptr;         // [n] the run records, ascending (set by pack_queue, with `index`)
+    Grown<uint32_t> mask;            // [n_run][mask_words] bit c: chunk c of the run record is a run chunk (from the slots' flags),
                                      // then the same transposed, [mask_words][n_run]
-    uint32_t *known = nullptr;       // [nchunks] known reference sites of every chunk (cold sites only: without_hot lists)
-    uint32_t *panel_first = nullptr; // [n_panels + 1] first run record of every column panel
-    uint32_t *state = nullptr;       // device: [0] run records, [1] 1: stripping is on for this upload
-    uint32_t *aent = nullptr;        // [kMaxWords][entries] a-words of every list entry (aconst_kernel), what the tables sum
-    uint8_t *s7 = nullptr;           // [words][5][tiles of 32 records][mask_words][1 KB] every record's per-chunk sums of them, in 7-bit pieces
-    uint32_t *corr = nullptr;        // [words][n_run][n]   X's terms by (run record, record) ...
-    uint32_t *corr_t = nullptr;      // [words][n][n_run]   ... and transposed
-    size_t n_alloc = 0, mask_words = 0, mask_cap = 0, known_cap = 0, panel_cap = 0, aent_cap = 0, corr_cap = 0, corr_t_cap = 0, s7_cap = 0;   // (capacities in bytes)
+    Grown<uint32_t> known;           // [nchunks] known reference sites of every chunk (cold sites only: without_hot lists)
+    Grown<uint32_t> panel_first;     // [n_panels + 1] first run record of every column panel
+    Grown<uint32_t> state;           // device: [0] run records, [1] 1: stripping is on for this upload (grown with `index`)
+    Grown<uint32_t> aent;            // [kMaxWords][entries] a-words of every list entry (aconst_kernel), what the tables sum;
+                                     // entries = aent.bytes / (kMaxWords words): the launchers' stride
+    Grown<uint8_t> s7;               // [words][5][tiles of 32 records][mask_words][1 KB] every record's per-chunk sums of them, in 7-bit pieces
+    Grown<uint32_t> corr;            // [words][n_run][n]   X's terms by (run record, record) ...
+    Grown<uint32_t> corr_t;          // [words][n][n_run]   ... and transposed
+    size_t mask_words = 0;
     uint64_t removed = 0;            // entries the run records' lists lost (host copy: rescales the sample's statistics)
     uint32_t n_run = 0;              // host copy (0: no run records, or stripping off)
     bool active = false;             // this upload's lists are stripped of the run records' run chunks
@@ -166,17 +170,15 @@ struct SiteIndex {                // the same entries of a column set by (site, 
     // entries as record-in-panel | nibble << 11.  The pair kernel reads THIS: one request per (row entry, panel)
     // brings the whole bucket of a typical site.  A larger bucket keeps kInlineOverflowing entries inline and its
     // last word is the place of the others in `ent`.
-    uint4 *inl = nullptr;
-    uint32_t *ent = nullptr;      // overflow entries by bucket: record | nibble << 28 (any order inside a bucket)
-    size_t inl_cap = 0, ent_cap = 0;
+    Grown<uint4> inl;
+    Grown<uint32_t> ent;          // overflow entries by bucket: record | nibble << 28 (any order inside a bucket)
     uint32_t n_panels = 0;
     bool valid = false;
 };
 
 struct DeviceSet {
-    uint4 *planes = nullptr;      // PL_COUNT * nchunks * npad
-    uint32_t *counts = nullptr;   // npad x 4 {A,T,G,C}
-    size_t planes_bytes = 0, counts_cap = 0;   // what the two allocations hold (bytes; records)
+    Grown<uint4> planes;          // PL_COUNT * nchunks * npad   } kept while big enough for the next upload, else the whole
+    Grown<uint32_t> counts;       // npad x 4 {A,T,G,C}          } set is freed first (shape_set)
     size_t n = 0, len = 0, nchunks = 0, npad = 0;
     bool loaded = false;
     bool have_counts = false;
@@ -195,15 +197,14 @@ struct DeviceSet {
     RecordIndex rec;
     SiteIndex site;
     RunIndex runs;
-    uint32_t *aconst = nullptr;   // [kMaxWords][npad] packed A_k words of one measure family (see the key below)
-    size_t aconst_cap = 0;
+    Grown<uint32_t> aconst;       // [kMaxWords][npad] packed A_k words of one measure family (see the key below)
     int aconst_family = -1;       // what `aconst` currently holds: family, packing, and the lists it was summed from
     bool aconst_wide = false;
     uint64_t aconst_epoch = 0, aconst_ref_epoch = 0;
     const void *aconst_ref_owner = nullptr;
     bool aconst_without_hot = false;
     // hybrid path: the hot columns of this set (by some set's reference) as a packed set of their own
-    DeviceSet *hot = nullptr;
+    std::unique_ptr<DeviceSet> hot;
     const void *hot_ref_owner = nullptr;
     uint64_t hot_epoch = 0, hot_ref_epoch = 0;
 };

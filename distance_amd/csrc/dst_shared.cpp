@@ -32,6 +32,7 @@ int pack_from_device(dst_ctx *ctx, int slot, const uint8_t *d_codes, size_t n, s
                      const uint32_t *d_counts, hipStream_t stream);
 int shape_set(dst_ctx *ctx, DeviceSet &s, size_t n, size_t len);
 int alloc_ref(dst_ctx *ctx, DeviceSet &s);
+int pack_counters(dst_ctx *ctx, DeviceSet &s, size_t n, size_t *words);
 int ensure_lut(dst_ctx *ctx);
 int wait_for_other_runs(dst_ctx *ctx, hipStream_t stream);
 int publish_prep(dst_ctx *ctx, hipStream_t stream);
@@ -82,23 +83,11 @@ extern "C" int dst_upload_shared(dst_comm *comm, int slot, const void *d_codes_v
     const size_t count = rec_end - rec_begin;
     const size_t block_bytes = (size_t)lay.words * sizeof(uint32_t);
     // buffers: the pack's counts and slots (like pack_queue), the exchange blocks, the CSR of the whole set
-    if (s.rec.pre_cap < n + 1) {
-        if (s.rec.pre_cold)
-            HIP_TRY(ctx, hipFree(s.rec.pre_cold));
-        s.rec.pre_cold = s.rec.pre_hot = nullptr;
-        s.rec.pre_totals = nullptr;
-        s.rec.pre_cap = 0;
-        const size_t words = 5 * (n + 1) + 8 + ((2 * (n + 1)) & 1);   // (pack_queue's layout: the run-chunk counters behind the totals)
-        HIP_TRY(ctx, hipMalloc((void **)&s.rec.pre_cold, words * sizeof(uint32_t)));
-        s.rec.pre_cap = n + 1;
-    }
-    {
-        const size_t cap = s.rec.pre_cap, pad = (2 * cap) & 1;
-        s.rec.pre_hot = s.rec.pre_cold + cap;
-        s.rec.pre_totals = reinterpret_cast<unsigned long long *>(s.rec.pre_cold + 2 * cap + pad);
-    }
+    size_t counter_words = 0;
+    rc = pack_counters(ctx, s, n, &counter_words);
     const size_t n_ranges = (s.nchunks * kChunkSites + kBucketSites - 1) / kBucketSites;
-    rc = ensure_bytes(ctx, (void **)&s.rec.pre_slots, &s.rec.pre_slots_cap, s.nchunks * s.npad * sizeof(uint4));
+    if (!rc)
+        rc = s.rec.pre_slots.grow(ctx, s.nchunks * s.npad * sizeof(uint4));
     if (!rc)
         rc = sh.send.grow(ctx, block_bytes);
     if (!rc)
@@ -106,26 +95,26 @@ extern "C" int dst_upload_shared(dst_comm *comm, int slot, const void *d_codes_v
     if (!rc)
         rc = sh.off_local.grow(ctx, (lay.rmax + 2) * sizeof(uint32_t));
     if (!rc)
-        rc = ensure_bytes(ctx, (void **)&s.rec.off, &s.rec.off_cap, (n + 1) * sizeof(uint32_t));
+        rc = s.rec.off.grow(ctx, (n + 1) * sizeof(uint32_t));
     if (!rc)
-        rc = ensure_bytes(ctx, (void **)&s.rec.ent, &s.rec.ent_cap, ((size_t)lay.ent_cap * world + 4) * sizeof(uint32_t));
+        rc = s.rec.ent.grow(ctx, ((size_t)lay.ent_cap * world + 4) * sizeof(uint32_t));
     if (!rc)
-        rc = ensure_bytes(ctx, (void **)&s.site.ent, &s.site.ent_cap, (size_t)lay.ent_cap * world * sizeof(uint32_t));
+        rc = s.site.ent.grow(ctx, (size_t)lay.ent_cap * world * sizeof(uint32_t));
     if (!rc)
-        rc = ensure_bytes(ctx, (void **)&s.rec.range_start, &s.rec.range_cap, n_ranges * s.npad * sizeof(uint32_t));
+        rc = s.rec.range_start.grow(ctx, n_ranges * s.npad * sizeof(uint32_t));
     if (!rc)
         rc = ctx->scan_tmp.grow(ctx, scan_tmp_words(n + 1) * sizeof(uint32_t));
     if (rc)
         return rc;
     // ---- this rank's share: reference from the bytes, pack + count, scan, lists straight into the block
     // (the pack's counts and first-invalid-byte cell are cleared on the sample's way: no fills of their own)
-    HIP_TRY(ctx, launch_ref_sample_bytes(d_codes, row_stride, s, stream, s.rec.pre_cold, 5 * s.rec.pre_cap + ((2 * s.rec.pre_cap) & 1) + 8,
+    HIP_TRY(ctx, launch_ref_sample_bytes(d_codes, row_stride, s, stream, s.rec.pre_cold, counter_words,
                                          ctx->d_first_bad));
     HIP_TRY(ctx, launch_hot_list(s, stream));
     PackLists pl{};
     pl.ref_planes = s.ref.planes;
     pl.hot_planes = s.ref.hot_planes;
-    pl.stats = reinterpret_cast<const unsigned long long *>(s.ref.stats);
+    pl.stats = reinterpret_cast<const unsigned long long *>(s.ref.stats.ptr);
     pl.max_dev_sum = (unsigned long long)(kListsMaxDeviation * (double)len * (double)std::min<size_t>(n, kRefSamples));
     pl.cnt_cold = s.rec.pre_cold;
     pl.cnt_hot = s.rec.pre_hot;

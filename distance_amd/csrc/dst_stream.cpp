@@ -43,9 +43,13 @@ struct dst_stream {
     size_t max_records = 0, len = 0, pitch = 0;
     size_t out_bytes_per_record = 0;
     struct Slot {
-        uint8_t *h_in = nullptr, *d_in = nullptr;  // max_records x pitch codes, then max_records x 4 base counts
-        void *d_out = nullptr, *h_out = nullptr;
-        void *d_lists = nullptr, *h_lists = nullptr;   // FOR_STREAMED: max_records x k_streamed entries, device and page-locked
+        // the slot's buffers (and its set's) go with the slot: dst_stream_close, or an open that fails
+        Grown<uint8_t, true> h_in;   // max_records x pitch codes, then max_records x 4 base counts
+        Grown<uint8_t> d_in;
+        Grown<> d_out;
+        Grown<void, true> h_out;
+        Grown<> d_lists;             // FOR_STREAMED: max_records x k_streamed entries, device and page-locked
+        Grown<void, true> h_lists;
         NearestLists nl{}, h_nl{};
         // a links stream: d_lists = block counts, offsets, header (and the window, copy route), h_lists = header and window
         LinksBuffers lb{}, h_lb{};           // lb: what the kernels write (its window: h_lb's by device address, or d_lists')
@@ -53,9 +57,10 @@ struct dst_stream {
         uint64_t *d_hdr = nullptr, *h_hdr = nullptr;   // [0] the batch's links, [1] its bad-code word
         uint64_t total = 0;                  // of the collected batch
         uint64_t window_first = ~0ull;       // the first link of the window the page-locked buffer holds (~0: none)
-        unsigned long long *d_bad = nullptr, *h_bad = nullptr;
+        Grown<unsigned long long> d_bad;
+        Grown<unsigned long long, true> h_bad;
         DeviceSet set;
-        hipEvent_t h2d = nullptr, computed = nullptr, landed = nullptr;
+        Event h2d, computed, landed;   // (made by their first record, in the slot's first submit)
         size_t n = 0;
         int state = 0;  // 0 free, 1 acquired, 2 submitted, 3 collected (results still readable)
     };
@@ -68,7 +73,7 @@ struct dst_stream {
     uint32_t k = 0, k_streamed = 0;   // asked for; min(k, n_loaded): what a FOR_STREAMED batch's lists hold
     size_t n_loaded = 0;
     int W = 0;
-    void *d_lists = nullptr;          // FOR_LOADED: n_loaded x k values, indices and W tallies
+    Grown<> d_lists;                  // FOR_LOADED: n_loaded x k values, indices and W tallies
     NearestLists nl{};
     uint64_t next_ordinal = 0, submitted = 0;
     bool poisoned = false;            // a batch held an invalid code: the lists are not trustworthy
@@ -131,22 +136,8 @@ void destroy(dst_stream *s)
     for (hipStream_t st : {s->s_in, s->s_compute, s->s_out})
         if (st)
             forget_stream(s->ctx, st);
-    for (auto &sl : s->slots) {
-        if (sl.h_in) (void)hipHostFree(sl.h_in);
-        if (sl.h_out) (void)hipHostFree(sl.h_out);
-        if (sl.h_bad) (void)hipHostFree(sl.h_bad);
-        if (sl.d_in) (void)hipFree(sl.d_in);
-        if (sl.d_out) (void)hipFree(sl.d_out);
-        if (sl.d_bad) (void)hipFree(sl.d_bad);
-        if (sl.h_lists) (void)hipHostFree(sl.h_lists);
-        if (sl.d_lists) (void)hipFree(sl.d_lists);
-        free_set(sl.set);
-        for (hipEvent_t e : {sl.h2d, sl.computed, sl.landed})
-            if (e)
-                (void)hipEventDestroy(e);
-    }
-    if (s->d_lists)
-        (void)hipFree(s->d_lists);
+    s->slots.clear();   // the slots' memory, device and page-locked, their sets' and their events
+    (void)s->d_lists.release();
     for (hipStream_t st : {s->s_in, s->s_compute, s->s_out})
         if (st)
             (void)hipStreamDestroy(st);
@@ -232,11 +223,14 @@ int dst_stream_open_links(dst_ctx *ctx, int measure, double threshold, int what,
     const size_t work_bytes = counts_bytes + offsets_bytes + 256;
     hipError_t e = hipSuccess;
     for (auto &sl : s->slots) {
-        if (e == hipSuccess) e = hipMalloc(&sl.d_lists, work_bytes + (s->via_copy ? win_bytes : 0));
-        if (e == hipSuccess) e = hipHostMalloc(&sl.h_lists, 256 + win_bytes, hipHostMallocDefault);
         if (e != hipSuccess)
             break;
-        char *d = static_cast<char *>(sl.d_lists), *h = static_cast<char *>(sl.h_lists);
+        rc = sl.d_lists.grow(ctx, work_bytes + (s->via_copy ? win_bytes : 0));
+        if (!rc)
+            rc = sl.h_lists.grow(ctx, 256 + win_bytes);
+        if (rc)
+            break;
+        char *d = static_cast<char *>(sl.d_lists.ptr), *h = static_cast<char *>(sl.h_lists.ptr);
         sl.lb.counts = reinterpret_cast<uint32_t *>(d);
         sl.lb.offsets = reinterpret_cast<uint64_t *>(d + counts_bytes);
         sl.lb.grand = reinterpret_cast<uint64_t *>(d + counts_bytes + offsets_bytes);
@@ -254,9 +248,9 @@ int dst_stream_open_links(dst_ctx *ctx, int measure, double threshold, int what,
         sl.lb.row = sl.d_win.row, sl.lb.col = sl.d_win.col, sl.lb.val = sl.d_win.val, sl.lb.tal = sl.d_win.tal;
         if (e == hipSuccess) e = hipMemsetAsync(sl.lb.grand, 0, 8, s->s_compute);
     }
-    if (e != hipSuccess) {
+    if (rc || e != hipSuccess) {
         destroy(s);
-        return fail_hip(ctx, e, "dst_stream_open_links");
+        return rc ? rc : fail_hip(ctx, e, "dst_stream_open_links");
     }
     *out = s;
     return DST_OK;
@@ -311,36 +305,40 @@ int open_stream(dst_ctx *ctx, int measure, int out_kind, size_t max_records, int
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->s_out, hipStreamNonBlocking);
     const size_t in_bytes = counts_offset(s) + max_records * 16;
     const size_t out_bytes = std::max<size_t>(s->out_bytes_per_record * max_records, 16);
+    // after the first failure, the runtime's (e) or an allocation's (rc), nothing more is made; destroy() frees the rest
+    int rc = DST_OK;
+    auto grow = [&](GrownBase &b, size_t bytes) {
+        if (e == hipSuccess && !rc)
+            rc = b.grow(ctx, bytes);
+    };
     for (auto &sl : s->slots) {
-        if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_in, in_bytes, hipHostMallocDefault);
-        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_in, in_bytes);
-        if (e == hipSuccess) e = hipMalloc(&sl.d_out, out_bytes);
-        if (e == hipSuccess && closest < 0) e = hipHostMalloc(&sl.h_out, out_bytes, hipHostMallocDefault);
+        grow(sl.h_in, in_bytes);
+        grow(sl.d_in, in_bytes);
+        grow(sl.d_out, out_bytes);
+        if (closest < 0)
+            grow(sl.h_out, out_bytes);
         if (closest == DST_CLOSEST_FOR_STREAMED) {
             const uint64_t entries = (uint64_t)max_records * s->k_streamed;
             const size_t bytes = std::max<size_t>(lists_layout(nullptr, entries, s->W, sl.nl), 16);
-            if (e == hipSuccess) e = hipMalloc(&sl.d_lists, bytes);
-            if (e == hipSuccess) e = hipHostMalloc(&sl.h_lists, bytes, hipHostMallocDefault);
+            grow(sl.d_lists, bytes);
+            grow(sl.h_lists, bytes);
             lists_layout(sl.d_lists, entries, s->W, sl.nl);
             lists_layout(sl.h_lists, entries, s->W, sl.h_nl);
             sl.nl.k = sl.h_nl.k = s->k_streamed;
         }
-        if (e == hipSuccess) e = hipMalloc((void **)&sl.d_bad, sizeof(unsigned long long));
-        if (e == hipSuccess) e = hipHostMalloc((void **)&sl.h_bad, sizeof(unsigned long long), hipHostMallocDefault);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.h2d, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.computed, hipEventDisableTiming);
-        if (e == hipSuccess) e = hipEventCreateWithFlags(&sl.landed, hipEventDisableTiming);
+        grow(sl.d_bad, sizeof(unsigned long long));
+        grow(sl.h_bad, sizeof(unsigned long long));
     }
     if (closest == DST_CLOSEST_FOR_LOADED) {
         const uint64_t entries = (uint64_t)loaded.n * k;
-        if (e == hipSuccess) e = hipMalloc(&s->d_lists, std::max<size_t>(lists_layout(nullptr, entries, s->W, s->nl), 16));
+        grow(s->d_lists, std::max<size_t>(lists_layout(nullptr, entries, s->W, s->nl), 16));
         lists_layout(s->d_lists, entries, s->W, s->nl);
         s->nl.k = k;
-        if (e == hipSuccess) e = launch_nearest_init(s->nl, loaded.n, s->s_compute);
+        if (e == hipSuccess && !rc) e = launch_nearest_init(s->nl, loaded.n, s->s_compute);
     }
-    if (e != hipSuccess) {
+    if (rc || e != hipSuccess) {
         destroy(s);
-        return fail_hip(ctx, e, "dst_stream_open");
+        return rc ? rc : fail_hip(ctx, e, "dst_stream_open");
     }
     *out = s;
     return DST_OK;
@@ -396,7 +394,7 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
     if (use_base_counts)
         HIP_TRY(ctx, hipMemcpyAsync(sl.d_in + counts_offset(s), sl.h_in + counts_offset(s), n_records * 16,
                                     hipMemcpyHostToDevice, s->s_in));
-    HIP_TRY(ctx, hipEventRecord(sl.h2d, s->s_in));
+    HIP_TRY(ctx, sl.h2d.record(s->s_in));
     // compute: pack, then the batch (rows) against the loaded set (columns): streamed-major order
     HIP_TRY(ctx, hipStreamWaitEvent(s->s_compute, sl.h2d, 0));
     int rc = pack_queue(ctx, sl.set, sl.d_in, n_records, s->len, s->pitch,
@@ -419,7 +417,7 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
     if (rc)
         return rc;
     // a closest stream: the selection directly behind the batch's pair kernel, on the one compute stream
-    const uint32_t *tallies = static_cast<const uint32_t *>(sl.d_out);
+    const uint32_t *tallies = static_cast<const uint32_t *>(sl.d_out.ptr);
     if (s->closest == DST_CLOSEST_FOR_LOADED) {
         HIP_TRY(ctx, launch_nearest_stream_cols(s->measure, tallies, n_records, s->n_loaded, (uint32_t)s->next_ordinal,
                                                 sl.set.counts, loaded.counts, s->nl, s->s_compute));
@@ -443,7 +441,7 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
         sl.window_first = 0;
         s->last_collected = -1;   // the collected batch's links were valid until this submit
     }
-    HIP_TRY(ctx, hipEventRecord(sl.computed, s->s_compute));
+    HIP_TRY(ctx, sl.computed.record(s->s_compute));
     // copy-out
     HIP_TRY(ctx, hipStreamWaitEvent(s->s_out, sl.computed, 0));
     if (s->closest == kLinksStream)
@@ -459,7 +457,7 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
         HIP_TRY(ctx, hipMemcpyAsync(sl.h_nl.val, sl.nl.val, e * 8, hipMemcpyDeviceToHost, s->s_out));
         HIP_TRY(ctx, hipMemcpyAsync(sl.h_nl.tal, sl.nl.tal, e * 4 * (size_t)s->W, hipMemcpyDeviceToHost, s->s_out));
     }
-    HIP_TRY(ctx, hipEventRecord(sl.landed, s->s_out));
+    HIP_TRY(ctx, sl.landed.record(s->s_out));
     if (s->closest == DST_CLOSEST_FOR_LOADED) {
         s->next_ordinal += n_records;
         s->submitted += n_records;
