@@ -26,6 +26,8 @@ LINKS_CHUNK = 1 << 22   # DST_LINKS_CHUNK: the most links of one sink call
 STREAM_LINKS_WINDOW = 1 << 20   # DST_STREAM_LINKS_WINDOW: the default most links of one window of a links stream
 PAIR_SITES_BATCH = 1 << 20    # DST_PAIR_SITES_BATCH: the most pairs of one device batch of dst_pair_sites
 PAIR_SITES_WINDOW = 1 << 24   # DST_PAIR_SITES_WINDOW: the most entries of one device output window
+RUN_PAIRS_BATCH = 1 << 20     # DST_RUN_PAIRS_BATCH: the most pairs of one device batch of dst_run_pairs
+PAIRS_AUTO, PAIRS_DIRECT, PAIRS_SWEEP = 0, 1, 2   # DST_PAIRS_*: the routes of dst_run_pairs
 WINDOWS_MAX = 65536           # DST_WINDOWS_MAX: the most windows of one dst_run_windows call
 SUMMARY_SCALE_BITS = 37  # DST_SUMMARY_SCALE_BITS: f64 distances are summed as rint(v * 2^37)
 SUMMARY_MAX_BINS = 4096   # DST_SUMMARY_MAX_BINS
@@ -52,6 +54,12 @@ class GroupCell(C.Structure):
     """dst_group_cell"""
     _fields_ = [("pairs", C.c_uint64), ("nan_pairs", C.c_uint64), ("summable_pairs", C.c_uint64), ("links", C.c_uint64),
                 ("sum", C.c_double), ("min_bits", C.c_uint64), ("max_bits", C.c_uint64)]
+
+
+class PairsInfo(C.Structure):
+    """dst_pairs_info"""
+    _fields_ = [("route", C.c_int), ("lanes_per_pair", C.c_uint32), ("direct_pairs", C.c_uint64), ("swept_pairs", C.c_uint64),
+                ("slabs", C.c_uint64)]
 
 
 class DistanceError(RuntimeError):
@@ -137,6 +145,9 @@ _SIGS = {
     "dst_representatives": (C.c_int, [_vp, C.c_int, C.c_double, C.c_uint64, _vp, _vp, _vp, C.c_size_t, _u64p]),
     "dst_links": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_int, _vp, _vp, _u64p]),
     "dst_pair_sites": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_uint64, _vp, _vp, _vp, C.c_size_t, _u64p]),
+    "dst_run_pairs": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_uint64, C.c_int, C.c_uint64, _vp, _vp,
+                                C.c_size_t, _vp]),
+    "dst_run_pairs_lanes": (C.c_uint32, [C.c_uint64]),
     "dst_run_windows": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint32, C.c_int,
                                   _vp, C.c_size_t, _vp]),
     "dst_run_windows_host": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, C.c_uint64, _vp, _vp, C.c_uint32,

@@ -204,6 +204,101 @@ void write_links(const Run &run, double threshold, bool with_sites)
     s.out.finish();
 }
 
+// --pairs: the pair file, read before any input is opened.  One "id1<TAB>id2" per line, empty lines skipped, no header.
+struct PairFile {
+    std::string path;
+    std::vector<std::string> first, second;
+    std::vector<size_t> line;   // the line that gave the pair
+};
+
+PairFile read_pair_file(const std::string &path)
+{
+    PairFile pf;
+    pf.path = path;
+    FILE *fh = open_input(path);
+    std::string text;
+    char buf[1 << 16];
+    for (size_t got; (got = std::fread(buf, 1, sizeof buf, fh)) > 0;)
+        text.append(buf, got);
+    std::fclose(fh);
+    size_t line_no = 0;
+    for (size_t at = 0; at < text.size();) {
+        size_t end = text.find('\n', at);
+        if (end == std::string::npos)
+            end = text.size();
+        std::string line = text.substr(at, end - at);
+        at = end + 1;
+        ++line_no;
+        if (!line.empty() && line.back() == '\r')
+            line.pop_back();
+        if (line.empty())
+            continue;
+        const std::string where = "--pairs: line " + std::to_string(line_no) + " of '" + path + "' ";
+        const size_t tab = line.find('\t');
+        if (tab == std::string::npos)
+            die_message(where + "has no tab: expected 'id1<TAB>id2'");
+        if (line.find('\t', tab + 1) != std::string::npos)
+            die_message(where + "has more than two fields");
+        if (tab == 0 || tab + 1 == line.size())
+            die_message(where + "has an empty id");
+        pf.first.push_back(line.substr(0, tab));
+        pf.second.push_back(line.substr(tab + 1));
+        pf.line.push_back(line_no);
+    }
+    return pf;
+}
+
+// ... its ids as records of the inputs (one input: both ids in it; two: id1 in the first, id2 in the second), once the
+// inputs are loaded and before the device is looked at
+struct PairList {
+    std::vector<uint32_t> row, col;
+};
+
+PairList resolve_pairs(const PairFile &pf, const std::vector<Alignment> &loaded)
+{
+    // id -> (its first record, how many records carry it)
+    std::vector<std::unordered_map<std::string, std::pair<uint32_t, uint32_t>>> of(loaded.size());
+    for (size_t k = 0; k < loaded.size(); ++k)
+        for (size_t r = 0; r < loaded[k].n; ++r) {
+            const auto ins = of[k].emplace(loaded[k].ids[r], std::make_pair((uint32_t)r, 1u));
+            if (!ins.second)
+                ++ins.first->second.second;
+        }
+    const bool two = loaded.size() > 1;
+    auto record = [&](const std::string &id, size_t k, size_t line_no) -> uint32_t {
+        const std::string where = "--pairs: line " + std::to_string(line_no) + " of '" + pf.path + "' ";
+        const char *which = !two ? "" : k == 0 ? "first " : "second ";
+        const auto it = of[k].find(id);
+        if (it == of[k].end())
+            die_message(where + "names '" + id + "', which is not in the " + which + "input");
+        if (it->second.second > 1)
+            die_message(where + "names '" + id + "', which " + std::to_string(it->second.second) + " records of the " + which +
+                        "input carry");
+        return it->second.first;
+    };
+    PairList pl;
+    for (size_t e = 0; e < pf.first.size(); ++e) {
+        pl.row.push_back(record(pf.first[e], 0, pf.line[e]));
+        pl.col.push_back(record(pf.second[e], two ? 1 : 0, pf.line[e]));
+    }
+    return pl;
+}
+
+// --pairs: one line per line of the file, in its order: the two ids as given and the value from the pair's DST_OUT_TALLY
+// words (dst_run_pairs), which is the long output's text for that pair; with --sites the fourth field
+void write_pair_list(const Run &run, const PairList &pl, bool with_sites)
+{
+    const uint64_t n = pl.row.size();
+    std::vector<uint32_t> tallies(std::max<size_t>(n * run.tally_width(), 1));
+    if (n)
+        run.gpu.check(dst_run_pairs(run.gpu.h, run.measure, run.square() ? 1 : 0, 0, 1, pl.row.data(), pl.col.data(), n, DST_PAIRS_AUTO,
+                                    run.max_pairs, nullptr, tallies.data(), n, nullptr),
+                      "run pairs");
+    LineWriter out(run.wr);
+    write_pairs(run, out, pl.row.data(), pl.col.data(), tallies.data(), n, with_sites);
+    out.finish();
+}
+
 // --summary: one line per record of the first input in input order, "id, within, compared, mean" from dst_summary: the
 // records within T, the partners with a summable distance, and sum / compared printed as an f64 distance (NaN: none)
 void write_summary(const Run &run, double threshold)

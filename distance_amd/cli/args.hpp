@@ -87,10 +87,14 @@ void print_help()
         "      --mst                    Print only the edges of the minimum spanning tree of the records (pairs without a "
         "distance, NaN, are no edges: a forest then), in ascending order of (distance, first record, second record), each "
         "as the line the full run prints for that pair. One input, one GPU, no --stream and no other output mode\n"
-        "      --sites                  With one of the two pair-list outputs (the pairs within a distance, the minimum spanning "
-        "tree): a fourth field per line, the sites that separate the two "
+        "      --sites                  With one of the pair-list outputs (the pairs within a distance, the minimum spanning "
+        "tree, the pairs of --pairs): a fourth field per line, the sites that separate the two "
         "records as a comma-separated list of X<pos>Y (pos 1-based, X the first record's IUPAC letter, Y the second's; '.' "
         "when there are none): the sites the measure counts as differences\n"
+        "      --pairs <FILE>           Print only the pairs FILE names: FILE has one 'id1<TAB>id2' line per pair (no header, empty "
+        "lines skipped); with one input both ids are looked up in it, with two id1 in the first and id2 in the second. One "
+        "line per line of FILE, in its order, the two ids as given and the distance exactly as the long output prints it "
+        "for that pair (with the separating sites as a fourth field when those are asked for). One GPU, no --stream and no other output mode\n"
         "      --windows <W>            Print every pair's distance per column window instead of over the whole width: windows "
         "of W sites (an integer >= 1) starting every S sites, the last one cut at the alignment's end; a line per pair and "
         "window, 'id1, id2, window number, start, end (1-based, inclusive), distance', the distance exactly what the long "
@@ -124,7 +128,7 @@ enum Flag {
     F_STREAM, F_MEASURE, F_OUTPUT, F_THREADS, F_BATCHSIZE, F_GPUS, F_DEVICES, F_SLAB_PAIRS, F_NEAREST, F_CLOSEST, F_CLOSEST_FOR,
     F_WITHIN, F_CLUSTERS, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS, F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX,
     F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM, F_SELFTEST, F_REPRESENTATIVES,
-    F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_COUNT
+    F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_PAIRS, F_COUNT
 };
 struct FlagDef {
     const char *shown;   // "--name <value>": its first word is the flag itself
@@ -143,12 +147,12 @@ const FlagDef kFlags[F_COUNT] = {
     {"--mst", nullptr, false}, {"--sites", nullptr, false}, {"--dendrogram <linkage>", nullptr, false},
     {"--host-selftest <what>", nullptr, false}, {"--representatives <T>", nullptr, true},
     {"--windows <W>", nullptr, true}, {"--step <S>", nullptr, true}, {"--regions <FILE>", nullptr, true},
-    {"--window-nearest <K>", nullptr, true},
+    {"--window-nearest <K>", nullptr, true}, {"--pairs <FILE>", nullptr, true},
 };
 
 // what the run prints, decided once by parse_args
 enum class Mode { Pairs, Stream, Closest, Within, Nearest, Clusters, MaxDistance, Summary, Histogram, Groups, Matrix, Tree, Mst,
-                  Dendrogram, Representatives, Windows };
+                  Dendrogram, Representatives, Windows, PairList };
 
 struct Args {
     bool has[F_COUNT] = {};               // the flag was given
@@ -179,6 +183,7 @@ struct Args {
     size_t windows = 0, step = 0;         // --windows W --step S (step 0: W)
     std::string regions;                  // --regions FILE
     size_t window_nearest = 0;            // --window-nearest K (0: every pair)
+    std::string pairs;                    // --pairs FILE
     std::string selftest;
     size_t n_inputs() const { return flag_inputs.size() + pos_inputs.size(); }
     // the slab size an analysis is given: the library's own choice unless --slab-pairs was passed
@@ -265,6 +270,12 @@ std::vector<Flag> after(Flag first, std::vector<Flag> rest)
     return rest;
 }
 const Rule kRules[] = {
+    // (before every other row: a command line with --pairs is judged here first, and no other line's outcome changes; --sites
+    // is the one modifier it takes)
+    {F_PAIRS, Mode::PairList,
+     {F_STREAM, F_NEAREST, F_CLOSEST, F_CLOSEST_FOR, F_WITHIN, F_CLUSTERS, F_REPRESENTATIVES, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS,
+      F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_DENDROGRAM, F_WINDOWS,
+      F_STEP, F_REGIONS, F_WINDOW_NEAREST}, kNone, nullptr, TWO_OK, true},
     // (before every other row: a command line with --window-nearest is judged here first, and no other line's outcome changes)
     {F_WINDOW_NEAREST, Mode::Pairs, kWindowRefuses, {F_WINDOWS, F_REGIONS}, "'--windows <W>' or '--regions <FILE>'", TWO_OK, true},
     // (before every older row: a command line with one of these three flags is judged here, and no other line's outcome
@@ -283,9 +294,11 @@ const Rule kRules[] = {
     {F_GROUPS, Mode::Groups,
      {F_STREAM, F_NEAREST, F_CLOSEST, F_WITHIN, F_CLUSTERS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_MST, F_DENDROGRAM, F_MAX_DISTANCE,
       F_SITES, F_HISTOGRAM, F_SUMMARY}, kNone, nullptr, TWO_OK, true},
+    // (the message's first line is the recorded one of tests/cli_usage_outcomes.json; --pairs, the third pair-list
+    // output, is named on a line of its own)
     {F_SITES, Mode::Pairs,
      {F_STREAM, F_NEAREST, F_CLOSEST, F_CLUSTERS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_DENDROGRAM, F_SUMMARY, F_HISTOGRAM},
-     {F_MAX_DISTANCE, F_MST}, "'--max-distance <T>' or '--mst'", TWO_OK, false},
+     {F_MAX_DISTANCE, F_MST, F_PAIRS}, "'--max-distance <T>' or '--mst'\n       (or '--pairs <FILE>')", TWO_OK, false},
     {F_CLOSEST, Mode::Closest,
      {F_NEAREST, F_CLUSTERS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_MST, F_DENDROGRAM, F_MAX_DISTANCE, F_HISTOGRAM, F_SUMMARY, F_WITHIN},
      {F_STREAM}, "'--stream <stream>'", ONE_LOADED, true},
@@ -395,7 +408,7 @@ Args parse_args(int argc, char **argv)
             while (a.flag_inputs.size() < 2 && k + 1 < argc && (argv[k + 1][0] != '-' || !std::strcmp(argv[k + 1], "-")))
                 a.flag_inputs.push_back(argv[++k]);
         } else if (text(F_STREAM, a.stream) || text(F_MEASURE, a.measure) || text(F_OUTPUT, a.output) ||
-                   text(F_GROUPS, a.groups) || text(F_REGIONS, a.regions) || count(F_WINDOWS, a.windows, 1, SIZE_MAX) ||
+                   text(F_GROUPS, a.groups) || text(F_REGIONS, a.regions) || text(F_PAIRS, a.pairs) || count(F_WINDOWS, a.windows, 1, SIZE_MAX) ||
                    count(F_STEP, a.step, 1, SIZE_MAX) || count(F_THREADS, a.threads, 0, SIZE_MAX) ||
                    count(F_BATCHSIZE, a.batchsize, 0, SIZE_MAX) || count(F_SEED, a.seed, 0, SIZE_MAX) ||
                    count(F_NEAREST, a.nearest, 1, 256) || count(F_CLOSEST, a.closest, 1, 256) ||

@@ -155,6 +155,10 @@ int main(int argc, char **argv)
     GroupFile group_file;
     if (a.mode == Mode::Groups)
         group_file = read_group_file(a.groups);
+    // --pairs: likewise
+    PairFile pair_file;
+    if (a.mode == Mode::PairList)
+        pair_file = read_pair_file(a.pairs);
     // --regions: likewise
     WindowList windows;
     if (a.has[F_REGIONS])
@@ -188,6 +192,10 @@ int main(int argc, char **argv)
     std::vector<GroupLabels> group_labels;
     if (a.mode == Mode::Groups)
         group_labels = label_inputs(group_file, loaded);
+    // --pairs: the records its ids name
+    PairList pair_list;
+    if (a.mode == Mode::PairList)
+        pair_list = resolve_pairs(pair_file, loaded);
     // --windows / --regions: the windows over the width the inputs turned out to have
     if (a.has[F_REGIONS])
         check_regions(windows, loaded[0].width);
@@ -234,7 +242,8 @@ int main(int argc, char **argv)
     job.measure = measure;
     job.fmt_threads = std::max<size_t>(1, threads / gpus.size());
     const bool pair_lines = a.mode == Mode::Pairs || a.mode == Mode::Stream || a.mode == Mode::Closest ||
-                            a.mode == Mode::Within || a.mode == Mode::Nearest || a.mode == Mode::MaxDistance || a.mode == Mode::Mst;
+                            a.mode == Mode::Within || a.mode == Mode::Nearest || a.mode == Mode::MaxDistance || a.mode == Mode::Mst ||
+                            a.mode == Mode::PairList;
     if (pair_lines)   // src/lib.rs:613
         run.header(a.has[F_SITES] ? "sequence1\tsequence2\tdistance\tsites\n" : "sequence1\tsequence2\tdistance\n");
     switch (a.mode) {
@@ -244,6 +253,7 @@ int main(int argc, char **argv)
     case Mode::Representatives: write_representatives(run, a.representatives); break;
     case Mode::Mst: write_mst(run, a.has[F_SITES]); break;
     case Mode::MaxDistance: write_links(run, a.max_distance, a.has[F_SITES]); break;
+    case Mode::PairList: write_pair_list(run, pair_list, a.has[F_SITES]); break;
     case Mode::Summary: write_summary(run, a.summary); break;
     case Mode::Groups: write_groups(run, group_labels, a.has[F_GROUPS_WITHIN], a.groups_within, a.has[F_PER_RECORD]); break;
     case Mode::Histogram: write_histogram(run, a.histogram, (uint32_t)a.bins); break;

@@ -376,6 +376,139 @@ int dg_finish(dst_ctx *ctx, const DgBuffers &b, uint64_t n, int linkage, uint32_
     return DST_OK;
 }
 
+// ---- dst_run_pairs -------------------------------------------------------------------------------------
+// DST_PAIRS_AUTO compares two estimates, in nanoseconds, over the entries that have a canonical position:
+//   direct   entries x (kPairsDirectEntryNs + 2 NP nchunks cache lines (dst_pairs.hip, "memory") x kPairsLineNs)
+//   sweep    the pairs of the slabs the list touches x the cost of a swept pair + entries x kPairsSweepEntryNs
+// The constants were set from a run of tools/run_pairs_bench.py and are held to the figures of one MI355X session with them
+// built in (profiles/run_pairs/), the tools/synth
+// alignment at 50,000 x 30,000 and 10,000 x 1,000, -m n and tn93, lists of 1e3 to 1e7 random pairs:
+//   kPairsLineNs         0.0197 - 0.0211 ns per line at 30,000 sites on lists of 1e5 and 1e7 pairs
+//   kPairsDirectEntryNs  what is left of the 2.2 - 2.3 ns per entry at 1,000 sites: staging and scatter on the host
+//   kPairsSweepEntryNs   5.7 - 6.0 ns per entry at 10,000 records, 19.4 - 19.5 at 50,000 (the counting sort, the staging, the
+//                        gather from a 268 MB slab, the scatter): the larger, so that AUTO errs towards the direct route
+//   kPairsSweepIntNs,    a swept pair on the consensus path, which writes at its output's rate whatever the width, by the
+//   kPairsSweepF64Ns     slab's payload: 3.8 ps for -m n and 8.2 ps for tn93 at 50,000 records (7.2 and 15.5 ps at 10,000,
+//                        where the direct route wins at every size anyway).  n_high takes n's figure and raw, jc69 and
+//                        k80 take tn93's, the dearest finalisation: a supposition, none of the four was measured, and
+//                        neither was a slab of tallies (a call that wants the tallies), which takes the same figures.
+//                        Taken only where the slabs will run on that path: it is forced, or it is automatic and the
+//                        column set's lists exist or were counted by its upload.
+//   kPairsDenseNs        else: the dense pair kernel's 1.95e14 sites x pairs per second (kHotPermille's note in
+//                        dst_internal.h; not measured again in that session), times len
+// What the rule gives at 50,000 x 30,000 on the consensus path: the sweep from 2.5e5 listed pairs on for -m n (4.6 ms over
+// 38.6 - 20 ns) and from 1.1e6 on for tn93 (10.4 ms over 29.2 - 20 ns), beside fitted crossovers of 2.6e5 and 1.05e6;
+// at 10,000 x 1,000 never (2.3 ns per entry direct), as measured.
+constexpr double kPairsLineNs = 0.02;
+constexpr double kPairsDirectEntryNs = 1.0;
+constexpr double kPairsSweepEntryNs = 20.0;
+constexpr double kPairsSweepIntNs = 0.0037;
+constexpr double kPairsSweepF64Ns = 0.0083;
+constexpr double kPairsDenseNs = 1.0 / 1.95e5;
+
+int pairs_planes(int measure)   // M::NP of the measure's traits (dst_measures.hpp)
+{
+    return measure == DST_RAW || measure == DST_JC69 ? 5 : measure == DST_TN93 ? 3 : 4;
+}
+
+// one batch of m entries on the device (and its page-locked copy): what goes in, then what comes back
+struct PairsBatch {
+    uint32_t *row, *col;
+    uint64_t *pos, *val;
+    uint32_t *tal;
+    size_t idx_bytes, in_bytes;   // row + col; row + col + pos
+};
+size_t pairs_layout(void *base, uint64_t m, int W, PairsBatch &b)
+{
+    Carve c(base);
+    b.row = c.take<uint32_t>(m);
+    b.col = c.take<uint32_t>(m);
+    b.idx_bytes = c.used;
+    b.pos = c.take<uint64_t>(m);
+    b.in_bytes = c.used;
+    b.val = c.take<uint64_t>(m);
+    b.tal = c.take<uint32_t>(m * (size_t)W);
+    return c.used;
+}
+
+struct PairsJob {
+    dst_ctx *ctx;
+    int measure;
+    bool square;
+    DeviceSet *rows, *cols;
+    const uint32_t *row, *col;   // the caller's list
+    uint64_t *values;            // the caller's outputs (either may be NULL)
+    uint32_t *tallies;
+    int W;
+    uint32_t lanes = 0;          // of the direct kernel's last launch
+
+    // m <= DST_RUN_PAIRS_BATCH entries: entry k of the batch is list entry entry_of(k).  slab == NULL: the direct kernel;
+    // else the gather from `slab` at pos_of(k).  Waits for the results and puts them where the caller wants them.
+    template <typename EntryOf, typename PosOf>
+    int batch(uint64_t m, EntryOf entry_of, const void *slab, bool tally_slab, PosOf pos_of)
+    {
+        hipStream_t stream = ctx->stream;
+        PairsBatch d, h;
+        pairs_layout(ctx->rp_batch.ptr, m, W, d);
+        pairs_layout(ctx->rp_batch_host.ptr, m, W, h);
+        for (uint64_t k = 0; k < m; ++k) {
+            const uint64_t e = entry_of(k);
+            const uint32_t i = row[e], j = col[e];
+            const bool swap = square && i > j;   // the canonical pair (min, max): dst_nearest's rule
+            h.row[k] = swap ? j : i;
+            h.col[k] = swap ? i : j;
+            if (slab)
+                h.pos[k] = pos_of(k);
+        }
+        HIP_TRY(ctx, hipMemcpyAsync(d.row, h.row, slab ? d.in_bytes : d.idx_bytes, hipMemcpyHostToDevice, stream));
+        PairsLaunch pl{};
+        pl.rows = rows;
+        pl.cols = cols;
+        pl.row = d.row;
+        pl.col = d.col;
+        pl.pos = slab ? d.pos : nullptr;
+        pl.pairs = (uint32_t)m;
+        pl.values = values ? d.val : nullptr;
+        pl.tallies = tallies ? d.tal : nullptr;
+        pl.q_counts = rows->counts;
+        pl.t_counts = cols->counts;
+        if (slab)
+            HIP_TRY(ctx, launch_pairs_gather(measure, pl, slab, tally_slab, stream));
+        else
+            HIP_TRY(ctx, launch_pairs_direct(measure, pl, stream, &lanes));
+        if (values)
+            HIP_TRY(ctx, hipMemcpyAsync(h.val, d.val, m * 8, hipMemcpyDeviceToHost, stream));
+        if (tallies)
+            HIP_TRY(ctx, hipMemcpyAsync(h.tal, d.tal, m * 4 * (size_t)W, hipMemcpyDeviceToHost, stream));
+        HIP_TRY(ctx, hipStreamSynchronize(stream));
+        for (uint64_t k = 0; k < m; ++k) {
+            const uint64_t e = entry_of(k);
+            if (values)
+                values[e] = h.val[k];
+            if (tallies)
+                std::memcpy(tallies + e * (size_t)W, h.tal + k * (size_t)W, 4 * (size_t)W);
+        }
+        return DST_OK;
+    }
+
+    // what the direct kernel reads: the planes of the measure's traits, tn93's base counts for the values
+    int prepare_direct()
+    {
+        hipStream_t stream = ctx->stream;
+        if (int rc = order_after_prep(ctx, stream))
+            return rc;
+        const bool derived = measure != DST_N && measure != DST_N_HIGH;   // MRaw reads K, MK80 / MTN93 K, X1, X0 (, CL)
+        for (DeviceSet *s : {rows, cols}) {
+            if (int rc = derived ? ensure_derived(ctx, *s, stream) : ensure_planes(ctx, *s, stream))
+                return rc;
+            if (measure == DST_TN93 && values)
+                if (int rc = need_counts(ctx, *s, stream))
+                    return rc;
+        }
+        return DST_OK;
+    }
+};
+
 }  // namespace
 
 extern "C" {
@@ -706,6 +839,179 @@ int dst_links(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
     }
     if (n_links)
         *n_links = total;
+    return DST_OK;
+}
+
+uint32_t dst_run_pairs_lanes(uint64_t len)
+{
+    return pairs_lanes(std::max<uint64_t>((len + kChunkSites - 1) / kChunkSites, 1));
+}
+
+int dst_run_pairs(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, const uint32_t *row, const uint32_t *col,
+                  uint64_t n_pairs, int route, uint64_t max_pairs, void *values, uint32_t *tallies, size_t cap_entries,
+                  dst_pairs_info *info)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (info)
+        *info = dst_pairs_info{};
+    if (!row || !col)
+        return fail(ctx, DST_ERR_ARG, "null pointer");
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (route != DST_PAIRS_AUTO && route != DST_PAIRS_DIRECT && route != DST_PAIRS_SWEEP)
+        return fail(ctx, DST_ERR_ARG, "unknown route");
+    if (!values && !tallies)
+        return fail(ctx, DST_ERR_ARG, "values and tallies are both NULL");
+    TwoSets ts;
+    if (int rc = two_sets(ctx, square != 0, row_slot, col_slot, ts))
+        return rc;
+    DeviceSet &rows = *ts.rows, &cols = *ts.cols;
+    if (rows.partial || cols.partial)
+        return fail(ctx, DST_ERR_STATE, "a set uploaded with dst_upload_shared runs on the consensus path only (this rank holds "
+                                        "the planes of its own records)");
+    if (rows.len >= ((uint64_t)1 << 32))
+        return fail(ctx, DST_ERR_ARG, "alignments of 2^32 sites or more are beyond dst_run_pairs");
+    for (uint64_t e = 0; e < n_pairs; ++e)
+        if (row[e] >= rows.n || col[e] >= cols.n) {
+            char msg[160];
+            std::snprintf(msg, sizeof msg, "pair %llu (%u, %u) is out of range: %zu row records, %zu column records",
+                          (unsigned long long)e, row[e], col[e], rows.n, cols.n);
+            return fail(ctx, DST_ERR_ARG, msg);
+        }
+    if (n_pairs == 0)
+        return DST_OK;
+    if (cap_entries < n_pairs)
+        return fail(ctx, DST_ERR_CAPACITY, "cap_entries is below n_pairs");
+    const bool sq = square != 0;
+    const uint64_t n_cols = cols.n;
+    const int W = tally_width(measure);
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // (nothing queued earlier reads the grow-only buffers any more)
+
+    // ---- the route: every entry's canonical position and slab; the square's diagonal has neither and stays direct
+    SlabPlan plan;
+    std::vector<std::pair<uint64_t, uint64_t>> swept;   // (canonical position, list entry), the entries of a slab together
+    std::vector<uint64_t> first_of;                      // per slab of the plan: where its entries start in `swept` (+ the end)
+    std::vector<uint64_t> diagonal;
+    if (route != DST_PAIRS_DIRECT) {
+        plan = plan_slabs(sq, rows.n, n_cols, max_pairs, kClusterSlabPairs);
+        const size_t n_slabs = plan.slabs.size();
+        std::vector<uint32_t> slab_of_row(rows.n, 0);   // (a row without pairs, the square's last, is never asked for)
+        for (size_t s = 0; s < n_slabs; ++s)
+            std::fill(slab_of_row.begin() + plan.slabs[s].rb, slab_of_row.begin() + plan.slabs[s].re, (uint32_t)s);
+        first_of.assign(n_slabs + 1, 0);
+        for (uint64_t e = 0; e < n_pairs; ++e) {
+            if (sq && row[e] == col[e])
+                diagonal.push_back(e);
+            else
+                ++first_of[slab_of_row[sq ? std::min(row[e], col[e]) : row[e]] + 1];
+        }
+        double swept_pairs = 0;
+        for (size_t s = 0; s < n_slabs; ++s)
+            if (first_of[s + 1])
+                swept_pairs += (double)plan.slabs[s].pairs;
+        const uint64_t n_swept = n_pairs - diagonal.size();
+        if (route == DST_PAIRS_AUTO) {
+            const double direct_ns = (double)n_swept * (kPairsDirectEntryNs + 2.0 * pairs_planes(measure) * (double)rows.nchunks * kPairsLineNs);
+            const bool lists = ctx->path == DST_PATH_CONSENSUS || ctx->path == DST_PATH_HYBRID ||
+                               (ctx->path == DST_PATH_AUTO && (cols.rec.valid || cols.rec.pre_valid));
+            const double pair_ns = !lists ? (double)rows.len * kPairsDenseNs
+                                   : measure_is_int(measure) ? kPairsSweepIntNs : kPairsSweepF64Ns;
+            const double sweep_ns = swept_pairs * pair_ns + (double)n_swept * kPairsSweepEntryNs;
+            route = sweep_ns < direct_ns ? DST_PAIRS_SWEEP : DST_PAIRS_DIRECT;
+        }
+        if (route == DST_PAIRS_SWEEP) {
+            // a counting sort by slab: inside a slab the gather takes the entries in the list's order
+            for (size_t s = 0; s < n_slabs; ++s)
+                first_of[s + 1] += first_of[s];
+            std::vector<uint64_t> next(first_of.begin(), first_of.end() - 1);
+            swept.resize(n_swept);
+            for (uint64_t e = 0; e < n_pairs; ++e) {
+                const uint64_t i = sq ? std::min(row[e], col[e]) : row[e], j = sq ? std::max(row[e], col[e]) : col[e];
+                if (sq && i == j)
+                    continue;
+                swept[next[slab_of_row[i]]++] = {sq ? square_row_start(n_cols, i) + (j - i - 1) : i * n_cols + j, e};
+            }
+        }
+    }
+    const bool all_direct = route == DST_PAIRS_DIRECT;
+    const uint64_t n_direct = all_direct ? n_pairs : diagonal.size();
+
+    PairsJob job{ctx, measure, sq, &rows, &cols, row, col, static_cast<uint64_t *>(values), tallies, W};
+    const uint64_t mb = std::min<uint64_t>(n_pairs, DST_RUN_PAIRS_BATCH);
+    PairsBatch sizes;
+    const size_t batch_bytes = pairs_layout(nullptr, mb, W, sizes);
+    if (int rc = ctx->rp_batch.grow(ctx, batch_bytes))
+        return rc;
+    if (int rc = ctx->rp_batch_host.grow(ctx, batch_bytes, "run pairs"))
+        return rc;
+    const auto no_pos = [](uint64_t) { return (uint64_t)0; };
+    if (n_direct) {
+        if (int rc = job.prepare_direct())
+            return rc;
+        for (uint64_t e0 = 0; e0 < n_direct; e0 += mb) {
+            const uint64_t m = std::min(mb, n_direct - e0);
+            const int rc = all_direct ? job.batch(m, [&](uint64_t k) { return e0 + k; }, nullptr, false, no_pos)
+                                      : job.batch(m, [&](uint64_t k) { return diagonal[e0 + k]; }, nullptr, false, no_pos);
+            if (rc)
+                return rc;
+        }
+    }
+    uint64_t slabs_run = 0;
+    if (!all_direct && !swept.empty()) {
+        // the touched slabs, each with its range of `swept`; a request for the tallies runs the slab in tallies and the
+        // gather finalises the values from them (pair_value: no second arithmetic)
+        const bool tally_slab = tallies != nullptr;
+        const int kind = tally_slab ? DST_OUT_TALLY : DST_OUT_DISTANCE;
+        std::vector<RowSlab> walk;
+        std::vector<std::pair<uint64_t, uint64_t>> range;   // [begin, end) of `swept` per walked slab
+        uint64_t biggest = 0;
+        for (size_t s = 0; s + 1 < first_of.size(); ++s)
+            if (first_of[s + 1] > first_of[s]) {
+                walk.push_back(plan.slabs[s]);
+                range.emplace_back(first_of[s], first_of[s + 1]);
+                biggest = std::max(biggest, plan.slabs[s].pairs);
+            }
+        if (tally_slab && values && measure == DST_TN93) {
+            int rc = need_counts(ctx, rows, ctx->stream);
+            if (!rc && &cols != &rows)
+                rc = need_counts(ctx, cols, ctx->stream);
+            if (rc)
+                return rc;
+        }
+        if (int rc = slab_scratch(ctx, dst_out_bytes(measure, kind, biggest)))
+            return rc;
+        // the slabs' pair kernels are this call's own business: what the caller's last run left to ask about stays
+        const int last_path = ctx->last_path;
+        const dst_launch_info last_launch = ctx->last_launch;
+        size_t at = 0;
+        const int rc = walk_slabs(ctx, measure, sq, rows, cols, walk, kind, [&](const RowSlab &s) -> int {
+            const uint64_t a = range[at].first, b = range[at].second;
+            ++at;
+            for (uint64_t e0 = a; e0 < b; e0 += mb) {
+                const uint64_t m = std::min(mb, b - e0);
+                if (int rc2 = job.batch(m, [&](uint64_t k) { return swept[e0 + k].second; }, ctx->pair_slab.ptr, tally_slab,
+                                        [&](uint64_t k) { return swept[e0 + k].first - s.first; }))
+                    return rc2;
+            }
+            return DST_OK;
+        });
+        ctx->last_path = last_path;
+        ctx->last_launch = last_launch;
+        if (rc) {
+            (void)hipStreamSynchronize(ctx->stream);
+            return rc;
+        }
+        slabs_run = walk.size();
+    }
+    if (info) {
+        info->route = route;
+        info->lanes_per_pair = job.lanes;
+        info->direct_pairs = n_direct;
+        info->swept_pairs = n_pairs - n_direct;
+        info->slabs = slabs_run;
+    }
     return DST_OK;
 }
 

@@ -108,6 +108,10 @@ struct dst_ctx {
     // host memory
     Grown<char> ps_batch, ps_window;
     Grown<char, true> ps_batch_host, ps_window_host;
+    // dst_run_pairs: one batch of list entries (indices, slab positions, values, tallies) on the device and again in
+    // page-locked host memory
+    Grown<char> rp_batch;
+    Grown<char, true> rp_batch_host;
     // dst_run_windows / dst_window_base_counts: the window table on the device and in page-locked memory, and the per
     // (window, record) base counts (tn93)
     Grown<uint2> win_table;

@@ -506,6 +506,26 @@ hipError_t launch_pair_sites_count(int measure, const DeviceSet &rows, const Dev
 hipError_t launch_pair_sites_write(int measure, const DeviceSet &rows, const DeviceSet &cols, uint32_t pairs, const PairSitesBuffers &b,
                                    uint64_t lo, uint64_t hi, hipStream_t stream);
 
+// ---- distances of a pair list (dst_pairs.hip, driven by dst_run_pairs in dst_analysis.cpp) ----------------------------
+// One batch of at most DST_RUN_PAIRS_BATCH list entries on the device.  Direct route: entry k is the pair (row[k], col[k])
+// swept over the two records' planes.  Sweep route: entry k is entry pos[k] of a row slab that a pair kernel has just
+// written; row / col are read for tn93's base counts only.
+struct PairsLaunch {
+    const DeviceSet *rows, *cols;
+    const uint32_t *row, *col;   // [pairs] valid record indices of rows / cols
+    const uint64_t *pos;         // [pairs] positions inside the slab (the sweep route)
+    uint32_t pairs;
+    uint64_t *values;            // [pairs] DST_OUT_DISTANCE payloads, or NULL
+    uint32_t *tallies;           // [pairs][tally_width] DST_OUT_TALLY words, or NULL
+    const uint32_t *q_counts, *t_counts;   // tn93 values: the {A,T,G,C} counts of the row and the column set
+};
+// the lanes that serve one pair of the direct kernel for an alignment of `nchunks` 128-site chunks: a power of two, 1..64
+uint32_t pairs_lanes(uint64_t nchunks);
+// two packed sets of one width with the planes the measure reads stored; *lanes (may be NULL) = the launch's lanes per pair
+hipError_t launch_pairs_direct(int measure, const PairsLaunch &pl, hipStream_t stream, uint32_t *lanes);
+// tally: the slab holds DST_OUT_TALLY words (values are finalised from them), else DST_OUT_DISTANCE payloads (values only)
+hipError_t launch_pairs_gather(int measure, const PairsLaunch &pl, const void *slab, bool tally, hipStream_t stream);
+
 // ---- per-record and histogram summaries (dst_summary.hip, driven by dst_summary in dst_analysis.cpp) -------------------
 // Per row slab of DST_OUT_DISTANCE payloads (cut as for dst_clusters) up to three launches, each wanted or not: the row pass
 // (dst_clusters' geometry, one set of atomics per workgroup to its row's record), the column pass (square only: thread =

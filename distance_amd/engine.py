@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (ALLGATHER_FN, GROUP_NONE, LINKS_CHUNK, LINKS_SINK, LINKS_TALLIES, LINKS_VALUES, SLAB_SINK, DistanceError,
-                   GroupCell, LaunchInfo, SummaryTotals, load)
+                   GroupCell, LaunchInfo, PairsInfo, SummaryTotals, load)
 
 MEASURES = {"n": 0, "n_high": 1, "raw": 2, "jc69": 3, "k80": 4, "tn93": 5}
 INT_MEASURES = ("n", "n_high")
@@ -605,6 +605,43 @@ class Engine:
                                              n_pairs, offsets.ctypes.data, sites.ctypes.data, bases.ctypes.data, cap,
                                              C.byref(total)))
         return offsets, sites[:int(total.value)], bases[:int(total.value)]
+
+    def run_pairs(self, measure, row, col, square: bool = True, row_slot: int = 0, col_slot: int = 1, values: bool = True,
+                  tallies: bool = False, route: str = "auto", max_pairs: int = 0, info: bool = False):
+        """The distances of the listed pairs and only these (dst_run_pairs): values (n_pairs,) int64 / f64 and/or tallies
+        (n_pairs, width) uint32, bitwise what run_square / run_rect gives for each pair; plus the info dict when asked.
+        Pair e is record row[e] against record col[e] (square: both of slot 0, any order, repeats and row == col allowed —
+        (j, i) is the canonical pair (i, j), (i, i) the record against itself; else of row_slot and col_slot).  route:
+        "auto", "direct" (from the two records' planes) or "sweep" (gathered from the row slabs of at most max_pairs pairs
+        that the list touches; 0: the default); the result does not depend on either."""
+        m = _measure_id(measure)
+        routes = {"auto": 0, "direct": 1, "sweep": 2}
+        r = routes.get(route, route)   # (anything else goes to the library as it is: its refusal)
+        row = np.ascontiguousarray(row, np.uint32).ravel()
+        col = np.ascontiguousarray(col, np.uint32).ravel()
+        if row.size != col.size:
+            raise ValueError("row and col must have the same length")
+        n_pairs = int(row.size)
+        rbuf = row if n_pairs else np.zeros(1, np.uint32)   # (never a NULL index array, also for an empty list)
+        cbuf = col if n_pairs else np.zeros(1, np.uint32)
+        width = self._lib.dst_tally_width(m)
+        val = np.zeros(n_pairs, np.int64 if m in (0, 1) else np.float64) if values else None
+        tal = np.zeros((n_pairs, width), np.uint32) if tallies else None
+        pi = PairsInfo()
+        # (an empty output array still has an address: NULL means "not wanted")
+        vptr = (val.ctypes.data if n_pairs else rbuf.ctypes.data) if values else None
+        tptr = (tal.ctypes.data if n_pairs else rbuf.ctypes.data) if tallies else None
+        self._check(self._lib.dst_run_pairs(self._h, m, int(square), row_slot, col_slot, rbuf.ctypes.data, cbuf.ctypes.data,
+                                            n_pairs, int(r), int(max_pairs), vptr, tptr, n_pairs, C.byref(pi)))
+        out = ()
+        if values:
+            out += (val,)
+        if tallies:
+            out += (tal,)
+        if info:
+            out += ({"route": {1: "direct", 2: "sweep"}.get(pi.route, pi.route), "lanes_per_pair": int(pi.lanes_per_pair),
+                     "direct_pairs": int(pi.direct_pairs), "swept_pairs": int(pi.swept_pairs), "slabs": int(pi.slabs)},)
+        return out[0] if len(out) == 1 else out
 
     def run_windows(self, measure, windows, square: bool = True, row_slot: int = 0, col_slot: int = 1, row_begin: int = 0,
                     row_end: int | None = None, tallies: bool = False) -> np.ndarray:

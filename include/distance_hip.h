@@ -582,6 +582,58 @@ int dst_links(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
 int dst_pair_sites(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
                    const uint32_t *row, const uint32_t *col, uint64_t n_pairs,
                    uint64_t *offsets, uint32_t *sites, uint8_t *bases, size_t cap_entries, uint64_t *total);
+/* ---- distances of a list of pairs ------------------------------------------------------------------ */
+/* The distance of THESE pairs and only these (contact-traced pairs, the edges of a tree or a network another tool built, a
+ * k-nearest-neighbour graph that needs exact distances, "tn93 for the 3 million links -m n --max-distance 5 gave me"): the
+ * value of dst_run_square / dst_run_rect for a list of pairs the caller names, without the all-pairs result.  The
+ * definition is fixed to the bit.
+ *   pairs    dst_pair_sites': square != 0: both indices address slot 0 (row_slot / col_slot ignored); any row[e], col[e]
+ *            below n, in any order, repeated pairs allowed, and row[e] == col[e].  square == 0: row[e] indexes row_slot,
+ *            col[e] indexes col_slot; equal slots are DST_ERR_ARG.  The sets are resolved as in dst_nearest, with its
+ *            messages, in its order.
+ *   result   (host memory) values[e]: the 8-byte DST_OUT_DISTANCE payload (int64 for n / n_high, else f64) that
+ *            dst_run_square / dst_run_rect returns for the pair, bitwise; tallies[e * W ..], W = dst_tally_width(measure):
+ *            bitwise its DST_OUT_TALLY words.  Either pointer may be NULL; both NULL is DST_ERR_ARG.
+ *            square, row[e] > col[e]: the result of the canonical pair (min, max), tn93 base counts in that order
+ *            (dst_nearest's rule), so (j, i) equals (i, j).
+ *            square, row[e] == col[e]: the record against itself.  Tallies: the sum over the sites of
+ *            dst_site_tallies(code, code); value: the device finalisation of those tallies with the record's base counts on
+ *            both sides — bitwise what dst_run_rect returns for (i, i) when the same set is also loaded in the other slot.
+ *   route    how the entries are computed; the result does not depend on it, nor on max_pairs, the kernel path, the order
+ *            of the list or how it is batched.
+ *              DST_PAIRS_DIRECT  every pair from the bit-planes of its two records (a gather; work ~ pairs x len)
+ *              DST_PAIRS_SWEEP   the row slabs of the all-pairs result that the list touches are run (at most max_pairs
+ *                                pairs each, 0: 2^25, at least one row; a slab no listed pair falls into is skipped) and
+ *                                the listed entries are gathered from each slab on the device.  The square's diagonal
+ *                                entries have no place in that result: they take the direct route whatever `route` says.
+ *              DST_PAIRS_AUTO    the cheaper of the two by a cost estimate
+ *   info     (may be NULL) the route taken (DST_PAIRS_DIRECT or DST_PAIRS_SWEEP), the lanes that served one pair in the
+ *            direct kernel's last launch (0: none ran; dst_run_pairs_lanes(len)), the pairs that went each way, the slabs
+ *            the sweep ran.
+ * n_pairs == 0: DST_OK, nothing written.  DST_ERR_ARG: a NULL ctx, row or col; an unknown measure or route; both outputs
+ * NULL; a bad slot; an index out of range (the message names the first such pair, as dst_pair_sites does); len >= 2^32.
+ * DST_ERR_CAPACITY: cap_entries < n_pairs (nothing written).  DST_ERR_STATE: a set is not uploaded, the widths differ, or a
+ * set came from dst_upload_shared (it holds no planes: the dense kernels' refusal, same message).  Synchronous on the
+ * context's stream.  A set with deferred planes gets them when the direct route first reads them, and the derived planes
+ * where the measure reads them (raw, jc69, k80, tn93); slots, the path choice, dst_last_path, dst_last_launch and later
+ * results are untouched.  Device memory besides the sets is bounded whatever n_pairs: the pairs go to the device in batches of
+ * at most DST_RUN_PAIRS_BATCH and the results come back the same way, through page-locked staging; the sweep adds one
+ * slab.  Single GPU, loaded sets only (not dst_stream). */
+typedef struct {
+    int route;                /* DST_PAIRS_DIRECT or DST_PAIRS_SWEEP: what the call did */
+    uint32_t lanes_per_pair;  /* of the direct kernel's last launch, 0: none ran */
+    uint64_t direct_pairs, swept_pairs, slabs;
+} dst_pairs_info;
+#define DST_PAIRS_AUTO 0
+#define DST_PAIRS_DIRECT 1
+#define DST_PAIRS_SWEEP 2
+#define DST_RUN_PAIRS_BATCH (1u << 20) /* most pairs of one device batch */
+int dst_run_pairs(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
+                  const uint32_t *row, const uint32_t *col, uint64_t n_pairs, int route, uint64_t max_pairs,
+                  void *values, uint32_t *tallies, size_t cap_entries, dst_pairs_info *info);
+/* Pure host code: the lanes the direct route gives one pair for an alignment of len sites — the smallest power of two that
+ * covers its 128-site chunks, at most 64. */
+uint32_t dst_run_pairs_lanes(uint64_t len);
 /* ---- distances per column window ------------------------------------------------------------------- */
 /* Distances ALONG the alignment (recombination scans: a query against a panel in windows of 500-1,000 sites sliding by
  * 100-200; per-gene or per-region distances; the genome without its masked ends), from the bit-planes the GPU already
