@@ -130,6 +130,9 @@ _SIGS = {
     "dst_stream_open_links": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, C.c_uint64, C.c_size_t, C.c_int, C.c_int, C.POINTER(_vp)]),
     "dst_stream_links_batch": (C.c_int, [_vp, C.c_uint64, _u64p, _u64p, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "dst_stream_links_stats": (C.c_int, [_vp, _u64p, _u64p]),
+    "dst_stream_open_window_closest": (C.c_int, [_vp, C.c_int, C.c_uint32, _vp, _vp, C.c_uint32, C.c_uint64, C.c_size_t, C.c_int,
+                                                 C.c_int, C.POINTER(_vp)]),
+    "dst_stream_window_closest_result": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _u32p]),
     "dst_comm_unique_id": (C.c_int, [_vp, C.c_size_t]),
     "dst_comm_create": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(_vp)]),
     "dst_comm_create_custom": (C.c_int, [_vp, C.c_int, C.c_int, ALLGATHER_FN, _vp, C.POINTER(_vp)]),

@@ -109,6 +109,10 @@ void print_help()
         "of the first input in every window (of the same file with one input, of the second file with two): per record and "
         "window the K lines of the plain --windows / --regions run with the smallest distance, nearest first, ties in input "
         "order\n"
+        "      --window-closest <K>     Stream mode, with --windows or --regions: for every loaded record and every window the K "
+        "(1-256) nearest STREAMED records, written when the stream ends: byte for byte what '--window-nearest K loaded.fasta "
+        "streamed.fasta' prints, for a streamed file that need not fit on the GPU. Requires --stream, one loaded file, one "
+        "GPU, no other output mode\n"
         "      --dendrogram <linkage>   Print the rooted hierarchical-clustering tree of the records as one Newick line instead "
         "of distances: linkage average (UPGMA), weighted (WPGMA) or complete. One input, one GPU, no --stream and no other "
         "output mode\n"
@@ -128,7 +132,7 @@ enum Flag {
     F_STREAM, F_MEASURE, F_OUTPUT, F_THREADS, F_BATCHSIZE, F_GPUS, F_DEVICES, F_SLAB_PAIRS, F_NEAREST, F_CLOSEST, F_CLOSEST_FOR,
     F_WITHIN, F_CLUSTERS, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS, F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX,
     F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM, F_SELFTEST, F_REPRESENTATIVES,
-    F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_PAIRS, F_COUNT
+    F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_PAIRS, F_WINDOW_CLOSEST, F_COUNT
 };
 struct FlagDef {
     const char *shown;   // "--name <value>": its first word is the flag itself
@@ -147,12 +151,12 @@ const FlagDef kFlags[F_COUNT] = {
     {"--mst", nullptr, false}, {"--sites", nullptr, false}, {"--dendrogram <linkage>", nullptr, false},
     {"--host-selftest <what>", nullptr, false}, {"--representatives <T>", nullptr, true},
     {"--windows <W>", nullptr, true}, {"--step <S>", nullptr, true}, {"--regions <FILE>", nullptr, true},
-    {"--window-nearest <K>", nullptr, true}, {"--pairs <FILE>", nullptr, true},
+    {"--window-nearest <K>", nullptr, true}, {"--pairs <FILE>", nullptr, true}, {"--window-closest <K>", nullptr, true},
 };
 
 // what the run prints, decided once by parse_args
 enum class Mode { Pairs, Stream, Closest, Within, Nearest, Clusters, MaxDistance, Summary, Histogram, Groups, Matrix, Tree, Mst,
-                  Dendrogram, Representatives, Windows, PairList };
+                  Dendrogram, Representatives, Windows, PairList, WindowClosest };
 
 struct Args {
     bool has[F_COUNT] = {};               // the flag was given
@@ -183,6 +187,7 @@ struct Args {
     size_t windows = 0, step = 0;         // --windows W --step S (step 0: W)
     std::string regions;                  // --regions FILE
     size_t window_nearest = 0;            // --window-nearest K (0: every pair)
+    size_t window_closest = 0;            // --window-closest K (stream mode)
     std::string pairs;                    // --pairs FILE
     std::string selftest;
     size_t n_inputs() const { return flag_inputs.size() + pos_inputs.size(); }
@@ -270,6 +275,15 @@ std::vector<Flag> after(Flag first, std::vector<Flag> rest)
     return rest;
 }
 const Rule kRules[] = {
+    // (before every other row: a command line with --window-closest is judged here first, and no other line's outcome
+    // changes.  It is the one flag that takes --windows / --regions into stream mode: check_rules lets those two rows pass
+    // --stream, and keep their hands off the mode, when it is there.  Two rows: what it needs is two things.)
+    {F_WINDOW_CLOSEST, Mode::Pairs,
+     {F_WINDOW_NEAREST, F_NEAREST, F_CLOSEST, F_CLOSEST_FOR, F_WITHIN, F_CLUSTERS, F_REPRESENTATIVES, F_MAX_DISTANCE, F_SUMMARY,
+      F_GROUPS, F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES,
+      F_DENDROGRAM, F_PAIRS},
+     {F_WINDOWS, F_REGIONS}, "'--windows <W>' or '--regions <FILE>'", ONE_LOADED, true},
+    {F_WINDOW_CLOSEST, Mode::WindowClosest, kNone, {F_STREAM}, "'--stream <stream>'", ONE_LOADED, true},
     // (before every other row: a command line with --pairs is judged here first, and no other line's outcome changes; --sites
     // is the one modifier it takes)
     {F_PAIRS, Mode::PairList,
@@ -334,8 +348,10 @@ void check_rules(Args &a)
         if (!a.has[r.flag])
             continue;
         const std::string self = std::string("the argument '") + kFlags[r.flag].shown + "'";
+        // (--windows / --regions in stream mode: with --window-closest, whose rows have spoken by now)
+        const bool window_stream = a.has[F_WINDOW_CLOSEST] && (r.flag == F_WINDOWS || r.flag == F_REGIONS);
         for (const Flag other : r.refuses)
-            if (a.has[other])
+            if (a.has[other] && !(window_stream && other == F_STREAM))
                 die_usage(self + " cannot be used with '" + kFlags[other].shown + "'");
         if (!r.needs.empty() && std::none_of(r.needs.begin(), r.needs.end(), [&](Flag f) { return a.has[f]; }))
             die_usage(self + " requires " + r.needs_shown);
@@ -346,7 +362,7 @@ void check_rules(Args &a)
         if (r.one_gpu && many_gpus)
             die_usage(self + " cannot be used with '" + kFlags[a.devices.size() > 1 ? F_DEVICES : F_GPUS].shown +
                       "' naming more than one GPU");
-        if (r.mode != Mode::Pairs)
+        if (r.mode != Mode::Pairs && !window_stream)
             a.mode = r.mode;   // the modes refuse each other: at most one row gets here
     }
 }
@@ -412,7 +428,7 @@ Args parse_args(int argc, char **argv)
                    count(F_STEP, a.step, 1, SIZE_MAX) || count(F_THREADS, a.threads, 0, SIZE_MAX) ||
                    count(F_BATCHSIZE, a.batchsize, 0, SIZE_MAX) || count(F_SEED, a.seed, 0, SIZE_MAX) ||
                    count(F_NEAREST, a.nearest, 1, 256) || count(F_CLOSEST, a.closest, 1, 256) ||
-                   count(F_WINDOW_NEAREST, a.window_nearest, 1, 256) ||
+                   count(F_WINDOW_NEAREST, a.window_nearest, 1, 256) || count(F_WINDOW_CLOSEST, a.window_closest, 1, 256) ||
                    count(F_BINS, a.bins, 1, DST_SUMMARY_MAX_BINS) || count(F_BOOTSTRAP, a.bootstrap, 1, 10000) ||
                    threshold(F_CLUSTERS, a.clusters) || threshold(F_REPRESENTATIVES, a.representatives) || threshold(F_MAX_DISTANCE, a.max_distance) ||
                    threshold(F_WITHIN, a.within) || threshold(F_SUMMARY, a.summary) ||

@@ -199,7 +199,7 @@ int main(int argc, char **argv)
     // --windows / --regions: the windows over the width the inputs turned out to have
     if (a.has[F_REGIONS])
         check_regions(windows, loaded[0].width);
-    else if (a.mode == Mode::Windows)
+    else if (a.mode == Mode::Windows || a.mode == Mode::WindowClosest)
         windows = sliding_windows(loaded[0].width, a.windows, a.has[F_STEP] ? a.step : a.windows);
     Writer wr;
     if (a.has[F_OUTPUT]) {
@@ -276,7 +276,8 @@ int main(int argc, char **argv)
     case Mode::Pairs: run_load_mode(gpus, job, loaded, run.tn93, a, wr); break;
     case Mode::Stream:
     case Mode::Closest:
-    case Mode::Within: StreamRun(a, gpus, loaded[0], counts[0], job, stream_fh, table, parse_threads, wr).run(); break;
+    case Mode::WindowClosest:
+    case Mode::Within: StreamRun(a, gpus, loaded[0], counts[0], job, stream_fh, table, parse_threads, wr, &windows).run(); break;
     }
     timer.mark("compute + format + write");
     wr.flush();

@@ -3,6 +3,7 @@
 #pragma once
 #include <map>
 
+#include "analyses.hpp"
 #include "args.hpp"
 #include "slabs.hpp"
 
@@ -43,6 +44,10 @@ struct StreamRun {
     // --closest for the loaded records: the lists stay on the GPU until the stream ends (one GPU, so submission order is
     // stream order)
     const bool closest_loaded;
+    // --window-closest: likewise, one list per (loaded record, window) of `windows`
+    const WindowList *const windows;
+    const bool window_closest;
+    const bool keep_ids;                   // the final lines name streamed records: their ids stay, in one arena
 
     std::mutex qmu;                        // reader -> dispatcher -> per-GPU input queues
     std::condition_variable qcv;
@@ -64,14 +69,16 @@ struct StreamRun {
     std::vector<uint32_t> kept_counts;
 
     StreamRun(const Args &args, std::vector<Ctx> &g, const Alignment &loaded, const std::vector<uint32_t> &counts, const Job &j,
-              FILE *stream_fh, const uint8_t *tab, size_t threads, Writer &w)
+              FILE *stream_fh, const uint8_t *tab, size_t threads, Writer &w, const WindowList *wl = nullptr)
         : a(args), gpus(g), ref(loaded), ref_counts(tn93_counts(j.measure, counts, counts)), job(j), measure(j.measure),
           tn93(j.measure == DST_TN93), fh(stream_fh), table(tab), parse_threads(threads), wr(w), G(g.size()),
           TW((size_t)dst_tally_width(j.measure)),
           batch_records(std::max<size_t>(1, std::min<size_t>({(size_t)4096, args.slab_pairs / std::max<size_t>(loaded.n, 1),
                                                               ((size_t)512 << 20) / std::max<size_t>(loaded.width, 1)}))),
           nibbles(!(std::getenv("DISTANCE_WIRE") && std::strcmp(std::getenv("DISTANCE_WIRE"), "codes") == 0)),
-          closest_loaded(args.mode == Mode::Closest && args.closest_side == DST_CLOSEST_FOR_LOADED), gq(G), gdone(G, false),
+          closest_loaded(args.mode == Mode::Closest && args.closest_side == DST_CLOSEST_FOR_LOADED), windows(wl),
+          window_closest(args.mode == Mode::WindowClosest),
+          keep_ids(closest_loaded || window_closest), gq(G), gdone(G, false),
           window(G * (kDepth + 2)), streams(G, nullptr)
     {
     }
@@ -249,9 +256,10 @@ struct StreamRun {
         gpus[g].check(dst_stream_collect(streams[g], &n_rec, &res), "stream collect");
         Item it = std::move(inflight.front());
         inflight.pop_front();
-        hand_over(it.idx, a.mode == Mode::Within    ? collect_within(g, it)
-                          : a.mode == Mode::Closest ? collect_closest(g, it, n_rec)
-                                                    : collect_matrix(it, res));
+        hand_over(it.idx, a.mode == Mode::Within          ? collect_within(g, it)
+                          : a.mode == Mode::Closest       ? collect_closest(g, it, n_rec)
+                          : a.mode == Mode::WindowClosest ? std::vector<TextBuf>()   // (the lines follow the stream's end)
+                                                          : collect_matrix(it, res));
     }
 
     // one GPU's worker: its queue's batches through its pipeline, kDepth - 1 in flight
@@ -281,15 +289,17 @@ struct StreamRun {
             gpus[g].check(dst_stream_acquire(streams[g], &buf, &pitch, &cbuf), "stream acquire");
             const Alignment &al = *it.batch;
             pack(al, buf, pitch);
-            if (tn93)
+            // (a window-closest stream counts per window on the device: the caller's counts are not read)
+            const bool send_counts = tn93 && !window_closest;
+            if (send_counts)
                 std::memcpy(cbuf, al.counts.data(), al.n * 4 * sizeof(uint32_t));
-            gpus[g].check(dst_stream_submit(streams[g], al.n, tn93 ? 1 : 0), "stream submit");
-            if (closest_loaded) {   // ordinal = position in submission order: keep what the final lines need
+            gpus[g].check(dst_stream_submit(streams[g], al.n, send_counts ? 1 : 0), "stream submit");
+            if (keep_ids) {   // ordinal = position in submission order: keep what the final lines need
                 for (size_t r = 0; r < al.n; ++r) {
                     kept_ids.insert(kept_ids.end(), al.ids[r].begin(), al.ids[r].end());
                     kept_off.push_back(kept_ids.size());
                 }
-                if (tn93)
+                if (send_counts)
                     kept_counts.insert(kept_counts.end(), al.counts.begin(), al.counts.end());
                 it.batch.reset();
             }
@@ -340,6 +350,54 @@ struct StreamRun {
         out.finish();
     }
 
+    // --window-closest K: every loaded record in input order and every window in the given order with its k_used nearest
+    // streamed records, each as the line '--window-nearest K loaded streamed' prints for it: the value from the entry's
+    // DST_OUT_TALLY words and, for tn93, the loaded record's base counts inside the window (dst_window_base_counts) and the
+    // streamed record's, which the lists carry (the batch is gone), through dst_finalize and the long output's formatter
+    void write_window_closest()
+    {
+        static const char header[] = "sequence1\tsequence2\twindow\tstart\tend\tdistance\n";
+        wr.write(header, sizeof header - 1);
+        if (ref.n == 0 || kept_off.size() < 2)
+            return;
+        const WindowList &wl = *windows;
+        const size_t nw = wl.begin.size();
+        const size_t cap = ref.n * nw * std::min<size_t>(a.window_closest, kept_off.size() - 1);
+        std::vector<uint32_t> index(cap), tal(cap * TW), counts(tn93 ? cap * 4 : 0), row_counts(tn93 ? nw * ref.n * 4 : 0);
+        uint32_t ku = 0;
+        gpus[0].check(dst_stream_window_closest_result(streams[0], index.data(), tal.data(), nullptr,
+                                                       tn93 ? counts.data() : nullptr, cap, &ku),
+                      "stream window closest result");
+        if (tn93)
+            gpus[0].check(dst_window_base_counts(gpus[0].h, 0, wl.begin.data(), wl.end.data(), (uint32_t)nw, row_counts.data(),
+                                                 row_counts.size()),
+                          "window base counts");
+        LineWriter out(wr);
+        size_t e = 0;
+        for (size_t i = 0; i < ref.n; ++i)
+            for (size_t w = 0; w < nw; ++w)
+                for (size_t r = 0; r < ku; ++r, ++e) {
+                    const size_t o = index[e];
+                    double f = 0;
+                    int64_t iv = 0;
+                    dst_finalize(measure, &tal[e * TW], tn93 ? &row_counts[(w * ref.n + i) * 4] : nullptr,
+                                 tn93 ? &counts[e * 4] : nullptr, &f, &iv);
+                    out.put(ref.ids[i]);
+                    out.put('\t');
+                    out.put(kept_ids.data() + kept_off[o], (size_t)(kept_off[o + 1] - kept_off[o]));
+                    out.put('\t');
+                    out.put(wl.names[w]);
+                    out.put('\t');
+                    out.number(wl.begin[w] + 1);
+                    out.put('\t');
+                    out.number(wl.end[w]);
+                    out.put('\t');
+                    out.distance(measure, f, iv);
+                    out.end_line();
+                }
+        out.finish();
+    }
+
     void run()
     {
         std::thread reader([this] { read(); });
@@ -348,6 +406,10 @@ struct StreamRun {
             gpus[g].check(a.mode == Mode::Closest
                               ? dst_stream_open_closest(gpus[g].h, measure, (uint32_t)a.closest, a.closest_side, batch_records,
                                                         kDepth, wire, &streams[g])
+                          : window_closest
+                              ? dst_stream_open_window_closest(gpus[g].h, measure, (uint32_t)a.window_closest, windows->begin.data(),
+                                                               windows->end.data(), (uint32_t)windows->begin.size(),
+                                                               a.analysis_slab(), batch_records, kDepth, wire, &streams[g])
                           : a.mode == Mode::Within
                               ? dst_stream_open_links(gpus[g].h, measure, a.within, DST_LINKS_TALLIES, 0, batch_records, kDepth,
                                                       wire, &streams[g])
@@ -363,6 +425,8 @@ struct StreamRun {
             t.join();
         if (closest_loaded)
             write_closest_loaded();
+        if (a.mode == Mode::WindowClosest)
+            write_window_closest();
         for (size_t g = 0; g < G; ++g)
             dst_stream_close(streams[g]);
         reader.join();

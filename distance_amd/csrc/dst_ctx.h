@@ -168,6 +168,10 @@ int ensure_planes(dst_ctx *ctx, DeviceSet &s, hipStream_t stream);
 int ensure_derived(dst_ctx *ctx, DeviceSet &s, hipStream_t stream);
 // data another run's stream derived (lists, constants, counts, planes): `stream` waits for it on the device (dst_api.cpp)
 int order_after_prep(dst_ctx *ctx, hipStream_t stream);
+// behind a launch on `stream` that reads a set: what a later rebuild of the set's derived data on another stream waits for
+int note_run(dst_ctx *ctx, hipStream_t stream);
+// every window a column range [begin, end) of an alignment of len sites, else DST_ERR_ARG naming the first (dst_windows.hip)
+int windows_valid(dst_ctx *ctx, const uint64_t *wb, const uint64_t *we, uint32_t n_windows, uint64_t len);
 void free_set(DeviceSet &s);
 // forget the mark of a stream that is idle and about to be destroyed (dst_ctx::Mark; dst_api.cpp)
 void forget_stream(dst_ctx *ctx, hipStream_t stream);

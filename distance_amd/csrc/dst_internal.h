@@ -696,6 +696,26 @@ constexpr uint64_t kWindowNearestListsMax = (uint64_t)1 << 31;   // lists of one
 hipError_t launch_window_nearest(int measure, const uint32_t *slab, const uint4 *q_counts, const uint4 *t_counts, uint64_t q_n,
                                  uint64_t n_cols, uint64_t row0, uint64_t nr, uint32_t win0, uint32_t nw, bool square,
                                  const NearestLists &nl, hipStream_t stream);
+// The rows x windows of a job cut into ranges whose tallies (x n_cols column records) fit max_entries (0: 2^25): whole
+// row ranges of all the windows while a row's windows fit the budget, else a few rows (the sweep's tile holds eight) of
+// a range of windows; at least one (row, window) (dst_nearest_windows, window-closest streams; dst_windows.hip)
+struct WindowSlabs {
+    uint64_t rows;   // rows of a slab (the last one of a job may hold fewer)
+    uint32_t wins;   // windows of a slab (likewise)
+};
+WindowSlabs cut_window_slabs(uint64_t n_rows, uint32_t n_windows, uint64_t n_cols, uint64_t max_entries);
+
+// ---- k nearest streamed records per window (dst_window_nearest_stream.hip, driven by dst_stream.cpp) ------------------
+// The merge of one batch into the lists of a window-closest stream.  The slab is the one above with the batch as the
+// column set: loaded rows [row0, row0 + nr) x windows [win0, win0 + nw) x n_batch records.  List i * n_windows + w of nl
+// (k entries each; q_n * n_windows <= 2^31) is loaded, offered the batch's candidates with the ordinals first_ordinal + j
+// (<= 2^32-2) and stored.  q_counts: the loaded set's per-window table [n_windows][q_n], t_counts: the batch's
+// [n_windows][n_batch], cnt: the listed streamed records' counts, 4 words per entry (all three tn93 only, else unused).
+// Launches that share lists must follow one another on one stream.
+hipError_t launch_window_nearest_stream(int measure, const uint32_t *slab, const uint4 *q_counts, const uint4 *t_counts,
+                                        uint64_t q_n, uint64_t n_batch, uint64_t row0, uint64_t nr, uint32_t win0, uint32_t nw,
+                                        uint32_t n_windows, uint32_t first_ordinal, const NearestLists &nl, uint32_t *cnt,
+                                        hipStream_t stream);
 
 // ---- host-only logic (dst_host.cpp) ----------------------------------------------------------
 int tally_width(int measure);

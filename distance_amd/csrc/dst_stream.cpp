@@ -27,6 +27,12 @@
 // page-locked window through its device address, and a one-thread launch puts the batch's total beside the bad-code word,
 // so that the copy-out stream carries 16 bytes per batch.  (DST_STREAM_LINKS_COPY, a measurement knob: the window in device
 // memory, its present entries copied after collect.)
+//
+// A window-closest stream (dst_stream_open_window_closest) is the fourth: per (loaded record, window) the k
+// nearest streamed records.  No plain pair kernel and no matrix: behind the pack, on the compute stream, come the batch's
+// per-window base counts (tn93), then per (rows x windows) range the window sweep of loaded x batch as DST_OUT_TALLY words
+// into the stream's one scratch and window_nearest_stream_kernel's merge into the lists.  The window table, the count
+// tables, the scratch and the lists are the stream's own, so no other call on the context can disturb them.
 #include <algorithm>
 #include <cmath>
 #include <cstdio>
@@ -85,9 +91,18 @@ struct dst_stream {
     uint64_t window = 0;              // links of one window
     bool via_copy = false;            // DST_STREAM_LINKS_COPY
     uint64_t links_total = 0, late_windows = 0;   // dst_stream_links_stats
+    // window-closest streams: n_loaded x n_windows lists in d_lists (nl, and wc_cnt: tn93's 4 count words per entry)
+    uint32_t n_windows = 0;
+    Grown<uint2> wc_table;            // [n_windows] {begin, end}
+    Grown<uint4> wc_q_counts;         // tn93: [n_windows][n_loaded], built at open
+    Grown<uint4> wc_t_counts;         // tn93: [n_windows][the batch's records], rebuilt per batch
+    Grown<uint32_t> wc_scratch;       // one range's tallies: wc_cut.rows x wc_cut.wins x max_records entries
+    WindowSlabs wc_cut{};
+    uint32_t *wc_cnt = nullptr;
 };
 
 constexpr int kLinksStream = 2;       // dst_stream::closest of a links stream (after the two dst_closest_side values)
+constexpr int kWindowClosestStream = 3;   // ... and of a window-closest stream
 
 namespace {
 
@@ -138,6 +153,10 @@ void destroy(dst_stream *s)
             forget_stream(s->ctx, st);
     s->slots.clear();   // the slots' memory, device and page-locked, their sets' and their events
     (void)s->d_lists.release();
+    (void)s->wc_scratch.release();   // (a window-closest stream's)
+    (void)s->wc_t_counts.release();
+    (void)s->wc_q_counts.release();
+    (void)s->wc_table.release();
     for (hipStream_t st : {s->s_in, s->s_compute, s->s_out})
         if (st)
             (void)hipStreamDestroy(st);
@@ -256,9 +275,146 @@ int dst_stream_open_links(dst_ctx *ctx, int measure, double threshold, int what,
     return DST_OK;
 }
 
+int dst_stream_open_window_closest(dst_ctx *ctx, int measure, uint32_t k, const uint64_t *win_begin, const uint64_t *win_end,
+                                   uint32_t n_windows, uint64_t max_entries, size_t max_records, int depth, int wire,
+                                   dst_stream **out)
+{
+    if (!ctx || !out)
+        return DST_ERR_ARG;
+    *out = nullptr;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (wire != DST_WIRE_CODES && wire != DST_WIRE_NIBBLES)
+        return fail(ctx, DST_ERR_ARG, "unknown wire format");
+    if (k < 1 || k > kNearestMaxK)
+        return fail(ctx, DST_ERR_ARG, "k must be between 1 and 256");
+    if (n_windows == 0)
+        return fail(ctx, DST_ERR_ARG, "a window-closest stream needs at least one window");
+    if (n_windows > DST_WINDOWS_MAX)
+        return fail(ctx, DST_ERR_ARG, "more than DST_WINDOWS_MAX (65,536) windows");
+    if (!win_begin || !win_end)
+        return fail(ctx, DST_ERR_ARG, "null pointer");
+    if (max_records == 0 || depth < 2 || depth > 16)
+        return fail(ctx, DST_ERR_ARG, "max_records must be positive and depth in 2..16");
+    DeviceSet &loaded = ctx->set[0];
+    if (!loaded.loaded)
+        return fail(ctx, DST_ERR_STATE, "upload the loaded set to slot 0 before opening a stream");
+    if (loaded.partial)
+        return fail(ctx, DST_ERR_STATE, "a set uploaded with dst_upload_shared runs on the consensus path only (this rank holds "
+                                        "the planes of its own records)");
+    if (int rc = windows_valid(ctx, win_begin, win_end, n_windows, loaded.len))
+        return rc;
+    if (loaded.len >= ((uint64_t)1 << 32))
+        return fail(ctx, DST_ERR_ARG, "alignments of 2^32 sites or more are beyond a window-closest stream");
+    if (loaded.n >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    const uint64_t n_lists = (uint64_t)loaded.n * n_windows;
+    if (n_lists > kWindowNearestListsMax)
+        return fail(ctx, DST_ERR_ARG, "more than 2^31 (loaded record, window) lists");
+    // the loaded set's deferred planes, on the context's stream and waited for: the stream's kernels come later
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (int rc = order_after_prep(ctx, ctx->stream))
+        return rc;
+    if (int rc = ensure_derived(ctx, loaded, ctx->stream))
+        return rc;
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    dst_stream *s = nullptr;
+    int rc = open_stream(ctx, measure, DST_OUT_TALLY, max_records, depth, wire, kWindowClosestStream, k, &s);
+    if (rc)
+        return rc;
+    s->n_windows = n_windows;
+    const int W = s->W;
+    const bool tn93 = measure == DST_TN93;
+    const char *const what = "window-closest stream";
+    // the ranges of a batch: cut for a full batch, so that every batch's range fits the one scratch
+    if (loaded.n)
+        s->wc_cut = cut_window_slabs(loaded.n, n_windows, max_records, max_entries);
+    const uint64_t scratch_entries = s->wc_cut.rows * s->wc_cut.wins * (uint64_t)max_records;
+    // the lists: payloads, ordinals, tallies and (tn93) the streamed records' counts, each 256-byte aligned
+    const uint64_t entries = n_lists * k;
+    const auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t val_bytes = pad(entries * 8), idx_bytes = pad(entries * 4), tal_bytes = pad(entries * W * 4);
+    const size_t cnt_bytes = tn93 ? pad(entries * 16) : 0;
+    rc = s->wc_table.grow(ctx, (size_t)n_windows * sizeof(uint2), what);
+    if (!rc)
+        rc = s->d_lists.grow(ctx, std::max<size_t>(val_bytes + idx_bytes + tal_bytes + cnt_bytes, 256), what);
+    if (!rc)
+        rc = s->wc_scratch.grow(ctx, std::max<size_t>((size_t)scratch_entries * W * 4, 256), what);
+    if (!rc && tn93)
+        rc = s->wc_q_counts.grow(ctx, std::max<size_t>((size_t)n_lists * sizeof(uint4), 256), what);
+    if (!rc && tn93)
+        rc = s->wc_t_counts.grow(ctx, (size_t)n_windows * max_records * sizeof(uint4), what);
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        char *lists = static_cast<char *>(s->d_lists.ptr);
+        s->nl.val = reinterpret_cast<uint64_t *>(lists);
+        s->nl.idx = reinterpret_cast<uint32_t *>(lists + val_bytes);
+        s->nl.tal = reinterpret_cast<uint32_t *>(lists + val_bytes + idx_bytes);
+        s->wc_cnt = tn93 ? reinterpret_cast<uint32_t *>(lists + val_bytes + idx_bytes + tal_bytes) : nullptr;
+        s->nl.k = k;
+        std::vector<uint2> table(n_windows);
+        for (uint32_t w = 0; w < n_windows; ++w)
+            table[w] = make_uint2((uint32_t)win_begin[w], (uint32_t)win_end[w]);
+        e = hipMemcpyAsync(s->wc_table, table.data(), table.size() * sizeof(uint2), hipMemcpyHostToDevice, s->s_compute);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->s_compute);   // (the table's host copy goes with this scope)
+        if (e == hipSuccess && tn93) e = launch_window_counts(loaded, s->wc_table, n_windows, s->wc_q_counts, s->s_compute);
+        if (e == hipSuccess) e = launch_nearest_init(s->nl, n_lists, s->s_compute);
+    }
+    if (rc || e != hipSuccess) {
+        destroy(s);
+        return rc ? rc : fail_hip(ctx, e, "dst_stream_open_window_closest");
+    }
+    *out = s;
+    return DST_OK;
+}
+
 }  // extern "C"
 
 namespace {
+
+// One batch of a window-closest stream, queued on the compute stream behind the batch's pack: the batch's per-window base
+// counts (tn93), then range by range the window sweep (rows = loaded, columns = the batch, whose records the sweep's lanes
+// run along) into the stream's scratch and the merge into the lists.  One scratch is enough: sweep and merge follow each
+// other on the one stream.  Every list has one writer per launch.
+int window_closest_batch(dst_stream *s, DeviceSet &batch, size_t n_records)
+{
+    dst_ctx *ctx = s->ctx;
+    DeviceSet &loaded = ctx->set[0];
+    hipStream_t stream = s->s_compute;
+    if (s->n_loaded == 0)
+        return DST_OK;
+    if (int rc = order_after_prep(ctx, stream))
+        return rc;
+    if (int rc = ensure_derived(ctx, loaded, stream))   // (derived at open; a no-op unless the set was packed again)
+        return rc;
+    const bool tn93 = s->measure == DST_TN93;
+    if (tn93)
+        HIP_TRY(ctx, launch_window_counts(batch, s->wc_table, s->n_windows, s->wc_t_counts, stream));
+    WindowLaunch wl{};
+    wl.rows = &loaded;
+    wl.cols = &batch;
+    wl.square = false;
+    wl.out_kind = DST_OUT_TALLY;
+    wl.d_out = s->wc_scratch;
+    wl.d_windows = s->wc_table;
+    const uint64_t n_loaded = s->n_loaded;
+    for (uint64_t r0 = 0; r0 < n_loaded; r0 += s->wc_cut.rows) {
+        const uint64_t nr = std::min<uint64_t>(s->wc_cut.rows, n_loaded - r0);
+        for (uint32_t w0 = 0; w0 < s->n_windows; w0 += s->wc_cut.wins) {
+            const uint32_t nw = std::min<uint32_t>(s->wc_cut.wins, s->n_windows - w0);
+            wl.row_begin = r0;
+            wl.row_end = r0 + nr;
+            wl.pairs = nr * n_records;
+            wl.win_first = w0;
+            wl.n_windows = nw;
+            HIP_TRY(ctx, launch_window_pairs(s->measure, wl, stream));
+            HIP_TRY(ctx, launch_window_nearest_stream(s->measure, s->wc_scratch, s->wc_q_counts, s->wc_t_counts, n_loaded, n_records,
+                                                      r0, nr, w0, nw, s->n_windows, (uint32_t)s->next_ordinal, s->nl, s->wc_cnt,
+                                                      stream));
+        }
+    }
+    return note_run(ctx, stream);   // a rebuild of the loaded set's planes on another stream waits for these sweeps
+}
 
 // closest: -1 a plain stream, else the dst_closest_side of a closest stream (out_kind DST_OUT_TALLY, on the device only)
 int open_stream(dst_ctx *ctx, int measure, int out_kind, size_t max_records, int depth, int wire, int closest, uint32_t k,
@@ -304,12 +460,14 @@ int open_stream(dst_ctx *ctx, int measure, int out_kind, size_t max_records, int
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->s_compute, hipStreamNonBlocking);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&s->s_out, hipStreamNonBlocking);
     const size_t in_bytes = counts_offset(s) + max_records * 16;
-    const size_t out_bytes = std::max<size_t>(s->out_bytes_per_record * max_records, 16);
+    // (a window-closest stream has no matrix: its tallies go range by range through the stream's one scratch)
+    const size_t out_bytes = closest == kWindowClosestStream ? 16 : std::max<size_t>(s->out_bytes_per_record * max_records, 16);
+    const char *const what = closest == kWindowClosestStream ? "window-closest stream" : nullptr;   // (NOMEM with the byte count)
     // after the first failure, the runtime's (e) or an allocation's (rc), nothing more is made; destroy() frees the rest
     int rc = DST_OK;
     auto grow = [&](GrownBase &b, size_t bytes) {
         if (e == hipSuccess && !rc)
-            rc = b.grow(ctx, bytes);
+            rc = b.grow(ctx, bytes, what);
     };
     for (auto &sl : s->slots) {
         grow(sl.h_in, in_bytes);
@@ -384,8 +542,11 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
         return fail(ctx, DST_ERR_STATE, "the loaded set changed while the stream was open");
     if (s->poisoned)
         return fail(ctx, DST_ERR_STATE, "a batch of this closest stream held an invalid code: its lists are not trustworthy");
-    if (s->closest == DST_CLOSEST_FOR_LOADED && s->next_ordinal + n_records - 1 > 0xFFFFFFFEull)
+    const bool windowed = s->closest == kWindowClosestStream;
+    if ((s->closest == DST_CLOSEST_FOR_LOADED || windowed) && s->next_ordinal + n_records - 1 > 0xFFFFFFFEull)
         return fail(ctx, DST_ERR_CAPACITY, "streamed ordinals end at 2^32-2");
+    if (windowed)
+        use_base_counts = 0;   // per-window counts cannot come from the caller: counted by code on the device
     auto &sl = s->slots[(size_t)s->acquired];
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // copy-in: the batch's bytes (and the caller's base counts)
@@ -403,17 +564,19 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
     if (rc)
         return rc;
     sl.set.loaded = true;  // validity is reported by dst_stream_collect
-    if (s->measure == DST_TN93 && (s->out_kind == DST_OUT_DISTANCE || s->closest >= 0) && !sl.set.have_counts) {
+    if (!windowed && s->measure == DST_TN93 && (s->out_kind == DST_OUT_DISTANCE || s->closest >= 0) && !sl.set.have_counts) {
         HIP_TRY(ctx, launch_fill_counts(sl.set, s->s_compute));  // same stream as the kernel that reads them
         sl.set.have_counts = true;
     }
-    if (s->measure == DST_TN93 && s->closest >= 0) {   // the selection finalises the tallies: the loaded set's counts too
+    if (!windowed && s->measure == DST_TN93 && s->closest >= 0) {   // the selection finalises the tallies: the loaded set's counts too
         rc = need_counts(ctx, loaded, s->s_compute);
         if (rc)
             return rc;
     }
-    const size_t bytes = s->out_bytes_per_record * n_records;
-    rc = run_sets(ctx, s->measure, false, sl.set, loaded, 0, n_records, s->out_kind, sl.d_out, bytes, (void *)s->s_compute);
+    // a window-closest stream: no pair kernel and no matrix, the window sweep and the merge range by range
+    const size_t bytes = windowed ? 0 : s->out_bytes_per_record * n_records;
+    rc = windowed ? window_closest_batch(s, sl.set, n_records)
+                  : run_sets(ctx, s->measure, false, sl.set, loaded, 0, n_records, s->out_kind, sl.d_out, bytes, (void *)s->s_compute);
     if (rc)
         return rc;
     // a closest stream: the selection directly behind the batch's pair kernel, on the one compute stream
@@ -458,7 +621,7 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
         HIP_TRY(ctx, hipMemcpyAsync(sl.h_nl.tal, sl.nl.tal, e * 4 * (size_t)s->W, hipMemcpyDeviceToHost, s->s_out));
     }
     HIP_TRY(ctx, sl.landed.record(s->s_out));
-    if (s->closest == DST_CLOSEST_FOR_LOADED) {
+    if (s->closest == DST_CLOSEST_FOR_LOADED || windowed) {
         s->next_ordinal += n_records;
         s->submitted += n_records;
     }
@@ -513,8 +676,8 @@ int dst_stream_closest_next_index(dst_stream *s, uint64_t next)
 {
     if (!s)
         return DST_ERR_ARG;
-    if (s->closest != DST_CLOSEST_FOR_LOADED)
-        return fail(s->ctx, DST_ERR_ARG, "not a DST_CLOSEST_FOR_LOADED stream");
+    if (s->closest != DST_CLOSEST_FOR_LOADED && s->closest != kWindowClosestStream)
+        return fail(s->ctx, DST_ERR_ARG, "not a DST_CLOSEST_FOR_LOADED or window-closest stream");
     if (s->in_flight != 0)
         return fail(s->ctx, DST_ERR_STATE, "collect every submitted batch before renumbering");
     if (next < s->next_ordinal || next > 0xFFFFFFFFull)
@@ -553,6 +716,53 @@ int dst_stream_closest_result(dst_stream *s, uint32_t *index, uint32_t *tallies,
         HIP_TRY(ctx, hipMemcpy2DAsync(values, ku * 8, s->nl.val, k * 8, ku * 8, n, hipMemcpyDeviceToHost, s->s_compute));
     if (tallies)
         HIP_TRY(ctx, hipMemcpy2DAsync(tallies, ku * w4, s->nl.tal, k * w4, ku * w4, n, hipMemcpyDeviceToHost, s->s_compute));
+    HIP_TRY(ctx, hipStreamSynchronize(s->s_compute));
+    return DST_OK;
+}
+
+int dst_stream_window_closest_result(dst_stream *s, uint32_t *index, uint32_t *tallies, void *values, uint32_t *col_counts,
+                                     size_t cap_entries, uint32_t *k_used)
+{
+    if (!s)
+        return DST_ERR_ARG;
+    dst_ctx *ctx = s->ctx;
+    if (k_used)
+        *k_used = 0;
+    if (s->closest != kWindowClosestStream)
+        return fail(ctx, DST_ERR_ARG, "not a window-closest stream");
+    if (!index || !k_used)
+        return fail(ctx, DST_ERR_ARG, "null index or k_used pointer");
+    if (col_counts && s->measure != DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "col_counts are tn93's: the lists of another measure carry no base counts");
+    if (s->poisoned)
+        return fail(ctx, DST_ERR_STATE, "a batch of this closest stream held an invalid code: its lists are not trustworthy");
+    if (s->in_flight != 0)
+        return fail(ctx, DST_ERR_STATE, "collect every submitted batch before reading the lists");
+    const uint32_t ku = (uint32_t)std::min<uint64_t>(s->k, s->submitted);
+    *k_used = ku;
+    const uint64_t n_lists = (uint64_t)s->n_loaded * s->n_windows;
+    if ((unsigned __int128)n_lists * ku > (unsigned __int128)cap_entries)
+        return fail(ctx, DST_ERR_CAPACITY, "cap_entries is below n_loaded x n_windows x k_used");
+    if (ku == 0 || n_lists == 0)
+        return DST_OK;
+    // every batch is collected; the wait is for the merges behind the last one.  The first k_used entries of every list,
+    // dense: one strided copy per array (one plain copy when the lists are full).
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    HIP_TRY(ctx, hipStreamSynchronize(s->s_compute));
+    const size_t k = s->k;
+    const auto compact = [&](void *host, const void *dev, size_t entry_bytes) -> hipError_t {
+        if (ku == k)
+            return hipMemcpyAsync(host, dev, n_lists * k * entry_bytes, hipMemcpyDeviceToHost, s->s_compute);
+        return hipMemcpy2DAsync(host, ku * entry_bytes, dev, k * entry_bytes, ku * entry_bytes, n_lists, hipMemcpyDeviceToHost,
+                                s->s_compute);
+    };
+    HIP_TRY(ctx, compact(index, s->nl.idx, 4));
+    if (values)
+        HIP_TRY(ctx, compact(values, s->nl.val, 8));
+    if (tallies)
+        HIP_TRY(ctx, compact(tallies, s->nl.tal, 4 * (size_t)s->W));
+    if (col_counts)
+        HIP_TRY(ctx, compact(col_counts, s->wc_cnt, 16));
     HIP_TRY(ctx, hipStreamSynchronize(s->s_compute));
     return DST_OK;
 }

@@ -24,6 +24,36 @@ __device__ __forceinline__ uint64_t shfl64(uint64_t x, int src)
 }
 __device__ __forceinline__ uint32_t shfl32(uint32_t x, int src) { return (uint32_t)__shfl((int)x, src, 64); }
 
+// W consecutive 32-bit words as one 4 / 8 / 16-byte access where W allows it (p aligned to it), else word by word
+template <int W>
+__device__ __forceinline__ void load_words(const uint32_t *__restrict__ p, uint32_t *o)
+{
+    if constexpr (W == 4) {
+        const uint4 v = *reinterpret_cast<const uint4 *>(p);
+        o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w;
+    } else if constexpr (W == 2) {
+        const uint2 v = *reinterpret_cast<const uint2 *>(p);
+        o[0] = v.x, o[1] = v.y;
+    } else {
+#pragma unroll
+        for (int t = 0; t < W; ++t)
+            o[t] = p[t];
+    }
+}
+template <int W>
+__device__ __forceinline__ void store_words(uint32_t *p, const uint32_t *o)
+{
+    if constexpr (W == 4) {
+        *reinterpret_cast<uint4 *>(p) = make_uint4(o[0], o[1], o[2], o[3]);
+    } else if constexpr (W == 2) {
+        *reinterpret_cast<uint2 *>(p) = make_uint2(o[0], o[1]);
+    } else {
+#pragma unroll
+        for (int t = 0; t < W; ++t)
+            p[t] = o[t];
+    }
+}
+
 // one record's list, spread over the wave
 template <int W>
 struct WaveList {
@@ -48,8 +78,10 @@ struct WaveList {
         thr_idx = kSentinelIdx;
     }
 
-    template <bool INT>
-    __device__ void load(const uint64_t *lval, const uint32_t *lidx, const uint32_t *ltal, uint64_t base, uint32_t k, int lane)
+    // WA < W: the entry's words in two arrays, [0, WA) in ltal (WA per entry) and [WA, W) in lext (W - WA per entry)
+    template <bool INT, int WA = W>
+    __device__ void load(const uint64_t *lval, const uint32_t *lidx, const uint32_t *ltal, uint64_t base, uint32_t k, int lane,
+                         const uint32_t *lext = nullptr)
     {
 #pragma unroll
         for (int s = 0; s < kSlots; ++s) {
@@ -57,9 +89,14 @@ struct WaveList {
             if (e < k) {
                 val[s] = lval[base + e];
                 idx[s] = lidx[base + e];
+                if constexpr (WA == W) {
 #pragma unroll
-                for (int t = 0; t < W; ++t)
-                    tal[s][t] = ltal[(base + e) * W + t];
+                    for (int t = 0; t < W; ++t)
+                        tal[s][t] = ltal[(base + e) * W + t];
+                } else {
+                    load_words<WA>(ltal + (base + e) * WA, tal[s]);
+                    load_words<W - WA>(lext + (base + e) * (W - WA), tal[s] + WA);
+                }
                 key[s] = idx[s] == kSentinelIdx ? ~0ull : nn_key<INT>(val[s]);
             } else {
                 val[s] = kSentinelVal;
@@ -73,7 +110,9 @@ struct WaveList {
         threshold(k);
     }
 
-    __device__ void store(uint64_t *lval, uint32_t *lidx, uint32_t *ltal, uint64_t base, uint32_t k, int lane) const
+    template <int WA = W>
+    __device__ void store(uint64_t *lval, uint32_t *lidx, uint32_t *ltal, uint64_t base, uint32_t k, int lane,
+                          uint32_t *lext = nullptr) const
     {
 #pragma unroll
         for (int s = 0; s < kSlots; ++s) {
@@ -81,9 +120,14 @@ struct WaveList {
             if (e < k) {
                 lval[base + e] = val[s];
                 lidx[base + e] = idx[s];
+                if constexpr (WA == W) {
 #pragma unroll
-                for (int t = 0; t < W; ++t)
-                    ltal[(base + e) * W + t] = tal[s][t];
+                    for (int t = 0; t < W; ++t)
+                        ltal[(base + e) * W + t] = tal[s][t];
+                } else {
+                    store_words<WA>(ltal + (base + e) * WA, tal[s]);
+                    store_words<W - WA>(lext + (base + e) * (W - WA), tal[s] + WA);
+                }
             }
         }
     }

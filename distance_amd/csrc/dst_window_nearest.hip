@@ -17,22 +17,6 @@
 namespace dst {
 namespace {
 
-template <int W>
-__device__ __forceinline__ void load_tallies(const uint32_t *__restrict__ p, uint32_t (&o)[W])
-{
-    if constexpr (W == 4) {
-        const uint4 v = *reinterpret_cast<const uint4 *>(p);
-        o[0] = v.x, o[1] = v.y, o[2] = v.z, o[3] = v.w;
-    } else if constexpr (W == 2) {
-        const uint2 v = *reinterpret_cast<const uint2 *>(p);
-        o[0] = v.x, o[1] = v.y;
-    } else {
-#pragma unroll
-        for (int t = 0; t < W; ++t)
-            o[t] = p[t];
-    }
-}
-
 template <int M, int W>
 __global__ __launch_bounds__(256) void window_nearest_kernel(const uint32_t *__restrict__ slab, const uint4 *__restrict__ q_counts,
                                                              const uint4 *__restrict__ t_counts, uint32_t q_n, uint32_t n_cols,
@@ -60,7 +44,7 @@ __global__ __launch_bounds__(256) void window_nearest_kernel(const uint32_t *__r
         uint32_t o[W];
         uint64_t v = 0, key = ~0ull;
         if (valid) {
-            load_tallies<W>(slab + (base + j) * W, o);
+            load_words<W>(slab + (base + j) * W, o);
             uint4 rc = qc, cc = make_uint4(0, 0, 0, 0);
             if constexpr (M == DST_TN93) {
                 cc = t_counts[(uint64_t)w * n_cols + j];

@@ -333,6 +333,8 @@ namespace {
 const char *const kSharedRefusal = "a set uploaded with dst_upload_shared runs on the consensus path only (this rank holds "
                                    "the planes of its own records)";
 
+}  // namespace
+
 int windows_valid(dst_ctx *ctx, const uint64_t *wb, const uint64_t *we, uint32_t n_windows, uint64_t len)
 {
     for (uint32_t w = 0; w < n_windows; ++w)
@@ -344,6 +346,8 @@ int windows_valid(dst_ctx *ctx, const uint64_t *wb, const uint64_t *we, uint32_t
         }
     return DST_OK;
 }
+
+namespace {
 
 int grow_or_nomem(dst_ctx *ctx, GrownBase &buf, size_t want, const char *what)
 {
@@ -472,12 +476,11 @@ int windows_run(dst_ctx *ctx, int measure, const TwoSets &ts, bool square, uint6
     return DST_OK;
 }
 
-// The (row, window) lists of a dst_nearest_windows call cut into slabs of rows x windows: whole row ranges of all the
-// windows while a row's windows fit the budget, else a few rows (the sweep's tile holds eight) of a range of windows.
-struct WindowSlabs {
-    uint64_t rows;   // rows of a slab (the last one of a job may hold fewer)
-    uint32_t wins;   // windows of a slab (likewise)
-};
+}  // namespace
+
+// The (row, window) lists of a dst_nearest_windows call (or of a window-closest stream's batch) cut into slabs of rows x
+// windows: whole row ranges of all the windows while a row's windows fit the budget, else a few rows (the sweep's tile
+// holds eight) of a range of windows.
 WindowSlabs cut_window_slabs(uint64_t n_rows, uint32_t n_windows, uint64_t n_cols, uint64_t max_entries)
 {
     // (no more than 2^40 entries, 16 TB of tn93 tallies: a slab's byte count stays far inside 64 bits)
@@ -494,7 +497,6 @@ WindowSlabs cut_window_slabs(uint64_t n_rows, uint32_t n_windows, uint64_t n_col
     return s;
 }
 
-}  // namespace
 }  // namespace dst
 
 extern "C" {

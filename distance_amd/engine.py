@@ -448,6 +448,13 @@ class Engine:
         side="streamed": every streamed record's k nearest loaded records, per batch (pop())."""
         return ClosestStream(self, measure, k, max_records, side, depth, nibbles)
 
+    def window_closest_stream(self, measure, windows, k: int, max_records: int, depth: int = 3, nibbles: bool = False,
+                              max_entries: int = 0) -> "WindowClosestStream":
+        """A stream that keeps, for every (loaded record, column window), the k nearest streamed records
+        (dst_stream_open_window_closest): nearest_windows() against a panel that does not fit on the GPU.
+        max_entries: the most tallies of one device range (0: the default); the result does not depend on it."""
+        return WindowClosestStream(self, measure, windows, k, max_records, depth, nibbles, max_entries)
+
     def links_stream(self, measure, threshold: float, max_records: int, depth: int = 3, nibbles: bool = False,
                      values: bool = True, tallies: bool = False, window: int = 0) -> "LinksStream":
         """A stream that hands back the pairs within `threshold` instead of the result matrix (dst_stream_open_links):
@@ -1174,6 +1181,59 @@ class ClosestStream(Stream):
         if tallies:
             return index, values, tal[:n * k * self._w].reshape(n, k, self._w).copy()
         return index, values
+
+
+class WindowClosestStream(Stream):
+    """dst_stream_open_window_closest: a Stream whose batches leave, for every (loaded record, window), the k nearest
+    streamed records behind.  pop() returns the batch's record count; result() the lists so far, index = streamed
+    ordinals, ascending by (key of the window's value, ordinal); values int64 for n / n_high, float64 otherwise."""
+
+    def __init__(self, eng: Engine, measure, windows, k: int, max_records: int, depth: int = 3, nibbles: bool = False,
+                 max_entries: int = 0):
+        self.k, self.max_entries = int(k), int(max_entries)
+        self._begin, self._end, self.n_windows = _window_arrays(windows)
+        super().__init__(eng, measure, max_records, depth, True, nibbles)
+        self._w = self._lib.dst_tally_width(self._m)
+        self._vtype = np.int64 if self._m in (0, 1) else np.float64
+
+    def _open(self):
+        h = C.c_void_p()
+        self._eng._check(self._lib.dst_stream_open_window_closest(
+            self._eng._h, self._m, self.k, self._begin.ctypes.data, self._end.ctypes.data, self.n_windows, self.max_entries,
+            self.max_records, self.depth, int(self.nibbles), C.byref(h)))
+        return h
+
+    def pop(self, copy: bool = True):
+        n, p = C.c_size_t(), C.c_void_p()
+        self._eng._check(self._lib.dst_stream_collect(self._h, C.byref(n), C.byref(p)))
+        return n.value
+
+    def next_index(self, n: int):
+        """The ordinal of the next pushed record (dst_stream_closest_next_index)"""
+        self._eng._check(self._lib.dst_stream_closest_next_index(self._h, int(n)))
+
+    def result(self, tallies: bool = False, counts: bool = False, cap_entries: int | None = None):
+        """(index, values[, tallies][, counts]) shaped (n_loaded, n_windows, k_used[, width or 4]), a snapshot
+        (dst_stream_window_closest_result); every pushed batch must have been popped.  counts (tn93): the listed streamed
+        records' {A,T,G,C} inside the window, counted by code."""
+        n, nw = self._n_loaded, self.n_windows
+        cap = n * nw * self.k if cap_entries is None else int(cap_entries)
+        index = np.zeros(max(cap, 1), np.uint32)
+        values = np.zeros(max(cap, 1), self._vtype)
+        tal = np.zeros(max(cap, 1) * self._w, np.uint32) if tallies else None
+        cnt = np.zeros(max(cap, 1) * 4, np.uint32) if counts else None
+        ku = C.c_uint32()
+        self._eng._check(self._lib.dst_stream_window_closest_result(
+            self._h, index.ctypes.data, None if tal is None else tal.ctypes.data, values.ctypes.data,
+            None if cnt is None else cnt.ctypes.data, cap, C.byref(ku)))
+        k = ku.value
+        e = n * nw * k
+        out = (index[:e].reshape(n, nw, k).copy(), values[:e].reshape(n, nw, k).copy())
+        if tallies:
+            out += (tal[:e * self._w].reshape(n, nw, k, self._w).copy(),)
+        if counts:
+            out += (cnt[:e * 4].reshape(n, nw, k, 4).copy(),)
+        return out
 
 
 class LinksStream(Stream):

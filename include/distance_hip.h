@@ -293,7 +293,7 @@ int dst_stream_close(dst_stream *stream);
 typedef enum { DST_CLOSEST_FOR_LOADED = 0, DST_CLOSEST_FOR_STREAMED = 1 } dst_closest_side;
 int dst_stream_open_closest(dst_ctx *ctx, int measure, uint32_t k, int side, size_t max_records, int depth, int wire,
                             dst_stream **stream);
-/* FOR_LOADED only.  Sets the ordinal of the next submitted record (numbering the shards of one database).  Allowed only with
+/* FOR_LOADED (and window-closest streams, below) only.  Sets the ordinal of the next submitted record (numbering the shards of one database).  Allowed only with
  * nothing in flight (else DST_ERR_STATE) and with the current ordinal <= next <= 2^32-1 (else DST_ERR_ARG). */
 int dst_stream_closest_next_index(dst_stream *stream, uint64_t next);
 /* FOR_LOADED only.  A snapshot of the lists: n_loaded x k_used entries, row-major by loaded record, dense, ascending;
@@ -353,6 +353,51 @@ int dst_stream_links_batch(dst_stream *stream, uint64_t first_link, uint64_t *n_
 /* A diagnostic, like dst_text_stats: the links of every batch collected so far, and how many windows were written after
  * collect.  Either pointer may be NULL.  DST_ERR_ARG on a NULL, plain or closest stream. */
 int dst_stream_links_stats(const dst_stream *stream, uint64_t *links, uint64_t *late_windows);
+/* ---- nearest records per window in stream mode ---------------------------------------------------- */
+/* A window-closest stream: for every (loaded record of slot 0, window) the k nearest STREAMED records inside that window,
+ * kept over the whole life of the stream - the recombination scan of dst_nearest_windows against a panel that does not fit
+ * on the GPU.  Few loaded queries against a long stream; the per-streamed-record side is not offered.
+ * Definition, fixed to the bit.  Let S be the set that holds every record submitted so far, in ordinal order; a record's
+ * ordinal is the number of records submitted before it, plus whatever dst_stream_closest_next_index skipped.  The result is
+ * what dst_nearest_windows(square = 0, rows = slot 0, cols = S, every row, the same windows, the same k) returns, with
+ * `index` holding the ordinals: a candidate's value is dst_run_windows' DST_OUT_DISTANCE payload of the pair (loaded i,
+ * streamed s) in window w, its tallies are that entry's DST_OUT_TALLY words, tn93 takes per-window base counts COUNTED BY
+ * CODE, the loaded record's and the streamed record's in that order, and the order is ascending (dst_nearest's key,
+ * ordinal): a strict total order.  So the answer does not depend on how the stream is cut into batches, on depth, on the
+ * wire format or on max_entries; an empty window lists the first k_used ordinals; and k_used = min(k, records submitted),
+ * the records and not the ordinal.  use_base_counts of dst_stream_submit is IGNORED on this stream: per-window counts cannot
+ * come from the caller.
+ * It IS a dst_stream: dst_stream_acquire / _submit / _collect / _in_flight / _close work as on a closest stream
+ * (dst_stream_collect returns *results = NULL, still waits for the batch and still reports DST_ERR_INVALID_CODE; after a
+ * batch with an invalid code every later dst_stream_submit and dst_stream_window_closest_result is DST_ERR_STATE, as for
+ * DST_CLOSEST_FOR_LOADED).  Ordinals are uint32 with 2^32-1 as the sentinel: a submit whose last ordinal would pass 2^32-2
+ * is DST_ERR_CAPACITY and changes nothing; dst_stream_closest_next_index works on this stream with its rules.  The other
+ * closest and links calls on it are DST_ERR_ARG, as is dst_stream_window_closest_result on any other stream.
+ * Open.  windows as dst_run_windows' (half-open, may overlap, repeat, be empty, come in any order), 1 <= n_windows <=
+ * DST_WINDOWS_MAX.  max_entries: the most (loaded record x window x streamed record) tallies of one device range, 0: 2^25;
+ * a batch is cut into (rows x windows) ranges by dst_nearest_windows' rule (at least one (row, window) of max_records
+ * records), swept and merged range by range.  Errors, in this order: DST_ERR_ARG for a NULL ctx or stream pointer, an unknown
+ * measure or wire, k outside 1..256, n_windows 0 or above DST_WINDOWS_MAX, a NULL window array, max_records == 0, depth
+ * outside 2..16; DST_ERR_STATE for slot 0 not loaded or from dst_upload_shared; DST_ERR_ARG for a bad window (the message
+ * names the first), len >= 2^32, a loaded set of 2^32-1 records or more, n_loaded x n_windows above 2^31 lists;
+ * DST_ERR_NOMEM with the byte count.  Submit: DST_ERR_STATE when the loaded set's record count or width changed.
+ * The stream owns its window table, its per-window count tables (tn93: the loaded set's, built once at open, and one
+ * batch's), its lists and one tally scratch - not the context's - so dst_run_windows, dst_nearest_windows or any other call
+ * on the context between two submits does not disturb it.  The loaded set's deferred planes are written at open.  Per
+ * submit, on the compute stream behind the pack: the batch's per-window counts (tn93), then per range the window sweep
+ * (rows = loaded, columns = the batch) and the merge, one wave per list.  No pair kernel, no matrix.  Single GPU. */
+int dst_stream_open_window_closest(dst_ctx *ctx, int measure, uint32_t k,
+                                   const uint64_t *win_begin, const uint64_t *win_end, uint32_t n_windows,
+                                   uint64_t max_entries, size_t max_records, int depth, int wire, dst_stream **stream);
+/* A snapshot of the lists (host memory): entry (i * n_windows + w) * k_used + e, e ascending, as dst_nearest_windows lays
+ * them out.  index: the streamed ordinals (required); tallies: dst_tally_width(measure) words per entry, values: the 8-byte
+ * payloads, col_counts: 4 uint32 {A,T,G,C} per entry, the listed streamed record's counts inside window w, by code - with
+ * tallies and dst_window_base_counts(slot 0) what dst_finalize needs for the reference's bits, the batch being gone; any
+ * of the three may be NULL.  col_counts is tn93's: non-NULL with another measure is DST_ERR_ARG.  Needs
+ * dst_stream_in_flight() == 0, else DST_ERR_STATE; cap_entries below n_loaded * n_windows * k_used: DST_ERR_CAPACITY with
+ * *k_used set.  The call may be repeated, and streaming may go on afterwards. */
+int dst_stream_window_closest_result(dst_stream *stream, uint32_t *index, uint32_t *tallies, void *values,
+                                     uint32_t *col_counts, size_t cap_entries, uint32_t *k_used);
 
 /* ---- multi-GPU: the gather of the result slabs (one process per GPU, RCCL over xGMI) --------- */
 /* The pair space shards by contiguous canonical ranges (dst_partition_square / dst_partition_rect): every rank
