@@ -21,8 +21,12 @@ References, all exact:
   histogram           the integer Walsh-Hadamard autocorrelation of the words' indicator, binned by popcount
   per-record sum      sum over the bits b of the number of records whose bit b differs from the record's own
   one row             popcount of the row's word against all n
+  a column window   the same forms with the word masked to the window's bits and 40 replaced by the window's comparable
+                      sites (window_tallies, window_values, window_base_counts)
 test_record_boundary_host.py holds this design to the oracle on picked rows; test_gpu_record_boundary.py and
-test_gpu_cli_record_boundary.py run the engine and the command-line tool on it."""
+test_gpu_cli_record_boundary.py run the engine and the command-line tool on it, test_gpu_record_boundary_windows.py the
+windowed operations, the pair lists and the window-closest stream, the latter also on tall_set(): 524,289 records of the
+same design, nine more than the 65,535 rows of one launch grid hold at eight records each."""
 import functools
 import itertools
 
@@ -139,6 +143,48 @@ class RecordSet:
     def row(self, measure, i):
         """record i against all n records (itself included: 0)"""
         return self.values(measure, np.full(self.n, i), np.arange(self.n))
+
+    # ---- per pair, inside a column window [b, e) of the 40 sites -----------------------------------------------------
+    def window_comparable(self, i, j, b, e):
+        """the sites of [b, e) at which neither record holds N: e - b less site 39 when max(i % 3, j % 3) >= 1 and
+        site 38 when it is 2, each only when the window holds it (i == j: the record against itself)"""
+        worst = np.maximum(np.asarray(i, np.int64) % 3, np.asarray(j, np.int64) % 3)
+        gone = ((worst >= 1) & (b <= LENGTH - 1 < e)).astype(np.int64) + ((worst == 2) & (b <= LENGTH - 2 < e))
+        return max(e - b, 0) - gone
+
+    def window_tallies(self, measure, i, j, b, e):
+        """tallies() of the pairs (i, j) on the sets cut to the columns [b, e): the xor word masked to the window's bits,
+        LENGTH replaced by the window's comparable sites; an empty window gives zeros"""
+        x = self.xor(i, j) & window_mask(b, e)
+        d, comp = POP[x].astype(np.int64), self.window_comparable(i, j, b, e)
+        ts, tv = POP[x & EVEN].astype(np.int64), POP[x & ODD].astype(np.int64)
+        if measure in ("n", "n_high"):
+            return d[:, None]
+        if measure in ("raw", "jc69"):
+            return np.stack([d, comp], axis=1)
+        if measure == "k80":
+            return np.stack([comp, ts, tv], axis=1)
+        if measure == "tn93":
+            return np.stack([comp, d, ts, np.zeros_like(d)], axis=1)
+        raise ValueError(measure)
+
+    def window_values(self, measure, i, j, b, e):
+        """values() of the pairs (i, j) on the sets cut to the columns [b, e); raw is NaN where no site is comparable"""
+        d = POP[self.xor(i, j) & window_mask(b, e)].astype(np.int64)
+        if measure in ("n", "n_high"):
+            return d
+        if measure == "raw":
+            with np.errstate(invalid="ignore", divide="ignore"):
+                return d.astype(np.float64) / self.window_comparable(i, j, b, e).astype(np.float64)
+        raise ValueError(measure)
+
+    def window_base_counts(self, b, e):
+        """{A, T, G, C} of every record inside the columns [b, e), uint32 (n, 4)"""
+        mask = window_mask(b, e)
+        g, c = POP[self.words & EVEN & mask].astype(np.int64), POP[self.words & ODD & mask].astype(np.int64)
+        r = np.arange(self.n)
+        a = self.window_comparable(r, r, b, e) - g - c
+        return np.stack([a, np.zeros_like(a), g, c], axis=1).astype(np.uint32)
 
     # ---- whole set --------------------------------------------------------------------------------------------------
     @functools.lru_cache(maxsize=None)
@@ -279,6 +325,96 @@ def wht(a):
 def record_set():
     """the set of the module docstring, built once per process"""
     return RecordSet()
+
+
+# ---- windows, named pairs and window streams (test_gpu_record_boundary_windows.py) ---------------------------------------
+# the whole width, the varying half, an inner cut, the N tail, the last two sites (almost all ties), one site, an empty window
+WINDOWS = ((0, 40), (0, 20), (3, 17), (20, 40), (38, 40), (0, 1), (39, 39))
+NEAREST_WINDOWS = ((0, 40), (3, 17), (38, 40))
+WIN_ROWS = 8                                # row records of one block of the window sweep
+TALL_RECORDS = WIN_ROWS * GRID_ROWS + 9     # 524,289: one window launch of more than 65,535 row tiles, a second grid
+TALL_SEED = 2027
+TALL_ROW_BEGIN = 3                          # a row range whose second grid begins off a multiple of 8
+WINDOW_NEAREST_PAIRS = 1 << 25              # pair-windows of a slab of dst_nearest_windows unless the caller says otherwise
+WINDOW_NEAREST_LISTS_MAX = 1 << 31          # (row, window) lists of one slab
+FIRST_RECT_ROW_PAST_2_32 = 46_332           # the first row of the 92,700 x 92,700 rectangle whose start i n is >= 2^32
+
+
+def window_mask(b, e):
+    """bits b .. min(e, 20) - 1 of a word: the varying sites inside the window [b, e)"""
+    return np.uint32(sum(1 << s for s in range(b, min(e, BITS))))
+
+
+def cut_window_slabs(n_rows, n_windows, n_cols, max_entries=0):
+    """The engine's cut of the (row, window) lists of dst_nearest_windows or of a window-closest stream's batch restated:
+    (rows, windows) of one slab.  Whole row ranges of all the windows while a row's windows fit the budget, else at most
+    eight rows of a range of windows."""
+    budget = min(max_entries, 1 << 40) if max_entries else WINDOW_NEAREST_PAIRS
+    lists = min(max(budget // n_cols, 1), WINDOW_NEAREST_LISTS_MAX)
+    if lists >= n_windows:
+        return min(lists // n_windows, n_rows), n_windows
+    rows = min(lists, WIN_ROWS, n_rows)
+    return rows, lists // rows
+
+
+def second_grid_first_row(row_begin, row_end):
+    """the first row of the window sweep's second launch grid over rows [row_begin, row_end), or None when one grid holds
+    all the row tiles"""
+    tiles = -(-(row_end - row_begin) // WIN_ROWS)
+    return row_begin + GRID_ROWS * WIN_ROWS if tiles > GRID_ROWS else None
+
+
+@functools.lru_cache(maxsize=None)
+def tall_set():
+    """524,289 records of the same design (2^20 distinct words suffice), built once per process"""
+    return RecordSet(n=TALL_RECORDS, seed=TALL_SEED)
+
+
+def tall_columns(n=TALL_RECORDS):
+    """the five records of the tall set that are the columns (or the streamed batch): first, last, three in between"""
+    return np.array([0, WIN_ROWS * GRID_ROWS - 1, WIN_ROWS * GRID_ROWS, n - 2, n - 1], np.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_pairs(n=N_RECORDS, seed=31):
+    """(row, col) int64 of the square list of run_pairs: the pairs at the boundaries and two diagonal entries, about 2,000
+    seeded pairs whose canonical rows lie in [65,530, 65,545) and [90,890, n - 1) (so the sweep runs a handful of slabs), each
+    in both orders, shuffled, with repeats"""
+    F = FIRST_ROW_PAST_2_32
+    fixed = [(65_535, 65_536), (65_536, n - 1), (F - 1, F), (F, n - 1), (n - 2, n - 1), (65_536, 65_536), (n - 1, n - 1)]
+    rng = np.random.default_rng(seed)
+    i = np.concatenate([rng.integers(65_530, 65_545, 1_000), rng.integers(90_890, n - 1, 1_000)])
+    j = i + 1 + (rng.random(2_000) * (n - 1 - i)).astype(np.int64)
+    i, j = np.concatenate([[p[0] for p in fixed], i]), np.concatenate([[p[1] for p in fixed], j])
+    row, col = np.concatenate([i, j, i[:5]]), np.concatenate([j, i, j[:5]])
+    order = rng.permutation(len(row))
+    return row[order].astype(np.int64), col[order].astype(np.int64)
+
+
+@functools.lru_cache(maxsize=None)
+def boundary_rect_pairs(n=N_RECORDS, seed=32):
+    """(row, col) int64 of the rectangle list of run_pairs on 92,700 x 92,700: the two entries either side of position 2^32,
+    two diagonal entries, and about 1,000 seeded pairs of the rows [46,334, 46,340), [65,530, 65,545) and [n - 10, n), all
+    past 2^32; shuffled, with repeats"""
+    fixed = [(FIRST_RECT_ROW_PAST_2_32 - 1, TWO32 - (FIRST_RECT_ROW_PAST_2_32 - 1) * n - 1),
+             (FIRST_RECT_ROW_PAST_2_32 - 1, TWO32 - (FIRST_RECT_ROW_PAST_2_32 - 1) * n),
+             (FIRST_RECT_ROW_PAST_2_32, 0), (65_535, n - 1), (65_536, 0), (65_536, 65_536), (n - 1, n - 1), (n - 1, 0)]
+    rng = np.random.default_rng(seed)
+    i = rng.choice(np.concatenate([np.arange(46_334, 46_340), np.arange(65_530, 65_545), np.arange(n - 10, n)]), 1_000)
+    j = rng.integers(0, n, 1_000)
+    row, col = np.concatenate([[p[0] for p in fixed], i, i[:5]]), np.concatenate([[p[1] for p in fixed], j, j[:5]])
+    order = rng.permutation(len(row))
+    return row[order].astype(np.int64), col[order].astype(np.int64)
+
+
+def touched_slabs(n, max_pairs, row, col):
+    """the slabs of cut_row_slabs(n, max_pairs) that hold a listed pair off the diagonal, by its canonical row"""
+    slabs = cut_row_slabs(n, max_pairs)
+    lo = np.minimum(row, col)[row != col]
+    begins = np.array([s[0] for s in slabs])
+    hit = np.unique(np.searchsorted(begins, lo, side="right") - 1)
+    assert all(slabs[k][0] <= r < slabs[k][1] for k, r in zip(np.searchsorted(begins, lo, side="right") - 1, lo))
+    return [slabs[k] for k in hit]
 
 
 def max_pairs_cutting_in(n, row_lo, row_hi, lo=1 << 25, hi=1 << 26):

@@ -1,6 +1,6 @@
 """GPU (-m gpu): the command-line tool on the designed set of record_boundary_cases.py (92,700 records, 4,296,598,650
-pairs): --max-distance with --sites, --clusters, --summary, --histogram and --mst, every line against the set's closed
-forms.  This reaches the tool's link store, the --sites batching and the id arena at 92,700 ids of mixed length."""
+pairs): --max-distance with --sites, --clusters, --summary, --histogram, --pairs and --mst, every line against the set's
+closed forms.  This reaches the tool's link store, the --sites batching and the id arena at 92,700 ids of mixed length."""
 import os
 import subprocess
 
@@ -84,6 +84,23 @@ def test_histogram(rs, fasta):
     hist[:rbc.BITS + 1] = rs.histogram()
     want = "distance\tpairs\n" + "".join(f"{b}\t{int(c)}\n" for b, c in enumerate(hist)) + "NaN\t0\n"
     assert run(["-m", "n", "--histogram", "1", "--bins", "32", path]) == want
+
+
+@pytest.mark.parametrize("measure", ["n", "raw"])
+def test_pairs(rs, fasta, measure, tmp_path):
+    """--pairs FILE naming the pairs at record 65,536 and at offset 2^32 by id, in both orders: a line per line of the
+    file, the ids as given"""
+    ids, path = fasta
+    n, F = rs.n, rbc.FIRST_ROW_PAST_2_32
+    pairs = [(65_535, 65_536), (65_536, n - 1), (F - 1, F), (F, n - 1), (n - 2, n - 1)]
+    assert rbc.canon(n, *pairs[-1]) == 4_296_598_649 and rbc.canon(n, *pairs[2]) < rbc.TWO32 <= rbc.canon(n, *pairs[3])
+    pairs = pairs + [(b, a) for a, b in pairs]
+    listed = tmp_path / "pairs.tsv"
+    listed.write_text("".join(f"{ids[a]}\t{ids[b]}\n" for a, b in pairs))
+    values = rs.values(measure, [a for a, _ in pairs], [b for _, b in pairs]).tolist()
+    want = "sequence1\tsequence2\tdistance\n" + "".join(
+        f"{ids[a]}\t{ids[b]}\t{oracle.format_distance(v)}\n" for (a, b), v in zip(pairs, values))
+    assert_same_lines(run(["-m", measure, "--pairs", str(listed), path]), want)
 
 
 def test_mst(rs, fasta):

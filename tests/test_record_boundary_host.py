@@ -1,5 +1,5 @@
 """No GPU: the designed set of record_boundary_cases.py held to the oracle, not to itself, and the counts the GPU tests
-rely on (test_gpu_record_boundary.py, test_gpu_cli_record_boundary.py).
+rely on (test_gpu_record_boundary.py, test_gpu_record_boundary_windows.py, test_gpu_cli_record_boundary.py).
 
 On the picked rows the closed forms (n, comparable, transitions, transversions, base counts) are the oracle's tallies of
 the code bytes, the Walsh-Hadamard histogram and the bit-flip links are brute force over those rows, and the greedy slab
@@ -110,6 +110,91 @@ def test_clusters_and_mst_counts(rs):
         assert (np.diff(at) > 0).all()
     assert (canon(rs.n, edges[:, 0], edges[:, 1]) >= TWO32).sum() > 0   # forest edges past the 2^32 offset
     assert (edges[:, 0] >= 65_536).sum() > 0
+
+
+@pytest.mark.parametrize("which", ["set", "tall"])
+def test_windowed_closed_forms_are_the_oracles_tallies(rs, which):
+    """every window of test_gpu_record_boundary_windows.py: the closed forms are the oracle's on the cut columns"""
+    rs = rs if which == "set" else rbc.tall_set()
+    rng = np.random.default_rng(8)
+    rows = np.concatenate([rs.picked[:6], rs.picked[-6:], [rs.n - 3, rs.n - 2, rs.n - 1]])
+    cols = np.concatenate([rng.choice(rs.n, 24, replace=False), rows[:3], [65_536, rs.n - 1, rs.n - 2]])   # (all residues, i == j)
+    i, j = [x.ravel() for x in np.meshgrid(rows, cols, indexing="ij")]
+    assert 300 <= len(i) <= 600 and (i == j).any()
+    some = np.concatenate([rs.picked, rng.choice(rs.n, 200, replace=False)])
+    for b, e in rbc.WINDOWS:
+        for m in MEASURES:
+            mine = rs.window_tallies(m, i, j, b, e)
+            if e <= b:
+                assert not mine.any(), (m, b, e)
+                continue
+            got = oracle.tallies_rect(m, rs.codes[rows, b:e], rs.codes[cols, b:e]).reshape(len(i), -1)
+            assert np.array_equal(got, mine.astype(np.uint64)), (m, b, e)
+        mine = rs.window_base_counts(b, e)
+        direct = np.stack([(rs.codes[:, b:e] == code).sum(axis=1) for code in (rbc.A, 24, rbc.G, rbc.C)], axis=1)
+        assert np.array_equal(mine, direct.astype(np.uint32)), (b, e)
+        if e > b:
+            assert np.array_equal(oracle.count_bases_matrix(rs.codes[some, b:e]), mine[some].astype(np.uint64)), (b, e)
+            want = oracle.all_pairs_rect("raw", rs.codes[rows, b:e], rs.codes[cols, b:e]).ravel()
+            got = rs.window_values("raw", i, j, b, e)
+            assert np.array_equal(np.isnan(got), np.isnan(want)), (b, e)
+            ok = ~np.isnan(want)
+            assert np.array_equal(got[ok].view(np.uint64), want[ok].view(np.uint64)), (b, e)
+        else:
+            assert np.isnan(rs.window_values("raw", i, j, b, e)).all() and not rs.window_values("n", i, j, b, e).any()
+    # the whole width is the unwindowed form, and the last two sites leave some pairs without a comparable site
+    for m in MEASURES:
+        assert np.array_equal(rs.window_tallies(m, i, j, 0, 40), rs.tallies(m, i, j)), m
+    assert np.array_equal(rs.window_base_counts(0, 40), rs.base_counts())
+    assert set(np.unique(rs.window_comparable(i, j, 38, 40))) == {0, 1, 2}
+    assert set(rbc.NEAREST_WINDOWS) <= set(rbc.WINDOWS)
+
+
+def test_window_cases_reach_what_they_claim(rs):
+    """the constants of test_gpu_record_boundary_windows.py: a later change of one cannot silently empty a test"""
+    n, tall = rs.n, rbc.TALL_RECORDS
+    # d. more than 65,535 row tiles in one window launch, the second grid inside the set and, with the row begin, off a
+    # multiple of 8; the slab cut of nearest_windows and of the stream keeps all the rows in one slab
+    assert rbc.WIN_ROWS == 8 and tall == 524_289 and -(-tall // rbc.WIN_ROWS) > rbc.GRID_ROWS
+    assert rbc.second_grid_first_row(0, tall) == 524_280 < tall
+    assert rbc.second_grid_first_row(rbc.TALL_ROW_BEGIN, tall) == 524_283 < tall and 524_283 % 8 != 0
+    assert rbc.second_grid_first_row(0, n) is None
+    cols = rbc.tall_columns()
+    assert len(cols) == 5 and cols[0] == 0 and cols[-1] == tall - 1 and (np.diff(cols) > 0).all()
+    for n_windows in (1, 2):
+        assert rbc.cut_window_slabs(tall, n_windows, len(cols)) == (tall, n_windows)   # nearest_windows, the stream
+    ts = rbc.tall_set()
+    assert ts.n == tall and len(np.unique(ts.words)) == tall and ts.codes.nbytes < 22 << 20
+    # e. the cuts of nearest_windows on 10 rows x 3 windows x 92,700 columns: one list; a few rows of all windows; all rows
+    assert rbc.cut_window_slabs(10, 3, n, 1) == (1, 1)
+    assert rbc.cut_window_slabs(10, 3, n, n * 16) == (5, 3)
+    assert rbc.cut_window_slabs(10, 3, n) == (10, 3)
+    # f. the stream's ranges of the loaded 92,700 x 3 windows at batches of 128: two ranges of rows, each one grid
+    rows, wins = rbc.cut_window_slabs(n, 3, 128)
+    assert wins == 3 and n / 2 < rows < n and rbc.second_grid_first_row(0, rows) is None
+    # c. the square list: positions at or above 2^32, both sides of row 65,536, the diagonal, both orders, repeats
+    row, col = rbc.boundary_pairs()
+    lo, hi = np.minimum(row, col), np.maximum(row, col)
+    off = lo != hi
+    at = canon(n, lo[off], hi[off])
+    assert at.max() == n * (n - 1) // 2 - 1 == 4_296_598_649 and (at >= TWO32).sum() > 100 and (at < TWO32).sum() > 100
+    assert (lo == 65_535).any() and (lo == 65_536).any() and (~off).sum() == 4
+    assert (row < col).sum() > 1_000 and (row > col).sum() > 1_000 and not (np.diff(at) >= 0).all()
+    assert len(np.unique(at)) < off.sum() // 2 + 1   # every pair at least twice
+    assert lo[off].min() >= 65_530 and ((lo >= 65_545) & (lo < 90_890)).sum() == 0 and hi.max() == n - 1
+    default = rbc.touched_slabs(n, 1 << 25, row, col)
+    at_row = rbc.touched_slabs(n, rbc.max_pairs_cutting_in(n, 65_536, 65_536), row, col)
+    past = rbc.touched_slabs(n, rbc.max_pairs_cutting_in(n, FIRST_ROW_PAST_2_32, n - 2), row, col)
+    assert 2 <= len(default) <= 6 and 2 <= len(at_row) <= 6 and 2 <= len(past) <= 6
+    assert any(s[1] == 65_536 for s in at_row) and any(s[0] == 65_536 for s in at_row)
+    assert past[-1][2] >= TWO32 and default[-1][2] < TWO32 < default[-1][2] + default[-1][3]
+    # c. the rectangle list: positions i n + j either side of 2^32
+    row, col = rbc.boundary_rect_pairs()
+    at = row * n + col
+    assert rbc.FIRST_RECT_ROW_PAST_2_32 * n >= TWO32 > (rbc.FIRST_RECT_ROW_PAST_2_32 - 1) * n
+    assert (at == TWO32 - 1).sum() == 1 and (at == TWO32).sum() == 1 and (at >= TWO32).sum() == len(at) - 1
+    assert (row == col).sum() == 2 and at.max() == n * n - 1 and (row >= 65_536).any() and (col >= 65_536).any()
+    assert len(np.unique(row // 300)) <= 6   # (a slab of the default bound holds 361 rows)
 
 
 def greedy_cut(n, max_pairs):
