@@ -161,6 +161,8 @@ _SIGS = {
     "dst_sliding_windows": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, C.c_size_t, _u32p]),
     "dst_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint32, C.c_double, _vp, _vp,
                               _vp, _vp, C.c_size_t, _vp]),
+    "dst_window_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_uint32, C.c_double, _vp, _vp, _vp,
+                                     _vp, C.c_size_t]),
     "dst_group_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, C.c_double,
                                     C.c_uint64, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t]),
     "dst_mst": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, C.c_size_t, _u64p, _u32p]),

@@ -847,4 +847,66 @@ void write_window_nearest(const Run &run, const WindowList &wl, uint32_t k, uint
     out.finish();
 }
 
+// --window-summary T: dst_window_summary's counts and means, the mean (sum / compared) printed as --summary prints its own
+// (NaN: nothing compared).  By window: one line per window in the given order, "window, start, end, pairs, compared,
+// within, mean" from the windows' totals alone.  By record: for every record of the first input in input order one line per
+// window, "sequence, window, start, end, within, compared, mean".  The first three window fields are the plain --windows /
+// --regions run's.
+void write_window_summary(const Run &run, const WindowList &wl, double threshold, bool by_record)
+{
+    const Alignment &rows = run.rows();
+    const size_t nw = wl.begin.size();
+    run.header(by_record ? "sequence\twindow\tstart\tend\twithin\tcompared\tmean\n"
+                         : "window\tstart\tend\tpairs\tcompared\twithin\tmean\n");
+    if (nw == 0)
+        return;
+    const size_t entries = by_record ? nw * rows.n : 0, cap = std::max<size_t>(entries, 1);
+    std::vector<dst_summary_totals> totals(by_record ? 0 : nw);
+    std::vector<uint32_t> within(by_record ? cap : 0), summable(by_record ? cap : 0);
+    std::vector<double> sum(by_record ? cap : 0);
+    run.gpu.check(dst_window_summary(run.gpu.h, run.measure, run.square() ? 1 : 0, 0, 1, wl.begin.data(), wl.end.data(), (uint32_t)nw,
+                                     threshold, by_record ? nullptr : totals.data(), by_record ? within.data() : nullptr,
+                                     by_record ? summable.data() : nullptr, by_record ? sum.data() : nullptr, entries),
+                  "window summary");
+    LineWriter out(run.wr);
+    auto window_fields = [&](size_t w) {
+        out.put(wl.names[w]);
+        out.put('\t');
+        out.number(wl.begin[w] + 1);
+        out.put('\t');
+        out.number(wl.end[w]);
+        out.put('\t');
+    };
+    auto mean = [&](double s, uint64_t compared) {
+        out.distance(DST_RAW, compared ? s / (double)compared : std::nan(""), 0);
+        out.end_line();
+    };
+    if (!by_record) {
+        for (size_t w = 0; w < nw; ++w) {
+            window_fields(w);
+            out.number(totals[w].pairs);
+            out.put('\t');
+            out.number(totals[w].summable_pairs);
+            out.put('\t');
+            out.number(totals[w].links);
+            out.put('\t');
+            mean(totals[w].sum, totals[w].summable_pairs);
+        }
+    } else {
+        for (size_t i = 0; i < rows.n; ++i)
+            for (size_t w = 0; w < nw; ++w) {
+                const size_t e = w * rows.n + i;
+                out.put(rows.ids[i]);
+                out.put('\t');
+                window_fields(w);
+                out.number(within[e]);
+                out.put('\t');
+                out.number(summable[e]);
+                out.put('\t');
+                mean(sum[e], summable[e]);
+            }
+    }
+    out.finish();
+}
+
 }  // namespace

@@ -109,6 +109,13 @@ void print_help()
         "of the first input in every window (of the same file with one input, of the second file with two): per record and "
         "window the K lines of the plain --windows / --regions run with the smallest distance, nearest first, ties in input "
         "order\n"
+        "      --window-summary <T>     With --windows or --regions: print one line per window instead of one per pair and window: "
+        "the window, its pairs, how many were compared (pairs with a distance inside the window), how many lie within "
+        "distance T (a number >= 0, or inf) and their mean distance: diversity along the alignment, reduced on the GPU. "
+        "One input, or two (the records of the first against the second). One GPU, no --stream and no other output mode\n"
+        "      --window-summary-by <what>  What --window-summary prints a line for: window, or record (for every record of the "
+        "first input one line per window: the records within T of it inside the window, how many it was compared with and "
+        "its mean distance to those) [default: window]\n"
         "      --window-closest <K>     Stream mode, with --windows or --regions: for every loaded record and every window the K "
         "(1-256) nearest STREAMED records, written when the stream ends: byte for byte what '--window-nearest K loaded.fasta "
         "streamed.fasta' prints, for a streamed file that need not fit on the GPU. Requires --stream, one loaded file, one "
@@ -132,7 +139,8 @@ enum Flag {
     F_STREAM, F_MEASURE, F_OUTPUT, F_THREADS, F_BATCHSIZE, F_GPUS, F_DEVICES, F_SLAB_PAIRS, F_NEAREST, F_CLOSEST, F_CLOSEST_FOR,
     F_WITHIN, F_CLUSTERS, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS, F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX,
     F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM, F_SELFTEST, F_REPRESENTATIVES,
-    F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_PAIRS, F_WINDOW_CLOSEST, F_COUNT
+    F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_PAIRS, F_WINDOW_CLOSEST,
+    F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY, F_COUNT
 };
 struct FlagDef {
     const char *shown;   // "--name <value>": its first word is the flag itself
@@ -152,6 +160,7 @@ const FlagDef kFlags[F_COUNT] = {
     {"--host-selftest <what>", nullptr, false}, {"--representatives <T>", nullptr, true},
     {"--windows <W>", nullptr, true}, {"--step <S>", nullptr, true}, {"--regions <FILE>", nullptr, true},
     {"--window-nearest <K>", nullptr, true}, {"--pairs <FILE>", nullptr, true}, {"--window-closest <K>", nullptr, true},
+    {"--window-summary <T>", nullptr, true}, {"--window-summary-by <what>", nullptr, false},
 };
 
 // what the run prints, decided once by parse_args
@@ -189,6 +198,8 @@ struct Args {
     size_t window_nearest = 0;            // --window-nearest K (0: every pair)
     size_t window_closest = 0;            // --window-closest K (stream mode)
     std::string pairs;                    // --pairs FILE
+    double window_summary = 0;            // --window-summary T
+    bool window_summary_by_record = false;   // --window-summary-by window|record
     std::string selftest;
     size_t n_inputs() const { return flag_inputs.size() + pos_inputs.size(); }
     // the slab size an analysis is given: the library's own choice unless --slab-pairs was passed
@@ -275,6 +286,11 @@ std::vector<Flag> after(Flag first, std::vector<Flag> rest)
     return rest;
 }
 const Rule kRules[] = {
+    // (before every other row: a command line with --window-summary or --window-summary-by is judged here first, and no
+    // other line's outcome changes.  Like --window-nearest it leaves the mode to --windows / --regions.)
+    {F_WINDOW_SUMMARY_BY, Mode::Pairs, kNone, {F_WINDOW_SUMMARY}, "'--window-summary <T>'", TWO_OK, false},
+    {F_WINDOW_SUMMARY, Mode::Pairs, after(F_WINDOW_NEAREST, after(F_WINDOW_CLOSEST, after(F_PAIRS, kWindowRefuses))),
+     {F_WINDOWS, F_REGIONS}, "'--windows <W>' or '--regions <FILE>'", TWO_OK, true},
     // (before every other row: a command line with --window-closest is judged here first, and no other line's outcome
     // changes.  It is the one flag that takes --windows / --regions into stream mode: check_rules lets those two rows pass
     // --stream, and keep their hands off the mode, when it is there.  Two rows: what it needs is two things.)
@@ -432,7 +448,7 @@ Args parse_args(int argc, char **argv)
                    count(F_BINS, a.bins, 1, DST_SUMMARY_MAX_BINS) || count(F_BOOTSTRAP, a.bootstrap, 1, 10000) ||
                    threshold(F_CLUSTERS, a.clusters) || threshold(F_REPRESENTATIVES, a.representatives) || threshold(F_MAX_DISTANCE, a.max_distance) ||
                    threshold(F_WITHIN, a.within) || threshold(F_SUMMARY, a.summary) ||
-                   threshold(F_GROUPS_WITHIN, a.groups_within)) {
+                   threshold(F_GROUPS_WITHIN, a.groups_within) || threshold(F_WINDOW_SUMMARY, a.window_summary)) {
             // a word, a count in a range or a threshold: stored
         } else if (opt(F_GPUS)) {
             a.gpus = (int)parse_usize(v, shown(F_GPUS));
@@ -447,6 +463,8 @@ Args parse_args(int argc, char **argv)
         } else if (opt(F_CLOSEST_FOR)) {
             a.closest_side = parse_choice(v, shown(F_CLOSEST_FOR), {{"loaded", DST_CLOSEST_FOR_LOADED},
                                           {"streamed", DST_CLOSEST_FOR_STREAMED}});
+        } else if (opt(F_WINDOW_SUMMARY_BY)) {
+            a.window_summary_by_record = parse_choice(v, shown(F_WINDOW_SUMMARY_BY), {{"window", 0}, {"record", 1}}) != 0;
         } else if (opt(F_HISTOGRAM)) {
             a.histogram = parse_number(v, shown(F_HISTOGRAM));
             // dst_summary's bounds: the width as a fixed-point value is at least one unit (2^-37) and below 2^62

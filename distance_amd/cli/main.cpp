@@ -259,7 +259,9 @@ int main(int argc, char **argv)
     case Mode::Histogram: write_histogram(run, a.histogram, (uint32_t)a.bins); break;
     case Mode::Nearest: write_nearest(run, (uint32_t)a.nearest); break;
     case Mode::Windows:
-        if (a.has[F_WINDOW_NEAREST])
+        if (a.has[F_WINDOW_SUMMARY])
+            write_window_summary(run, windows, a.window_summary, a.window_summary_by_record);
+        else if (a.has[F_WINDOW_NEAREST])
             write_window_nearest(run, windows, (uint32_t)a.window_nearest, a.analysis_slab());
         else
             write_windows(run, windows, a.slab_pairs);

@@ -91,6 +91,14 @@ int matrix_finite(dst_ctx *ctx, const std::string &prefix, const double *d, uint
 
 }  // namespace
 
+// dst_summary's conversion: the exact sum hi 2^32 + lo to double once (round to nearest even), f64 measures scaled by
+// 2^-DST_SUMMARY_SCALE_BITS (exact)
+double dst::summary_value(__int128 s, bool int_payload)
+{
+    const double d = (double)s;
+    return int_payload ? d : std::ldexp(d, -DST_SUMMARY_SCALE_BITS);
+}
+
 // The threshold of dst_clusters / dst_links / a links stream as a payload: int64 payloads link when v <= floor(T) (clamped
 // to the int64 range), f64 payloads on their bits through nn_key.  false: floor(T) is below -2^63, nothing links.
 bool dst::threshold_payload(int measure, double threshold, uint64_t &t_bits)
@@ -138,14 +146,6 @@ size_t summary_layout(void *base, uint64_t records, uint32_t bins, SummaryBuffer
     b.hist = c.take<uint64_t>(bins);
     b.tot = c.take<uint64_t>(kSummaryTotals);
     return c.used;
-}
-
-// dst_summary's conversion: the exact sum hi 2^32 + lo to double once (round to nearest even), f64 measures scaled by
-// 2^-DST_SUMMARY_SCALE_BITS (exact)
-double summary_value(__int128 s, bool int_payload)
-{
-    const double d = (double)s;
-    return int_payload ? d : std::ldexp(d, -DST_SUMMARY_SCALE_BITS);
 }
 
 size_t nearest_layout(void *base, uint64_t entries, int W, NearestLists &nl)

@@ -117,6 +117,9 @@ struct dst_ctx {
     Grown<uint2> win_table;
     Grown<uint2, true> win_table_host;
     Grown<uint4> win_counts;
+    // dst_window_summary: the per (window, record) accumulators and the windows' totals, and their page-locked copy
+    Grown<> win_summary_work;
+    Grown<char, true> win_summary_host;
     Grown<> summary_work;   // dst_summary: the per-record counters and accumulators, the histogram and the totals
     // dst_group_summary: the labels, the cells and the per-record table; the labels' page-locked staging
     Grown<> group_work;
@@ -200,5 +203,7 @@ SlabPlan plan_slabs(bool square, uint64_t n_rows, uint64_t n_cols, uint64_t max_
 // the threshold of dst_clusters / dst_links / dst_stream_open_links as a payload of `measure`; false: nothing can link
 // (dst_analysis.cpp)
 bool threshold_payload(int measure, double threshold, uint64_t &t_bits);
+// dst_summary's one conversion of an exact integer sum to double (dst_analysis.cpp; dst_window_summary shares it)
+double summary_value(__int128 s, bool int_payload);
 
 }  // namespace dst

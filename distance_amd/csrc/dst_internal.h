@@ -686,6 +686,33 @@ hipError_t launch_window_pairs(int measure, const WindowLaunch &wl, hipStream_t 
 // counts[w * set.n + record] = the record's {A,T,G,C}, counted by code, inside window w
 hipError_t launch_window_counts(const DeviceSet &set, const uint2 *d_windows, uint32_t n_windows, uint4 *counts, hipStream_t stream);
 
+// ---- per-window summaries (dst_window_summary.hip, driven by dst_window_summary in dst_windows.hip) -------------------
+// The window sweep of all the rows with dst_summary's reduction in its epilogue.  The state is zeroed by the caller and
+// window-major: the per-record arrays [n_windows][rows->n] (all four, or all NULL: the totals only, O(n_windows) of
+// state), tot [n_windows][kWindowSummaryTotals]: NaN pairs, summable pairs, links, the high and the low word of the
+// 128-bit sum.  rows->n x n_windows <= 2^31 when the per-record arrays are there.
+constexpr int kWindowSummaryTotals = 5;
+enum {
+    kWinSumRect = 0,       // every row record against every column record; per-record entries of the row records
+    kWinSumTriangle = 1,   // one set, the pairs i < j; a pair adds to both of its records (row side and column side)
+    kWinSumFull = 2,       // one set, every row against all j != i, the row side only: links, summable pairs and the sum
+                           // of tot come out doubled; needs the per-record arrays (the measured alternative)
+};
+struct WindowSummaryLaunch {
+    const DeviceSet *rows, *cols;
+    int mode;
+    const uint2 *d_windows;        // [n_windows] {begin, end}
+    uint32_t n_windows;
+    const uint4 *q_counts, *t_counts;   // tn93: [n_windows][rows.n] / [n_windows][cols.n] {A,T,G,C} inside the window
+    uint64_t t_bits;               // the threshold as a payload; any: false when nothing can link (threshold_payload)
+    bool any;
+    uint32_t *within, *summable;
+    int64_t *hi;
+    uint64_t *lo;
+    uint64_t *tot;
+};
+hipError_t launch_window_summary(int measure, const WindowSummaryLaunch &wl, hipStream_t stream);
+
 // ---- k nearest records per window (dst_window_nearest.hip, driven by dst_nearest_windows in dst_windows.hip) ----------
 // A slab is rows [row0, row0 + nr) x windows [win0, win0 + nw) x all n_cols column records as DST_OUT_TALLY words, entry
 // (w_local * nr + i_local) * n_cols + j (launch_window_pairs with win_first = win0 on the rectangle; a square job sweeps

@@ -12,82 +12,15 @@
 // Tallies live in VGPRs for the sweep; the epilogue is the dense kernel's (M::tallies, then the tally words, the int64, or
 // finalize_pair).  Every entry has one writer: plain vector stores.
 //
-// The mask rule.  n / n_high / raw count the sites whose base sets SHARE a member and subtract from `total`; so a site
-// outside the window is taken out of the counted word, and total = end - begin (never the chunks' span).  Zeroing a
-// record's planes instead would make its masked sites certain differences.  k80 / tn93 count known sites only: every
-// counted word derives from one that the mask went into.
+// The sweep itself, with its mask rule, is dst_window_sweep.hpp's: window_summary_kernel (dst_window_summary.hip) runs the
+// same one.
 #include "dst_ctx.h"
 #include "dst_device.hpp"
 #include "dst_measures.hpp"
+#include "dst_window_sweep.hpp"
 
 namespace dst {
 namespace {
-
-constexpr int kWinRows = 8;          // row records of one block
-constexpr int kWinCols = 256;        // column records of one block: one per thread
-
-__device__ __forceinline__ uint32_t bits_below(uint32_t x) { return x >= 32u ? 0xFFFFFFFFu : (1u << x) - 1u; }
-
-// the sites of chunk c inside [begin, end), one bit per site (wave-uniform: SALU)
-__device__ __forceinline__ void window_mask(uint32_t c, uint32_t begin, uint32_t end, uint32_t (&m)[4])
-{
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const uint64_t ws = (uint64_t)c * kChunkSites + 32u * k;   // the word's first site
-        const uint32_t lo = begin <= ws ? 0u : begin - ws >= 32u ? 32u : (uint32_t)(begin - ws);
-        const uint32_t hi = end <= ws ? 0u : end - ws >= 32u ? 32u : (uint32_t)(end - ws);
-        m[k] = bits_below(hi) & ~bits_below(lo);   // (lo >= hi: empty)
-    }
-}
-
-// M::step with the sites outside m left out of every counted word
-template <class M>
-struct Masked;
-template <>
-struct Masked<MNHigh> {
-    static __device__ __forceinline__ void step(uint32_t *a, const uint32_t *q, const uint32_t *t, uint32_t m)
-    {
-        bcnt_acc(a[0], share_bits(q, t) & m);
-    }
-};
-template <>
-struct Masked<MRaw> {
-    static __device__ __forceinline__ void step(uint32_t *a, const uint32_t *q, const uint32_t *t, uint32_t m)
-    {
-        const uint32_t share = share_bits(q, t) & m;
-        bcnt_acc(a[0], share);
-        bcnt_acc(a[1], bitop3<TT_AND3>(share, q[4], t[4]));
-    }
-};
-template <>
-struct Masked<MK80> {
-    static __device__ __forceinline__ void step(uint32_t *a, const uint32_t *q, const uint32_t *t, uint32_t m)
-    {
-        const uint32_t e1 = q[1] ^ t[1];
-        const uint32_t sc = bitop3<TT_A_AND_B_ANDN_C>(q[0] & m, t[0], e1);   // (q and m are scalars: the AND is SALU)
-        const uint32_t ts = bitop3<TT_A_AND_B_NE_C>(sc, q[2], t[2]);
-        const uint32_t tv = bitop3<TT_AND3>(q[3] & m, t[3], e1);
-        bcnt_acc(a[0], sc);
-        bcnt_acc(a[1], ts);
-        bcnt_acc(a[2], tv);
-    }
-};
-template <>
-struct Masked<MTN93> {
-    static __device__ __forceinline__ void step(uint32_t *a, const uint32_t *q, const uint32_t *t, uint32_t m)
-    {
-        const uint32_t bk = bitop3<TT_AND3>(q[0], t[0], m);
-        const uint32_t sc = bitop3<TT_A_AND_B_EQ_C>(bk, q[1], t[1]);
-        const uint32_t ts = bitop3<TT_A_AND_B_NE_C>(sc, q[2], t[2]);
-        const uint32_t p2 = ts & q[1];
-        bcnt_acc(a[0], bk);
-        bcnt_acc(a[1], sc);
-        bcnt_acc(a[2], ts);
-        bcnt_acc(a[3], p2);
-    }
-};
-
-__device__ __forceinline__ uint32_t word_of(const uint4 &v, int k) { return k == 0 ? v.x : k == 1 ? v.y : k == 2 ? v.z : v.w; }
 
 // OUT: OUT_TALLY, OUT_INT, or the measure id whose f64 the epilogue writes (as pair_kernel)
 template <class M, int OUT>
@@ -97,7 +30,7 @@ __global__ __launch_bounds__(kWinCols) void window_pair_kernel(
     uint32_t q_n, uint32_t n_cols, uint32_t row_begin, uint32_t row_end, uint32_t row0, uint32_t win0, uint32_t win_first,
     uint64_t pairs, uint64_t out_base, int square)
 {
-    constexpr int NP = M::NP, NC = M::NC, NT = M::NT;
+    constexpr int NC = M::NC, NT = M::NT;
     constexpr int STAGE_WORDS = OUT >= 0 ? kWinRows * NT * kWinCols : 1;
     __shared__ uint32_t stage[STAGE_WORDS];
 
@@ -122,58 +55,7 @@ __global__ __launch_bounds__(kWinCols) void window_pair_kernel(
     const uint4 *qbase = qpl + (size_t)M::P0 * q_ps;
     const uint4 *tbase = tpl + (size_t)M::P0 * t_ps + jl;
 
-    if (we > wb) {
-        const uint32_t c_first = wb / kChunkSites, c_last = (we - 1u) / kChunkSites;
-#pragma unroll 1
-        for (uint32_t c = c_first; c <= c_last; ++c) {
-            uint4 tv[NP];
-#pragma unroll
-            for (int p = 0; p < NP; ++p)
-                tv[p] = tbase[(size_t)p * t_ps + (size_t)c * t_npad];
-            const bool whole = (uint64_t)c * kChunkSites >= wb && (uint64_t)c * kChunkSites + kChunkSites <= we;
-            if (whole) {
-#pragma unroll
-                for (int r = 0; r < kWinRows; ++r) {
-                    const uint32_t i = i0 + r < row_end ? i0 + r : row_end - 1u;   // (wave-uniform)
-                    uint4 qv[NP];
-#pragma unroll
-                    for (int p = 0; p < NP; ++p)
-                        qv[p] = qbase[(size_t)p * q_ps + (size_t)c * q_npad + i];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        uint32_t q[NP], t[NP];
-#pragma unroll
-                        for (int p = 0; p < NP; ++p) {
-                            q[p] = word_of(qv[p], k);
-                            t[p] = word_of(tv[p], k);
-                        }
-                        M::step(acc[r], q, t);
-                    }
-                }
-            } else {
-                uint32_t m[4];
-                window_mask(c, wb, we, m);
-#pragma unroll
-                for (int r = 0; r < kWinRows; ++r) {
-                    const uint32_t i = i0 + r < row_end ? i0 + r : row_end - 1u;
-                    uint4 qv[NP];
-#pragma unroll
-                    for (int p = 0; p < NP; ++p)
-                        qv[p] = qbase[(size_t)p * q_ps + (size_t)c * q_npad + i];
-#pragma unroll
-                    for (int k = 0; k < 4; ++k) {
-                        uint32_t q[NP], t[NP];
-#pragma unroll
-                        for (int p = 0; p < NP; ++p) {
-                            q[p] = word_of(qv[p], k);
-                            t[p] = word_of(tv[p], k);
-                        }
-                        Masked<M>::step(acc[r], q, t, m[k]);
-                    }
-                }
-            }
-        }
-    }
+    window_sweep<M>(acc, qbase, tbase, q_ps, t_ps, q_npad, t_npad, i0, row_end, wb, we);
 
     const uint32_t total = we - wb;
     const uint64_t win_at = (uint64_t)(w - win_first) * pairs;   // (the launch's first window lies at 0)
@@ -704,6 +586,126 @@ int dst_nearest_windows(dst_ctx *ctx, int measure, int square, int row_slot, int
         }
     }
     HIP_TRY(ctx, hipStreamSynchronize(stream));
+    return DST_OK;
+}
+
+int dst_window_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, const uint64_t *win_begin,
+                       const uint64_t *win_end, uint32_t n_windows, double threshold, dst_summary_totals *totals,
+                       uint32_t *rec_within, uint32_t *rec_summable, double *rec_sum, size_t rec_cap)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (n_windows > DST_WINDOWS_MAX)
+        return fail(ctx, DST_ERR_ARG, "more than DST_WINDOWS_MAX (65,536) windows");
+    if (n_windows && (!win_begin || !win_end))
+        return fail(ctx, DST_ERR_ARG, "null pointer");
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (std::isnan(threshold))
+        return fail(ctx, DST_ERR_ARG, "threshold is NaN");
+    const bool per_record = rec_within || rec_summable || rec_sum;
+    if (!totals && !per_record)
+        return fail(ctx, DST_ERR_ARG, "null output pointers: neither the totals nor a per-record array is wanted");
+    TwoSets ts;
+    if (int rc = two_sets(ctx, square != 0, row_slot, col_slot, ts))
+        return rc;
+    DeviceSet &rows = *ts.rows, &cols = *ts.cols;
+    if (rows.partial || cols.partial)
+        return fail(ctx, DST_ERR_STATE, kSharedRefusal);
+    if (rows.len >= ((uint64_t)1 << 32))
+        return fail(ctx, DST_ERR_ARG, "alignments of 2^32 sites or more are beyond dst_window_summary");
+    if (int rc = windows_valid(ctx, win_begin, win_end, n_windows, rows.len))
+        return rc;
+    if (rows.n >= 0xFFFFFFFFull || cols.n >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    const uint64_t n_rows = rows.n, n_cols = cols.n;
+    const uint64_t entries = n_rows * n_windows;   // (below 2^48)
+    if (per_record && entries > ((uint64_t)1 << 31))
+        return fail(ctx, DST_ERR_ARG, "per-record arrays of more than 2^31 entries (n_windows x the row set's records)");
+    if (per_record && (unsigned __int128)rec_cap < entries)
+        return fail(ctx, DST_ERR_CAPACITY, "rec_cap is below n_windows x the row set's record count");
+    const uint64_t pairs = pairs_in_rows(square != 0, n_cols, 0, n_rows);
+    if (n_windows == 0 || pairs == 0) {   // no launch: zero counts and sums
+        for (uint32_t w = 0; totals && w < n_windows; ++w)
+            totals[w] = dst_summary_totals{pairs, 0, 0, 0, 0.0};
+        for (uint64_t e = 0; per_record && e < entries; ++e) {
+            if (rec_within)
+                rec_within[e] = 0;
+            if (rec_summable)
+                rec_summable[e] = 0;
+            if (rec_sum)
+                rec_sum[e] = 0.0;
+        }
+        return DST_OK;
+    }
+    const bool int_payload = measure_is_int(measure);
+    // the state: the per-record arrays, window-major (the lanes of a column-side add hit adjacent words), then the totals
+    const auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t rec_entries = per_record ? (size_t)entries : 0;
+    const size_t at_summable = pad(rec_entries * 4), at_hi = at_summable + pad(rec_entries * 4), at_lo = at_hi + pad(rec_entries * 8),
+                 at_tot = at_lo + pad(rec_entries * 8), state_bytes = at_tot + pad((size_t)n_windows * kWindowSummaryTotals * 8);
+    {
+        const int rc = ctx->win_summary_work.grow(ctx, state_bytes);
+        if (rc == DST_ERR_NOMEM)
+            return fail(ctx, DST_ERR_NOMEM, "window summary: cannot allocate " + std::to_string(state_bytes) + " bytes for the per-window state");
+        if (rc)
+            return rc;
+    }
+    if (ctx->win_summary_host.bytes < state_bytes)   // (page-locked: the copy back runs at the link's rate)
+        if (int rc = ctx->win_summary_host.grow(ctx, state_bytes, "window summary"))
+            return rc;
+    hipStream_t stream = ctx->stream;
+    if (int rc = windows_prepare(ctx, ts, win_begin, win_end, n_windows, stream))
+        return rc;
+    char *state = static_cast<char *>(ctx->win_summary_work.ptr);
+    // measurement knob: the full square with the row side only, instead of the triangle's column side
+    static const bool full_square = std::getenv("DST_WINDOW_SUMMARY_FULL_SQUARE") != nullptr;
+    WindowSummaryLaunch wl{};
+    wl.rows = &rows;
+    wl.cols = &cols;
+    wl.mode = !square ? kWinSumRect : full_square && per_record ? kWinSumFull : kWinSumTriangle;    wl.d_windows = ctx->win_table;
+    wl.n_windows = n_windows;
+    wl.any = threshold_payload(measure, threshold, wl.t_bits);
+    if (per_record) {
+        wl.within = reinterpret_cast<uint32_t *>(state);
+        wl.summable = reinterpret_cast<uint32_t *>(state + at_summable);
+        wl.hi = reinterpret_cast<int64_t *>(state + at_hi);
+        wl.lo = reinterpret_cast<uint64_t *>(state + at_lo);
+    }
+    wl.tot = reinterpret_cast<uint64_t *>(state + at_tot);
+    HIP_TRY(ctx, hipMemsetAsync(state, 0, state_bytes, stream));
+    if (measure == DST_TN93)
+        if (int rc = window_count_tables(ctx, rows, cols, n_windows, stream, wl.q_counts, wl.t_counts))
+            return rc;
+    HIP_TRY(ctx, launch_window_summary(measure, wl, stream));
+    // the state back in one copy, then the 128-bit sums here
+    const char *host = ctx->win_summary_host;
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->win_summary_host, state, state_bytes, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    const uint32_t *h_within = reinterpret_cast<const uint32_t *>(host);
+    const uint32_t *h_summable = reinterpret_cast<const uint32_t *>(host + at_summable);
+    const int64_t *h_hi = reinterpret_cast<const int64_t *>(host + at_hi);
+    const uint64_t *h_lo = reinterpret_cast<const uint64_t *>(host + at_lo);
+    const uint64_t *h_tot = reinterpret_cast<const uint64_t *>(host + at_tot);
+    for (uint64_t e = 0; e < rec_entries; ++e) {
+        if (rec_within)
+            rec_within[e] = h_within[e];
+        if (rec_summable)
+            rec_summable[e] = h_summable[e];
+        if (rec_sum)
+            rec_sum[e] = summary_value((__int128)h_hi[e] * ((__int128)1 << 32) + (__int128)h_lo[e], int_payload);
+    }
+    const unsigned each = wl.mode == kWinSumFull ? 2 : 1;   // (the full square meets every pair twice)
+    for (uint32_t w = 0; w < n_windows; ++w) {
+        const uint64_t *t = h_tot + (size_t)w * kWindowSummaryTotals;
+        const __int128 all = (__int128)(((unsigned __int128)t[3] << 64) | t[4]);
+        if (t[1] % each || t[2] % each || all % each)
+            return fail(ctx, DST_ERR_STATE, "window summary: internal error, the two sides of the square disagree");
+        if (t[0] > pairs || t[1] / each > pairs - t[0] || t[2] / each > pairs - t[0])
+            return fail(ctx, DST_ERR_STATE, "window summary: internal error, a window counts more than its pairs");
+        if (totals)
+            totals[w] = dst_summary_totals{pairs, t[0], t[1] / each, t[2] / each, summary_value(all / each, int_payload)};
+    }
     return DST_OK;
 }
 

@@ -739,6 +739,39 @@ class Engine:
             out["hist"] = hist[:bins]
         return out
 
+    def window_summary(self, measure, windows, threshold: float = 0.0, square: bool = True, row_slot: int = 0,
+                       col_slot: int = 1, per_record: bool = True) -> dict:
+        """summary()'s counts and sums inside every column window [begin, end) of `windows` ((n_windows, 2) integers), reduced
+        next to the window sweep (dst_window_summary): a dict of `within`, `summable` (uint32) and `sum` (float64), each of
+        shape (n_windows, n_rows), unless per_record is False; and the totals `pairs`, `nan_pairs`, `summable_pairs`,
+        `links` (uint64) and `total_sum` (float64), each of shape (n_windows,).  Window w's entries are bitwise summary()'s
+        definition applied to run_windows(...)[w].  square: slot 0, every pair counts for both of its records; else the
+        records of row_slot against those of col_slot."""
+        m = _measure_id(measure)
+        begin, end, nw = _window_arrays(windows)
+        n_rows, _ = self.set_info(0 if square else row_slot)
+        entries = nw * n_rows
+        cap = max(entries, 1)
+        within = np.zeros(cap, np.uint32) if per_record else None
+        summable = np.zeros(cap, np.uint32) if per_record else None
+        sums = np.zeros(cap, np.float64) if per_record else None
+        tot = (SummaryTotals * max(nw, 1))()
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data
+
+        self._check(self._lib.dst_window_summary(self._h, m, int(square), row_slot, col_slot, begin.ctypes.data,
+                                                 end.ctypes.data, nw, float(threshold), C.addressof(tot), ptr(within),
+                                                 ptr(summable), ptr(sums), entries))
+        t = np.frombuffer(tot, dtype=np.dtype([("pairs", np.uint64), ("nan_pairs", np.uint64), ("summable_pairs", np.uint64),
+                                               ("links", np.uint64), ("sum", np.float64)]))[:nw]
+        out = {"pairs": t["pairs"].copy(), "nan_pairs": t["nan_pairs"].copy(), "summable_pairs": t["summable_pairs"].copy(),
+               "links": t["links"].copy(), "total_sum": t["sum"].copy()}
+        if per_record:
+            out.update(within=within[:entries].reshape(nw, n_rows), summable=summable[:entries].reshape(nw, n_rows),
+                       sum=sums[:entries].reshape(nw, n_rows))
+        return out
+
     def group_summary(self, measure, groups, n_groups=None, threshold: float = float("inf"), square: bool = True,
                       row_slot: int = 0, col_slot: int = 1, col_groups=None, n_col_groups=None, max_pairs: int = 0,
                       per_record: bool = False) -> dict:

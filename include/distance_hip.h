@@ -826,6 +826,46 @@ typedef struct dst_summary_totals {
 int dst_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, double threshold, uint64_t max_pairs,
                 uint32_t bins, double width, uint64_t *hist, uint32_t *within, uint32_t *summable, double *sum, size_t cap,
                 dst_summary_totals *totals);
+/* ---- summaries per column window ------------------------------------------------------------------- */
+/* dst_summary's counts and sums INSIDE every column window, reduced next to the window sweep on the GPU: diversity along
+ * the genome (pi per window with raw on one set, d_xy per window between two sets), the mean distance of a query to a
+ * panel per window, how many pairs lie within T inside each gene.  The state is O(n_windows), or O(n_windows x n_rows)
+ * when a per-record array is wanted; the n_windows x P result of dst_run_windows is never written.  The definition is
+ * fixed to the bit, and every accumulation is an integer one: the result does not depend on the order the pairs are met in.
+ *   sets, windows   exactly dst_run_windows': square != 0 is slot 0 against itself (row_slot / col_slot ignored), the pairs
+ *            i < j; else two different slots, every record of row_slot against every record of col_slot.  A window is a
+ *            half-open [begin, end), 0 <= begin <= end <= len; windows may overlap, repeat, be empty and come in any order;
+ *            1 <= n_windows <= DST_WINDOWS_MAX.  tn93 takes the per-window {A,T,G,C} counts counted by code.
+ *   payload  v of a pair in window w: bitwise the DST_OUT_DISTANCE entry dst_run_windows writes for it.
+ *   result of window w: dst_summary's definition applied to that window's payloads — the same link rule against
+ *            `threshold`, the same fixed-point q in units of 2^-DST_SUMMARY_SCALE_BITS, the same "summable", the same NaN
+ *            count, the same one conversion of the exact integer sum to double.
+ *   totals[w]   (n_windows entries, or NULL) pairs = P, the same in every window; nan_pairs; summable_pairs; links; sum.
+ *   rec_within, rec_summable, rec_sum   (each n_windows x n_rows entries, or NULL) entry w * n_rows + x, window-major as
+ *            dst_run_windows and dst_window_base_counts lay theirs out; n_rows = the row set's record count.  A square pair
+ *            counts for both of its records, as in dst_summary; a rectangle gives the row records only.
+ *   rec_cap  the room of each non-NULL per-record array in entries.
+ * An empty window follows from the definition: n / n_high give v = 0 for every pair (all summable, sum 0, links when
+ * threshold >= 0); raw gives NaN for every pair (nan_pairs = P).  Consequence: for a set uploaded without caller base
+ * counts, the window [0, len) gives dst_summary's totals and per-record arrays bitwise.
+ * Errors are dst_run_windows', in its order and with its messages, with these additions: DST_ERR_ARG for a NULL ctx; more
+ * than DST_WINDOWS_MAX windows; a NULL window array; an unknown measure; then a NaN threshold; then `totals` and all three
+ * per-record arrays NULL; a bad slot or equal slots; DST_ERR_STATE for a set not uploaded, different widths, or a set from
+ * dst_upload_shared (the windows' refusal); DST_ERR_ARG for len >= 2^32, a bad window (the message names the first), sets
+ * of 2^32-1 records or more, and a per-record array wanted with n_rows x n_windows above 2^31; DST_ERR_CAPACITY, with
+ * nothing written, when rec_cap is below n_windows x n_rows and a per-record array is given; DST_ERR_NOMEM, with the byte
+ * count, when the state (24 bytes per (window, record) when a per-record array is wanted, 40 bytes per window), the window
+ * table or tn93's count table does not fit.
+ * n_windows == 0, an empty row or column set, or a square set of fewer than 2 records: DST_OK with zero counts and sums,
+ * `pairs` set, and no launch.  Synchronous on the context's stream: one fused sweep-and-reduce launch family and one copy
+ * back.  A set with deferred planes gets them first; slots, the path choice, dst_last_path, dst_last_launch and later
+ * results are untouched.  Single GPU, loaded sets only. */
+int dst_window_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
+                       const uint64_t *win_begin, const uint64_t *win_end, uint32_t n_windows,
+                       double threshold,
+                       dst_summary_totals *totals,
+                       uint32_t *rec_within, uint32_t *rec_summable, double *rec_sum,
+                       size_t rec_cap);
 /* ---- group summaries ------------------------------------------------------------------------------ */
 /* dst_summary's exact sums keyed by a labelling of the records (lineages, sites, sampling months): per pair of groups the
  * number of pairs, of links and of summable pairs, the sum of the distances, the smallest and the largest distance ("within
