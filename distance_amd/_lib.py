@@ -32,6 +32,7 @@ WINDOWS_MAX = 65536           # DST_WINDOWS_MAX: the most windows of one dst_run
 SUMMARY_SCALE_BITS = 37  # DST_SUMMARY_SCALE_BITS: f64 distances are summed as rint(v * 2^37)
 SUMMARY_MAX_BINS = 4096   # DST_SUMMARY_MAX_BINS
 GROUPS_MAX = 1024         # DST_GROUPS_MAX: the most groups of one side of dst_group_summary
+WINDOW_GROUPS_MAX = 256   # DST_WINDOW_GROUPS_MAX: the most groups of one side of dst_window_group_summary
 GROUP_NONE = 0xFFFFFFFF   # DST_GROUP_NONE: a record that belongs to no group
 
 
@@ -165,6 +166,8 @@ _SIGS = {
                                      _vp, C.c_size_t]),
     "dst_group_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, C.c_double,
                                     C.c_uint64, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t]),
+    "dst_window_group_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp,
+                                           C.c_uint32, C.c_double, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t]),
     "dst_mst": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, C.c_size_t, _u64p, _u32p]),
     "dst_nj": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, C.c_size_t]),
     "dst_nj_matrix": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_size_t]),

@@ -328,13 +328,15 @@ void write_summary(const Run &run, double threshold)
 // --groups: the label file, read before any input is opened.  One "id<TAB>group" per line, empty lines skipped, no header.
 struct GroupFile {
     std::string path;
+    std::string flag = "--groups";   // the flag the messages name (--window-groups reads the same file)
     std::unordered_map<std::string, std::pair<std::string, size_t>> of;   // id -> (group, the line that set it)
 };
 
-GroupFile read_group_file(const std::string &path)
+GroupFile read_group_file(const std::string &path, const char *flag = "--groups")
 {
     GroupFile gf;
     gf.path = path;
+    gf.flag = flag;
     FILE *fh = open_input(path);
     std::string text;
     char buf[1 << 16];
@@ -353,7 +355,7 @@ GroupFile read_group_file(const std::string &path)
             line.pop_back();
         if (line.empty())
             continue;
-        const std::string where = "--groups: line " + std::to_string(line_no) + " of '" + path + "' ";
+        const std::string where = gf.flag + ": line " + std::to_string(line_no) + " of '" + path + "' ";
         const size_t tab = line.find('\t');
         if (tab == std::string::npos)
             die_message(where + "has no tab: expected 'id<TAB>group'");
@@ -377,7 +379,8 @@ struct GroupLabels {
     size_t assigned = 0;
 };
 
-GroupLabels label_records(const GroupFile &gf, const Alignment &set, const char *which, std::unordered_set<std::string> &seen)
+GroupLabels label_records(const GroupFile &gf, const Alignment &set, const char *which, std::unordered_set<std::string> &seen,
+                          size_t max_groups)
 {
     GroupLabels gl;
     gl.label.assign(set.n, DST_GROUP_NONE);
@@ -389,31 +392,76 @@ GroupLabels label_records(const GroupFile &gf, const Alignment &set, const char 
         seen.insert(set.ids[r]);
         const auto ins = number.emplace(it->second.first, (uint32_t)gl.names.size());
         if (ins.second) {
-            if (gl.names.size() == DST_GROUPS_MAX)
-                die_message("--groups: line " + std::to_string(it->second.second) + " of '" + gf.path + "' starts group " +
-                            std::to_string(DST_GROUPS_MAX + 1) + " of the " + which + " input: more than " +
-                            std::to_string(DST_GROUPS_MAX) + " groups");
+            if (gl.names.size() == max_groups)
+                die_message(gf.flag + ": line " + std::to_string(it->second.second) + " of '" + gf.path + "' starts group " +
+                            std::to_string(max_groups + 1) + " of the " + which + " input: more than " +
+                            std::to_string(max_groups) + " groups");
             gl.names.push_back(it->second.first);
         }
         gl.label[r] = ins.first->second;
         ++gl.assigned;
     }
     if (gl.assigned == 0)
-        die_message("--groups: no record of the " + std::string(which) + " input has a group in '" + gf.path + "'");
+        die_message(gf.flag + ": no record of the " + std::string(which) + " input has a group in '" + gf.path + "'");
     return gl;
 }
 
 // the records' labels, and what can be wrong with them: every input against the one label file
-std::vector<GroupLabels> label_inputs(const GroupFile &gf, const std::vector<Alignment> &loaded)
+std::vector<GroupLabels> label_inputs(const GroupFile &gf, const std::vector<Alignment> &loaded, size_t max_groups = DST_GROUPS_MAX)
 {
     std::vector<GroupLabels> labels;
     std::unordered_set<std::string> seen;
     for (size_t k = 0; k < loaded.size(); ++k)
-        labels.push_back(label_records(gf, loaded[k], k == 0 ? "first" : "second", seen));
+        labels.push_back(label_records(gf, loaded[k], k == 0 ? "first" : "second", seen, max_groups));
     if (seen.size() < gf.of.size())
-        std::fprintf(stderr, "warning: --groups: %zu ids of '%s' are not in the input and were skipped\n",
+        std::fprintf(stderr, "warning: %s: %zu ids of '%s' are not in the input and were skipped\n", gf.flag.c_str(),
                      gf.of.size() - seen.size(), gf.path.c_str());
     return labels;
+}
+
+// The fields --groups and --window-groups print behind the names of a line, each with its tab in front.
+// a cell: pairs, compared, [within,] mean, min, max
+void put_group_cell(LineWriter &out, int measure, const dst_group_cell &c, bool has_within)
+{
+    const bool int_payload = measure == DST_N || measure == DST_N_HIGH;
+    auto tab_number = [&](uint64_t v) {
+        out.put('\t');
+        out.number(v);
+    };
+    auto tab_distance = [&](int m, bool known, double v, int64_t iv) {
+        out.put('\t');
+        if (known)
+            out.distance(m, v, iv);
+        else
+            out.put("NaN");
+    };
+    tab_number(c.pairs);
+    tab_number(c.summable_pairs);
+    if (has_within)
+        tab_number(c.links);
+    tab_distance(DST_RAW, c.summable_pairs != 0, c.summable_pairs ? c.sum / (double)c.summable_pairs : 0.0, 0);
+    const bool known = c.pairs > c.nan_pairs;   // a pair whose payload is not NaN
+    for (const uint64_t bits : {c.min_bits, c.max_bits}) {
+        double v = 0;
+        std::memcpy(&v, &bits, 8);
+        tab_distance(measure, known, int_payload ? 0.0 : v, int_payload ? (int64_t)bits : 0);
+    }
+}
+
+// a record's entry for one group: compared, [within,] mean
+void put_group_record(LineWriter &out, uint32_t summable, uint32_t within, double sum, bool has_within)
+{
+    out.put('\t');
+    out.number(summable);
+    if (has_within) {
+        out.put('\t');
+        out.number(within);
+    }
+    out.put('\t');
+    if (summable)
+        out.distance(DST_RAW, sum / (double)summable, 0);
+    else
+        out.put("NaN");
 }
 
 // --groups: one line per cell (one input: a <= b; two: every cell), or with --per-record one line per record of the first
@@ -432,24 +480,12 @@ void write_groups(const Run &run, const std::vector<GroupLabels> &labels, bool h
                                     cells.size(), per_record ? within.data() : nullptr, per_record ? summable.data() : nullptr,
                                     per_record ? sum.data() : nullptr, sum.size()),
                   "group summary");
-    const bool int_payload = run.measure == DST_N || run.measure == DST_N_HIGH;
     LineWriter out(run.wr);
     out.put(per_record ? "sequence\tgroup\tcompared" : "group1\tgroup2\tpairs\tcompared");
     if (has_within)
         out.put("\twithin");
     out.put(per_record ? "\tmean" : "\tmean\tmin\tmax");
     out.end_line();
-    auto tab_number = [&](uint64_t v) {
-        out.put('\t');
-        out.number(v);
-    };
-    auto tab_distance = [&](int measure, bool known, double v, int64_t iv) {
-        out.put('\t');
-        if (known)
-            out.distance(measure, v, iv);
-        else
-            out.put("NaN");
-    };
     if (per_record) {
         for (size_t x = 0; x < n_rows; ++x)
             for (uint32_t g = 0; g < Gc; ++g) {
@@ -457,10 +493,7 @@ void write_groups(const Run &run, const std::vector<GroupLabels> &labels, bool h
                 out.put(run.rows().ids[x]);
                 out.put('\t');
                 out.put(cl.names[g]);
-                tab_number(summable[e]);
-                if (has_within)
-                    tab_number(within[e]);
-                tab_distance(DST_RAW, summable[e] != 0, summable[e] ? sum[e] / (double)summable[e] : 0.0, 0);
+                put_group_record(out, summable[e], within[e], sum[e], has_within);
                 out.end_line();
             }
     } else {
@@ -470,17 +503,7 @@ void write_groups(const Run &run, const std::vector<GroupLabels> &labels, bool h
                 out.put(rl.names[a]);
                 out.put('\t');
                 out.put(cl.names[b]);
-                tab_number(c.pairs);
-                tab_number(c.summable_pairs);
-                if (has_within)
-                    tab_number(c.links);
-                tab_distance(DST_RAW, c.summable_pairs != 0, c.summable_pairs ? c.sum / (double)c.summable_pairs : 0.0, 0);
-                const bool known = c.pairs > c.nan_pairs;   // a pair whose payload is not NaN
-                for (const uint64_t bits : {c.min_bits, c.max_bits}) {
-                    double v = 0;
-                    std::memcpy(&v, &bits, 8);
-                    tab_distance(run.measure, known, int_payload ? 0.0 : v, int_payload ? (int64_t)bits : 0);
-                }
+                put_group_cell(out, run.measure, c, has_within);
                 out.end_line();
             }
     }
@@ -905,6 +928,73 @@ void write_window_summary(const Run &run, const WindowList &wl, double threshold
                 out.put('\t');
                 mean(sum[e], summable[e]);
             }
+    }
+    out.finish();
+}
+
+// --window-groups FILE: --groups' lines per window, from dst_window_group_summary.  By cell: per window in the given order
+// "window, start, end" and then what --groups prints for the cell (one input: a <= b; two: every cell).  By record: for
+// every record of the first input and every window one line per group of the other side, "sequence, window, start, end"
+// and then what --groups --per-record prints.  The window fields are the plain --windows / --regions run's.
+void write_window_groups(const Run &run, const WindowList &wl, const std::vector<GroupLabels> &labels, bool has_within,
+                         double threshold, bool by_record)
+{
+    const bool square = run.square();
+    const GroupLabels &rl = labels[0], &cl = labels.back();
+    const uint32_t Gr = (uint32_t)rl.names.size(), Gc = (uint32_t)cl.names.size();
+    const Alignment &rows = run.rows();
+    const size_t nw = wl.begin.size();
+    LineWriter out(run.wr);
+    out.put(by_record ? "sequence\twindow\tstart\tend\tgroup\tcompared" : "window\tstart\tend\tgroup1\tgroup2\tpairs\tcompared");
+    if (has_within)
+        out.put("\twithin");
+    out.put(by_record ? "\tmean" : "\tmean\tmin\tmax");
+    out.end_line();
+    if (nw == 0) {
+        out.finish();
+        return;
+    }
+    const size_t entries = by_record ? nw * rows.n * Gc : 0, cap = std::max<size_t>(entries, 1);
+    std::vector<dst_group_cell> cells(by_record ? 0 : nw * Gr * Gc);
+    std::vector<uint32_t> within(by_record ? cap : 0), summable(by_record ? cap : 0);
+    std::vector<double> sum(by_record ? cap : 0);
+    run.gpu.check(dst_window_group_summary(run.gpu.h, run.measure, square ? 1 : 0, 0, 1, wl.begin.data(), wl.end.data(),
+                                           (uint32_t)nw, rl.label.data(), Gr, cl.label.data(), Gc,
+                                           has_within ? threshold : HUGE_VAL, by_record ? nullptr : cells.data(), cells.size(),
+                                           by_record ? within.data() : nullptr, by_record ? summable.data() : nullptr,
+                                           by_record ? sum.data() : nullptr, entries),
+                  "window group summary");
+    auto window_fields = [&](size_t w) {
+        out.put(wl.names[w]);
+        out.put('\t');
+        out.number(wl.begin[w] + 1);
+        out.put('\t');
+        out.number(wl.end[w]);
+        out.put('\t');
+    };
+    if (by_record) {
+        for (size_t x = 0; x < rows.n; ++x)
+            for (size_t w = 0; w < nw; ++w)
+                for (uint32_t g = 0; g < Gc; ++g) {
+                    const size_t e = (w * rows.n + x) * Gc + g;
+                    out.put(rows.ids[x]);
+                    out.put('\t');
+                    window_fields(w);
+                    out.put(cl.names[g]);
+                    put_group_record(out, summable[e], within[e], sum[e], has_within);
+                    out.end_line();
+                }
+    } else {
+        for (size_t w = 0; w < nw; ++w)
+            for (uint32_t a = 0; a < Gr; ++a)
+                for (uint32_t b = square ? a : 0; b < Gc; ++b) {
+                    window_fields(w);
+                    out.put(rl.names[a]);
+                    out.put('\t');
+                    out.put(cl.names[b]);
+                    put_group_cell(out, run.measure, cells[(w * Gr + a) * Gc + b], has_within);
+                    out.end_line();
+                }
     }
     out.finish();
 }

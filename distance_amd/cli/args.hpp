@@ -116,6 +116,16 @@ void print_help()
         "      --window-summary-by <what>  What --window-summary prints a line for: window, or record (for every record of the "
         "first input one line per window: the records within T of it inside the window, how many it was compared with and "
         "its mean distance to those) [default: window]\n"
+        "      --window-groups <FILE>   With --windows or --regions: print --groups' lines per window instead of one line per pair "
+        "and window: FILE as for --groups (at most 256 groups in one input); per window and pair of groups the pairs, how many "
+        "were compared, their mean, smallest and largest distance inside the window, reduced on the GPU. With '-m raw' the "
+        "mean of a group with itself is its nucleotide diversity in the window, the mean between two groups their d_xy. One "
+        "input, or two (the records of the first against the second). One GPU, no --stream and no other output mode\n"
+        "      --window-groups-within <T>  With --window-groups: a 'within' column, the compared pairs within distance T (a "
+        "number >= 0, or inf)\n"
+        "      --window-groups-by <what>  What --window-groups prints a line for: cell (a pair of groups), or record (for every "
+        "record of the first input and every window one line per group of the other side: how many of the group it was "
+        "compared with and its mean distance to them) [default: cell]\n"
         "      --window-closest <K>     Stream mode, with --windows or --regions: for every loaded record and every window the K "
         "(1-256) nearest STREAMED records, written when the stream ends: byte for byte what '--window-nearest K loaded.fasta "
         "streamed.fasta' prints, for a streamed file that need not fit on the GPU. Requires --stream, one loaded file, one "
@@ -140,7 +150,7 @@ enum Flag {
     F_WITHIN, F_CLUSTERS, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS, F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX,
     F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM, F_SELFTEST, F_REPRESENTATIVES,
     F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_PAIRS, F_WINDOW_CLOSEST,
-    F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY, F_COUNT
+    F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY, F_WINDOW_GROUPS, F_WINDOW_GROUPS_WITHIN, F_WINDOW_GROUPS_BY, F_COUNT
 };
 struct FlagDef {
     const char *shown;   // "--name <value>": its first word is the flag itself
@@ -161,6 +171,8 @@ const FlagDef kFlags[F_COUNT] = {
     {"--windows <W>", nullptr, true}, {"--step <S>", nullptr, true}, {"--regions <FILE>", nullptr, true},
     {"--window-nearest <K>", nullptr, true}, {"--pairs <FILE>", nullptr, true}, {"--window-closest <K>", nullptr, true},
     {"--window-summary <T>", nullptr, true}, {"--window-summary-by <what>", nullptr, false},
+    {"--window-groups <FILE>", nullptr, true}, {"--window-groups-within <T>", nullptr, true},
+    {"--window-groups-by <what>", nullptr, false},
 };
 
 // what the run prints, decided once by parse_args
@@ -200,6 +212,9 @@ struct Args {
     std::string pairs;                    // --pairs FILE
     double window_summary = 0;            // --window-summary T
     bool window_summary_by_record = false;   // --window-summary-by window|record
+    std::string window_groups;            // --window-groups FILE
+    double window_groups_within = 0;      // --window-groups-within T
+    bool window_groups_by_record = false;    // --window-groups-by cell|record
     std::string selftest;
     size_t n_inputs() const { return flag_inputs.size() + pos_inputs.size(); }
     // the slab size an analysis is given: the library's own choice unless --slab-pairs was passed
@@ -286,6 +301,13 @@ std::vector<Flag> after(Flag first, std::vector<Flag> rest)
     return rest;
 }
 const Rule kRules[] = {
+    // (before every other row: a command line with --window-groups or one of its two modifiers is judged here first, and no
+    // other line's outcome changes.  Like --window-summary it leaves the mode to --windows / --regions.)
+    {F_WINDOW_GROUPS_WITHIN, Mode::Pairs, kNone, {F_WINDOW_GROUPS}, "'--window-groups <FILE>'", TWO_OK, false},
+    {F_WINDOW_GROUPS_BY, Mode::Pairs, kNone, {F_WINDOW_GROUPS}, "'--window-groups <FILE>'", TWO_OK, false},
+    {F_WINDOW_GROUPS, Mode::Pairs,
+     after(F_WINDOW_NEAREST, after(F_WINDOW_CLOSEST, after(F_WINDOW_SUMMARY, after(F_PAIRS, kWindowRefuses)))),
+     {F_WINDOWS, F_REGIONS}, "'--windows <W>' or '--regions <FILE>'", TWO_OK, true},
     // (before every other row: a command line with --window-summary or --window-summary-by is judged here first, and no
     // other line's outcome changes.  Like --window-nearest it leaves the mode to --windows / --regions.)
     {F_WINDOW_SUMMARY_BY, Mode::Pairs, kNone, {F_WINDOW_SUMMARY}, "'--window-summary <T>'", TWO_OK, false},
@@ -440,7 +462,7 @@ Args parse_args(int argc, char **argv)
             while (a.flag_inputs.size() < 2 && k + 1 < argc && (argv[k + 1][0] != '-' || !std::strcmp(argv[k + 1], "-")))
                 a.flag_inputs.push_back(argv[++k]);
         } else if (text(F_STREAM, a.stream) || text(F_MEASURE, a.measure) || text(F_OUTPUT, a.output) ||
-                   text(F_GROUPS, a.groups) || text(F_REGIONS, a.regions) || text(F_PAIRS, a.pairs) || count(F_WINDOWS, a.windows, 1, SIZE_MAX) ||
+                   text(F_GROUPS, a.groups) || text(F_WINDOW_GROUPS, a.window_groups) || text(F_REGIONS, a.regions) || text(F_PAIRS, a.pairs) || count(F_WINDOWS, a.windows, 1, SIZE_MAX) ||
                    count(F_STEP, a.step, 1, SIZE_MAX) || count(F_THREADS, a.threads, 0, SIZE_MAX) ||
                    count(F_BATCHSIZE, a.batchsize, 0, SIZE_MAX) || count(F_SEED, a.seed, 0, SIZE_MAX) ||
                    count(F_NEAREST, a.nearest, 1, 256) || count(F_CLOSEST, a.closest, 1, 256) ||
@@ -448,7 +470,8 @@ Args parse_args(int argc, char **argv)
                    count(F_BINS, a.bins, 1, DST_SUMMARY_MAX_BINS) || count(F_BOOTSTRAP, a.bootstrap, 1, 10000) ||
                    threshold(F_CLUSTERS, a.clusters) || threshold(F_REPRESENTATIVES, a.representatives) || threshold(F_MAX_DISTANCE, a.max_distance) ||
                    threshold(F_WITHIN, a.within) || threshold(F_SUMMARY, a.summary) ||
-                   threshold(F_GROUPS_WITHIN, a.groups_within) || threshold(F_WINDOW_SUMMARY, a.window_summary)) {
+                   threshold(F_GROUPS_WITHIN, a.groups_within) || threshold(F_WINDOW_GROUPS_WITHIN, a.window_groups_within) ||
+                   threshold(F_WINDOW_SUMMARY, a.window_summary)) {
             // a word, a count in a range or a threshold: stored
         } else if (opt(F_GPUS)) {
             a.gpus = (int)parse_usize(v, shown(F_GPUS));
@@ -465,6 +488,8 @@ Args parse_args(int argc, char **argv)
                                           {"streamed", DST_CLOSEST_FOR_STREAMED}});
         } else if (opt(F_WINDOW_SUMMARY_BY)) {
             a.window_summary_by_record = parse_choice(v, shown(F_WINDOW_SUMMARY_BY), {{"window", 0}, {"record", 1}}) != 0;
+        } else if (opt(F_WINDOW_GROUPS_BY)) {
+            a.window_groups_by_record = parse_choice(v, shown(F_WINDOW_GROUPS_BY), {{"cell", 0}, {"record", 1}}) != 0;
         } else if (opt(F_HISTOGRAM)) {
             a.histogram = parse_number(v, shown(F_HISTOGRAM));
             // dst_summary's bounds: the width as a fixed-point value is at least one unit (2^-37) and below 2^62

@@ -155,6 +155,8 @@ int main(int argc, char **argv)
     GroupFile group_file;
     if (a.mode == Mode::Groups)
         group_file = read_group_file(a.groups);
+    else if (a.has[F_WINDOW_GROUPS])
+        group_file = read_group_file(a.window_groups, "--window-groups");
     // --pairs: likewise
     PairFile pair_file;
     if (a.mode == Mode::PairList)
@@ -192,6 +194,8 @@ int main(int argc, char **argv)
     std::vector<GroupLabels> group_labels;
     if (a.mode == Mode::Groups)
         group_labels = label_inputs(group_file, loaded);
+    else if (a.has[F_WINDOW_GROUPS])
+        group_labels = label_inputs(group_file, loaded, DST_WINDOW_GROUPS_MAX);
     // --pairs: the records its ids name
     PairList pair_list;
     if (a.mode == Mode::PairList)
@@ -259,7 +263,10 @@ int main(int argc, char **argv)
     case Mode::Histogram: write_histogram(run, a.histogram, (uint32_t)a.bins); break;
     case Mode::Nearest: write_nearest(run, (uint32_t)a.nearest); break;
     case Mode::Windows:
-        if (a.has[F_WINDOW_SUMMARY])
+        if (a.has[F_WINDOW_GROUPS])
+            write_window_groups(run, windows, group_labels, a.has[F_WINDOW_GROUPS_WITHIN], a.window_groups_within,
+                                a.window_groups_by_record);
+        else if (a.has[F_WINDOW_SUMMARY])
             write_window_summary(run, windows, a.window_summary, a.window_summary_by_record);
         else if (a.has[F_WINDOW_NEAREST])
             write_window_nearest(run, windows, (uint32_t)a.window_nearest, a.analysis_slab());

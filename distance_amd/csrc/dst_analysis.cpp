@@ -1167,6 +1167,12 @@ size_t group_layout(void *base, bool square, uint64_t n_rows, uint64_t n_cols, u
     return c.used;
 }
 
+}  // namespace
+
+// shared with dst_window_group_summary (dst_windows.hip; declared in dst_internal.h)
+extern "C++" {
+namespace dst {
+
 // the payload of a sort key (nn_key, dst_device.hpp): -0.0 has the key of +0.0 and comes back as +0.0
 uint64_t payload_of_key(uint64_t key, bool int_payload)
 {
@@ -1191,7 +1197,8 @@ int group_labels(dst_ctx *ctx, const uint32_t *group, uint64_t n, uint32_t count
     return DST_OK;
 }
 
-}  // namespace
+}  // namespace dst
+}  // extern "C++"
 
 int dst_group_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, const uint32_t *row_group,
                       uint32_t n_row_groups, const uint32_t *col_group, uint32_t n_col_groups, double threshold,

@@ -120,6 +120,10 @@ struct dst_ctx {
     // dst_window_summary: the per (window, record) accumulators and the windows' totals, and their page-locked copy
     Grown<> win_summary_work;
     Grown<char, true> win_summary_host;
+    // dst_window_group_summary: the labels, the per-window cells and the per (window, record, group) accumulators, and
+    // their page-locked copy
+    Grown<> win_group_work;
+    Grown<char, true> win_group_host;
     Grown<> summary_work;   // dst_summary: the per-record counters and accumulators, the histogram and the totals
     // dst_group_summary: the labels, the cells and the per-record table; the labels' page-locked staging
     Grown<> group_work;

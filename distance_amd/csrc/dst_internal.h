@@ -713,6 +713,40 @@ struct WindowSummaryLaunch {
 };
 hipError_t launch_window_summary(int measure, const WindowSummaryLaunch &wl, hipStream_t stream);
 
+// ---- per-window group summaries (dst_window_group_summary.hip, driven by dst_window_group_summary in dst_windows.hip) --
+// The same sweep with dst_group_summary's reduction in its epilogue.  The state is zeroed by the caller, the cells' min
+// keys then set by launch_window_group_init.  cell [n_windows][g_rows][g_cols][kWindowGroupCellWords]: NaN pairs, links,
+// summable pairs, the high and the low word of the 128-bit sum, the smallest nn_key (~0: none), the largest (0: none).
+// The per-record arrays [n_windows][rows->n][g_cols] (all three, or all NULL): within << 32 | summable, hi, lo.
+// mode: kWinSumRect; kWinSumTriangle (cells alone: each pair i < j once at (group of i, group of j)); kWinSumFull (with the
+// per-record arrays: every row against all j != i, so cell (a, b != a) holds each pair once and cell (a, a) each twice).
+constexpr int kWindowGroupCellWords = 7;
+struct WindowGroupLaunch {
+    const DeviceSet *rows, *cols;
+    int mode;
+    const uint2 *d_windows;        // [n_windows] {begin, end}
+    uint32_t n_windows;
+    const uint4 *q_counts;         // tn93 only: per-window base counts of the row set [n_windows][rows->n] and of the
+    const uint4 *t_counts;         // column set [n_windows][cols->n]
+    uint64_t t_bits;               // the threshold as a payload; any: false when nothing can link (threshold_payload)
+    bool any;
+    const uint32_t *row_group;     // [rows->n] labels below g_rows, or DST_GROUP_NONE
+    const uint32_t *col_group;     // [cols->n] labels below g_cols (one set: row_group again)
+    uint32_t g_rows, g_cols;       // 1 .. DST_WINDOW_GROUPS_MAX
+    uint64_t *cell;
+    uint64_t *rec_counts;
+    int64_t *rec_hi;
+    uint64_t *rec_lo;
+};
+hipError_t launch_window_group_init(uint64_t *cell, uint64_t cells, hipStream_t stream);
+hipError_t launch_window_groups(int measure, const WindowGroupLaunch &wl, hipStream_t stream);
+
+// dst_group_summary's label check (dst_analysis.cpp): size[a] = the records of group a; the error names the first record
+// whose label is neither below `count` nor DST_GROUP_NONE, and its side
+int group_labels(dst_ctx *ctx, const uint32_t *group, uint64_t n, uint32_t count, const char *side, std::vector<uint64_t> &size);
+// the payload of a sort key (nn_key): -0.0 has the key of +0.0 and comes back as +0.0
+uint64_t payload_of_key(uint64_t key, bool int_payload);
+
 // ---- k nearest records per window (dst_window_nearest.hip, driven by dst_nearest_windows in dst_windows.hip) ----------
 // A slab is rows [row0, row0 + nr) x windows [win0, win0 + nw) x all n_cols column records as DST_OUT_TALLY words, entry
 // (w_local * nr + i_local) * n_cols + j (launch_window_pairs with win_first = win0 on the rectangle; a square job sweeps

@@ -19,6 +19,10 @@
 #include "dst_measures.hpp"
 #include "dst_window_sweep.hpp"
 
+#include <algorithm>
+#include <cstring>
+#include <vector>
+
 namespace dst {
 namespace {
 
@@ -705,6 +709,195 @@ int dst_window_summary(dst_ctx *ctx, int measure, int square, int row_slot, int 
             return fail(ctx, DST_ERR_STATE, "window summary: internal error, a window counts more than its pairs");
         if (totals)
             totals[w] = dst_summary_totals{pairs, t[0], t[1] / each, t[2] / each, summary_value(all / each, int_payload)};
+    }
+    return DST_OK;
+}
+
+int dst_window_group_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, const uint64_t *win_begin,
+                             const uint64_t *win_end, uint32_t n_windows, const uint32_t *row_group, uint32_t n_row_groups,
+                             const uint32_t *col_group, uint32_t n_col_groups, double threshold, dst_group_cell *cells,
+                             size_t cells_cap, uint32_t *rec_within, uint32_t *rec_summable, double *rec_sum, size_t rec_cap)
+{
+    if (!ctx)
+        return DST_ERR_ARG;
+    if (n_windows > DST_WINDOWS_MAX)
+        return fail(ctx, DST_ERR_ARG, "more than DST_WINDOWS_MAX (65,536) windows");
+    if (n_windows && (!win_begin || !win_end))
+        return fail(ctx, DST_ERR_ARG, "null pointer");
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (std::isnan(threshold))
+        return fail(ctx, DST_ERR_ARG, "threshold is NaN");
+    const bool per_record = rec_within || rec_summable || rec_sum;
+    if (!cells && !per_record)
+        return fail(ctx, DST_ERR_ARG, "null cells pointer and no per-record array");
+    if (!row_group)
+        return fail(ctx, DST_ERR_ARG, "null row_group pointer");
+    if (square) {
+        col_group = row_group;
+        n_col_groups = n_row_groups;
+    } else if (!col_group)
+        return fail(ctx, DST_ERR_ARG, "null col_group pointer");
+    if (n_row_groups == 0 || n_row_groups > DST_WINDOW_GROUPS_MAX || n_col_groups == 0 || n_col_groups > DST_WINDOW_GROUPS_MAX)
+        return fail(ctx, DST_ERR_ARG, "a group count must be between 1 and " + std::to_string(DST_WINDOW_GROUPS_MAX));
+    TwoSets ts;
+    if (int rc = two_sets(ctx, square != 0, row_slot, col_slot, ts))
+        return rc;
+    DeviceSet &rows = *ts.rows, &cols = *ts.cols;
+    if (rows.partial || cols.partial)
+        return fail(ctx, DST_ERR_STATE, kSharedRefusal);
+    if (rows.len >= ((uint64_t)1 << 32))
+        return fail(ctx, DST_ERR_ARG, "alignments of 2^32 sites or more are beyond dst_window_group_summary");
+    if (int rc = windows_valid(ctx, win_begin, win_end, n_windows, rows.len))
+        return rc;
+    if (rows.n >= 0xFFFFFFFFull || cols.n >= 0xFFFFFFFFull)
+        return fail(ctx, DST_ERR_ARG, "sets of 2^32-1 records or more");
+    const uint64_t n_rows = rows.n, n_cols = cols.n;
+    const uint32_t Gr = n_row_groups, Gc = n_col_groups;
+    std::vector<uint64_t> row_size, col_size_own;
+    if (int rc = group_labels(ctx, row_group, n_rows, Gr, square ? "set" : "row", row_size))
+        return rc;
+    if (!square)
+        if (int rc = group_labels(ctx, col_group, n_cols, Gc, "column", col_size_own))
+            return rc;
+    const std::vector<uint64_t> &col_size = square ? row_size : col_size_own;
+    const uint64_t per_window = (uint64_t)Gr * Gc;                              // cells of one window (at most 2^16)
+    const uint64_t n_cells = per_window * n_windows;                            // (at most 2^32)
+    const unsigned __int128 entries = (unsigned __int128)n_rows * n_windows * Gc;   // per-record entries
+    if (n_cells > ((uint64_t)1 << 31))
+        return fail(ctx, DST_ERR_ARG, "more than 2^31 cells (n_windows x row groups x column groups)");
+    if (per_record && entries > ((unsigned __int128)1 << 31))
+        return fail(ctx, DST_ERR_ARG, "per-record arrays of more than 2^31 entries (n_windows x the row set's records x column groups)");
+    if (cells && (unsigned __int128)cells_cap < n_cells)
+        return fail(ctx, DST_ERR_CAPACITY, "cells_cap is below " + std::to_string(n_cells) + " entries (n_windows x row groups x column groups)");
+    if (per_record && (unsigned __int128)rec_cap < entries)
+        return fail(ctx, DST_ERR_CAPACITY, "rec_cap is below " + std::to_string((uint64_t)entries) +
+                                               " entries (n_windows x the row set's records x column groups)");
+    const size_t rec_entries = per_record ? (size_t)entries : 0;
+    const bool int_payload = measure_is_int(measure);
+    // what an empty call returns; `pairs` from the group sizes, the same in every window
+    const uint64_t none = int_payload ? 0 : 0x7FF8000000000000ull;
+    std::vector<uint64_t> cell_pairs(per_window);
+    for (uint32_t a = 0; a < Gr; ++a)
+        for (uint32_t b = 0; b < Gc; ++b)
+            cell_pairs[(size_t)a * Gc + b] =
+                square && a == b ? row_size[a] * (row_size[a] - (row_size[a] ? 1 : 0)) / 2 : row_size[a] * col_size[b];
+    if (cells)
+        for (uint32_t w = 0; w < n_windows; ++w)
+            for (uint64_t c = 0; c < per_window; ++c)
+                cells[(size_t)w * per_window + c] = dst_group_cell{cell_pairs[c], 0, 0, 0, 0.0, none, none};
+    for (size_t e = 0; e < rec_entries; ++e) {
+        if (rec_within)
+            rec_within[e] = 0;
+        if (rec_summable)
+            rec_summable[e] = 0;
+        if (rec_sum)
+            rec_sum[e] = 0.0;
+    }
+    if (n_windows == 0 || pairs_in_rows(square != 0, n_cols, 0, n_rows) == 0)
+        return DST_OK;   // (no pair: no launch)
+    uint64_t rows_assigned = 0, cols_assigned = 0;
+    for (uint64_t s : row_size)
+        rows_assigned += s;
+    for (uint64_t s : col_size)
+        cols_assigned += s;
+    if (cols_assigned == 0 || (rows_assigned == 0 && !per_record))
+        return DST_OK;   // (no partner has a group, or no cell has a pair and only the cells are wanted)
+    // the state: the labels, then what comes back: the cells and the per-record arrays behind them
+    const auto pad = [](size_t b) { return (b + 255) / 256 * 256; };
+    const size_t at_col = pad((size_t)n_rows * 4), at_cells = square ? at_col : at_col + pad((size_t)n_cols * 4),
+                 at_counts = at_cells + pad((size_t)n_cells * kWindowGroupCellWords * 8), at_hi = at_counts + pad(rec_entries * 8),
+                 at_lo = at_hi + pad(rec_entries * 8), state_bytes = at_lo + pad(rec_entries * 8);
+    {
+        const int rc = ctx->win_group_work.grow(ctx, state_bytes);
+        if (rc == DST_ERR_NOMEM)
+            return fail(ctx, DST_ERR_NOMEM,
+                        "window group summary: cannot allocate " + std::to_string(state_bytes) + " bytes for the per-window state");
+        if (rc)
+            return rc;
+    }
+    if (ctx->win_group_host.bytes < state_bytes)   // (page-locked: the copy back runs at the link's rate)
+        if (int rc = ctx->win_group_host.grow(ctx, state_bytes, "window group summary"))
+            return rc;
+    hipStream_t stream = ctx->stream;
+    if (int rc = windows_prepare(ctx, ts, win_begin, win_end, n_windows, stream))
+        return rc;
+    char *state = static_cast<char *>(ctx->win_group_work.ptr);
+    char *host = ctx->win_group_host;
+    std::memcpy(host, row_group, (size_t)n_rows * 4);
+    if (!square)
+        std::memcpy(host + at_col, col_group, (size_t)n_cols * 4);
+    WindowGroupLaunch wl{};
+    wl.rows = &rows;
+    wl.cols = &cols;
+    // the square: the triangle for the cells alone; with per-record arrays the full square, the row side only
+    wl.mode = !square ? kWinSumRect : per_record ? kWinSumFull : kWinSumTriangle;
+    wl.d_windows = ctx->win_table;
+    wl.n_windows = n_windows;
+    wl.any = threshold_payload(measure, threshold, wl.t_bits);
+    wl.row_group = reinterpret_cast<const uint32_t *>(state);
+    wl.col_group = square ? wl.row_group : reinterpret_cast<const uint32_t *>(state + at_col);
+    wl.g_rows = Gr;
+    wl.g_cols = Gc;
+    wl.cell = reinterpret_cast<uint64_t *>(state + at_cells);
+    if (per_record) {
+        wl.rec_counts = reinterpret_cast<uint64_t *>(state + at_counts);
+        wl.rec_hi = reinterpret_cast<int64_t *>(state + at_hi);
+        wl.rec_lo = reinterpret_cast<uint64_t *>(state + at_lo);
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(state, host, at_cells, hipMemcpyHostToDevice, stream));
+    HIP_TRY(ctx, hipMemsetAsync(state + at_cells, 0, state_bytes - at_cells, stream));
+    HIP_TRY(ctx, launch_window_group_init(wl.cell, n_cells, stream));
+    if (measure == DST_TN93)
+        if (int rc = window_count_tables(ctx, rows, cols, n_windows, stream, wl.q_counts, wl.t_counts))
+            return rc;
+    HIP_TRY(ctx, launch_window_groups(measure, wl, stream));
+    // the cells and the arrays behind them back in one copy, then the 128-bit sums here
+    HIP_TRY(ctx, hipMemcpyAsync(host + at_cells, state + at_cells, state_bytes - at_cells, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(ctx, hipStreamSynchronize(stream));
+    const uint64_t *h_cell = reinterpret_cast<const uint64_t *>(host + at_cells);
+    const uint64_t *h_counts = reinterpret_cast<const uint64_t *>(host + at_counts);
+    const int64_t *h_hi = reinterpret_cast<const int64_t *>(host + at_hi);
+    const uint64_t *h_lo = reinterpret_cast<const uint64_t *>(host + at_lo);
+    for (uint32_t w = 0; cells && w < n_windows; ++w)
+        for (uint32_t a = 0; a < Gr; ++a)
+            for (uint32_t g = 0; g < Gc; ++g) {
+                const size_t c = (size_t)w * per_window + (size_t)a * Gc + g;
+                const uint64_t *t = h_cell + c * kWindowGroupCellWords;
+                uint64_t n_nan = t[0], n_links = t[1], n_summ = t[2], lo_key = t[5], hi_key = t[6];
+                __int128 S = (__int128)(((unsigned __int128)t[3] << 64) | t[4]);
+                if (wl.mode == kWinSumFull && a == g) {
+                    // the full square met every pair of the diagonal cell from both of its records
+                    if (n_nan % 2 || n_links % 2 || n_summ % 2 || S % 2)
+                        return fail(ctx, DST_ERR_STATE, "window group summary: internal error, the two sides of the square disagree");
+                    n_nan /= 2, n_links /= 2, n_summ /= 2, S /= 2;
+                } else if (wl.mode == kWinSumTriangle && a != g) {
+                    // the triangle met a pair as (group of i, group of j), i < j: either order may hold it
+                    const uint64_t *m = h_cell + ((size_t)w * per_window + (size_t)g * Gc + a) * kWindowGroupCellWords;
+                    n_nan += m[0], n_links += m[1], n_summ += m[2];
+                    S += (__int128)(((unsigned __int128)m[3] << 64) | m[4]);
+                    lo_key = std::min(lo_key, m[5]);
+                    hi_key = std::max(hi_key, m[6]);
+                }
+                dst_group_cell &out = cells[c];
+                if (n_nan + n_summ > out.pairs || n_links > out.pairs)
+                    return fail(ctx, DST_ERR_STATE, "window group summary: internal error, a cell counts more than its pairs");
+                out.nan_pairs = n_nan;
+                out.summable_pairs = n_summ;
+                out.links = n_links;
+                out.sum = summary_value(S, int_payload);
+                if (out.pairs > n_nan) {
+                    out.min_bits = payload_of_key(lo_key, int_payload);
+                    out.max_bits = payload_of_key(hi_key, int_payload);
+                }
+            }
+    for (size_t e = 0; e < rec_entries; ++e) {
+        if (rec_within)
+            rec_within[e] = (uint32_t)(h_counts[e] >> 32);
+        if (rec_summable)
+            rec_summable[e] = (uint32_t)h_counts[e];
+        if (rec_sum)
+            rec_sum[e] = summary_value((__int128)h_hi[e] * ((__int128)1 << 32) + (__int128)h_lo[e], int_payload);
     }
     return DST_OK;
 }

@@ -772,18 +772,9 @@ class Engine:
                        sum=sums[:entries].reshape(nw, n_rows))
         return out
 
-    def group_summary(self, measure, groups, n_groups=None, threshold: float = float("inf"), square: bool = True,
-                      row_slot: int = 0, col_slot: int = 1, col_groups=None, n_col_groups=None, max_pairs: int = 0,
-                      per_record: bool = False) -> dict:
-        """dst_summary's sums keyed by group (dst_group_summary).  `groups`: one integer label per row record (square: per
-        record of slot 0), -1 or 2^32-1 for a record that belongs to no group; n_groups defaults to the largest label + 1.
-        A rectangle takes col_groups / n_col_groups for the column set too.  Returns a dict of (G_r, G_c) arrays: `pairs`,
-        `nan_pairs`, `summable_pairs`, `links` (uint64), `sum` (float64, the exact fixed-point sum rounded once), `min` and
-        `max` (int64 or float64 by measure; NaN, or 0 for n / n_high, in a cell without a pair that is not NaN).  The square
-        stores both orders of a cell; cell (a, a) holds the pairs inside a.  per_record=True adds `rec_within`,
-        `rec_summable` (uint32) and `rec_sum` (float64) of shape (n_rows, G_c): dst_summary's per-record results restricted
-        to the partners in each group, for every row record, assigned or not."""
-        m = _measure_id(measure)
+    def _group_labels(self, groups, n_groups, square, row_slot, col_slot, col_groups, n_col_groups):
+        """The label arrays (uint32, -1 as DST_GROUP_NONE) and group counts of both sides, for group_summary() and
+        window_group_summary()."""
         n_rows, _ = self.set_info(0 if square else row_slot)
 
         def labels(g, n, count, side):
@@ -809,6 +800,22 @@ class Engine:
         for count in (Gr, Gc):
             if not 0 <= count <= GROUP_NONE:
                 raise ValueError("a group count must fit 32 bits")
+        return rg, Gr, cg, Gc
+
+    def group_summary(self, measure, groups, n_groups=None, threshold: float = float("inf"), square: bool = True,
+                      row_slot: int = 0, col_slot: int = 1, col_groups=None, n_col_groups=None, max_pairs: int = 0,
+                      per_record: bool = False) -> dict:
+        """dst_summary's sums keyed by group (dst_group_summary).  `groups`: one integer label per row record (square: per
+        record of slot 0), -1 or 2^32-1 for a record that belongs to no group; n_groups defaults to the largest label + 1.
+        A rectangle takes col_groups / n_col_groups for the column set too.  Returns a dict of (G_r, G_c) arrays: `pairs`,
+        `nan_pairs`, `summable_pairs`, `links` (uint64), `sum` (float64, the exact fixed-point sum rounded once), `min` and
+        `max` (int64 or float64 by measure; NaN, or 0 for n / n_high, in a cell without a pair that is not NaN).  The square
+        stores both orders of a cell; cell (a, a) holds the pairs inside a.  per_record=True adds `rec_within`,
+        `rec_summable` (uint32) and `rec_sum` (float64) of shape (n_rows, G_c): dst_summary's per-record results restricted
+        to the partners in each group, for every row record, assigned or not."""
+        m = _measure_id(measure)
+        n_rows, _ = self.set_info(0 if square else row_slot)
+        rg, Gr, cg, Gc = self._group_labels(groups, n_groups, square, row_slot, col_slot, col_groups, n_col_groups)
         cells = (GroupCell * max(Gr * Gc, 1))()
         n_rec = n_rows * Gc
         within = np.zeros(max(n_rec, 1), np.uint32) if per_record else None
@@ -829,6 +836,43 @@ class Engine:
         if per_record:
             out.update(rec_within=within[:n_rec].reshape(n_rows, Gc), rec_summable=summable[:n_rec].reshape(n_rows, Gc),
                        rec_sum=sums[:n_rec].reshape(n_rows, Gc))
+        return out
+
+    def window_group_summary(self, measure, windows, groups, n_groups=None, threshold: float = float("inf"), square: bool = True,
+                             row_slot: int = 0, col_slot: int = 1, col_groups=None, n_col_groups=None,
+                             per_record: bool = False) -> dict:
+        """group_summary()'s cells inside every column window [begin, end) of `windows` ((n_windows, 2) integers), reduced
+        next to the window sweep (dst_window_group_summary).  Labels as for group_summary(), at most WINDOW_GROUPS_MAX groups
+        of one side.  Returns group_summary()'s keys with a leading window axis: `pairs`, `nan_pairs`, `summable_pairs`,
+        `links`, `sum`, `min`, `max` of shape (n_windows, G_r, G_c), and with per_record=True `rec_within`, `rec_summable`
+        and `rec_sum` of shape (n_windows, n_rows, G_c).  Window w's entries are bitwise group_summary()'s definition
+        applied to run_windows(...)[w]."""
+        m = _measure_id(measure)
+        begin, end, nw = _window_arrays(windows)
+        n_rows, _ = self.set_info(0 if square else row_slot)
+        rg, Gr, cg, Gc = self._group_labels(groups, n_groups, square, row_slot, col_slot, col_groups, n_col_groups)
+        n_cells = nw * Gr * Gc
+        cells = (GroupCell * max(n_cells, 1))()
+        n_rec = nw * n_rows * Gc
+        within = np.zeros(max(n_rec, 1), np.uint32) if per_record else None
+        summable = np.zeros(max(n_rec, 1), np.uint32) if per_record else None
+        sums = np.zeros(max(n_rec, 1), np.float64) if per_record else None
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data
+
+        self._check(self._lib.dst_window_group_summary(self._h, m, int(square), row_slot, col_slot, begin.ctypes.data,
+                                                       end.ctypes.data, nw, rg.ctypes.data, Gr,
+                                                       None if square else cg.ctypes.data, Gc, float(threshold),
+                                                       C.addressof(cells), n_cells, ptr(within), ptr(summable), ptr(sums), n_rec))
+        raw = np.frombuffer(cells, dtype=np.uint64, count=n_cells * 7).reshape(nw, Gr, Gc, 7)
+        value = np.int64 if m in (0, 1) else np.float64
+        out = {"pairs": raw[..., 0].copy(), "nan_pairs": raw[..., 1].copy(), "summable_pairs": raw[..., 2].copy(),
+               "links": raw[..., 3].copy(), "sum": raw[..., 4].copy().view(np.float64),
+               "min": raw[..., 5].copy().view(value), "max": raw[..., 6].copy().view(value)}
+        if per_record:
+            out.update(rec_within=within[:n_rec].reshape(nw, n_rows, Gc), rec_summable=summable[:n_rec].reshape(nw, n_rows, Gc),
+                       rec_sum=sums[:n_rec].reshape(nw, n_rows, Gc))
         return out
 
     def mst(self, measure, max_pairs: int = 0, tallies: bool = False):

@@ -924,6 +924,54 @@ int dst_group_summary(dst_ctx *ctx, int measure, int square, int row_slot, int c
                       double threshold, uint64_t max_pairs,
                       dst_group_cell *cells, size_t cells_cap,
                       uint32_t *rec_within, uint32_t *rec_summable, double *rec_sum, size_t rec_cap);
+/* ---- group summaries per column window ------------------------------------------------------------ */
+/* dst_group_summary's cells and per-record tables INSIDE every column window, reduced next to the window sweep on the GPU:
+ * pi per population and d_xy between populations along the genome (the means F_ST is formed from), a query's mean distance
+ * to each group of reference sequences per window.  The state is n_windows x G_r x G_c cells, plus n_windows x n_rows x G_c
+ * entries when a per-record array is wanted, whatever the record count; the n_windows x P result of dst_run_windows is
+ * never written.  The definition is fixed to the bit and every accumulation is an integer one.
+ *   sets, windows   exactly dst_window_summary's: square != 0 is slot 0 against itself (row_slot / col_slot ignored), the
+ *            pairs i < j; else two different slots.  Windows are half-open, may overlap, repeat, be empty and come in any
+ *            order; 1 <= n_windows <= DST_WINDOWS_MAX.  tn93 takes the per-window {A,T,G,C} counts counted by code.
+ *   labels   exactly dst_group_summary's: a group below its count or DST_GROUP_NONE; in the square form row_group /
+ *            n_row_groups serve both sides and col_group / n_col_groups are ignored.  Group counts are
+ *            1 .. DST_WINDOW_GROUPS_MAX.
+ *   payload  v of a pair in window w: bitwise the DST_OUT_DISTANCE entry dst_run_windows writes for it.
+ *   result of window w: dst_group_summary's definition, word for word, applied to that window's payloads and the labels:
+ *            link, q, "summable" and NaN; `pairs` from the group sizes alone (so the same in every window); `sum` the one
+ *            conversion of the exact integer sum; min_bits / max_bits decoded from the sort key, the empty cell's quiet
+ *            NaN or 0; both orders stored in the square, cell (a, a) the pairs inside a.
+ *   cells    (n_windows x G_r x G_c entries, or NULL when a rec_* array is given) entry (w * G_r + a) * G_c + b.
+ *   rec_within, rec_summable, rec_sum   (each n_windows x n_rows x G_c entries, or NULL) entry (w * n_rows + x) * G_c + g:
+ *            window-major like every other window result, then dst_group_summary's row.
+ *   cells_cap, rec_cap   the room of cells, and of each non-NULL rec_* array, in entries.
+ * Consequences: for a set uploaded without caller base counts, the window [0, len) gives dst_group_summary's cells and
+ * per-record tables bitwise.  With one group and every record assigned, cell (0, 0) of window w is dst_window_summary's
+ * totals[w] and rec_*[w][x][0] its per-record entry, bitwise.  Within one window dst_group_summary's own consequences
+ * hold: for a != b cell (a, b) is the sum of rec_* over the records of a, and cell (a, a) is half of that sum.
+ * Errors are dst_window_summary's, in its order and with its messages, with these additions: after "unknown measure" a NaN
+ * threshold; `cells` and all three rec_* NULL; a NULL row_group, or a NULL col_group in the rectangle; a group count of 0
+ * or above DST_WINDOW_GROUPS_MAX (all DST_ERR_ARG).  Then the slots, the sets' state (a dst_upload_shared set is refused
+ * as the other window calls refuse it), len >= 2^32, a bad window, sets of 2^32-1 records or more, as they are.  Then
+ * DST_ERR_ARG for a label that is neither below its count nor DST_GROUP_NONE (dst_group_summary's message: the first such
+ * record and its side); DST_ERR_ARG when n_windows x G_r x G_c exceeds 2^31 (whether or not `cells` is given: the device
+ * keeps the cells), or n_windows x n_rows x G_c does and a per-record array is wanted; DST_ERR_CAPACITY, with nothing
+ * written, when cells_cap or rec_cap is too small (each looked at only when its array is given); DST_ERR_NOMEM with the
+ * byte count when the state (56 bytes per cell, 24 per per-record entry, 4 per label), the window table or tn93's count
+ * table does not fit.
+ * n_windows == 0, an empty row or column set, a square set of fewer than 2 records, no record of the column side (the
+ * square: of the set) assigned, or the cells alone wanted while no row record is assigned: DST_OK, zero counts and sums,
+ * min / max as for an empty cell, `pairs` still set from the group sizes, and no launch.  Synchronous on the context's
+ * stream: one fused sweep-and-reduce launch family and one copy back.  A set with deferred planes gets them first; slots,
+ * the path choice, dst_last_path, dst_last_launch and later results are untouched.  Single GPU, loaded sets only. */
+#define DST_WINDOW_GROUPS_MAX 256u   /* most groups of one side in the per-window form */
+int dst_window_group_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot,
+                             const uint64_t *win_begin, const uint64_t *win_end, uint32_t n_windows,
+                             const uint32_t *row_group, uint32_t n_row_groups,
+                             const uint32_t *col_group, uint32_t n_col_groups,
+                             double threshold,
+                             dst_group_cell *cells, size_t cells_cap,
+                             uint32_t *rec_within, uint32_t *rec_summable, double *rec_sum, size_t rec_cap);
 /* ---- minimum spanning tree --------------------------------------------------------------------- */
 /* The single-linkage picture for every threshold at once: the minimum spanning tree (forest) of one set (slot 0, n
  * records), as GrapeTree- and PHYLOViZ-style viewers draw it, computed next to the values on the GPU by Boruvka rounds
