@@ -31,6 +31,9 @@ PAIRS_AUTO, PAIRS_DIRECT, PAIRS_SWEEP = 0, 1, 2   # DST_PAIRS_*: the routes of d
 WINDOWS_MAX = 65536           # DST_WINDOWS_MAX: the most windows of one dst_run_windows call
 SUMMARY_SCALE_BITS = 37  # DST_SUMMARY_SCALE_BITS: f64 distances are summed as rint(v * 2^37)
 SUMMARY_MAX_BINS = 4096   # DST_SUMMARY_MAX_BINS
+STREAM_SUMMARY_LOADED, STREAM_SUMMARY_STREAMED = 1, 2   # DST_STREAM_SUMMARY_*: the sides of a summary stream
+STREAM_SUMMARY_ROWS = 64     # kStreamSummaryRows (csrc/dst_internal.h): the tile of a summary stream's kernel, streamed records
+STREAM_SUMMARY_COLS = 256    # kStreamSummaryCols: ... and loaded records
 GROUPS_MAX = 1024         # DST_GROUPS_MAX: the most groups of one side of dst_group_summary
 WINDOW_GROUPS_MAX = 256   # DST_WINDOW_GROUPS_MAX: the most groups of one side of dst_window_group_summary
 GROUP_NONE = 0xFFFFFFFF   # DST_GROUP_NONE: a record that belongs to no group
@@ -162,6 +165,10 @@ _SIGS = {
     "dst_sliding_windows": (C.c_int, [C.c_uint64, C.c_uint64, C.c_uint64, _vp, _vp, C.c_size_t, _u32p]),
     "dst_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_uint64, C.c_uint32, C.c_double, _vp, _vp,
                               _vp, _vp, C.c_size_t, _vp]),
+    "dst_stream_open_summary": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, C.c_uint32, C.c_double, C.c_size_t, C.c_int, C.c_int,
+                                          C.POINTER(_vp)]),
+    "dst_stream_summary_batch": (C.c_int, [_vp, C.POINTER(C.c_size_t), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "dst_stream_summary_result": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _u64p]),
     "dst_window_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_uint32, C.c_double, _vp, _vp, _vp,
                                      _vp, C.c_size_t]),
     "dst_group_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, C.c_double,

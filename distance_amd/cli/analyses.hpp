@@ -299,6 +299,18 @@ void write_pair_list(const Run &run, const PairList &pl, bool with_sites)
     out.finish();
 }
 
+// a record's "id, within, compared, mean" (without the line's end): --summary's line, and --stream-summary's
+void summary_line(LineWriter &out, const std::string &id, uint32_t within, uint32_t summable, double sum)
+{
+    out.put(id);
+    out.put('\t');
+    out.number(within);
+    out.put('\t');
+    out.number(summable);
+    out.put('\t');
+    out.distance(DST_RAW, summable ? sum / (double)summable : std::nan(""), 0);
+}
+
 // --summary: one line per record of the first input in input order, "id, within, compared, mean" from dst_summary: the
 // records within T, the partners with a summable distance, and sum / compared printed as an f64 distance (NaN: none)
 void write_summary(const Run &run, double threshold)
@@ -313,13 +325,7 @@ void write_summary(const Run &run, double threshold)
     run.header("sequence\twithin\tcompared\tmean\n");
     LineWriter out(run.wr);
     for (size_t i = 0; i < set.n; ++i) {
-        out.put(set.ids[i]);
-        out.put('\t');
-        out.number(within[i]);
-        out.put('\t');
-        out.number(summable[i]);
-        out.put('\t');
-        out.distance(DST_RAW, summable[i] ? sum[i] / (double)summable[i] : std::nan(""), 0);
+        summary_line(out, set.ids[i], within[i], summable[i], sum[i]);
         out.end_line();
     }
     out.finish();
@@ -510,6 +516,22 @@ void write_groups(const Run &run, const std::vector<GroupLabels> &labels, bool h
     out.finish();
 }
 
+// a histogram's lines behind the header: --histogram's, and --stream-histogram's
+void histogram_lines(Writer &wr, int measure, double width, const std::vector<uint64_t> &hist, uint64_t nan_pairs)
+{
+    LineWriter out(wr);
+    for (size_t b = 0; b < hist.size(); ++b) {
+        out.distance(measure, (double)b * width, (int64_t)b * (int64_t)width);
+        out.put('\t');
+        out.number(hist[b]);
+        out.end_line();
+    }
+    out.put("NaN\t");
+    out.number(nan_pairs);
+    out.end_line();
+    out.finish();
+}
+
 // --histogram: one line per bin, "lower edge, pairs" (the edge b W as the measure's distances are printed; the last bin is
 // open-ended), then "NaN, pairs without a distance"
 void write_histogram(const Run &run, double width, uint32_t bins)
@@ -520,17 +542,7 @@ void write_histogram(const Run &run, double width, uint32_t bins)
                               nullptr, nullptr, nullptr, 0, &totals),
                   "histogram");
     run.header("distance\tpairs\n");
-    LineWriter out(run.wr);
-    for (uint32_t b = 0; b < bins; ++b) {
-        out.distance(run.measure, (double)b * width, (int64_t)b * (int64_t)width);
-        out.put('\t');
-        out.number(hist[b]);
-        out.end_line();
-    }
-    out.put("NaN\t");
-    out.number(totals.nan_pairs);
-    out.end_line();
-    out.finish();
+    histogram_lines(run.wr, run.measure, width, hist, totals.nan_pairs);
 }
 
 // a DST_ERR_STATE message "... the distance of records I and J is not finite" of the NJ calls, with the pair named by

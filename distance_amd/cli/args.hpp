@@ -49,6 +49,17 @@ void print_help()
         "      --within <T>             Stream mode only: print only the pairs within distance T (a number >= 0, or inf): the "
         "lines of the full run whose distance is at most T, in the same order and with the same text. Requires --stream, one "
         "loaded file, one GPU, no other output mode\n"
+        "      --stream-summary <T>     Stream mode only: print one line per record instead of one per pair, as --summary "
+        "does: how many records of the other file lie within distance T (a number >= 0, or inf) of it, how many it was "
+        "compared with and its mean distance to those. Reduced on the GPU: no pair is sent back. Requires --stream, one "
+        "loaded file, one GPU, no other output mode\n"
+        "      --stream-summary-for <side>  Whose lines --stream-summary prints: loaded (every loaded record against the whole "
+        "stream, written when the stream ends) or streamed (every streamed record against the loaded file, in stream "
+        "order) [default: loaded]\n"
+        "      --stream-histogram <W>   Stream mode only: print the histogram of the distances between the loaded and the "
+        "streamed records, as --histogram does, bins of width W. Requires --stream, one loaded file, one GPU, no other "
+        "output mode\n"
+        "      --stream-bins <B>        Bins of --stream-histogram, 1 to 4096 [default: 256]\n"
         "      --clusters <T>           Print the single-linkage cluster of every record instead of distances: records "
         "within distance T (a number >= 0) of each other share a cluster, numbered from 1 in order of first record. One "
         "input, one GPU, no --stream or --nearest\n"
@@ -150,7 +161,8 @@ enum Flag {
     F_WITHIN, F_CLUSTERS, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS, F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX,
     F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM, F_SELFTEST, F_REPRESENTATIVES,
     F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_PAIRS, F_WINDOW_CLOSEST,
-    F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY, F_WINDOW_GROUPS, F_WINDOW_GROUPS_WITHIN, F_WINDOW_GROUPS_BY, F_COUNT
+    F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY, F_WINDOW_GROUPS, F_WINDOW_GROUPS_WITHIN, F_WINDOW_GROUPS_BY,
+    F_STREAM_SUMMARY, F_STREAM_SUMMARY_FOR, F_STREAM_HISTOGRAM, F_STREAM_BINS, F_COUNT
 };
 struct FlagDef {
     const char *shown;   // "--name <value>": its first word is the flag itself
@@ -173,11 +185,13 @@ const FlagDef kFlags[F_COUNT] = {
     {"--window-summary <T>", nullptr, true}, {"--window-summary-by <what>", nullptr, false},
     {"--window-groups <FILE>", nullptr, true}, {"--window-groups-within <T>", nullptr, true},
     {"--window-groups-by <what>", nullptr, false},
+    {"--stream-summary <T>", nullptr, true}, {"--stream-summary-for <side>", nullptr, false},
+    {"--stream-histogram <W>", nullptr, true}, {"--stream-bins <B>", nullptr, false},
 };
 
 // what the run prints, decided once by parse_args
 enum class Mode { Pairs, Stream, Closest, Within, Nearest, Clusters, MaxDistance, Summary, Histogram, Groups, Matrix, Tree, Mst,
-                  Dendrogram, Representatives, Windows, PairList, WindowClosest };
+                  Dendrogram, Representatives, Windows, PairList, WindowClosest, StreamSummary, StreamHistogram };
 
 struct Args {
     bool has[F_COUNT] = {};               // the flag was given
@@ -215,6 +229,10 @@ struct Args {
     std::string window_groups;            // --window-groups FILE
     double window_groups_within = 0;      // --window-groups-within T
     bool window_groups_by_record = false;    // --window-groups-by cell|record
+    double stream_summary = 0;            // --stream-summary T (stream mode)
+    bool stream_summary_streamed = false;    // --stream-summary-for loaded|streamed
+    double stream_histogram = 0;          // --stream-histogram W (stream mode)
+    size_t stream_bins = 256;             // --stream-bins B
     std::string selftest;
     size_t n_inputs() const { return flag_inputs.size() + pos_inputs.size(); }
     // the slab size an analysis is given: the library's own choice unless --slab-pairs was passed
@@ -300,7 +318,22 @@ std::vector<Flag> after(Flag first, std::vector<Flag> rest)
     rest.insert(rest.begin(), first);
     return rest;
 }
+// everything --stream-summary / --stream-histogram cannot go with: every other output mode and every modifier of one (each
+// other and each other's modifier: in their rows)
+const std::vector<Flag> kStreamSummaryRefuses = {
+    F_NEAREST, F_CLOSEST, F_CLOSEST_FOR, F_WITHIN, F_CLUSTERS, F_REPRESENTATIVES, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS,
+    F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM,
+    F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_PAIRS, F_WINDOW_CLOSEST, F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY,
+    F_WINDOW_GROUPS, F_WINDOW_GROUPS_WITHIN, F_WINDOW_GROUPS_BY};
 const Rule kRules[] = {
+    // (before every other row: a command line with --stream-summary, --stream-histogram or one of their modifiers is judged
+    // here first, and no other line's outcome changes)
+    {F_STREAM_SUMMARY_FOR, Mode::Pairs, kNone, {F_STREAM_SUMMARY}, "'--stream-summary <T>'", TWO_OK, false},
+    {F_STREAM_BINS, Mode::Pairs, kNone, {F_STREAM_HISTOGRAM}, "'--stream-histogram <W>'", TWO_OK, false},
+    {F_STREAM_SUMMARY, Mode::StreamSummary, after(F_STREAM_HISTOGRAM, after(F_STREAM_BINS, kStreamSummaryRefuses)), {F_STREAM},
+     "'--stream <stream>'", ONE_LOADED, true},
+    {F_STREAM_HISTOGRAM, Mode::StreamHistogram, after(F_STREAM_SUMMARY_FOR, kStreamSummaryRefuses), {F_STREAM},
+     "'--stream <stream>'", ONE_LOADED, true},
     // (before every other row: a command line with --window-groups or one of its two modifiers is judged here first, and no
     // other line's outcome changes.  Like --window-summary it leaves the mode to --windows / --regions.)
     {F_WINDOW_GROUPS_WITHIN, Mode::Pairs, kNone, {F_WINDOW_GROUPS}, "'--window-groups <FILE>'", TWO_OK, false},
@@ -437,6 +470,13 @@ Args parse_args(int argc, char **argv)
         return opt(f) && (into = parse_in_range(v, shown(f), lo, hi), true);
     };
     auto threshold = [&](Flag f, double &into) { return opt(f) && (into = parse_threshold(v, shown(f)), true); };
+    // a histogram's bin width, dst_summary's bounds: as a fixed-point value it is at least one unit (2^-37) and below 2^62
+    auto bin_width = [&](Flag f) {
+        const double w = parse_number(v, shown(f));
+        if (!(w > 0) || !(w < 0x1p25) || std::rint(std::ldexp(w, DST_SUMMARY_SCALE_BITS)) < 1)
+            die_value(v, shown(f), ": the bin width must be above 0 and below 2^25");
+        return w;
+    };
     bool only_pos = false;
     for (; k < argc; ++k) {
         arg = argv[k];
@@ -471,7 +511,8 @@ Args parse_args(int argc, char **argv)
                    threshold(F_CLUSTERS, a.clusters) || threshold(F_REPRESENTATIVES, a.representatives) || threshold(F_MAX_DISTANCE, a.max_distance) ||
                    threshold(F_WITHIN, a.within) || threshold(F_SUMMARY, a.summary) ||
                    threshold(F_GROUPS_WITHIN, a.groups_within) || threshold(F_WINDOW_GROUPS_WITHIN, a.window_groups_within) ||
-                   threshold(F_WINDOW_SUMMARY, a.window_summary)) {
+                   threshold(F_WINDOW_SUMMARY, a.window_summary) || threshold(F_STREAM_SUMMARY, a.stream_summary) ||
+                   count(F_STREAM_BINS, a.stream_bins, 1, DST_SUMMARY_MAX_BINS)) {
             // a word, a count in a range or a threshold: stored
         } else if (opt(F_GPUS)) {
             a.gpus = (int)parse_usize(v, shown(F_GPUS));
@@ -491,10 +532,11 @@ Args parse_args(int argc, char **argv)
         } else if (opt(F_WINDOW_GROUPS_BY)) {
             a.window_groups_by_record = parse_choice(v, shown(F_WINDOW_GROUPS_BY), {{"cell", 0}, {"record", 1}}) != 0;
         } else if (opt(F_HISTOGRAM)) {
-            a.histogram = parse_number(v, shown(F_HISTOGRAM));
-            // dst_summary's bounds: the width as a fixed-point value is at least one unit (2^-37) and below 2^62
-            if (!(a.histogram > 0) || !(a.histogram < 0x1p25) || std::rint(std::ldexp(a.histogram, DST_SUMMARY_SCALE_BITS)) < 1)
-                die_value(v, shown(F_HISTOGRAM), ": the bin width must be above 0 and below 2^25");
+            a.histogram = bin_width(F_HISTOGRAM);
+        } else if (opt(F_STREAM_HISTOGRAM)) {
+            a.stream_histogram = bin_width(F_STREAM_HISTOGRAM);
+        } else if (opt(F_STREAM_SUMMARY_FOR)) {
+            a.stream_summary_streamed = parse_choice(v, shown(F_STREAM_SUMMARY_FOR), {{"loaded", 0}, {"streamed", 1}}) != 0;
         } else if (opt(F_MATRIX)) {
             a.matrix = parse_choice(v, shown(F_MATRIX), {{"tsv", DST_MATRIX_TSV}, {"phylip", DST_MATRIX_PHYLIP}});
         } else if (opt(F_TREE)) {
@@ -519,6 +561,9 @@ Args parse_args(int argc, char **argv)
         die_value(a.measure, shown(F_MEASURE), "\n  [possible values: n, n_high, raw, jc69, k80, tn93]");
     if (a.has[F_HISTOGRAM] && dst_measure_from_name(a.measure.c_str()) <= DST_N_HIGH && a.histogram != std::floor(a.histogram))
         die_usage("invalid value for '--histogram <W>': the bin width must be an integer with '--measure " + a.measure + "'");
+    if (a.has[F_STREAM_HISTOGRAM] && dst_measure_from_name(a.measure.c_str()) <= DST_N_HIGH &&
+        a.stream_histogram != std::floor(a.stream_histogram))
+        die_usage("invalid value for '--stream-histogram <W>': the bin width must be an integer with '--measure " + a.measure + "'");
     return a;
 }
 

@@ -286,6 +286,8 @@ int main(int argc, char **argv)
     case Mode::Stream:
     case Mode::Closest:
     case Mode::WindowClosest:
+    case Mode::StreamSummary:
+    case Mode::StreamHistogram:
     case Mode::Within: StreamRun(a, gpus, loaded[0], counts[0], job, stream_fh, table, parse_threads, wr, &windows).run(); break;
     }
     timer.mark("compute + format + write");

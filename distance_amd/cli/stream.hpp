@@ -48,6 +48,8 @@ struct StreamRun {
     const WindowList *const windows;
     const bool window_closest;
     const bool keep_ids;                   // the final lines name streamed records: their ids stay, in one arena
+    // --stream-summary / --stream-histogram: the sums stay on the GPU; only --stream-summary-for streamed has lines per batch
+    const bool summary, summary_streamed;
 
     std::mutex qmu;                        // reader -> dispatcher -> per-GPU input queues
     std::condition_variable qcv;
@@ -78,7 +80,9 @@ struct StreamRun {
           nibbles(!(std::getenv("DISTANCE_WIRE") && std::strcmp(std::getenv("DISTANCE_WIRE"), "codes") == 0)),
           closest_loaded(args.mode == Mode::Closest && args.closest_side == DST_CLOSEST_FOR_LOADED), windows(wl),
           window_closest(args.mode == Mode::WindowClosest),
-          keep_ids(closest_loaded || window_closest), gq(G), gdone(G, false),
+          keep_ids(closest_loaded || window_closest),
+          summary(args.mode == Mode::StreamSummary || args.mode == Mode::StreamHistogram),
+          summary_streamed(args.mode == Mode::StreamSummary && args.stream_summary_streamed), gq(G), gdone(G, false),
           window(G * (kDepth + 2)), streams(G, nullptr)
     {
     }
@@ -249,6 +253,26 @@ struct StreamRun {
         return text;
     }
 
+    // --stream-summary-for streamed: the batch's records in stream order, each with --summary's line against the loaded set
+    // (--stream-summary-for loaded and --stream-histogram: nothing per batch, the lines follow the stream's end)
+    std::vector<TextBuf> collect_summary(size_t g, const Item &it)
+    {
+        std::vector<TextBuf> text;
+        if (!summary_streamed)
+            return text;
+        size_t n_rec = 0;
+        const uint32_t *within = nullptr, *summable = nullptr;
+        const double *sum = nullptr;
+        gpus[g].check(dst_stream_summary_batch(streams[g], &n_rec, &within, &summable, &sum), "stream summary batch");
+        LineWriter out(wr);
+        for (size_t r = 0; r < n_rec; ++r) {
+            summary_line(out, it.batch->ids[r], within[r], summable[r], sum[r]);
+            out.put('\n');   // (not end_line: the text goes to the ordered writer, not out now)
+        }
+        text.push_back(std::move(out.buf));
+        return text;
+    }
+
     void collect_one(size_t g, std::deque<Item> &inflight)
     {
         size_t n_rec = 0;
@@ -258,6 +282,7 @@ struct StreamRun {
         inflight.pop_front();
         hand_over(it.idx, a.mode == Mode::Within          ? collect_within(g, it)
                           : a.mode == Mode::Closest       ? collect_closest(g, it, n_rec)
+                          : summary                       ? collect_summary(g, it)
                           : a.mode == Mode::WindowClosest ? std::vector<TextBuf>()   // (the lines follow the stream's end)
                                                           : collect_matrix(it, res));
     }
@@ -303,6 +328,8 @@ struct StreamRun {
                     kept_counts.insert(kept_counts.end(), al.counts.begin(), al.counts.end());
                 it.batch.reset();
             }
+            if (summary && !summary_streamed)
+                it.batch.reset();   // no line names a streamed record: host memory does not grow with the stream
             inflight.push_back(std::move(it));
         }
         while (!inflight.empty())
@@ -398,12 +425,50 @@ struct StreamRun {
         out.finish();
     }
 
+    // --stream-summary (loaded): every loaded record in input order with --summary's line against the whole stream
+    void write_summary_loaded()
+    {
+        const size_t cap = std::max<size_t>(ref.n, 1);
+        std::vector<uint32_t> within(cap), summable(cap);
+        std::vector<double> sum(cap);
+        gpus[0].check(dst_stream_summary_result(streams[0], nullptr, within.data(), summable.data(), sum.data(), ref.n, nullptr,
+                                                nullptr),
+                      "stream summary result");
+        LineWriter out(wr);
+        for (size_t i = 0; i < ref.n; ++i) {
+            summary_line(out, ref.ids[i], within[i], summable[i], sum[i]);
+            out.end_line();
+        }
+        out.finish();
+    }
+
+    // --stream-histogram: --histogram's lines over every loaded x streamed pair
+    void write_stream_histogram()
+    {
+        std::vector<uint64_t> hist(a.stream_bins);
+        dst_summary_totals totals;
+        gpus[0].check(dst_stream_summary_result(streams[0], hist.data(), nullptr, nullptr, nullptr, 0, &totals, nullptr),
+                      "stream summary result");
+        histogram_lines(wr, measure, a.stream_histogram, hist, totals.nan_pairs);
+    }
+
     void run()
     {
+        if (summary) {
+            const char *header = a.mode == Mode::StreamSummary ? "sequence\twithin\tcompared\tmean\n" : "distance\tpairs\n";
+            wr.write(header, std::strlen(header));
+        }
         std::thread reader([this] { read(); });
         const int wire = nibbles ? DST_WIRE_NIBBLES : DST_WIRE_CODES;
         for (size_t g = 0; g < G; ++g)
-            gpus[g].check(a.mode == Mode::Closest
+            gpus[g].check(a.mode == Mode::StreamSummary
+                              ? dst_stream_open_summary(gpus[g].h, measure, a.stream_summary,
+                                                        summary_streamed ? DST_STREAM_SUMMARY_STREAMED : DST_STREAM_SUMMARY_LOADED, 0,
+                                                        0.0, batch_records, kDepth, wire, &streams[g])
+                          : a.mode == Mode::StreamHistogram
+                              ? dst_stream_open_summary(gpus[g].h, measure, 0.0, 0, (uint32_t)a.stream_bins, a.stream_histogram,
+                                                        batch_records, kDepth, wire, &streams[g])
+                          : a.mode == Mode::Closest
                               ? dst_stream_open_closest(gpus[g].h, measure, (uint32_t)a.closest, a.closest_side, batch_records,
                                                         kDepth, wire, &streams[g])
                           : window_closest
@@ -427,6 +492,10 @@ struct StreamRun {
             write_closest_loaded();
         if (a.mode == Mode::WindowClosest)
             write_window_closest();
+        if (a.mode == Mode::StreamSummary && !summary_streamed)
+            write_summary_loaded();
+        if (a.mode == Mode::StreamHistogram)
+            write_stream_histogram();
         for (size_t g = 0; g < G; ++g)
             dst_stream_close(streams[g]);
         reader.join();

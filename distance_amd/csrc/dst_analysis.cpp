@@ -99,6 +99,20 @@ double dst::summary_value(__int128 s, bool int_payload)
     return int_payload ? d : std::ldexp(d, -DST_SUMMARY_SCALE_BITS);
 }
 
+// dst_summary's rules for a histogram's bin width, and the width as a fixed-point value (a summary stream shares them)
+int dst::summary_width_q(dst_ctx *ctx, int measure, double width, uint64_t &width_q)
+{
+    const bool int_payload = measure_is_int(measure);
+    if (!(width > 0 && width < 0x1p25))   // (NaN fails both)
+        return fail(ctx, DST_ERR_ARG, "width must be finite, above 0 and below 2^25");
+    if (int_payload && width != std::floor(width))
+        return fail(ctx, DST_ERR_ARG, "width must be an integer for n and n_high");
+    width_q = int_payload ? (uint64_t)width : (uint64_t)std::llrint(std::ldexp(width, DST_SUMMARY_SCALE_BITS));
+    if (width_q < 1)
+        return fail(ctx, DST_ERR_ARG, "width is below one unit of the fixed-point scale");
+    return DST_OK;
+}
+
 // The threshold of dst_clusters / dst_links / a links stream as a payload: int64 payloads link when v <= floor(T) (clamped
 // to the int64 range), f64 payloads on their bits through nn_key.  false: floor(T) is below -2^63, nothing links.
 bool dst::threshold_payload(int measure, double threshold, uint64_t &t_bits)
@@ -1034,13 +1048,8 @@ int dst_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slo
             return fail(ctx, DST_ERR_ARG, "bins must be between 0 and 4096");
         if (!hist)
             return fail(ctx, DST_ERR_ARG, "null hist pointer");
-        if (!(width > 0 && width < 0x1p25))   // (NaN fails both)
-            return fail(ctx, DST_ERR_ARG, "width must be finite, above 0 and below 2^25");
-        if (int_payload && width != std::floor(width))
-            return fail(ctx, DST_ERR_ARG, "width must be an integer for n and n_high");
-        width_q = int_payload ? (uint64_t)width : (uint64_t)std::llrint(std::ldexp(width, DST_SUMMARY_SCALE_BITS));
-        if (width_q < 1)
-            return fail(ctx, DST_ERR_ARG, "width is below one unit of the fixed-point scale");
+        if (int rc = summary_width_q(ctx, measure, width, width_q))
+            return rc;
     }
     TwoSets ts;
     if (int rc = two_sets(ctx, square != 0, row_slot, col_slot, ts, true, true))

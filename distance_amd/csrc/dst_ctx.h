@@ -209,5 +209,7 @@ SlabPlan plan_slabs(bool square, uint64_t n_rows, uint64_t n_cols, uint64_t max_
 bool threshold_payload(int measure, double threshold, uint64_t &t_bits);
 // dst_summary's one conversion of an exact integer sum to double (dst_analysis.cpp; dst_window_summary shares it)
 double summary_value(__int128 s, bool int_payload);
+// dst_summary's checks of a bin width (its messages), and width_q: the width as a fixed-point value (dst_analysis.cpp)
+int summary_width_q(dst_ctx *ctx, int measure, double width, uint64_t &width_q);
 
 }  // namespace dst

@@ -553,6 +553,16 @@ hipError_t launch_summary_cols(int measure, const uint64_t *slab, uint64_t out_b
 // aggregate: lanes of a wave that share a bin add once (false: the measurement's other side)
 hipError_t launch_summary_hist(int measure, const uint64_t *slab, uint64_t pairs, uint32_t bins, uint64_t width_q,
                                uint64_t t_bits, bool any, bool aggregate, const SummaryBuffers &b, hipStream_t stream);
+// A summary stream's batch (dst_stream.cpp): one tile pass over the batch's n_records x n_loaded matrix of
+// DST_OUT_DISTANCE payloads, entry s n_loaded + i, every entry read once for both sides.  A workgroup takes a tile of
+// kStreamSummaryRows rows x kStreamSummaryCols columns, a thread one column.  loaded / streamed: the per-record state of
+// either side (within, summable, hi, lo; NULL: the side is not wanted and its code is not compiled in); tot: the first
+// five words of a SummaryBuffers::tot.  Adds only: the state is zeroed by the caller.
+constexpr uint32_t kStreamSummaryRows = 64;    // mirrored as STREAM_SUMMARY_ROWS in distance_amd/_lib.py
+constexpr uint32_t kStreamSummaryCols = 256;   // ... and STREAM_SUMMARY_COLS
+hipError_t launch_summary_stream(int measure, const uint64_t *matrix, uint64_t n_records, uint64_t n_loaded, uint64_t t_bits,
+                                 bool any, const SummaryBuffers *loaded, const SummaryBuffers *streamed, uint64_t *tot,
+                                 hipStream_t stream);
 
 // ---- group summaries (dst_group_summary.hip, driven by dst_group_summary in dst_analysis.cpp) --------------------------
 // dst_summary's per-pair quantities keyed by group.  Per row slab a row pass (the per-record table's entry (row, group of

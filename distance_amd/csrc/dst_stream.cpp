@@ -33,7 +33,15 @@
 // per-window base counts (tn93), then per (rows x windows) range the window sweep of loaded x batch as DST_OUT_TALLY words
 // into the stream's one scratch and window_nearest_stream_kernel's merge into the lists.  The window table, the count
 // tables, the scratch and the lists are the stream's own, so no other call on the context can disturb them.
+//
+// A summary stream (dst_stream_open_summary) is the fifth: dst_summary's counts and exact sums of the
+// batch's DST_OUT_DISTANCE matrix, which stays in the slot's d_out.  Behind the pair kernel, on the compute stream, one
+// tile pass (summary_stream_kernel) reads every entry once for both sides: the loaded records' words and the totals are
+// the stream's own kept state, zeroed at open; the batch's records' words are the slot's, zeroed in front of the kernel,
+// copied to the slot's page-locked block on the copy-out stream and converted at collect.  With bins, dst_summary's
+// histogram pass follows into the kept histogram, with totals of its own that the result compares with the tile pass'.
 #include <algorithm>
+#include <cstring>
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -99,10 +107,18 @@ struct dst_stream {
     Grown<uint32_t> wc_scratch;       // one range's tallies: wc_cut.rows x wc_cut.wins x max_records entries
     WindowSlabs wc_cut{};
     uint32_t *wc_cnt = nullptr;
+    // summary streams (what, t_bits, any_links as a links stream's; submitted: the records so far).  The kept state in
+    // d_lists: the loaded records' four words (LOADED), the histogram, the tile kernel's totals and the histogram pass'
+    uint32_t bins = 0;
+    uint64_t width_q = 0;
+    size_t sum_state_bytes = 0;
+    SummaryBuffers sum_kept{};        // within / summable / hi / lo: NULL without LOADED; hist; tot: the tile kernel's
+    SummaryBuffers sum_hist{};        // hist: sum_kept's; tot: the histogram pass' own
 };
 
 constexpr int kLinksStream = 2;       // dst_stream::closest of a links stream (after the two dst_closest_side values)
 constexpr int kWindowClosestStream = 3;   // ... and of a window-closest stream
+constexpr int kSummaryStream = 4;     // ... and of a summary stream
 
 namespace {
 
@@ -135,6 +151,32 @@ size_t window_layout(void *base, uint64_t window, bool values, int W, LinksBuffe
     b.val = reinterpret_cast<uint64_t *>(take(values ? window * 8 : 0));
     b.tal = reinterpret_cast<uint32_t *>(take(window * 4 * (size_t)W));
     return used;   // (the size alone with base == NULL)
+}
+
+// a summary stream's four words of `records` records in one block of 24 bytes per record: hi, lo, within, summable
+size_t records_layout(void *base, uint64_t records, SummaryBuffers &b)
+{
+    if (base) {
+        char *p = static_cast<char *>(base);
+        b.hi = reinterpret_cast<int64_t *>(p);
+        b.lo = reinterpret_cast<uint64_t *>(p + records * 8);
+        b.within = reinterpret_cast<uint32_t *>(p + records * 16);
+        b.summable = reinterpret_cast<uint32_t *>(p + records * 20);
+    }
+    return (size_t)(records * 24);   // (the size alone with base == NULL)
+}
+
+// ... and its kept state: the loaded records' words (LOADED), the histogram, the tile kernel's totals, the histogram pass'
+size_t summary_state_layout(void *base, uint64_t n_loaded, bool loaded, uint32_t bins, SummaryBuffers &kept, SummaryBuffers &hist)
+{
+    const size_t records = loaded ? records_layout(base, n_loaded, kept) : 0;   // (a multiple of 8 bytes)
+    if (base) {
+        uint64_t *p = reinterpret_cast<uint64_t *>(static_cast<char *>(base) + records);
+        kept.hist = hist.hist = p;
+        kept.tot = p + bins;
+        hist.tot = p + bins + kSummaryTotals;
+    }
+    return records + ((size_t)bins + 2 * kSummaryTotals) * 8;
 }
 
 void destroy(dst_stream *s)
@@ -270,6 +312,61 @@ int dst_stream_open_links(dst_ctx *ctx, int measure, double threshold, int what,
     if (rc || e != hipSuccess) {
         destroy(s);
         return rc ? rc : fail_hip(ctx, e, "dst_stream_open_links");
+    }
+    *out = s;
+    return DST_OK;
+}
+
+int dst_stream_open_summary(dst_ctx *ctx, int measure, double threshold, int what, uint32_t bins, double width,
+                            size_t max_records, int depth, int wire, dst_stream **out)
+{
+    if (!ctx || !out)
+        return DST_ERR_ARG;
+    *out = nullptr;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (wire != DST_WIRE_CODES && wire != DST_WIRE_NIBBLES)
+        return fail(ctx, DST_ERR_ARG, "unknown wire format");
+    if (std::isnan(threshold))
+        return fail(ctx, DST_ERR_ARG, "threshold is NaN");
+    if (what & ~(DST_STREAM_SUMMARY_LOADED | DST_STREAM_SUMMARY_STREAMED))
+        return fail(ctx, DST_ERR_ARG, "unknown bits in what");
+    uint64_t width_q = 0;
+    if (bins) {
+        if (bins > DST_SUMMARY_MAX_BINS)
+            return fail(ctx, DST_ERR_ARG, "bins must be between 0 and 4096");
+        if (int rc = summary_width_q(ctx, measure, width, width_q))
+            return rc;
+    }
+    dst_stream *s = nullptr;
+    int rc = open_stream(ctx, measure, DST_OUT_DISTANCE, max_records, depth, wire, kSummaryStream, 0, &s);
+    if (rc)
+        return rc;
+    s->what = what;
+    s->bins = bins;
+    s->width_q = width_q;
+    s->any_links = threshold_payload(measure, threshold, s->t_bits);
+    const bool loaded = (what & DST_STREAM_SUMMARY_LOADED) != 0, streamed = (what & DST_STREAM_SUMMARY_STREAMED) != 0;
+    const char *const name = "summary stream";
+    // the kept state, zeroed once; per slot the batch's records' words, device and page-locked
+    s->sum_state_bytes = summary_state_layout(nullptr, s->n_loaded, loaded, bins, s->sum_kept, s->sum_hist);
+    rc = s->d_lists.grow(ctx, s->sum_state_bytes, name);
+    SummaryBuffers none{};
+    const size_t batch_bytes = records_layout(nullptr, max_records, none);
+    for (auto &sl : s->slots) {
+        if (!rc && streamed)
+            rc = sl.d_lists.grow(ctx, batch_bytes, name);
+        if (!rc && streamed)
+            rc = sl.h_lists.grow(ctx, batch_bytes, name);
+    }
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        summary_state_layout(s->d_lists, s->n_loaded, loaded, bins, s->sum_kept, s->sum_hist);
+        e = hipMemsetAsync(s->d_lists, 0, s->sum_state_bytes, s->s_compute);
+    }
+    if (rc || e != hipSuccess) {
+        destroy(s);
+        return rc ? rc : fail_hip(ctx, e, "dst_stream_open_summary");
     }
     *out = s;
     return DST_OK;
@@ -540,8 +637,13 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
     DeviceSet &loaded = ctx->set[0];
     if (!loaded.loaded || loaded.len != s->len || (s->closest >= 0 && loaded.n != s->n_loaded))
         return fail(ctx, DST_ERR_STATE, "the loaded set changed while the stream was open");
+    const bool summary = s->closest == kSummaryStream;
+    if (s->poisoned && summary)
+        return fail(ctx, DST_ERR_STATE, "a batch of this summary stream held an invalid code: its sums are not trustworthy");
     if (s->poisoned)
         return fail(ctx, DST_ERR_STATE, "a batch of this closest stream held an invalid code: its lists are not trustworthy");
+    if (summary && s->submitted + (uint64_t)n_records > 0xFFFFFFFEull)   // (64-bit: the counters are uint32, the hi / lo split
+        return fail(ctx, DST_ERR_CAPACITY, "a summary stream ends at 2^32-2 records");   //  needs fewer than 2^32 partners)
     const bool windowed = s->closest == kWindowClosestStream;
     if ((s->closest == DST_CLOSEST_FOR_LOADED || windowed) && s->next_ordinal + n_records - 1 > 0xFFFFFFFEull)
         return fail(ctx, DST_ERR_CAPACITY, "streamed ordinals end at 2^32-2");
@@ -604,6 +706,21 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
         sl.window_first = 0;
         s->last_collected = -1;   // the collected batch's links were valid until this submit
     }
+    // a summary stream: the tile pass for both sides and the totals, then the histogram pass, behind the pair kernel
+    const bool sum_streamed = summary && (s->what & DST_STREAM_SUMMARY_STREAMED);
+    if (summary) {
+        const uint64_t *matrix = static_cast<const uint64_t *>(sl.d_out.ptr);
+        SummaryBuffers batch{};
+        if (sum_streamed)
+            HIP_TRY(ctx, hipMemsetAsync(sl.d_lists, 0, records_layout(sl.d_lists, n_records, batch), s->s_compute));
+        HIP_TRY(ctx, launch_summary_stream(s->measure, matrix, n_records, s->n_loaded, s->t_bits, s->any_links,
+                                           (s->what & DST_STREAM_SUMMARY_LOADED) ? &s->sum_kept : nullptr,
+                                           sum_streamed ? &batch : nullptr, s->sum_kept.tot, s->s_compute));
+        if (s->bins)
+            HIP_TRY(ctx, launch_summary_hist(s->measure, matrix, (uint64_t)n_records * s->n_loaded, s->bins, s->width_q, s->t_bits,
+                                             s->any_links, true, s->sum_hist, s->s_compute));
+        s->last_collected = -1;   // the collected batch's results were valid until this submit
+    }
     HIP_TRY(ctx, sl.computed.record(s->s_compute));
     // copy-out
     HIP_TRY(ctx, hipStreamWaitEvent(s->s_out, sl.computed, 0));
@@ -619,12 +736,17 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
         HIP_TRY(ctx, hipMemcpyAsync(sl.h_nl.idx, sl.nl.idx, e * 4, hipMemcpyDeviceToHost, s->s_out));
         HIP_TRY(ctx, hipMemcpyAsync(sl.h_nl.val, sl.nl.val, e * 8, hipMemcpyDeviceToHost, s->s_out));
         HIP_TRY(ctx, hipMemcpyAsync(sl.h_nl.tal, sl.nl.tal, e * 4 * (size_t)s->W, hipMemcpyDeviceToHost, s->s_out));
+    } else if (sum_streamed) {
+        SummaryBuffers none{};
+        HIP_TRY(ctx, hipMemcpyAsync(sl.h_lists, sl.d_lists, records_layout(nullptr, n_records, none), hipMemcpyDeviceToHost, s->s_out));
     }
     HIP_TRY(ctx, sl.landed.record(s->s_out));
     if (s->closest == DST_CLOSEST_FOR_LOADED || windowed) {
         s->next_ordinal += n_records;
         s->submitted += n_records;
     }
+    if (summary)
+        s->submitted += n_records;
     sl.n = n_records;
     sl.state = 2;
     s->acquired = -1;
@@ -667,8 +789,113 @@ int dst_stream_collect(dst_stream *s, size_t *n_records, const void **results)
                 return rc;
         }
     }
+    if (s->closest == kSummaryStream && (s->what & DST_STREAM_SUMMARY_STREAMED)) {
+        // the batch's records: the 128-bit sums here, each converted once into the place of its high word
+        SummaryBuffers h{};
+        records_layout(sl.h_lists, sl.n, h);
+        const bool int_payload = s->measure == DST_N || s->measure == DST_N_HIGH;
+        for (size_t x = 0; x < sl.n; ++x) {
+            const double v = summary_value((__int128)h.hi[x] * ((__int128)1 << 32) + (__int128)h.lo[x], int_payload);
+            std::memcpy(h.hi + x, &v, 8);
+        }
+    }
     *n_records = sl.n;
     *results = sl.h_out;   // (NULL for a closest stream: its results never leave the device as a matrix)
+    return DST_OK;
+}
+
+int dst_stream_summary_batch(dst_stream *s, size_t *n_records, const uint32_t **within, const uint32_t **summable,
+                             const double **sum)
+{
+    if (!s)
+        return DST_ERR_ARG;
+    dst_ctx *ctx = s->ctx;
+    if (s->closest != kSummaryStream)
+        return fail(ctx, DST_ERR_ARG, "not a summary stream");
+    if (!(s->what & DST_STREAM_SUMMARY_STREAMED))
+        return fail(ctx, DST_ERR_ARG, "the stream was opened without DST_STREAM_SUMMARY_STREAMED");
+    if (!n_records)
+        return fail(ctx, DST_ERR_ARG, "null n_records pointer");
+    *n_records = 0;
+    if (s->poisoned)
+        return fail(ctx, DST_ERR_STATE, "a batch of this summary stream held an invalid code: its sums are not trustworthy");
+    if (s->last_collected < 0 || s->slots[(size_t)s->last_collected].state != 3)
+        return fail(ctx, DST_ERR_STATE, "no collected batch: its results are valid from dst_stream_collect to the next submit");
+    const auto &sl = s->slots[(size_t)s->last_collected];
+    SummaryBuffers h{};
+    records_layout(sl.h_lists, sl.n, h);
+    *n_records = sl.n;
+    if (within)
+        *within = h.within;
+    if (summable)
+        *summable = h.summable;
+    if (sum)
+        *sum = reinterpret_cast<const double *>(h.hi);   // (converted at collect)
+    return DST_OK;
+}
+
+int dst_stream_summary_result(dst_stream *s, uint64_t *hist, uint32_t *within, uint32_t *summable, double *sum, size_t cap,
+                              dst_summary_totals *totals, uint64_t *records)
+{
+    if (!s)
+        return DST_ERR_ARG;
+    dst_ctx *ctx = s->ctx;
+    if (totals)
+        *totals = dst_summary_totals{0, 0, 0, 0, 0.0};
+    if (records)
+        *records = 0;
+    if (s->closest != kSummaryStream)
+        return fail(ctx, DST_ERR_ARG, "not a summary stream");
+    const bool loaded = (s->what & DST_STREAM_SUMMARY_LOADED) != 0;
+    if (!loaded && (within || summable || sum))
+        return fail(ctx, DST_ERR_ARG, "the stream was opened without DST_STREAM_SUMMARY_LOADED: the per-record pointers must be NULL");
+    if (s->poisoned)
+        return fail(ctx, DST_ERR_STATE, "a batch of this summary stream held an invalid code: its sums are not trustworthy");
+    if (s->in_flight != 0)
+        return fail(ctx, DST_ERR_STATE, "collect every submitted batch before reading the summary");
+    const size_t n = s->n_loaded;
+    if ((within || summable || sum) && cap < n)
+        return fail(ctx, DST_ERR_CAPACITY, "cap is below the loaded set's record count");
+    // every batch is collected, so the compute stream is idle: the kept state back in one copy, the 128-bit sums here
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    std::vector<char> host(s->sum_state_bytes);
+    HIP_TRY(ctx, hipMemcpyAsync(host.data(), s->d_lists, s->sum_state_bytes, hipMemcpyDeviceToHost, s->s_compute));
+    HIP_TRY(ctx, hipStreamSynchronize(s->s_compute));
+    SummaryBuffers h{}, hh{};
+    summary_state_layout(host.data(), n, loaded, s->bins, h, hh);
+    const bool int_payload = s->measure == DST_N || s->measure == DST_N_HIGH;
+    dst_summary_totals t{s->submitted * (uint64_t)n, h.tot[0], h.tot[1], h.tot[2], 0.0};
+    const __int128 all = (__int128)(((unsigned __int128)h.tot[3] << 64) | h.tot[4]);
+    // no total is counted twice: the histogram pass' own totals, and the loaded records' entries, only have to agree
+    if (s->bins && (hh.tot[0] != h.tot[0] || hh.tot[1] != h.tot[1] || hh.tot[2] != h.tot[2] || hh.tot[3] != h.tot[3] ||
+                    hh.tot[4] != h.tot[4]))
+        return fail(ctx, DST_ERR_STATE, "summary stream: internal error, the passes disagree");
+    if (loaded) {
+        uint64_t w2 = 0, s2 = 0;
+        __int128 all2 = 0;
+        for (size_t x = 0; x < n; ++x) {
+            const __int128 S = (__int128)h.hi[x] * ((__int128)1 << 32) + (__int128)h.lo[x];
+            if (within)
+                within[x] = h.within[x];
+            if (summable)
+                summable[x] = h.summable[x];
+            if (sum)
+                sum[x] = summary_value(S, int_payload);
+            w2 += h.within[x];
+            s2 += h.summable[x];
+            all2 += S;
+        }
+        if (w2 != t.links || s2 != t.summable_pairs || all2 != all)
+            return fail(ctx, DST_ERR_STATE, "summary stream: internal error, the loaded records and the totals disagree");
+    }
+    if (hist)
+        for (uint32_t b = 0; b < s->bins; ++b)
+            hist[b] = h.hist[b];
+    t.sum = summary_value(all, int_payload);
+    if (totals)
+        *totals = t;
+    if (records)
+        *records = s->submitted;
     return DST_OK;
 }
 

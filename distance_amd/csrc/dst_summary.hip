@@ -25,6 +25,11 @@
 //                         data puts nearly every pair of a wave into one or two bins.  The kernel also counts the call's
 //                         totals (NaN, summable, links, the sum as a 128-bit integer in two words), so a call that wants
 //                         no per-record result reads the slab once.
+//   summary_stream_kernel a summary stream's batch (dst_stream.cpp): a tile pass over the batch's n_records x
+//                         n_loaded matrix that reads every entry once for both sides: thread = column (loaded record) with
+//                         register accumulators and one set of atomics per tile, the tile's rows (streamed records) reduced
+//                         over the wave eight at a time and over the waves through LDS, the totals from the column
+//                         accumulators.  The two sides are template parameters.
 #include "dst_device.hpp"
 #include "dst_pair_sum.hpp"
 
@@ -276,6 +281,169 @@ __global__ __launch_bounds__(256) void summary_hist_kernel(const uint64_t *__res
     }
 }
 
+// A workgroup's share of the totals, tot[0 .. 4] as summary_hist_kernel's: its NaN pairs, and the sums of fewer than 2^32
+// entries.  The exact sum hi 2^32 + lo goes in as a 128-bit integer in two words, the carry of the low word's add taken
+// from the value the atomic returns (summary_hist_kernel explains why every carry is added once).
+__device__ __forceinline__ void add_to_totals(unsigned long long *tot, unsigned long long nans, const Acc &total)
+{
+    if (nans)
+        __hip_atomic_fetch_add(tot + 0, nans, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (total.summable)
+        __hip_atomic_fetch_add(tot + 1, (unsigned long long)total.summable, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (total.within)
+        __hip_atomic_fetch_add(tot + 2, (unsigned long long)total.within, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long shifted = (unsigned long long)total.hi << 32, low = shifted + total.lo;
+    long long high = (total.hi >> 32) + (low < shifted ? 1 : 0);
+    if (low) {
+        const unsigned long long old = __hip_atomic_fetch_add(tot + 4, low, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        high += old + low < old ? 1 : 0;
+    }
+    if (high)
+        __hip_atomic_fetch_add(tot + 3, (unsigned long long)high, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+constexpr int kStreamSumUnroll = 8;   // rows whose loads a thread has in flight at once
+
+__device__ __forceinline__ unsigned long long shfl_xor64(unsigned long long x, int mask)
+{
+    const uint32_t lo = (uint32_t)__shfl_xor((int)(uint32_t)x, mask, 64), hi = (uint32_t)__shfl_xor((int)(uint32_t)(x >> 32), mask, 64);
+    return (unsigned long long)hi << 32 | lo;
+}
+
+// The wave's sums of eight rows at once, v[u] this lane's entry of row u.  Three exchanges halve the rows a lane holds: with
+// the partner across lane bit 5 (then 4, then 3) a lane keeps the rows of its own half, sends the others and adds what it
+// receives.  One row is left, row 4 b5 + 2 b4 + b3 of the lane's bits, and three plain steps across bits 2, 1, 0 finish it:
+// ten 64-bit exchanges for the eight rows, where eight separate reductions take 48.  Lane sum_rows_lane(u) (and the seven
+// lanes behind it) returns row u's sum; two's complement, so the signed word adds like the unsigned one.
+__device__ __forceinline__ constexpr int sum_rows_lane(int u) { return ((u >> 2) & 1) * 32 + ((u >> 1) & 1) * 16 + (u & 1) * 8; }
+
+__device__ __forceinline__ unsigned long long wave_sum_rows(const unsigned long long (&v)[kStreamSumUnroll], int lane)
+{
+    static_assert(kStreamSumUnroll == 8, "three halving steps");
+    const bool b5 = (lane & 32) != 0, b4 = (lane & 16) != 0, b3 = (lane & 8) != 0;
+    unsigned long long w[4], x[2];
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+        w[k] = (b5 ? v[k + 4] : v[k]) + shfl_xor64(b5 ? v[k] : v[k + 4], 32);
+#pragma unroll
+    for (int k = 0; k < 2; ++k)
+        x[k] = (b4 ? w[k + 2] : w[k]) + shfl_xor64(b4 ? w[k] : w[k + 2], 16);
+    unsigned long long y = (b3 ? x[1] : x[0]) + shfl_xor64(b3 ? x[0] : x[1], 8);
+    y += shfl_xor64(y, 4);
+    y += shfl_xor64(y, 2);
+    y += shfl_xor64(y, 1);
+    return y;
+}
+
+static_assert(kStreamSummaryCols == 64u * kSumWaves, "a thread of the workgroup per column of the tile");
+static_assert(kStreamSummaryRows % kStreamSumUnroll == 0 && kStreamSummaryRows <= kStreamSummaryCols,
+              "whole unrolled steps; a thread per row of the tile flushes it");
+
+// A summary stream's batch: the n_rows x n_cols matrix (row = streamed record, column = loaded record), tile
+// (tile0 + blockIdx.y, blockIdx.x) of kStreamSummaryRows x kStreamSummaryCols entries.  Thread t owns column blockIdx.x
+// kStreamSummaryCols + t and walks the tile's rows, so a wave reads 64 adjacent entries of a row per load.  The column's
+// four quantities stay in registers and go to loaded record j with one set of atomics per tile (LOADED).  Per row the
+// wave's counts come from ballots and its two sum words from wave_sum_rows, eight rows at a time (skipped when the wave
+// has nothing summable in them); one lane per row leaves them in LDS, and behind the barrier thread r adds the four waves'
+// to streamed record r (STREAMED).
+// The totals are the sum of the column accumulators: every entry of the tile once.
+template <bool INT, bool LOADED, bool STREAMED>
+__global__ __launch_bounds__(256) void summary_stream_kernel(const uint64_t *__restrict__ matrix, uint32_t n_rows, uint32_t n_cols,
+                                                             uint32_t tile0, uint64_t t_bits, int any, SummaryState cols, SummaryState rows,
+                                                             unsigned long long *tot)
+{
+    __shared__ Acc row_acc[STREAMED ? kStreamSummaryRows : 1][kSumWaves];
+    __shared__ Acc wave_acc[kSumWaves];
+    __shared__ uint32_t wave_nan[kSumWaves];
+    const int lane = (int)(threadIdx.x & 63), wave = (int)(threadIdx.x >> 6);
+    const uint64_t j64 = (uint64_t)blockIdx.x * kStreamSummaryCols + threadIdx.x;
+    const bool col_ok = j64 < n_cols;
+    const uint32_t r0 = (tile0 + blockIdx.y) * kStreamSummaryRows;        // (below n_rows: the grids have no empty tile row)
+    const uint32_t rows_here = min(kStreamSummaryRows, n_rows - r0);
+    const uint64_t t_key = nn_key<INT>(t_bits);
+    const uint64_t *p = matrix + (uint64_t)r0 * n_cols + (col_ok ? j64 : 0);
+    Acc col{};
+    uint32_t nan = 0;   // of the wave (uniform)
+    for (uint32_t r = 0; r < rows_here; r += kStreamSumUnroll) {   // (uniform)
+        uint64_t v[kStreamSumUnroll];
+        [[maybe_unused]] uint32_t row_within[kStreamSumUnroll], row_summable[kStreamSumUnroll];   // of the wave (uniform)
+        [[maybe_unused]] unsigned long long row_hi[kStreamSumUnroll], row_lo[kStreamSumUnroll];   // this lane's entry of each row
+#pragma unroll
+        for (int u = 0; u < kStreamSumUnroll; ++u)
+            v[u] = col_ok && r + u < rows_here ? __builtin_nontemporal_load(p + (uint64_t)(r + u) * n_cols) : 0;
+#pragma unroll
+        for (int u = 0; u < kStreamSumUnroll; ++u) {
+            const bool ok = col_ok && r + u < rows_here;
+            Acc a{};
+            if (ok)
+                add_pair<INT>(a, v[u], t_key, any != 0);
+            col.within += a.within;
+            col.summable += a.summable;
+            col.hi += a.hi;
+            col.lo += a.lo;
+            if constexpr (!INT)
+                nan += (uint32_t)__popcll(__ballot(ok && is_nan<INT>(v[u])));
+            if constexpr (STREAMED) {
+                row_within[u] = (uint32_t)__popcll(__ballot(a.within != 0));
+                row_summable[u] = (uint32_t)__popcll(__ballot(a.summable != 0));
+                row_hi[u] = (unsigned long long)a.hi;
+                row_lo[u] = a.lo;
+            }
+        }
+        if constexpr (STREAMED) {
+            uint32_t summable = 0;
+#pragma unroll
+            for (int u = 0; u < kStreamSumUnroll; ++u)
+                summable |= row_summable[u];
+            unsigned long long hi = 0, lo = 0;
+            if (summable) {   // (uniform)
+                hi = wave_sum_rows(row_hi, lane);
+                lo = wave_sum_rows(row_lo, lane);
+            }
+#pragma unroll
+            for (int u = 0; u < kStreamSumUnroll; ++u)
+                if (lane == sum_rows_lane(u) && r + u < rows_here)
+                    row_acc[r + u][wave] = Acc{row_within[u], row_summable[u], (long long)hi, lo};
+        }
+    }
+    if constexpr (LOADED) {
+        if (col_ok)
+            add_to_record(cols, (uint32_t)j64, col);
+    }
+    wave_sum(col);
+    if (lane == 0) {
+        wave_acc[wave] = col;
+        wave_nan[wave] = nan;
+    }
+    __syncthreads();
+    if constexpr (STREAMED) {
+        if (threadIdx.x < rows_here) {
+            Acc total{};
+#pragma unroll
+            for (int w = 0; w < kSumWaves; ++w) {
+                total.within += row_acc[threadIdx.x][w].within;
+                total.summable += row_acc[threadIdx.x][w].summable;
+                total.hi += row_acc[threadIdx.x][w].hi;
+                total.lo += row_acc[threadIdx.x][w].lo;
+            }
+            add_to_record(rows, r0 + threadIdx.x, total);
+        }
+    }
+    if (threadIdx.x == 0) {
+        Acc total{};
+        unsigned long long nans = 0;
+#pragma unroll
+        for (int w = 0; w < kSumWaves; ++w) {
+            total.within += wave_acc[w].within;
+            total.summable += wave_acc[w].summable;
+            total.hi += wave_acc[w].hi;
+            total.lo += wave_acc[w].lo;
+            nans += wave_nan[w];
+        }
+        add_to_totals(tot, nans, total);
+    }
+}
+
 SummaryState state_of(const SummaryBuffers &b)
 {
     return SummaryState{b.within, b.summable, reinterpret_cast<long long *>(b.hi), reinterpret_cast<unsigned long long *>(b.lo),
@@ -363,6 +531,46 @@ hipError_t launch_summary_hist(int measure, const uint64_t *slab, uint64_t pairs
     }
 #undef DST_SUMMARY_HIST
     return hipGetLastError();
+}
+
+hipError_t launch_summary_stream(int measure, const uint64_t *matrix, uint64_t n_records, uint64_t n_loaded, uint64_t t_bits,
+                                 bool any, const SummaryBuffers *loaded, const SummaryBuffers *streamed, uint64_t *tot,
+                                 hipStream_t stream)
+{
+    if (n_records == 0 || n_loaded == 0)
+        return hipSuccess;
+    if (n_records > 0xFFFFFFFFull || n_loaded > 0xFFFFFFFFull)
+        return hipErrorInvalidValue;
+    const bool int_payload = measure == DST_N || measure == DST_N_HIGH;
+    const unsigned col_tiles = (unsigned)((n_loaded + kStreamSummaryCols - 1) / kStreamSummaryCols);
+    const uint64_t row_tiles = (n_records + kStreamSummaryRows - 1) / kStreamSummaryRows;
+    const SummaryState none{};
+    const SummaryState c = loaded ? state_of(*loaded) : none, r = streamed ? state_of(*streamed) : none;
+    unsigned long long *t = reinterpret_cast<unsigned long long *>(tot);
+    return for_row_grids(0, row_tiles, [&](uint64_t tile0, unsigned tiles) {
+        const dim3 grid(col_tiles, tiles);
+#define DST_SUMMARY_STREAM(INT, L, S)                                                                                          \
+    hipLaunchKernelGGL((summary_stream_kernel<INT, L, S>), grid, dim3(256), 0, stream, matrix, (uint32_t)n_records,            \
+                       (uint32_t)n_loaded, (uint32_t)tile0, t_bits, any ? 1 : 0, c, r, t)
+#define DST_SUMMARY_STREAM_SIDES(INT)                                                                                          \
+    do {                                                                                                                       \
+        if (loaded && streamed)                                                                                                \
+            DST_SUMMARY_STREAM(INT, true, true);                                                                               \
+        else if (loaded)                                                                                                       \
+            DST_SUMMARY_STREAM(INT, true, false);                                                                              \
+        else if (streamed)                                                                                                     \
+            DST_SUMMARY_STREAM(INT, false, true);                                                                              \
+        else                                                                                                                   \
+            DST_SUMMARY_STREAM(INT, false, false);                                                                             \
+    } while (0)
+        if (int_payload)
+            DST_SUMMARY_STREAM_SIDES(true);
+        else
+            DST_SUMMARY_STREAM_SIDES(false);
+#undef DST_SUMMARY_STREAM_SIDES
+#undef DST_SUMMARY_STREAM
+        return hipGetLastError();
+    });
 }
 
 }  // namespace dst

@@ -11,7 +11,8 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (ALLGATHER_FN, GROUP_NONE, LINKS_CHUNK, LINKS_SINK, LINKS_TALLIES, LINKS_VALUES, SLAB_SINK, DistanceError,
+from ._lib import (ALLGATHER_FN, GROUP_NONE, LINKS_CHUNK, LINKS_SINK, LINKS_TALLIES, LINKS_VALUES, SLAB_SINK,
+                   STREAM_SUMMARY_LOADED, STREAM_SUMMARY_STREAMED, DistanceError,
                    GroupCell, LaunchInfo, PairsInfo, SummaryTotals, load)
 
 MEASURES = {"n": 0, "n_high": 1, "raw": 2, "jc69": 3, "k80": 4, "tn93": 5}
@@ -461,6 +462,13 @@ class Engine:
         per batch (n_records, streamed, loaded[, values][, tallies]), by dst_links' rule, in the stream's own order.
         window: the most links of one window (0: the default); the result does not depend on it."""
         return LinksStream(self, measure, threshold, max_records, depth, nibbles, values, tallies, window)
+
+    def summary_stream(self, measure, max_records: int, threshold: float = 0.0, loaded: bool = True, streamed: bool = False,
+                       bins: int = 0, width: float = 1.0, depth: int = 3, nibbles: bool = False) -> "SummaryStream":
+        """A stream that keeps summary()'s counts and exact sums instead of the result matrix (dst_stream_open_summary).
+        loaded: every loaded record's `within`, `summable` and `sum` over the whole stream (result()); streamed: the same
+        for every streamed record over the loaded set, per batch (pop()); bins: the histogram of every pair so far."""
+        return SummaryStream(self, measure, max_records, threshold, loaded, streamed, bins, width, depth, nibbles)
 
     def run_slabs(self, measure, sink, max_pairs: int, square: bool = True, row_slot: int = 0, col_slot: int = 1,
                   tallies: bool = False):
@@ -1371,3 +1379,62 @@ class LinksStream(Stream):
         links, late = C.c_uint64(), C.c_uint64()
         self._eng._check(self._lib.dst_stream_links_stats(self._h, C.byref(links), C.byref(late)))
         return int(links.value), int(late.value)
+
+
+class SummaryStream(Stream):
+    """dst_stream_open_summary: a Stream whose batches leave summary()'s counts and exact sums behind instead of the result
+    matrix.  pop() returns the batch's record count, or with streamed=True (n_records, within, summable, sum) of the batch's
+    records over the loaded set, as copies; result() is summary()'s dict over every pair so far plus `records`: the totals,
+    `within` / `summable` / `sum` of the loaded records when loaded=True, `hist` when bins > 0."""
+
+    def __init__(self, eng: Engine, measure, max_records: int, threshold: float = 0.0, loaded: bool = True,
+                 streamed: bool = False, bins: int = 0, width: float = 1.0, depth: int = 3, nibbles: bool = False):
+        self.threshold, self.loaded, self.streamed = float(threshold), bool(loaded), bool(streamed)
+        self.bins, self.width = int(bins), float(width)
+        super().__init__(eng, measure, max_records, depth, False, nibbles)
+
+    def _open(self):
+        h = C.c_void_p()
+        what = (STREAM_SUMMARY_LOADED if self.loaded else 0) | (STREAM_SUMMARY_STREAMED if self.streamed else 0)
+        self._eng._check(self._lib.dst_stream_open_summary(self._eng._h, self._m, self.threshold, what, self.bins, self.width,
+                                                           self.max_records, self.depth, int(self.nibbles), C.byref(h)))
+        return h
+
+    def summary_batch(self):
+        """(n_records, within, summable, sum) of the batch pop() collected last: copies (dst_stream_summary_batch)"""
+        n, wp, sp, dp = C.c_size_t(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._eng._check(self._lib.dst_stream_summary_batch(self._h, C.byref(n), C.byref(wp), C.byref(sp), C.byref(dp)))
+        m = int(n.value)
+        within = np.ctypeslib.as_array(C.cast(wp, C.POINTER(C.c_uint32)), shape=(m,)).copy()
+        summable = np.ctypeslib.as_array(C.cast(sp, C.POINTER(C.c_uint32)), shape=(m,)).copy()
+        sums = np.ctypeslib.as_array(C.cast(dp, C.POINTER(C.c_double)), shape=(m,)).copy()
+        return m, within, summable, sums
+
+    def pop(self, copy: bool = True):
+        n, p = C.c_size_t(), C.c_void_p()
+        self._eng._check(self._lib.dst_stream_collect(self._h, C.byref(n), C.byref(p)))
+        return self.summary_batch() if self.streamed else int(n.value)
+
+    def result(self, cap: int | None = None) -> dict:
+        """A snapshot of everything kept so far (dst_stream_summary_result); every pushed batch must have been popped."""
+        n = self._n_loaded
+        cap = n if cap is None else int(cap)
+        room = max(cap, 1)
+        within = np.zeros(room, np.uint32) if self.loaded else None
+        summable = np.zeros(room, np.uint32) if self.loaded else None
+        sums = np.zeros(room, np.float64) if self.loaded else None
+        hist = np.zeros(max(self.bins, 1), np.uint64) if self.bins else None
+        tot, records = SummaryTotals(), C.c_uint64()
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data
+
+        self._eng._check(self._lib.dst_stream_summary_result(self._h, ptr(hist), ptr(within), ptr(summable), ptr(sums), cap,
+                                                             C.byref(tot), C.byref(records)))
+        out = {"records": int(records.value), "pairs": int(tot.pairs), "nan_pairs": int(tot.nan_pairs),
+               "summable_pairs": int(tot.summable_pairs), "links": int(tot.links), "total_sum": float(tot.sum)}
+        if self.loaded:
+            out.update(within=within[:n], summable=summable[:n], sum=sums[:n])
+        if self.bins:
+            out["hist"] = hist[:self.bins]
+        return out

@@ -826,6 +826,55 @@ typedef struct dst_summary_totals {
 int dst_summary(dst_ctx *ctx, int measure, int square, int row_slot, int col_slot, double threshold, uint64_t max_pairs,
                 uint32_t bins, double width, uint64_t *hist, uint32_t *within, uint32_t *summable, double *sum, size_t cap,
                 dst_summary_totals *totals);
+/* ---- summaries in stream mode ---------------------------------------------------------------------- */
+/* A stream that keeps dst_summary's counts and exact sums instead of the result matrix: how many records of a database that
+ * does not fit in memory lie within T of each of mine, each record's mean distance to the database, the distribution of
+ * the distances - and, per database record, how it sits against the loaded set.  A summary stream IS a dst_stream, the
+ * fifth kind: dst_stream_acquire / _submit / _collect / _in_flight / _close work on it as on a closest stream, with both
+ * wire formats, the caller's base counts and the ring of `depth` slots (2..16); dst_stream_collect returns *results = NULL,
+ * but still waits for the batch and still reports DST_ERR_INVALID_CODE.
+ * Definition, fixed to the bit.  The payload v of the pair (streamed s, loaded i) is what the same stream would deliver for
+ * it as DST_OUT_DISTANCE, bit for bit: the rectangle with the batch as rows (tn93: the streamed record's base counts as q,
+ * the loaded record's as t; the same use_base_counts).  link, summable, q, bin, the one conversion of an exact integer sum
+ * to double and the scaling by 2^-DST_SUMMARY_SCALE_BITS are dst_summary's (above), word for word, and so are threshold,
+ * bins and width with their checks and messages.
+ *  DST_STREAM_SUMMARY_STREAMED  per batch: within[s], summable[s], sum[s] of every record s of the batch over all loaded i -
+ *                               what dst_summary(square = 0, rows = the batch, cols = slot 0) returns per row record
+ *  DST_STREAM_SUMMARY_LOADED    kept over the stream's life: within[i], summable[i], sum[i] of every loaded record i over
+ *                               every streamed record of every batch submitted so far
+ * hist and the totals run over every pair so far, each once; totals.pairs = records x n_loaded, *records the number of
+ * records submitted.  `what` may be 0: the totals and the histogram alone are kept, O(bins) of state.  All accumulation is
+ * integer, so the answer does not depend on how the stream is cut into batches, on depth, on the wire format or on the path.
+ * Limits.  The per-record counters are uint32 and the hi / lo split of a sum needs fewer than 2^32 partners: a submit that
+ * would take the records past 2^32-2 (compared in 64 bits) is DST_ERR_CAPACITY and changes nothing.  A batch's atomics cannot
+ * be taken back: after a batch with an invalid code every later dst_stream_submit, dst_stream_summary_batch and
+ * dst_stream_summary_result on that stream is DST_ERR_STATE, as for DST_CLOSEST_FOR_LOADED.
+ * Open, errors in this order: DST_ERR_ARG for a NULL ctx or stream pointer, an unknown measure or wire, a NaN threshold, bits
+ * in `what` other than the two, the bins and width rules of dst_summary (hist is not asked for here), max_records == 0, depth
+ * outside 2..16; DST_ERR_STATE for slot 0 not loaded; DST_ERR_ARG for a loaded set of 2^32-1 records or more; DST_ERR_NOMEM.
+ * Submit: DST_ERR_STATE when the loaded set's record count or width changed.  An empty loaded set runs no reduction and
+ * gives zero results.  The calls below on any other stream are DST_ERR_ARG, as are the closest, links and window-closest
+ * calls on this one; a NULL stream is DST_ERR_ARG.
+ * The stream owns all of its state - the kept words, zeroed once at open, and per ring slot the batch's records' words - so
+ * dst_summary or any other call on the context between two submits does not disturb it.  Per submit, on the compute stream
+ * behind the batch's pair kernel: one tile pass over the batch's matrix that reads every entry once for both sides and the
+ * totals, and with bins > 0 dst_summary's histogram pass.  Per batch the bad-code word and (STREAMED) 24 bytes per streamed
+ * record cross the host link, never the matrix.  Single GPU. */
+#define DST_STREAM_SUMMARY_LOADED   1  /* keep the loaded records' per-record state over the stream's life */
+#define DST_STREAM_SUMMARY_STREAMED 2  /* hand out every batch's streamed records' per-record results     */
+int dst_stream_open_summary(dst_ctx *ctx, int measure, double threshold, int what, uint32_t bins, double width,
+                            size_t max_records, int depth, int wire, dst_stream **stream);
+/* STREAMED only (else DST_ERR_ARG).  After dst_stream_collect: the collected batch, *n_records entries per array, in
+ * page-locked, library-owned memory that is valid until the next dst_stream_submit.  n_records is required; within, summable
+ * and sum may be NULL.  DST_ERR_STATE when no batch has been collected since the last submit. */
+int dst_stream_summary_batch(dst_stream *stream, size_t *n_records, const uint32_t **within,
+                             const uint32_t **summable, const double **sum);
+/* A snapshot of everything kept so far (host memory): hist (bins entries), the loaded records' within / summable / sum
+ * (n_loaded entries each), the totals and *records; every pointer may be NULL.  Without DST_STREAM_SUMMARY_LOADED the three
+ * per-record pointers must be NULL, else DST_ERR_ARG.  Needs dst_stream_in_flight() == 0, else DST_ERR_STATE; cap below
+ * n_loaded with a non-NULL per-record array: DST_ERR_CAPACITY.  The call may be repeated, and streaming may go on afterwards. */
+int dst_stream_summary_result(dst_stream *stream, uint64_t *hist, uint32_t *within, uint32_t *summable, double *sum,
+                              size_t cap, dst_summary_totals *totals, uint64_t *records);
 /* ---- summaries per column window ------------------------------------------------------------------- */
 /* dst_summary's counts and sums INSIDE every column window, reduced next to the window sweep on the GPU: diversity along
  * the genome (pi per window with raw on one set, d_xy per window between two sets), the mean distance of a query to a
