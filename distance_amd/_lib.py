@@ -34,6 +34,9 @@ SUMMARY_MAX_BINS = 4096   # DST_SUMMARY_MAX_BINS
 STREAM_SUMMARY_LOADED, STREAM_SUMMARY_STREAMED = 1, 2   # DST_STREAM_SUMMARY_*: the sides of a summary stream
 STREAM_SUMMARY_ROWS = 64     # kStreamSummaryRows (csrc/dst_internal.h): the tile of a summary stream's kernel, streamed records
 STREAM_SUMMARY_COLS = 256    # kStreamSummaryCols: ... and loaded records
+STREAM_GROUPS_LOADED, STREAM_GROUPS_STREAMED = 1, 2   # DST_STREAM_GROUPS_*: the tables of a group-summary stream
+STREAM_GROUPS_ROWS = 64      # kStreamGroupRows (csrc/dst_internal.h): the tile of a group-summary stream's column kernel, streamed records
+STREAM_GROUPS_COLS = 256     # kStreamGroupCols: ... and loaded records
 GROUPS_MAX = 1024         # DST_GROUPS_MAX: the most groups of one side of dst_group_summary
 WINDOW_GROUPS_MAX = 256   # DST_WINDOW_GROUPS_MAX: the most groups of one side of dst_window_group_summary
 GROUP_NONE = 0xFFFFFFFF   # DST_GROUP_NONE: a record that belongs to no group
@@ -169,6 +172,11 @@ _SIGS = {
                                           C.POINTER(_vp)]),
     "dst_stream_summary_batch": (C.c_int, [_vp, C.POINTER(C.c_size_t), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
     "dst_stream_summary_result": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.c_size_t, _vp, _u64p]),
+    "dst_stream_open_group_summary": (C.c_int, [_vp, C.c_int, C.c_double, C.c_int, _vp, C.c_uint32, C.c_uint32, C.c_size_t, C.c_int,
+                                                C.c_int, C.POINTER(_vp)]),
+    "dst_stream_group_labels": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "dst_stream_group_summary_batch": (C.c_int, [_vp, C.POINTER(C.c_size_t), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp)]),
+    "dst_stream_group_summary_result": (C.c_int, [_vp, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t, _u64p]),
     "dst_window_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_uint32, C.c_double, _vp, _vp, _vp,
                                      _vp, C.c_size_t]),
     "dst_group_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, C.c_uint32, _vp, C.c_uint32, C.c_double,

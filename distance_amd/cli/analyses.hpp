@@ -425,6 +425,28 @@ std::vector<GroupLabels> label_inputs(const GroupFile &gf, const std::vector<Ali
     return labels;
 }
 
+// --stream-groups: the label file against the loaded set, before the device is looked at.  The streamed records meet the
+// file batch by batch (stream.hpp); `seen` collects the ids of the file that either side carries.
+struct StreamGroups {
+    const GroupFile *file = nullptr;
+    GroupLabels loaded;                        // by loaded: no labels, one group
+    std::unordered_set<std::string> seen;
+};
+
+StreamGroups label_loaded_for_stream(const GroupFile &gf, const Alignment &set, int by)
+{
+    StreamGroups sg;
+    sg.file = &gf;
+    if (by != 2) {
+        sg.loaded = label_records(gf, set, "loaded", sg.seen, DST_GROUPS_MAX);
+        return sg;
+    }
+    for (size_t r = 0; r < set.n; ++r)
+        if (gf.of.count(set.ids[r]))
+            sg.seen.insert(set.ids[r]);
+    return sg;
+}
+
 // The fields --groups and --window-groups print behind the names of a line, each with its tab in front.
 // a cell: pairs, compared, [within,] mean, min, max
 void put_group_cell(LineWriter &out, int measure, const dst_group_cell &c, bool has_within)

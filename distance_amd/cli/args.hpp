@@ -60,6 +60,17 @@ void print_help()
         "streamed records, as --histogram does, bins of width W. Requires --stream, one loaded file, one GPU, no other "
         "output mode\n"
         "      --stream-bins <B>        Bins of --stream-histogram, 1 to 4096 [default: 256]\n"
+        "      --stream-groups <FILE>   Stream mode only: print --groups' lines for the streamed file against the loaded one, "
+        "reduced on the GPU batch by batch: FILE as for --groups, an id's group applies to whichever file carries it; the "
+        "streamed groups are numbered in order of their first record (at most 1024). Requires --stream, one loaded file, one "
+        "GPU, no other output mode\n"
+        "      --stream-groups-by <what>  What --stream-groups prints a line for: cell (a streamed group and a loaded group, "
+        "written when the stream ends: the lines of '--groups FILE streamed loaded'), streamed (every streamed record and "
+        "loaded group, in stream order: the lines '--groups FILE streamed loaded' prints when asked for a line per record; "
+        "needs no streamed labels) or loaded (every loaded record and streamed group, written when the stream ends; needs no loaded labels) "
+        "[default: cell]\n"
+        "      --stream-groups-within <T>  With --stream-groups: a 'within' column, the compared pairs within distance T (a "
+        "number >= 0, or inf)\n"
         "      --clusters <T>           Print the single-linkage cluster of every record instead of distances: records "
         "within distance T (a number >= 0) of each other share a cluster, numbered from 1 in order of first record. One "
         "input, one GPU, no --stream or --nearest\n"
@@ -162,7 +173,8 @@ enum Flag {
     F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM, F_SELFTEST, F_REPRESENTATIVES,
     F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_PAIRS, F_WINDOW_CLOSEST,
     F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY, F_WINDOW_GROUPS, F_WINDOW_GROUPS_WITHIN, F_WINDOW_GROUPS_BY,
-    F_STREAM_SUMMARY, F_STREAM_SUMMARY_FOR, F_STREAM_HISTOGRAM, F_STREAM_BINS, F_COUNT
+    F_STREAM_SUMMARY, F_STREAM_SUMMARY_FOR, F_STREAM_HISTOGRAM, F_STREAM_BINS,
+    F_STREAM_GROUPS, F_STREAM_GROUPS_BY, F_STREAM_GROUPS_WITHIN, F_COUNT
 };
 struct FlagDef {
     const char *shown;   // "--name <value>": its first word is the flag itself
@@ -187,11 +199,13 @@ const FlagDef kFlags[F_COUNT] = {
     {"--window-groups-by <what>", nullptr, false},
     {"--stream-summary <T>", nullptr, true}, {"--stream-summary-for <side>", nullptr, false},
     {"--stream-histogram <W>", nullptr, true}, {"--stream-bins <B>", nullptr, false},
+    {"--stream-groups <FILE>", nullptr, true}, {"--stream-groups-by <what>", nullptr, false},
+    {"--stream-groups-within <T>", nullptr, true},
 };
 
 // what the run prints, decided once by parse_args
 enum class Mode { Pairs, Stream, Closest, Within, Nearest, Clusters, MaxDistance, Summary, Histogram, Groups, Matrix, Tree, Mst,
-                  Dendrogram, Representatives, Windows, PairList, WindowClosest, StreamSummary, StreamHistogram };
+                  Dendrogram, Representatives, Windows, PairList, WindowClosest, StreamSummary, StreamHistogram, StreamGroups };
 
 struct Args {
     bool has[F_COUNT] = {};               // the flag was given
@@ -233,6 +247,9 @@ struct Args {
     bool stream_summary_streamed = false;    // --stream-summary-for loaded|streamed
     double stream_histogram = 0;          // --stream-histogram W (stream mode)
     size_t stream_bins = 256;             // --stream-bins B
+    std::string stream_groups;            // --stream-groups FILE (stream mode)
+    int stream_groups_by = 0;             // --stream-groups-by cell|streamed|loaded: 0, 1, 2
+    double stream_groups_within = 0;      // --stream-groups-within T
     std::string selftest;
     size_t n_inputs() const { return flag_inputs.size() + pos_inputs.size(); }
     // the slab size an analysis is given: the library's own choice unless --slab-pairs was passed
@@ -326,6 +343,13 @@ const std::vector<Flag> kStreamSummaryRefuses = {
     F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_PAIRS, F_WINDOW_CLOSEST, F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY,
     F_WINDOW_GROUPS, F_WINDOW_GROUPS_WITHIN, F_WINDOW_GROUPS_BY};
 const Rule kRules[] = {
+    // (before every other row: a command line with --stream-groups or one of its two modifiers is judged here first, and no
+    // other line's outcome changes)
+    {F_STREAM_GROUPS_BY, Mode::Pairs, kNone, {F_STREAM_GROUPS}, "'--stream-groups <FILE>'", TWO_OK, false},
+    {F_STREAM_GROUPS_WITHIN, Mode::Pairs, kNone, {F_STREAM_GROUPS}, "'--stream-groups <FILE>'", TWO_OK, false},
+    {F_STREAM_GROUPS, Mode::StreamGroups,
+     after(F_STREAM_SUMMARY, after(F_STREAM_SUMMARY_FOR, after(F_STREAM_HISTOGRAM, after(F_STREAM_BINS, kStreamSummaryRefuses)))),
+     {F_STREAM}, "'--stream <stream>'", ONE_LOADED, true},
     // (before every other row: a command line with --stream-summary, --stream-histogram or one of their modifiers is judged
     // here first, and no other line's outcome changes)
     {F_STREAM_SUMMARY_FOR, Mode::Pairs, kNone, {F_STREAM_SUMMARY}, "'--stream-summary <T>'", TWO_OK, false},
@@ -502,7 +526,7 @@ Args parse_args(int argc, char **argv)
             while (a.flag_inputs.size() < 2 && k + 1 < argc && (argv[k + 1][0] != '-' || !std::strcmp(argv[k + 1], "-")))
                 a.flag_inputs.push_back(argv[++k]);
         } else if (text(F_STREAM, a.stream) || text(F_MEASURE, a.measure) || text(F_OUTPUT, a.output) ||
-                   text(F_GROUPS, a.groups) || text(F_WINDOW_GROUPS, a.window_groups) || text(F_REGIONS, a.regions) || text(F_PAIRS, a.pairs) || count(F_WINDOWS, a.windows, 1, SIZE_MAX) ||
+                   text(F_GROUPS, a.groups) || text(F_WINDOW_GROUPS, a.window_groups) || text(F_STREAM_GROUPS, a.stream_groups) || text(F_REGIONS, a.regions) || text(F_PAIRS, a.pairs) || count(F_WINDOWS, a.windows, 1, SIZE_MAX) ||
                    count(F_STEP, a.step, 1, SIZE_MAX) || count(F_THREADS, a.threads, 0, SIZE_MAX) ||
                    count(F_BATCHSIZE, a.batchsize, 0, SIZE_MAX) || count(F_SEED, a.seed, 0, SIZE_MAX) ||
                    count(F_NEAREST, a.nearest, 1, 256) || count(F_CLOSEST, a.closest, 1, 256) ||
@@ -512,6 +536,7 @@ Args parse_args(int argc, char **argv)
                    threshold(F_WITHIN, a.within) || threshold(F_SUMMARY, a.summary) ||
                    threshold(F_GROUPS_WITHIN, a.groups_within) || threshold(F_WINDOW_GROUPS_WITHIN, a.window_groups_within) ||
                    threshold(F_WINDOW_SUMMARY, a.window_summary) || threshold(F_STREAM_SUMMARY, a.stream_summary) ||
+                   threshold(F_STREAM_GROUPS_WITHIN, a.stream_groups_within) ||
                    count(F_STREAM_BINS, a.stream_bins, 1, DST_SUMMARY_MAX_BINS)) {
             // a word, a count in a range or a threshold: stored
         } else if (opt(F_GPUS)) {
@@ -535,6 +560,8 @@ Args parse_args(int argc, char **argv)
             a.histogram = bin_width(F_HISTOGRAM);
         } else if (opt(F_STREAM_HISTOGRAM)) {
             a.stream_histogram = bin_width(F_STREAM_HISTOGRAM);
+        } else if (opt(F_STREAM_GROUPS_BY)) {
+            a.stream_groups_by = parse_choice(v, shown(F_STREAM_GROUPS_BY), {{"cell", 0}, {"streamed", 1}, {"loaded", 2}});
         } else if (opt(F_STREAM_SUMMARY_FOR)) {
             a.stream_summary_streamed = parse_choice(v, shown(F_STREAM_SUMMARY_FOR), {{"loaded", 0}, {"streamed", 1}}) != 0;
         } else if (opt(F_MATRIX)) {

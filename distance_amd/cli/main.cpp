@@ -157,6 +157,8 @@ int main(int argc, char **argv)
         group_file = read_group_file(a.groups);
     else if (a.has[F_WINDOW_GROUPS])
         group_file = read_group_file(a.window_groups, "--window-groups");
+    else if (a.mode == Mode::StreamGroups)
+        group_file = read_group_file(a.stream_groups, "--stream-groups");
     // --pairs: likewise
     PairFile pair_file;
     if (a.mode == Mode::PairList)
@@ -196,6 +198,10 @@ int main(int argc, char **argv)
         group_labels = label_inputs(group_file, loaded);
     else if (a.has[F_WINDOW_GROUPS])
         group_labels = label_inputs(group_file, loaded, DST_WINDOW_GROUPS_MAX);
+    // --stream-groups: the loaded records' labels (cell, streamed), and the ids of the file that the loaded side carries
+    StreamGroups stream_groups;
+    if (a.mode == Mode::StreamGroups)
+        stream_groups = label_loaded_for_stream(group_file, loaded[0], a.stream_groups_by);
     // --pairs: the records its ids name
     PairList pair_list;
     if (a.mode == Mode::PairList)
@@ -288,7 +294,10 @@ int main(int argc, char **argv)
     case Mode::WindowClosest:
     case Mode::StreamSummary:
     case Mode::StreamHistogram:
-    case Mode::Within: StreamRun(a, gpus, loaded[0], counts[0], job, stream_fh, table, parse_threads, wr, &windows).run(); break;
+    case Mode::StreamGroups:
+    case Mode::Within:
+        StreamRun(a, gpus, loaded[0], counts[0], job, stream_fh, table, parse_threads, wr, &windows, &stream_groups).run();
+        break;
     }
     timer.mark("compute + format + write");
     wr.flush();

@@ -50,6 +50,13 @@ struct StreamRun {
     const bool keep_ids;                   // the final lines name streamed records: their ids stay, in one arena
     // --stream-summary / --stream-histogram: the sums stay on the GPU; only --stream-summary-for streamed has lines per batch
     const bool summary, summary_streamed;
+    // --stream-groups: the cells and the tables stay on the GPU; only --stream-groups-by streamed has lines per batch.  The
+    // streamed groups are numbered as their first record is submitted (one GPU, so submission order is stream order).
+    StreamGroups *const groups;
+    const bool grouped, groups_streamed, groups_within;
+    const uint32_t groups_open;            // the streamed group count the stream was opened with
+    std::unordered_map<std::string, uint32_t> group_number;
+    std::vector<std::string> group_names;
 
     std::mutex qmu;                        // reader -> dispatcher -> per-GPU input queues
     std::condition_variable qcv;
@@ -71,7 +78,7 @@ struct StreamRun {
     std::vector<uint32_t> kept_counts;
 
     StreamRun(const Args &args, std::vector<Ctx> &g, const Alignment &loaded, const std::vector<uint32_t> &counts, const Job &j,
-              FILE *stream_fh, const uint8_t *tab, size_t threads, Writer &w, const WindowList *wl = nullptr)
+              FILE *stream_fh, const uint8_t *tab, size_t threads, Writer &w, const WindowList *wl = nullptr, StreamGroups *sg = nullptr)
         : a(args), gpus(g), ref(loaded), ref_counts(tn93_counts(j.measure, counts, counts)), job(j), measure(j.measure),
           tn93(j.measure == DST_TN93), fh(stream_fh), table(tab), parse_threads(threads), wr(w), G(g.size()),
           TW((size_t)dst_tally_width(j.measure)),
@@ -82,9 +89,21 @@ struct StreamRun {
           window_closest(args.mode == Mode::WindowClosest),
           keep_ids(closest_loaded || window_closest),
           summary(args.mode == Mode::StreamSummary || args.mode == Mode::StreamHistogram),
-          summary_streamed(args.mode == Mode::StreamSummary && args.stream_summary_streamed), gq(G), gdone(G, false),
+          summary_streamed(args.mode == Mode::StreamSummary && args.stream_summary_streamed), groups(sg),
+          grouped(args.mode == Mode::StreamGroups), groups_streamed(grouped && args.stream_groups_by == 1),
+          groups_within(args.has[F_STREAM_GROUPS_WITHIN]),
+          groups_open(grouped && !groups_streamed ? (uint32_t)std::min<size_t>(std::max<size_t>(distinct_groups(sg), 1), DST_GROUPS_MAX) : 1),
+          gq(G), gdone(G, false),
           window(G * (kDepth + 2)), streams(G, nullptr)
     {
+    }
+
+    static size_t distinct_groups(const StreamGroups *sg)
+    {
+        std::unordered_set<std::string> names;
+        for (const auto &entry : sg->file->of)
+            names.insert(entry.second.first);
+        return names.size();
     }
 
     void read()
@@ -273,6 +292,60 @@ struct StreamRun {
         return text;
     }
 
+    // --stream-groups: the batch's labels into the acquired slot's block (by streamed: none, every record in group 0), the
+    // ids of the file that the batch carries into `seen`
+    void label_batch(size_t g, const Alignment &al)
+    {
+        uint32_t *labels = nullptr;
+        gpus[g].check(dst_stream_group_labels(streams[g], &labels), "stream group labels");
+        const GroupFile &gf = *groups->file;
+        for (size_t r = 0; r < al.n; ++r) {
+            const auto it = gf.of.find(al.ids[r]);
+            if (it == gf.of.end()) {
+                if (!groups_streamed)
+                    labels[r] = DST_GROUP_NONE;
+                continue;
+            }
+            groups->seen.insert(al.ids[r]);
+            if (groups_streamed)
+                continue;
+            const auto ins = group_number.emplace(it->second.first, (uint32_t)group_names.size());
+            if (ins.second) {
+                if (group_names.size() == groups_open)
+                    die_message(gf.flag + ": the streamed record '" + al.ids[r] + "' starts group " + std::to_string(groups_open + 1) +
+                                " of the stream: more than " + std::to_string(groups_open) + " groups");
+                group_names.push_back(it->second.first);
+            }
+            labels[r] = ins.first->second;
+        }
+    }
+
+    // --stream-groups-by streamed: the batch's records in stream order, each with --groups --per-record's lines against the
+    // loaded groups (cell, loaded: nothing per batch, the lines follow the stream's end)
+    std::vector<TextBuf> collect_groups(size_t g, const Item &it)
+    {
+        std::vector<TextBuf> text;
+        if (!groups_streamed)
+            return text;
+        size_t n_rec = 0;
+        const uint32_t *within = nullptr, *summable = nullptr;
+        const double *sum = nullptr;
+        gpus[g].check(dst_stream_group_summary_batch(streams[g], &n_rec, &within, &summable, &sum), "stream group summary batch");
+        const std::vector<std::string> &names = groups->loaded.names;
+        LineWriter out(wr);
+        for (size_t r = 0; r < n_rec; ++r)
+            for (size_t b = 0; b < names.size(); ++b) {
+                const size_t e = r * names.size() + b;
+                out.put(it.batch->ids[r]);
+                out.put('\t');
+                out.put(names[b]);
+                put_group_record(out, summable[e], within[e], sum[e], groups_within);
+                out.put('\n');   // (not end_line: the text goes to the ordered writer, not out now)
+            }
+        text.push_back(std::move(out.buf));
+        return text;
+    }
+
     void collect_one(size_t g, std::deque<Item> &inflight)
     {
         size_t n_rec = 0;
@@ -283,6 +356,7 @@ struct StreamRun {
         hand_over(it.idx, a.mode == Mode::Within          ? collect_within(g, it)
                           : a.mode == Mode::Closest       ? collect_closest(g, it, n_rec)
                           : summary                       ? collect_summary(g, it)
+                          : grouped                       ? collect_groups(g, it)
                           : a.mode == Mode::WindowClosest ? std::vector<TextBuf>()   // (the lines follow the stream's end)
                                                           : collect_matrix(it, res));
     }
@@ -318,6 +392,8 @@ struct StreamRun {
             const bool send_counts = tn93 && !window_closest;
             if (send_counts)
                 std::memcpy(cbuf, al.counts.data(), al.n * 4 * sizeof(uint32_t));
+            if (grouped)
+                label_batch(g, al);
             gpus[g].check(dst_stream_submit(streams[g], al.n, send_counts ? 1 : 0), "stream submit");
             if (keep_ids) {   // ordinal = position in submission order: keep what the final lines need
                 for (size_t r = 0; r < al.n; ++r) {
@@ -328,7 +404,7 @@ struct StreamRun {
                     kept_counts.insert(kept_counts.end(), al.counts.begin(), al.counts.end());
                 it.batch.reset();
             }
-            if (summary && !summary_streamed)
+            if ((summary && !summary_streamed) || (grouped && !groups_streamed))
                 it.batch.reset();   // no line names a streamed record: host memory does not grow with the stream
             inflight.push_back(std::move(it));
         }
@@ -452,8 +528,53 @@ struct StreamRun {
         histogram_lines(wr, measure, a.stream_histogram, hist, totals.nan_pairs);
     }
 
+    // --stream-groups (cell): --groups' line per (streamed group, loaded group); (loaded): --per-record's line per loaded
+    // record in input order and streamed group, the groups in order of their first record
+    void write_groups_end()
+    {
+        const size_t Gs = groups_open, Gl = std::max<size_t>(groups->loaded.names.size(), 1), seen_groups = group_names.size();
+        LineWriter out(wr);
+        if (a.stream_groups_by == 0) {
+            std::vector<dst_group_cell> cells(Gs * Gl);
+            gpus[0].check(dst_stream_group_summary_result(streams[0], cells.data(), cells.size(), nullptr, nullptr, nullptr, 0, nullptr),
+                          "stream group summary result");
+            for (size_t s = 0; s < seen_groups; ++s)
+                for (size_t b = 0; b < Gl; ++b) {
+                    out.put(group_names[s]);
+                    out.put('\t');
+                    out.put(groups->loaded.names[b]);
+                    put_group_cell(out, measure, cells[s * Gl + b], groups_within);
+                    out.end_line();
+                }
+        } else {
+            const size_t cap = std::max<size_t>(ref.n * Gs, 1);
+            std::vector<uint32_t> within(cap), summable(cap);
+            std::vector<double> sum(cap);
+            gpus[0].check(dst_stream_group_summary_result(streams[0], nullptr, 0, within.data(), summable.data(), sum.data(), ref.n * Gs,
+                                                          nullptr),
+                          "stream group summary result");
+            for (size_t i = 0; i < ref.n; ++i)
+                for (size_t s = 0; s < seen_groups; ++s) {
+                    const size_t e = i * Gs + s;
+                    out.put(ref.ids[i]);
+                    out.put('\t');
+                    out.put(group_names[s]);
+                    put_group_record(out, summable[e], within[e], sum[e], groups_within);
+                    out.end_line();
+                }
+        }
+        out.finish();
+    }
+
     void run()
     {
+        if (grouped) {
+            std::string header = a.stream_groups_by == 0 ? "group1\tgroup2\tpairs\tcompared" : "sequence\tgroup\tcompared";
+            if (groups_within)
+                header += "\twithin";
+            header += a.stream_groups_by == 0 ? "\tmean\tmin\tmax\n" : "\tmean\n";
+            wr.write(header.data(), header.size());
+        }
         if (summary) {
             const char *header = a.mode == Mode::StreamSummary ? "sequence\twithin\tcompared\tmean\n" : "distance\tpairs\n";
             wr.write(header, std::strlen(header));
@@ -461,7 +582,14 @@ struct StreamRun {
         std::thread reader([this] { read(); });
         const int wire = nibbles ? DST_WIRE_NIBBLES : DST_WIRE_CODES;
         for (size_t g = 0; g < G; ++g)
-            gpus[g].check(a.mode == Mode::StreamSummary
+            gpus[g].check(grouped
+                              ? dst_stream_open_group_summary(
+                                    gpus[g].h, measure, groups_within ? a.stream_groups_within : HUGE_VAL,
+                                    groups_streamed ? DST_STREAM_GROUPS_STREAMED : a.stream_groups_by == 2 ? DST_STREAM_GROUPS_LOADED : 0,
+                                    a.stream_groups_by == 2 ? nullptr : groups->loaded.label.data(),
+                                    a.stream_groups_by == 2 ? 1 : (uint32_t)groups->loaded.names.size(), groups_open, batch_records,
+                                    kDepth, wire, &streams[g])
+                          : a.mode == Mode::StreamSummary
                               ? dst_stream_open_summary(gpus[g].h, measure, a.stream_summary,
                                                         summary_streamed ? DST_STREAM_SUMMARY_STREAMED : DST_STREAM_SUMMARY_LOADED, 0,
                                                         0.0, batch_records, kDepth, wire, &streams[g])
@@ -496,6 +624,11 @@ struct StreamRun {
             write_summary_loaded();
         if (a.mode == Mode::StreamHistogram)
             write_stream_histogram();
+        if (grouped && !groups_streamed)
+            write_groups_end();
+        if (grouped && groups->seen.size() < groups->file->of.size())
+            std::fprintf(stderr, "warning: %s: %zu ids of '%s' are not in the input and were skipped\n", groups->file->flag.c_str(),
+                         groups->file->of.size() - groups->seen.size(), groups->file->path.c_str());
         for (size_t g = 0; g < G; ++g)
             dst_stream_close(streams[g]);
         reader.join();

@@ -27,6 +27,13 @@
 //                       a stretch of kGroupFoldRecs records taken in order of their group (`order`, from the host), again
 //                       with register accumulators flushed on a change; the carry of the low word's add comes from the
 //                       value the atomic returns, as for dst_summary's totals.
+//   group_stream_cols_kernel   a group-summary stream's LOADED side (dst_stream.cpp): group_cols_kernel's
+//                       method on the batch's rectangle, without the triangle.  Tile = kStreamGroupRows streamed rows x
+//                       kStreamGroupCols loaded columns, thread = loaded column j; the tile's rows are ranked by their
+//                       streamed group in LDS and walked in that order, eight loads in flight, register accumulators
+//                       flushed to the kept table's entry (group, j) on a change.  The table is group-major, so a wave's
+//                       64 flushes of one word are 512 adjacent bytes: one lane per line is the slow shape of a global
+//                       atomic.
 #include "dst_device.hpp"
 #include "dst_pair_sum.hpp"
 
@@ -263,6 +270,67 @@ __global__ __launch_bounds__(256) void group_cols_kernel(const uint64_t *__restr
         add_to_entry(s, (uint64_t)j * G + cur, a);
 }
 
+static_assert(kStreamGroupRows <= kStreamGroupCols && kStreamGroupCols == 256, "a thread per column, and one per row to rank");
+constexpr int kStreamGroupUnroll = 8;   // rows whose loads a thread has in flight at once
+
+// A group-summary stream's batch, the loaded side: the n_rows x n_cols matrix (row = streamed record, column = loaded
+// record), tile (tile0 + blockIdx.y, blockIdx.x).  s.row_group: the batch's labels; s.counts / hi / lo: the kept table
+// [G][n_cols], G = s.g_cols the STREAMED group count.  Rows without a group rank last and are not walked.
+template <bool INT>
+__global__ __launch_bounds__(256) void group_stream_cols_kernel(const uint64_t *__restrict__ matrix, uint32_t n_rows, uint32_t n_cols,
+                                                                uint32_t tile0, uint64_t t_bits, int any, GroupState s)
+{
+    __shared__ uint32_t seg_grp[kStreamGroupRows], ord_row[kStreamGroupRows], ord_grp[kStreamGroupRows];
+    const uint64_t first = (uint64_t)(tile0 + blockIdx.y) * kStreamGroupRows;
+    if (first >= n_rows)
+        return;   // (whole workgroups)
+    const uint32_t r0 = (uint32_t)first, rows = min(kStreamGroupRows, n_rows - r0);
+    if (threadIdx.x < kStreamGroupRows)
+        seg_grp[threadIdx.x] = threadIdx.x < rows ? s.row_group[r0 + threadIdx.x] : DST_GROUP_NONE;
+    __syncthreads();
+    if (threadIdx.x < kStreamGroupRows) {   // (every slot of the order is written: the rows past the batch rank last)
+        const uint32_t mine = seg_grp[threadIdx.x];
+        uint32_t rank = 0;
+        for (uint32_t u = 0; u < kStreamGroupRows; ++u) {
+            const uint32_t other = seg_grp[u];
+            rank += (other < mine || (other == mine && u < threadIdx.x)) ? 1u : 0u;
+        }
+        ord_row[rank] = threadIdx.x;
+        ord_grp[rank] = mine;
+    }
+    __syncthreads();
+    const uint64_t j64 = (uint64_t)blockIdx.x * kStreamGroupCols + threadIdx.x;
+    if (j64 >= n_cols)
+        return;
+    const uint64_t t_key = nn_key<INT>(t_bits);
+    const uint64_t *p = matrix + (uint64_t)r0 * n_cols + j64;
+    Acc a{};
+    uint32_t cur = DST_GROUP_NONE;
+    for (uint32_t k = 0; k < kStreamGroupRows; k += kStreamGroupUnroll) {   // (uniform)
+        if (ord_grp[k] == DST_GROUP_NONE)
+            break;
+        uint64_t v[kStreamGroupUnroll];
+#pragma unroll
+        for (int u = 0; u < kStreamGroupUnroll; ++u)   // (a row with a group lies inside the batch)
+            v[u] = ord_grp[k + u] != DST_GROUP_NONE ? __builtin_nontemporal_load(p + (uint64_t)ord_row[k + u] * n_cols) : 0;
+#pragma unroll
+        for (int u = 0; u < kStreamGroupUnroll; ++u) {
+            const uint32_t gi = ord_grp[k + u];   // (uniform)
+            if (gi == DST_GROUP_NONE)
+                break;
+            if (gi != cur) {
+                if (cur != DST_GROUP_NONE)
+                    add_to_entry(s, (uint64_t)cur * n_cols + j64, a);
+                a = Acc{};
+                cur = gi;
+            }
+            add_pair<INT>(a, v[u], t_key, any != 0);
+        }
+    }
+    if (cur != DST_GROUP_NONE)
+        add_to_entry(s, (uint64_t)cur * n_cols + j64, a);
+}
+
 // one record's entry added to 128-bit running words (high, low) of a thread: S = hi 2^32 + lo as a 128-bit integer
 struct Wide {
     unsigned long long links, summable;
@@ -393,6 +461,29 @@ hipError_t launch_group_cols(int measure, const uint64_t *slab, uint64_t out_bas
             return e;
     }
     return hipSuccess;
+}
+
+hipError_t launch_group_stream_cols(int measure, const uint64_t *matrix, uint64_t n_records, uint64_t n_loaded, uint64_t t_bits,
+                                    bool any, const GroupBuffers &b, hipStream_t stream)
+{
+    if (n_records == 0 || n_loaded == 0)
+        return hipSuccess;
+    if (n_records > 0xFFFFFFFFull || n_loaded > 0xFFFFFFFFull || b.g_cols == 0 || b.g_cols > DST_GROUPS_MAX)
+        return hipErrorInvalidValue;
+    const bool int_payload = measure == DST_N || measure == DST_N_HIGH;
+    const unsigned col_tiles = (unsigned)((n_loaded + kStreamGroupCols - 1) / kStreamGroupCols);
+    const uint64_t row_tiles = (n_records + kStreamGroupRows - 1) / kStreamGroupRows;
+    const GroupState s = state_of(b);
+    return for_row_grids(0, row_tiles, [&](uint64_t tile0, unsigned tiles) {
+        const dim3 grid(col_tiles, tiles);
+        if (int_payload)
+            hipLaunchKernelGGL(group_stream_cols_kernel<true>, grid, dim3(256), 0, stream, matrix, (uint32_t)n_records,
+                               (uint32_t)n_loaded, (uint32_t)tile0, t_bits, any ? 1 : 0, s);
+        else
+            hipLaunchKernelGGL(group_stream_cols_kernel<false>, grid, dim3(256), 0, stream, matrix, (uint32_t)n_records,
+                               (uint32_t)n_loaded, (uint32_t)tile0, t_bits, any ? 1 : 0, s);
+        return hipGetLastError();
+    });
 }
 
 hipError_t launch_group_fold(const GroupBuffers &b, uint64_t assigned, hipStream_t stream)

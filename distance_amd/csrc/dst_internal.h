@@ -589,6 +589,15 @@ hipError_t launch_group_cols(int measure, const uint64_t *slab, uint64_t out_bas
                              uint64_t t_bits, bool any, const GroupBuffers &b, hipStream_t stream);
 // the table of the first `assigned` records of b.order into the cells
 hipError_t launch_group_fold(const GroupBuffers &b, uint64_t assigned, hipStream_t stream);
+// A group-summary stream's LOADED side (dst_stream.cpp): one tile pass over the batch's n_records x n_loaded
+// matrix of DST_OUT_DISTANCE payloads, entry s n_loaded + i.  A workgroup takes a tile of kStreamGroupRows rows x
+// kStreamGroupCols columns, a thread one loaded column, the rows in order of their streamed group.  b.row_group: the
+// batch's labels; b.counts / hi / lo: the kept table [b.g_cols][n_loaded], group-major (a wave's adds of one word are
+// adjacent), b.g_cols the STREAMED group count; nothing else of b is read.  Adds only.
+constexpr uint32_t kStreamGroupRows = 64;    // mirrored as STREAM_GROUPS_ROWS in distance_amd/_lib.py
+constexpr uint32_t kStreamGroupCols = 256;   // ... and STREAM_GROUPS_COLS
+hipError_t launch_group_stream_cols(int measure, const uint64_t *matrix, uint64_t n_records, uint64_t n_loaded, uint64_t t_bits,
+                                    bool any, const GroupBuffers &b, hipStream_t stream);
 
 // ---- minimum spanning forest (dst_mst.hip, driven by dst_mst in dst_analysis.cpp) -------------------------------------
 // Boruvka rounds: every round runs each row slab of the triangle into the DST_OUT_DISTANCE scratch (as dst_clusters) and

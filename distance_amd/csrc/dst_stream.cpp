@@ -40,6 +40,13 @@
 // the stream's own kept state, zeroed at open; the batch's records' words are the slot's, zeroed in front of the kernel,
 // copied to the slot's page-locked block on the copy-out stream and converted at collect.  With bins, dst_summary's
 // histogram pass follows into the kept histogram, with totals of its own that the result compares with the tile pass'.
+//
+// A group-summary stream (dst_stream_open_group_summary) is the sixth: dst_group_summary on the rectangle
+// (every record so far) x (the loaded set).  The batch's labels travel in the slot's page-locked label block, with the
+// batch's assigned records in order of their group behind them (a counting sort at submit).  Behind the pair kernel, on the
+// compute stream: dst_group_summary's row pass into the slot's table (zeroed in front of it) and the kept cells' NaN / min /
+// max, its fold of that table into the kept cells' links / summable / 128-bit sum, and with LOADED group_stream_cols_kernel
+// into the kept table of the loaded records (group-major on the device, transposed by the result call).  The kept state is the stream's own, zeroed once at open.
 #include <algorithm>
 #include <cstring>
 #include <cmath>
@@ -73,6 +80,11 @@ struct dst_stream {
         uint64_t window_first = ~0ull;       // the first link of the window the page-locked buffer holds (~0: none)
         Grown<unsigned long long> d_bad;
         Grown<unsigned long long, true> h_bad;
+        // a group-summary stream: max_records labels, then the batch's assigned records in order of their group;
+        // d_lists = the batch's table (counts, hi, lo planes), h_lists = the same and the split counts behind them
+        Grown<uint32_t, true> h_labels;
+        Grown<uint32_t> d_labels;
+        uint64_t assigned = 0;               // of the submitted batch
         DeviceSet set;
         Event h2d, computed, landed;   // (made by their first record, in the slot's first submit)
         size_t n = 0;
@@ -114,11 +126,19 @@ struct dst_stream {
     size_t sum_state_bytes = 0;
     SummaryBuffers sum_kept{};        // within / summable / hi / lo: NULL without LOADED; hist; tot: the tile kernel's
     SummaryBuffers sum_hist{};        // hist: sum_kept's; tot: the histogram pass' own
+    // group-summary streams (what, t_bits, any_links, submitted as a summary stream's).  The kept state in d_lists: the
+    // loaded labels, the cells, the loaded records' table (LOADED)
+    uint32_t g_loaded = 0, g_streamed = 0;
+    GroupBuffers grp_kept{};          // col_group: the loaded labels; cell; counts / hi / lo: [g_streamed][n_loaded] or NULL
+    size_t grp_state_bytes = 0, grp_cells_at = 0;
+    std::vector<uint64_t> loaded_size, streamed_size;   // records per group, the streamed side's so far
+    uint64_t loaded_assigned = 0;
 };
 
 constexpr int kLinksStream = 2;       // dst_stream::closest of a links stream (after the two dst_closest_side values)
 constexpr int kWindowClosestStream = 3;   // ... and of a window-closest stream
 constexpr int kSummaryStream = 4;     // ... and of a summary stream
+constexpr int kGroupSummaryStream = 5;   // ... and of a group-summary stream
 
 namespace {
 
@@ -177,6 +197,31 @@ size_t summary_state_layout(void *base, uint64_t n_loaded, bool loaded, uint32_t
         hist.tot = p + bins + kSummaryTotals;
     }
     return records + ((size_t)bins + 2 * kSummaryTotals) * 8;
+}
+
+// a group-summary stream's table of `entries` (record, group) entries in one block of 24 bytes per entry: counts, hi, lo
+size_t table_layout(void *base, uint64_t entries, GroupBuffers &b)
+{
+    if (base) {
+        char *p = static_cast<char *>(base);
+        b.counts = reinterpret_cast<uint64_t *>(p);
+        b.hi = reinterpret_cast<int64_t *>(p + entries * 8);
+        b.lo = reinterpret_cast<uint64_t *>(p + entries * 16);
+    }
+    return (size_t)(entries * 24);   // (the size alone with base == NULL)
+}
+
+// ... and its kept state: the loaded labels, the cells' planes from cells_at, the loaded records' table (LOADED)
+size_t group_state_layout(void *base, uint64_t n_loaded, uint64_t cells, uint64_t table_entries, GroupBuffers &b, size_t &cells_at)
+{
+    cells_at = (size_t)((n_loaded * 4 + 255) / 256 * 256);
+    const size_t cell_bytes = (size_t)(cells * kGroupCellWords * 8);
+    if (base) {
+        char *p = static_cast<char *>(base);
+        b.col_group = reinterpret_cast<uint32_t *>(p);
+        b.cell = reinterpret_cast<uint64_t *>(p + cells_at);
+    }
+    return cells_at + cell_bytes + table_layout(base ? static_cast<char *>(base) + cells_at + cell_bytes : nullptr, table_entries, b);
 }
 
 void destroy(dst_stream *s)
@@ -367,6 +412,85 @@ int dst_stream_open_summary(dst_ctx *ctx, int measure, double threshold, int wha
     if (rc || e != hipSuccess) {
         destroy(s);
         return rc ? rc : fail_hip(ctx, e, "dst_stream_open_summary");
+    }
+    *out = s;
+    return DST_OK;
+}
+
+int dst_stream_open_group_summary(dst_ctx *ctx, int measure, double threshold, int what, const uint32_t *loaded_group,
+                                  uint32_t n_loaded_groups, uint32_t n_streamed_groups, size_t max_records, int depth, int wire,
+                                  dst_stream **out)
+{
+    if (!ctx || !out)
+        return DST_ERR_ARG;
+    *out = nullptr;
+    if (measure < DST_N || measure > DST_TN93)
+        return fail(ctx, DST_ERR_ARG, "unknown measure");
+    if (wire != DST_WIRE_CODES && wire != DST_WIRE_NIBBLES)
+        return fail(ctx, DST_ERR_ARG, "unknown wire format");
+    if (std::isnan(threshold))
+        return fail(ctx, DST_ERR_ARG, "threshold is NaN");
+    if (what & ~(DST_STREAM_GROUPS_LOADED | DST_STREAM_GROUPS_STREAMED))
+        return fail(ctx, DST_ERR_ARG, "unknown bits in what");
+    if (n_loaded_groups == 0 || n_loaded_groups > DST_GROUPS_MAX || n_streamed_groups == 0 || n_streamed_groups > DST_GROUPS_MAX)
+        return fail(ctx, DST_ERR_ARG, "a group count must be between 1 and " + std::to_string(DST_GROUPS_MAX));
+    if (!loaded_group && n_loaded_groups != 1)
+        return fail(ctx, DST_ERR_ARG, "a null loaded_group puts every loaded record in group 0: n_loaded_groups must be 1");
+    dst_stream *s = nullptr;
+    int rc = open_stream(ctx, measure, DST_OUT_DISTANCE, max_records, depth, wire, kGroupSummaryStream, 0, &s);
+    if (rc)
+        return rc;
+    const uint64_t n_loaded = s->n_loaded;
+    const uint32_t Gl = n_loaded_groups, Gs = n_streamed_groups;
+    if (loaded_group) {
+        rc = group_labels(ctx, loaded_group, n_loaded, Gl, "loaded", s->loaded_size);
+        if (rc) {
+            destroy(s);
+            return rc;
+        }
+    } else
+        s->loaded_size.assign(1, n_loaded);
+    for (uint64_t size : s->loaded_size)
+        s->loaded_assigned += size;
+    s->streamed_size.assign(Gs, 0);
+    s->what = what;
+    s->g_loaded = Gl;
+    s->g_streamed = Gs;
+    s->any_links = threshold_payload(measure, threshold, s->t_bits);
+    const bool loaded = (what & DST_STREAM_GROUPS_LOADED) != 0, streamed = (what & DST_STREAM_GROUPS_STREAMED) != 0;
+    const char *const name = "group-summary stream";
+    // the kept state, zeroed once; per slot the batch's labels and order, its table, and (STREAMED) the table page-locked
+    const uint64_t cells = (uint64_t)Gs * Gl, kept_entries = loaded ? n_loaded * Gs : 0;
+    s->grp_state_bytes = group_state_layout(nullptr, n_loaded, cells, kept_entries, s->grp_kept, s->grp_cells_at);
+    rc = s->d_lists.grow(ctx, s->grp_state_bytes, name);
+    const uint64_t batch_entries = (uint64_t)max_records * Gl;
+    GroupBuffers none{};
+    for (auto &sl : s->slots) {
+        if (!rc)
+            rc = sl.h_labels.grow(ctx, max_records * 8, name);
+        if (!rc)
+            rc = sl.d_labels.grow(ctx, max_records * 8, name);
+        if (!rc)
+            rc = sl.d_lists.grow(ctx, table_layout(nullptr, batch_entries, none), name);
+        if (!rc && streamed)
+            rc = sl.h_lists.grow(ctx, table_layout(nullptr, batch_entries, none) + (size_t)batch_entries * 8, name);
+    }
+    hipError_t e = hipSuccess;
+    if (!rc) {
+        group_state_layout(s->d_lists, n_loaded, cells, kept_entries, s->grp_kept, s->grp_cells_at);
+        if (!loaded)
+            s->grp_kept.counts = nullptr, s->grp_kept.hi = nullptr, s->grp_kept.lo = nullptr;
+        s->grp_kept.g_rows = Gs;
+        s->grp_kept.g_cols = Gl;
+        e = hipMemsetAsync(s->d_lists, 0, s->grp_state_bytes, s->s_compute);
+        if (e == hipSuccess) e = hipMemsetAsync(s->grp_kept.cell + 5 * cells, 0xFF, cells * 8, s->s_compute);   // (the min keys: none yet)
+        if (e == hipSuccess && loaded_group && n_loaded)   // (pageable memory: the copy has read it when the call returns)
+            e = hipMemcpyAsync(s->grp_kept.col_group, loaded_group, n_loaded * 4, hipMemcpyHostToDevice, s->s_compute);
+        if (e == hipSuccess) e = hipStreamSynchronize(s->s_compute);
+    }
+    if (rc || e != hipSuccess) {
+        destroy(s);
+        return rc ? rc : fail_hip(ctx, e, "dst_stream_open_group_summary");
     }
     *out = s;
     return DST_OK;
@@ -617,6 +741,8 @@ int dst_stream_acquire(dst_stream *s, uint8_t **codes, size_t *pitch, uint32_t *
     if (sl.landed && sl.state == 3)
         HIP_TRY(s->ctx, hipEventSynchronize(sl.landed));
     sl.state = 1;
+    if (s->closest == kGroupSummaryStream)
+        std::memset(sl.h_labels.ptr, 0, s->max_records * 4);   // (every record in streamed group 0 until the caller says otherwise)
     s->acquired = (int)(s->next_acquire % s->slots.size());
     *codes = sl.h_in;
     *pitch = s->pitch;
@@ -637,7 +763,8 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
     DeviceSet &loaded = ctx->set[0];
     if (!loaded.loaded || loaded.len != s->len || (s->closest >= 0 && loaded.n != s->n_loaded))
         return fail(ctx, DST_ERR_STATE, "the loaded set changed while the stream was open");
-    const bool summary = s->closest == kSummaryStream;
+    const bool grouped = s->closest == kGroupSummaryStream;
+    const bool summary = s->closest == kSummaryStream || grouped;   // (what the two kinds share)
     if (s->poisoned && summary)
         return fail(ctx, DST_ERR_STATE, "a batch of this summary stream held an invalid code: its sums are not trustworthy");
     if (s->poisoned)
@@ -650,8 +777,30 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
     if (windowed)
         use_base_counts = 0;   // per-window counts cannot come from the caller: counted by code on the device
     auto &sl = s->slots[(size_t)s->acquired];
+    // a group-summary stream: the labels are checked here, before anything changes; the batch's assigned records in order
+    // of their group (a counting sort) go behind them
+    std::vector<uint64_t> batch_size;
+    if (grouped) {
+        const uint32_t *labels = sl.h_labels;
+        if (int rc = group_labels(ctx, labels, n_records, s->g_streamed, "streamed", batch_size))
+            return rc;
+        std::vector<uint64_t> next(s->g_streamed, 0);
+        for (uint32_t a = 1; a < s->g_streamed; ++a)
+            next[a] = next[a - 1] + batch_size[a - 1];
+        uint32_t *order = sl.h_labels + s->max_records;
+        for (size_t x = 0; x < n_records; ++x)
+            if (labels[x] != DST_GROUP_NONE)
+                order[next[labels[x]]++] = (uint32_t)x;
+        sl.assigned = next[s->g_streamed - 1];
+    }
     HIP_TRY(ctx, hipSetDevice(ctx->device));
     // copy-in: the batch's bytes (and the caller's base counts)
+    if (grouped) {
+        HIP_TRY(ctx, hipMemcpyAsync(sl.d_labels, sl.h_labels, n_records * 4, hipMemcpyHostToDevice, s->s_in));
+        if (sl.assigned)
+            HIP_TRY(ctx, hipMemcpyAsync(sl.d_labels + s->max_records, sl.h_labels + s->max_records, sl.assigned * 4,
+                                        hipMemcpyHostToDevice, s->s_in));
+    }
     if (s->len)
         HIP_TRY(ctx, hipMemcpyAsync(sl.d_in, sl.h_in, n_records * s->pitch, hipMemcpyHostToDevice, s->s_in));
     if (use_base_counts)
@@ -707,8 +856,8 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
         s->last_collected = -1;   // the collected batch's links were valid until this submit
     }
     // a summary stream: the tile pass for both sides and the totals, then the histogram pass, behind the pair kernel
-    const bool sum_streamed = summary && (s->what & DST_STREAM_SUMMARY_STREAMED);
-    if (summary) {
+    const bool sum_streamed = s->closest == kSummaryStream && (s->what & DST_STREAM_SUMMARY_STREAMED);
+    if (s->closest == kSummaryStream) {
         const uint64_t *matrix = static_cast<const uint64_t *>(sl.d_out.ptr);
         SummaryBuffers batch{};
         if (sum_streamed)
@@ -719,6 +868,31 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
         if (s->bins)
             HIP_TRY(ctx, launch_summary_hist(s->measure, matrix, (uint64_t)n_records * s->n_loaded, s->bins, s->width_q, s->t_bits,
                                              s->any_links, true, s->sum_hist, s->s_compute));
+        s->last_collected = -1;   // the collected batch's results were valid until this submit
+    }
+    // a group-summary stream: dst_group_summary's row pass and its fold into the kept cells, then the loaded side
+    const bool grp_streamed = grouped && (s->what & DST_STREAM_GROUPS_STREAMED);
+    const uint64_t batch_entries = grouped ? (uint64_t)n_records * s->g_loaded : 0;
+    if (grouped) {
+        const uint64_t *matrix = static_cast<const uint64_t *>(sl.d_out.ptr);
+        const bool cells_run = s->n_loaded != 0 && s->loaded_assigned != 0;
+        GroupBuffers b = s->grp_kept;   // col_group, cell, g_rows, g_cols
+        b.row_group = sl.d_labels;
+        b.order = sl.d_labels + s->max_records;
+        if (grp_streamed || cells_run)
+            HIP_TRY(ctx, hipMemsetAsync(sl.d_lists, 0, table_layout(sl.d_lists, batch_entries, b), s->s_compute));
+        if (cells_run) {
+            static const bool no_aggregation = std::getenv("DST_GROUPS_NO_AGGREGATION") != nullptr;   // 
+            HIP_TRY(ctx, launch_group_rows(s->measure, false, matrix, 0, s->n_loaded, 0, n_records, s->t_bits, s->any_links,
+                                           !no_aggregation, b, s->s_compute));
+            HIP_TRY(ctx, launch_group_fold(b, sl.assigned, s->s_compute));
+        }
+        if ((s->what & DST_STREAM_GROUPS_LOADED) && sl.assigned) {
+            GroupBuffers t = s->grp_kept;   // the kept table, keyed by the streamed group
+            t.row_group = sl.d_labels;
+            t.g_cols = s->g_streamed;
+            HIP_TRY(ctx, launch_group_stream_cols(s->measure, matrix, n_records, s->n_loaded, s->t_bits, s->any_links, t, s->s_compute));
+        }
         s->last_collected = -1;   // the collected batch's results were valid until this submit
     }
     HIP_TRY(ctx, sl.computed.record(s->s_compute));
@@ -739,6 +913,9 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
     } else if (sum_streamed) {
         SummaryBuffers none{};
         HIP_TRY(ctx, hipMemcpyAsync(sl.h_lists, sl.d_lists, records_layout(nullptr, n_records, none), hipMemcpyDeviceToHost, s->s_out));
+    } else if (grp_streamed) {
+        GroupBuffers none{};
+        HIP_TRY(ctx, hipMemcpyAsync(sl.h_lists, sl.d_lists, table_layout(nullptr, batch_entries, none), hipMemcpyDeviceToHost, s->s_out));
     }
     HIP_TRY(ctx, sl.landed.record(s->s_out));
     if (s->closest == DST_CLOSEST_FOR_LOADED || windowed) {
@@ -747,6 +924,8 @@ int dst_stream_submit(dst_stream *s, size_t n_records, int use_base_counts)
     }
     if (summary)
         s->submitted += n_records;
+    for (uint32_t a = 0; grouped && a < s->g_streamed; ++a)
+        s->streamed_size[a] += batch_size[a];
     sl.n = n_records;
     sl.state = 2;
     s->acquired = -1;
@@ -797,6 +976,22 @@ int dst_stream_collect(dst_stream *s, size_t *n_records, const void **results)
         for (size_t x = 0; x < sl.n; ++x) {
             const double v = summary_value((__int128)h.hi[x] * ((__int128)1 << 32) + (__int128)h.lo[x], int_payload);
             std::memcpy(h.hi + x, &v, 8);
+        }
+    }
+    if (s->closest == kGroupSummaryStream && (s->what & DST_STREAM_GROUPS_STREAMED)) {
+        // the batch's table: the packed counts split into the two arrays behind the planes, the 128-bit sums converted
+        // once into the place of their high words
+        const uint64_t entries = (uint64_t)sl.n * s->g_loaded, room = (uint64_t)s->max_records * s->g_loaded;
+        uint32_t *within = reinterpret_cast<uint32_t *>(static_cast<char *>(sl.h_lists.ptr) + room * 24);
+        uint32_t *summable = within + room;
+        GroupBuffers got{};
+        table_layout(sl.h_lists, entries, got);   // (as the copy left it: planes of the batch's own entries)
+        const bool int_payload = s->measure == DST_N || s->measure == DST_N_HIGH;
+        for (uint64_t x = 0; x < entries; ++x) {
+            within[x] = (uint32_t)(got.counts[x] >> 32);
+            summable[x] = (uint32_t)got.counts[x];
+            const double v = summary_value((__int128)got.hi[x] * ((__int128)1 << 32) + (__int128)got.lo[x], int_payload);
+            std::memcpy(got.hi + x, &v, 8);
         }
     }
     *n_records = sl.n;
@@ -894,6 +1089,126 @@ int dst_stream_summary_result(dst_stream *s, uint64_t *hist, uint32_t *within, u
     t.sum = summary_value(all, int_payload);
     if (totals)
         *totals = t;
+    if (records)
+        *records = s->submitted;
+    return DST_OK;
+}
+
+int dst_stream_group_labels(dst_stream *s, uint32_t **labels)
+{
+    if (!s)
+        return DST_ERR_ARG;
+    dst_ctx *ctx = s->ctx;
+    if (labels)
+        *labels = nullptr;
+    if (s->closest != kGroupSummaryStream)
+        return fail(ctx, DST_ERR_ARG, "not a group-summary stream");
+    if (!labels)
+        return fail(ctx, DST_ERR_ARG, "null labels pointer");
+    if (s->acquired < 0)
+        return fail(ctx, DST_ERR_STATE, "no buffer acquired: the label block is valid between dst_stream_acquire and dst_stream_submit");
+    *labels = s->slots[(size_t)s->acquired].h_labels;
+    return DST_OK;
+}
+
+int dst_stream_group_summary_batch(dst_stream *s, size_t *n_records, const uint32_t **within, const uint32_t **summable,
+                                   const double **sum)
+{
+    if (!s)
+        return DST_ERR_ARG;
+    dst_ctx *ctx = s->ctx;
+    if (s->closest != kGroupSummaryStream)
+        return fail(ctx, DST_ERR_ARG, "not a group-summary stream");
+    if (!(s->what & DST_STREAM_GROUPS_STREAMED))
+        return fail(ctx, DST_ERR_ARG, "the stream was opened without DST_STREAM_GROUPS_STREAMED");
+    if (!n_records)
+        return fail(ctx, DST_ERR_ARG, "null n_records pointer");
+    *n_records = 0;
+    if (s->poisoned)
+        return fail(ctx, DST_ERR_STATE, "a batch of this summary stream held an invalid code: its sums are not trustworthy");
+    if (s->last_collected < 0 || s->slots[(size_t)s->last_collected].state != 3)
+        return fail(ctx, DST_ERR_STATE, "no collected batch: its results are valid from dst_stream_collect to the next submit");
+    const auto &sl = s->slots[(size_t)s->last_collected];
+    const uint64_t entries = (uint64_t)sl.n * s->g_loaded, room = (uint64_t)s->max_records * s->g_loaded;
+    GroupBuffers h{};
+    table_layout(sl.h_lists, entries, h);
+    const uint32_t *w = reinterpret_cast<const uint32_t *>(static_cast<const char *>(sl.h_lists.ptr) + room * 24);
+    *n_records = sl.n;
+    if (within)
+        *within = w;
+    if (summable)
+        *summable = w + room;
+    if (sum)
+        *sum = reinterpret_cast<const double *>(h.hi);   // (converted at collect)
+    return DST_OK;
+}
+
+int dst_stream_group_summary_result(dst_stream *s, dst_group_cell *cells, size_t cells_cap, uint32_t *rec_within,
+                                    uint32_t *rec_summable, double *rec_sum, size_t rec_cap, uint64_t *records)
+{
+    if (!s)
+        return DST_ERR_ARG;
+    dst_ctx *ctx = s->ctx;
+    if (records)
+        *records = 0;
+    if (s->closest != kGroupSummaryStream)
+        return fail(ctx, DST_ERR_ARG, "not a group-summary stream");
+    const bool loaded = (s->what & DST_STREAM_GROUPS_LOADED) != 0, per_record = rec_within || rec_summable || rec_sum;
+    if (!loaded && per_record)
+        return fail(ctx, DST_ERR_ARG, "the stream was opened without DST_STREAM_GROUPS_LOADED: the per-record pointers must be NULL");
+    if (s->poisoned)
+        return fail(ctx, DST_ERR_STATE, "a batch of this summary stream held an invalid code: its sums are not trustworthy");
+    if (s->in_flight != 0)
+        return fail(ctx, DST_ERR_STATE, "collect every submitted batch before reading the summary");
+    const uint32_t Gs = s->g_streamed, Gl = s->g_loaded;
+    const size_t n_cells = (size_t)Gs * Gl;
+    const uint64_t n_rec = (uint64_t)s->n_loaded * Gs;
+    if (cells && cells_cap < n_cells)
+        return fail(ctx, DST_ERR_CAPACITY, "cells_cap is below " + std::to_string(n_cells) + " entries (streamed groups x loaded groups)");
+    if (per_record && rec_cap < n_rec)
+        return fail(ctx, DST_ERR_CAPACITY, "rec_cap is below " + std::to_string(n_rec) + " entries (the loaded records x streamed groups)");
+    // every batch is collected, so the compute stream is idle: the cells, and the table behind them when it is wanted, back
+    // in one copy
+    HIP_TRY(ctx, hipSetDevice(ctx->device));
+    const size_t back = (per_record ? s->grp_state_bytes : s->grp_cells_at + n_cells * kGroupCellWords * 8) - s->grp_cells_at;
+    std::vector<char> host(back);
+    HIP_TRY(ctx, hipMemcpyAsync(host.data(), static_cast<const char *>(s->d_lists.ptr) + s->grp_cells_at, back, hipMemcpyDeviceToHost,
+                                s->s_compute));
+    HIP_TRY(ctx, hipStreamSynchronize(s->s_compute));
+    const bool int_payload = s->measure == DST_N || s->measure == DST_N_HIGH;
+    const uint64_t *cell = reinterpret_cast<const uint64_t *>(host.data());
+    if (cells) {
+        const uint64_t none = int_payload ? 0 : 0x7FF8000000000000ull;
+        const uint64_t *nan = cell, *links = cell + n_cells, *summ = cell + 2 * n_cells, *high = cell + 3 * n_cells,
+                       *low = cell + 4 * n_cells, *kmin = cell + 5 * n_cells, *kmax = cell + 6 * n_cells;
+        for (uint32_t a = 0; a < Gs; ++a)
+            for (uint32_t g = 0; g < Gl; ++g) {
+                const size_t c = (size_t)a * Gl + g;
+                dst_group_cell out{s->streamed_size[a] * s->loaded_size[g], nan[c], summ[c], links[c], 0.0, none, none};
+                if (out.nan_pairs + out.summable_pairs > out.pairs || out.links > out.pairs)
+                    return fail(ctx, DST_ERR_STATE, "group-summary stream: internal error, a cell counts more than its pairs");
+                out.sum = summary_value((__int128)(((unsigned __int128)high[c] << 64) | low[c]), int_payload);
+                if (out.pairs > out.nan_pairs) {
+                    out.min_bits = payload_of_key(kmin[c], int_payload);
+                    out.max_bits = payload_of_key(kmax[c], int_payload);
+                }
+                cells[c] = out;
+            }
+    }
+    if (per_record) {
+        GroupBuffers h{};
+        table_layout(host.data() + n_cells * kGroupCellWords * 8, n_rec, h);
+        for (uint64_t i = 0; i < s->n_loaded; ++i)   // (the kept table is group-major: entry g n_loaded + i)
+            for (uint32_t g = 0; g < Gs; ++g) {
+                const uint64_t e = i * Gs + g, at = (uint64_t)g * s->n_loaded + i;
+                if (rec_within)
+                    rec_within[e] = (uint32_t)(h.counts[at] >> 32);
+                if (rec_summable)
+                    rec_summable[e] = (uint32_t)h.counts[at];
+                if (rec_sum)
+                    rec_sum[e] = summary_value((__int128)h.hi[at] * ((__int128)1 << 32) + (__int128)h.lo[at], int_payload);
+            }
+    }
     if (records)
         *records = s->submitted;
     return DST_OK;

@@ -12,7 +12,7 @@ import ctypes as C
 import numpy as np
 
 from ._lib import (ALLGATHER_FN, GROUP_NONE, LINKS_CHUNK, LINKS_SINK, LINKS_TALLIES, LINKS_VALUES, SLAB_SINK,
-                   STREAM_SUMMARY_LOADED, STREAM_SUMMARY_STREAMED, DistanceError,
+                   STREAM_GROUPS_LOADED, STREAM_GROUPS_STREAMED, STREAM_SUMMARY_LOADED, STREAM_SUMMARY_STREAMED, DistanceError,
                    GroupCell, LaunchInfo, PairsInfo, SummaryTotals, load)
 
 MEASURES = {"n": 0, "n_high": 1, "raw": 2, "jc69": 3, "k80": 4, "tn93": 5}
@@ -469,6 +469,16 @@ class Engine:
         loaded: every loaded record's `within`, `summable` and `sum` over the whole stream (result()); streamed: the same
         for every streamed record over the loaded set, per batch (pop()); bins: the histogram of every pair so far."""
         return SummaryStream(self, measure, max_records, threshold, loaded, streamed, bins, width, depth, nibbles)
+
+    def group_summary_stream(self, measure, max_records: int, loaded_groups=None, n_loaded_groups=None,
+                             n_streamed_groups: int = 1, threshold: float = float("inf"), loaded: bool = False,
+                             streamed: bool = False, depth: int = 3, nibbles: bool = False) -> "GroupSummaryStream":
+        """A stream that keeps group_summary()'s cells of (every record so far) x (the loaded set) instead of the result
+        matrix (dst_stream_open_group_summary).  loaded_groups: one label per loaded record as for group_summary() (None:
+        all in group 0); the streamed records' labels come with every push().  streamed: every batch's records' table over
+        the loaded groups (pop()); loaded: every loaded record's table over the streamed groups (result())."""
+        return GroupSummaryStream(self, measure, max_records, loaded_groups, n_loaded_groups, n_streamed_groups, threshold,
+                                  loaded, streamed, depth, nibbles)
 
     def run_slabs(self, measure, sink, max_pairs: int, square: bool = True, row_slot: int = 0, col_slot: int = 1,
                   tallies: bool = False):
@@ -1438,3 +1448,111 @@ class SummaryStream(Stream):
         if self.bins:
             out["hist"] = hist[:self.bins]
         return out
+
+
+class GroupSummaryStream(Stream):
+    """dst_stream_open_group_summary: a Stream whose batches leave group_summary()'s sums behind instead of the result
+    matrix.  push() takes the batch's labels (groups; None: all in streamed group 0; -1: no group).  pop() returns the batch's
+    record count, or with streamed=True (n_records, within, summable, sum), each (n_records, G_l), as copies: the batch's
+    records over the loaded groups.  result() is group_summary()'s cell keys of shape (G_s, G_l) over every record so far
+    plus `records`, and with loaded=True `rec_within` / `rec_summable` / `rec_sum` of shape (n_loaded, G_s)."""
+
+    def __init__(self, eng: Engine, measure, max_records: int, loaded_groups=None, n_loaded_groups=None,
+                 n_streamed_groups: int = 1, threshold: float = float("inf"), loaded: bool = False, streamed: bool = False,
+                 depth: int = 3, nibbles: bool = False):
+        self.threshold, self.loaded, self.streamed = float(threshold), bool(loaded), bool(streamed)
+        n_loaded, _ = eng.set_info(0)
+        if loaded_groups is None:
+            self._labels, self.n_loaded_groups = None, 1 if n_loaded_groups is None else int(n_loaded_groups)
+        else:
+            g = np.asarray(loaded_groups)
+            if g.ndim != 1 or len(g) != n_loaded or not np.issubdtype(g.dtype, np.integer):
+                raise ValueError(f"loaded_groups must be a 1-D integer array with one label per loaded record ({n_loaded})")
+            self._labels = _group_labels_u32(g, "loaded_groups")
+            if n_loaded_groups is None:
+                assigned = self._labels[self._labels != GROUP_NONE]
+                n_loaded_groups = int(assigned.max()) + 1 if len(assigned) else 1
+            self.n_loaded_groups = int(n_loaded_groups)
+        self.n_streamed_groups = int(n_streamed_groups)
+        for count in (self.n_loaded_groups, self.n_streamed_groups):
+            if not 0 <= count <= GROUP_NONE:
+                raise ValueError("a group count must fit 32 bits")
+        super().__init__(eng, measure, max_records, depth, False, nibbles)
+
+    def _open(self):
+        h = C.c_void_p()
+        what = (STREAM_GROUPS_LOADED if self.loaded else 0) | (STREAM_GROUPS_STREAMED if self.streamed else 0)
+        self._eng._check(self._lib.dst_stream_open_group_summary(
+            self._eng._h, self._m, self.threshold, what, None if self._labels is None else self._labels.ctypes.data,
+            self.n_loaded_groups, self.n_streamed_groups, self.max_records, self.depth, int(self.nibbles), C.byref(h)))
+        return h
+
+    def labels(self) -> np.ndarray:
+        """The acquired buffer's label block (max_records,) uint32, zero-filled by buffer() (dst_stream_group_labels)"""
+        p = C.c_void_p()
+        self._eng._check(self._lib.dst_stream_group_labels(self._h, C.byref(p)))
+        return np.ctypeslib.as_array(C.cast(p, C.POINTER(C.c_uint32)), shape=(self.max_records,))
+
+    def push(self, codes: np.ndarray, counts=None, groups=None):
+        buf, cbuf = self.buffer()
+        buf[:len(codes)] = self.to_nibbles(codes) if self.nibbles else codes
+        if counts is not None:
+            cbuf[:len(codes)] = counts
+        if groups is not None:
+            g = np.asarray(groups)
+            if g.ndim != 1 or len(g) != len(codes) or not np.issubdtype(g.dtype, np.integer):
+                raise ValueError(f"groups must be a 1-D integer array with one label per record ({len(codes)})")
+            self.labels()[:len(codes)] = _group_labels_u32(g, "groups")
+        self.submit(len(codes), counts is not None)
+
+    def group_summary_batch(self):
+        """(n_records, within, summable, sum) of the batch pop() collected last: copies (dst_stream_group_summary_batch)"""
+        n, wp, sp, dp = C.c_size_t(), C.c_void_p(), C.c_void_p(), C.c_void_p()
+        self._eng._check(self._lib.dst_stream_group_summary_batch(self._h, C.byref(n), C.byref(wp), C.byref(sp), C.byref(dp)))
+        m, G = int(n.value), self.n_loaded_groups
+        within = np.ctypeslib.as_array(C.cast(wp, C.POINTER(C.c_uint32)), shape=(m, G)).copy()
+        summable = np.ctypeslib.as_array(C.cast(sp, C.POINTER(C.c_uint32)), shape=(m, G)).copy()
+        sums = np.ctypeslib.as_array(C.cast(dp, C.POINTER(C.c_double)), shape=(m, G)).copy()
+        return m, within, summable, sums
+
+    def pop(self, copy: bool = True):
+        n, p = C.c_size_t(), C.c_void_p()
+        self._eng._check(self._lib.dst_stream_collect(self._h, C.byref(n), C.byref(p)))
+        return self.group_summary_batch() if self.streamed else int(n.value)
+
+    def result(self, cells_cap: int | None = None, rec_cap: int | None = None) -> dict:
+        """A snapshot of everything kept so far (dst_stream_group_summary_result); every pushed batch must have been popped."""
+        Gs, Gl, n = self.n_streamed_groups, self.n_loaded_groups, self._n_loaded
+        n_cells, n_rec = Gs * Gl, n * Gs
+        cells_cap = n_cells if cells_cap is None else int(cells_cap)
+        rec_cap = n_rec if rec_cap is None else int(rec_cap)
+        cells = (GroupCell * max(cells_cap, 1))()
+        room = max(rec_cap, 1)
+        within = np.zeros(room, np.uint32) if self.loaded else None
+        summable = np.zeros(room, np.uint32) if self.loaded else None
+        sums = np.zeros(room, np.float64) if self.loaded else None
+        records = C.c_uint64()
+
+        def ptr(a):
+            return None if a is None else a.ctypes.data
+
+        self._eng._check(self._lib.dst_stream_group_summary_result(self._h, C.addressof(cells), cells_cap, ptr(within), ptr(summable),
+                                                                   ptr(sums), rec_cap, C.byref(records)))
+        raw = np.frombuffer(cells, dtype=np.uint64, count=n_cells * 7).reshape(Gs, Gl, 7)
+        value = np.int64 if self._m in (0, 1) else np.float64
+        out = {"records": int(records.value), "pairs": raw[:, :, 0].copy(), "nan_pairs": raw[:, :, 1].copy(),
+               "summable_pairs": raw[:, :, 2].copy(), "links": raw[:, :, 3].copy(), "sum": raw[:, :, 4].copy().view(np.float64),
+               "min": raw[:, :, 5].copy().view(value), "max": raw[:, :, 6].copy().view(value)}
+        if self.loaded:
+            out.update(rec_within=within[:n_rec].reshape(n, Gs), rec_summable=summable[:n_rec].reshape(n, Gs),
+                       rec_sum=sums[:n_rec].reshape(n, Gs))
+        return out
+
+
+def _group_labels_u32(g: np.ndarray, side: str) -> np.ndarray:
+    """integer labels as uint32, -1 as DST_GROUP_NONE (Engine._group_labels' rule)"""
+    g64 = g.astype(np.int64)
+    g64 = np.where(g64 == -1, GROUP_NONE, g64)
+    if ((g64 < 0) | (g64 > GROUP_NONE)).any():
+        raise ValueError(f"{side}: a label is neither -1 nor a 32-bit unsigned value")
+    return np.ascontiguousarray(g64.astype(np.uint32))

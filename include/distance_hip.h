@@ -959,7 +959,8 @@ int dst_window_summary(dst_ctx *ctx, int measure, int square, int row_slot, int 
  * the byte count).  A square set of fewer than 2 records, an empty row or column set, and a call in which no record of
  * the column side (the square: of the set) is assigned or whose cells alone are wanted while no row record is assigned:
  * DST_OK, zero counts and sums, min / max as for an empty cell, no slab run.  Synchronous on the context's stream; slots,
- * the path choice and later results are untouched.  Single GPU, loaded sets only (not dst_stream). */
+ * the path choice and later results are untouched.  Single GPU, loaded sets only (stream mode:
+ * dst_stream_open_group_summary). */
 #define DST_GROUPS_MAX 1024u          /* most groups of one side */
 #define DST_GROUP_NONE 0xFFFFFFFFu    /* a record that belongs to no group */
 typedef struct dst_group_cell {
@@ -973,6 +974,73 @@ int dst_group_summary(dst_ctx *ctx, int measure, int square, int row_slot, int c
                       double threshold, uint64_t max_pairs,
                       dst_group_cell *cells, size_t cells_cap,
                       uint32_t *rec_within, uint32_t *rec_summable, double *rec_sum, size_t rec_cap);
+/* ---- group summaries in stream mode ----------------------------------------------------------------- */
+/* dst_group_summary for a labelled database that does not fit on the GPU: the mean distance of each of my records to each
+ * lineage of the database, the reference group every database record sits closest to, d_xy between my lineages and the
+ * database's.  A group-summary stream IS a dst_stream, the sixth kind: dst_stream_acquire / _submit / _collect /
+ * _in_flight / _close work on it as on a summary stream, with both wire formats, the caller's base counts and the ring of
+ * `depth` slots (2..16); dst_stream_collect returns *results = NULL, but still waits for the batch and still reports
+ * DST_ERR_INVALID_CODE.
+ * Definition, fixed to the bit.  S is the set of every record submitted so far, in stream order.  The payload of the pair
+ * (streamed s, loaded i) is the summary stream's: what the same stream would deliver for it as DST_OUT_DISTANCE, bit for
+ * bit, with the batch as rows (tn93's count order and use_base_counts included).  The answer is dst_group_summary's
+ * definition (above), word for word, applied to the rectangle rows = S, cols = slot 0: the link rule, q, "summable", NaN,
+ * the 128-bit cell sum and its one conversion to double, min / max decoded from the sort key, the empty cell's quiet NaN
+ * or 0.
+ *   cells (always kept)          n_streamed_groups x n_loaded_groups entries, entry a G_l + b: streamed group a against
+ *                                loaded group b; `pairs` from the group sizes so far
+ *   DST_STREAM_GROUPS_STREAMED   per batch: n_records x G_l entries, dst_group_summary's rec_* rows of the batch's records
+ *   DST_STREAM_GROUPS_LOADED     kept over the stream's life: n_loaded x G_s entries, entry i G_s + g: loaded record i's
+ *                                within / summable / sum over its streamed partners in streamed group g - the rec_* rows
+ *                                of the transposed rectangle
+ * Every record has a row, assigned or not: a record labelled DST_GROUP_NONE still gets its STREAMED row and its LOADED table
+ * row.  All accumulation is by integer atomics (add; min / max on the key), so the answer does not depend on the cut into
+ * batches, on depth, on the wire format or on the kernel path.
+ * Labels.  loaded_group: n_loaded entries, copied at open, each a group below n_loaded_groups or DST_GROUP_NONE; NULL: every
+ * loaded record is in group 0, and then n_loaded_groups must be 1.  The streamed records' labels go into the acquired
+ * slot's page-locked label block of max_records entries (dst_stream_group_labels, valid between dst_stream_acquire and
+ * dst_stream_submit), which dst_stream_acquire has filled with 0: a stream that never asks for the block puts the whole
+ * database in streamed group 0.  dst_stream_submit checks the first n_records labels on the host: one that is neither below
+ * n_streamed_groups nor DST_GROUP_NONE is DST_ERR_ARG naming the record, and changes nothing.  Both group counts are
+ * 1..DST_GROUPS_MAX.
+ * Open, errors in this order: DST_ERR_ARG for a NULL ctx or stream pointer, an unknown measure or wire, a NaN threshold, bits
+ * in `what` other than the two, a group count of 0 or above DST_GROUPS_MAX, a NULL loaded_group with n_loaded_groups != 1,
+ * max_records == 0, depth outside 2..16; DST_ERR_STATE for slot 0 not loaded; DST_ERR_ARG for a loaded set of 2^32-1 records
+ * or more and for a bad loaded label (dst_group_summary's message); DST_ERR_NOMEM with the byte count when 56 bytes per cell,
+ * 24 bytes per (loaded record, streamed group) with LOADED, or per ring slot 24 bytes per (record, loaded group) do not fit.
+ * Submit: DST_ERR_CAPACITY past 2^32-2 records (compared in 64 bits), changing nothing; DST_ERR_STATE when the loaded set's
+ * record count or width changed.  A batch's atomics cannot be taken back: after a batch with an invalid code every later
+ * dst_stream_submit, dst_stream_group_summary_batch and dst_stream_group_summary_result on that stream is DST_ERR_STATE.
+ * An empty loaded set runs no reduction and gives zero results; when no loaded record is assigned and LOADED is not asked
+ * for, nothing is launched.  The calls below on any other stream are DST_ERR_ARG, as are the other kinds' calls on this one;
+ * a NULL stream is DST_ERR_ARG.
+ * The stream owns all of its state - the loaded labels, the cells and the LOADED table, zeroed once at open, and per ring
+ * slot the batch's labels and table - so dst_group_summary or any other call on the context between two submits does not
+ * disturb it.  Per submit, on the compute stream behind the batch's pair kernel: dst_group_summary's row pass over the
+ * batch's matrix (the STREAMED table, the cells' NaN / min / max), its fold of that table into the cells, and with LOADED
+ * a column pass.  Per batch the labels, the bad-code word and (STREAMED) 24 bytes per (record, loaded group) cross the host
+ * link, never the matrix.  Single GPU. */
+#define DST_STREAM_GROUPS_LOADED   1   /* keep, per loaded record and STREAMED group, the table over the stream's life */
+#define DST_STREAM_GROUPS_STREAMED 2   /* hand out, per batch, every streamed record's table over the LOADED groups    */
+int dst_stream_open_group_summary(dst_ctx *ctx, int measure, double threshold, int what,
+                                  const uint32_t *loaded_group, uint32_t n_loaded_groups, uint32_t n_streamed_groups,
+                                  size_t max_records, int depth, int wire, dst_stream **stream);
+/* The acquired slot's label block: max_records entries, page-locked, library-owned, filled with 0 by dst_stream_acquire.
+ * DST_ERR_STATE when no buffer is acquired. */
+int dst_stream_group_labels(dst_stream *stream, uint32_t **labels);
+/* STREAMED only (else DST_ERR_ARG).  After dst_stream_collect: the collected batch, *n_records x n_loaded_groups entries per
+ * array, in page-locked, library-owned memory that is valid until the next dst_stream_submit.  n_records is required;
+ * within, summable and sum may be NULL.  DST_ERR_STATE when no batch has been collected since the last submit. */
+int dst_stream_group_summary_batch(dst_stream *stream, size_t *n_records, const uint32_t **within,
+                                   const uint32_t **summable, const double **sum);
+/* A snapshot of everything kept so far (host memory): the cells (n_streamed_groups x n_loaded_groups), the LOADED table
+ * (n_loaded x n_streamed_groups entries per array) and *records; every pointer may be NULL.  Without
+ * DST_STREAM_GROUPS_LOADED the three rec_* pointers must be NULL, else DST_ERR_ARG.  Needs dst_stream_in_flight() == 0, else
+ * DST_ERR_STATE; cells_cap or rec_cap below the entries of a non-NULL array: DST_ERR_CAPACITY.  The call may be repeated,
+ * and streaming may go on afterwards. */
+int dst_stream_group_summary_result(dst_stream *stream, dst_group_cell *cells, size_t cells_cap,
+                                    uint32_t *rec_within, uint32_t *rec_summable, double *rec_sum, size_t rec_cap,
+                                    uint64_t *records);
 /* ---- group summaries per column window ------------------------------------------------------------ */
 /* dst_group_summary's cells and per-record tables INSIDE every column window, reduced next to the window sweep on the GPU:
  * pi per population and d_xy between populations along the genome (the means F_ST is formed from), a query's mean distance
