@@ -40,6 +40,9 @@ STREAM_GROUPS_COLS = 256     # kStreamGroupCols: ... and loaded records
 GROUPS_MAX = 1024         # DST_GROUPS_MAX: the most groups of one side of dst_group_summary
 WINDOW_GROUPS_MAX = 256   # DST_WINDOW_GROUPS_MAX: the most groups of one side of dst_window_group_summary
 GROUP_NONE = 0xFFFFFFFF   # DST_GROUP_NONE: a record that belongs to no group
+SITE_CLASSES = 5          # DST_SITE_CLASSES: A, T, G, C, ambiguous of a dst_site_counts entry
+SITE_FLUSH_PERIOD = 15    # DST_SITE_FLUSH_PERIOD: records a thread of the site-count kernel takes before it adds to the counts
+SITE_STRIP_RECORDS = 3840   # DST_SITE_STRIP_RECORDS: records of one group a workgroup of that kernel counts
 
 
 class LaunchInfo(C.Structure):
@@ -61,6 +64,12 @@ class GroupCell(C.Structure):
     """dst_group_cell"""
     _fields_ = [("pairs", C.c_uint64), ("nan_pairs", C.c_uint64), ("summable_pairs", C.c_uint64), ("links", C.c_uint64),
                 ("sum", C.c_double), ("min_bits", C.c_uint64), ("max_bits", C.c_uint64)]
+
+
+class SiteWindow(C.Structure):
+    """dst_site_window"""
+    _fields_ = [("records", C.c_uint64), ("sites", C.c_uint64), ("called", C.c_uint64), ("segregating", C.c_uint64),
+                ("theta_sum", C.c_double), ("pi_sum", C.c_double)]
 
 
 class PairsInfo(C.Structure):
@@ -183,6 +192,8 @@ _SIGS = {
                                     C.c_uint64, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t]),
     "dst_window_group_summary": (C.c_int, [_vp, C.c_int, C.c_int, C.c_int, C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_uint32, _vp,
                                            C.c_uint32, C.c_double, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t]),
+    "dst_site_counts": (C.c_int, [_vp, C.c_int, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, C.c_size_t]),
+    "dst_site_stats": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_size_t]),
     "dst_mst": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, C.c_size_t, _u64p, _u32p]),
     "dst_nj": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, C.c_size_t]),
     "dst_nj_matrix": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_size_t]),

@@ -1033,4 +1033,147 @@ void write_window_groups(const Run &run, const WindowList &wl, const std::vector
     out.finish();
 }
 
+// --site-counts / --window-site-stats: the per-site allele counts of the one input (dst_site_counts), walked in ranges of
+// sites of at most 2^26 entries.  `labels` is empty without --site-groups: one group, "all", of every record.
+struct SiteGroups {
+    const uint32_t *label = nullptr;
+    uint32_t count = 1;
+    std::vector<std::string> names{"all"};
+    std::vector<uint64_t> size;
+};
+
+SiteGroups site_groups(const Run &run, const std::vector<GroupLabels> &labels)
+{
+    SiteGroups sg;
+    if (labels.empty()) {
+        sg.size.assign(1, run.rows().n);
+        return sg;
+    }
+    const GroupLabels &gl = labels[0];
+    sg.label = gl.label.data();
+    sg.count = (uint32_t)gl.names.size();
+    sg.names = gl.names;
+    sg.size.assign(sg.count, 0);
+    for (const uint32_t g : gl.label)
+        if (g != DST_GROUP_NONE)
+            ++sg.size[g];
+    return sg;
+}
+
+constexpr size_t kSiteRangeEntries = (size_t)1 << 26;
+
+// the most entries of one range; DISTANCE_SITE_RANGE_ENTRIES makes it smaller (the tests walk a small input in many ranges)
+size_t site_range_entries()
+{
+    const char *env = std::getenv("DISTANCE_SITE_RANGE_ENTRIES");
+    const size_t asked = env ? (size_t)std::strtoull(env, nullptr, 10) : 0;
+    return asked ? std::min(asked, kSiteRangeEntries) : kSiteRangeEntries;
+}
+
+// the counts of sites [begin, end), in ranges: sink(first site of the range, sites, the range's entries)
+template <typename Sink>
+void walk_site_counts(const Run &run, const SiteGroups &sg, uint64_t begin, uint64_t end, Sink &&sink)
+{
+    const size_t per_site = (size_t)sg.count * DST_SITE_CLASSES;
+    const uint64_t sites_per_range = std::max<uint64_t>(1, site_range_entries() / per_site);
+    std::vector<uint32_t> counts((size_t)std::min<uint64_t>(sites_per_range, end - begin) * per_site);
+    for (uint64_t s = begin; s < end; s += sites_per_range) {
+        const uint64_t e = std::min(end, s + sites_per_range);
+        run.gpu.check(dst_site_counts(run.gpu.h, 0, sg.label, sg.count, s, e, counts.data(), counts.size()), "site counts");
+        sink(s, e - s, counts.data());
+    }
+}
+
+// --site-counts: "site, group, records, A, C, G, T, ambiguous, missing", one line per site (1-based) and group in group order
+void write_site_counts(const Run &run, const std::vector<GroupLabels> &labels)
+{
+    const SiteGroups sg = site_groups(run, labels);
+    run.header("site\tgroup\trecords\tA\tC\tG\tT\tambiguous\tmissing\n");
+    LineWriter out(run.wr);
+    walk_site_counts(run, sg, 0, run.rows().width, [&](uint64_t first, uint64_t sites, const uint32_t *counts) {
+        for (uint64_t s = 0; s < sites; ++s)
+            for (uint32_t g = 0; g < sg.count; ++g) {
+                const uint32_t *c = counts + (s * sg.count + g) * DST_SITE_CLASSES;   // A, T, G, C, ambiguous
+                out.number(first + s + 1);
+                out.put('\t');
+                out.put(sg.names[g]);
+                for (const uint64_t v : {sg.size[g], (uint64_t)c[0], (uint64_t)c[3], (uint64_t)c[2], (uint64_t)c[1], (uint64_t)c[4],
+                                         sg.size[g] - c[0] - c[1] - c[2] - c[3] - c[4]}) {
+                    out.put('\t');
+                    out.number(v);
+                }
+                out.end_line();
+            }
+    });
+    out.finish();
+}
+
+// --window-site-stats: per window and group "window, start, end, group, records, sites, called, segregating, theta_w, pi" from
+// dst_site_stats; the two means (over the called sites) printed as --summary prints its mean, NaN when no site is called.
+// The window fields are the plain --windows / --regions run's.  The counts are walked in ranges of sites; a range's counts
+// serve the windows that lie inside it, and a window that crosses a range's end is counted on its own.
+void write_window_site_stats(const Run &run, const WindowList &wl, const std::vector<GroupLabels> &labels)
+{
+    const SiteGroups sg = site_groups(run, labels);
+    const size_t nw = wl.begin.size(), G = sg.count;
+    run.header("window\tstart\tend\tgroup\trecords\tsites\tcalled\tsegregating\ttheta_w\tpi\n");
+    if (nw == 0)
+        return;
+    std::vector<dst_site_window> stats(nw * G);
+    std::vector<char> done(nw, 0);
+    auto reduce = [&](size_t w, uint64_t first, uint64_t sites, const uint32_t *counts) {
+        if (dst_site_stats(counts, first, first + sites, sg.count, &wl.begin[w], &wl.end[w], 1, sg.size.data(), &stats[w * G], G) != DST_OK)
+            die_message("site stats: window " + wl.names[w] + " does not lie inside the counted sites");
+        done[w] = 1;
+    };
+    uint64_t lo = UINT64_MAX, hi = 0;
+    for (size_t w = 0; w < nw; ++w) {
+        lo = std::min<uint64_t>(lo, wl.begin[w]);
+        hi = std::max<uint64_t>(hi, wl.end[w]);
+    }
+    walk_site_counts(run, sg, lo, std::max(lo, hi), [&](uint64_t first, uint64_t sites, const uint32_t *counts) {
+        for (size_t w = 0; w < nw; ++w)
+            if (!done[w] && wl.begin[w] >= first && wl.end[w] <= first + sites)
+                reduce(w, first, sites, counts);
+    });
+    for (size_t w = 0; w < nw; ++w) {
+        if (done[w])
+            continue;
+        if (wl.begin[w] == wl.end[w]) {   // (an empty window outside every range: nothing to count)
+            uint32_t none = 0;
+            reduce(w, wl.begin[w], 0, &none);
+            continue;
+        }
+        // a window across a range's end: its own sites, counted in ranges again and reduced as one piece (the sums are
+        // taken in site order over the whole window)
+        std::vector<uint32_t> whole;
+        walk_site_counts(run, sg, wl.begin[w], wl.end[w], [&](uint64_t, uint64_t sites, const uint32_t *counts) {
+            whole.insert(whole.end(), counts, counts + sites * G * DST_SITE_CLASSES);
+        });
+        reduce(w, wl.begin[w], wl.end[w] - wl.begin[w], whole.data());
+    }
+    LineWriter out(run.wr);
+    for (size_t w = 0; w < nw; ++w)
+        for (size_t g = 0; g < G; ++g) {
+            const dst_site_window &r = stats[w * G + g];
+            out.put(wl.names[w]);
+            out.put('\t');
+            out.number(wl.begin[w] + 1);
+            out.put('\t');
+            out.number(wl.end[w]);
+            out.put('\t');
+            out.put(sg.names[g]);
+            for (const uint64_t v : {r.records, r.sites, r.called, r.segregating}) {
+                out.put('\t');
+                out.number(v);
+            }
+            for (const double s : {r.theta_sum, r.pi_sum}) {
+                out.put('\t');
+                out.distance(DST_RAW, r.called ? s / (double)r.called : std::nan(""), 0);
+            }
+            out.end_line();
+        }
+    out.finish();
+}
+
 }  // namespace

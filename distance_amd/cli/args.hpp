@@ -152,6 +152,18 @@ void print_help()
         "(1-256) nearest STREAMED records, written when the stream ends: byte for byte what '--window-nearest K loaded.fasta "
         "streamed.fasta' prints, for a streamed file that need not fit on the GPU. Requires --stream, one loaded file, one "
         "GPU, no other output mode\n"
+        "      --site-counts            Print the allele counts of every site instead of distances: one line per site (1-based) "
+        "and group, 'site, group, records, A, C, G, T, ambiguous, missing': the records of the group whose letter there is "
+        "exactly that base, those with an ambiguity code of 2 or 3 bases, and those with N, - or ?. Counted on the GPU. "
+        "One input, one GPU; -m is accepted and ignored; no --stream and no other output mode\n"
+        "      --window-site-stats      With --windows or --regions: print one line per window and group instead of one per pair "
+        "and window, 'window, start, end, group, records, sites, called, segregating, theta_w, pi': the sites with at least "
+        "two single-base calls, those of them with more than one base (S), Watterson's theta per called site and the "
+        "per-site nucleotide diversity over single-base calls (not the mean of the pairwise raw distances, which counts "
+        "each pair's own comparable sites). From the per-site allele counts of the GPU. One input, one GPU; -m is accepted "
+        "and ignored\n"
+        "      --site-groups <FILE>     With --site-counts or --window-site-stats: count per group. FILE as for --groups (at "
+        "most 1024 groups, numbered in order of their first record); without it there is one group, 'all', of every record\n"
         "      --dendrogram <linkage>   Print the rooted hierarchical-clustering tree of the records as one Newick line instead "
         "of distances: linkage average (UPGMA), weighted (WPGMA) or complete. One input, one GPU, no --stream and no other "
         "output mode\n"
@@ -174,7 +186,8 @@ enum Flag {
     F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_PAIRS, F_WINDOW_CLOSEST,
     F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY, F_WINDOW_GROUPS, F_WINDOW_GROUPS_WITHIN, F_WINDOW_GROUPS_BY,
     F_STREAM_SUMMARY, F_STREAM_SUMMARY_FOR, F_STREAM_HISTOGRAM, F_STREAM_BINS,
-    F_STREAM_GROUPS, F_STREAM_GROUPS_BY, F_STREAM_GROUPS_WITHIN, F_COUNT
+    F_STREAM_GROUPS, F_STREAM_GROUPS_BY, F_STREAM_GROUPS_WITHIN,
+    F_SITE_COUNTS, F_WINDOW_SITE_STATS, F_SITE_GROUPS, F_COUNT
 };
 struct FlagDef {
     const char *shown;   // "--name <value>": its first word is the flag itself
@@ -201,11 +214,13 @@ const FlagDef kFlags[F_COUNT] = {
     {"--stream-histogram <W>", nullptr, true}, {"--stream-bins <B>", nullptr, false},
     {"--stream-groups <FILE>", nullptr, true}, {"--stream-groups-by <what>", nullptr, false},
     {"--stream-groups-within <T>", nullptr, true},
+    {"--site-counts", nullptr, true}, {"--window-site-stats", nullptr, true}, {"--site-groups <FILE>", nullptr, true},
 };
 
 // what the run prints, decided once by parse_args
 enum class Mode { Pairs, Stream, Closest, Within, Nearest, Clusters, MaxDistance, Summary, Histogram, Groups, Matrix, Tree, Mst,
-                  Dendrogram, Representatives, Windows, PairList, WindowClosest, StreamSummary, StreamHistogram, StreamGroups };
+                  Dendrogram, Representatives, Windows, PairList, WindowClosest, StreamSummary, StreamHistogram, StreamGroups,
+                  SiteCounts };
 
 struct Args {
     bool has[F_COUNT] = {};               // the flag was given
@@ -250,6 +265,7 @@ struct Args {
     std::string stream_groups;            // --stream-groups FILE (stream mode)
     int stream_groups_by = 0;             // --stream-groups-by cell|streamed|loaded: 0, 1, 2
     double stream_groups_within = 0;      // --stream-groups-within T
+    std::string site_groups;              // --site-groups FILE
     std::string selftest;
     size_t n_inputs() const { return flag_inputs.size() + pos_inputs.size(); }
     // the slab size an analysis is given: the library's own choice unless --slab-pairs was passed
@@ -342,7 +358,23 @@ const std::vector<Flag> kStreamSummaryRefuses = {
     F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM,
     F_WINDOWS, F_STEP, F_REGIONS, F_WINDOW_NEAREST, F_PAIRS, F_WINDOW_CLOSEST, F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY,
     F_WINDOW_GROUPS, F_WINDOW_GROUPS_WITHIN, F_WINDOW_GROUPS_BY};
+// everything --site-counts / --window-site-stats cannot go with besides --windows / --regions / --step: stream mode, every
+// other output mode and every modifier of one (--sites, the pair lists' modifier, among them)
+const std::vector<Flag> kSiteRefuses = {
+    F_STREAM, F_NEAREST, F_CLOSEST, F_CLOSEST_FOR, F_WITHIN, F_CLUSTERS, F_REPRESENTATIVES, F_MAX_DISTANCE, F_SUMMARY, F_GROUPS,
+    F_GROUPS_WITHIN, F_PER_RECORD, F_HISTOGRAM, F_BINS, F_MATRIX, F_TREE, F_BOOTSTRAP, F_SEED, F_MST, F_SITES, F_DENDROGRAM,
+    F_WINDOW_NEAREST, F_PAIRS, F_WINDOW_CLOSEST, F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY, F_WINDOW_GROUPS, F_WINDOW_GROUPS_WITHIN,
+    F_WINDOW_GROUPS_BY, F_STREAM_SUMMARY, F_STREAM_SUMMARY_FOR, F_STREAM_HISTOGRAM, F_STREAM_BINS, F_STREAM_GROUPS,
+    F_STREAM_GROUPS_BY, F_STREAM_GROUPS_WITHIN};
 const Rule kRules[] = {
+    // (before every other row: a command line with --site-counts, --window-site-stats or --site-groups is judged here first,
+    // and no other line's outcome changes.  --window-site-stats leaves the mode to --windows / --regions.)
+    {F_SITE_GROUPS, Mode::Pairs, kNone, {F_SITE_COUNTS, F_WINDOW_SITE_STATS}, "'--site-counts' or '--window-site-stats'", TWO_OK,
+     false},
+    {F_SITE_COUNTS, Mode::SiteCounts, after(F_WINDOW_SITE_STATS, after(F_WINDOWS, after(F_STEP, after(F_REGIONS, kSiteRefuses)))),
+     kNone, nullptr, ONE_INPUT, true},
+    {F_WINDOW_SITE_STATS, Mode::Pairs, kSiteRefuses, {F_WINDOWS, F_REGIONS}, "'--windows <W>' or '--regions <FILE>'", ONE_INPUT,
+     true},
     // (before every other row: a command line with --stream-groups or one of its two modifiers is judged here first, and no
     // other line's outcome changes)
     {F_STREAM_GROUPS_BY, Mode::Pairs, kNone, {F_STREAM_GROUPS}, "'--stream-groups <FILE>'", TWO_OK, false},
@@ -526,7 +558,7 @@ Args parse_args(int argc, char **argv)
             while (a.flag_inputs.size() < 2 && k + 1 < argc && (argv[k + 1][0] != '-' || !std::strcmp(argv[k + 1], "-")))
                 a.flag_inputs.push_back(argv[++k]);
         } else if (text(F_STREAM, a.stream) || text(F_MEASURE, a.measure) || text(F_OUTPUT, a.output) ||
-                   text(F_GROUPS, a.groups) || text(F_WINDOW_GROUPS, a.window_groups) || text(F_STREAM_GROUPS, a.stream_groups) || text(F_REGIONS, a.regions) || text(F_PAIRS, a.pairs) || count(F_WINDOWS, a.windows, 1, SIZE_MAX) ||
+                   text(F_GROUPS, a.groups) || text(F_WINDOW_GROUPS, a.window_groups) || text(F_STREAM_GROUPS, a.stream_groups) || text(F_SITE_GROUPS, a.site_groups) || text(F_REGIONS, a.regions) || text(F_PAIRS, a.pairs) || count(F_WINDOWS, a.windows, 1, SIZE_MAX) ||
                    count(F_STEP, a.step, 1, SIZE_MAX) || count(F_THREADS, a.threads, 0, SIZE_MAX) ||
                    count(F_BATCHSIZE, a.batchsize, 0, SIZE_MAX) || count(F_SEED, a.seed, 0, SIZE_MAX) ||
                    count(F_NEAREST, a.nearest, 1, 256) || count(F_CLOSEST, a.closest, 1, 256) ||
@@ -576,6 +608,11 @@ Args parse_args(int argc, char **argv)
             a.selftest = v;
         } else if (arg == "--per-record" || arg == "--mst" || arg == "--sites") {
             a.has[arg == "--per-record" ? F_PER_RECORD : arg == "--mst" ? F_MST : F_SITES] = true;
+        } else if (arg == "--site-counts" || arg == "--window-site-stats") {
+            const Flag f = arg == "--site-counts" ? F_SITE_COUNTS : F_WINDOW_SITE_STATS;
+            if (a.has[f])
+                die_usage(std::string("the argument '") + kFlags[f].shown + "' cannot be used multiple times");
+            a.has[f] = true;
         } else {
             die_usage("unexpected argument '" + arg + "' found");
         }

@@ -159,6 +159,8 @@ int main(int argc, char **argv)
         group_file = read_group_file(a.window_groups, "--window-groups");
     else if (a.mode == Mode::StreamGroups)
         group_file = read_group_file(a.stream_groups, "--stream-groups");
+    else if (a.has[F_SITE_GROUPS])
+        group_file = read_group_file(a.site_groups, "--site-groups");
     // --pairs: likewise
     PairFile pair_file;
     if (a.mode == Mode::PairList)
@@ -198,6 +200,8 @@ int main(int argc, char **argv)
         group_labels = label_inputs(group_file, loaded);
     else if (a.has[F_WINDOW_GROUPS])
         group_labels = label_inputs(group_file, loaded, DST_WINDOW_GROUPS_MAX);
+    else if (a.has[F_SITE_GROUPS])
+        group_labels = label_inputs(group_file, loaded);
     // --stream-groups: the loaded records' labels (cell, streamed), and the ids of the file that the loaded side carries
     StreamGroups stream_groups;
     if (a.mode == Mode::StreamGroups)
@@ -268,8 +272,11 @@ int main(int argc, char **argv)
     case Mode::Groups: write_groups(run, group_labels, a.has[F_GROUPS_WITHIN], a.groups_within, a.has[F_PER_RECORD]); break;
     case Mode::Histogram: write_histogram(run, a.histogram, (uint32_t)a.bins); break;
     case Mode::Nearest: write_nearest(run, (uint32_t)a.nearest); break;
+    case Mode::SiteCounts: write_site_counts(run, group_labels); break;
     case Mode::Windows:
-        if (a.has[F_WINDOW_GROUPS])
+        if (a.has[F_WINDOW_SITE_STATS])
+            write_window_site_stats(run, windows, group_labels);
+        else if (a.has[F_WINDOW_GROUPS])
             write_window_groups(run, windows, group_labels, a.has[F_WINDOW_GROUPS_WITHIN], a.window_groups_within,
                                 a.window_groups_by_record);
         else if (a.has[F_WINDOW_SUMMARY])

@@ -124,6 +124,9 @@ struct dst_ctx {
     // their page-locked copy
     Grown<> win_group_work;
     Grown<char, true> win_group_host;
+    // dst_site_counts: the counts, the record list and the strips on the device; the list's and strips' page-locked staging
+    Grown<> site_work;
+    Grown<char, true> site_host;
     Grown<> summary_work;   // dst_summary: the per-record counters and accumulators, the histogram and the totals
     // dst_group_summary: the labels, the cells and the per-record table; the labels' page-locked staging
     Grown<> group_work;

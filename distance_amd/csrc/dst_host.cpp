@@ -586,6 +586,42 @@ int dst_sliding_windows(uint64_t len, uint64_t width, uint64_t step, uint64_t *b
     return DST_OK;
 }
 
+// dst_site_counts' entries reduced to windows (include/distance_hip.h fixes every operation and its order)
+int dst_site_stats(const uint32_t *counts, uint64_t site_begin, uint64_t site_end, uint32_t n_groups, const uint64_t *win_begin,
+                   const uint64_t *win_end, uint32_t n_windows, const uint64_t *group_size, dst_site_window *out, size_t cap)
+{
+    if (!counts || !group_size || !out || n_groups == 0 || site_begin > site_end || (n_windows && (!win_begin || !win_end)))
+        return DST_ERR_ARG;
+    for (uint32_t w = 0; w < n_windows; ++w)
+        if (win_begin[w] > win_end[w] || win_begin[w] < site_begin || win_end[w] > site_end)
+            return DST_ERR_ARG;
+    if ((unsigned __int128)n_windows * n_groups > (unsigned __int128)cap)
+        return DST_ERR_CAPACITY;
+    std::vector<double> harmonic(1, 0.0);   // H[k], grown to the largest m - 1 met
+    for (uint32_t w = 0; w < n_windows; ++w)
+        for (uint32_t g = 0; g < n_groups; ++g) {
+            dst_site_window r{group_size[g], win_end[w] - win_begin[w], 0, 0, 0.0, 0.0};
+            for (uint64_t s = win_begin[w]; s < win_end[w]; ++s) {
+                const uint32_t *c = counts + ((s - site_begin) * n_groups + g) * DST_SITE_CLASSES;
+                const uint64_t a = c[0], t = c[1], gg = c[2], cc = c[3];
+                const uint64_t m = a + t + gg + cc;
+                if (m < 2)
+                    continue;
+                ++r.called;
+                const uint64_t d = a * t + a * gg + a * cc + t * gg + t * cc + gg * cc;
+                r.pi_sum += (double)d / (double)(m * (m - 1) / 2);
+                if ((a != 0) + (t != 0) + (gg != 0) + (cc != 0) < 2)
+                    continue;
+                ++r.segregating;
+                while (harmonic.size() < m)
+                    harmonic.push_back(harmonic.back() + 1.0 / (double)harmonic.size());
+                r.theta_sum += 1.0 / harmonic[m - 1];
+            }
+            out[(size_t)w * n_groups + g] = r;
+        }
+    return DST_OK;
+}
+
 int dst_shared_range(uint64_t n, int rank, int world, uint64_t *begin, uint64_t *end)
 {
     if (world < 1 || rank < 0 || rank >= world || !begin || !end)

@@ -13,7 +13,7 @@ import numpy as np
 
 from ._lib import (ALLGATHER_FN, GROUP_NONE, LINKS_CHUNK, LINKS_SINK, LINKS_TALLIES, LINKS_VALUES, SLAB_SINK,
                    STREAM_GROUPS_LOADED, STREAM_GROUPS_STREAMED, STREAM_SUMMARY_LOADED, STREAM_SUMMARY_STREAMED, DistanceError,
-                   GroupCell, LaunchInfo, PairsInfo, SummaryTotals, load)
+                   GroupCell, LaunchInfo, PairsInfo, SITE_CLASSES, SiteWindow, SummaryTotals, load)
 
 MEASURES = {"n": 0, "n_high": 1, "raw": 2, "jc69": 3, "k80": 4, "tn93": 5}
 INT_MEASURES = ("n", "n_high")
@@ -74,6 +74,29 @@ def sliding_windows(length: int, width: int, step: int) -> np.ndarray:
     if rc:
         raise DistanceError(rc, "dst_sliding_windows")
     return np.stack([begin[:k], end[:k]], axis=1)
+
+
+def site_stats(counts, windows, group_sizes, site_begin: int = 0) -> dict:
+    """Engine.site_counts' (sites, G, 5) entries of the sites from `site_begin` reduced to windows (dst_site_stats, pure
+    host code): a dict of (n_windows, G) arrays `records`, `sites`, `called`, `segregating` (uint64), `theta_sum` and
+    `pi_sum` (float64).  Watterson's theta per site is theta_sum / called, the per-site pi is pi_sum / called."""
+    c = np.ascontiguousarray(counts, np.uint32)
+    if c.ndim != 3 or c.shape[2] != SITE_CLASSES or c.shape[1] == 0:
+        raise ValueError(f"counts must be a (sites, groups, {SITE_CLASSES}) array")
+    sites, G = int(c.shape[0]), int(c.shape[1])
+    sizes = np.ascontiguousarray(group_sizes, np.uint64)
+    if sizes.shape != (G,):
+        raise ValueError(f"group_sizes must hold one size per group ({G})")
+    begin, end, nw = _window_arrays(windows)
+    out = (SiteWindow * max(nw * G, 1))()
+    anchor = c if c.size else np.zeros(1, np.uint32)   # (never a NULL array)
+    rc = load().dst_site_stats(anchor.ctypes.data, site_begin, site_begin + sites, G, begin.ctypes.data, end.ctypes.data, nw,
+                               sizes.ctypes.data, C.addressof(out), nw * G)
+    if rc:
+        raise DistanceError(rc, "dst_site_stats: a window outside the counted sites" if rc == 1 else "dst_site_stats")
+    rec = np.frombuffer(out, dtype=np.dtype([("records", "<u8"), ("sites", "<u8"), ("called", "<u8"), ("segregating", "<u8"),
+                                             ("theta_sum", "<f8"), ("pi_sum", "<f8")]))[:nw * G].reshape(nw, G)
+    return {name: rec[name].copy() for name in rec.dtype.names}
 
 
 def _window_arrays(windows):
@@ -697,6 +720,36 @@ class Engine:
         out = np.zeros((nw, n, 4), np.uint32)
         self._check(self._lib.dst_window_base_counts(self._h, slot, begin.ctypes.data, end.ctypes.data, nw, out.ctypes.data,
                                                      out.size))
+        return out
+
+    def site_counts(self, slot: int = 0, groups=None, n_groups=None, begin: int = 0, end: int | None = None) -> np.ndarray:
+        """(sites, G, 5) uint32: per site of [begin, end) and group the records whose code is exactly A, T, G, C, and those
+        whose code names 2 or 3 bases (dst_site_counts).  `groups`: one integer label per record of `slot`, -1 or 2^32-1 for
+        a record that belongs to no group (group_summary's rule); None: one group of every record.  n_groups defaults to
+        the largest label + 1."""
+        n, length = self.set_info(slot)
+        if end is None:
+            end = length
+        if groups is None:
+            labels, G = None, 1 if n_groups is None else int(n_groups)
+        else:
+            g = np.asarray(groups)
+            if g.ndim != 1 or len(g) != n or not np.issubdtype(g.dtype, np.integer):
+                raise ValueError(f"groups must be a 1-D integer array with one label per record ({n})")
+            labels = _group_labels_u32(g, "groups")
+            if n_groups is None:
+                assigned = labels[labels != GROUP_NONE]
+                n_groups = int(assigned.max()) + 1 if len(assigned) else 1
+            G = int(n_groups)
+            if len(labels) == 0:
+                labels = np.zeros(1, np.uint32)   # (never a NULL array: NULL means one group)
+        if not (0 <= begin <= GROUP_NONE * 2 ** 32 and 0 <= end <= GROUP_NONE * 2 ** 32 and 0 <= G <= GROUP_NONE):
+            raise ValueError("begin, end and n_groups must be unsigned")
+        sites = max(end - begin, 0)
+        out = np.zeros((sites, G, SITE_CLASSES), np.uint32)
+        anchor = out if out.size else np.zeros(1, np.uint32)
+        self._check(self._lib.dst_site_counts(self._h, slot, None if labels is None else labels.ctypes.data, G, begin, end,
+                                              anchor.ctypes.data, out.size))
         return out
 
     def nearest_windows(self, measure, windows, k: int, square: bool = True, row_slot: int = 0, col_slot: int = 1,

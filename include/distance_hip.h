@@ -1089,6 +1089,64 @@ int dst_window_group_summary(dst_ctx *ctx, int measure, int square, int row_slot
                              double threshold,
                              dst_group_cell *cells, size_t cells_cap,
                              uint32_t *rec_within, uint32_t *rec_summable, double *rec_sum, size_t rec_cap);
+/* ---- per-site allele counts ------------------------------------------------------------------------- */
+/* The column side of the library: per (site, group) how many records hold each base, counted from the set's base planes on
+ * the GPU.  The site-frequency spectrum, minor-allele counts, a per-group consensus, which sites vary at all, and (through
+ * dst_site_stats below) the segregating sites, Watterson's theta and the per-site pi of every window come from these
+ * counts.  They are exact integers added with integer atomics: the result depends on no order.
+ *   labels   group[x] for every record x of `slot`: a group below n_groups, or DST_GROUP_NONE (the record is counted
+ *            nowhere).  group == NULL: one group that holds every record; n_groups must then be 1.  1 <= n_groups <=
+ *            DST_GROUPS_MAX.
+ *   counts   (host memory) entry ((s - site_begin) * n_groups + g) * DST_SITE_CLASSES + k for the sites site_begin <= s <
+ *            site_end: k = 0..3 the records of group g whose code at site s is exactly A, T, G, C (the library's {A,T,G,C}
+ *            order; the code's high nibble is one-hot), k = 4 those whose code names 2 or 3 bases (R M W S K Y V H D B).
+ *            Records whose code is N, - or ? (high nibble 1111) are in no class: missing = the group's size - the five.
+ *            cap_entries: the room of counts in entries.
+ * Only the A, G, C, T planes are read: a lean set serves as it is, a set with deferred planes gets them first.  Padding
+ * records and padding sites are never counted, whatever they hold.
+ * Errors, in this order: DST_ERR_ARG for a NULL ctx or counts, a bad slot, a group count of 0 or above DST_GROUPS_MAX, NULL
+ * labels with n_groups != 1; DST_ERR_STATE for a set not uploaded or one from dst_upload_shared (the window calls' refusal);
+ * DST_ERR_ARG for site_begin > site_end or site_end > len, len >= 2^32, a set of 2^32-1 records or more, or a label that is
+ * neither below n_groups nor DST_GROUP_NONE (the message names the first such record); DST_ERR_CAPACITY when cap_entries is
+ * below (site_end - site_begin) x n_groups x 5, nothing written; DST_ERR_NOMEM with the byte count (4 bytes per entry and
+ * per labelled record).  An empty site range, an empty set or no labelled record: DST_OK, the range's entries zero, no
+ * launch.  Synchronous on the context's stream.  Slots, the path choice, dst_last_path, dst_last_launch and later results
+ * are untouched.  Single GPU, loaded sets only.
+ * DST_SITE_STRIP_RECORDS and DST_SITE_FLUSH_PERIOD describe the kernel, not the result: a workgroup counts
+ * at most DST_SITE_STRIP_RECORDS records of one group, DST_SITE_FLUSH_PERIOD per thread, before it adds to the counts. */
+#define DST_SITE_CLASSES 5
+#define DST_SITE_FLUSH_PERIOD 15u
+#define DST_SITE_STRIP_RECORDS 3840u   /* 256 threads x DST_SITE_FLUSH_PERIOD */
+int dst_site_counts(dst_ctx *ctx, int slot, const uint32_t *group, uint32_t n_groups,
+                    uint64_t site_begin, uint64_t site_end, uint32_t *counts, size_t cap_entries);
+/* Pure host code: dst_site_counts' entries of the sites [site_begin, site_end) reduced to windows.  Windows are
+ * dst_run_windows': half-open, they may overlap, repeat, be empty and come in any order; each must lie inside [site_begin,
+ * site_end), else DST_ERR_ARG (the first such window decides; there is no context to carry a message).  out[w * n_groups + g];
+ * cap: the room of out in entries, below n_windows x n_groups DST_ERR_CAPACITY with nothing written.  group_size[g] is
+ * copied to `records`.  Per site s of the window and group g, with c_A, c_T, c_G, c_C the four base counts:
+ *   m = c_A + c_T + c_G + c_C
+ *   D = the sum over the six unordered base pairs of c_a x c_b (exact in uint64: m < 2^32)
+ *   sites        the window's length
+ *   called       the sites with m >= 2
+ *   segregating  the called sites with at least two non-zero base counts
+ *   pi_sum       the sum over the called sites, in ascending s from +0.0, of (double)D / (double)(m (m - 1) / 2): each
+ *                conversion one rounding, then one division, then one addition
+ *   theta_sum    the sum over the segregating sites, in ascending s from +0.0, of 1.0 / H[m - 1], with H[0] = 0 and
+ *                H[k] = H[k - 1] + 1.0 / (double)k in double
+ * compiled without fused multiply-add, like dst_finalize.  Watterson's theta per site is theta_sum / called and pi is
+ * pi_sum / called.  This pi is the per-site estimator over single-base calls: every site weighs the same and a site's
+ * pairs are those of its called records.  It is NOT the mean of the pairwise `raw` distances that dst_window_summary and
+ * dst_window_group_summary sum, where every pair is divided by its own comparable sites.  Tajima's D is left out on
+ * purpose: its variance term has no agreed form when m varies by site, and every variant is a function of these fields.
+ * DST_ERR_ARG also for a NULL counts, group_size or out, NULL window arrays with n_windows > 0, n_groups == 0, or
+ * site_begin > site_end. */
+typedef struct {
+    uint64_t records, sites, called, segregating;
+    double theta_sum, pi_sum;
+} dst_site_window;
+int dst_site_stats(const uint32_t *counts, uint64_t site_begin, uint64_t site_end, uint32_t n_groups,
+                   const uint64_t *win_begin, const uint64_t *win_end, uint32_t n_windows,
+                   const uint64_t *group_size, dst_site_window *out, size_t cap);
 /* ---- minimum spanning tree --------------------------------------------------------------------- */
 /* The single-linkage picture for every threshold at once: the minimum spanning tree (forest) of one set (slot 0, n
  * records), as GrapeTree- and PHYLOViZ-style viewers draw it, computed next to the values on the GPU by Boruvka rounds
