@@ -23,6 +23,9 @@ SLAB_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_uint64,
 LINKS_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p)
 LINKS_VALUES, LINKS_TALLIES = 1, 2
 LINKS_CHUNK = 1 << 22   # DST_LINKS_CHUNK: the most links of one sink call
+# dst_ld_sink(user, first_link, n_links, pos_i, pos_j, tallies)
+LD_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p)
+LD_CHUNK = 1 << 22      # DST_LD_CHUNK: the most links of one dst_ld_sink call
 STREAM_LINKS_WINDOW = 1 << 20   # DST_STREAM_LINKS_WINDOW: the default most links of one window of a links stream
 PAIR_SITES_BATCH = 1 << 20    # DST_PAIR_SITES_BATCH: the most pairs of one device batch of dst_pair_sites
 PAIR_SITES_WINDOW = 1 << 24   # DST_PAIR_SITES_WINDOW: the most entries of one device output window
@@ -194,6 +197,10 @@ _SIGS = {
                                            C.c_uint32, C.c_double, _vp, C.c_size_t, _vp, _vp, _vp, C.c_size_t]),
     "dst_site_counts": (C.c_int, [_vp, C.c_int, _vp, C.c_uint32, C.c_uint64, C.c_uint64, _vp, C.c_size_t]),
     "dst_site_stats": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_size_t]),
+    "dst_site_ld": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_size_t]),
+    "dst_site_ld_links": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_double, C.c_uint64, _vp, _vp, _u64p]),
+    "dst_ld_finalize": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp]),
+    "dst_site_major": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "dst_mst": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, C.c_size_t, _u64p, _u32p]),
     "dst_nj": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, C.c_size_t]),
     "dst_nj_matrix": (C.c_int, [_vp, _vp, C.c_uint64, _vp, _vp, C.c_size_t]),

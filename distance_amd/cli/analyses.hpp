@@ -1176,4 +1176,77 @@ void write_window_site_stats(const Run &run, const WindowList &wl, const std::ve
     out.finish();
 }
 
+// --ld: "site1, site2, group, major1, major2, called, minor1, minor2, both, r2, D, Dprime", one line per link of
+// dst_site_ld_links at R2, per group in canonical order.  A group lists the sites whose major base and whose other bases
+// together are each held by at least min_count of its records (walk_site_counts + dst_site_major), with the major base as
+// the reference allele.  The three doubles come from dst_ld_finalize, printed as --summary prints its mean.
+struct LdSink {
+    LineWriter &out;
+    const std::string &group;
+    const std::vector<uint32_t> &sites;
+    const std::vector<uint8_t> &allele;
+    std::vector<double> r2, d, dprime;
+};
+
+int ld_sink(void *user, uint64_t, uint64_t n_links, const uint32_t *pos_i, const uint32_t *pos_j, const uint32_t *tallies)
+{
+    LdSink &s = *static_cast<LdSink *>(user);
+    s.r2.resize(n_links), s.d.resize(n_links), s.dprime.resize(n_links);
+    if (dst_ld_finalize(tallies, n_links, s.r2.data(), s.d.data(), s.dprime.data()) != DST_OK)
+        return 1;
+    for (uint64_t e = 0; e < n_links; ++e) {
+        s.out.number((uint64_t)s.sites[pos_i[e]] + 1);
+        s.out.put('\t');
+        s.out.number((uint64_t)s.sites[pos_j[e]] + 1);
+        s.out.put('\t');
+        s.out.put(s.group);
+        for (const uint32_t p : {pos_i[e], pos_j[e]}) {
+            s.out.put('\t');
+            s.out.put("ATGC"[s.allele[p]]);   // (the library's class order)
+        }
+        for (int k = 0; k < 4; ++k) {
+            s.out.put('\t');
+            s.out.number(tallies[4 * e + k]);
+        }
+        for (const double v : {s.r2[e], s.d[e], s.dprime[e]}) {
+            s.out.put('\t');
+            s.out.distance(DST_RAW, v, 0);
+        }
+        s.out.end_line();
+    }
+    return 0;
+}
+
+void write_ld(const Run &run, const std::vector<GroupLabels> &labels, double min_r2, uint32_t min_count)
+{
+    const SiteGroups sg = site_groups(run, labels);
+    run.header("site1\tsite2\tgroup\tmajor1\tmajor2\tcalled\tminor1\tminor2\tboth\tr2\tD\tDprime\n");
+    std::vector<std::vector<uint32_t>> sites(sg.count);
+    std::vector<std::vector<uint8_t>> allele(sg.count);
+    std::vector<uint8_t> al;
+    std::vector<uint32_t> major, other;
+    walk_site_counts(run, sg, 0, run.rows().width, [&](uint64_t first, uint64_t n_sites, const uint32_t *counts) {
+        al.resize(n_sites), major.resize(n_sites), other.resize(n_sites);
+        for (uint32_t g = 0; g < sg.count; ++g) {
+            if (dst_site_major(counts, n_sites, sg.count, g, al.data(), major.data(), other.data()) != DST_OK)
+                die_message("ld: the major alleles of group " + sg.names[g]);
+            for (uint64_t s = 0; s < n_sites; ++s)
+                if (major[s] >= min_count && other[s] >= min_count) {
+                    sites[g].push_back((uint32_t)(first + s));
+                    allele[g].push_back(al[s]);
+                }
+        }
+    });
+    LineWriter out(run.wr);
+    for (uint32_t g = 0; g < sg.count; ++g) {
+        if (sites[g].size() < 2)
+            continue;
+        LdSink s{out, sg.names[g], sites[g], allele[g], {}, {}, {}};
+        run.gpu.check(dst_site_ld_links(run.gpu.h, 0, sites[g].data(), allele[g].data(), (uint32_t)sites[g].size(), sg.label, g, min_r2,
+                                        run.max_pairs, ld_sink, &s, nullptr),
+                      "site ld links");
+    }
+    out.finish();
+}
+
 }  // namespace

@@ -164,6 +164,16 @@ void print_help()
         "and ignored\n"
         "      --site-groups <FILE>     With --site-counts or --window-site-stats: count per group. FILE as for --groups (at "
         "most 1024 groups, numbered in order of their first record); without it there is one group, 'all', of every record\n"
+        "      --ld <R2>                Print the linkage disequilibrium between the variable sites instead of distances: one line "
+        "per pair of sites whose r^2 is at least R2 (a number from 0 to 1), 'site1, site2 (1-based), group, major1, major2 (the "
+        "sites' major bases), called (records with a single base at both sites), minor1, minor2 (of those, the records whose base "
+        "is not the major one at site1, at site2), both, r2, D, Dprime'. Tallied on the GPU. One input, one GPU; -m is accepted "
+        "and ignored; no --stream and no other output mode\n"
+        "      --ld-min-count <C>       With --ld: a site is listed when both its major base and all its other bases together "
+        "are held by at least C records (an integer >= 1) [default: 1]\n"
+        "      --ld-groups <FILE>       With --ld: per group. FILE as for --groups (at most 1024 groups, numbered in order of "
+        "their first record); each group chooses its own sites and major bases. Without it there is one group, 'all', of every "
+        "record\n"
         "      --dendrogram <linkage>   Print the rooted hierarchical-clustering tree of the records as one Newick line instead "
         "of distances: linkage average (UPGMA), weighted (WPGMA) or complete. One input, one GPU, no --stream and no other "
         "output mode\n"
@@ -187,7 +197,7 @@ enum Flag {
     F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY, F_WINDOW_GROUPS, F_WINDOW_GROUPS_WITHIN, F_WINDOW_GROUPS_BY,
     F_STREAM_SUMMARY, F_STREAM_SUMMARY_FOR, F_STREAM_HISTOGRAM, F_STREAM_BINS,
     F_STREAM_GROUPS, F_STREAM_GROUPS_BY, F_STREAM_GROUPS_WITHIN,
-    F_SITE_COUNTS, F_WINDOW_SITE_STATS, F_SITE_GROUPS, F_COUNT
+    F_SITE_COUNTS, F_WINDOW_SITE_STATS, F_SITE_GROUPS, F_LD, F_LD_MIN_COUNT, F_LD_GROUPS, F_COUNT
 };
 struct FlagDef {
     const char *shown;   // "--name <value>": its first word is the flag itself
@@ -215,12 +225,13 @@ const FlagDef kFlags[F_COUNT] = {
     {"--stream-groups <FILE>", nullptr, true}, {"--stream-groups-by <what>", nullptr, false},
     {"--stream-groups-within <T>", nullptr, true},
     {"--site-counts", nullptr, true}, {"--window-site-stats", nullptr, true}, {"--site-groups <FILE>", nullptr, true},
+    {"--ld <R2>", nullptr, true}, {"--ld-min-count <C>", nullptr, true}, {"--ld-groups <FILE>", nullptr, true},
 };
 
 // what the run prints, decided once by parse_args
 enum class Mode { Pairs, Stream, Closest, Within, Nearest, Clusters, MaxDistance, Summary, Histogram, Groups, Matrix, Tree, Mst,
                   Dendrogram, Representatives, Windows, PairList, WindowClosest, StreamSummary, StreamHistogram, StreamGroups,
-                  SiteCounts };
+                  SiteCounts, Ld };
 
 struct Args {
     bool has[F_COUNT] = {};               // the flag was given
@@ -266,6 +277,9 @@ struct Args {
     int stream_groups_by = 0;             // --stream-groups-by cell|streamed|loaded: 0, 1, 2
     double stream_groups_within = 0;      // --stream-groups-within T
     std::string site_groups;              // --site-groups FILE
+    double ld = 0;                        // --ld R2
+    size_t ld_min_count = 1;              // --ld-min-count C
+    std::string ld_groups;                // --ld-groups FILE
     std::string selftest;
     size_t n_inputs() const { return flag_inputs.size() + pos_inputs.size(); }
     // the slab size an analysis is given: the library's own choice unless --slab-pairs was passed
@@ -366,7 +380,15 @@ const std::vector<Flag> kSiteRefuses = {
     F_WINDOW_NEAREST, F_PAIRS, F_WINDOW_CLOSEST, F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY, F_WINDOW_GROUPS, F_WINDOW_GROUPS_WITHIN,
     F_WINDOW_GROUPS_BY, F_STREAM_SUMMARY, F_STREAM_SUMMARY_FOR, F_STREAM_HISTOGRAM, F_STREAM_BINS, F_STREAM_GROUPS,
     F_STREAM_GROUPS_BY, F_STREAM_GROUPS_WITHIN};
+// everything --ld cannot go with: what the site modes refuse, the window flags and the site modes themselves
+const std::vector<Flag> kLdRefuses = after(F_WINDOWS, after(F_STEP, after(F_REGIONS, after(F_SITE_COUNTS, after(F_WINDOW_SITE_STATS,
+                                           after(F_SITE_GROUPS, kSiteRefuses))))));
 const Rule kRules[] = {
+    // (before every other row: a command line with --ld or one of its two modifiers is judged here first, and no other
+    // line's outcome changes)
+    {F_LD_MIN_COUNT, Mode::Pairs, kNone, {F_LD}, "'--ld <R2>'", TWO_OK, false},
+    {F_LD_GROUPS, Mode::Pairs, kNone, {F_LD}, "'--ld <R2>'", TWO_OK, false},
+    {F_LD, Mode::Ld, kLdRefuses, kNone, nullptr, ONE_INPUT, true},
     // (before every other row: a command line with --site-counts, --window-site-stats or --site-groups is judged here first,
     // and no other line's outcome changes.  --window-site-stats leaves the mode to --windows / --regions.)
     {F_SITE_GROUPS, Mode::Pairs, kNone, {F_SITE_COUNTS, F_WINDOW_SITE_STATS}, "'--site-counts' or '--window-site-stats'", TWO_OK,
@@ -558,7 +580,8 @@ Args parse_args(int argc, char **argv)
             while (a.flag_inputs.size() < 2 && k + 1 < argc && (argv[k + 1][0] != '-' || !std::strcmp(argv[k + 1], "-")))
                 a.flag_inputs.push_back(argv[++k]);
         } else if (text(F_STREAM, a.stream) || text(F_MEASURE, a.measure) || text(F_OUTPUT, a.output) ||
-                   text(F_GROUPS, a.groups) || text(F_WINDOW_GROUPS, a.window_groups) || text(F_STREAM_GROUPS, a.stream_groups) || text(F_SITE_GROUPS, a.site_groups) || text(F_REGIONS, a.regions) || text(F_PAIRS, a.pairs) || count(F_WINDOWS, a.windows, 1, SIZE_MAX) ||
+                   text(F_GROUPS, a.groups) || text(F_WINDOW_GROUPS, a.window_groups) || text(F_STREAM_GROUPS, a.stream_groups) || text(F_SITE_GROUPS, a.site_groups) || text(F_LD_GROUPS, a.ld_groups) ||
+                   count(F_LD_MIN_COUNT, a.ld_min_count, 1, 0xFFFFFFFFull) || text(F_REGIONS, a.regions) || text(F_PAIRS, a.pairs) || count(F_WINDOWS, a.windows, 1, SIZE_MAX) ||
                    count(F_STEP, a.step, 1, SIZE_MAX) || count(F_THREADS, a.threads, 0, SIZE_MAX) ||
                    count(F_BATCHSIZE, a.batchsize, 0, SIZE_MAX) || count(F_SEED, a.seed, 0, SIZE_MAX) ||
                    count(F_NEAREST, a.nearest, 1, 256) || count(F_CLOSEST, a.closest, 1, 256) ||
@@ -571,6 +594,10 @@ Args parse_args(int argc, char **argv)
                    threshold(F_STREAM_GROUPS_WITHIN, a.stream_groups_within) ||
                    count(F_STREAM_BINS, a.stream_bins, 1, DST_SUMMARY_MAX_BINS)) {
             // a word, a count in a range or a threshold: stored
+        } else if (opt(F_LD)) {
+            a.ld = parse_number(v, shown(F_LD));
+            if (!(a.ld >= 0 && a.ld <= 1))
+                die_value(v, shown(F_LD), ": r^2 is a number from 0 to 1");
         } else if (opt(F_GPUS)) {
             a.gpus = (int)parse_usize(v, shown(F_GPUS));
         } else if (opt(F_DEVICES)) {

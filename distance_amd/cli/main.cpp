@@ -161,6 +161,8 @@ int main(int argc, char **argv)
         group_file = read_group_file(a.stream_groups, "--stream-groups");
     else if (a.has[F_SITE_GROUPS])
         group_file = read_group_file(a.site_groups, "--site-groups");
+    else if (a.has[F_LD_GROUPS])
+        group_file = read_group_file(a.ld_groups, "--ld-groups");
     // --pairs: likewise
     PairFile pair_file;
     if (a.mode == Mode::PairList)
@@ -200,7 +202,7 @@ int main(int argc, char **argv)
         group_labels = label_inputs(group_file, loaded);
     else if (a.has[F_WINDOW_GROUPS])
         group_labels = label_inputs(group_file, loaded, DST_WINDOW_GROUPS_MAX);
-    else if (a.has[F_SITE_GROUPS])
+    else if (a.has[F_SITE_GROUPS] || a.has[F_LD_GROUPS])
         group_labels = label_inputs(group_file, loaded);
     // --stream-groups: the loaded records' labels (cell, streamed), and the ids of the file that the loaded side carries
     StreamGroups stream_groups;
@@ -273,6 +275,7 @@ int main(int argc, char **argv)
     case Mode::Histogram: write_histogram(run, a.histogram, (uint32_t)a.bins); break;
     case Mode::Nearest: write_nearest(run, (uint32_t)a.nearest); break;
     case Mode::SiteCounts: write_site_counts(run, group_labels); break;
+    case Mode::Ld: write_ld(run, group_labels, a.ld, (uint32_t)a.ld_min_count); break;
     case Mode::Windows:
         if (a.has[F_WINDOW_SITE_STATS])
             write_window_site_stats(run, windows, group_labels);

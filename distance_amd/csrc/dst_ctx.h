@@ -127,6 +127,10 @@ struct dst_ctx {
     // dst_site_counts: the counts, the record list and the strips on the device; the list's and strips' page-locked staging
     Grown<> site_work;
     Grown<char, true> site_host;
+    // dst_site_ld / dst_site_ld_links: the transposed vectors, the list's tables, one slab of tallies and the links' counts,
+    // offsets and one window of outputs on the device; the tables' staging and that window again in page-locked memory
+    Grown<> ld_work;
+    Grown<char, true> ld_host;
     Grown<> summary_work;   // dst_summary: the per-record counters and accumulators, the histogram and the totals
     // dst_group_summary: the labels, the cells and the per-record table; the labels' page-locked staging
     Grown<> group_work;

@@ -622,6 +622,51 @@ int dst_site_stats(const uint32_t *counts, uint64_t site_begin, uint64_t site_en
     return DST_OK;
 }
 
+// r^2, D and D' of dst_site_ld's tallies (include/distance_hip.h fixes every operation and its order; dst_site_ld.hip's
+// link test is the r2 lines of this, on the device)
+int dst_ld_finalize(const uint32_t *tallies, uint64_t n_pairs, double *r2, double *d, double *dprime)
+{
+    if (!tallies && n_pairs)
+        return DST_ERR_ARG;
+    const double nan = std::nan("");   // (the quiet NaN 0x7FF8000000000000)
+    for (uint64_t e = 0; e < n_pairs; ++e) {
+        const int64_t m = tallies[4 * e], a = tallies[4 * e + 1], b = tallies[4 * e + 2], c = tallies[4 * e + 3];
+        const int64_t num = m * c - a * b;
+        const int64_t A = a * (m - a), B = b * (m - b);
+        const bool defined = A != 0 && B != 0;
+        if (d)
+            d[e] = m ? (double)num / (double)(m * m) : nan;
+        if (r2)
+            r2[e] = defined ? ((double)num * (double)num) / ((double)A * (double)B) : nan;
+        if (dprime) {
+            const int64_t x = num >= 0 ? std::min(a * (m - b), (m - a) * b) : std::min(a * b, (m - a) * (m - b));
+            dprime[e] = defined ? (double)num / (double)x : nan;
+        }
+    }
+    return DST_OK;
+}
+
+// the major allele of every site from dst_site_counts' entries of group g
+int dst_site_major(const uint32_t *counts, uint64_t n_sites, uint32_t n_groups, uint32_t g, uint8_t *allele, uint32_t *major_count,
+                   uint32_t *other_count)
+{
+    if (g >= n_groups || (n_sites && (!counts || !allele)))
+        return DST_ERR_ARG;
+    for (uint64_t s = 0; s < n_sites; ++s) {
+        const uint32_t *c = counts + (s * n_groups + g) * DST_SITE_CLASSES;
+        uint32_t best = 0;
+        for (uint32_t k = 1; k < 4; ++k)
+            if (c[k] > c[best])
+                best = k;
+        allele[s] = (uint8_t)best;
+        if (major_count)
+            major_count[s] = c[best];
+        if (other_count)
+            other_count[s] = (uint32_t)((uint64_t)c[0] + c[1] + c[2] + c[3] - c[best]);
+    }
+    return DST_OK;
+}
+
 int dst_shared_range(uint64_t n, int rank, int world, uint64_t *begin, uint64_t *end)
 {
     if (world < 1 || rank < 0 || rank >= world || !begin || !end)

@@ -485,6 +485,9 @@ hipError_t launch_links_count(int measure, bool tally, bool square, const void *
 hipError_t launch_links_write(int measure, bool tally, bool square, const void *slab, uint64_t out_base, uint64_t n_cols,
                               uint64_t rb, uint64_t re, uint64_t t_bits, const uint32_t *q_counts, const uint32_t *t_counts,
                               const LinksBuffers &b, uint64_t lo, uint64_t hi, bool values, bool tallies, hipStream_t stream);
+// the scan alone (dst_site_ld.hip counts its own blocks): offsets[b] = counts[0] + .. + counts[b - 1] for b <= blocks, *grand
+// += offsets[blocks]
+hipError_t launch_links_scan(const uint32_t *counts, uint64_t blocks, uint64_t *offsets, uint64_t *grand, hipStream_t stream);
 // a links stream's batch (dst_stream.cpp): hdr[0] = *total (NULL: 0), hdr[1] = *bad, side by side for the one copy back
 hipError_t launch_links_stream_header(const uint64_t *total, const unsigned long long *bad, uint64_t *hdr, hipStream_t stream);
 

@@ -238,6 +238,12 @@ hipError_t launch_links_stream_header(const uint64_t *total, const unsigned long
     return hipGetLastError();
 }
 
+hipError_t launch_links_scan(const uint32_t *counts, uint64_t blocks, uint64_t *offsets, uint64_t *grand, hipStream_t stream)
+{
+    hipLaunchKernelGGL(links_scan_kernel, dim3(1), dim3(kScanThreads), 0, stream, counts, blocks, offsets, grand);
+    return hipGetLastError();
+}
+
 uint64_t links_blocks(bool square, uint64_t n_cols, uint64_t rb, uint64_t re)
 {
     if (re <= rb)

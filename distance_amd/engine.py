@@ -11,7 +11,7 @@ import ctypes as C
 
 import numpy as np
 
-from ._lib import (ALLGATHER_FN, GROUP_NONE, LINKS_CHUNK, LINKS_SINK, LINKS_TALLIES, LINKS_VALUES, SLAB_SINK,
+from ._lib import (ALLGATHER_FN, GROUP_NONE, LD_SINK, LINKS_CHUNK, LINKS_SINK, LINKS_TALLIES, LINKS_VALUES, SLAB_SINK,
                    STREAM_GROUPS_LOADED, STREAM_GROUPS_STREAMED, STREAM_SUMMARY_LOADED, STREAM_SUMMARY_STREAMED, DistanceError,
                    GroupCell, LaunchInfo, PairsInfo, SITE_CLASSES, SiteWindow, SummaryTotals, load)
 
@@ -97,6 +97,37 @@ def site_stats(counts, windows, group_sizes, site_begin: int = 0) -> dict:
     rec = np.frombuffer(out, dtype=np.dtype([("records", "<u8"), ("sites", "<u8"), ("called", "<u8"), ("segregating", "<u8"),
                                              ("theta_sum", "<f8"), ("pi_sum", "<f8")]))[:nw * G].reshape(nw, G)
     return {name: rec[name].copy() for name in rec.dtype.names}
+
+
+def site_major(counts, g: int = 0):
+    """(allele uint8[sites], major uint32[sites], other uint32[sites]) of group `g` of Engine.site_counts' (sites, G, 5)
+    entries (dst_site_major, pure host code): per site the class (0 A, 1 T, 2 G, 3 C) with the largest of the four base
+    counts, ties to the smallest class, that count, and the sum of the other three."""
+    c = np.ascontiguousarray(counts, np.uint32)
+    if c.ndim != 3 or c.shape[2] != SITE_CLASSES or c.shape[1] == 0:
+        raise ValueError(f"counts must be a (sites, groups, {SITE_CLASSES}) array")
+    sites, G = int(c.shape[0]), int(c.shape[1])
+    allele, major, other = np.zeros(max(sites, 1), np.uint8), np.zeros(max(sites, 1), np.uint32), np.zeros(max(sites, 1), np.uint32)
+    anchor = c if c.size else np.zeros(1, np.uint32)
+    rc = load().dst_site_major(anchor.ctypes.data, sites, G, int(g), allele.ctypes.data, major.ctypes.data, other.ctypes.data)
+    if rc:
+        raise DistanceError(rc, "dst_site_major: g is not a group of the counts")
+    return allele[:sites], major[:sites], other[:sites]
+
+
+def ld_finalize(tallies) -> dict:
+    """{"r2", "d", "dprime"}: float64 arrays, one entry per row {m, a, b, c} of `tallies` (dst_ld_finalize, pure host code,
+    every operation fixed by the header); NaN where the statistic is not defined."""
+    t = np.ascontiguousarray(tallies, np.uint32)
+    if t.ndim != 2 or t.shape[1] != 4:
+        raise ValueError("tallies must be an (n_pairs, 4) array")
+    n = int(t.shape[0])
+    out = {k: np.zeros(max(n, 1), np.float64) for k in ("r2", "d", "dprime")}
+    anchor = t if n else np.zeros(4, np.uint32)
+    rc = load().dst_ld_finalize(anchor.ctypes.data, n, out["r2"].ctypes.data, out["d"].ctypes.data, out["dprime"].ctypes.data)
+    if rc:
+        raise DistanceError(rc, "dst_ld_finalize")
+    return {k: v[:n] for k, v in out.items()}
 
 
 def _window_arrays(windows):
@@ -751,6 +782,88 @@ class Engine:
         self._check(self._lib.dst_site_counts(self._h, slot, None if labels is None else labels.ctypes.data, G, begin, end,
                                               anchor.ctypes.data, out.size))
         return out
+
+    def _ld_inputs(self, sites, alleles, slot, groups, which):
+        """the arrays of a site_ld call: (sites uint32, alleles uint8, labels uint32 or None); alleles None: the major
+        allele of every listed site among the participating records (site_counts over the listed range + dst_site_major)"""
+        n, _ = self.set_info(slot)
+        s = np.ascontiguousarray(sites, np.uint32).ravel()
+        labels = None
+        if groups is not None:
+            g = np.asarray(groups)
+            if g.ndim != 1 or len(g) != n or not np.issubdtype(g.dtype, np.integer):
+                raise ValueError(f"groups must be a 1-D integer array with one label per record ({n})")
+            labels = _group_labels_u32(g, "groups")
+            if len(labels) == 0:
+                labels = np.zeros(1, np.uint32)   # (never a NULL array: NULL means every record)
+        if alleles is None:
+            a = np.zeros(len(s), np.uint8)
+            if len(s):
+                lo, hi = int(s.min()), int(s.max()) + 1
+                member = None if labels is None else np.where(labels[:n] == np.uint32(which), 0, -1)
+                counts = self.site_counts(slot, member, 1, lo, hi)
+                a = site_major(counts, 0)[0][s.astype(np.int64) - lo]
+        else:
+            a = np.ascontiguousarray(alleles, np.uint8).ravel()
+            if len(a) != len(s):
+                raise ValueError("alleles must hold one allele per listed site")
+        return s, np.ascontiguousarray(a, np.uint8), labels
+
+    def site_ld(self, sites, alleles=None, slot: int = 0, groups=None, which: int = 0, row_begin: int = 0, row_end: int | None = None):
+        """(tallies uint32[P, 4], alleles uint8[S]): {m, a, b, c} of the pairs of listed positions p < q with row_begin <= p
+        < row_end, in canonical order (dst_site_ld).  `sites`: strictly ascending 0-based sites; `alleles`: the reference
+        allele of each (0 A, 1 T, 2 G, 3 C), None: the major allele among the participating records.  `groups`: one integer
+        label per record (-1: none); the records labelled `which` take part; None: every record."""
+        s, a, labels = self._ld_inputs(sites, alleles, slot, groups, which)
+        S = len(s)
+        if row_end is None:
+            row_end = S
+        pairs = 0
+        if 0 <= row_begin <= row_end <= S and S >= 2:
+            pairs = square_row_start(S, min(row_end, S - 1)) - square_row_start(S, min(row_begin, S - 1))
+        out = np.zeros((pairs, 4), np.uint32)
+        anchor = out if pairs else np.zeros(4, np.uint32)
+        sa, aa = (s, a) if S else (np.zeros(1, np.uint32), np.zeros(1, np.uint8))
+        self._check(self._lib.dst_site_ld(self._h, slot, sa.ctypes.data, aa.ctypes.data, S, None if labels is None else labels.ctypes.data,
+                                          which, row_begin, row_end, anchor.ctypes.data, pairs))
+        return out, a
+
+    def site_ld_links(self, sites, min_r2: float, alleles=None, slot: int = 0, groups=None, which: int = 0, max_pairs: int = 0,
+                      count_only: bool = False):
+        """The pairs of listed positions whose r2 is defined and >= min_r2 (dst_site_ld_links), in canonical order:
+        (pos_i uint32[L], pos_j uint32[L], tallies uint32[L, 4], alleles uint8[S]); count_only: the int L, nothing copied.
+        The arguments are site_ld's; last_ld_calls keeps the n_links of every sink call, last_ld_first its first_link.
+        max_pairs: the most site pairs of one row slab (0: the default); the result does not depend on it."""
+        s, a, labels = self._ld_inputs(sites, alleles, slot, groups, which)
+        S = len(s)
+        sa, aa = (s, a) if S else (np.zeros(1, np.uint32), np.zeros(1, np.uint8))
+        lp = None if labels is None else labels.ctypes.data
+        total = C.c_uint64()
+        self.last_ld_calls, self.last_ld_first = [], []
+        if count_only:
+            self._check(self._lib.dst_site_ld_links(self._h, slot, sa.ctypes.data, aa.ctypes.data, S, lp, which, float(min_r2),
+                                                    int(max_pairs), None, None, C.byref(total)))
+            return int(total.value)
+        parts = ([], [], [])
+
+        def _cb(_user, first, count, pos_i, pos_j, tal):
+            count = int(count)
+            self.last_ld_calls.append(count)
+            self.last_ld_first.append(int(first))
+            parts[0].append(np.ctypeslib.as_array(C.cast(pos_i, C.POINTER(C.c_uint32)), shape=(count,)).copy())
+            parts[1].append(np.ctypeslib.as_array(C.cast(pos_j, C.POINTER(C.c_uint32)), shape=(count,)).copy())
+            parts[2].append(np.ctypeslib.as_array(C.cast(tal, C.POINTER(C.c_uint32)), shape=(count, 4)).copy())
+            return 0
+
+        cb = LD_SINK(_cb)
+        self._check(self._lib.dst_site_ld_links(self._h, slot, sa.ctypes.data, aa.ctypes.data, S, lp, which, float(min_r2),
+                                                int(max_pairs), cb, None, C.byref(total)))
+        assert int(total.value) == sum(self.last_ld_calls)
+
+        def cat(p, shape):
+            return np.concatenate(p) if p else np.zeros(shape, np.uint32)
+
+        return cat(parts[0], 0), cat(parts[1], 0), cat(parts[2], (0, 4)), a
 
     def nearest_windows(self, measure, windows, k: int, square: bool = True, row_slot: int = 0, col_slot: int = 1,
                         row_begin: int = 0, row_end: int | None = None, tallies: bool = False, max_entries: int = 0):

@@ -1147,6 +1147,67 @@ typedef struct {
 int dst_site_stats(const uint32_t *counts, uint64_t site_begin, uint64_t site_end, uint32_t n_groups,
                    const uint64_t *win_begin, const uint64_t *win_end, uint32_t n_windows,
                    const uint64_t *group_size, dst_site_window *out, size_t cap);
+/* ---- linkage disequilibrium between sites --------------------------------------------------------- */
+/* Which mutations travel together: for a list of sites, four exact integers per pair of sites, from which r^2, D and D' are
+ * fixed to the bit (PLINK's --r2, scikit-allel's rogers_huff_r on haploid calls).  The all-pairs job with the roles of
+ * sites and records swapped: AND and popcount over bit vectors that run along the records.
+ *   sites    sites[0..n_sites): 0-based sites of the set in `slot`, strictly ascending.  A site's place in the list is its
+ *            POSITION p; pairs are pairs of positions p < q, numbered in canonical order (row-major, as dst_run_square
+ *            numbers record pairs: dst_square_row_start(n_sites, p) + q - p - 1).
+ *   allele   allele[p] in {0, 1, 2, 3}: the reference allele of position p in dst_site_counts' order A, T, G, C.
+ *   records  group == NULL: every record takes part, and `which` must be 0.  Else group has one label per record and the
+ *            records with group[x] == which take part.
+ *   sets     for position p (site s) and a participating record x: C_p[x] = 1 iff x's code at s is exactly one base (the
+ *            code's high nibble is one-hot: dst_site_counts' classes 0..3); M_p[x] = 1 iff C_p[x] and that base is not
+ *            allele[p].  Ambiguity codes, N, - and ? are never called.
+ *   tallies  per pair p < q four uint32: m = |C_p & C_q|, a = |M_p & C_q|, b = |C_p & M_q|, c = |M_p & M_q|.  Only the
+ *            records with a single-base call at BOTH sites count for a pair (pairwise deletion, as in the distance measures).
+ * dst_site_ld, the full form: for the positions row_begin <= p < row_end and every q > p, in canonical order, {m, a, b, c}
+ * into `tallies` (host memory, 16 bytes per pair); cap_pairs: its room in pairs.
+ * dst_site_ld_links: the pairs whose r^2 (dst_ld_finalize below) is not NaN and >= min_r2, in canonical order, nothing
+ * reordered, handed to `sink` in chunks of at most DST_LD_CHUNK links: sink(user, first_link, n_links, pos_i, pos_j,
+ * tallies), tallies 16 bytes per link.  dst_links' rules: the sink runs on the calling thread, its arrays are page-locked
+ * buffers of the library's, valid during the call; a non-zero return stops the run with "stopped by sink" (DST_ERR_STATE);
+ * sink == NULL counts only; *n_links (may be NULL) is the number of links delivered or counted.  max_pairs: the most site
+ * pairs of one row slab (0: 2^24; at least one row per slab); the result does not depend on it.  min_r2: any double but
+ * NaN; min_r2 <= 0 delivers every pair with a defined r^2.  The device decides r^2 >= min_r2 with dst_ld_finalize's
+ * operations in their order, so a link is exactly a pair whose dst_ld_finalize r^2 passes.
+ * Errors, in this order: DST_ERR_ARG for a NULL ctx, sites, allele or tallies, a bad slot, or group == NULL with which != 0;
+ * DST_ERR_STATE for a set not uploaded or one from dst_upload_shared (the window calls' refusal); DST_ERR_ARG for a site
+ * >= len or a list that is not strictly ascending (the message names the first such position), an allele above 3,
+ * row_begin > row_end or row_end > n_sites, a set of 2^31 records or more, a NaN min_r2; DST_ERR_CAPACITY when cap_pairs is
+ * below the row range's pairs, nothing written; DST_ERR_NOMEM with the byte count.  n_sites < 2, an empty row range or no
+ * participating record: DST_OK without a launch (the full form's tallies are zero).  Synchronous on the context's stream.
+ * Slots, the path choice, dst_last_path, dst_last_launch and later results are untouched; a set with deferred planes gets
+ * them first.  Single GPU, loaded sets only. */
+#define DST_LD_CHUNK (1u << 22) /* the most links of one dst_ld_sink call */
+typedef int (*dst_ld_sink)(void *user, uint64_t first_link, uint64_t n_links, const uint32_t *pos_i, const uint32_t *pos_j,
+                           const uint32_t *tallies);
+int dst_site_ld(dst_ctx *ctx, int slot, const uint32_t *sites, const uint8_t *allele, uint32_t n_sites,
+                const uint32_t *group, uint32_t which, uint32_t row_begin, uint32_t row_end,
+                uint32_t *tallies, size_t cap_pairs);
+int dst_site_ld_links(dst_ctx *ctx, int slot, const uint32_t *sites, const uint8_t *allele, uint32_t n_sites,
+                      const uint32_t *group, uint32_t which, double min_r2, uint64_t max_pairs,
+                      dst_ld_sink sink, void *user, uint64_t *n_links);
+/* Pure host code, compiled without fused multiply-add: r^2, D and D' of n_pairs tallies {m, a, b, c} as the two calls above
+ * produce them (c <= a, b <= m < 2^31).  Any output pointer may be NULL.  Per pair, all integer arithmetic exact in 64 bits
+ * (which is why the calls refuse sets of 2^31 records or more):
+ *   num    = (int64)m c - (int64)a b          A = a (m - a)          B = b (m - b)
+ *   D      = (double)num / (double)(m m), NaN when m = 0
+ *   r2     = ((double)num (double)num) / ((double)A (double)B), NaN when A = 0 or B = 0 (a site that is monomorphic among
+ *            the pair's called records)
+ *   Dprime = (double)num / (double)X, X = min(a (m - b), (m - a) b) when num >= 0 and X = min(a b, (m - a) (m - b)) when
+ *            num < 0; NaN when A = 0 or B = 0 (else X is never 0)
+ * each conversion one rounding, each product or quotient one rounding, in the order written.  The integer conversions are
+ * exact below 94,906,266 records (m^2 < 2^53); beyond that each is the one correctly rounded conversion, and the rule is not
+ * tested there.  DST_ERR_ARG for NULL tallies with n_pairs > 0. */
+int dst_ld_finalize(const uint32_t *tallies, uint64_t n_pairs, double *r2, double *d, double *dprime);
+/* Pure host code: from dst_site_counts' entries (n_sites sites, n_groups groups) of group g, per site: allele = the class
+ * with the largest of the four base counts A, T, G, C (ties: the smallest class index), major_count = that count,
+ * other_count = the sum of the other three (m - major_count).  major_count and other_count may be NULL.  DST_ERR_ARG for a
+ * NULL counts or allele with n_sites > 0, or g >= n_groups. */
+int dst_site_major(const uint32_t *counts, uint64_t n_sites, uint32_t n_groups, uint32_t g, uint8_t *allele,
+                   uint32_t *major_count, uint32_t *other_count);
 /* ---- minimum spanning tree --------------------------------------------------------------------- */
 /* The single-linkage picture for every threshold at once: the minimum spanning tree (forest) of one set (slot 0, n
  * records), as GrapeTree- and PHYLOViZ-style viewers draw it, computed next to the values on the GPU by Boruvka rounds
