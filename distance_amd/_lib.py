@@ -26,6 +26,9 @@ LINKS_CHUNK = 1 << 22   # DST_LINKS_CHUNK: the most links of one sink call
 # dst_ld_sink(user, first_link, n_links, pos_i, pos_j, tallies)
 LD_SINK = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_uint64, C.c_uint64, C.c_void_p, C.c_void_p, C.c_void_p)
 LD_CHUNK = 1 << 22      # DST_LD_CHUNK: the most links of one dst_ld_sink call
+LD_SCALE_BITS = 30      # DST_LD_SCALE_BITS: a decay bin sums r2 as rint(r2 * 2^30)
+LD_DECAY_MAX_BINS = 4096    # DST_LD_DECAY_MAX_BINS
+LD_DECAY_LOCAL_BINS = 512   # DST_LD_DECAY_LOCAL_BINS: a tile spanning at most this many bins accumulates on chip
 STREAM_LINKS_WINDOW = 1 << 20   # DST_STREAM_LINKS_WINDOW: the default most links of one window of a links stream
 PAIR_SITES_BATCH = 1 << 20    # DST_PAIR_SITES_BATCH: the most pairs of one device batch of dst_pair_sites
 PAIR_SITES_WINDOW = 1 << 24   # DST_PAIR_SITES_WINDOW: the most entries of one device output window
@@ -55,6 +58,11 @@ class LaunchInfo(C.Structure):
                 ("tile_cols", C.c_uint32), ("tiles", C.c_uint64), ("hot", C.c_int), ("run_records", C.c_int),
                 ("variant", C.c_int), ("ksplit", C.c_uint32), ("pairs", C.c_uint64), ("events_per_pair", C.c_double),
                 ("list_length", C.c_double), ("run_adds", C.c_double)]
+
+
+class LdBin(C.Structure):
+    """dst_ld_bin"""
+    _fields_ = [("pairs", C.c_uint64), ("defined", C.c_uint64), ("links", C.c_uint64), ("r2_sum", C.c_double)]
 
 
 class SummaryTotals(C.Structure):
@@ -199,6 +207,12 @@ _SIGS = {
     "dst_site_stats": (C.c_int, [_vp, C.c_uint64, C.c_uint64, C.c_uint32, _vp, _vp, C.c_uint32, _vp, _vp, C.c_size_t]),
     "dst_site_ld": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint32, C.c_uint32, _vp, C.c_size_t]),
     "dst_site_ld_links": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_double, C.c_uint64, _vp, _vp, _u64p]),
+    "dst_ld_band": (C.c_int, [_vp, C.c_uint32, C.c_uint64, _vp, _u64p, _u64p]),
+    "dst_site_ld_band": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_uint64, C.c_uint32, C.c_uint32, _vp, C.c_size_t]),
+    "dst_site_ld_links_band": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_double, C.c_uint64, C.c_uint64, _vp, _vp,
+                                         _u64p]),
+    "dst_site_ld_decay": (C.c_int, [_vp, C.c_int, _vp, _vp, C.c_uint32, _vp, C.c_uint32, C.c_double, C.c_uint64, C.c_uint32, C.c_uint64,
+                                    _vp, C.c_size_t]),
     "dst_ld_finalize": (C.c_int, [_vp, C.c_uint64, _vp, _vp, _vp]),
     "dst_site_major": (C.c_int, [_vp, C.c_uint64, C.c_uint32, C.c_uint32, _vp, _vp, _vp]),
     "dst_mst": (C.c_int, [_vp, C.c_int, C.c_uint64, _vp, _vp, _vp, _vp, C.c_size_t, _u64p, _u32p]),

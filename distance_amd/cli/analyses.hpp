@@ -1217,10 +1217,15 @@ int ld_sink(void *user, uint64_t, uint64_t n_links, const uint32_t *pos_i, const
     return 0;
 }
 
-void write_ld(const Run &run, const std::vector<GroupLabels> &labels, double min_r2, uint32_t min_count)
+// --ld-max-gap G: the same lines from dst_site_ld_links_band.  --ld-decay W --ld-bins B: "group, gap, pairs, defined, linked,
+// mean_r2", one line per group and bin of dst_site_ld_decay in group and then bin order; gap = the bin's lower edge b x W;
+// mean_r2 = r2_sum / defined, printed as --summary prints its mean (NaN without a defined pair).
+void write_ld(const Run &run, const std::vector<GroupLabels> &labels, double min_r2, uint32_t min_count, const size_t *max_gap,
+              size_t decay_width, uint32_t decay_bins)
 {
     const SiteGroups sg = site_groups(run, labels);
-    run.header("site1\tsite2\tgroup\tmajor1\tmajor2\tcalled\tminor1\tminor2\tboth\tr2\tD\tDprime\n");
+    run.header(decay_width ? "group\tgap\tpairs\tdefined\tlinked\tmean_r2\n"
+                           : "site1\tsite2\tgroup\tmajor1\tmajor2\tcalled\tminor1\tminor2\tboth\tr2\tD\tDprime\n");
     std::vector<std::vector<uint32_t>> sites(sg.count);
     std::vector<std::vector<uint8_t>> allele(sg.count);
     std::vector<uint8_t> al;
@@ -1241,10 +1246,32 @@ void write_ld(const Run &run, const std::vector<GroupLabels> &labels, double min
     for (uint32_t g = 0; g < sg.count; ++g) {
         if (sites[g].size() < 2)
             continue;
+        if (decay_width) {
+            std::vector<dst_ld_bin> bins(decay_bins);
+            run.gpu.check(dst_site_ld_decay(run.gpu.h, 0, sites[g].data(), allele[g].data(), (uint32_t)sites[g].size(), sg.label, g, min_r2,
+                                            decay_width, decay_bins, run.max_pairs, bins.data(), bins.size()),
+                          "site ld decay");
+            for (uint32_t b = 0; b < decay_bins; ++b) {
+                out.put(sg.names[g]);
+                for (const uint64_t v : {(uint64_t)b * decay_width, bins[b].pairs, bins[b].defined, bins[b].links}) {
+                    out.put('\t');
+                    out.number(v);
+                }
+                out.put('\t');
+                out.distance(DST_RAW, bins[b].defined ? bins[b].r2_sum / (double)bins[b].defined : NAN, 0);
+                out.end_line();
+            }
+            continue;
+        }
         LdSink s{out, sg.names[g], sites[g], allele[g], {}, {}, {}};
-        run.gpu.check(dst_site_ld_links(run.gpu.h, 0, sites[g].data(), allele[g].data(), (uint32_t)sites[g].size(), sg.label, g, min_r2,
-                                        run.max_pairs, ld_sink, &s, nullptr),
-                      "site ld links");
+        if (max_gap)
+            run.gpu.check(dst_site_ld_links_band(run.gpu.h, 0, sites[g].data(), allele[g].data(), (uint32_t)sites[g].size(), sg.label, g,
+                                                 min_r2, *max_gap, run.max_pairs, ld_sink, &s, nullptr),
+                          "site ld links band");
+        else
+            run.gpu.check(dst_site_ld_links(run.gpu.h, 0, sites[g].data(), allele[g].data(), (uint32_t)sites[g].size(), sg.label, g, min_r2,
+                                            run.max_pairs, ld_sink, &s, nullptr),
+                          "site ld links");
     }
     out.finish();
 }

@@ -174,6 +174,13 @@ void print_help()
         "      --ld-groups <FILE>       With --ld: per group. FILE as for --groups (at most 1024 groups, numbered in order of "
         "their first record); each group chooses its own sites and major bases. Without it there is one group, 'all', of every "
         "record\n"
+        "      --ld-max-gap <G>         With --ld: only the pairs of sites at most G sites apart (site2 - site1 <= G, an integer; "
+        "PLINK's --ld-window-kb in sites): exactly those lines of the plain --ld output, from the band of the triangle alone\n"
+        "      --ld-decay <W>           With --ld: print the LD-decay curve instead of the pairs, one line per group and bin of W "
+        "sites (an integer from 1 to 4294967295) of the distance site2 - site1, 'group, gap (the bin's lower edge), pairs, defined (pairs whose "
+        "r^2 is defined), linked (those with r^2 >= R2), mean_r2 (over the defined pairs; NaN without one)'. Pairs past the last "
+        "bin are left out. Summed on the GPU\n"
+        "      --ld-bins <B>            With --ld-decay: the number of bins (1-4096) [default: 256]\n"
         "      --dendrogram <linkage>   Print the rooted hierarchical-clustering tree of the records as one Newick line instead "
         "of distances: linkage average (UPGMA), weighted (WPGMA) or complete. One input, one GPU, no --stream and no other "
         "output mode\n"
@@ -197,7 +204,8 @@ enum Flag {
     F_WINDOW_SUMMARY, F_WINDOW_SUMMARY_BY, F_WINDOW_GROUPS, F_WINDOW_GROUPS_WITHIN, F_WINDOW_GROUPS_BY,
     F_STREAM_SUMMARY, F_STREAM_SUMMARY_FOR, F_STREAM_HISTOGRAM, F_STREAM_BINS,
     F_STREAM_GROUPS, F_STREAM_GROUPS_BY, F_STREAM_GROUPS_WITHIN,
-    F_SITE_COUNTS, F_WINDOW_SITE_STATS, F_SITE_GROUPS, F_LD, F_LD_MIN_COUNT, F_LD_GROUPS, F_COUNT
+    F_SITE_COUNTS, F_WINDOW_SITE_STATS, F_SITE_GROUPS, F_LD, F_LD_MIN_COUNT, F_LD_GROUPS, F_LD_MAX_GAP,
+    F_LD_DECAY, F_LD_BINS, F_COUNT
 };
 struct FlagDef {
     const char *shown;   // "--name <value>": its first word is the flag itself
@@ -226,6 +234,7 @@ const FlagDef kFlags[F_COUNT] = {
     {"--stream-groups-within <T>", nullptr, true},
     {"--site-counts", nullptr, true}, {"--window-site-stats", nullptr, true}, {"--site-groups <FILE>", nullptr, true},
     {"--ld <R2>", nullptr, true}, {"--ld-min-count <C>", nullptr, true}, {"--ld-groups <FILE>", nullptr, true},
+    {"--ld-max-gap <G>", nullptr, true}, {"--ld-decay <W>", nullptr, true}, {"--ld-bins <B>", nullptr, true},
 };
 
 // what the run prints, decided once by parse_args
@@ -280,6 +289,9 @@ struct Args {
     double ld = 0;                        // --ld R2
     size_t ld_min_count = 1;              // --ld-min-count C
     std::string ld_groups;                // --ld-groups FILE
+    size_t ld_max_gap = 0;                // --ld-max-gap G (has[F_LD_MAX_GAP])
+    size_t ld_decay = 0;                  // --ld-decay W (0: the pairs)
+    size_t ld_bins = 256;                 // --ld-bins B
     std::string selftest;
     size_t n_inputs() const { return flag_inputs.size() + pos_inputs.size(); }
     // the slab size an analysis is given: the library's own choice unless --slab-pairs was passed
@@ -384,6 +396,10 @@ const std::vector<Flag> kSiteRefuses = {
 const std::vector<Flag> kLdRefuses = after(F_WINDOWS, after(F_STEP, after(F_REGIONS, after(F_SITE_COUNTS, after(F_WINDOW_SITE_STATS,
                                            after(F_SITE_GROUPS, kSiteRefuses))))));
 const Rule kRules[] = {
+    // (before every other row: the band and the decay curve are modifiers of --ld; the curve has its own band, B x W - 1)
+    {F_LD_BINS, Mode::Pairs, kNone, {F_LD_DECAY}, "'--ld-decay <W>'", TWO_OK, false},
+    {F_LD_MAX_GAP, Mode::Pairs, {F_LD_DECAY}, {F_LD}, "'--ld <R2>'", TWO_OK, false},
+    {F_LD_DECAY, Mode::Pairs, kNone, {F_LD}, "'--ld <R2>'", TWO_OK, false},
     // (before every other row: a command line with --ld or one of its two modifiers is judged here first, and no other
     // line's outcome changes)
     {F_LD_MIN_COUNT, Mode::Pairs, kNone, {F_LD}, "'--ld <R2>'", TWO_OK, false},
@@ -592,7 +608,8 @@ Args parse_args(int argc, char **argv)
                    threshold(F_GROUPS_WITHIN, a.groups_within) || threshold(F_WINDOW_GROUPS_WITHIN, a.window_groups_within) ||
                    threshold(F_WINDOW_SUMMARY, a.window_summary) || threshold(F_STREAM_SUMMARY, a.stream_summary) ||
                    threshold(F_STREAM_GROUPS_WITHIN, a.stream_groups_within) ||
-                   count(F_STREAM_BINS, a.stream_bins, 1, DST_SUMMARY_MAX_BINS)) {
+                   count(F_STREAM_BINS, a.stream_bins, 1, DST_SUMMARY_MAX_BINS) || count(F_LD_MAX_GAP, a.ld_max_gap, 0, SIZE_MAX) ||
+                   count(F_LD_DECAY, a.ld_decay, 1, 0xFFFFFFFFull) || count(F_LD_BINS, a.ld_bins, 1, DST_LD_DECAY_MAX_BINS)) {
             // a word, a count in a range or a threshold: stored
         } else if (opt(F_LD)) {
             a.ld = parse_number(v, shown(F_LD));

@@ -275,7 +275,7 @@ int main(int argc, char **argv)
     case Mode::Histogram: write_histogram(run, a.histogram, (uint32_t)a.bins); break;
     case Mode::Nearest: write_nearest(run, (uint32_t)a.nearest); break;
     case Mode::SiteCounts: write_site_counts(run, group_labels); break;
-    case Mode::Ld: write_ld(run, group_labels, a.ld, (uint32_t)a.ld_min_count); break;
+    case Mode::Ld: write_ld(run, group_labels, a.ld, (uint32_t)a.ld_min_count, a.has[F_LD_MAX_GAP] ? &a.ld_max_gap : nullptr, a.ld_decay, (uint32_t)a.ld_bins); break;
     case Mode::Windows:
         if (a.has[F_WINDOW_SITE_STATS])
             write_window_site_stats(run, windows, group_labels);

@@ -13,7 +13,7 @@ import numpy as np
 
 from ._lib import (ALLGATHER_FN, GROUP_NONE, LD_SINK, LINKS_CHUNK, LINKS_SINK, LINKS_TALLIES, LINKS_VALUES, SLAB_SINK,
                    STREAM_GROUPS_LOADED, STREAM_GROUPS_STREAMED, STREAM_SUMMARY_LOADED, STREAM_SUMMARY_STREAMED, DistanceError,
-                   GroupCell, LaunchInfo, PairsInfo, SITE_CLASSES, SiteWindow, SummaryTotals, load)
+                   GroupCell, LaunchInfo, LdBin, PairsInfo, SITE_CLASSES, SiteWindow, SummaryTotals, load)
 
 MEASURES = {"n": 0, "n_high": 1, "raw": 2, "jc69": 3, "k80": 4, "tn93": 5}
 INT_MEASURES = ("n", "n_high")
@@ -128,6 +128,21 @@ def ld_finalize(tallies) -> dict:
     if rc:
         raise DistanceError(rc, "dst_ld_finalize")
     return {k: v[:n] for k, v in out.items()}
+
+
+def ld_band(sites, max_gap: int):
+    """(row_end uint32[S], pairs, tiles) of the band of `max_gap` over the strictly ascending `sites` (dst_ld_band, pure host
+    code): the band pairs of position p are p < q < row_end[p]; `pairs` their number; `tiles` the 64 x 64 position tiles
+    that hold one, which is what the band kernels launch."""
+    s = np.ascontiguousarray(sites, np.uint32).ravel()
+    S = len(s)
+    row_end = np.zeros(max(S, 1), np.uint32)
+    pairs, tiles = C.c_uint64(), C.c_uint64()
+    anchor = s if S else np.zeros(1, np.uint32)
+    rc = load().dst_ld_band(anchor.ctypes.data, S, int(max_gap), row_end.ctypes.data, C.byref(pairs), C.byref(tiles))
+    if rc:
+        raise DistanceError(rc, "dst_ld_band: the list must be strictly ascending")
+    return row_end[:S], int(pairs.value), int(tiles.value)
 
 
 def _window_arrays(windows):
@@ -828,21 +843,65 @@ class Engine:
                                           which, row_begin, row_end, anchor.ctypes.data, pairs))
         return out, a
 
+    def site_ld_band(self, sites, max_gap: int, alleles=None, slot: int = 0, groups=None, which: int = 0, row_begin: int = 0,
+                     row_end: int | None = None):
+        """(tallies uint32[P, 4], alleles uint8[S]): site_ld's {m, a, b, c} of the pairs with sites[q] - sites[p] <= max_gap
+        and row_begin <= p < row_end, in canonical order (dst_site_ld_band); ld_band(sites, max_gap) names them."""
+        s, a, labels = self._ld_inputs(sites, alleles, slot, groups, which)
+        S = len(s)
+        if row_end is None:
+            row_end = S
+        pairs = 0
+        if 0 <= row_begin <= row_end <= S and S >= 2 and (np.diff(s.astype(np.int64)) > 0).all():
+            ends = ld_band(s, max_gap)[0].astype(np.int64)
+            pairs = int((ends - np.arange(S) - 1)[row_begin:row_end].sum())
+        out = np.zeros((pairs, 4), np.uint32)
+        anchor = out if pairs else np.zeros(4, np.uint32)
+        sa, aa = (s, a) if S else (np.zeros(1, np.uint32), np.zeros(1, np.uint8))
+        self._check(self._lib.dst_site_ld_band(self._h, slot, sa.ctypes.data, aa.ctypes.data, S, None if labels is None else labels.ctypes.data,
+                                               which, int(max_gap), row_begin, row_end, anchor.ctypes.data, pairs))
+        return out, a
+
+    def site_ld_decay(self, sites, width: int, bins: int, min_r2: float = 0.0, alleles=None, slot: int = 0, groups=None, which: int = 0,
+                      max_pairs: int = 0) -> dict:
+        """The LD-decay curve (dst_site_ld_decay): {"pairs", "defined", "links" uint64[bins], "r2_sum" float64[bins], "alleles"}.
+        Bin b holds the pairs with sites[q] - sites[p] in [b width, (b + 1) width); `defined` those with an r2, `links` those
+        with r2 >= min_r2, r2_sum the exact fixed-point sum of r2 (units of 2^-LD_SCALE_BITS): the mean r2 is r2_sum / defined.
+        max_pairs: the most band pairs one launch covers (0: the default); the result does not depend on it."""
+        s, a, labels = self._ld_inputs(sites, alleles, slot, groups, which)
+        S, B = len(s), int(bins)
+        out = (LdBin * max(B, 1))()
+        sa, aa = (s, a) if S else (np.zeros(1, np.uint32), np.zeros(1, np.uint8))
+        self._check(self._lib.dst_site_ld_decay(self._h, slot, sa.ctypes.data, aa.ctypes.data, S, None if labels is None else labels.ctypes.data,
+                                                which, float(min_r2), int(width), B, int(max_pairs), C.addressof(out), max(B, 0)))
+        rows = np.frombuffer(out, np.dtype([("pairs", "<u8"), ("defined", "<u8"), ("links", "<u8"), ("r2_sum", "<f8")]))[:B]
+        return {"pairs": rows["pairs"].copy(), "defined": rows["defined"].copy(), "links": rows["links"].copy(),
+                "r2_sum": rows["r2_sum"].copy(), "alleles": a}
+
     def site_ld_links(self, sites, min_r2: float, alleles=None, slot: int = 0, groups=None, which: int = 0, max_pairs: int = 0,
-                      count_only: bool = False):
+                      count_only: bool = False, max_gap: int | None = None):
         """The pairs of listed positions whose r2 is defined and >= min_r2 (dst_site_ld_links), in canonical order:
         (pos_i uint32[L], pos_j uint32[L], tallies uint32[L, 4], alleles uint8[S]); count_only: the int L, nothing copied.
         The arguments are site_ld's; last_ld_calls keeps the n_links of every sink call, last_ld_first its first_link.
-        max_pairs: the most site pairs of one row slab (0: the default); the result does not depend on it."""
+        max_pairs: the most site pairs of one row slab (0: the default); the result does not depend on it.  max_gap: only
+        the links with sites[pos_j] - sites[pos_i] <= max_gap, from the band alone (dst_site_ld_links_band; max_pairs then counts
+        band pairs); None: every link."""
         s, a, labels = self._ld_inputs(sites, alleles, slot, groups, which)
         S = len(s)
         sa, aa = (s, a) if S else (np.zeros(1, np.uint32), np.zeros(1, np.uint8))
         lp = None if labels is None else labels.ctypes.data
         total = C.c_uint64()
         self.last_ld_calls, self.last_ld_first = [], []
+
+        def call(sink):
+            head = (self._h, slot, sa.ctypes.data, aa.ctypes.data, S, lp, which, float(min_r2))
+            tail = (int(max_pairs), sink, None, C.byref(total))
+            if max_gap is None:
+                return self._lib.dst_site_ld_links(*head, *tail)
+            return self._lib.dst_site_ld_links_band(*head, int(max_gap), *tail)
+
         if count_only:
-            self._check(self._lib.dst_site_ld_links(self._h, slot, sa.ctypes.data, aa.ctypes.data, S, lp, which, float(min_r2),
-                                                    int(max_pairs), None, None, C.byref(total)))
+            self._check(call(None))
             return int(total.value)
         parts = ([], [], [])
 
@@ -856,8 +915,7 @@ class Engine:
             return 0
 
         cb = LD_SINK(_cb)
-        self._check(self._lib.dst_site_ld_links(self._h, slot, sa.ctypes.data, aa.ctypes.data, S, lp, which, float(min_r2),
-                                                int(max_pairs), cb, None, C.byref(total)))
+        self._check(call(cb))
         assert int(total.value) == sum(self.last_ld_calls)
 
         def cat(p, shape):

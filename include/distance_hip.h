@@ -1189,6 +1189,65 @@ int dst_site_ld(dst_ctx *ctx, int slot, const uint32_t *sites, const uint8_t *al
 int dst_site_ld_links(dst_ctx *ctx, int slot, const uint32_t *sites, const uint8_t *allele, uint32_t n_sites,
                       const uint32_t *group, uint32_t which, double min_r2, uint64_t max_pairs,
                       dst_ld_sink sink, void *user, uint64_t *n_links);
+/* ---- banded LD and the LD-decay curve ---------------------------------------------------------------
+ * The pairs within a distance along the genome (PLINK's --ld-window-kb) and one mean r^2 per distance bin, without walking
+ * the whole triangle.  Sites, positions, alleles, records (group / which) and the tallies {m, a, b, c} are dst_site_ld's,
+ * word for word.  Definitions, fixed to the bit:
+ *   gap    of a pair of positions p < q: sites[q] - sites[p]; >= 1, the list is strictly ascending.
+ *   band   of max_gap: the pairs with gap <= max_gap.  The band pairs of row p are the contiguous positions p < q <
+ *          row_end[p]; row_end[p] >= p + 1 and row_end is non-decreasing.  The BAND ORDER is the canonical order restricted to
+ *          the band.
+ * dst_ld_band (pure host code, no context): row_end[0..n_sites) (may be NULL), *pairs = the band's pairs, *tiles = the
+ * number of 64 x 64 position tiles (tile row p / 64, tile column q / 64) that hold at least one band pair (either may be
+ * NULL).  `tiles` describes the kernels, not the result, like DST_SITE_STRIP_RECORDS: it is exactly the number of tiles the
+ * band kernels launch work for in one pass over the band.  DST_ERR_ARG for NULL sites with n_sites > 0 or a list that is
+ * not strictly ascending.
+ * dst_site_ld_band, the full form: {m, a, b, c} of every band pair with row_begin <= p < row_end, in band order, 16 bytes
+ * per pair into `tallies` (host memory); every entry is bitwise dst_site_ld's entry of that pair.  cap_pairs below the row
+ * range's band pairs: DST_ERR_CAPACITY, nothing written.
+ * dst_site_ld_links_band: dst_site_ld_links' arguments plus max_gap, the same sink contract and DST_LD_CHUNK windows.
+ * Delivers exactly those links of dst_site_ld_links(min_r2) whose gap is <= max_gap, in the same order, with the same
+ * pos_i, pos_j and tallies.  max_pairs bounds the BAND pairs of one row slab (0: 2^24; at least one row per slab) and never
+ * changes the result.  max_gap >= sites[n_sites - 1] - sites[0] gives dst_site_ld_links' answer; max_gap = 0 gives no pair:
+ * DST_OK, no launch.
+ * dst_site_ld_decay: 1 <= bin_width, 1 <= n_bins <= DST_LD_DECAY_MAX_BINS.  A pair lies in bin gap / bin_width (integer
+ * division); pairs whose bin is >= n_bins are left out: the call is banded at max_gap = n_bins x bin_width - 1.  No gap
+ * reaches 2^32 - 1 (sites are uint32), so a bin_width above 2^32 - 1 is taken as 2^32 - 1: the same bins, and the product
+ * cannot overflow.  bins[0..n_bins), cap: the room of `bins` in entries.  Per bin:
+ *   pairs     the bin's pairs: a function of the list alone, filled even when nothing is launched
+ *   defined   those whose dst_ld_finalize r^2 is not NaN
+ *   links     those of them with r^2 >= min_r2: dst_site_ld_links' rule, the same operations in the same order
+ *   r2_sum    with q = rint(r^2 x 2^DST_LD_SCALE_BITS) (round to nearest even; the product by a power of two is exact), the
+ *             exact unsigned 64-bit sum of q over the bin's defined pairs, converted once to double and scaled by
+ *             2^-DST_LD_SCALE_BITS (exact).  The mean r^2 of a bin is r2_sum / defined.
+ * r^2 <= 1 up to a few ulp, so q <= 2^30 + 4 and the sum cannot overflow while the band holds at most 2^33 pairs; a band
+ * above that is DST_ERR_ARG (from dst_ld_band's count, on the host).  Every accumulation across workgroups is an integer
+ * atomic: the result depends on no order, on no slab size and on no kernel detail.  max_pairs only bounds the band pairs
+ * whose tiles one launch covers (0: 2^24; whole tile rows, at least one).  No record takes part, n_sites < 2 or an empty
+ * band: DST_OK, no launch, `pairs` filled, the rest zero.  DST_LD_DECAY_LOCAL_BINS describes the kernel, not the result: a tile
+ * whose pairs span at most that many bins is gathered in on-chip memory and flushed once.
+ * Errors of the three device calls: dst_site_ld's, in its order and with its messages under the calls' own names ("site ld
+ * band", "site ld links band", "site ld decay"; the NULL output of the decay call is `bins`); then DST_ERR_ARG for a NaN
+ * min_r2, bin_width 0, n_bins 0 or above DST_LD_DECAY_MAX_BINS, a band above 2^33 pairs; DST_ERR_CAPACITY; DST_ERR_NOMEM with
+ * the byte count.  Slots, the path choice, dst_last_path, dst_last_launch and later results are untouched; a set with
+ * deferred planes gets them first; a set from dst_upload_shared is refused as by dst_site_ld.  Single GPU, loaded sets only. */
+#define DST_LD_SCALE_BITS 30        /* r2_sum counts in units of 2^-30 */
+#define DST_LD_DECAY_MAX_BINS 4096u /* the most bins of one dst_site_ld_decay call */
+#define DST_LD_DECAY_LOCAL_BINS 512u /* a tile spanning at most this many bins accumulates on chip */
+typedef struct {
+    uint64_t pairs, defined, links;
+    double r2_sum;
+} dst_ld_bin;
+int dst_ld_band(const uint32_t *sites, uint32_t n_sites, uint64_t max_gap, uint32_t *row_end, uint64_t *pairs, uint64_t *tiles);
+int dst_site_ld_band(dst_ctx *ctx, int slot, const uint32_t *sites, const uint8_t *allele, uint32_t n_sites,
+                     const uint32_t *group, uint32_t which, uint64_t max_gap, uint32_t row_begin, uint32_t row_end,
+                     uint32_t *tallies, size_t cap_pairs);
+int dst_site_ld_links_band(dst_ctx *ctx, int slot, const uint32_t *sites, const uint8_t *allele, uint32_t n_sites,
+                           const uint32_t *group, uint32_t which, double min_r2, uint64_t max_gap, uint64_t max_pairs,
+                           dst_ld_sink sink, void *user, uint64_t *n_links);
+int dst_site_ld_decay(dst_ctx *ctx, int slot, const uint32_t *sites, const uint8_t *allele, uint32_t n_sites,
+                      const uint32_t *group, uint32_t which, double min_r2, uint64_t bin_width, uint32_t n_bins,
+                      uint64_t max_pairs, dst_ld_bin *bins, size_t cap);
 /* Pure host code, compiled without fused multiply-add: r^2, D and D' of n_pairs tallies {m, a, b, c} as the two calls above
  * produce them (c <= a, b <= m < 2^31).  Any output pointer may be NULL.  Per pair, all integer arithmetic exact in 64 bits
  * (which is why the calls refuse sets of 2^31 records or more):
